@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — Mrays/s of the wavefront path-tracing hot path on MI355X (BASELINE.json metric).
 
-  python bench.py [--config c3] --gpus N --steps K --warmup W
+  python bench.py [--config c3] --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step` = the wall time of one
+timed step). `--dump-outputs DIR` then writes what a caller of the timed path receives after its last step (`dump_outputs`).
+`--full` adds everything else below, each piece still switchable off with its --no-* option: the `roofline` object (HIP
+events bracket every bounce launch of the timed steps), the S = 1 legs and `cpu_baseline`.
 
 A "step" is P passes of the hot path; a pass = one call of the generateFrame drop-in (reference
 CudaTracer.cu:587-647): eye rays -> up to B x [intersect + NEE + scatter + compaction] -> accumulate,
@@ -26,7 +31,7 @@ RCCL gather inside the timed region.
 
 `value` counts rays the way BASELINE.md §2 defines them: one live ray processed in one bounce,
 summed over bounces and passes (device-side counter), over the wall time of the K timed steps.
-`roofline` prices the bounce kernel two ways and names the binding one: `frac` = algorithmic bytes (152 B per
+With --full, `roofline` prices the bounce kernel two ways and names the binding one: `frac` = algorithmic bytes (152 B per
 ray-bounce: 76 B SoA state read + 76 B written, BASELINE.md §3) / HIP-event time of the kernel against 8 TB/s HBM;
 `valu.issue_frac` = wave-level VALU instructions per launch (SQ_INSTS_VALU, from the committed PMC summary
 profiles/pmc_counters.json, taken with this configuration) / (1,024 SIMDs x 2.4 GHz / 2 cycles x the launch time
@@ -42,6 +47,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "cuda-path-tracer-ss_amd"))
@@ -86,6 +93,31 @@ def moved_bytes(live, first_in=32, later_in=76, survivor_out=76, ended_out=36):
         nxt = live[b + 1] if b + 1 < len(live) else 0
         total += n * (first_in if b == 0 else later_in) + nxt * survivor_out + (n - nxt) * ended_out
     return total
+
+
+DUMP_MAX_PIXELS = 1 << 20   # 48 B a pixel (3 x f64 + 4 x f32 + f64 index): 48 MiB, inside the 64 MB a dump may take
+
+
+def dump_pixel_index(npix):
+    """The frame pixels (row-major, y * width + x) --dump-outputs writes: all of them up to DUMP_MAX_PIXELS, else that many
+    drawn without replacement by a generator seeded with SEED (the same set for every run of one frame size), in order."""
+    if npix <= DUMP_MAX_PIXELS:
+        return np.arange(npix, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(npix, DUMP_MAX_PIXELS, replace=False))
+
+
+def dump_outputs(out_dir, accumulator, pixels):
+    """What a caller of the timed path holds after its last step, whole-frame and in frame order: `accumulator` (npix x 3,
+    the uint3 sums the passes added up, float64: exact) and `pixels` (npix x 4, the RGBA bytes of the last pass's display,
+    float32: exact), at the pixels `pixel_index` names (float64). Returns the file names."""
+    idx = dump_pixel_index(len(accumulator))
+    arrays = {"accumulator": np.asarray(accumulator).view(np.uint32)[idx].astype(np.float64),
+              "pixels": np.asarray(pixels)[idx].astype(np.float32),
+              "pixel_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(n + ".npy" for n in arrays)
 
 
 def cpu_baseline(cfg, budget_s=12.0):
@@ -177,6 +209,11 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--samples-per-pass", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last step's accumulator and display pixels as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: roofline (HIP-event kernel timing), the S = 1 legs, the CPU baseline")
+    # --full only: leave one of its pieces out
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-s1-leg", action="store_true")
@@ -226,9 +263,10 @@ def main():
 
     import tiles
     scene = ptss.Scene(preset)
+    kernel_timing = args.full and not args.no_kernel_timing   # the roofline's HIP events, in the timed steps themselves
     r = ptss.Renderer(scene, W, H, max_iterations=B, seed=SEED, device=local_rank,
                       tile_rank=rank, tile_world=world, band_rows=BAND_ROWS, sync_each_frame=False,
-                      time_kernels=not args.no_kernel_timing, samples_per_pass=samples,
+                      time_kernels=kernel_timing, samples_per_pass=samples,
                       # Nothing is enqueued on this stream between two frames (the one reader of the accumulator, the gather, comes
                       # after the last frame and behind its join), so the context may run its lanes free (include/ptss.h
                       # lanesFreeRun): the library then gives a small shard of a multi-GPU frame two lanes, a wide pass one.
@@ -259,7 +297,8 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    r.bounce_kernel_time()            # reset the event accumulators
+    if kernel_timing:
+        r.bounce_kernel_time()        # reset the event accumulators
     rays0 = r.total_ray_bounces()
     barrier()
     t0 = time.perf_counter()
@@ -271,20 +310,25 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
 
-    if rank == 0 and dist is not None:   # untimed sanity: the gathered tiles tile the frame
+    frame = None                         # rank 0: the whole-frame accumulator, in frame order
+    if rank == 0 and dist is not None and (args.full or args.dump_frame or args.dump_outputs):
         sizes = [len(ptss.tile_rows(H, BAND_ROWS, k, world)) * W for k in range(world)]
         frame = tiles.untile([g[:sizes[k]].cpu().numpy() for k, g in enumerate(gather_list)], W, H, BAND_ROWS)
+        # untimed sanity: the gathered tiles tile the frame
         assert frame.shape == (W * H, 3) and int(frame.max()) <= 255 * (steps + args.warmup) * passes_per_step * samples
-        if args.dump_frame:
-            import numpy as np
-            np.save(args.dump_frame, frame)
-    if rank == 0 and dist is None and args.dump_frame:
-        import numpy as np
-        np.save(args.dump_frame, acc.cpu().numpy())
+    if rank == 0 and dist is None and (args.dump_frame or args.dump_outputs):
+        frame = acc.cpu().numpy()
+    if frame is not None and args.dump_frame:
+        np.save(args.dump_frame, frame)
+    if args.dump_outputs:                # the display pixels stay on their ranks in the timed path: one untimed gather here
+        frame_pixels = (pix.cpu().numpy() if dist is None else
+                        tiles.gather_to_rank0(pix.to(coll_dev), W, H, BAND_ROWS, dist))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, frame, frame_pixels)
     rays = r.total_ray_bounces() - rays0
     # bounce-kernel BUSY time of this rank: the union of its launches' event intervals (one lane: the sum of the launch
     # durations; lanes overlap in time, and a sum of their durations would not be a time)
-    kms, klaunches = (0.0, 0) if args.no_kernel_timing else r.bounce_kernel_time()
+    kms, klaunches = r.bounce_kernel_time() if kernel_timing else (0.0, 0)
     lanes = r.frame_lanes
     live = [int(x) for x in r.live_counts()]      # this rank's rays entering each bounce of the last pass
     moved = float(moved_bytes(live)) * (float(rays) / max(sum(live), 1))   # scaled from the last pass to the timed region
@@ -383,7 +427,7 @@ def main():
                             "`frac`/`achieved`/`peak` are the HBM figures the contract asks for, `bound` names the higher of "
                             "the HBM and VALU-issue fractions")
             out["roofline"] = roof
-        if world == 1 and not args.no_s1_leg:
+        if world == 1 and args.full and not args.no_s1_leg:
             v, ms = s1_leg(ptss, torch, scene, cfg)               # the default configuration: ordered on the caller's stream, one lane
             out["s1_mrays_per_s"] = v
             out["s1_ms_per_pass"] = ms
@@ -393,7 +437,7 @@ def main():
             v2, ms2 = s1_leg(ptss, torch, scene, cfg, shards=2, frame_lanes=1)
             out["s1_two_shards_two_streams_mrays_per_s"] = v2
             out["s1_two_shards_two_streams_ms_per_pass"] = ms2
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)
 

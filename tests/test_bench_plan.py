@@ -1,5 +1,10 @@
 """bench.py's bookkeeping that needs no GPU: K timed steps always render the configuration's spp (K x P passes x S sample lanes,
-`plan_steps`), and `roofline.moved_bytes_frac` prices a pass by the bytes the fused kernels really move (`moved_bytes`)."""
+`plan_steps`), `roofline.moved_bytes_frac` prices a pass by the bytes the fused kernels really move (`moved_bytes`), and
+--dump-outputs writes a fixed set of pixels within its size bound (`dump_pixel_index`, `dump_outputs`)."""
+import os
+
+import numpy as np
+
 import bench
 
 
@@ -36,3 +41,24 @@ def test_moved_bytes_per_ray_bounce():
     # always below SURVEY §8(d)'s 152 B per ray-bounce
     assert bench.moved_bytes(live) < 152 * sum(live)
     assert bench.moved_bytes([]) == 0
+
+
+def test_dump_outputs_are_whole_small_frames_and_a_fixed_sample_of_large_ones(tmp_path):
+    for cfg in bench.CONFIGS.values():
+        npix = cfg["width"] * cfg["height"]
+        idx = bench.dump_pixel_index(npix)
+        assert len(idx) == min(npix, bench.DUMP_MAX_PIXELS) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < npix
+        assert np.array_equal(idx, bench.dump_pixel_index(npix))   # the same pixels in every run
+    # a 3840x2160 frame: accumulator (uint3 sums, above 2^31 included) and RGBA pixels come back exact, within 64 MB
+    npix = 3840 * 2160
+    rng = np.random.default_rng(1)
+    acc = rng.integers(0, 2**32, size=(npix, 3), dtype=np.uint32).view(np.int32)
+    pix = rng.integers(0, 256, size=(npix, 4), dtype=np.uint8)
+    names = bench.dump_outputs(str(tmp_path), acc, pix)
+    assert names == ["accumulator.npy", "pixel_index.npy", "pixels.npy"]
+    assert sum(os.path.getsize(os.path.join(str(tmp_path), n)) for n in names) <= 64 * 10**6
+    idx = np.load(os.path.join(str(tmp_path), "pixel_index.npy"))
+    a, p = np.load(os.path.join(str(tmp_path), "accumulator.npy")), np.load(os.path.join(str(tmp_path), "pixels.npy"))
+    assert idx.dtype == a.dtype == np.float64 and p.dtype == np.float32
+    i = idx.astype(np.int64)
+    assert np.array_equal(a, acc.view(np.uint32)[i].astype(np.float64)) and np.array_equal(p, pix[i].astype(np.float32))

@@ -20,13 +20,14 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(world, port, tmp_path, steps=2, warmup=1, extra=(), rehearsal=("--rehearse-on-one-gpu", "--backend", "gloo")):
+def run_bench(world, port, tmp_path, steps=2, warmup=1, extra=(), rehearsal=("--rehearse-on-one-gpu", "--backend", "gloo"),
+              full=True):
     dump = os.path.join(str(tmp_path), f"frame_{world}_{port}.npy")
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup),
-           "--no-s1-leg", "--dump-frame", dump] + list(rehearsal) + list(extra)
+           "--no-s1-leg", "--dump-frame", dump] + (["--full"] if full else []) + list(rehearsal) + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:] + r.stdout[-1000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -98,11 +99,11 @@ def test_config5_runs_sharded(tmp_path):
 
 
 def test_config2_line_is_complete(tmp_path):
-    """`bench.py --config c2` as the driver would run it on one GPU (short): the contract keys, the roofline object with its
+    """`bench.py --config c2 --full` on one GPU (short): the contract keys, the roofline object with its
     HBM figures and — from the committed PMC summary of exactly this configuration — traffic and the VALU object, the S = 1
     legs and the CPU baseline with its sample description."""
     env = dict(os.environ)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -118,3 +119,30 @@ def test_config2_line_is_complete(tmp_path):
     assert 0 < roof["valu"]["issue_frac"] < 1 and 0 < roof["valu"]["lanes_active"] <= 1
     assert j["cpu_baseline"]["kind"] == "port" and j["cpu_baseline"]["cores"] >= 1 and "1280x720" in j["cpu_baseline"]["sample"]
     assert j["s1_mrays_per_s"] > 0 and j["s1_free_running_lanes_mrays_per_s"] > 0
+
+
+def test_plain_run_prints_the_headline_alone_and_dumps_what_the_caller_receives(tmp_path):
+    """Without --full the line carries the headline and no roofline, S = 1 legs or CPU baseline; --dump-outputs writes the
+    last step's accumulator (the frame --dump-frame saves) and display pixels, the same in a second run and at two ranks."""
+    dumps = []
+    for k, (world, port, rehearsal) in enumerate(((1, 29581, ()), (1, 29582, ()),
+                                                  (2, 29583, ("--rehearse-on-one-gpu", "--backend", "gloo")))):
+        out = os.path.join(str(tmp_path), f"outputs_{k}")
+        j, frame = run_bench(world, port, tmp_path, steps=2, warmup=1, extra=["--config", "c2", "--dump-outputs", out],
+                             rehearsal=rehearsal, full=False)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in j, key
+        assert j["steps"] == 2 and j["n_gpus"] == world and j["value"] > 0 and j["ms_per_step"] > 0
+        assert not [key for key in j if key == "roofline" or key == "cpu_baseline" or key.startswith("s1_")], j.keys()
+        d = {n: np.load(os.path.join(out, n + ".npy")) for n in ("accumulator", "pixels", "pixel_index")}
+        assert sorted(os.listdir(out)) == ["accumulator.npy", "pixel_index.npy", "pixels.npy"]
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 * 10**6
+        assert d["accumulator"].dtype == np.float64 and d["pixels"].dtype == np.float32
+        assert np.array_equal(d["pixel_index"], np.arange(1280 * 720))   # c2's frame fits whole
+        assert d["accumulator"].shape == (1280 * 720, 3) and d["pixels"].shape == (1280 * 720, 4)
+        assert np.array_equal(d["accumulator"], frame.astype(np.int64).astype(np.float64)) and d["accumulator"].max() > 0
+        assert np.all(d["pixels"][:, 3] == 255) and d["pixels"][:, :3].max() > 0
+        dumps.append(d)
+    for d in dumps[1:]:
+        for n in d:
+            assert np.array_equal(d[n], dumps[0][n]), n

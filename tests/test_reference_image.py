@@ -5,8 +5,11 @@ QUALITATIVE ONLY. The image comes from an older, brighter revision of the refere
 ~2000 spp, unknown seed), so it pins no number: parity stays "unpinned by the reference" (DESIGN.md §4). What it can show
 is that the oracle's frame has the reference's structure — same framing, the red wall on the left, the green one on the
 right, the light patch in the ceiling, the darkest object where the reference has it — which a wrong camera model, a
-flipped axis, a wrong scene table or a wrong row order would break. Reads /root/reference (this container only; skipped
-where it does not exist, e.g. on the GPU box)."""
+flipped axis, a wrong scene table or a wrong row order would break.
+
+The test needs only the image's 64x64-pixel block means, so that is what tests/golden/reference_image_blocks.npz stores:
+`blocks` (8 x 8 x RGB, float64, block row 0 = top of the picture) of the uncompressed 24-bit true-colour TGA (BGR, row 0 =
+bottom; saveScreenshot, CudaTracer.cu:795-813), and its `shape` (512, 512, 3)."""
 import os
 
 import numpy as np
@@ -15,17 +18,7 @@ import pytest
 import oracle
 import ptss
 
-TGA = "/root/reference/CudaTracer/image.tga"
-pytestmark = pytest.mark.skipif(not os.path.exists(TGA), reason="the reference tree is not present here")
-
-
-def read_tga(path):
-    raw = open(path, "rb").read()
-    h18 = raw[:18]
-    assert h18[2] == 2 and h18[16] == 24, "uncompressed 24-bit true-colour TGA (saveScreenshot, CudaTracer.cu:795-813)"
-    w, h = h18[12] | h18[13] << 8, h18[14] | h18[15] << 8
-    bgr = np.frombuffer(raw[18:18 + w * h * 3], dtype=np.uint8).reshape(h, w, 3)   # row 0 = bottom (GL order)
-    return bgr[:, :, ::-1].astype(np.float64)
+REF_BLOCKS = os.path.join(os.path.dirname(__file__), "golden", "reference_image_blocks.npz")
 
 
 def blocks(img, b=64):
@@ -34,8 +27,8 @@ def blocks(img, b=64):
 
 
 def test_cornell_preset_has_the_structure_of_the_reference_image():
-    ref = read_tga(TGA)
-    assert ref.shape == (512, 512, 3)
+    ref = np.load(REF_BLOCKS)
+    assert tuple(ref["shape"]) == (512, 512, 3)
     scene = ptss.Scene("cornell")
     o = oracle.Oracle(scene.desc, 512, 512, max_iterations=15, seed=0x5EED)   # CudaUtils.h:7 DIM, CudaTracer.h:39
     spp = 8
@@ -43,7 +36,7 @@ def test_cornell_preset_has_the_structure_of_the_reference_image():
         o.generate_frame()
     ours = o.accumulator().astype(np.float64).reshape(512, 512, 3) / spp        # row 0 = bottom, like the TGA
     o.close()
-    R, O = blocks(ref), blocks(ours)
+    R, O = ref["blocks"], blocks(ours)
     for B in (R, O):
         left = B[2:6, 0:2].mean(axis=(0, 1))        # the left wall: red, nothing else
         assert left[0] > 100 and left[0] > 10 * max(left[1], left[2], 1.0), left

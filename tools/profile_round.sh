@@ -4,7 +4,7 @@
 #   2. PMC passes, each its own run with --kernel-trace only (FETCH_SIZE / WRITE_SIZE cannot share a pass;
 #      MI355X_MICROARCH.md): HBM bytes, SQ instruction / wave counters, LDS + cache counters
 #   3. tools/pmc_counters.py -> profiles/pmc_counters.json["<config>_s<S>"] (bench.py reads it)
-#   4. bench.py, default flags for that config, LAST, so that its roofline carries this run's PMC figures -> bench.json
+#   4. bench.py --full, default flags for that config, LAST, so that its roofline carries this run's PMC figures -> bench.json
 # Run on the GPU box from the repo root:  tools/profile_round.sh r02 c3
 set -e
 tag=${1:-r02}; cfg=${2:-c3}; S=${3:-}
@@ -28,5 +28,5 @@ S_used=$(python3 -c "import json;print(json.load(open('$out/bench.json'))['confi
 python3 tools/pmc_summary.py $out/trace $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE $out/pmc_sq $out/pmc_mem > $out/summary.txt 2>&1
 python3 tools/pmc_counters.py $out $cfg $S_used > $out/pmc_counters.log 2>&1
 cp profiles/pmc_counters.json $out/pmc_counters.json
-python3 bench.py --config $cfg > $out/bench.json 2> $out/bench.err   # the default run of that configuration (its default S is the one profiled)
+python3 bench.py --config $cfg --full > $out/bench.json 2> $out/bench.err   # the default run of that configuration (its default S is the one profiled)
 cat $out/bench.json
