@@ -45,6 +45,8 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
         if (_e != hipSuccess) return fail(PTSS_EHIP, #expr, _e); \
     } while (0)
 
+#define RC_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)   // a step that reports a PTSS_* code
+
 struct EventPair {
     hipEvent_t a, b;
 };
@@ -73,16 +75,23 @@ struct Lane {
     bool hintPending[4] = {false, false, false, false};
 };
 
+// One packed scene (packScene) on the device, with how the frames use it.
+struct SceneImage {
+    float4* dBlob = nullptr;
+    ptss::SceneLayout layout{};
+    bool inLds = true;       // staged in LDS (true) or read through scalar loads (false)
+    bool oneLaunch = false;  // the frame is traced by ONE launch (frameKernel)
+};
+
 struct ptss_context {
     ptss_render_config cfg{};
     hipStream_t stream = nullptr;
     ptss::TileMap tile{};
-    ptss::SceneLayout layout{};
-    float4* dScene = nullptr;       // the scene image the frames use
-    float4* dSceneAlt = nullptr;    // with sphere acceleration on: the plain image, for cameras outside its range
-    ptss::SceneLayout layoutAlt{};
-    bool sceneInLdsAlt = true;
-    bool haveAccel = false, accelActive = false;
+    // images[0]: the scene image the context was made for; images[1] (sphere acceleration on, else empty): the plain image,
+    // for cameras outside the chunked image's range. The frames use images[active].
+    SceneImage images[2];
+    int active = 0;
+    const SceneImage& image() const { return images[active]; }
     std::vector<Lane> lanes;
     hipEvent_t evFork = nullptr;            // several lanes: the caller's stream has reached this frame
     int countParity = 0;                    // which of a lane's two count buffers the next frame uses
@@ -110,9 +119,7 @@ struct ptss_context {
     bool usePathTracer = true;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     float lastMs = 0.0f;
-    bool oneLaunch = false, oneLaunchAlt = false;   // the frame is traced by ONE launch (frameKernel) with the current / the alternate scene image
     int gridCap = 0;             // workgroups per shard at most = 16 resident rounds of this scene's bounce kernel (0 = uncapped)
-    bool sceneInLds = true;      // scene staged in LDS (true) or read through scalar loads (false)
     unsigned frameIndex = 0;
     // bounce-kernel timing (cfg.timeKernels): every launch is bracketed by two events on ITS stream; a finished pair becomes
     // an interval [start, end) in ms since evEpoch. ptss_bounce_kernel_time reports the UNION of the intervals: with one lane
@@ -472,6 +479,58 @@ int validateScene(const ptss_scene_desc& s) {
     return PTSS_OK;
 }
 
+// rows of the frame this context owns: bands of cfg.bandRows rows, dealt round-robin to the tileWorld ranks
+int localRows(const ptss_render_config& cfg) {
+    int rows = 0;
+    for (int y = 0; y < cfg.height; ++y)
+        if ((y / cfg.bandRows) % cfg.tileWorld == cfg.tileRank) ++rows;
+    return rows;
+}
+
+// ptss_create's failures: PTSS_ENOMEM when the device ran out of memory, PTSS_EHIP for any other HIP error
+int createCheck(hipError_t e, const char* what) { return e == hipSuccess ? PTSS_OK : fail(e == hipErrorOutOfMemory ? PTSS_ENOMEM : PTSS_EHIP, what, e); }
+#define ALLOC_TRY(expr) RC_TRY(createCheck((expr), #expr))
+template <class T>
+hipError_t mallocZeroed(T** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess ? hipMemset(*p, 0, bytes) : e;
+}
+
+// A lane's device resources (ptss_create). releaseLane frees whatever of them exists: ptss_destroy, also after a failed create.
+int allocLane(Lane& ln, const uint32_t (&shardCount0)[ptss::kShards], bool ownStream) {
+    const size_t poolBytes = (size_t)ptss::kRayPlanes * ln.regionCap * ptss::kShards * sizeof(float);
+    for (float*& pool : ln.dPool) ALLOC_TRY(hipMalloc(&pool, poolBytes));
+    for (uint32_t*& counts : ln.dCounts) ALLOC_TRY(mallocZeroed(&counts, ptss::kCountWords * sizeof(uint32_t)));
+    ALLOC_TRY(mallocZeroed(&ln.dLastCounts, ptss::kCountWords * sizeof(uint32_t)));
+    for (int s = 0; s < ptss::kShards; ++s)  // arm bounce 0 of the first frame (flushKernel arms every later one)
+        ALLOC_TRY(hipMemcpy(ln.dCounts[0] + ptss::countIndex(0, s), &shardCount0[s], sizeof(uint32_t), hipMemcpyHostToDevice));
+    ALLOC_TRY(hipMalloc(&ln.dShardCount0, sizeof(shardCount0)));
+    ALLOC_TRY(hipMemcpy(ln.dShardCount0, shardCount0, sizeof(shardCount0), hipMemcpyHostToDevice));
+    ALLOC_TRY(mallocZeroed(&ln.dDone, (ptss::kCountWords + ptss::kCountStride) * sizeof(uint32_t)));  // + the finished-frames counter
+    if (ownStream) {
+        ALLOC_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+        for (hipEvent_t& ev : ln.evDone) ALLOC_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    ALLOC_TRY(hipHostMalloc(&ln.hCounts, 4 * ptss::kCountWords * sizeof(uint32_t), hipHostMallocDefault));
+    for (hipEvent_t& ev : ln.hintEvent) ALLOC_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return PTSS_OK;
+}
+#undef ALLOC_TRY
+
+void releaseLane(Lane& ln) {
+    for (hipEvent_t ev : ln.hintEvent)
+        if (ev) (void)hipEventDestroy(ev);
+    if (ln.hCounts) (void)hipHostFree(ln.hCounts);
+    (void)hipFree(ln.dDone);
+    for (hipEvent_t ev : ln.evDone)
+        if (ev) (void)hipEventDestroy(ev);
+    if (ln.stream) (void)hipStreamDestroy(ln.stream);
+    for (float* pool : ln.dPool) (void)hipFree(pool);
+    for (uint32_t* counts : ln.dCounts) (void)hipFree(counts);
+    (void)hipFree(ln.dShardCount0);
+    (void)hipFree(ln.dLastCounts);
+}
+
 ptss::FrameBuffers frameBuffers(const ptss_context* c, int laneIdx, ptss_uchar4* pixels, int sample) {
     const Lane& ln = c->lanes[(size_t)laneIdx];
     ptss::FrameBuffers fb{};
@@ -487,7 +546,7 @@ ptss::FrameBuffers frameBuffers(const ptss_context* c, int laneIdx, ptss_uchar4*
     fb.accum = c->dAccum;
     fb.fsum = c->dFsum;
     fb.staged = c->dStaged ? c->dStaged + (c->stagedTwice ? (size_t)(c->frameIndex & 1u) * c->capacity * c->samples : 0) : nullptr;
-    fb.quantTable = reinterpret_cast<const float*>(c->dScene + c->layout.offQuant);
+    fb.quantTable = reinterpret_cast<const float*>(c->image().dBlob + c->image().layout.offQuant);
     fb.pixels = pixels;
     fb.regionCap = ln.regionCap;
     fb.numPixels = c->numPixels;
@@ -546,13 +605,163 @@ void drainKernelEvents(ptss_context* c, bool wait) {
 // Frame lanes: did a lane give up waiting for a peer since the last check (FrameBuffers::guardTimeouts)? Called by the
 // entry points that have just synchronised; one 4-byte read-back, and only in contexts with more than one lane.
 int checkLaneTimeouts(ptss_context* c) {
-    if (c->lanes.size() < 2 && !c->oneLaunch && !c->oneLaunchAlt) return PTSS_OK;   // only kernels that wait for others can time out
+    if (c->lanes.size() < 2 && !c->images[0].oneLaunch && !c->images[1].oneLaunch) return PTSS_OK;   // only kernels that wait for others can time out
     uint32_t v = 0;
     HIP_TRY(hipMemcpy(&v, c->dTotal + ptss::kMaxLanes + 8, sizeof(v), hipMemcpyDeviceToHost));
     if (v != c->timeoutsSeen) {
         c->timeoutsSeen = v;
         return fail(PTSS_ETIMEOUT, "a bounded wait on the device expired (a frame lane for a peer lane, or a workgroup of the one-launch "
                                    "frame kernel for its shard): the frame was not traced as specified");
+    }
+    return PTSS_OK;
+}
+
+// ---- the steps of a frame (ptss_generate_frame) ------------------------------------------------------------------------
+// The chunked image assumes a camera within the geometry's magnitude range (packScene): outside it the frames use the plain one.
+void selectImage(ptss_context* c) {
+    if (!c->images[1].dBlob) return;
+    const int want = cameraInRange(c->camera) ? 0 : 1;
+    if (want != c->active) {
+        c->active = want;
+        c->cameraDirty = true;
+    }
+}
+
+ptss::EyeParams eyeParams(const ptss_context* c) {   // {camera, s (CudaTracer.cu:334), aspect, invW, invH}
+    return {c->camera, -2 * ptm::tan(c->camera.fieldOfView * 0.5f), (float)c->tile.height / (float)c->tile.width, 1.0f / c->tile.width,
+            1.0f / c->tile.height};
+}
+
+// harvest the newest finished live-count readbacks (never blocks)
+void harvestHints(ptss_context* c) {
+    for (Lane& ln : c->lanes)
+        for (int q = 0; q < 4; ++q) {
+            if (!ln.hintPending[q] || hipEventQuery(ln.hintEvent[q]) != hipSuccess) continue;
+            const uint32_t* src = ln.hCounts + (size_t)q * ptss::kCountWords;
+            for (int b = 0; b <= ptss::kMaxBounces; ++b) {
+                uint32_t mx = 0;
+                for (int s = 0; s < ptss::kShards; ++s) mx = std::max(mx, src[ptss::countIndex(b, s)]);
+                ln.hint[b] = mx;
+            }
+            ln.haveHint = true;
+            ln.hintPending[q] = false;
+        }
+    (void)hipGetLastError();
+}
+
+// Several lanes: each runs on its own stream, forked from the caller's here and joined into it by flushAndJoin; their
+// launches are issued round-robin, bounce by bounce, so that the streams advance together.
+// STRICT ordering (the default): every frame forks, so the lanes start behind whatever the caller put on its stream
+// before this call — a reader of the previous frame's pixels or accumulator, a zero-fill, a newly bound buffer's writer.
+// FREE-RUNNING (cfg.lanesFreeRun, opt-in): the fork happens only when the library's own work on the caller's stream
+// requires it (the clear of a reset, the camera precomputes) — otherwise a lane's next frame depends on nothing but
+// its own previous one, and the lanes run on, frame after frame, while the caller's stream merely waits for each
+// frame's end (the join); the caller has promised not to touch the buffers in between (include/ptss.h).
+int forkLanes(ptss_context* c, bool forkNeeded) {
+    if (c->lanes.size() > 1 && (forkNeeded || c->frameIndex == 0 || !c->cfg.lanesFreeRun)) {
+        HIP_TRY(hipEventRecord(c->evFork, c->stream));
+        for (Lane& ln : c->lanes) HIP_TRY(hipStreamWaitEvent(ln.stream, c->evFork, 0));
+    }
+    // Free-running lanes with S > 1: this frame parks its samples in the buffer of its parity, which displayKernel of the frame
+    // two back (same parity, on the caller's stream) must have emptied — the only thing a free-running lane ever waits for
+    // on the caller's side, and an event that has nearly always fired by now.
+    if (c->stagedTwice && c->frameIndex >= 2)
+        for (Lane& ln : c->lanes) HIP_TRY(hipStreamWaitEvent(ln.stream, c->evDisplay[c->frameIndex & 1u], 0));
+    return PTSS_OK;
+}
+
+// cfg.timeKernels: brackets the one kernel that launch() enqueues on stream s with an event pair (drainKernelEvents)
+template <class Launch>
+int timedLaunch(ptss_context* c, hipStream_t s, Launch launch) {
+    if (!c->cfg.timeKernels) return launch();
+    EventPair ev{nullptr, nullptr};
+    if (c->evFree.empty() && c->evBusy.size() >= 4096) drainKernelEvents(c, true);
+    if (c->evFree.empty()) {
+        HIP_TRY(hipEventCreate(&ev.a));
+        HIP_TRY(hipEventCreate(&ev.b));
+    } else {
+        ev = c->evFree.back();
+        c->evFree.pop_back();
+    }
+    HIP_TRY(hipEventRecord(ev.a, s));
+    RC_TRY(launch());
+    HIP_TRY(hipEventRecord(ev.b, s));
+    c->evBusy.push_back(ev);
+    return PTSS_OK;
+}
+
+// every bounce in ONE launch (frameKernel): CudaTracer.cu:622-633 without leaving the device; its grid is the frame's tiles
+int traceOneLaunch(ptss_context* c, const ptss::FrameBuffers& fb, int numIterations, bool bounded, const ptss::EyeParams& eye) {
+    const SceneImage& im = c->image();
+    return timedLaunch(c, c->stream, [&] {
+        HIP_TRY(ptss::launchFrame(c->stream, fb, im.dBlob, im.layout, numIterations, bounded, c->lanes[0].maxBlocks, c->tile, eye));
+        return PTSS_OK;
+    });
+}
+
+// one launch per bounce and lane (CudaTracer.cu:622-633, guard evaluated on the device), the lanes round-robin inside a bounce
+int traceBounces(ptss_context* c, ptss::FrameBuffers* fbs, int numIterations, bool bounded, const ptss::EyeParams& eye) {
+    const SceneImage& im = c->image();
+    const int K = (int)c->lanes.size();
+    for (int i = 0; i < numIterations; ++i)
+        for (int k = 0; k < K; ++k) {
+            Lane& ln = c->lanes[(size_t)k];
+            const hipStream_t ls = K > 1 ? ln.stream : c->stream;
+            // grid: one tile per workgroup for the expected live count (+1.5 %), never more than the lane's share of the
+            // frame; the kernel grid-strides, so a low hint costs time, not correctness
+            int blocks = ln.maxBlocks;
+            if (i > 0 && ln.haveHint) {
+                // tiles for the fullest shard (+1.5 %), times kShards (workgroup b serves shard b % kShards)
+                const unsigned long long tilesPerShard = ((unsigned long long)ln.hint[i] * 65 / 64 + ptss::kBlock) / ptss::kBlock + 1;
+                const unsigned long long want = tilesPerShard * ptss::kShards;
+                if (want < (unsigned long long)blocks) blocks = (int)want;
+            }
+            // launches wider than 16 resident rounds stop growing (gridCap, ptss_create)
+            if (c->gridCap > 0 && c->gridCap * ptss::kShards < blocks) blocks = c->gridCap * ptss::kShards;
+            // the peers' done totals once their bounce i - 1 of this frame has ended (all of those launches precede this
+            // one in host order, so a kernel that waits for them never waits for something behind it in a shared queue)
+            if (i > 0)
+                for (int j = 0, p = 0; j < K; ++j)
+                    if (j != k) fbs[k].peerTarget[p++] = c->lanes[(size_t)j].doneTarget[i - 1];
+            RC_TRY(timedLaunch(c, ls, [&] {
+                HIP_TRY(ptss::launchBounce(ls, fbs[k], im.dBlob, im.layout, i, i == numIterations - 1, im.inLds, bounded, blocks, c->tile, eye));
+                return PTSS_OK;
+            }));
+            ln.doneTarget[i] += (uint32_t)blocks;  // every workgroup of the launch adds 1 to done[i][its shard] as it ends
+        }
+    return PTSS_OK;
+}
+
+// flushKernel of every lane (CudaTracer.cu:637), the live-count readbacks for later grids, and the join into the caller's stream
+int flushAndJoin(ptss_context* c, const ptss::FrameBuffers* fbs, int numIterations) {
+    const int K = (int)c->lanes.size();
+    for (int k = 0; k < K; ++k) {
+        Lane& ln = c->lanes[(size_t)k];
+        const hipStream_t ls = K > 1 ? ln.stream : c->stream;
+        // (flushKernel itself waits, on the device, until every peer lane has finished the previous frame: FrameBuffers::myFrameDone)
+        ptss::FlushTargets targets{};
+        for (int j = 0, p = 0; j < K; ++j)
+            if (j != k) {
+                for (int b = 0; b <= ptss::kMaxBounces; ++b) targets.target[p][b] = c->lanes[(size_t)j].doneTarget[b];
+                ++p;
+            }
+        HIP_TRY(ptss::launchFlush(ls, fbs[k], numIterations, targets));
+        // every 8th frame (and until a hint exists) copy counts[] to pinned memory for later grid sizing
+        if (!ln.haveHint || (c->frameIndex & 7u) == 0) {
+            const int q = (int)((c->frameIndex >> 3) & 3u);
+            if (!ln.hintPending[q]) {
+                HIP_TRY(hipMemcpyAsync(ln.hCounts + (size_t)q * ptss::kCountWords, ln.dLastCounts, ptss::kCountWords * sizeof(uint32_t),
+                                       hipMemcpyDeviceToHost, ls));
+                HIP_TRY(hipEventRecord(ln.hintEvent[q], ls));
+                ln.hintPending[q] = true;
+            }
+        }
+        // the join: the caller's stream is ordered behind every lane's frame (the lanes themselves run on) — ONE event, behind
+        // the last lane's flushKernel, which ends only when every other lane's has (FrameBuffers::joinsFrame); an event per lane cost 1-2 %
+        if (K > 1 && k == K - 1) {
+            HIP_TRY(hipEventRecord(ln.evDone[c->frameIndex & 1u], ls));
+            HIP_TRY(hipStreamWaitEvent(c->stream, ln.evDone[c->frameIndex & 1u], 0));
+        }
     }
     return PTSS_OK;
 }
@@ -619,9 +828,7 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         // A ray's word inside its shard's region is addressed in 32 bits (slotWord: 19 planes per block): the rays of one
         // pass — local pixels x sample lanes, rounded up to whole tiles per shard — must stay below 2^32 / 19 (~226
         // million; the whole pool may be larger than 4 GB, regions are based with 64-bit arithmetic).
-        long long rows = 0;
-        for (int y = 0; y < cfg->height; ++y)
-            if ((y / cfg->bandRows) % cfg->tileWorld == cfg->tileRank) ++rows;
+        const long long rows = localRows(*cfg);
         const unsigned long long rays = ((unsigned long long)cfg->width * rows + 255ull) / 256ull * 256ull * (unsigned long long)spp;
         if ((rays + (unsigned long long)ptss::kShards * ptss::kBlock) * ptss::kRayPlanes >= (1ull << 32))
             return fail(PTSS_EINVAL, "too many rays per pass: width x local rows x samplesPerPass must stay below ~226 million");
@@ -653,11 +860,8 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
     c->camera.zFar = -100.0f;
     c->camera.fieldOfView = ptm::kPi / 2.0f;
 
-    int localRows = 0;
-    for (int y = 0; y < cfg->height; ++y)
-        if ((y / cfg->bandRows) % cfg->tileWorld == cfg->tileRank) ++localRows;
-    c->tile = ptss::TileMap{cfg->width, cfg->height, localRows, cfg->tileRank, cfg->tileWorld, cfg->bandRows};
-    c->numPixels = (uint32_t)cfg->width * (uint32_t)localRows;
+    c->tile = ptss::TileMap{cfg->width, cfg->height, localRows(*cfg), cfg->tileRank, cfg->tileWorld, cfg->bandRows};
+    c->numPixels = (uint32_t)cfg->width * (uint32_t)c->tile.localRows;
     const uint32_t gran = ptss::kBlock > 256 ? (uint32_t)ptss::kBlock : 256u;  // pixel planes are whole tiles
     c->capacity = ((c->numPixels + gran - 1) / gran) * gran;
     if (c->capacity == 0) c->capacity = gran;
@@ -703,74 +907,38 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         }
     }
 
-    // Scenes with many spheres get the chunked image (see accelEligible / packScene); cfg.everySphereLoop keeps the plain one
+    // Scenes with many spheres get the chunked image (see accelEligible / packScene), and the plain one as images[1] for cameras
+    // outside its range; cfg.everySphereLoop keeps the plain one only
     const bool wantAccel = accelEligible(*scene) && !cfg->everySphereLoop;
-    std::vector<float4> blob, blobAlt;
-    packScene(*scene, c->layout, blob, wantAccel);
-    if (wantAccel) packScene(*scene, c->layoutAlt, blobAlt, false);
-    c->haveAccel = c->accelActive = wantAccel;
-    // Scenes whose image fits the default 64 KiB dynamic-LDS window are staged in LDS; larger ones are read in place
-    // (wave-uniform scalar loads + per-lane gathers from global memory) — same kernel, same results, no size limit.
-    const bool sceneFitsLds = ptss::bounceLdsBytes(c->layout, true) <= 64 * 1024;
-    const bool sceneFitsLdsAlt = wantAccel && ptss::bounceLdsBytes(c->layoutAlt, true) <= 64 * 1024;
+    const int numImages = wantAccel ? 2 : 1;
+    std::vector<float4> blob[2];
+    for (int i = 0; i < numImages; ++i) {
+        SceneImage& im = c->images[i];
+        packScene(*scene, im.layout, blob[i], wantAccel && i == 0);
+        // Scene access path: images that fit the default 64 KiB dynamic-LDS window are staged in LDS (north_star); larger ones
+        // are read in place (wave-uniform scalar loads + per-lane gathers from global memory) — same kernel, same results, no
+        // size limit. (On the 38-primitive "mixed" scene reading in place measured 16 % slower, profiles/README.md r01.)
+        im.inLds = ptss::bounceLdsBytes(im.layout, true) <= 64 * 1024;
+    }
 
-#define CREATE_TRY(expr)                                  \
-    do {                                                  \
-        hipError_t _e = (expr);                           \
-        if (_e != hipSuccess) {                           \
-            int _rc = fail(_e == hipErrorOutOfMemory ? PTSS_ENOMEM : PTSS_EHIP, #expr, _e); \
-            ptss_destroy(c);                              \
-            return _rc;                                   \
-        }                                                 \
-    } while (0)
+#define CREATE_TRY(expr) do { if (int _rc = createCheck((expr), #expr)) return (ptss_destroy(c), _rc); } while (0)   // frees what exists
 
-    CREATE_TRY(hipMalloc(&c->dScene, blob.size() * sizeof(float4)));
-    CREATE_TRY(hipMemcpy(c->dScene, blob.data(), blob.size() * sizeof(float4), hipMemcpyHostToDevice));
-    if (wantAccel) {
-        CREATE_TRY(hipMalloc(&c->dSceneAlt, blobAlt.size() * sizeof(float4)));
-        CREATE_TRY(hipMemcpy(c->dSceneAlt, blobAlt.data(), blobAlt.size() * sizeof(float4), hipMemcpyHostToDevice));
+    for (int i = 0; i < numImages; ++i) {
+        CREATE_TRY(hipMalloc(&c->images[i].dBlob, blob[i].size() * sizeof(float4)));
+        CREATE_TRY(hipMemcpy(c->images[i].dBlob, blob[i].data(), blob[i].size() * sizeof(float4), hipMemcpyHostToDevice));
     }
     CREATE_TRY(hipMalloc(&c->dRngHome, (size_t)ptss::kHomeWords * c->capacity * c->samples * sizeof(uint32_t)));
-    for (int k = 0; k < numLanes; ++k) {
-        Lane& ln = c->lanes[(size_t)k];
-        const size_t poolBytes = (size_t)ptss::kRayPlanes * ln.regionCap * ptss::kShards * sizeof(float);
-        CREATE_TRY(hipMalloc(&ln.dPool[0], poolBytes));
-        CREATE_TRY(hipMalloc(&ln.dPool[1], poolBytes));
-        for (int b = 0; b < 2; ++b) {
-            CREATE_TRY(hipMalloc(&ln.dCounts[b], ptss::kCountWords * sizeof(uint32_t)));
-            CREATE_TRY(hipMemset(ln.dCounts[b], 0, ptss::kCountWords * sizeof(uint32_t)));
-        }
-        CREATE_TRY(hipMalloc(&ln.dLastCounts, ptss::kCountWords * sizeof(uint32_t)));
-        CREATE_TRY(hipMemset(ln.dLastCounts, 0, ptss::kCountWords * sizeof(uint32_t)));
-        for (int s = 0; s < ptss::kShards; ++s)  // arm bounce 0 of the first frame (flushKernel arms every later one)
-            CREATE_TRY(hipMemcpy(ln.dCounts[0] + ptss::countIndex(0, s), &shardCount0[k][s], sizeof(uint32_t), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&ln.dShardCount0, sizeof(shardCount0[k])));
-        CREATE_TRY(hipMemcpy(ln.dShardCount0, shardCount0[k], sizeof(shardCount0[k]), hipMemcpyHostToDevice));
-        CREATE_TRY(hipMalloc(&ln.dDone, (ptss::kCountWords + ptss::kCountStride) * sizeof(uint32_t)));  // + the finished-frames counter
-        CREATE_TRY(hipMemset(ln.dDone, 0, (ptss::kCountWords + ptss::kCountStride) * sizeof(uint32_t)));
-        if (numLanes > 1) {
-            CREATE_TRY(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            CREATE_TRY(hipEventCreateWithFlags(&ln.evDone[0], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&ln.evDone[1], hipEventDisableTiming));
-        }
-        CREATE_TRY(hipHostMalloc(&ln.hCounts, 4 * ptss::kCountWords * sizeof(uint32_t), hipHostMallocDefault));
-        for (int q = 0; q < 4; ++q) CREATE_TRY(hipEventCreateWithFlags(&ln.hintEvent[q], hipEventDisableTiming));
-    }
+    for (int k = 0; k < numLanes; ++k)
+        if (int laneRc = allocLane(c->lanes[(size_t)k], shardCount0[k], numLanes > 1)) return (ptss_destroy(c), laneRc);
     if (numLanes > 1) CREATE_TRY(hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming));
-    CREATE_TRY(hipMalloc(&c->dTotal, kTotalWords * sizeof(unsigned long long)));
-    CREATE_TRY(hipMemset(c->dTotal, 0, kTotalWords * sizeof(unsigned long long)));
-    CREATE_TRY(hipMalloc(&c->dAccumOwned, (size_t)3 * c->capacity * sizeof(uint32_t)));
-    CREATE_TRY(hipMemset(c->dAccumOwned, 0, (size_t)3 * c->capacity * sizeof(uint32_t)));
+    CREATE_TRY(mallocZeroed(&c->dTotal, kTotalWords * sizeof(unsigned long long)));
+    CREATE_TRY(mallocZeroed(&c->dAccumOwned, (size_t)3 * c->capacity * sizeof(uint32_t)));
     c->dAccum = c->dAccumOwned;
-    if (cfg->floatAccumulator) {
-        CREATE_TRY(hipMalloc(&c->dFsum, (size_t)3 * c->capacity * c->samples * sizeof(float)));
-        CREATE_TRY(hipMemset(c->dFsum, 0, (size_t)3 * c->capacity * c->samples * sizeof(float)));
-    }
+    if (cfg->floatAccumulator) CREATE_TRY(mallocZeroed(&c->dFsum, (size_t)3 * c->capacity * c->samples * sizeof(float)));
     if (c->samples > 1) {
         c->stagedTwice = numLanes > 1 && cfg->lanesFreeRun != 0;
         const size_t words = (size_t)c->capacity * c->samples * (c->stagedTwice ? 2 : 1);
-        CREATE_TRY(hipMalloc(&c->dStaged, words * sizeof(uint32_t)));
-        CREATE_TRY(hipMemset(c->dStaged, 0, words * sizeof(uint32_t)));
+        CREATE_TRY(mallocZeroed(&c->dStaged, words * sizeof(uint32_t)));
         if (c->stagedTwice)
             for (int q = 0; q < 2; ++q) CREATE_TRY(hipEventCreateWithFlags(&c->evDisplay[q], hipEventDisableTiming));
     }
@@ -794,11 +962,6 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         CREATE_TRY(e3);
     }
 
-    // Scene access path: staged into LDS whenever the image fits (north_star); larger scenes are read in place. (On the
-    // 38-primitive "mixed" scene reading in place — wave-uniform s_load through the scalar cache — measured 16 % slower,
-    // profiles/README.md r01.)
-    c->sceneInLds = sceneFitsLds;
-    c->sceneInLdsAlt = sceneFitsLdsAlt;
     {
         // Launches wider than 16 resident rounds stop growing: a workgroup then walks several tiles and stages the scene
         // into LDS once for all of them. One round = CUs x workgroups per CU of THIS scene's bounce kernel (LDS image and
@@ -807,22 +970,26 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         // 448: -4.6 %, 896: -1.3 %, 1,280-3,584: equal, uncapped: -2 % (profiles/README.md).
         hipDeviceProp_t prop;
         CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
-        const int perCU = ptss::bounceOccupancyBlocksPerCU(c->layout, c->sceneInLds, wantAccel);
+        const SceneImage& primary = c->images[0];   // (not recomputed when the frames switch to images[1])
+        const int perCU = ptss::bounceOccupancyBlocksPerCU(primary.layout, primary.inLds, primary.layout.sphereBounded != 0);
         c->gridCap = prop.multiProcessorCount * (perCU > 0 ? perCU : 4) * 16 / ptss::kShards;
         // One launch per frame (ptss_kernels.hip frameKernel): only when every workgroup of the frame's grid is resident at once —
         // its workgroups wait for each other — i.e. bounce-0 tiles <= CUs x resident workgroups per CU of THAT kernel with this
         // scene's LDS image. The occupancy API over-reports by one workgroup per CU for kernels of more than 96 SGPRs
         // (MI355X_MICROARCH.md, "Residency and cooperative launch"): one is kept in reserve. One lane, scene staged in LDS.
-        auto qualifies = [&](const ptss::SceneLayout& lay, bool inLds) {
-            if (cfg->oneLaunchFrames <= 0 || numLanes != 1 || !inLds) return false;   // opt-in (include/ptss.h)
-            const int resident = ptss::frameOccupancyBlocksPerCU(lay, lay.sphereBounded != 0) - 1;
+        // A bounded image runs the bounded or the unbounded frame kernel, as the camera is in range or not: both must fit.
+        auto qualifies = [&](const SceneImage& im) {
+            if (cfg->oneLaunchFrames <= 0 || numLanes != 1 || !im.inLds) return false;   // opt-in (include/ptss.h)
+            int perCU = ptss::frameOccupancyBlocksPerCU(im.layout, false);
+            if (im.layout.sphereBounded) perCU = std::min(perCU, ptss::frameOccupancyBlocksPerCU(im.layout, true));
+            const int resident = perCU - 1;
             return resident >= 1 && c->lanes[0].maxBlocks <= prop.multiProcessorCount * resident;
         };
-        c->oneLaunch = qualifies(c->layout, c->sceneInLds);
-        c->oneLaunchAlt = wantAccel && qualifies(c->layoutAlt, c->sceneInLdsAlt);
+        for (int i = 0; i < numImages; ++i) c->images[i].oneLaunch = qualifies(c->images[i]);
 #ifdef PTSS_TUNING_KNOBS   // measurement builds only (tools/build_variants.py "knobs"); the shipped library reads no environment
         if (const char* e = getenv("PTSS_SCENE_PATH")) {
-            if (!strcmp(e, "scalar")) c->sceneInLds = c->sceneInLdsAlt = false;
+            if (!strcmp(e, "scalar"))
+                for (SceneImage& im : c->images) im.inLds = false;
         }
         if (const char* e = getenv("PTSS_GRID_CAP")) c->gridCap = atoi(e);
 #endif
@@ -842,29 +1009,10 @@ int ptss_destroy(ptss_context* c) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
     }
-    for (Lane& ln : c->lanes) {
-        for (int q = 0; q < 4; ++q)
-            if (ln.hintEvent[q]) (void)hipEventDestroy(ln.hintEvent[q]);
-        if (ln.hCounts) (void)hipHostFree(ln.hCounts);
-        (void)hipFree(ln.dDone);
-        if (ln.evDone[0]) (void)hipEventDestroy(ln.evDone[0]);
-        if (ln.evDone[1]) (void)hipEventDestroy(ln.evDone[1]);
-        if (ln.stream) (void)hipStreamDestroy(ln.stream);
-        (void)hipFree(ln.dPool[0]);
-        (void)hipFree(ln.dPool[1]);
-        (void)hipFree(ln.dCounts[0]);
-        (void)hipFree(ln.dCounts[1]);
-        (void)hipFree(ln.dShardCount0);
-        (void)hipFree(ln.dLastCounts);
-    }
-    if (c->evFork) (void)hipEventDestroy(c->evFork);
-    for (int q = 0; q < 2; ++q)
-        if (c->evDisplay[q]) (void)hipEventDestroy(c->evDisplay[q]);
-    if (c->evStart) (void)hipEventDestroy(c->evStart);
-    if (c->evStop) (void)hipEventDestroy(c->evStop);
-    if (c->evEpoch) (void)hipEventDestroy(c->evEpoch);
-    (void)hipFree(c->dScene);
-    (void)hipFree(c->dSceneAlt);
+    for (Lane& ln : c->lanes) releaseLane(ln);
+    for (hipEvent_t ev : {c->evFork, c->evDisplay[0], c->evDisplay[1], c->evStart, c->evStop, c->evEpoch})
+        if (ev) (void)hipEventDestroy(ev);
+    for (SceneImage& im : c->images) (void)hipFree(im.dBlob);
     (void)hipFree(c->dRngHome);
     (void)hipFree(c->dTotal);
     (void)hipFree(c->dAccumOwned);
@@ -886,17 +1034,7 @@ int ptss_generate_frame(ptss_context* c, ptss_uchar4* pixels, int ticks) {
         return PTSS_OK;
     }
 
-    if (c->haveAccel) {  // the chunked image assumes a camera within the geometry's magnitude range (packScene)
-        const bool want = cameraInRange(c->camera);
-        if (want != c->accelActive) {
-            std::swap(c->dScene, c->dSceneAlt);
-            std::swap(c->layout, c->layoutAlt);
-            std::swap(c->sceneInLds, c->sceneInLdsAlt);
-            std::swap(c->oneLaunch, c->oneLaunchAlt);
-            c->accelActive = want;
-            c->cameraDirty = true;
-        }
-    }
+    selectImage(c);
     bool forkNeeded = false;
     if (c->resetTicksThisFrame) {  // CudaTracer.cu:602-608
         forkNeeded = true;
@@ -912,154 +1050,19 @@ int ptss_generate_frame(ptss_context* c, ptss_uchar4* pixels, int ticks) {
     if (c->cfg.syncEachFrame) HIP_TRY(hipEventRecord(c->evStart, st));  // :611
 
     const int numIterations = c->usePathTracer ? (int)c->maxIterations : 1;  // :620
-
-    ptss::EyeParams eye;
-    eye.camera = c->camera;
-    eye.s = -2 * ptm::tan(c->camera.fieldOfView * 0.5f);  // :334
-    eye.aspect = (float)c->tile.height / (float)c->tile.width;
-    eye.invW = 1.0f / c->tile.width;
-    eye.invH = 1.0f / c->tile.height;
+    const ptss::EyeParams eye = eyeParams(c);
     if (c->cameraDirty) {  // origin-only parts of the primary-ray tests (computeEyeRaysKernel :614 itself is fused into bounce 0)
         forkNeeded = true;
-        HIP_TRY(ptss::launchPrimaryPrep(st, c->dScene, c->layout, c->camera.position));
+        HIP_TRY(ptss::launchPrimaryPrep(st, c->image().dBlob, c->image().layout, c->camera.position));
         c->cameraDirty = false;
     }
-
-    // harvest the newest finished live-count readbacks (never blocks)
-    for (Lane& ln : c->lanes)
-        for (int q = 0; q < 4; ++q) {
-            if (!ln.hintPending[q]) continue;
-            if (hipEventQuery(ln.hintEvent[q]) == hipSuccess) {
-                const uint32_t* src = ln.hCounts + (size_t)q * ptss::kCountWords;
-                for (int b = 0; b <= ptss::kMaxBounces; ++b) {
-                    uint32_t mx = 0;
-                    for (int s = 0; s < ptss::kShards; ++s) {
-                        const uint32_t v = src[ptss::countIndex(b, s)];
-                        if (v > mx) mx = v;
-                    }
-                    ln.hint[b] = mx;
-                }
-                ln.haveHint = true;
-                ln.hintPending[q] = false;
-            }
-        }
-    (void)hipGetLastError();
-
-    // Several lanes: each runs on its own stream, forked from the caller's here and joined into it below; their
-    // launches are issued round-robin, bounce by bounce, so that the streams advance together.
-    // STRICT ordering (the default): every frame forks, so the lanes start behind whatever the caller put on its stream
-    // before this call — a reader of the previous frame's pixels or accumulator, a zero-fill, a newly bound buffer's writer.
-    // FREE-RUNNING (cfg.lanesFreeRun, opt-in): the fork happens only when the library's own work on the caller's stream
-    // requires it (the clear of a reset, the camera precomputes) — otherwise a lane's next frame depends on nothing but
-    // its own previous one, and the lanes run on, frame after frame, while the caller's stream merely waits for each
-    // frame's end (the join below); the caller has promised not to touch the buffers in between (include/ptss.h).
-    if (K > 1 && (forkNeeded || c->frameIndex == 0 || !c->cfg.lanesFreeRun)) {
-        HIP_TRY(hipEventRecord(c->evFork, st));
-        for (Lane& ln : c->lanes) HIP_TRY(hipStreamWaitEvent(ln.stream, c->evFork, 0));
-    }
-    // Free-running lanes with S > 1: this frame parks its samples in the buffer of its parity, which displayKernel of the frame
-    // two back (same parity, on the caller's stream) must have emptied — the only thing a free-running lane ever waits for
-    // on the caller's side, and an event that has nearly always fired by now.
-    if (c->stagedTwice && c->frameIndex >= 2)
-        for (Lane& ln : c->lanes) HIP_TRY(hipStreamWaitEvent(ln.stream, c->evDisplay[c->frameIndex & 1u], 0));
+    harvestHints(c);
+    RC_TRY(forkLanes(c, forkNeeded));
     if (c->cfg.timeKernels) drainKernelEvents(c, false);
     // the shorter sphere candidate test: bounded geometry AND a camera within the same range (ray origins are the camera or points on primitives)
-    const bool bounded = c->layout.sphereBounded != 0 && cameraInRange(c->camera);
-    // The frame kernel's bounded form of the sphere test needs what the bounce kernels' needs (above); its grid is the frame's tiles.
-    if (c->oneLaunch && K == 1) {   // every bounce in ONE launch (frameKernel): :622-633 without leaving the device
-        Lane& ln = c->lanes[0];
-        EventPair ev{nullptr, nullptr};
-        if (c->cfg.timeKernels) {
-            if (c->evFree.empty()) {
-                if (c->evBusy.size() >= 4096) drainKernelEvents(c, true);
-                if (c->evFree.empty()) {
-                    HIP_TRY(hipEventCreate(&ev.a));
-                    HIP_TRY(hipEventCreate(&ev.b));
-                }
-            }
-            if (!ev.a) {
-                ev = c->evFree.back();
-                c->evFree.pop_back();
-            }
-            HIP_TRY(hipEventRecord(ev.a, st));
-        }
-        HIP_TRY(ptss::launchFrame(st, fbs[0], c->dScene, c->layout, numIterations, bounded, ln.maxBlocks, c->tile, eye));
-        if (c->cfg.timeKernels) {
-            HIP_TRY(hipEventRecord(ev.b, st));
-            c->evBusy.push_back(ev);
-        }
-    } else
-    for (int i = 0; i < numIterations; ++i) {  // :622-633, guard evaluated on the device
-        for (int k = 0; k < K; ++k) {
-            Lane& ln = c->lanes[(size_t)k];
-            hipStream_t ls = K > 1 ? ln.stream : st;
-            // grid: one tile per workgroup for the expected live count (+1.5 %), never more than the lane's share of the
-            // frame; the kernel grid-strides, so a low hint costs time, not correctness
-            int blocks = ln.maxBlocks;
-            if (i > 0 && ln.haveHint) {
-                // tiles for the fullest shard (+1.5 %), times kShards (workgroup b serves shard b % kShards)
-                const unsigned long long tilesPerShard = ((unsigned long long)ln.hint[i] * 65 / 64 + ptss::kBlock) / ptss::kBlock + 1;
-                const unsigned long long want = tilesPerShard * ptss::kShards;
-                if (want < (unsigned long long)blocks) blocks = (int)want;
-            }
-            // launches wider than 16 resident rounds stop growing (gridCap, ptss_create)
-            if (c->gridCap > 0 && c->gridCap * ptss::kShards < blocks) blocks = c->gridCap * ptss::kShards;
-            EventPair ev{nullptr, nullptr};
-            if (c->cfg.timeKernels) {
-                if (c->evFree.empty()) {
-                    if (c->evBusy.size() >= 4096) drainKernelEvents(c, true);
-                    if (c->evFree.empty()) {
-                        HIP_TRY(hipEventCreate(&ev.a));
-                        HIP_TRY(hipEventCreate(&ev.b));
-                    }
-                }
-                if (!ev.a) {
-                    ev = c->evFree.back();
-                    c->evFree.pop_back();
-                }
-                HIP_TRY(hipEventRecord(ev.a, ls));
-            }
-            // the peers' done totals once their bounce i - 1 of this frame has ended (all of those launches precede this
-            // one in host order, so a kernel that waits for them never waits for something behind it in a shared queue)
-            if (i > 0)
-                for (int j = 0, p = 0; j < K; ++j)
-                    if (j != k) fbs[k].peerTarget[p++] = c->lanes[(size_t)j].doneTarget[i - 1];
-            HIP_TRY(ptss::launchBounce(ls, fbs[k], c->dScene, c->layout, i, i == numIterations - 1, c->sceneInLds, bounded, blocks, c->tile, eye));
-            ln.doneTarget[i] += (uint32_t)blocks;  // every workgroup of the launch adds 1 to done[i][its shard] as it ends
-            if (c->cfg.timeKernels) {
-                HIP_TRY(hipEventRecord(ev.b, ls));
-                c->evBusy.push_back(ev);
-            }
-        }
-    }
-    for (int k = 0; k < K; ++k) {
-        Lane& ln = c->lanes[(size_t)k];
-        hipStream_t ls = K > 1 ? ln.stream : st;
-        // (flushKernel itself waits, on the device, until every peer lane has finished the previous frame: FrameBuffers::myFrameDone)
-        ptss::FlushTargets targets{};
-        for (int j = 0, p = 0; j < K; ++j)
-            if (j != k) {
-                for (int b = 0; b <= ptss::kMaxBounces; ++b) targets.target[p][b] = c->lanes[(size_t)j].doneTarget[b];
-                ++p;
-            }
-        HIP_TRY(ptss::launchFlush(ls, fbs[k], numIterations, targets));  // :637
-        // every 8th frame (and until a hint exists) copy counts[] to pinned memory for later grid sizing
-        if (!ln.haveHint || (c->frameIndex & 7u) == 0) {
-            const int q = (int)((c->frameIndex >> 3) & 3u);
-            if (!ln.hintPending[q]) {
-                HIP_TRY(hipMemcpyAsync(ln.hCounts + (size_t)q * ptss::kCountWords, ln.dLastCounts, ptss::kCountWords * sizeof(uint32_t),
-                                       hipMemcpyDeviceToHost, ls));
-                HIP_TRY(hipEventRecord(ln.hintEvent[q], ls));
-                ln.hintPending[q] = true;
-            }
-        }
-        // the join: the caller's stream is ordered behind every lane's frame (the lanes themselves run on) — ONE event, behind
-        // the last lane's flushKernel, which ends only when every other lane's has (FrameBuffers::joinsFrame); an event per lane cost 1-2 %
-        if (K > 1 && k == K - 1) {
-            HIP_TRY(hipEventRecord(ln.evDone[c->frameIndex & 1u], ls));
-            HIP_TRY(hipStreamWaitEvent(st, ln.evDone[c->frameIndex & 1u], 0));
-        }
-    }
+    const bool bounded = c->image().layout.sphereBounded != 0 && cameraInRange(c->camera);
+    RC_TRY(c->image().oneLaunch && K == 1 ? traceOneLaunch(c, fbs[0], numIterations, bounded, eye) : traceBounces(c, fbs, numIterations, bounded, eye));
+    RC_TRY(flushAndJoin(c, fbs, numIterations));
     if (c->samples > 1) {
         HIP_TRY(ptss::launchDisplay(st, fbs[0]));  // S > 1: add the pass's staged samples, then the display value
         if (c->stagedTwice) HIP_TRY(hipEventRecord(c->evDisplay[c->frameIndex & 1u], st));
@@ -1277,7 +1280,7 @@ int ptss_guard_timeouts(ptss_context* c, unsigned int* out) {
 
 int ptss_one_launch_frames(const ptss_context* c, int* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
-    *out = (c->oneLaunch && c->lanes.size() == 1) ? 1 : 0;
+    *out = (c->image().oneLaunch && c->lanes.size() == 1) ? 1 : 0;
     return PTSS_OK;
 }
 

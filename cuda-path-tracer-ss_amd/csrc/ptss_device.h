@@ -40,8 +40,8 @@ constexpr int kMaxBounces = 64;  // counts has (kMaxBounces + 1) x kShards entri
 #define PTSS_SHARDS 16    // pool regions / live-ray counters per bounce
 #endif
 #ifndef PTSS_CHUNK
-#define PTSS_CHUNK 16     // spheres per chunk of the many-sphere traversal; with the kd-split order (ptss_api.hip spatialOrder),
-                          // configs[4]'s scene at S = 4, same box: 4: 2,224, 8: 3,762, 16: 4,158-4,167, 32: 3,476 Mrays/s — every
+#define PTSS_CHUNK 16     // spheres per chunk of the many-sphere traversal (at most 16: chunkCandidates); with the kd-split order (ptss_api.hip
+                          // spatialOrder), configs[4]'s scene at S = 4, same box: 4: 2,224, 8: 3,762, 16: 4,158-4,167 Mrays/s — every
                           // lane tests every chunk bound, so halving their number is worth more than the tighter fit of smaller chunks
 #endif
 #ifndef PTSS_MINWAVES
@@ -215,6 +215,6 @@ struct FlushTargets {  // flushKernel re-derives the guard of every bounce: targ
     uint32_t target[kMaxLanes - 1][kMaxBounces + 1];
 };
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets);  // one per lane
-int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool accel);
+int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool bounded);
 
 }  // namespace ptss

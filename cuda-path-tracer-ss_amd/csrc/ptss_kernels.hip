@@ -27,6 +27,9 @@
 #include "ptquant.h"
 #include "pttri.h"
 
+#include <array>
+#include <utility>
+
 using namespace ptv;
 
 namespace ptss {
@@ -2095,6 +2098,8 @@ __global__ __launch_bounds__(kBlock, kAccel ? 4 : (kFirst ? PTSS_MINWAVES_FIRST 
 // workgroup a waiter depends on is running or has finished; every wait is bounded all the same (peerWaitExpired) and a
 // workgroup whose wait expires leaves — the host then reports PTSS_ETIMEOUT.
 constexpr int kDoneWord = 1;
+// the whole-frame guard adds the shards' counts up across lanes 0..kShards-1 of one wave with a butterfly
+static_assert((kShards & (kShards - 1)) == 0 && kShards <= 64, "frameKernel's guard needs a power-of-two shard count of at most 64");
 
 __device__ __forceinline__ bool waitForCount(const uint32_t* word, uint32_t target) {   // bounded; true = reached
     unsigned long long since = 0ull;
@@ -2194,7 +2199,7 @@ __global__ __launch_bounds__(kBlock, kAccel ? 4 : (kBounded ? PTSS_MINWAVES_BOUN
                 }
                 uint32_t total = theirs;
 #pragma unroll
-                for (int off = 8; off >= 1; off >>= 1) total += (uint32_t)__shfl_xor((int)total, off);
+                for (int off = kShards / 2; off >= 1; off >>= 1) total += (uint32_t)__shfl_xor((int)total, off);
                 const bool allOk = __builtin_amdgcn_ballot_w64(!ok) == 0ull;
                 if (lane == 0) {
                     if (!allOk) atomicAdd(fb.guardTimeouts, 1u);
@@ -2355,15 +2360,6 @@ hipError_t launchPrimaryPrep(hipStream_t st, float4* sceneBlob, const SceneLayou
     return hipGetLastError();
 }
 
-template <bool kLast, bool kLds, bool kFirst, bool kAccel, bool kBounded, bool kPairs>
-static hipError_t launchBounceT(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, const SceneLayout& layout,
-                                int bounce, int gridBlocks, const TileMap& tile, const EyeParams& eye) {
-    const size_t lds = bounceLdsBytes(layout, kLds);
-    hipLaunchKernelGGL((bounceKernel<kLast, kLds, kFirst, kAccel, kBounded, kPairs>), dim3(gridBlocks), dim3(kBlock), lds, st, fb, sceneBlob, layout, bounce,
-                       tile, eye);
-    return hipGetLastError();
-}
-
 #if PTSS_DIAG
 hipError_t readDiagCounters(unsigned long long* out8) { return hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_diag), 64); }
 #endif
@@ -2371,49 +2367,57 @@ size_t bounceLdsBytes(const SceneLayout& layout, bool sceneInLds) {
     return ((sceneInLds ? (size_t)layout.ldsVec4 : 0) + kBlockLdsVec4) * sizeof(float4);
 }
 
-hipError_t launchBounce(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int bounce,
-                        bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye) {
-    const bool isFirst = bounce == 0;
-#define PTSS_GO(a, b, c)                                                                                   \
-    do {                                                                                                   \
-        if (layout.accelSpheres) return launchBounceT<a, b, c, true, false, false>(st, fb, sceneBlob, layout, bounce, gridBlocks, tile, eye); \
-        if (bounded && layout.neePairs) return launchBounceT<a, b, c, false, true, true>(st, fb, sceneBlob, layout, bounce, gridBlocks, tile, eye); \
-        if (bounded) return launchBounceT<a, b, c, false, true, false>(st, fb, sceneBlob, layout, bounce, gridBlocks, tile, eye);     \
-        return launchBounceT<a, b, c, false, false, false>(st, fb, sceneBlob, layout, bounce, gridBlocks, tile, eye);                 \
-    } while (0)
-    if (sceneInLds) {
-        if (isFirst) { if (isLast) PTSS_GO(true, true, true); else PTSS_GO(false, true, true); }
-        if (isLast) PTSS_GO(true, true, false); else PTSS_GO(false, true, false);
-    }
-    if (isFirst) { if (isLast) PTSS_GO(true, false, true); else PTSS_GO(false, false, true); }
-    if (isLast) PTSS_GO(true, false, false); else PTSS_GO(false, false, false);
-#undef PTSS_GO
+// ---- which instantiation runs: four scene variants, each one {kAccel, kBounded, kPairs} of bounceKernel and frameKernel.
+// sceneVariant is the one place that decides; every launch and occupancy query below looks its kernel up through it.
+enum SceneVariant : int { kVariantAccel, kVariantBoundedPairs, kVariantBounded, kVariantPlain, kNumVariants };
+constexpr bool kVariantArgs[kNumVariants][3] = {{true, false, false}, {false, true, true}, {false, true, false}, {false, false, false}};
+
+// bounded: the frame may take the shorter sphere test (SceneLayout::sphereBounded and a camera in range, ptss_api.hip)
+static SceneVariant sceneVariant(const SceneLayout& layout, bool bounded) {
+    if (layout.accelSpheres) return kVariantAccel;
+    if (bounded && layout.neePairs) return kVariantBoundedPairs;
+    return bounded ? kVariantBounded : kVariantPlain;
 }
 
-template <bool kAccel, bool kBounded, bool kPairs>
-static hipError_t launchFrameT(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, const SceneLayout& layout, int numBounces, int gridBlocks,
-                               const TileMap& tile, const EyeParams& eye) {
-    hipLaunchKernelGGL((frameKernel<kAccel, kBounded, kPairs>), dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, true), st, fb, sceneBlob, layout,
-                       numBounces, tile, eye);
+using KernelFn = void (*)(FrameBuffers, const float4*, SceneLayout, int, TileMap, EyeParams);   // bounceKernel and frameKernel alike
+
+template <size_t... I>   // entry I = variant * 8 + kLast * 4 + kSceneInLds * 2 + kFirst
+constexpr std::array<KernelFn, sizeof...(I)> bounceTable(std::index_sequence<I...>) {
+    return {{bounceKernel<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, kVariantArgs[I / 8][0], kVariantArgs[I / 8][1], kVariantArgs[I / 8][2]>...}};
+}
+template <size_t... V>
+constexpr std::array<KernelFn, sizeof...(V)> frameTable(std::index_sequence<V...>) {
+    return {{frameKernel<kVariantArgs[V][0], kVariantArgs[V][1], kVariantArgs[V][2]>...}};
+}
+static KernelFn bounceKernelFor(SceneVariant v, bool last, bool sceneInLds, bool first) {
+    static constexpr auto table = bounceTable(std::make_index_sequence<kNumVariants * 8>{});
+    return table[v * 8 + last * 4 + sceneInLds * 2 + first];
+}
+static KernelFn frameKernelFor(SceneVariant v) {
+    static constexpr auto table = frameTable(std::make_index_sequence<kNumVariants>{});
+    return table[v];
+}
+static int blocksPerCU(KernelFn k, size_t lds) {
+    int a = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k, kBlock, lds) == hipSuccess ? a : 0;
+}
+
+hipError_t launchBounce(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int bounce,
+                        bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye) {
+    const KernelFn k = bounceKernelFor(sceneVariant(layout, bounded), isLast, sceneInLds, bounce == 0);
+    hipLaunchKernelGGL(k, dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, sceneInLds), st, fb, sceneBlob, layout, bounce, tile, eye);
     return hipGetLastError();
 }
+
 hipError_t launchFrame(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int numBounces, bool bounded, int gridBlocks,
                        TileMap tile, EyeParams eye) {
-    if (layout.accelSpheres) return launchFrameT<true, false, false>(st, fb, sceneBlob, layout, numBounces, gridBlocks, tile, eye);
-    if (bounded && layout.neePairs) return launchFrameT<false, true, true>(st, fb, sceneBlob, layout, numBounces, gridBlocks, tile, eye);
-    if (bounded) return launchFrameT<false, true, false>(st, fb, sceneBlob, layout, numBounces, gridBlocks, tile, eye);
-    return launchFrameT<false, false, false>(st, fb, sceneBlob, layout, numBounces, gridBlocks, tile, eye);
+    const KernelFn k = frameKernelFor(sceneVariant(layout, bounded));
+    hipLaunchKernelGGL(k, dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, true), st, fb, sceneBlob, layout, numBounces, tile, eye);
+    return hipGetLastError();
 }
 // resident workgroups per CU of the frame kernel `layout` would run (the API's answer; the caller keeps one in reserve)
 int frameOccupancyBlocksPerCU(const SceneLayout& layout, bool bounded) {
-    const size_t lds = bounceLdsBytes(layout, true);
-    int a = 0;
-    hipError_t e;
-    if (layout.accelSpheres) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, frameKernel<true, false, false>, kBlock, lds);
-    else if (bounded && layout.neePairs) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, frameKernel<false, true, true>, kBlock, lds);
-    else if (bounded) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, frameKernel<false, true, false>, kBlock, lds);
-    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, frameKernel<false, false, false>, kBlock, lds);
-    return e == hipSuccess ? a : 0;
+    return blocksPerCU(frameKernelFor(sceneVariant(layout, bounded)), bounceLdsBytes(layout, true));
 }
 
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets) {
@@ -2422,20 +2426,8 @@ hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, c
 }
 
 // Resident workgroups per CU of the mid-bounce instantiation that `layout` runs (registers and this scene's LDS image)
-int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool accel) {
-    const size_t lds = bounceLdsBytes(layout, sceneInLds);
-    int a = 0;
-    hipError_t e;
-    if (accel)
-        e = sceneInLds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, true, false, true, false, false>, kBlock, lds)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, false, false, true, false, false>, kBlock, lds);
-    else if (layout.sphereBounded)   // (the paired-shadow instantiations have the same launch bounds)
-        e = sceneInLds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, true, false, false, true, false>, kBlock, lds)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, false, false, false, true, false>, kBlock, lds);
-    else
-        e = sceneInLds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, true, false, false, false, false>, kBlock, lds)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, bounceKernel<false, false, false, false, false, false>, kBlock, lds);
-    return e == hipSuccess ? a : 0;
+int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool bounded) {
+    return blocksPerCU(bounceKernelFor(sceneVariant(layout, bounded), false, sceneInLds, false), bounceLdsBytes(layout, sceneInLds));
 }
 
 }  // namespace ptss

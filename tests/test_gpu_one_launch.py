@@ -129,3 +129,32 @@ def test_which_frames_qualify():
         r = ptss.Renderer(scene, w, h, samples_per_pass=S, frame_lanes=lanes, one_launch_frames=1)
         assert r.one_launch_frames == want, (w, h, S, lanes)
         r.close()
+
+
+@pytest.mark.parametrize("one_launch,lanes", [(0, 1), (0, 2), (1, 1)])
+def test_kernel_timing_counts_every_launch_and_changes_nothing(one_launch, lanes):
+    """cfg.timeKernels brackets each bounce launch (each frame's one launch) with an event pair on its stream: the results are
+    an untimed run's, bit for bit, and ptss_bounce_kernel_time reports one span per launch — every bounce of every lane is
+    launched, whatever the loop guard then decides on the device."""
+    scene = ptss.Scene("mixed")
+    w, h, bounces, frames = 100, 37, 8, 3
+    out = {}
+    for timed in (False, True):
+        r = ptss.Renderer(scene, w, h, max_iterations=bounces, float_accumulator=True, time_kernels=timed, frame_lanes=lanes,
+                          one_launch_frames=one_launch)
+        assert r.one_launch_frames == (one_launch == 1) and r.frame_lanes == lanes
+        for _ in range(frames):
+            r.generate_frame()
+        if timed:
+            ms, launches = r.bounce_kernel_time()
+            assert launches == (frames if one_launch else frames * bounces * lanes)
+            assert ms > 0
+        out[timed] = (r.accumulator(), r.pixels(), r.float_accumulator(), r.live_counts().copy(), r.total_ray_bounces())
+        assert r.guard_timeouts() == 0
+        r.close()
+    acc, pix, fsum, live, total = out[False]
+    assert np.array_equal(out[True][0], acc)
+    assert np.array_equal(out[True][1], pix)
+    assert np.array_equal(out[True][2], fsum, equal_nan=True)
+    assert np.array_equal(out[True][3], live)
+    assert out[True][4] == total

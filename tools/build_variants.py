@@ -29,7 +29,6 @@ VARIANTS = {
     "s8": ["PTSS_SHARDS=8"],
     "s32": ["PTSS_SHARDS=32"],
     "ck8": ["PTSS_CHUNK=8"],
-    "ck32": ["PTSS_CHUNK=32"],
     # ablations (results are WRONG by construction; timing only)
     "a1": ["PTSS_ABLATE=1"],   # no NEE
     "a2": ["PTSS_ABLATE=2"],   # no closest-hit loops
