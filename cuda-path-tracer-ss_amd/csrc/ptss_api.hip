@@ -129,6 +129,7 @@ struct ptss_context {
     std::vector<std::pair<double, double>> kernelSpans;
     hipEvent_t evEpoch = nullptr;
     unsigned int timeoutsSeen = 0;   // ptss_guard_timeouts value already reported as PTSS_ETIMEOUT
+    unsigned long long launchedKernels = 0;   // bounce / frame kernel instantiations enqueued since ptss_create (ptss_launched_kernels)
 };
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 
@@ -694,7 +695,8 @@ int timedLaunch(ptss_context* c, hipStream_t s, Launch launch) {
 int traceOneLaunch(ptss_context* c, const ptss::FrameBuffers& fb, int numIterations, bool bounded, const ptss::EyeParams& eye) {
     const SceneImage& im = c->image();
     return timedLaunch(c, c->stream, [&] {
-        HIP_TRY(ptss::launchFrame(c->stream, fb, im.dBlob, im.layout, numIterations, bounded, c->lanes[0].maxBlocks, c->tile, eye));
+        HIP_TRY(ptss::launchFrame(c->stream, fb, im.dBlob, im.layout, numIterations, bounded, c->lanes[0].maxBlocks, c->tile, eye,
+                                          &c->launchedKernels));
         return PTSS_OK;
     });
 }
@@ -724,7 +726,8 @@ int traceBounces(ptss_context* c, ptss::FrameBuffers* fbs, int numIterations, bo
                 for (int j = 0, p = 0; j < K; ++j)
                     if (j != k) fbs[k].peerTarget[p++] = c->lanes[(size_t)j].doneTarget[i - 1];
             RC_TRY(timedLaunch(c, ls, [&] {
-                HIP_TRY(ptss::launchBounce(ls, fbs[k], im.dBlob, im.layout, i, i == numIterations - 1, im.inLds, bounded, blocks, c->tile, eye));
+                HIP_TRY(ptss::launchBounce(ls, fbs[k], im.dBlob, im.layout, i, i == numIterations - 1, im.inLds, bounded, blocks, c->tile, eye,
+                                               &c->launchedKernels));
                 return PTSS_OK;
             }));
             ln.doneTarget[i] += (uint32_t)blocks;  // every workgroup of the launch adds 1 to done[i][its shard] as it ends
@@ -1287,6 +1290,12 @@ int ptss_one_launch_frames(const ptss_context* c, int* out) {
 int ptss_frame_lanes(const ptss_context* c, int* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     *out = (int)c->lanes.size();
+    return PTSS_OK;
+}
+
+int ptss_launched_kernels(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->launchedKernels;
     return PTSS_OK;
 }
 

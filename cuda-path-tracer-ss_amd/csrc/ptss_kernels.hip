@@ -2389,9 +2389,10 @@ template <size_t... V>
 constexpr std::array<KernelFn, sizeof...(V)> frameTable(std::index_sequence<V...>) {
     return {{frameKernel<kVariantArgs[V][0], kVariantArgs[V][1], kVariantArgs[V][2]>...}};
 }
-static KernelFn bounceKernelFor(SceneVariant v, bool last, bool sceneInLds, bool first) {
+static int bounceIndex(SceneVariant v, bool last, bool sceneInLds, bool first) { return v * 8 + last * 4 + sceneInLds * 2 + first; }
+static KernelFn bounceKernelFor(int index) {
     static constexpr auto table = bounceTable(std::make_index_sequence<kNumVariants * 8>{});
-    return table[v * 8 + last * 4 + sceneInLds * 2 + first];
+    return table[index];
 }
 static KernelFn frameKernelFor(SceneVariant v) {
     static constexpr auto table = frameTable(std::make_index_sequence<kNumVariants>{});
@@ -2402,18 +2403,24 @@ static int blocksPerCU(KernelFn k, size_t lds) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k, kBlock, lds) == hipSuccess ? a : 0;
 }
 
+// *launched collects bit `bounceTable index` / `32 + variant` of every instantiation enqueued (ptss_launched_kernels)
 hipError_t launchBounce(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int bounce,
-                        bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye) {
-    const KernelFn k = bounceKernelFor(sceneVariant(layout, bounded), isLast, sceneInLds, bounce == 0);
-    hipLaunchKernelGGL(k, dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, sceneInLds), st, fb, sceneBlob, layout, bounce, tile, eye);
-    return hipGetLastError();
+                        bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye, unsigned long long* launched) {
+    const int index = bounceIndex(sceneVariant(layout, bounded), isLast, sceneInLds, bounce == 0);
+    hipLaunchKernelGGL(bounceKernelFor(index), dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, sceneInLds), st, fb, sceneBlob, layout, bounce,
+                       tile, eye);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *launched |= 1ull << index;
+    return e;
 }
 
 hipError_t launchFrame(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int numBounces, bool bounded, int gridBlocks,
-                       TileMap tile, EyeParams eye) {
-    const KernelFn k = frameKernelFor(sceneVariant(layout, bounded));
-    hipLaunchKernelGGL(k, dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, true), st, fb, sceneBlob, layout, numBounces, tile, eye);
-    return hipGetLastError();
+                       TileMap tile, EyeParams eye, unsigned long long* launched) {
+    const SceneVariant v = sceneVariant(layout, bounded);
+    hipLaunchKernelGGL(frameKernelFor(v), dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, true), st, fb, sceneBlob, layout, numBounces, tile, eye);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *launched |= 1ull << (kNumVariants * 8 + v);
+    return e;
 }
 // resident workgroups per CU of the frame kernel `layout` would run (the API's answer; the caller keeps one in reserve)
 int frameOccupancyBlocksPerCU(const SceneLayout& layout, bool bounded) {
@@ -2427,7 +2434,7 @@ hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, c
 
 // Resident workgroups per CU of the mid-bounce instantiation that `layout` runs (registers and this scene's LDS image)
 int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool bounded) {
-    return blocksPerCU(bounceKernelFor(sceneVariant(layout, bounded), false, sceneInLds, false), bounceLdsBytes(layout, sceneInLds));
+    return blocksPerCU(bounceKernelFor(bounceIndex(sceneVariant(layout, bounded), false, sceneInLds, false)), bounceLdsBytes(layout, sceneInLds));
 }
 
 }  // namespace ptss

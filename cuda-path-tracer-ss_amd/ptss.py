@@ -36,6 +36,18 @@ class RenderConfig(C.Structure):
                 ("lanesFreeRun", C.c_int), ("oneLaunchFrames", C.c_int)]
 
 
+# scene variants of the bounce / frame kernels, in the order of their bit in ptss_launched_kernels (include/ptss.h)
+KERNEL_VARIANTS = ("accel", "bounded+pairs", "bounded", "plain")
+
+
+def all_kernels():
+    """Every instantiation ptss_launched_kernels can report: ("bounce", variant, last, inLds, first) and ("frame", variant)."""
+    out = {("frame", v) for v in KERNEL_VARIANTS}
+    for v in KERNEL_VARIANTS:
+        out |= {("bounce", v, last, lds, first) for last in (False, True) for lds in (False, True) for first in (False, True)}
+    return out
+
+
 _host = None
 _dev = None
 
@@ -121,6 +133,8 @@ def device_lib():
         L.ptss_one_launch_frames.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptss_guard_timeouts.argtypes = [vp, C.POINTER(C.c_uint)]
         L.ptss_bounce_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
+        L.ptss_launched_kernels.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_counters.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_error_string.argtypes = [C.c_int]
         L.ptss_error_string.restype = C.c_char_p
         L.ptss_last_error_detail.restype = C.c_char_p
@@ -374,6 +388,25 @@ class Renderer:
         v = C.c_uint()
         _check(device_lib().ptss_guard_timeouts(self._ctx, C.byref(v)))
         return v.value
+
+    def launched_kernels(self):
+        """The kernel instantiations this context has launched since it was created, as all_kernels() names them."""
+        v = C.c_ulonglong()
+        _check(device_lib().ptss_launched_kernels(self._ctx, C.byref(v)))
+        out = set()
+        for i, name in enumerate(KERNEL_VARIANTS):
+            for j in range(8):
+                if v.value >> (i * 8 + j) & 1:
+                    out.add(("bounce", name, bool(j & 4), bool(j & 2), bool(j & 1)))
+            if v.value >> (32 + i) & 1:
+                out.add(("frame", name))
+        return out
+
+    def debug_counters(self):
+        """The eight counter words of a diagnostic build (-DPTSS_DIAG); zeros from the shipped library."""
+        out = (C.c_ulonglong * 8)()
+        _check(device_lib().ptss_debug_counters(self._ctx, out))
+        return [int(x) for x in out]
 
     def bounce_kernel_time(self):
         ms = C.c_double()

@@ -149,6 +149,12 @@ int ptss_frame_lanes(const ptss_context* ctx, int* out);
  * ptss_generate_frame with syncEachFrame) returns PTSS_ETIMEOUT once when this count has grown since the last check. */
 int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
 
+/* Which kernel instantiations this context has enqueued since ptss_create, as a bitmask (tests/test_gpu_kernel_coverage.py):
+ * bit v*8 + last*4 + inLds*2 + first for the bounce kernel of scene variant v (0 many-sphere chunks, 1 bounded sphere test with
+ * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
+ * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v. Recorded on the host at launch. */
+int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
+
 /* Diagnostic builds only (-DPTSS_DIAG=<bits>, csrc/ptss_diag.h, tools/build_variants.py): the eight counter words of that
  * build (sphere candidates per lane, scatter blocks, chunk culling, shadow-segment pairs, queue lengths); all zero in the
  * shipped library, which carries no counter. */

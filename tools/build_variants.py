@@ -1,5 +1,6 @@
 """Builds A/B variants of libptss.so (the eight switches of csrc/ptss_device.h; extra ad-hoc -D flags: `python tools/build_variants.py tag=NAME=V,NAME2=V2`) as lib/libptss_<tag>.so.
-Select one at run time with PTSS_LIBNAME=libptss_<tag>.so. Used only for measurements (profiles/)."""
+Select one at run time with PTSS_LIBNAME=libptss_<tag>.so. Used only for measurements (profiles/); every entry except the
+ablations must trace the shipped library's image, and tests/test_gpu_build_variants.py checks each against the oracle."""
 import importlib.util
 import os
 import sys
