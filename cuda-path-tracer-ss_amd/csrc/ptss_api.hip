@@ -16,8 +16,10 @@
 #include "ptss.h"
 #include "ptss_device.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include "ptquant.h"
+#include "ptmesh.h"
 #include "pttri.h"
 
 using namespace ptv;
@@ -192,6 +194,54 @@ bool cameraInRange(const ptss_camera& cam) {
 
 bool accelEligible(const ptss_scene_desc& s) { return s.numSpheres >= (size_t)kAccelMinSpheres && geometryBounded(s); }
 
+// ---- the mesh image (SceneLayout::mesh) ---------------------------------------------------------------------
+// Scenes of many triangles and few spheres: 512 triangles or more — every edge-classed scene (T <= 255) keeps its image, and so
+// does every scene of the older test suites, the largest of which (tests/test_gpu_kernel_coverage.py, the in-place cases) holds
+// 484 triangles —, fewer than kAccelMinSpheres spheres (those keep the sphere chunks), at most 2^20 triangles,
+// and every vertex finite with |coordinate| <= 2^40 — which, with the kernels' per-query test |o|^2 < 2^80, |d|^2 = 1 +- 1e-5,
+// keeps every intermediate of the reference's test finite: |det| <= |e1| |e2| |d| < 2^84, |e2 . r| <= |e2| |o - v0| |e1| < 2^126
+// (so no NaN distance either), and the reciprocal inside its fast range.
+constexpr int kMeshMinTriangles = 512;
+constexpr size_t kMeshMaxTriangles = size_t(1) << 20;
+bool meshEligible(const ptss_scene_desc& s) {
+    if (s.numTriangles < (size_t)kMeshMinTriangles || s.numTriangles > kMeshMaxTriangles || s.numSpheres >= (size_t)kAccelMinSpheres) return false;
+    auto ok = [](float v) { return std::fabs(v) <= 0x1p40f; };   // false for NaN and infinities
+    for (size_t i = 0; i < s.numTriangles; ++i) {
+        const ptss_triangle& t = s.triangles[i];
+        for (const ptss_vec3* v : {&t.vertex0, &t.vertex1, &t.vertex2})
+            if (!ok(v->x) || !ok(v->y) || !ok(v->z)) return false;
+    }
+    return true;
+}
+// stored position -> original index: kdSplit's scheme on the triangles' centroids, the cut placed at a multiple of kMeshLeaf^2
+// while a part holds more than that and at a multiple of kMeshLeaf below, so that every kMeshLeaf consecutive positions are a
+// leaf and every kMeshLeaf^2 a group. Ties by original index (a deterministic order); any permutation is legal, the closest hit
+// being keyed by original index.
+void meshSplit(const std::vector<std::array<float, 3>>& c, std::vector<int>& idx, int lo, int hi) {
+    constexpr int kLeaf = ptss::kMeshLeaf, kGroup = ptss::kMeshLeaf * ptss::kMeshLeaf;
+    const int n = hi - lo;
+    if (n <= kLeaf) return;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = lo; i < hi; ++i)
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = std::min(mn[a], c[(size_t)idx[i]][a]);
+            mx[a] = std::max(mx[a], c[(size_t)idx[i]][a]);
+        }
+    int axis = 0;
+    for (int a = 1; a < 3; ++a)
+        if (mx[a] - mn[a] > mx[axis] - mn[axis]) axis = a;
+    const int unit = n > kGroup ? kGroup : kLeaf;
+    int left = ((n / 2 + unit - 1) / unit) * unit;
+    if (left >= n) left -= unit;
+    if (left <= 0) return;
+    std::nth_element(idx.begin() + lo, idx.begin() + lo + left, idx.begin() + hi, [&](int a, int b) {
+        const float ka = c[(size_t)a][axis], kb = c[(size_t)b][axis];
+        return ka < kb || (ka == kb && a < b);
+    });
+    meshSplit(c, idx, lo, lo + left);
+    meshSplit(c, idx, lo + left, hi);
+}
+
 // sorted position -> original index. The spheres are split recursively at the median of their centres along the axis of
 // largest extent (a kd-tree built by std::nth_element; ties by original index, so the order is deterministic), the cut
 // placed at a multiple of 64 spheres while a part holds more than 64 and at a multiple of kChunkSpheres below that: every
@@ -319,7 +369,7 @@ std::vector<int> spatialOrder(const ptss_scene_desc& s) {
     return order;
 }
 
-void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float4>& blob, bool accel) {
+void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float4>& blob, bool accel, bool mesh) {
     auto u2f = [](uint32_t u) { return __builtin_bit_cast(float, u); };
     L.accelSpheres = accel ? 1 : 0;
     L.numChunks = accel ? (int)((s.numSpheres + ptss::kChunkSpheres - 1) / ptss::kChunkSpheres) : 0;
@@ -336,6 +386,34 @@ void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float
     L.offSphere = off;      off += sphereAlloc;
     if (!accel) { L.offSphereMat = off; off += (sphereRows + 3) / 4; }
     L.offChunk = off;       off += (L.numChunks + 3) / 4 * 4;   // bound rows padded to a multiple of four (zero rows: chunkMask drops their bits)
+    const int numLeaves = mesh ? (L.numTriangles + ptss::kMeshLeaf - 1) / ptss::kMeshLeaf : 0;
+    const int numGroups = (numLeaves + ptss::kMeshLeaf - 1) / ptss::kMeshLeaf;
+    bool leavesInLds = false;
+    int offGroup = 0, offLeaf = 0;   // (L.mesh shares its words with triClassPack, which is cleared below)
+    if (mesh) {
+        // Mesh image: group bounds, leaf bounds where they fit, spheres, materials, lights and the tone-map table are staged in
+        // LDS; the triangle tables stay in global memory (read through `cold`) — T x 10 rows would not fit beyond ~400 triangles.
+        offGroup = off;   off += 3 * ((numGroups + 3) / 4 * 4);   // padded to whole trips of four bounds (meshGroupMask drops their bits)
+        const int leafRows = 3 * numLeaves;
+        const int rest = 5 * L.numMaterials + 2 * L.numPointLights + 2 * L.numAreaLights + ptq::kTableFloats / 4 + sphereAlloc;
+        ptss::SceneLayout probe{};
+        probe.ldsVec4 = off + leafRows + rest;
+        leavesInLds = ptss::bounceLdsBytes(probe, true) <= 64 * 1024;
+        if (leavesInLds) { offLeaf = off; off += leafRows; }
+        L.offMaterial = off;    off += 5 * L.numMaterials;
+        L.offPointLight = off;  off += 2 * L.numPointLights;
+        L.offAreaLight = off;   off += 2 * L.numAreaLights;
+        L.offQuant = off;       off += ptq::kTableFloats / 4;
+        L.offPrimSphere = off;  off += sphereAlloc;
+        L.offPrimChunk = off;
+        L.ldsVec4 = off;
+        if (!leavesInLds) { offLeaf = off; off += leafRows; }
+        L.offTri = off;         off += 3 * L.numTriangles;
+        L.offTriNormal = off;   off += 3 * L.numTriangles;
+        L.offTriVert = off;     off += 2 * L.numTriangles;
+        L.offTriPos = off;      off += (L.numTriangles + 3) / 4;
+        L.offPrimTri = off;     off += 2 * L.numTriangles;
+    } else {
     L.offTri = off;         off += 3 * L.numTriangles;
     L.offTriNormal = off;   off += 3 * L.numTriangles;
     L.offTriVert = off;     off += 2 * L.numTriangles;
@@ -348,6 +426,7 @@ void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float
     L.offPrimTri = off;     off += 2 * L.numTriangles;
     L.offPrimChunk = off;   off += accel ? (L.numChunks + 3) / 4 * 4 : 0;
     L.ldsVec4 = off;        // everything up to here is staged into LDS
+    }
     if (accel) {            // cold integer tables of the many-sphere image: global memory only
         L.offSphereMat = off;   off += (sphereRows + 3) / 4;
         L.offSphereOrig = off;  off += (sphereRows + 3) / 4;
@@ -393,6 +472,22 @@ void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float
     for (int code = 0, pos = 0; code <= 16 && L.triClassed; ++code) {
         while (pos < L.numTriangles && triCode[(size_t)triOrder[(size_t)pos]] < code) ++pos;
         L.triClassPack[code / 4] |= (uint32_t)pos << (8 * (code % 4));
+    }
+    if (mesh) {   // (T >= 512: never classed, so the union holds the mesh dimensions)
+        std::vector<std::array<float, 3>> centroid((size_t)L.numTriangles);
+        for (int i = 0; i < L.numTriangles; ++i) {
+            const ptss_triangle& t = s.triangles[i];
+            for (int a = 0; a < 3; ++a) {
+                const float* v0 = &t.vertex0.x, *v1 = &t.vertex1.x, *v2 = &t.vertex2.x;
+                centroid[(size_t)i][a] = (float)(((double)v0[a] + v1[a] + v2[a]) / 3);
+            }
+        }
+        meshSplit(centroid, triOrder, 0, L.numTriangles);
+        L.mesh.numLeaves = numLeaves;
+        L.mesh.numGroups = numGroups;
+        L.mesh.offGroup = offGroup;
+        L.mesh.offLeaf = offLeaf;
+        L.mesh.reserved = 0;
     }
     blob.assign((size_t)off + 1, float4{0, 0, 0, 0});
     ptq::build_thresholds(reinterpret_cast<float*>(&blob[L.offQuant]));
@@ -440,6 +535,55 @@ void packScene(const ptss_scene_desc& s, ptss::SceneLayout& L, std::vector<float
         blob[L.offTriVert + 2 * pos + 0] = float4{t.vertex1.x, t.vertex1.y, t.vertex1.z, 0};
         blob[L.offTriVert + 2 * pos + 1] = float4{t.vertex2.x, t.vertex2.y, t.vertex2.z, 0};
         reinterpret_cast<int*>(&blob[L.offTriPos])[i] = pos;
+    }
+    if (mesh) {
+        // THE BOUNDS OF THE MESH IMAGE (ptmesh.h mayTouch). A bound may exclude a leaf only if the reference's float
+        // test (Primitives.h:25-83) cannot accept any of its triangles for the ray, at any distance > 0. Notation: u = 2^-24; the
+        // triangle as the test sees it is v0, v0 + e1, v0 + e2 with the STORED float edges; s = o - v0, q = d x e2, r = s x e1 and the
+        // exact det = e1 . q, n1 = s . q, n2 = d . r, nd = e2 . r, so that o + t d = v0 + b1 e1 + b2 e2 with t = nd / det, b1 = n1 / det,
+        // b2 = n2 / det exactly. Lmax: the longest side of any triangle of the bound; sigma >= |s| (|o - C| + R).
+        //  (1) Rounding of the test (ptmath.h dot = two fma over a product, cross = fma over a product, each correctly rounded; every
+        //      intermediate finite, meshEligible): |det_f - det| <= 9.1 u |e1||e2||d| <= eta = 12 u |d| Lmax^2, and the three
+        //      numerators are off by at most 10.2 u times the product of their factors' norms, bounded by 12 u |d| sigma Lmax
+        //      (n1, n2) and 12 u sigma Lmax^2 (nd). The camera-origin precomputes (primaryPrepKernel) are the same operations.
+        //  (2) Let D <= |det| be known. If D >= 4 eta then det_f = det (1 + theta), |theta| <= rho = eta / D <= 1/4: same sign.
+        //      inv = RN(1 / det_f) (rcp_in_range is the correctly rounded reciprocal on its range).
+        //      b1_f = RN(n1_f inv) "not < 0" means n1_f / det >= 0 (a negative product rounding to -0 is below 2^-148), so
+        //      b1 >= -d1 with d1 = 12 u |d| sigma Lmax / D; likewise b2 >= -d1. b0_f "not < 0" means RN(b1_f + b2_f) <= 1, so
+        //      b1_f + b2_f <= 1 + u, and b1 <= b1_f (1 + rho)(1 + 2.1 u) + d1: b0 = 1 - b1 - b2 >= -(1.01 rho + 3.2 u + 2 d1).
+        //      The negative parts of (b0, b1, b2) sum to at most 1.01 rho + 3.2 u + 4 d1, and a point whose weights sum to 1 with
+        //      negative parts summing to n lies within n Lmax of the triangle: X = o + t d is within
+        //      Lmax (1.01 rho + 3.2 u) + 48 u |d| sigma Lmax^2 / D of it.
+        //  (3) dist_f = RN(nd_f inv) > 0 means nd_f / det > 0, so t >= -12 u sigma Lmax^2 / D: the point o + max(t, 0) d of the
+        //      HALF line lies within 12 u |d| sigma Lmax^2 / D of X. (The limit `dist <= distance` is not used: any distance.)
+        //  So an accepted ray passes within infl = Lmax (4 u + 1.02 eta / D) + B sigma / D, B = 64 u |d| Lmax^2, of the ball.
+        //  (4) D: every unit normal lies in the double cone (a, alpha), so |det| = |d . (e1 x e2)| >= Nmin (|d . a| cos alpha -
+        //      |d| sin alpha); and an accepted triangle has |det_f| > 1e-7 (Primitives.h:41), so |det| >= 1e-7 - eta. D is the larger.
+        //      A direction for which D < 4 eta may graze a triangle so flatly that its computed weights say nothing about where it
+        //      passes: such a ray ENTERS the bound unconditionally — that is the |det|-dependent term the absolute epsilon needs.
+        //  (5) The kernel's float evaluation: |d| <= kDirNorm, 1 / |d|^2 <= kInvDir2 (the per-query unit-direction test), 2^-16
+        //      relative allowances on the squared distance, on sigma and on D, 2^-20 on the cone term (the axis rounded to float,
+        //      |d . a| rounded), 2^-10 on infl. Here, in double from the exact float inputs: C rounded to float and R measured from
+        //      it, rounded up; Nmin and cos alpha rounded down, Lmax, sin alpha and B up (ptmesh::buildBound).
+        // tests/test_mesh_bound.py pins the predicate on random, grazing (|det| swept down to 1e-7), shared-edge and far-origin rays,
+        // and shows that the same test fails for a bound with its inflation scaled down.
+        auto boundOf = [&](int first, int count, float4* rows) {
+            std::vector<float> tri((size_t)count * 9);
+            for (int k = 0; k < count; ++k) {
+                const ptss_triangle& t = s.triangles[triOrder[(size_t)(first + k)]];
+                const vec3 e1 = t.vertex1 - t.vertex0, e2 = t.vertex2 - t.vertex0;   // as stored
+                const float v[9] = {t.vertex0.x, t.vertex0.y, t.vertex0.z, e1.x, e1.y, e1.z, e2.x, e2.y, e2.z};
+                std::copy(v, v + 9, tri.begin() + 9 * k);
+            }
+            float b[12];
+            ptmesh::buildBound(tri.data(), count, b);
+            for (int r = 0; r < 3; ++r) rows[r] = float4{b[4 * r], b[4 * r + 1], b[4 * r + 2], b[4 * r + 3]};
+        };
+        constexpr int kGroupTris = ptss::kMeshLeaf * ptss::kMeshLeaf;
+        for (int k = 0; k < numLeaves; ++k)
+            boundOf(k * ptss::kMeshLeaf, std::min(ptss::kMeshLeaf, L.numTriangles - k * ptss::kMeshLeaf), &blob[(size_t)(L.mesh.offLeaf + 3 * k)]);
+        for (int g = 0; g < numGroups; ++g)
+            boundOf(g * kGroupTris, std::min(kGroupTris, L.numTriangles - g * kGroupTris), &blob[(size_t)(L.mesh.offGroup + 3 * g)]);
     }
     for (int i = 0; i < L.numMaterials; ++i) {
         const ptss_material& m = s.materials[i];
@@ -912,12 +1056,16 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
 
     // Scenes with many spheres get the chunked image (see accelEligible / packScene), and the plain one as images[1] for cameras
     // outside its range; cfg.everySphereLoop keeps the plain one only
+    // outside its range; cfg.everySphereLoop keeps the plain one only. Scenes of many triangles and few spheres get the mesh image
+    // (meshEligible), which serves every camera (a query outside its derivation walks every triangle); everySphereLoop keeps the
+    // reference's loop over every triangle for them too.
     const bool wantAccel = accelEligible(*scene) && !cfg->everySphereLoop;
+    const bool wantMesh = !wantAccel && meshEligible(*scene) && !cfg->everySphereLoop;
     const int numImages = wantAccel ? 2 : 1;
     std::vector<float4> blob[2];
     for (int i = 0; i < numImages; ++i) {
         SceneImage& im = c->images[i];
-        packScene(*scene, im.layout, blob[i], wantAccel && i == 0);
+        packScene(*scene, im.layout, blob[i], wantAccel && i == 0, wantMesh);
         // Scene access path: images that fit the default 64 KiB dynamic-LDS window are staged in LDS (north_star); larger ones
         // are read in place (wave-uniform scalar loads + per-lane gathers from global memory) — same kernel, same results, no
         // size limit. (On the 38-primitive "mixed" scene reading in place measured 16 % slower, profiles/README.md r01.)
@@ -983,6 +1131,7 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         // A bounded image runs the bounded or the unbounded frame kernel, as the camera is in range or not: both must fit.
         auto qualifies = [&](const SceneImage& im) {
             if (cfg->oneLaunchFrames <= 0 || numLanes != 1 || !im.inLds) return false;   // opt-in (include/ptss.h)
+            if (ptss::meshImage(im.layout)) return false;   // the mesh image has no frame kernel
             int perCU = ptss::frameOccupancyBlocksPerCU(im.layout, false);
             if (im.layout.sphereBounded) perCU = std::min(perCU, ptss::frameOccupancyBlocksPerCU(im.layout, true));
             const int resident = perCU - 1;
@@ -1296,6 +1445,13 @@ int ptss_frame_lanes(const ptss_context* c, int* out) {
 int ptss_launched_kernels(const ptss_context* c, unsigned long long* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     *out = c->launchedKernels;
+    return PTSS_OK;
+}
+
+int ptss_triangle_leaves(const ptss_context* c, int* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    const ptss::SceneLayout& L = c->image().layout;
+    *out = ptss::meshImage(L) ? L.mesh.numLeaves : 0;
     return PTSS_OK;
 }
 

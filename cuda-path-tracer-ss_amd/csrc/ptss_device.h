@@ -117,11 +117,29 @@ struct SceneLayout {
                         //    leaves out the products with that class's exact-zero edge components; the closest hit decides by the key
                         //    (distance, ~original index), which is what the reference's sequential `dist <= distance` rule ends on.
                         //    0: the caller's order, the general body, the sequential rule
-    uint32_t triClassPack[5];  // positions [begin(c), begin(c + 1)) hold the triangles of class code c = class(e1) * 4 + class(e2): the 17 begins
-                               // (begin(16) = T) as BYTES, four per word — five scalar registers instead of seventeen (classed scenes have
-                               // T <= 255); a loop header extracts its two bounds with two s_bfe (ptss_kernels.hip classBegin)
+    // Classed scenes (T <= 255) and mesh images (T >= 512) never coincide, so the two share these five words: the layout keeps
+    // its size and every field its offset (the kernels of the other images read the same kernel-argument words as before).
+    union {
+        uint32_t triClassPack[5];  // positions [begin(c), begin(c + 1)) hold the triangles of class code c = class(e1) * 4 + class(e2): the 17 begins
+                                   // (begin(16) = T) as BYTES, four per word — five scalar registers instead of seventeen (classed scenes have
+                                   // T <= 255); a loop header extracts its two bounds with two s_bfe (ptss_kernels.hip classBegin)
+        struct {
+            // Mesh image (packScene meshEligible): the triangles stored in a kd order of their centroids, every
+            // kMeshLeaf consecutive positions a LEAF and every kMeshLeaf^2 a GROUP, each with a conservative bound of three rows
+            // (ptmesh.h). numLeaves = 0: not a mesh image. The triangle tables (offTri, offTriNormal, offTriVert, offTriPos,
+            // offPrimTri) lie beyond ldsVec4: global memory, read through the kernels' `cold` pointer.
+            int numLeaves, numGroups;
+            int offGroup;   // numGroups x 3 rows, staged in LDS
+            int offLeaf;    // numLeaves x 3 rows: in LDS when offLeaf < ldsVec4, else in global memory
+            int reserved;
+        } mesh;
+    };
     int offTriPos;      // ints: stored position of each original triangle index
 };
+
+constexpr int kMeshLeaf = 16;   // triangles per leaf = leaves per group of the mesh image
+// the mesh image is in use (a classed image's byte table would alias mesh.numLeaves; classed scenes have T <= 255)
+__host__ __device__ inline bool meshImage(const SceneLayout& L) { return !L.triClassed && L.mesh.numLeaves > 0; }
 
 struct TileMap {
     int width, height;      // full frame

@@ -628,6 +628,7 @@ __device__ __forceinline__ uint32_t chunkMask(const float4* bounds, int cnt, vec
 }
 
 #include "ptss_diag.h"
+#include "ptmesh.h"
 
 // Candidate mask of ONE chunk for a lane that gathers its own rows (lanes sit in different chunks): visit i reads slot
 // i ^ (chunk mod kChunkSpheres), so that the 16-byte gathers of a wave spread over the LDS banks; verdicts enter through
@@ -974,8 +975,119 @@ __device__ __forceinline__ bool anySpheresHybrid(const float4* sc, const SceneLa
     return occluded;
 }
 
+// ---- The mesh image (SceneLayout::mesh; the bound: ptmesh.h, its derivation: ptss_api.hip packScene). The
+// triangles sit in a kd order of their centroids: every kMeshLeaf consecutive positions a leaf, every kMeshLeaf leaves a group,
+// each with a conservative bound. A wave-uniform pass over the group bounds (four per trip, verdicts through the carry as in
+// chunkMask) gives every lane the groups its ray may touch; each lane then walks ITS groups, tests their leaf bounds, and walks
+// its leaves' triangles (per-lane gathers from global memory) with the keyed general body: the order-free minimum of
+// (distance, 0xFFFFFFFE - original index) is what the reference's sequential `dist <= distance` rule ends on.
+// What the bound needs of a query, tested once per wave (its live lanes): |d|^2 within kMeshDirEps of 1, |o|^2 < 2^80 (finite). Together with the
+// image's |coordinate| <= 2^40 that also keeps |det| < 2^126 (the reciprocal's fast range) and e2 . r finite. A wave with
+// any other lane walks every triangle in the caller's order with the guarded test (closestHit's last loop).
+__device__ __forceinline__ bool meshQueryOk(vec3 o, vec3 d, bool live) {   // (lanes without a query do not count)
+    return waveAll(!live || (ptm::abs(dot(d, d) - 1.0f) <= ptmesh::kMeshDirEps && dot(o, o) < 0x1p80f));
+}
+__device__ __forceinline__ bool meshMay(const float4* b, vec3 o, vec3 d) {
+    const float4 r0 = loadRow16(b), r1 = loadRow16(b + 1), r2 = loadRow16(b + 2);
+    return ptmesh::mayTouch(xyz(r0), r0.w, xyz(r1), r1.w, r2.x, r2.y, r2.z, r2.w, o, d, 1.0f);
+}
+// bit k = "the ray may touch group g0 + k", k < cnt <= 32 (the host pads the group rows to a multiple of four bounds)
+__device__ __forceinline__ uint32_t meshGroupMask(const float4* groups, int cnt, vec3 o, vec3 d) {
+    const int trips = (cnt + 3) >> 2;
+    uint32_t rev = 0;
+    for (int g = 0; g < trips; ++g) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned long long may = maskOf(meshMay(groups + 3 * (4 * g + k), o, d));
+            asm("v_addc_co_u32 %0, vcc, %0, %0, %1" : "+v"(rev) : "s"(may) : "vcc");
+        }
+    }
+    return (__builtin_bitreverse32(rev) >> (32 - 4 * trips)) & lowBits(cnt);
+}
+// bit j = "the ray may touch leaf kMeshLeaf * g + j" (per lane: lanes sit in different groups)
+__device__ __forceinline__ uint32_t meshLeafMask(const float4* leaves, int g, int numLeaves, vec3 o, vec3 d) {
+    const int first = g * kMeshLeaf;
+    const int cnt = numLeaves - first < kMeshLeaf ? numLeaves - first : kMeshLeaf;
+    uint32_t m = 0;
+    for (int j = 0; j < cnt; ++j) m |= meshMay(leaves + 3 * (first + j), o, d) ? (1u << j) : 0u;
+    return m;
+}
+__device__ __forceinline__ const float4* meshLeaves(const float4* sc, const float4* cold, const SceneLayout& L) {
+    return (L.mesh.offLeaf < L.ldsVec4 ? sc : cold) + L.mesh.offLeaf;   // staged when they fit (packScene)
+}
+template <bool kPrimary>
+__device__ __forceinline__ void closestTrianglesMesh(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, bool live,
+                                                     TriBest& best) {
+    const float4* leaves = meshLeaves(sc, cold, L);
+    for (int g0 = 0; g0 < L.mesh.numGroups; g0 += 32) {
+        const int left = L.mesh.numGroups - g0;   // wave-uniform
+        uint32_t groups = meshGroupMask(sc + L.mesh.offGroup + 3 * g0, left < 32 ? left : 32, o, d);
+        if (!live) groups = 0u;
+        while (groups != 0u) {
+            const int g = g0 + __builtin_ctz(groups);
+            groups &= groups - 1u;
+            uint32_t leafBits = meshLeafMask(leaves, g, L.mesh.numLeaves, o, d);
+            while (leafBits != 0u) {
+                const int t0 = (g * kMeshLeaf + __builtin_ctz(leafBits)) * kMeshLeaf;
+                leafBits &= leafBits - 1u;
+                const int t1 = L.numTriangles - t0 < kMeshLeaf ? L.numTriangles : t0 + kMeshLeaf;
+                for (int t = t0; t < t1; ++t)
+                    triangleClassed<kPrimary, 0, 0, true>(cold + L.offTri + 3 * t, cold + L.offPrimTri + 2 * t, 0u, o, d, ~0ull, best);
+            }
+        }
+    }
+}
+// the triangle half of lineOfSight on the mesh image: the same two levels against the segment, each lane stopping at its first
+// blocker (an OR over independent tests: any order); outside the derivation's domain, every triangle with the guarded test
+__device__ __forceinline__ bool anyTrianglesMesh(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, float limit, bool live) {
+    if (!meshQueryOk(o, d, live)) {
+        unsigned long long need = maskOf(live), blocked = 0ull;
+        for (int i = 0; i < L.numTriangles; ++i) {
+            if (need == 0ull) break;
+            const TriHit th = triangleTest(loadTri(cold + L.offTri + 3 * i), o, d, limit, need);
+            blocked |= th.hitMask;
+            need &= ~th.hitMask;
+        }
+        return __builtin_amdgcn_inverse_ballot_w64(blocked);
+    }
+    const float4* leaves = meshLeaves(sc, cold, L);
+    bool blocked = false;
+    for (int g0 = 0; g0 < L.mesh.numGroups; g0 += 32) {
+        if (!waveAny(live && !blocked)) break;
+        const int left = L.mesh.numGroups - g0;
+        uint32_t groups = meshGroupMask(sc + L.mesh.offGroup + 3 * g0, left < 32 ? left : 32, o, d);
+        if (!live || blocked) groups = 0u;
+        while (groups != 0u) {
+            const int g = g0 + __builtin_ctz(groups);
+            groups &= groups - 1u;
+            uint32_t leafBits = meshLeafMask(leaves, g, L.mesh.numLeaves, o, d);
+            while (leafBits != 0u) {
+                const int t0 = (g * kMeshLeaf + __builtin_ctz(leafBits)) * kMeshLeaf;
+                leafBits &= leafBits - 1u;
+                const int t1 = L.numTriangles - t0 < kMeshLeaf ? L.numTriangles : t0 + kMeshLeaf;
+                for (int t = t0; t < t1; ++t) {
+                    const float4* r = cold + L.offTri + 3 * t;
+                    const pttri::Head hh = pttri::head<0, 0, false>(xyz(loadRow16(r)), xyz(loadRow16(r + 1)), xyz(loadRow16(r + 2)), v3(0, 0, 0),
+                                                                    v3(0, 0, 0), 0.0f, o, d);
+                    if (pttri::passesHead(hh, limit)) {
+                        float b0, b1, b2;
+                        pttri::weights<0, 0>(hh, d, b0, b1, b2);
+                        if (pttri::passesWeights(b0, b1, b2)) {
+                            blocked = true;
+                            break;
+                        }
+                    }
+                }
+                if (blocked) leafBits = 0u;
+            }
+            if (blocked) groups = 0u;
+        }
+    }
+    return blocked;
+}
+
 // the triangle half of lineOfSight alone (the sphere half having been answered by anySpheresHybrid)
-template <bool kPrimary, bool kAccel, bool kBounded>
+template <bool kPrimary, bool kAccel, bool kBounded, bool kMesh = false>
 __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, bool live, uint32_t* ws) {
     Hit h;
     h.distance = ptm::inf();
@@ -1002,7 +1114,22 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
         }
     }
     const unsigned long long liveMask = maskOf(live);
-    if (L.triClassed) {
+    if constexpr (kMesh) {
+        if (meshQueryOk(o, d, live)) {
+            // (the general body throughout: its weights are the reference's, so no zero-weight re-evaluation is needed)
+            TriBest best{h.distance, kNoTriangle, 0.0f, 0.0f};
+            closestTrianglesMesh<kPrimary>(sc, cold, L, o, d, live, best);
+            if (best.key != kNoTriangle) {
+                h.distance = best.dist;
+                h.kind = 2;
+                h.idx = reinterpret_cast<const int*>(cold + L.offTriPos)[0xfffffffeu - best.key];   // per-lane gather
+                h.w1 = best.w1;
+                h.w2 = best.w2;
+                h.w0 = 1.0f - (best.w1 + best.w2);  // Primitives.h:64, from the kept pair
+            }
+            return h;
+        }
+    } else if (L.triClassed) {
         // The triangles are stored grouped by edge class. One test per query (not per triangle) admits the class bodies:
         // |d|^2 < 2^30 bounds |det| below the reciprocal's fast range, and with a finite origin every product the class
         // forms leave out is an exact zero (pttri.h). A wave that fails it (a NaN or enormous ray) walks the triangles in the
@@ -1056,11 +1183,12 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
         }
         return h;
     }
-    const int* posOfOriginal = reinterpret_cast<const int*>(sc + L.offTriPos);
+    const float4* td = kMesh ? cold : sc;   // the triangle tables (global memory in the mesh image)
+    const int* posOfOriginal = reinterpret_cast<const int*>(td + L.offTriPos);
     for (int k = 0; k < L.numTriangles; ++k) {   // the guarded loop, in the caller's order: unbounded edges, or a ray of enormous length
-        const int i = L.triClassed ? posOfOriginal[k] : k;   // where original triangle k is stored
-        const TriRows tcur = kPrimary ? loadTriEdges(sc + L.offTri + 3 * i) : loadTri(sc + L.offTri + 3 * i);
-        const TriHit th = kPrimary ? triangleTestPrimary(tcur, sc[L.offPrimTri + 2 * i], loadRow16(sc + L.offPrimTri + 2 * i + 1), d,
+        const int i = (kMesh || L.triClassed) ? posOfOriginal[k] : k;   // where original triangle k is stored
+        const TriRows tcur = kPrimary ? loadTriEdges(td + L.offTri + 3 * i) : loadTri(td + L.offTri + 3 * i);
+        const TriHit th = kPrimary ? triangleTestPrimary(tcur, td[L.offPrimTri + 2 * i], loadRow16(td + L.offPrimTri + 2 * i + 1), d,
                                                          h.distance, liveMask)
                                    : triangleTest(tcur, o, d, h.distance, liveMask);
         if (th.hit) {
@@ -1107,9 +1235,9 @@ __device__ __forceinline__ bool anyTriangles(const float4* sc, const SceneLayout
 // ---- the any-hit loops of lineOfSight, CudaTracer.cu:437-452: true when some primitive blocks the
 // segment. Order-independent (the reference returns at the first accepted primitive and no test
 // depends on another). `live`: this lane carries a segment. -----------------------------------------
-template <bool kAccel, bool kBounded>
+template <bool kAccel, bool kBounded, bool kMesh = false>
 __device__ __forceinline__ bool anyHit(const float4* sc, const SceneLayout& L, vec3 lo, vec3 w_i, float distance,
-                                       bool live) {
+                                       bool live, const float4* cold = nullptr) {
     bool occluded = false;
     if constexpr (kAccel) occluded = anySphereChunked(sc, L, lo, w_i, distance, live);
     for (int base = 0; base < (kAccel ? 0 : L.numSpheres); base += 32) {
@@ -1127,6 +1255,7 @@ __device__ __forceinline__ bool anyHit(const float4* sc, const SceneLayout& L, v
             }
         }
     }
+    if constexpr (kMesh) return anyTrianglesMesh(sc, cold, L, lo, w_i, distance, live && !occluded) || occluded;
     unsigned long long need = maskOf(live) & ~maskOf(occluded);  // lanes that still want an answer
     unsigned long long blocked = 0ull;
     anyTriangleLoop(sc, L, lo, w_i, distance, need, blocked);
@@ -1702,7 +1831,7 @@ struct TileEnv {
 
 // One tile = kBlock rays of bounce env.bounce, starting at slot / frame-tile offset `base` of the shard. kCoherentIo: the ray
 // pools are read and written past the L1 (ldPlane<true>): other workgroups of the SAME launch produced / will consume them.
-template <bool kLast, bool kFirst, bool kAccel, bool kBounded, bool kPairs, bool kCoherentIo>
+template <bool kLast, bool kFirst, bool kAccel, bool kBounded, bool kPairs, bool kCoherentIo, bool kMesh = false>
 __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLayout& L, const TileMap& tile, const EyeParams& eye, const TileEnv& env,
                                            uint32_t base) {
     const float4* sc = env.sc;
@@ -1758,12 +1887,13 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
         h.kind = 2; h.idx = (int)(pixOf(ray.pix) % (uint32_t)L.numTriangles); h.distance = 1.0f + ray.d.x;
         h.w0 = 0.3f; h.w1 = 0.3f; h.w2 = 0.4f;
 #else
-        const Hit h = closestHit<kFirst, kAccel, kBounded>(sc, sceneBlob, L, ray.o, ray.d, valid, reinterpret_cast<uint32_t*>(wq));
+        const Hit h = closestHit<kFirst, kAccel, kBounded, kMesh>(sc, sceneBlob, L, ray.o, ray.d, valid, reinterpret_cast<uint32_t*>(wq));
 #endif
         const bool hit = valid && h.kind != 0;
         if constexpr (!kFirst) {
             if (valid) loadRayRng<kCoherentIo>(tileBlock(in, base), threadIdx.x, ray);
         }
+        const float4* td = kMesh ? sceneBlob : sc;   // the triangle tables (global memory in the mesh image)
         vec3 point = v3(0, 0, 0), normal = v3(0, 0, 0);
         float cosI = 0;
         int materialIdx = 0;
@@ -1773,9 +1903,9 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                 normal = normalize(point - xyz(loadRow16(sc + L.offSphere + h.idx)));
                 materialIdx = reinterpret_cast<const int*>((kAccel ? sceneBlob : sc) + L.offSphereMat)[h.idx];
             } else {
-                const float4* nn = sc + L.offTriNormal + 3 * h.idx;
+                const float4* nn = td + L.offTriNormal + 3 * h.idx;
                 normal = (xyz(loadRow16(nn)) * h.w0 + xyz(loadRow16(nn + 1)) * h.w1) + xyz(loadRow16(nn + 2)) * h.w2;
-                materialIdx = (int)asU(sc[L.offTri + 3 * h.idx].w);
+                materialIdx = (int)asU(td[L.offTri + 3 * h.idx].w);
             }
             cosI = dot(-ray.d, normal);
         }
@@ -1815,9 +1945,9 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                         const float weight0 = u1 * inverseTotal, weight1 = u2 * inverseTotal, weight2 = u3 * inverseTotal;
                         // triangleIdx or triangleIdx + 1, :408 — as stored positions (the triangles may be stored grouped by class)
                         const int tri = (ptrng::uniform(ray.rng) > .5f) ? (int)asU(light.w) : (int)asU(sc[L.offAreaLight + 2 * (li - L.numPointLights) + 1].x);
-                        const vec3 a = xyz(loadRow16(sc + L.offTri + 3 * tri));
-                        const vec3 b = xyz(loadRow16(sc + L.offTriVert + 2 * tri));
-                        const vec3 c = xyz(loadRow16(sc + L.offTriVert + 2 * tri + 1));
+                        const vec3 a = xyz(loadRow16(td + L.offTri + 3 * tri));
+                        const vec3 b = xyz(loadRow16(td + L.offTriVert + 2 * tri));
+                        const vec3 c = xyz(loadRow16(td + L.offTriVert + 2 * tri + 1));
                         lightPoint = (a * weight0 + b * weight1) + c * weight2;
                     }
                     // head of lineOfSight :423-432
@@ -1919,7 +2049,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                 const uint32_t rem = queued - e0;
                 const uint32_t units = (rem + 7u) >> 3;  // of 8 segments
                 // (the chunked sphere traversal is per lane already: those scenes take dense passes only)
-                const int chunkLog = (units >= 7u || kAccel) ? 6 : (units >= 4u ? 5 : (units >= 2u ? 4 : 3));
+                const int chunkLog = (units >= 7u || kAccel || kMesh) ? 6 : (units >= 4u ? 5 : (units >= 2u ? 4 : 3));
                 const int shift = 6 - chunkLog;                      // lanes per segment = 1 << shift
                 const uint32_t mine = lane >> shift;                 // this lane's segment within the chunk
                 const uint32_t sub = lane & ((1u << shift) - 1u);    // its share of the primitive list
@@ -1933,7 +2063,8 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                     occ = anySpheresHybrid(sc, L, wq + e0, wq + (e0 == 0u ? 64 : 0), lo, wi, reach, have);
                     occ = occ || anyTriangles(sc, L, lo, wi, reach, have && !occ);
                 } else {
-                    occ = (shift == 0) ? anyHit<kAccel, kBounded>(sc, L, lo, wi, reach, have) : anyHitSplit<kBounded>(sc, L, lo, wi, reach, have, shift, (int)sub);
+                    occ = (shift == 0) ? anyHit<kAccel, kBounded, kMesh>(sc, L, lo, wi, reach, have, sceneBlob)
+                                       : anyHitSplit<kBounded>(sc, L, lo, wi, reach, have, shift, (int)sub);
                 }
                 const unsigned long long verdicts = __ballot(occ);  // all lanes vote before anyone branches
                 const unsigned long long group = ((1ull << (1u << shift)) - 1ull) << (mine << shift);
@@ -2010,7 +2141,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
     }
 }
 
-template <bool kLast, bool kSceneInLds, bool kFirst, bool kAccel, bool kBounded, bool kPairsWanted>
+template <bool kLast, bool kSceneInLds, bool kFirst, bool kAccel, bool kBounded, bool kPairsWanted, bool kMesh>
 __device__ __forceinline__ void bounceBody(const FrameBuffers& fb, const float4* __restrict__ sceneBlob, const SceneLayout& L, int bounce,
                                            const TileMap& tile, const EyeParams& eye) {
     extern __shared__ __attribute__((aligned(256))) float4 lds[];
@@ -2058,14 +2189,14 @@ __device__ __forceinline__ void bounceBody(const FrameBuffers& fb, const float4*
     const uint32_t roundsOfShard = (fb.firstTiles + kShards - 1 - shard) / kShards;
     const uint32_t span = kFirst ? ((roundsOfShard + fb.laneCount - 1 - fb.laneIndex) / fb.laneCount) * kBlock : n;
     for (uint32_t base = (blockIdx.x / kShards) * kBlock; base < span; base += (gridDim.x / kShards) * kBlock) {
-        bounceTile<kLast, kFirst, kAccel, kBounded, kPairs, false>(fb, L, tile, eye, env, base);
+        bounceTile<kLast, kFirst, kAccel, kBounded, kPairs, false, kMesh>(fb, L, tile, eye, env, base);
     }
 }
 
-template <bool kLast, bool kSceneInLds, bool kFirst, bool kAccel, bool kBounded, bool kPairs>
-__global__ __launch_bounds__(kBlock, kAccel ? 4 : (kFirst ? PTSS_MINWAVES_FIRST : (kBounded ? PTSS_MINWAVES_BOUNDED : PTSS_MINWAVES))) void bounceKernel(  // chunked scenes: their LDS image (21 KB + the work area) admits four workgroups per CU, so four waves per SIMD = 128 registers cost nothing (round 3: 5 -> 4, no scratch, c5 +2.8 %)
+template <bool kLast, bool kSceneInLds, bool kFirst, bool kAccel, bool kBounded, bool kPairs, bool kMesh>
+__global__ __launch_bounds__(kBlock, (kAccel || kMesh) ? 4 : (kFirst ? PTSS_MINWAVES_FIRST : (kBounded ? PTSS_MINWAVES_BOUNDED : PTSS_MINWAVES))) void bounceKernel(  // chunked scenes: their LDS image (21 KB + the work area) admits four workgroups per CU, so four waves per SIMD = 128 registers cost nothing (round 3: 5 -> 4, no scratch, c5 +2.8 %)
     FrameBuffers fb, const float4* __restrict__ sceneBlob, SceneLayout L, int bounce, TileMap tile, EyeParams eye) {
-    bounceBody<kLast, kSceneInLds, kFirst, kAccel, kBounded, kPairs>(fb, sceneBlob, L, bounce, tile, eye);
+    bounceBody<kLast, kSceneInLds, kFirst, kAccel, kBounded, kPairs, kMesh>(fb, sceneBlob, L, bounce, tile, eye);
     // frame lanes: "this workgroup of bounce `bounce` has ended" (every workgroup, also one that had nothing to do) — the
     // peers' loop guard of bounce + 1 waits for the whole grid (frameLiveCount). The survivor counters were raised by
     // returning device-scope atomics, so they have been performed when a wave gets here, and the barrier collects the
@@ -2367,13 +2498,17 @@ size_t bounceLdsBytes(const SceneLayout& layout, bool sceneInLds) {
     return ((sceneInLds ? (size_t)layout.ldsVec4 : 0) + kBlockLdsVec4) * sizeof(float4);
 }
 
-// ---- which instantiation runs: four scene variants, each one {kAccel, kBounded, kPairs} of bounceKernel and frameKernel.
+// ---- which instantiation runs: five scene variants, each one {kAccel, kBounded, kPairs, kMesh} of bounceKernel, the first four
+// also of frameKernel (the mesh image has none: ptss_create never qualifies it for one launch per frame).
 // sceneVariant is the one place that decides; every launch and occupancy query below looks its kernel up through it.
-enum SceneVariant : int { kVariantAccel, kVariantBoundedPairs, kVariantBounded, kVariantPlain, kNumVariants };
-constexpr bool kVariantArgs[kNumVariants][3] = {{true, false, false}, {false, true, true}, {false, true, false}, {false, false, false}};
+enum SceneVariant : int { kVariantAccel, kVariantBoundedPairs, kVariantBounded, kVariantPlain, kVariantMesh, kNumVariants };
+constexpr int kNumFrameVariants = kVariantMesh;
+constexpr bool kVariantArgs[kNumVariants][4] = {{true, false, false, false}, {false, true, true, false}, {false, true, false, false},
+                                                {false, false, false, false}, {false, false, false, true}};
 
 // bounded: the frame may take the shorter sphere test (SceneLayout::sphereBounded and a camera in range, ptss_api.hip)
 static SceneVariant sceneVariant(const SceneLayout& layout, bool bounded) {
+    if (meshImage(layout)) return kVariantMesh;   // (the reference's sphere test: one image for every camera)
     if (layout.accelSpheres) return kVariantAccel;
     if (bounded && layout.neePairs) return kVariantBoundedPairs;
     return bounded ? kVariantBounded : kVariantPlain;
@@ -2383,7 +2518,8 @@ using KernelFn = void (*)(FrameBuffers, const float4*, SceneLayout, int, TileMap
 
 template <size_t... I>   // entry I = variant * 8 + kLast * 4 + kSceneInLds * 2 + kFirst
 constexpr std::array<KernelFn, sizeof...(I)> bounceTable(std::index_sequence<I...>) {
-    return {{bounceKernel<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, kVariantArgs[I / 8][0], kVariantArgs[I / 8][1], kVariantArgs[I / 8][2]>...}};
+    return {{bounceKernel<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0, kVariantArgs[I / 8][0], kVariantArgs[I / 8][1], kVariantArgs[I / 8][2],
+                          kVariantArgs[I / 8][3]>...}};
 }
 template <size_t... V>
 constexpr std::array<KernelFn, sizeof...(V)> frameTable(std::index_sequence<V...>) {
@@ -2395,36 +2531,39 @@ static KernelFn bounceKernelFor(int index) {
     return table[index];
 }
 static KernelFn frameKernelFor(SceneVariant v) {
-    static constexpr auto table = frameTable(std::make_index_sequence<kNumVariants>{});
-    return table[v];
+    static constexpr auto table = frameTable(std::make_index_sequence<kNumFrameVariants>{});
+    return v < kNumFrameVariants ? table[v] : nullptr;
 }
 static int blocksPerCU(KernelFn k, size_t lds) {
     int a = 0;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k, kBlock, lds) == hipSuccess ? a : 0;
 }
 
-// *launched collects bit `bounceTable index` / `32 + variant` of every instantiation enqueued (ptss_launched_kernels)
+// *launched collects bit `bounceTable index` (the mesh variant's eight: 40 + ..., above the frame kernels' 32 + variant) / `32 + variant`
+// of every instantiation enqueued (ptss_launched_kernels)
 hipError_t launchBounce(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int bounce,
                         bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye, unsigned long long* launched) {
     const int index = bounceIndex(sceneVariant(layout, bounded), isLast, sceneInLds, bounce == 0);
     hipLaunchKernelGGL(bounceKernelFor(index), dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, sceneInLds), st, fb, sceneBlob, layout, bounce,
                        tile, eye);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << index;
+    if (e == hipSuccess) *launched |= 1ull << (index < kVariantMesh * 8 ? index : index + 8);
     return e;
 }
 
 hipError_t launchFrame(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int numBounces, bool bounded, int gridBlocks,
                        TileMap tile, EyeParams eye, unsigned long long* launched) {
     const SceneVariant v = sceneVariant(layout, bounded);
+    if (!frameKernelFor(v)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(frameKernelFor(v), dim3(gridBlocks), dim3(kBlock), bounceLdsBytes(layout, true), st, fb, sceneBlob, layout, numBounces, tile, eye);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << (kNumVariants * 8 + v);
+    if (e == hipSuccess) *launched |= 1ull << (kVariantMesh * 8 + v);
     return e;
 }
 // resident workgroups per CU of the frame kernel `layout` would run (the API's answer; the caller keeps one in reserve)
 int frameOccupancyBlocksPerCU(const SceneLayout& layout, bool bounded) {
-    return blocksPerCU(frameKernelFor(sceneVariant(layout, bounded)), bounceLdsBytes(layout, true));
+    const KernelFn k = frameKernelFor(sceneVariant(layout, bounded));
+    return k ? blocksPerCU(k, bounceLdsBytes(layout, true)) : 0;
 }
 
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets) {

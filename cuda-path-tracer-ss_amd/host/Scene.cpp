@@ -4,6 +4,14 @@
 // cited per block; the code that assembles them is this repo's own.
 #include "Scene.h"
 
+#include <cerrno>
+#include <cmath>
+#include <cstdlib>
+#include <fstream>
+#include <array>
+#include <map>
+#include <sstream>
+
 namespace {
 
 const vec3 kAxisX = {1, 0, 0};
@@ -262,6 +270,10 @@ bool Scene::buildPreset(const std::string& preset) {
         materialsVec.push_back(Material(v3(1.0f, 0.0f, 0.0f), 0.35f, v3(1.0f), 250, 0.6f, 2.5f));
         addSphereField(1024, 3.6f, -1.5f, -7.7f, 0.05f, 0.22f);
         addCornellBox(8);
+    } else if (name == "mesh") {  // a model instead of the two spheres: a level-4 icosphere (5,120 triangles) in Cook-Torrance
+        addCornellBox(8);
+        materialsVec.push_back(cookTorrance(v3(0.9f, 0.6f, 0.2f), v3(1.0f, 0.8f, 0.4f), 0.2f));
+        addIcosphere(v3(0.5f, -2.5f, -5.5f), 1.5f, 4, (int)materialsVec.size() - 1);
     } else if (name == "pointlight") {  // §8f-3: the commented-out point lights of Scene.cpp:21-22
         addDefinedSpheres(4);
         addCornellBox(8);
@@ -289,4 +301,185 @@ ptss_scene_desc Scene::desc(vec3 defaultColor) const {
     d.numAreaLights = areaLightsVec.size();
     d.defaultColor = defaultColor;
     return d;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Meshes (not in the reference, whose README names OBJ support as its next feature).
+// ------------------------------------------------------------------------------------------------
+
+namespace {
+
+bool parseFloat(const std::string& tok, float& out) {
+    if (tok.empty()) return false;
+    const char* b = tok.c_str();
+    char* e = nullptr;
+    errno = 0;
+    const float v = std::strtof(b, &e);
+    if (e != b + tok.size() || !std::isfinite(v)) return false;
+    out = v;
+    return true;
+}
+
+// an OBJ index: 1-based, or negative = relative to the `count` elements read so far; false if malformed or out of range
+bool parseIndex(const std::string& tok, size_t count, size_t& out) {
+    if (tok.empty()) return false;
+    const char* b = tok.c_str();
+    char* e = nullptr;
+    errno = 0;
+    const long long v = std::strtoll(b, &e, 10);
+    if (e != b + tok.size() || errno != 0 || v == 0) return false;
+    const long long idx = v > 0 ? v - 1 : (long long)count + v;
+    if (idx < 0 || idx >= (long long)count) return false;
+    out = (size_t)idx;
+    return true;
+}
+
+vec3 transformPoint(const mat4& m, vec3 p) {
+    const vec4 q = m * vec4{p.x, p.y, p.z, 1.0f};
+    return v3(q.x, q.y, q.z);
+}
+
+vec3 safeNormalize(vec3 n) {   // a degenerate face keeps a zero normal instead of NaNs
+    const float len2 = ptv::dot(n, n);
+    return len2 > 0.0f ? ptv::normalize(n) : v3(0, 0, 0);
+}
+
+}  // namespace
+
+long Scene::addObjText(const std::string& text, mat4 transformation, int materialIdx, std::string* error) {
+    using namespace ptv;
+    std::vector<vec3> positions, normals;
+    size_t texcoords = 0;
+    std::vector<Triangle> added;
+    const mat4 normalMatrix = inverse(transpose(transformation));
+    std::istringstream lines(text);
+    std::string line;
+    size_t lineNo = 0;
+    auto fail = [&](const std::string& why) -> long {
+        if (error) *error = "line " + std::to_string(lineNo) + ": " + why;
+        return -1;
+    };
+    while (std::getline(lines, line)) {
+        ++lineNo;
+        if (!line.empty() && line.back() == '\r') line.pop_back();   // CRLF files
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        std::istringstream words(line);
+        std::string key;
+        if (!(words >> key)) continue;   // blank or comment
+        std::vector<std::string> args;
+        for (std::string w; words >> w;) args.push_back(w);
+        if (key == "v" || key == "vn") {
+            // v x y z [w] (w is ignored: no rational curves here); vn x y z
+            if (args.size() < 3 || args.size() > (key == "v" ? 4u : 3u)) return fail("expected three coordinates after '" + key + "'");
+            float c[4];
+            for (size_t k = 0; k < args.size(); ++k)
+                if (!parseFloat(args[k], c[k])) return fail("not a finite number: '" + args[k] + "'");
+            (key == "v" ? positions : normals).push_back(v3(c[0], c[1], c[2]));
+        } else if (key == "vt") {
+            ++texcoords;   // counted so that a face's texture indices can be range-checked; the coordinates are not used
+        } else if (key == "f") {
+            if (args.size() < 3) return fail("a face needs at least three vertices");
+            std::vector<size_t> vi(args.size()), ni(args.size());
+            bool allNormals = true;
+            for (size_t k = 0; k < args.size(); ++k) {
+                // i, i/j, i//k, i/j/k
+                const std::string& a = args[k];
+                const size_t s1 = a.find('/');
+                const size_t s2 = s1 == std::string::npos ? std::string::npos : a.find('/', s1 + 1);
+                if (s2 != std::string::npos && a.find('/', s2 + 1) != std::string::npos) return fail("bad face vertex '" + a + "'");
+                if (!parseIndex(a.substr(0, s1), positions.size(), vi[k])) return fail("vertex index out of range or malformed in '" + a + "'");
+                if (s1 != std::string::npos) {
+                    const std::string t = a.substr(s1 + 1, s2 == std::string::npos ? std::string::npos : s2 - s1 - 1);
+                    size_t unused;
+                    if (!(t.empty() && s2 != std::string::npos) && !parseIndex(t, texcoords, unused))
+                        return fail("texture index out of range or malformed in '" + a + "'");
+                }
+                if (s2 != std::string::npos) {
+                    if (!parseIndex(a.substr(s2 + 1), normals.size(), ni[k])) return fail("normal index out of range or malformed in '" + a + "'");
+                } else {
+                    allNormals = false;
+                }
+            }
+            for (size_t k = 1; k + 1 < args.size(); ++k) {   // fan: (0, k, k + 1)
+                const size_t c[3] = {0, k, k + 1};
+                vec3 p[3], n[3];
+                for (int j = 0; j < 3; ++j) p[j] = transformPoint(transformation, positions[vi[c[j]]]);
+                if (allNormals) {
+                    for (int j = 0; j < 3; ++j) {
+                        const vec3 m = normals[ni[c[j]]];
+                        const vec4 q = normalMatrix * vec4{m.x, m.y, m.z, 0.0f};
+                        n[j] = safeNormalize(v3(q.x, q.y, q.z));
+                    }
+                } else {
+                    n[0] = n[1] = n[2] = safeNormalize(ptv::cross(p[1] - p[0], p[2] - p[0]));
+                }
+                added.push_back(Triangle(p[0], p[1], p[2], n[0], n[1], n[2], materialIdx));
+            }
+        } else if (key == "o" || key == "g" || key == "s" || key == "usemtl" || key == "mtllib") {
+            // grouping, smoothing and material statements: the whole model wears materialIdx
+        } else {
+            return fail("unsupported statement '" + key + "'");
+        }
+    }
+    trianglesVec.insert(trianglesVec.end(), added.begin(), added.end());
+    return (long)added.size();
+}
+
+long Scene::addObjModel(const std::string& path, mat4 transformation, int materialIdx, std::string* error) {
+    std::ifstream in(path, std::ios::binary);
+    if (!in) {
+        if (error) *error = "cannot open " + path;
+        return -2;
+    }
+    std::ostringstream text;
+    text << in.rdbuf();
+    if (in.bad()) {
+        if (error) *error = "cannot read " + path;
+        return -2;
+    }
+    return addObjText(text.str(), transformation, materialIdx, error);
+}
+
+void Scene::addIcosphere(vec3 centre, float radius, int level, int materialIdx) {
+    using namespace ptv;
+    const double g = (1 + std::sqrt(5.0)) / 2;
+    std::vector<std::array<double, 3>> verts = {{-1, g, 0}, {1, g, 0}, {-1, -g, 0}, {1, -g, 0}, {0, -1, g}, {0, 1, g},
+                                                {0, -1, -g}, {0, 1, -g}, {g, 0, -1}, {g, 0, 1}, {-g, 0, -1}, {-g, 0, 1}};
+    std::vector<std::array<int, 3>> faces = {{0, 11, 5}, {0, 5, 1}, {0, 1, 7}, {0, 7, 10}, {0, 10, 11}, {1, 5, 9}, {5, 11, 4},
+                                             {11, 10, 2}, {10, 7, 6}, {7, 1, 8}, {3, 9, 4}, {3, 4, 2}, {3, 2, 6}, {3, 6, 8},
+                                             {3, 8, 9}, {4, 9, 5}, {2, 4, 11}, {6, 2, 10}, {8, 6, 7}, {9, 8, 1}};
+    auto unit = [](std::array<double, 3> p) {
+        const double l = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+        return std::array<double, 3>{p[0] / l, p[1] / l, p[2] / l};
+    };
+    for (auto& v : verts) v = unit(v);
+    for (int l = 0; l < level; ++l) {
+        std::map<std::pair<int, int>, int> mid;   // one midpoint per edge, so that neighbours share their vertices exactly
+        auto midpoint = [&](int a, int b) {
+            const std::pair<int, int> key(a < b ? a : b, a < b ? b : a);
+            auto it = mid.find(key);
+            if (it != mid.end()) return it->second;
+            const auto& p = verts[(size_t)key.first];
+            const auto& q = verts[(size_t)key.second];
+            verts.push_back(unit({p[0] + q[0], p[1] + q[1], p[2] + q[2]}));
+            return mid[key] = (int)verts.size() - 1;
+        };
+        std::vector<std::array<int, 3>> next;
+        for (const auto& f : faces) {
+            const int a = midpoint(f[0], f[1]), b = midpoint(f[1], f[2]), c = midpoint(f[2], f[0]);
+            next.push_back({f[0], a, c});
+            next.push_back({f[1], b, a});
+            next.push_back({f[2], c, b});
+            next.push_back({a, b, c});
+        }
+        faces.swap(next);
+    }
+    std::vector<vec3> pos(verts.size()), nrm(verts.size());
+    for (size_t i = 0; i < verts.size(); ++i) {
+        nrm[i] = v3((float)verts[i][0], (float)verts[i][1], (float)verts[i][2]);
+        pos[i] = centre + nrm[i] * radius;
+    }
+    for (const auto& f : faces)
+        trianglesVec.push_back(Triangle(pos[(size_t)f[0]], pos[(size_t)f[1]], pos[(size_t)f[2]], nrm[(size_t)f[0]], nrm[(size_t)f[1]], nrm[(size_t)f[2]], materialIdx));
 }

@@ -40,6 +40,17 @@ public:
     void makeLambertOnly();
     ptss_scene_desc desc(vec3 defaultColor = v3(0)) const;
 
+    // A Wavefront OBJ model (v, vn, f; every face fan-triangulated) placed with `transformation`, as addRectangularModel places
+    // its square: positions by the matrix, normals by its inverse transpose; a face without normals gets its face normal on all
+    // three vertices. The whole model wears materialIdx. Returns the number of triangles added, or -1 for a malformed line or an
+    // index out of range, -2 for a file that cannot be read; on error the scene is left unchanged and *error says why.
+    long addObjModel(const std::string& path, mat4 transformation, int materialIdx, std::string* error = nullptr);
+    // ... the same from the text of a file
+    long addObjText(const std::string& text, mat4 transformation, int materialIdx, std::string* error = nullptr);
+    // A unit icosahedron subdivided `level` times (20 * 4^level triangles, shared vertices on the sphere), scaled by radius and
+    // moved to centre; vertex normals are the sphere's.
+    void addIcosphere(vec3 centre, float radius, int level, int materialIdx);
+
 private:
     // libc rand() stand-in: MSVC's LCG, unseeded (state 1), RAND_MAX 32767 (SURVEY.md §9.5 DECISION).
     unsigned int randState = 1u;

@@ -9,6 +9,7 @@
 #include "HostOps.h"
 #include "Scene.h"
 #include "ptquant.h"
+#include "ptmesh.h"
 #include "pttri.h"
 #include "xorwow.h"
 
@@ -62,6 +63,18 @@ void ptss_scene_destroy(ptss_scene* s) { delete s; }
 int ptss_scene_describe(const ptss_scene* s, ptss_scene_desc* out) {
     if (!s || !out) return PTSS_HOST_EINVAL;
     *out = s->scene.desc();
+    return PTSS_HOST_OK;
+}
+
+int ptss_scene_add_obj(ptss_scene* s, const char* path, const float* m, int materialIdx, size_t* added) {
+    if (!s || !path || materialIdx < 0 || (size_t)materialIdx >= s->scene.materialsVec.size()) return PTSS_HOST_EINVAL;
+    mat4 t = mat4::identity();
+    if (m)
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) t.c[c][r] = m[4 * r + c];   // mat4 is column-major
+    const long n = s->scene.addObjModel(path, t, materialIdx);
+    if (n < 0) return n == -2 ? PTSS_HOST_EIO : PTSS_HOST_EINVAL;
+    if (added) *added = (size_t)n;
     return PTSS_HOST_OK;
 }
 
@@ -160,6 +173,19 @@ static const uint32_t* jumpTable() {
         ptrng::build_subsequence_table(table.data());
     }
     return table.data();
+}
+
+int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const float* d3, size_t n, float margin, int* out, float* bound12) {
+    if (!tri9 || ntri == 0 || ntri > (1u << 20) || (n && (!o3 || !d3 || !out))) return PTSS_HOST_EINVAL;
+    float b[12];
+    ptmesh::buildBound(tri9, (int)ntri, b);
+    if (bound12)
+        for (int k = 0; k < 12; ++k) bound12[k] = b[k];
+    for (size_t i = 0; i < n; ++i) {
+        const vec3 o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+        out[i] = ptmesh::mayTouch(v3(b[0], b[1], b[2]), b[3], v3(b[4], b[5], b[6]), b[7], b[8], b[9], b[10], b[11], o, d, margin) ? 1 : 0;
+    }
+    return PTSS_HOST_OK;
 }
 
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6) {

@@ -5,6 +5,8 @@
 // optional overrides with the reference's values as defaults:
 //   ptss_main [--preset default] [--size 512x512] [--ticks 16] [--bounces 15] [--seed N] [--samples-per-pass S]
 //             [--keys "wwd f"] [--out image.tga] [--quiet]
+//             [--obj model.obj [--obj-at x,y,z,scale]]...   Wavefront OBJ models added to the preset (Scene::addObjModel), each
+//                                   placed by the --obj-at after it (default: where the file puts it), in the preset's first material
 //             [--gpus N]            the frame sharded by pixel tile over N GPUs of this node, one RCCL gather (MultiGpu.cpp)
 //             [--emulate-gpus N]    the same N shards on device 0, the gather as device copies (rehearsal on a one-GPU box)
 #include <stdlib.h>
@@ -17,6 +19,7 @@
 
 int main(int argc, char* argv[]) {
     std::string preset = "default", out, keys;
+    std::vector<std::pair<std::string, mat4>> objs;   // --obj, --obj-at
     int width = DIM, height = DIM, ticks = 16, gpus = 0, samples = 1;
     bool emulate = false;
     unsigned bounces = 15;
@@ -36,6 +39,12 @@ int main(int argc, char* argv[]) {
         else if (a == "--gpus") gpus = atoi(next());
         else if (a == "--emulate-gpus") { gpus = atoi(next()); emulate = true; }
         else if (a == "--samples-per-pass") samples = atoi(next());
+        else if (a == "--obj") objs.push_back({next(), mat4::identity()});
+        else if (a == "--obj-at") {
+            float x, y, z, k;
+            if (objs.empty() || sscanf(next(), "%f,%f,%f,%f", &x, &y, &z, &k) != 4) { fprintf(stderr, "bad --obj-at (x,y,z,scale after an --obj)\n"); return 2; }
+            objs.back().second = translate(v3(x, y, z)) * scale(v3(k));
+        }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
 
@@ -44,6 +53,13 @@ int main(int argc, char* argv[]) {
     if (!scene.buildPreset(preset)) {  // scene.build() for "default"
         fprintf(stderr, "unknown preset %s\n", preset.c_str());
         return 2;
+    }
+    for (const auto& obj : objs) {
+        std::string why;
+        if (scene.materialsVec.empty() || scene.addObjModel(obj.first, obj.second, 0, &why) < 0) {
+            fprintf(stderr, "--obj %s: %s\n", obj.first.c_str(), scene.materialsVec.empty() ? "the preset has no material" : why.c_str());
+            return 2;
+        }
     }
 
     // initialize bitmap and data

@@ -48,6 +48,11 @@ def all_kernels():
     return out
 
 
+def mesh_kernels():
+    """The bounce-kernel instantiations of the mesh image (no frame kernel): ("bounce", "mesh", last, inLds, first)."""
+    return {("bounce", "mesh", last, lds, first) for last in (False, True) for lds in (False, True) for first in (False, True)}
+
+
 _host = None
 _dev = None
 
@@ -71,6 +76,8 @@ def host_lib():
         L.ptss_probe_triangle_forms.argtypes = [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_size_t, C.POINTER(C.c_int), _f32p, _f32p]
         L.ptss_probe_quant_table.argtypes = [_f32p]
         L.ptss_probe_rng_init.argtypes = [C.c_ulonglong, C.c_uint, _u32p]
+        L.ptss_scene_add_obj.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_int, C.POINTER(C.c_size_t)]
+        L.ptss_probe_mesh_bound.argtypes = [_f32p, C.c_size_t, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int), _f32p]
         L.ptss_probe_rng_draw.argtypes = [_u32p, _u32p, _f32p, C.c_size_t]
         L.ptss_probe_rng_jump_table.argtypes = [_u32p, C.c_size_t]
         _host = L
@@ -135,6 +142,7 @@ def device_lib():
         L.ptss_bounce_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
         L.ptss_launched_kernels.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_counters.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_triangle_leaves.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptss_error_string.argtypes = [C.c_int]
         L.ptss_error_string.restype = C.c_char_p
         L.ptss_last_error_detail.restype = C.c_char_p
@@ -160,6 +168,25 @@ class Scene:
         self.desc = SceneDesc()
         host_lib().ptss_scene_describe(self._h, C.byref(self.desc))
         self.desc._owner = self  # desc borrows the scene's arrays: `Scene(p).desc` must keep the scene alive
+
+    def add_obj(self, path, transform=None, material=0):
+        """Scene::addObjModel: appends the triangles of a Wavefront OBJ file, placed by `transform` (4x4, row-major, applied to
+        column vectors; None = identity), all with material index `material`. Returns the number added. Raises PtssError on a
+        file that cannot be read, a malformed line or an index out of range; the scene is then unchanged. The scene's tables are
+        described again, so `desc` (and arrays taken from it before) must be re-read after this call."""
+        m = None
+        if transform is not None:
+            t = np.ascontiguousarray(np.asarray(transform, dtype=np.float32).reshape(4, 4))
+            m = t.ctypes.data_as(_f32p)
+        added = C.c_size_t()
+        rc = host_lib().ptss_scene_add_obj(self._h, os.fsencode(path), m, int(material), C.byref(added))
+        if rc != 0:
+            raise PtssError(f"add_obj({path!r}) failed: {'cannot read the file' if rc == -2 else 'malformed OBJ or bad argument'} ({rc})")
+        owner = self
+        self.desc = SceneDesc()
+        host_lib().ptss_scene_describe(self._h, C.byref(self.desc))
+        self.desc._owner = owner
+        return added.value
 
     def __del__(self):
         if getattr(self, "_h", None) and self._h.value and host_lib is not None:
@@ -198,6 +225,21 @@ class Scene:
             "pointLights": [struct_to_dict(s) for s in self.point_lights],
             "areaLights": [struct_to_dict(s) for s in self.area_lights],
         }
+
+
+def probe_mesh_bound(tris, origins, directions, margin=1.0):
+    """csrc/ptmesh.h on the host: ONE bound built around `tris` ((n, 9) floats {v0, e1, e2}); per ray (origin, direction) 1 if
+    the ray may be accepted by one of them, 0 if provably not. Returns (verdicts, the bound's 12 floats)."""
+    t = np.ascontiguousarray(np.asarray(tris, dtype=np.float32).reshape(-1, 9))
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float32).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(directions, dtype=np.float32).reshape(-1, 3))
+    out = np.zeros(len(o), dtype=np.int32)
+    bound = np.zeros(12, dtype=np.float32)
+    rc = host_lib().ptss_probe_mesh_bound(t.ctypes.data_as(_f32p), len(t), o.ctypes.data_as(_f32p), d.ctypes.data_as(_f32p), len(o),
+                                          float(margin), out.ctypes.data_as(C.POINTER(C.c_int)), bound.ctypes.data_as(_f32p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_mesh_bound: {rc}")
+    return out, bound
 
 
 def default_camera():
@@ -400,7 +442,16 @@ class Renderer:
                     out.add(("bounce", name, bool(j & 4), bool(j & 2), bool(j & 1)))
             if v.value >> (32 + i) & 1:
                 out.add(("frame", name))
+        for j in range(8):  # the mesh image's bounce kernels: bits 40 + last * 4 + inLds * 2 + first
+            if v.value >> (40 + j) & 1:
+                out.add(("bounce", "mesh", bool(j & 4), bool(j & 2), bool(j & 1)))
         return out
+
+    def triangle_leaves(self):
+        """Leaves (16 triangles each) of the mesh image in use; 0 when the image walks every triangle."""
+        v = C.c_int()
+        _check(device_lib().ptss_triangle_leaves(self._ctx, C.byref(v)))
+        return v.value
 
     def debug_counters(self):
         """The eight counter words of a diagnostic build (-DPTSS_DIAG); zeros from the shipped library."""

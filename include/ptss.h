@@ -55,8 +55,10 @@ typedef struct ptss_render_config {
      * is still tone-mapped on its own before it is summed (CudaTracer.cu:72-92); the display divides by
      * S*(ticks - lastResetTick + 1). Lets one launch carry S times the rays (multi-GPU shards stay busy). 1..64. */
     int samplesPerPass;
-    /* Scenes with >= 64 finite spheres are traversed through spatially sorted sphere chunks (same image
-     * as the reference's every-sphere loop, tests/test_gpu_many_spheres.py). 1 keeps the every-sphere loop for them too. */
+    /* 1 = the reference's loops over every primitive. By default scenes with >= 64 finite spheres are traversed through spatially
+     * sorted sphere chunks (tests/test_gpu_many_spheres.py), and scenes of 512 .. 2^20 triangles, fewer than 64
+     * spheres and |coordinate| <= 2^40 through a two-level hierarchy of triangle leaves and groups (the mesh image, DESIGN.md
+     * §3.15; tests/test_gpu_mesh.py) — the same image either way. 1 keeps the every-sphere and every-triangle loops for them too. */
     int everySphereLoop;
     /* Frame lanes: the frame traced as K ray populations on K streams of the device, the tail of one lane's launches
      * overlapping the other lanes' kernels. The image — loop guard included — does not depend on K.
@@ -152,8 +154,13 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
 /* Which kernel instantiations this context has enqueued since ptss_create, as a bitmask (tests/test_gpu_kernel_coverage.py):
  * bit v*8 + last*4 + inLds*2 + first for the bounce kernel of scene variant v (0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
- * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v. Recorded on the host at launch. */
+ * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
+ * the bounce kernel of the mesh image (which has no frame kernel). Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
+
+/* Leaves of the triangle hierarchy of the scene image in use (16 triangles each), 0 when that image walks
+ * every triangle. */
+int ptss_triangle_leaves(const ptss_context* ctx, int* out);
 
 /* Diagnostic builds only (-DPTSS_DIAG=<bits>, csrc/ptss_diag.h, tools/build_variants.py): the eight counter words of that
  * build (sphere candidates per lane, scatter blocks, chunk culling, shadow-segment pairs, queue lengths); all zero in the

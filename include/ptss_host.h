@@ -27,6 +27,14 @@ void ptss_scene_destroy(ptss_scene* s);
 /* Borrowed pointers into the scene's vectors (Scene.h:11-15); valid until destroy. */
 int ptss_scene_describe(const ptss_scene* s, ptss_scene_desc* out);
 
+/* Scene::addObjModel — a Wavefront OBJ file (v, vn, f in the i, i/j, i//k, i/j/k forms, negative indices relative; polygons
+ * fan-triangulated; vt, o, g, s, usemtl, mtllib and comments ignored) appended to the scene's triangles with materialIdx.
+ * mat4x4: 16 floats, ROW-major (row r = mat4x4[4r .. 4r + 3]), applied to positions (normals: its inverse transpose); NULL =
+ * identity. *added (may be NULL) = triangles appended. PTSS_HOST_EIO: the file cannot be read; PTSS_HOST_EINVAL: a malformed
+ * line, an index out of range, a non-finite number, or materialIdx outside the scene's materials. On any error the scene is
+ * unchanged. Pointers from an earlier ptss_scene_describe may be invalidated: describe again. */
+int ptss_scene_add_obj(ptss_scene* s, const char* path, const float* mat4x4, int materialIdx, size_t* added);
+
 /* Camera() defaults (RenderStructs.h:51-52) and moveCamera (CudaTracer.cu:822-870):
  * key is the reference's key code ('w','a','s','d','q','e','f','h','g','t'); *moved = 1 if handled. */
 int ptss_camera_default(ptss_camera* out);
@@ -51,6 +59,12 @@ int ptss_probe_quant_table(float* out257);
  * camera-origin precomputes of bounce 0. cls[i] = the class; per form six floats: accepted (0/1), dist, b0, b1, b2, det. */
 int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d3, const float* limit, int primary, size_t n, int* cls,
                               float* general6, float* classed6);
+/* The mesh image's leaf / group bound (csrc/ptmesh.h — the very predicate the kernels evaluate): builds ONE bound around the
+ * ntri triangles {v0, e1, e2} (nine floats each, as stored) and answers for each of n rays (origin, direction) whether it may be
+ * accepted by a triangle inside (out[i] = 1) or provably is not (0). The predicate holds for |d|^2 within 1e-5 of 1 and a
+ * finite origin; margin scales its inflation term (1 = the kernels'; smaller values exist to show that a test can catch an
+ * under-inflated bound). bound12 (may be NULL) receives the bound's three rows. */
+int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const float* d3, size_t n, float margin, int* out, float* bound12);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6);
 /* n raw draws and the matching (0,1] floats from a state; state advanced in place. */
