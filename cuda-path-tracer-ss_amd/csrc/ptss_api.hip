@@ -1448,6 +1448,32 @@ int ptss_launched_kernels(const ptss_context* c, unsigned long long* out) {
     return PTSS_OK;
 }
 
+// ptss_intersect / ptss_occluded: the context's own scene image (images[0]; the query kernel is exact on every image, so the
+// camera's range plays no part), no frame state, the caller's stream
+static int rayQuery(ptss_context* c, bool any, const ptss_ray_query* rays, void* out, size_t n, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (n == 0) return PTSS_OK;
+    if (!rays || !out) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (((uintptr_t)rays | (uintptr_t)out) & (any ? 3u : 15u) || (uintptr_t)rays & 15u)
+        return fail(PTSS_EINVAL, "rays and hits must be 16-byte aligned, verdicts 4-byte aligned");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchQuery(st, any, im.dBlob, im.layout, im.inLds, rays, out, (uint32_t)n, c->gridCap * ptss::kShards,
+                              &c->launchedKernels));
+    return PTSS_OK;
+}
+
+int ptss_intersect(ptss_context* c, const ptss_ray_query* dev_rays, ptss_ray_hit* dev_hits, size_t n, void* hipStream) {
+    return rayQuery(c, false, dev_rays, dev_hits, n, hipStream);
+}
+
+int ptss_occluded(ptss_context* c, const ptss_ray_query* dev_rays, uint32_t* dev_occluded, size_t n, void* hipStream) {
+    return rayQuery(c, true, dev_rays, dev_occluded, n, hipStream);
+}
+
 int ptss_triangle_leaves(const ptss_context* c, int* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     const ptss::SceneLayout& L = c->image().layout;

@@ -234,5 +234,8 @@ struct FlushTargets {  // flushKernel re-derives the guard of every bounce: targ
 };
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets);  // one per lane
 int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool bounded);
+// batched ray queries (ptss_intersect / ptss_occluded): rays = n x 32 B, out = n x 48 B hits (any = false) or n uint32 verdicts
+hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* out,
+                       uint32_t n, int maxBlocks, unsigned long long* launched);
 
 }  // namespace ptss

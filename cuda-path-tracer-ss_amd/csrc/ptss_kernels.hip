@@ -2464,6 +2464,130 @@ __global__ void flushKernel(FrameBuffers fb, int numBounces, FlushTargets target
     }
 }
 
+// ---- BATCHED RAY QUERIES (ptss_intersect / ptss_occluded) ---------------------------------------------------
+// One lane per query ray, kBlock rays per workgroup, grid-strided; the scene image is staged as bounceBody stages it. Neither kernel
+// reads the per-camera rows (offPrim*) nor any frame buffer: a query may run beside the frames of the same context.
+// Closest hit: intersectScene (CudaTracer.cu:120-141) with `distance` starting at the ray's tmax. Spheres in the CALLER's order
+// with the reference's own test (a sorted many-sphere image maps caller index k to its stored position, offSpherePos), then
+// triangles: on the mesh image, when every live lane of the wave meets the two-level traversal's preconditions (meshQueryOk: a unit
+// direction, a bounded origin) and carries a running distance > 0 into it (the keyed minimum of closestTrianglesMesh orders
+// (distance, ~index) by bit pattern, which holds for positive distances only — no NaN, no -0, no negative tmax), that traversal;
+// otherwise the caller's order with the guarded test (closestHit's last loop). Both end on what the sequential
+// `dist <= distance` rule ends on; every NaN, infinite, huge or zero input takes the literal loops, which ARE the reference's.
+// Occlusion: lineOfSight's loop (CudaTracer.cu:434-452) is an OR over independent tests, so anyHit's order-free loops answer it
+// for the images whose sphere tests are the literal ones (plain, mesh); the sorted many-sphere image's chunk tests assume origins
+// in the scene's range, so there the same loop walks its stored sphere rows instead of the chunks.
+// (Diagnostic builds: anyHit's candidate counter, PTSS_DIAG bit 0 slot 4, also counts the occlusion queries' sphere candidates.)
+template <bool kAny, bool kSceneInLds>
+__global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__ sceneBlob, SceneLayout L, const float4* __restrict__ rays,
+                                                       float4* __restrict__ out, uint32_t n) {
+    extern __shared__ __attribute__((aligned(256))) float4 lds[];
+    const float4* sc;
+    if constexpr (kSceneInLds) {
+        for (int k = threadIdx.x; k < L.ldsVec4; k += kBlock) lds[k] = sceneBlob[k];
+        __syncthreads();
+        sc = lds;
+    } else {
+        sc = sceneBlob;
+    }
+    const bool mesh = meshImage(L);
+    const float4* td = mesh ? sceneBlob : sc;   // the triangle tables (global memory in the mesh image)
+    const int* spherePos = reinterpret_cast<const int*>(sceneBlob + L.offSpherePos);   // (read only with accelSpheres)
+    const int* triPos = reinterpret_cast<const int*>(sceneBlob + L.offTriPos);         // (read only for classed and mesh images)
+    const bool triStoredElsewhere = mesh || L.triClassed;
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < n;
+        float4 r0 = float4{0, 0, 0, 0}, r1 = float4{0, 0, 0, 0};
+        if (live) {
+            r0 = rays[2 * (size_t)i];
+            r1 = rays[2 * (size_t)i + 1];
+        }
+        const vec3 o = xyz(r0), d = xyz(r1);
+        const float tmax = r0.w;
+        const unsigned long long liveMask = maskOf(live);
+        if constexpr (kAny) {
+            bool blocked;
+            if (L.accelSpheres) {
+                // every STORED sphere row (the sorted spheres and their padding copies: any order and repeats answer an OR) through
+                // the plain image's loop, literal discriminant masks then the reference's test
+                SceneLayout Ls = L;
+                Ls.numSpheres = L.numChunks * kChunkSpheres;
+                blocked = anyHit<false, false, false>(sc, Ls, o, d, tmax, live);
+            } else if (mesh) {
+                blocked = anyHit<false, false, true>(sc, L, o, d, tmax, live, sceneBlob);
+            } else {
+                blocked = anyHit<false, false, false>(sc, L, o, d, tmax, live);
+            }
+            if (live) reinterpret_cast<uint32_t*>(out)[i] = blocked ? 1u : 0u;
+        } else {
+            float dist = tmax;
+            int kind = 0, prim = -1, pos = 0;
+            float w0 = 0, w1 = 0, w2 = 0;
+            for (int k = 0; k < L.numSpheres; ++k) {   // the caller's order, the reference's test
+                const int p = L.accelSpheres ? spherePos[k] : k;
+                float t;
+                if (live && sphereTest(sc[L.offSphere + p], o, d, dist, t)) {
+                    dist = t;
+                    kind = 1;
+                    prim = k;
+                    pos = p;
+                }
+            }
+            if (mesh && meshQueryOk(o, d, live) && waveAll(!live || dist > 0.0f)) {
+                TriBest best{dist, kNoTriangle, 0.0f, 0.0f};
+                closestTrianglesMesh<false>(sc, sceneBlob, L, o, d, live, best);
+                if (best.key != kNoTriangle) {
+                    dist = best.dist;
+                    kind = 2;
+                    prim = (int)(0xfffffffeu - best.key);
+                    pos = triPos[prim];   // per-lane gather
+                    w1 = best.w1;
+                    w2 = best.w2;
+                    w0 = 1.0f - (w1 + w2);  // Primitives.h:64, from the kept pair
+                }
+            } else {
+                for (int k = 0; k < L.numTriangles; ++k) {   // the guarded loop, in the caller's order
+                    const int p = triStoredElsewhere ? triPos[k] : k;
+                    const TriHit th = triangleTest(loadTri(td + L.offTri + 3 * p), o, d, dist, liveMask);
+                    if (th.hit) {
+                        dist = th.dist;
+                        kind = 2;
+                        prim = k;
+                        pos = p;
+                        w0 = th.w0;
+                        w1 = th.w1;
+                        w2 = th.w2;
+                    }
+                }
+            }
+            // the SurfaceElement, with bounceTile's operations after its closest hit (Primitives.h:74, :100)
+            vec3 point = v3(0, 0, 0), normal = v3(0, 0, 0);
+            int materialIdx = -1;
+            if (kind != 0) {
+                point = o + d * dist;
+                if (kind == 1) {
+                    normal = normalize(point - xyz(loadRow16(sc + L.offSphere + pos)));
+                    materialIdx = reinterpret_cast<const int*>(sceneBlob + L.offSphereMat)[pos];
+                } else {
+                    const float4* nn = td + L.offTriNormal + 3 * pos;
+                    normal = (xyz(loadRow16(nn)) * w0 + xyz(loadRow16(nn + 1)) * w1) + xyz(loadRow16(nn + 2)) * w2;
+                    materialIdx = (int)asU(td[L.offTri + 3 * pos].w);
+                }
+            } else {
+                w1 = w2 = 0.0f;
+            }
+            if (kind == 1) w1 = w2 = 0.0f;
+            if (live) {
+                float4* h = out + 3 * (size_t)i;
+                h[0] = float4{point.x, point.y, point.z, dist};
+                h[1] = float4{normal.x, normal.y, normal.z, asF((uint32_t)materialIdx)};
+                h[2] = float4{asF((uint32_t)kind), asF((uint32_t)prim), w1, w2};
+            }
+        }
+    }
+}
+
 // =================================================================================================
 static inline unsigned blocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
 
@@ -2564,6 +2688,22 @@ hipError_t launchFrame(hipStream_t st, const FrameBuffers& fb, const float4* sce
 int frameOccupancyBlocksPerCU(const SceneLayout& layout, bool bounded) {
     const KernelFn k = frameKernelFor(sceneVariant(layout, bounded));
     return k ? blocksPerCU(k, bounceLdsBytes(layout, true)) : 0;
+}
+
+// the query kernel (bit 48 + any * 2 + inLds of *launched): one workgroup per kBlock rays, at most maxBlocks (resident rounds)
+hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* out,
+                       uint32_t n, int maxBlocks, unsigned long long* launched) {
+    using QueryFn = void (*)(const float4*, SceneLayout, const float4*, float4*, uint32_t);
+    static constexpr QueryFn table[4] = {queryKernel<false, false>, queryKernel<false, true>, queryKernel<true, false>, queryKernel<true, true>};
+    const int index = (any ? 2 : 0) + (sceneInLds ? 1 : 0);
+    unsigned blocks = blocksFor(n, kBlock);
+    if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
+    const size_t lds = sceneInLds ? (size_t)layout.ldsVec4 * sizeof(float4) : 0;
+    hipLaunchKernelGGL(table[index], dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, static_cast<const float4*>(rays),
+                       static_cast<float4*>(out), n);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *launched |= 1ull << (48 + index);
+    return e;
 }
 
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets) {

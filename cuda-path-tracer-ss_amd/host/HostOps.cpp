@@ -41,6 +41,22 @@ bool moveCamera(Camera& camera, unsigned char key) {
     return false;
 }
 
+ptss_ray_query cameraRay(const ptss_camera& camera, int width, int height, int x, int y, float jx, float jy) {
+    const float s = -2 * ptm::tan(camera.fieldOfView * 0.5f);   // EyeParams {s, aspect, invW, invH}
+    const float aspect = (float)height / (float)width;
+    const float invW = 1.0f / width, invH = 1.0f / height;
+    const float jitteredX = x + jx;
+    const float jitteredY = y + jy;
+    const vec3 start = v3(((jitteredX * invW) - 0.5f) * s, 1 * ((jitteredY * invH) - 0.5f) * s * aspect, 1.0f) * camera.zNear;
+    const vec3 d = normalize(rotate(camera.rotation, start));
+    ptss_ray_query q;
+    q.origin = camera.position;
+    q.tmax = ptm::inf();
+    q.direction = d;
+    q.pad = 0.0f;
+    return q;
+}
+
 bool writeTga(const char* filename, const ptss_uchar4* rgba, int width, int height) {
     std::FILE* f = std::fopen(filename, "wb");
     if (!f) return false;

@@ -84,6 +84,12 @@ int ptss_camera_default(ptss_camera* out) {
     return PTSS_HOST_OK;
 }
 
+int ptss_camera_ray(const ptss_camera* cam, int width, int height, int x, int y, float jx, float jy, ptss_ray_query* out) {
+    if (!cam || !out || width <= 0 || height <= 0) return PTSS_HOST_EINVAL;
+    *out = cameraRay(*cam, width, height, x, y, jx, jy);
+    return PTSS_HOST_OK;
+}
+
 int ptss_camera_move(ptss_camera* cam, unsigned char key, int* moved) {
     if (!cam) return PTSS_HOST_EINVAL;
     Camera c;

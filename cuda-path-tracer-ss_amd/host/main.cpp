@@ -9,6 +9,9 @@
 //                                   placed by the --obj-at after it (default: where the file puts it), in the preset's first material
 //             [--gpus N]            the frame sharded by pixel tile over N GPUs of this node, one RCCL gather (MultiGpu.cpp)
 //             [--emulate-gpus N]    the same N shards on device 0, the gather as device copies (rehearsal on a one-GPU box)
+//             [--pick x,y]...       after the ticks and --keys: the closest hit of pixel (x, y)'s centre ray (ptss_camera_ray with
+//                                   jitter 0.5, 0.5, through ptss_intersect) of the final camera, one line per pick
+#include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -20,6 +23,7 @@
 int main(int argc, char* argv[]) {
     std::string preset = "default", out, keys;
     std::vector<std::pair<std::string, mat4>> objs;   // --obj, --obj-at
+    std::vector<std::pair<int, int>> picks;            // --pick
     int width = DIM, height = DIM, ticks = 16, gpus = 0, samples = 1;
     bool emulate = false;
     unsigned bounces = 15;
@@ -44,6 +48,11 @@ int main(int argc, char* argv[]) {
             float x, y, z, k;
             if (objs.empty() || sscanf(next(), "%f,%f,%f,%f", &x, &y, &z, &k) != 4) { fprintf(stderr, "bad --obj-at (x,y,z,scale after an --obj)\n"); return 2; }
             objs.back().second = translate(v3(x, y, z)) * scale(v3(k));
+        }
+        else if (a == "--pick") {
+            int x, y;
+            if (sscanf(next(), "%d,%d", &x, &y) != 2) { fprintf(stderr, "bad --pick (x,y)\n"); return 2; }
+            picks.push_back({x, y});
         }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -76,6 +85,9 @@ int main(int argc, char* argv[]) {
     cfg.samplesPerPass = samples;
     const ptss_scene_desc desc = scene.desc(defaultColor);
     ptss_context* ctx = NULL;
+    if (!picks.empty() && gpus > 0) { fprintf(stderr, "--pick needs one context (no --gpus)\n"); return 2; }
+    for (const auto& p : picks)
+        if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
         createShards(data, desc, cfg, gpus, emulate);
         ctx = data->renderData.context;
@@ -105,6 +117,30 @@ int main(int argc, char* argv[]) {
         strncpy(name, out.c_str(), sizeof(name) - 1);
         name[sizeof(name) - 1] = 0;
         saveScreenshot(name, width, height);
+    }
+    if (!picks.empty()) {   // picking: the pixel-centre ray of the final camera through ptss_intersect
+        std::vector<ptss_ray_query> q;
+        for (const auto& p : picks) q.push_back(cameraRay(data->camera, width, height, p.first, p.second, 0.5f, 0.5f));
+        std::vector<ptss_ray_hit> h(q.size());
+        void *dq = nullptr, *dh = nullptr;
+        if (hipMalloc(&dq, q.size() * sizeof(ptss_ray_query)) != hipSuccess || hipMalloc(&dh, h.size() * sizeof(ptss_ray_hit)) != hipSuccess ||
+            hipMemcpy(dq, q.data(), q.size() * sizeof(ptss_ray_query), hipMemcpyHostToDevice) != hipSuccess) {
+            fprintf(stderr, "--pick: device buffers\n");
+            return 1;
+        }
+        PTSS_HANDLE(ptss_intersect(ctx, (const ptss_ray_query*)dq, (ptss_ray_hit*)dh, q.size(), NULL));
+        PTSS_HANDLE(ptss_synchronize(ctx));
+        if (hipMemcpy(h.data(), dh, h.size() * sizeof(ptss_ray_hit), hipMemcpyDeviceToHost) != hipSuccess) {
+            fprintf(stderr, "--pick: read-back\n");
+            return 1;
+        }
+        (void)hipFree(dq);
+        (void)hipFree(dh);
+        static const char* kinds[] = {"miss", "sphere", "triangle"};
+        for (size_t i = 0; i < h.size(); ++i)
+            printf("pick %d,%d: %s %d material %d distance %.9g point %.9g %.9g %.9g\n", picks[i].first, picks[i].second,
+                   kinds[h[i].kind >= 0 && h[i].kind <= 2 ? h[i].kind : 0], h[i].primitive, h[i].materialIdx, h[i].distance, h[i].point.x,
+                   h[i].point.y, h[i].point.z);
     }
     const unsigned long long rays = totalRayBounces(data);
     printf("%d ticks, %llu ray-bounces, last pass %.3f ms", ticks, rays, data->lastPassMs);

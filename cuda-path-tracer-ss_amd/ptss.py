@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ptss_types import (AreaLight, Camera, Material, PointLight, SceneDesc, Sphere, Triangle, UChar4, Vec3,
+from ptss_types import (AreaLight, Camera, Material, PointLight, RayHit, RayQuery, SceneDesc, Sphere, Triangle, UChar4, Vec3,
                         struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,8 +53,33 @@ def mesh_kernels():
     return {("bounce", "mesh", last, lds, first) for last in (False, True) for lds in (False, True) for first in (False, True)}
 
 
+def query_kernels():
+    """The query-kernel instantiations (ptss_intersect / ptss_occluded): ("query", "closest" | "any", inLds)."""
+    return {("query", kind, lds) for kind in ("closest", "any") for lds in (False, True)}
+
+
 _host = None
 _dev = None
+_hip = None
+
+
+def _hip_lib():
+    """The HIP runtime libptss.so links (device buffers of the numpy query path)."""
+    global _hip
+    if _hip is None:
+        device_lib()
+        L = C.CDLL("libamdhip64.so.7", mode=C.RTLD_GLOBAL)   # by soname: the runtime already loaded for libptss.so
+        L.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        L.hipFree.argtypes = [C.c_void_p]
+        L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        L.hipSetDevice.argtypes = [C.c_int]
+        _hip = L
+    return _hip
+
+
+def _hip_check(rc, what):
+    if rc != 0:
+        raise PtssError(f"{what} failed (hipError {rc})")
 
 
 def host_lib():
@@ -80,6 +105,7 @@ def host_lib():
         L.ptss_probe_mesh_bound.argtypes = [_f32p, C.c_size_t, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int), _f32p]
         L.ptss_probe_rng_draw.argtypes = [_u32p, _u32p, _f32p, C.c_size_t]
         L.ptss_probe_rng_jump_table.argtypes = [_u32p, C.c_size_t]
+        L.ptss_camera_ray.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RayQuery)]
         _host = L
     return _host
 
@@ -143,6 +169,8 @@ def device_lib():
         L.ptss_launched_kernels.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_counters.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_triangle_leaves.argtypes = [vp, C.POINTER(C.c_int)]
+        L.ptss_intersect.argtypes = [vp, vp, vp, C.c_size_t, vp]
+        L.ptss_occluded.argtypes = [vp, vp, vp, C.c_size_t, vp]
         L.ptss_error_string.argtypes = [C.c_int]
         L.ptss_error_string.restype = C.c_char_p
         L.ptss_last_error_detail.restype = C.c_char_p
@@ -252,6 +280,47 @@ def move_camera(cam, key):
     moved = C.c_int(0)
     host_lib().ptss_camera_move(C.byref(cam), ord(key), C.byref(moved))
     return bool(moved.value)
+
+
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("direction", np.float32, 3), ("pad", np.float32)])
+HIT_DTYPE = np.dtype([("point", np.float32, 3), ("distance", np.float32), ("normal", np.float32, 3), ("materialIdx", np.int32),
+                      ("kind", np.int32), ("primitive", np.int32), ("w1", np.float32), ("w2", np.float32)])
+assert RAY_DTYPE.itemsize == C.sizeof(RayQuery) and HIT_DTYPE.itemsize == C.sizeof(RayHit)
+
+
+def make_rays(origins, directions, tmax=float("inf")):
+    """(N, 8) float32 query rays {origin, tmax, direction, 0} (include/ptss_types.h ptss_ray_query); tmax: scalar or (N,)."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    out = np.zeros((o.shape[0], 8), dtype=np.float32)
+    out[:, 0:3], out[:, 4:7] = o, d
+    out[:, 3] = np.broadcast_to(np.asarray(tmax, dtype=np.float32), (o.shape[0],))
+    return out
+
+
+def camera_ray(cam, width, height, x, y, jitter=(0.5, 0.5)):
+    """ptss_camera_ray: the eye ray of pixel (x, y) through (x + jx, y + jy), as an (8,) float32 row."""
+    q = RayQuery()
+    rc = host_lib().ptss_camera_ray(C.byref(cam), width, height, x, y, jitter[0], jitter[1], C.byref(q))
+    if rc != 0:
+        raise PtssError(f"ptss_camera_ray: {rc}")
+    return np.frombuffer(bytes(q), dtype=np.float32).copy()
+
+
+def camera_rays(cam, width, height, jitter=(0.5, 0.5)):
+    """The eye rays of every pixel of a width x height frame, row-major (index y * width + x), as (width * height, 8) float32."""
+    out = np.empty((width * height, 8), dtype=np.float32)
+    q = RayQuery()
+    fn, jx, jy, ref_cam, ref_q = host_lib().ptss_camera_ray, C.c_float(jitter[0]), C.c_float(jitter[1]), C.byref(cam), C.byref(q)
+    buf = (C.c_float * 8).from_buffer(q)
+    for y in range(height):
+        for x in range(width):
+            if fn(ref_cam, width, height, x, y, jx, jy, ref_q) != 0:
+                raise PtssError("ptss_camera_ray failed")
+            out[y * width + x] = buf
+    return out
 
 
 def tile_rows(height, band_rows, rank, world):
@@ -445,6 +514,59 @@ class Renderer:
         for j in range(8):  # the mesh image's bounce kernels: bits 40 + last * 4 + inLds * 2 + first
             if v.value >> (40 + j) & 1:
                 out.add(("bounce", "mesh", bool(j & 4), bool(j & 2), bool(j & 1)))
+        for j in range(4):  # the query kernel: bits 48 + any * 2 + inLds
+            if v.value >> (48 + j) & 1:
+                out.add(("query", "any" if j & 2 else "closest", bool(j & 1)))
+        return out
+
+    # --- batched ray queries (ptss_intersect / ptss_occluded) ------------------------------------------
+    def intersect(self, rays):
+        """Closest hits. rays: (N, 8) float32 or an (N,) RAY_DTYPE array -> (N,) HIT_DTYPE array; or a contiguous (N, 8) float32
+        torch tensor on the context's device -> (N, 12) float32 tensor (bit-viewable as HIT_DTYPE), on the current stream."""
+        return self._query(rays, any_hit=False)
+
+    def occluded(self, rays):
+        """Occlusion verdicts (1 = some primitive accepts within tmax). numpy in -> (N,) uint32; torch in -> (N,) int32 tensor."""
+        return self._query(rays, any_hit=True)
+
+    def _query(self, rays, any_hit):
+        L = device_lib()
+        fn = L.ptss_occluded if any_hit else L.ptss_intersect
+        if type(rays).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+                raise ValueError("rays: a contiguous (N, 8) float32 device tensor")
+            n = rays.shape[0]
+            out = (torch.empty(n, dtype=torch.int32, device=rays.device) if any_hit
+                   else torch.empty((n, 12), dtype=torch.float32, device=rays.device))
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check(fn(self._ctx, C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
+            return out
+        a = np.asarray(rays)
+        if a.dtype == RAY_DTYPE:
+            a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays: (N, 8) float32 or (N,) RAY_DTYPE")
+        n = a.shape[0]
+        out = np.empty(n, dtype=np.uint32) if any_hit else np.empty(n, dtype=HIT_DTYPE)
+        if n == 0:
+            return out
+        H = _hip_lib()
+        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
+        d_rays, d_out = C.c_void_p(), C.c_void_p()
+        _hip_check(H.hipMalloc(C.byref(d_rays), a.nbytes), "hipMalloc")
+        try:
+            _hip_check(H.hipMalloc(C.byref(d_out), out.nbytes), "hipMalloc")
+            _hip_check(H.hipMemcpy(d_rays, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+            _check(fn(self._ctx, d_rays, d_out, n, None))
+            self.synchronize()
+            _hip_check(H.hipMemcpy(out.ctypes.data, d_out, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        finally:
+            H.hipFree(d_rays)
+            if d_out:
+                H.hipFree(d_out)
         return out
 
     def triangle_leaves(self):

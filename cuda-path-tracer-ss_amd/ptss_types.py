@@ -54,8 +54,18 @@ class SceneDesc(C.Structure):
                 ("defaultColor", Vec3)]
 
 
+class RayQuery(C.Structure):
+    _fields_ = [("origin", Vec3), ("tmax", C.c_float), ("direction", Vec3), ("pad", C.c_float)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("point", Vec3), ("distance", C.c_float), ("normal", Vec3), ("materialIdx", C.c_int), ("kind", C.c_int),
+                ("primitive", C.c_int), ("w1", C.c_float), ("w2", C.c_float)]
+
+
 assert C.sizeof(Sphere) == 20 and C.sizeof(Triangle) == 76 and C.sizeof(Material) == 76
 assert C.sizeof(PointLight) == 24 and C.sizeof(AreaLight) == 32 and C.sizeof(Camera) == 40
+assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48
 
 
 def struct_to_dict(s):

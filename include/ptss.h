@@ -155,8 +155,21 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * bit v*8 + last*4 + inLds*2 + first for the bounce kernel of scene variant v (0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
  * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
- * the bounce kernel of the mesh image (which has no frame kernel). Recorded on the host at launch. */
+ * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
+ * ptss_occluded). Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
+
+/* Batched ray queries against the context's scene. dev_rays / dev_hits / dev_occluded are DEVICE pointers of n
+ * entries on the context's device. ptss_intersect: what the reference's intersectScene loop (CudaTracer.cu:120-141) returns for
+ * ray (origin, direction) with `distance` starting at tmax — spheres 0..S-1, then triangles 0..T-1 — bit for bit, for every input
+ * (non-unit, zero, infinite and NaN components included). ptss_occluded: dev_occluded[i] = 1 iff some primitive's
+ * intersectRay(ray, tmax, surfel, false) accepts (lineOfSight's loop, CudaTracer.cu:434-452, without the bump and the
+ * shortening), else 0. Asynchronous on hipStream (NULL: the context's stream). They read the scene image only, never the
+ * per-camera rows, and leave no trace in frame state: they may run between frames or on another stream while frames run.
+ * n = 0 returns PTSS_OK; a null context or null pointers with n > 0 return PTSS_EINVAL, n >= 2^31 PTSS_ERANGE, without touching
+ * the device. ptss_launched_kernels reports the query kernel at bit 48 + any * 2 + inLds. */
+int ptss_intersect(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_ray_hit* dev_hits, size_t n, void* hipStream);
+int ptss_occluded(ptss_context* ctx, const ptss_ray_query* dev_rays, uint32_t* dev_occluded, size_t n, void* hipStream);
 
 /* Leaves of the triangle hierarchy of the scene image in use (16 triangles each), 0 when that image walks
  * every triangle. */

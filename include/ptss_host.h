@@ -39,6 +39,10 @@ int ptss_scene_add_obj(ptss_scene* s, const char* path, const float* mat4x4, int
  * key is the reference's key code ('w','a','s','d','q','e','f','h','g','t'); *moved = 1 if handled. */
 int ptss_camera_default(ptss_camera* out);
 int ptss_camera_move(ptss_camera* cam, unsigned char key, int* moved);
+/* The eye ray through (x + jx, y + jy) of a width x height frame, built with bounce 0's operations (computeEyeRay,
+ * CudaTracer.cu:321-343), tmax = +inf. With (jx, jy) = the pixel's two RNG uniforms it is the frame's own eye ray; (0.5, 0.5)
+ * is the pixel centre. */
+int ptss_camera_ray(const ptss_camera* cam, int width, int height, int x, int y, float jx, float jy, ptss_ray_query* out);
 
 /* saveScreenshot (CudaTracer.cu:795-813): 18-byte header, type 2, 24-bit BGR, bottom-up rows,
  * from a host copy of the RGBA display buffer (row 0 = bottom, as GPUAnimBitmap draws it). */

@@ -90,6 +90,48 @@ typedef struct ptss_scene_desc {
     ptss_vec3 defaultColor;
 } ptss_scene_desc;
 
+/* One ray of a batched query (ptss_intersect / ptss_occluded): two 16-byte rows. The direction is used as given (not
+ * normalised); tmax is the initial `distance` of the reference's intersectScene loop (CudaTracer.cu:120-141). */
+typedef struct ptss_ray_query {
+    ptss_vec3 origin;
+    float tmax;
+    ptss_vec3 direction;
+    float pad;
+} ptss_ray_query;
+
+/* The closest hit of one query: the reference's SurfaceElement (RenderStructs.h:110-121) plus what found it.
+ * kind: 0 miss, 1 sphere, 2 triangle; primitive: index into the caller's spheres[] / triangles[]; w1, w2: the triangle's
+ * weight[1], weight[2] (Primitives.h:58-60), 0 for spheres. A miss: distance = tmax, primitive = materialIdx = -1, the rest 0. */
+typedef struct ptss_ray_hit {
+    ptss_vec3 point;
+    float distance;
+    ptss_vec3 normal;
+    int materialIdx;
+    int kind;
+    int primitive;
+    float w1, w2;
+} ptss_ray_hit;
+
+#define PTSS_HIT_MISS 0
+#define PTSS_HIT_SPHERE 1
+#define PTSS_HIT_TRIANGLE 2
+
+#if defined(__cplusplus)
+static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
+              "ptss_ray_query is two 16-byte rows");
+static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) == 12 && offsetof(ptss_ray_hit, normal) == 16 &&
+                  offsetof(ptss_ray_hit, materialIdx) == 28 && offsetof(ptss_ray_hit, kind) == 32 &&
+                  offsetof(ptss_ray_hit, primitive) == 36 && offsetof(ptss_ray_hit, w1) == 40 && offsetof(ptss_ray_hit, w2) == 44,
+              "ptss_ray_hit is three 16-byte rows");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
+               "ptss_ray_query is two 16-byte rows");
+_Static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) == 12 && offsetof(ptss_ray_hit, normal) == 16 &&
+                   offsetof(ptss_ray_hit, materialIdx) == 28 && offsetof(ptss_ray_hit, kind) == 32 &&
+                   offsetof(ptss_ray_hit, primitive) == 36 && offsetof(ptss_ray_hit, w1) == 40 && offsetof(ptss_ray_hit, w2) == 44,
+               "ptss_ray_hit is three 16-byte rows");
+#endif
+
 #ifdef __cplusplus
 }
 #endif
