@@ -19,6 +19,7 @@
 #include <array>
 #include <cmath>
 #include "ptquant.h"
+#include "ptdenoise.h"
 #include "ptmesh.h"
 #include "pttri.h"
 
@@ -132,6 +133,10 @@ struct ptss_context {
     hipEvent_t evEpoch = nullptr;
     unsigned int timeoutsSeen = 0;   // ptss_guard_timeouts value already reported as PTSS_ETIMEOUT
     unsigned long long launchedKernels = 0;   // bounce / frame kernel instantiations enqueued since ptss_create (ptss_launched_kernels)
+    float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
+    int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
+    int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
+    hipStream_t denoiseStream = nullptr;
 };
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 
@@ -1170,6 +1175,7 @@ int ptss_destroy(ptss_context* c) {
     (void)hipFree(c->dAccumOwned);
     (void)hipFree(c->dFsum);
     (void)hipFree(c->dStaged);
+    for (float4* plane : c->dDenoise) (void)hipFree(plane);
     delete c;
     return PTSS_OK;
 }
@@ -1472,6 +1478,87 @@ int ptss_intersect(ptss_context* c, const ptss_ray_query* dev_rays, ptss_ray_hit
 
 int ptss_occluded(ptss_context* c, const ptss_ray_query* dev_rays, uint32_t* dev_occluded, size_t n, void* hipStream) {
     return rayQuery(c, true, dev_rays, dev_occluded, n, hipStream);
+}
+
+// ptss_render_features: the scene image the queries use (images[0], exact for every camera), the context's CURRENT camera, no frame state
+int ptss_render_features(ptss_context* c, ptss_pixel_feature* dev_features, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features) return fail(PTSS_EINVAL, "dev_features is null");
+    if ((uintptr_t)dev_features & 15u) return fail(PTSS_EINVAL, "dev_features must be 16-byte aligned");
+    if (c->numPixels == 0) return PTSS_OK;   // a rank whose tile is empty
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    HIP_TRY(ptss::launchFeatures(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, c->numPixels,
+                                 c->gridCap * ptss::kShards, &c->launchedKernels));
+    return PTSS_OK;
+}
+
+int ptss_default_denoise_params(ptss_denoise_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(*p);
+    p->levels = 5;
+    p->sigmaColor = 64.0f;
+    p->sigmaNormal = 0.1f;
+    p->sigmaDepth = 4.0f;
+    return PTSS_OK;
+}
+
+int ptss_denoise(ptss_context* c, const ptss_pixel_feature* dev_features, const ptss_denoise_params* params, ptss_uchar4* dev_out,
+                 void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features || !params || !dev_out) return fail(PTSS_EINVAL, "null argument");
+    if (params->structSize != (unsigned int)sizeof(ptss_denoise_params))
+        return fail(PTSS_EINVAL, "params->structSize is not this library's sizeof(ptss_denoise_params): start from ptss_default_denoise_params");
+    if (params->levels < 0 || params->levels > PTSS_DENOISE_MAX_LEVELS) return fail(PTSS_EINVAL, "levels must be in [0, 6]");
+    if (!(params->sigmaColor > 0.0f) || !(params->sigmaNormal > 0.0f) || !(params->sigmaDepth >= 0.0f))
+        return fail(PTSS_EINVAL, "sigmaColor and sigmaNormal must be positive, sigmaDepth not negative");
+    if (((uintptr_t)dev_features & 15u) || ((uintptr_t)dev_out & 3u)) return fail(PTSS_EINVAL, "dev_features must be 16-byte aligned, dev_out 4-byte aligned");
+    if (c->tile.world > 1)
+        return fail(PTSS_EINVAL, "ptss_denoise needs the whole frame: this context is a pixel-band shard (tileWorld > 1), whose bands of rows "
+                                 "have no neighbours to filter with");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const int levels = params->levels;
+    if (levels >= 2)
+        for (float4*& plane : c->dDenoise)
+            if (!plane) {
+                const hipError_t e = hipMalloc(&plane, (size_t)c->numPixels * sizeof(float4));
+                if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PTSS_ENOMEM : PTSS_EHIP, "ptss_denoise: colour planes", e);
+            }
+    // the display value's scale: displayKernel's / finishPath's inverseTicks of the last frame (frameBuffers)
+    const float inverseTicks = 1.f / (float)((int)c->samples * (c->lastTicks - c->lastResetTick + 1));
+    const int width = c->tile.width, height = c->tile.height;
+    c->denoiseLastPlane = levels >= 2 ? (levels - 2) & 1 : -1;
+    c->denoiseLastLevel = levels - 2;
+    c->denoiseStream = st;
+    for (int i = 0; i < (levels > 0 ? levels : 1); ++i) {
+        const bool first = i == 0, last = i + 1 >= levels;
+        const void* src = first ? static_cast<const void*>(c->dAccum) : c->dDenoise[(i - 1) & 1];
+        void* dst = last ? static_cast<void*>(dev_out) : c->dDenoise[i & 1];
+        HIP_TRY(ptss::launchDenoise(st, first, last, src, dst, dev_features, width, height, ptdn::levelOf(*params, i), inverseTicks,
+                                    &c->launchedKernels));
+    }
+    return PTSS_OK;
+}
+
+int ptss_read_denoise_plane(ptss_context* c, float* host_float3, size_t count, int* level) {
+    if (!c || !host_float3) return fail(PTSS_EINVAL, "null argument");
+    if (c->denoiseLastPlane < 0) return fail(PTSS_EINVAL, "no colour plane: the latest ptss_denoise of this context ran fewer than two levels");
+    if (count != (size_t)3 * c->numPixels) return fail(PTSS_ERANGE, "count must be 3 * local pixels");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->denoiseStream));
+    std::vector<float4> plane(c->numPixels);
+    HIP_TRY(hipMemcpy(plane.data(), c->dDenoise[c->denoiseLastPlane], plane.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < plane.size(); ++p) {
+        host_float3[3 * p] = plane[p].x;
+        host_float3[3 * p + 1] = plane[p].y;
+        host_float3[3 * p + 2] = plane[p].z;
+    }
+    if (level) *level = c->denoiseLastLevel;
+    return PTSS_OK;
 }
 
 int ptss_triangle_leaves(const ptss_context* c, int* out) {

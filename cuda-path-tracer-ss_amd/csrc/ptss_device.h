@@ -8,6 +8,8 @@
 #include "ptss_types.h"
 #include "xorwow.h"
 
+namespace ptdn { struct Level; }   // ptdenoise.h
+
 namespace ptss {
 
 // ---- ray pools: struct-of-arrays in tile blocks ------------------------------------------------------------
@@ -237,5 +239,12 @@ int bounceOccupancyBlocksPerCU(const SceneLayout& layout, bool sceneInLds, bool 
 // batched ray queries (ptss_intersect / ptss_occluded): rays = n x 32 B, out = n x 48 B hits (any = false) or n uint32 verdicts
 hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* out,
                        uint32_t n, int maxBlocks, unsigned long long* launched);
+// first-hit features (ptss_render_features): out = n x 32 B, one ptss_pixel_feature per local pixel
+hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                          ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launched);
+// one pass of ptss_denoise (ptss_denoise.hip; bit 54 of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
+// plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
+hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,
+                         const ptdn::Level& level, float inverseTicks, unsigned long long* launched);
 
 }  // namespace ptss

@@ -2478,6 +2478,82 @@ __global__ void flushKernel(FrameBuffers fb, int numBounces, FlushTargets target
 // for the images whose sphere tests are the literal ones (plain, mesh); the sorted many-sphere image's chunk tests assume origins
 // in the scene's range, so there the same loop walks its stored sphere rows instead of the chunks.
 // (Diagnostic builds: anyHit's candidate counter, PTSS_DIAG bit 0 slot 4, also counts the occlusion queries' sphere candidates.)
+// The closest hit of one ray per lane, shared by queryKernel (ptss_intersect) and featureKernel (ptss_render_features): one body,
+// two callers. sc: the scene image as staged (LDS or global), sceneBlob: the same in global memory.
+struct QueryHit {
+    vec3 point, normal;
+    float dist;
+    int materialIdx, kind, prim;
+    float w1, w2;
+};
+__device__ __forceinline__ QueryHit closestQuery(const float4* sc, const float4* __restrict__ sceneBlob, const SceneLayout& L, vec3 o, vec3 d, float tmax,
+                                                 bool live) {
+    const bool mesh = meshImage(L);
+    const float4* td = mesh ? sceneBlob : sc;   // the triangle tables (global memory in the mesh image)
+    const int* spherePos = reinterpret_cast<const int*>(sceneBlob + L.offSpherePos);   // (read only with accelSpheres)
+    const int* triPos = reinterpret_cast<const int*>(sceneBlob + L.offTriPos);         // (read only for classed and mesh images)
+    const bool triStoredElsewhere = mesh || L.triClassed;
+    const unsigned long long liveMask = maskOf(live);
+    float dist = tmax;
+    int kind = 0, prim = -1, pos = 0;
+    float w0 = 0, w1 = 0, w2 = 0;
+    for (int k = 0; k < L.numSpheres; ++k) {   // the caller's order, the reference's test
+        const int p = L.accelSpheres ? spherePos[k] : k;
+        float t;
+        if (live && sphereTest(sc[L.offSphere + p], o, d, dist, t)) {
+            dist = t;
+            kind = 1;
+            prim = k;
+            pos = p;
+        }
+    }
+    if (mesh && meshQueryOk(o, d, live) && waveAll(!live || dist > 0.0f)) {
+        TriBest best{dist, kNoTriangle, 0.0f, 0.0f};
+        closestTrianglesMesh<false>(sc, sceneBlob, L, o, d, live, best);
+        if (best.key != kNoTriangle) {
+            dist = best.dist;
+            kind = 2;
+            prim = (int)(0xfffffffeu - best.key);
+            pos = triPos[prim];   // per-lane gather
+            w1 = best.w1;
+            w2 = best.w2;
+            w0 = 1.0f - (w1 + w2);  // Primitives.h:64, from the kept pair
+        }
+    } else {
+        for (int k = 0; k < L.numTriangles; ++k) {   // the guarded loop, in the caller's order
+            const int p = triStoredElsewhere ? triPos[k] : k;
+            const TriHit th = triangleTest(loadTri(td + L.offTri + 3 * p), o, d, dist, liveMask);
+            if (th.hit) {
+                dist = th.dist;
+                kind = 2;
+                prim = k;
+                pos = p;
+                w0 = th.w0;
+                w1 = th.w1;
+                w2 = th.w2;
+            }
+        }
+    }
+    // the SurfaceElement, with bounceTile's operations after its closest hit (Primitives.h:74, :100)
+    vec3 point = v3(0, 0, 0), normal = v3(0, 0, 0);
+    int materialIdx = -1;
+    if (kind != 0) {
+        point = o + d * dist;
+        if (kind == 1) {
+            normal = normalize(point - xyz(loadRow16(sc + L.offSphere + pos)));
+            materialIdx = reinterpret_cast<const int*>(sceneBlob + L.offSphereMat)[pos];
+        } else {
+            const float4* nn = td + L.offTriNormal + 3 * pos;
+            normal = (xyz(loadRow16(nn)) * w0 + xyz(loadRow16(nn + 1)) * w1) + xyz(loadRow16(nn + 2)) * w2;
+            materialIdx = (int)asU(td[L.offTri + 3 * pos].w);
+        }
+    } else {
+        w1 = w2 = 0.0f;
+    }
+    if (kind == 1) w1 = w2 = 0.0f;
+    return QueryHit{point, normal, dist, materialIdx, kind, prim, w1, w2};
+}
+
 template <bool kAny, bool kSceneInLds>
 __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__ sceneBlob, SceneLayout L, const float4* __restrict__ rays,
                                                        float4* __restrict__ out, uint32_t n) {
@@ -2491,10 +2567,6 @@ __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__
         sc = sceneBlob;
     }
     const bool mesh = meshImage(L);
-    const float4* td = mesh ? sceneBlob : sc;   // the triangle tables (global memory in the mesh image)
-    const int* spherePos = reinterpret_cast<const int*>(sceneBlob + L.offSpherePos);   // (read only with accelSpheres)
-    const int* triPos = reinterpret_cast<const int*>(sceneBlob + L.offTriPos);         // (read only for classed and mesh images)
-    const bool triStoredElsewhere = mesh || L.triClassed;
     for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
         const uint32_t i = base + threadIdx.x;
         const bool live = i < n;
@@ -2505,7 +2577,6 @@ __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__
         }
         const vec3 o = xyz(r0), d = xyz(r1);
         const float tmax = r0.w;
-        const unsigned long long liveMask = maskOf(live);
         if constexpr (kAny) {
             bool blocked;
             if (L.accelSpheres) {
@@ -2521,69 +2592,52 @@ __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__
             }
             if (live) reinterpret_cast<uint32_t*>(out)[i] = blocked ? 1u : 0u;
         } else {
-            float dist = tmax;
-            int kind = 0, prim = -1, pos = 0;
-            float w0 = 0, w1 = 0, w2 = 0;
-            for (int k = 0; k < L.numSpheres; ++k) {   // the caller's order, the reference's test
-                const int p = L.accelSpheres ? spherePos[k] : k;
-                float t;
-                if (live && sphereTest(sc[L.offSphere + p], o, d, dist, t)) {
-                    dist = t;
-                    kind = 1;
-                    prim = k;
-                    pos = p;
-                }
-            }
-            if (mesh && meshQueryOk(o, d, live) && waveAll(!live || dist > 0.0f)) {
-                TriBest best{dist, kNoTriangle, 0.0f, 0.0f};
-                closestTrianglesMesh<false>(sc, sceneBlob, L, o, d, live, best);
-                if (best.key != kNoTriangle) {
-                    dist = best.dist;
-                    kind = 2;
-                    prim = (int)(0xfffffffeu - best.key);
-                    pos = triPos[prim];   // per-lane gather
-                    w1 = best.w1;
-                    w2 = best.w2;
-                    w0 = 1.0f - (w1 + w2);  // Primitives.h:64, from the kept pair
-                }
-            } else {
-                for (int k = 0; k < L.numTriangles; ++k) {   // the guarded loop, in the caller's order
-                    const int p = triStoredElsewhere ? triPos[k] : k;
-                    const TriHit th = triangleTest(loadTri(td + L.offTri + 3 * p), o, d, dist, liveMask);
-                    if (th.hit) {
-                        dist = th.dist;
-                        kind = 2;
-                        prim = k;
-                        pos = p;
-                        w0 = th.w0;
-                        w1 = th.w1;
-                        w2 = th.w2;
-                    }
-                }
-            }
-            // the SurfaceElement, with bounceTile's operations after its closest hit (Primitives.h:74, :100)
-            vec3 point = v3(0, 0, 0), normal = v3(0, 0, 0);
-            int materialIdx = -1;
-            if (kind != 0) {
-                point = o + d * dist;
-                if (kind == 1) {
-                    normal = normalize(point - xyz(loadRow16(sc + L.offSphere + pos)));
-                    materialIdx = reinterpret_cast<const int*>(sceneBlob + L.offSphereMat)[pos];
-                } else {
-                    const float4* nn = td + L.offTriNormal + 3 * pos;
-                    normal = (xyz(loadRow16(nn)) * w0 + xyz(loadRow16(nn + 1)) * w1) + xyz(loadRow16(nn + 2)) * w2;
-                    materialIdx = (int)asU(td[L.offTri + 3 * pos].w);
-                }
-            } else {
-                w1 = w2 = 0.0f;
-            }
-            if (kind == 1) w1 = w2 = 0.0f;
+            const QueryHit q = closestQuery(sc, sceneBlob, L, o, d, tmax, live);
             if (live) {
                 float4* h = out + 3 * (size_t)i;
-                h[0] = float4{point.x, point.y, point.z, dist};
-                h[1] = float4{normal.x, normal.y, normal.z, asF((uint32_t)materialIdx)};
-                h[2] = float4{asF((uint32_t)kind), asF((uint32_t)prim), w1, w2};
+                h[0] = float4{q.point.x, q.point.y, q.point.z, q.dist};
+                h[1] = float4{q.normal.x, q.normal.y, q.normal.z, asF((uint32_t)q.materialIdx)};
+                h[2] = float4{asF((uint32_t)q.kind), asF((uint32_t)q.prim), q.w1, q.w2};
             }
+        }
+    }
+}
+
+// ---- FIRST-HIT FEATURES (ptss_render_features) --------------------------------------------------------------
+// One lane per local pixel: the eye ray through the pixel's centre with bounce 0's operations (bounceTile, kFirst; a jitter of
+// 0.5 in place of the two random draws), then closestQuery with tmax = +inf. Like the queries it reads the scene image only.
+template <bool kSceneInLds>
+__global__ __launch_bounds__(kBlock) void featureKernel(const float4* __restrict__ sceneBlob, SceneLayout L, TileMap tile, EyeParams eye,
+                                                         vec3 defaultColor, float4* __restrict__ out, uint32_t n) {
+    extern __shared__ __attribute__((aligned(256))) float4 lds[];
+    const float4* sc;
+    if constexpr (kSceneInLds) {
+        for (int k = threadIdx.x; k < L.ldsVec4; k += kBlock) lds[k] = sceneBlob[k];
+        __syncthreads();
+        sc = lds;
+    } else {
+        sc = sceneBlob;
+    }
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const bool live = i < n;
+        vec3 d = v3(0, 0, 0);
+        if (live) {
+            const PixelCoord pc = locate(tile, i);
+            const float jitteredX = pc.x + 0.5f;
+            const float jitteredY = pc.gy + 0.5f;
+            const vec3 start = v3(((jitteredX * eye.invW) - 0.5f) * eye.s,
+                                  1 * ((jitteredY * eye.invH) - 0.5f) * eye.s * eye.aspect, 1.0f) *
+                               eye.camera.zNear;
+            d = normalize(rotate(eye.camera.rotation, start));
+        }
+        const QueryHit q = closestQuery(sc, sceneBlob, L, eye.camera.position, d, ptm::inf(), live);
+        if (live) {
+            vec3 albedo = defaultColor;
+            if (q.kind != 0) albedo = xyz(loadRow16(sc + L.offMaterial + 5 * q.materialIdx));
+            float4* f = out + 2 * (size_t)i;
+            f[0] = float4{q.normal.x, q.normal.y, q.normal.z, q.dist};
+            f[1] = float4{albedo.x, albedo.y, albedo.z, asF((uint32_t)q.materialIdx)};
         }
     }
 }
@@ -2703,6 +2757,19 @@ hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneL
                        static_cast<float4*>(out), n);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) *launched |= 1ull << (48 + index);
+    return e;
+}
+
+// the feature kernel (bit 52 + inLds of *launched): one workgroup per kBlock local pixels, at most maxBlocks
+hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                          ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launched) {
+    unsigned blocks = blocksFor(n, kBlock);
+    if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
+    const size_t lds = sceneInLds ? (size_t)layout.ldsVec4 * sizeof(float4) : 0;
+    hipLaunchKernelGGL(sceneInLds ? featureKernel<true> : featureKernel<false>, dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, tile, eye,
+                       defaultColor, static_cast<float4*>(out), n);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *launched |= 1ull << (52 + (sceneInLds ? 1 : 0));
     return e;
 }
 

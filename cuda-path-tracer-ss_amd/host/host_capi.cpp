@@ -8,6 +8,7 @@
 
 #include "HostOps.h"
 #include "Scene.h"
+#include "ptdenoise.h"
 #include "ptquant.h"
 #include "ptmesh.h"
 #include "pttri.h"
@@ -190,6 +191,37 @@ int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const
     for (size_t i = 0; i < n; ++i) {
         const vec3 o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
         out[i] = ptmesh::mayTouch(v3(b[0], b[1], b[2]), b[3], v3(b[4], b[5], b[6]), b[7], b[8], b[9], b[10], b[11], o, d, margin) ? 1 : 0;
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
+                       const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float) {
+    if (!accum || !features || !params || width <= 0 || height <= 0) return PTSS_HOST_EINVAL;
+    if (params->structSize != (unsigned int)sizeof(ptss_denoise_params) || params->levels < 0 || params->levels > PTSS_DENOISE_MAX_LEVELS)
+        return PTSS_HOST_EINVAL;
+    if (!(params->sigmaColor > 0.0f) || !(params->sigmaNormal > 0.0f) || !(params->sigmaDepth >= 0.0f)) return PTSS_HOST_EINVAL;
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<vec3> plane[2];
+    plane[0].resize(n);
+    for (size_t p = 0; p < n; ++p) plane[0][p] = ptdn::displayValue(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2], inverseTicks);
+    auto featureAt = [&](int q) { return ptdn::Feature{features[q].normal, features[q].depth, features[q].materialIdx}; };
+    auto depthAt = [&](int q) { return features[q].depth; };
+    int cur = 0;
+    for (int i = 0; i < params->levels; ++i) {   // the passes of ptss_denoise, plane to plane
+        const ptdn::Level lv = ptdn::levelOf(*params, i);
+        const std::vector<vec3>& src = plane[cur];
+        std::vector<vec3>& dst = plane[1 - cur];
+        dst.resize(n);
+        auto colourAt = [&](int q) { return src[(size_t)q]; };
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) dst[(size_t)y * width + x] = ptdn::filterPixel(x, y, width, height, lv, colourAt, featureAt, depthAt);
+        cur = 1 - cur;
+    }
+    for (size_t p = 0; p < n; ++p) {
+        const vec3 v = plane[cur][p];
+        if (out_float) { out_float[3 * p] = v.x; out_float[3 * p + 1] = v.y; out_float[3 * p + 2] = v.z; }
+        if (out_rgba) { out_rgba[4 * p] = ptdn::toByte(v.x); out_rgba[4 * p + 1] = ptdn::toByte(v.y); out_rgba[4 * p + 2] = ptdn::toByte(v.z); out_rgba[4 * p + 3] = 255; }
     }
     return PTSS_HOST_OK;
 }

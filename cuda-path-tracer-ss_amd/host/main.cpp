@@ -11,6 +11,8 @@
 //             [--emulate-gpus N]    the same N shards on device 0, the gather as device copies (rehearsal on a one-GPU box)
 //             [--pick x,y]...       after the ticks and --keys: the closest hit of pixel (x, y)'s centre ray (ptss_camera_ray with
 //                                   jitter 0.5, 0.5, through ptss_intersect) of the final camera, one line per pick
+//             [--denoise [levels]]  with --out image.tga: also image_denoised.tga, the accumulated image through ptss_render_features
+//                                   and ptss_denoise (default parameters; levels 0..6 overrides their level count)
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -29,6 +31,7 @@ int main(int argc, char* argv[]) {
     unsigned bounces = 15;
     unsigned long long seed = 0x5EED;
     bool quiet = false;
+    int denoise = -2;   // --denoise: -2 absent, -1 the default level count, else the level count
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -48,6 +51,10 @@ int main(int argc, char* argv[]) {
             float x, y, z, k;
             if (objs.empty() || sscanf(next(), "%f,%f,%f,%f", &x, &y, &z, &k) != 4) { fprintf(stderr, "bad --obj-at (x,y,z,scale after an --obj)\n"); return 2; }
             objs.back().second = translate(v3(x, y, z)) * scale(v3(k));
+        }
+        else if (a == "--denoise") {
+            denoise = -1;
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise = atoi(next());
         }
         else if (a == "--pick") {
             int x, y;
@@ -86,6 +93,7 @@ int main(int argc, char* argv[]) {
     const ptss_scene_desc desc = scene.desc(defaultColor);
     ptss_context* ctx = NULL;
     if (!picks.empty() && gpus > 0) { fprintf(stderr, "--pick needs one context (no --gpus)\n"); return 2; }
+    if (denoise != -2 && (gpus > 0 || out.empty())) { fprintf(stderr, "--denoise needs --out and one context (no --gpus)\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -117,6 +125,32 @@ int main(int argc, char* argv[]) {
         strncpy(name, out.c_str(), sizeof(name) - 1);
         name[sizeof(name) - 1] = 0;
         saveScreenshot(name, width, height);
+    }
+    if (denoise != -2) {   // the denoised twin of the screenshot: features of the final camera, then the filter
+        ptss_denoise_params params;
+        PTSS_HANDLE(ptss_default_denoise_params(&params));
+        if (denoise >= 0) params.levels = denoise;
+        const size_t n = (size_t)width * (size_t)height;
+        void *df = nullptr, *dp = nullptr;
+        if (hipMalloc(&df, n * sizeof(ptss_pixel_feature)) != hipSuccess || hipMalloc(&dp, n * sizeof(ptss_uchar4)) != hipSuccess) {
+            fprintf(stderr, "--denoise: device buffers\n");
+            return 1;
+        }
+        PTSS_HANDLE(ptss_render_features(ctx, (ptss_pixel_feature*)df, NULL));
+        PTSS_HANDLE(ptss_denoise(ctx, (const ptss_pixel_feature*)df, &params, (ptss_uchar4*)dp, NULL));
+        PTSS_HANDLE(ptss_synchronize(ctx));
+        std::vector<ptss_uchar4> host(n);
+        if (hipMemcpy(host.data(), dp, n * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) {
+            fprintf(stderr, "--denoise: read-back\n");
+            return 1;
+        }
+        (void)hipFree(df);
+        (void)hipFree(dp);
+        std::string name = out;
+        const size_t dot = name.rfind(".tga");
+        if (dot != std::string::npos && dot + 4 == name.size()) name.erase(dot);
+        name += "_denoised.tga";
+        if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--denoise: cannot write %s\n", name.c_str());
     }
     if (!picks.empty()) {   // picking: the pixel-centre ray of the final camera through ptss_intersect
         std::vector<ptss_ray_query> q;

@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ptss_types import (AreaLight, Camera, Material, PointLight, RayHit, RayQuery, SceneDesc, Sphere, Triangle, UChar4, Vec3,
-                        struct_to_dict)
+from ptss_types import (AreaLight, Camera, DenoiseParams, Material, PixelFeature, PointLight, RayHit, RayQuery, SceneDesc, Sphere,
+                        Triangle, UChar4, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -58,6 +58,11 @@ def query_kernels():
     return {("query", kind, lds) for kind in ("closest", "any") for lds in (False, True)}
 
 
+def feature_kernels():
+    """The feature-kernel instantiations (ptss_render_features): ("features", inLds)."""
+    return {("features", lds) for lds in (False, True)}
+
+
 _host = None
 _dev = None
 _hip = None
@@ -73,6 +78,7 @@ def _hip_lib():
         L.hipFree.argtypes = [C.c_void_p]
         L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
         L.hipSetDevice.argtypes = [C.c_int]
+        L.hipDeviceSynchronize.argtypes = []
         _hip = L
     return _hip
 
@@ -106,6 +112,7 @@ def host_lib():
         L.ptss_probe_rng_draw.argtypes = [_u32p, _u32p, _f32p, C.c_size_t]
         L.ptss_probe_rng_jump_table.argtypes = [_u32p, C.c_size_t]
         L.ptss_camera_ray.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RayQuery)]
+        L.ptss_probe_denoise.argtypes = [_u32p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
         _host = L
     return _host
 
@@ -171,6 +178,10 @@ def device_lib():
         L.ptss_triangle_leaves.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptss_intersect.argtypes = [vp, vp, vp, C.c_size_t, vp]
         L.ptss_occluded.argtypes = [vp, vp, vp, C.c_size_t, vp]
+        L.ptss_render_features.argtypes = [vp, vp, vp]
+        L.ptss_default_denoise_params.argtypes = [C.POINTER(DenoiseParams)]
+        L.ptss_denoise.argtypes = [vp, vp, C.POINTER(DenoiseParams), vp, vp]
+        L.ptss_read_denoise_plane.argtypes = [vp, _f32p, C.c_size_t, C.POINTER(C.c_int)]
         L.ptss_error_string.argtypes = [C.c_int]
         L.ptss_error_string.restype = C.c_char_p
         L.ptss_last_error_detail.restype = C.c_char_p
@@ -285,7 +296,35 @@ def move_camera(cam, key):
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("direction", np.float32, 3), ("pad", np.float32)])
 HIT_DTYPE = np.dtype([("point", np.float32, 3), ("distance", np.float32), ("normal", np.float32, 3), ("materialIdx", np.int32),
                       ("kind", np.int32), ("primitive", np.int32), ("w1", np.float32), ("w2", np.float32)])
+FEATURE_DTYPE = np.dtype([("normal", np.float32, 3), ("depth", np.float32), ("albedo", np.float32, 3), ("materialIdx", np.int32)])
 assert RAY_DTYPE.itemsize == C.sizeof(RayQuery) and HIT_DTYPE.itemsize == C.sizeof(RayHit)
+assert FEATURE_DTYPE.itemsize == C.sizeof(PixelFeature)
+
+
+def default_denoise_params(**overrides):
+    """ptss_default_denoise_params, with levels / sigmaColor / sigmaNormal / sigmaDepth overridden by keyword."""
+    p = DenoiseParams()
+    _check(device_lib().ptss_default_denoise_params(C.byref(p)))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def probe_denoise(accum, inverse_ticks, features, width, height, params):
+    """ptss_denoise on the host (csrc/ptdenoise.h): accum (H*W, 3) uint32, features (H*W,) FEATURE_DTYPE, row-major.
+    Returns (rgba (H*W, 4) uint8, the filtered floats (H*W, 3) float32)."""
+    a = np.ascontiguousarray(accum, dtype=np.uint32).reshape(-1, 3)
+    f = np.ascontiguousarray(features, dtype=FEATURE_DTYPE).reshape(-1)
+    if len(a) != width * height or len(f) != width * height:
+        raise ValueError("accum and features must hold width * height pixels")
+    rgba = np.empty((len(a), 4), dtype=np.uint8)
+    flt = np.empty((len(a), 3), dtype=np.float32)
+    rc = host_lib().ptss_probe_denoise(a.ctypes.data_as(_u32p), float(inverse_ticks), f.ctypes.data_as(C.c_void_p), width, height,
+                                       C.byref(params), rgba.ctypes.data_as(C.c_void_p), flt.ctypes.data_as(_f32p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_denoise: {rc}")
+    return rgba, flt
 
 
 def make_rays(origins, directions, tmax=float("inf")):
@@ -372,6 +411,8 @@ class Renderer:
         self.width, self.height = width, height
         self.local_rows = self.local_pixels // width
         self._own_pixels = None
+        self._buffers = {}            # device buffers of features() / denoise(), by name; freed by close()
+        self._have_features = False   # the features buffer holds the CURRENT camera's features
         self.ticks = 1  # GPUAnimBitmap::idle_func's static counter starts at 1 (CudaUtils.h:146)
 
     def close(self):
@@ -380,6 +421,9 @@ class Renderer:
             if self._own_pixels:
                 L.ptss_free_pixels(self._ctx, self._own_pixels)
                 self._own_pixels = None
+            for p in self._buffers.values():
+                _hip_lib().hipFree(p)
+            self._buffers = {}
             L.ptss_destroy(self._ctx)
             self._ctx = C.c_void_p()
 
@@ -423,6 +467,7 @@ class Renderer:
 
     def set_camera(self, cam):
         _check(device_lib().ptss_set_camera(self._ctx, C.byref(cam)))
+        self._have_features = False   # denoise(features=None) renders them again for the new camera
 
     def get_camera(self):
         cam = Camera()
@@ -517,6 +562,11 @@ class Renderer:
         for j in range(4):  # the query kernel: bits 48 + any * 2 + inLds
             if v.value >> (48 + j) & 1:
                 out.add(("query", "any" if j & 2 else "closest", bool(j & 1)))
+        for j in range(2):  # the feature kernel: bits 52 + inLds
+            if v.value >> (52 + j) & 1:
+                out.add(("features", bool(j)))
+        if v.value >> 54 & 1:
+            out.add(("denoise",))
         return out
 
     # --- batched ray queries (ptss_intersect / ptss_occluded) ------------------------------------------
@@ -568,6 +618,71 @@ class Renderer:
             if d_out:
                 H.hipFree(d_out)
         return out
+
+    # --- first-hit features and the denoiser (ptss_render_features / ptss_denoise) ---------------------
+    def _device_buffer(self, name, nbytes):
+        """A device buffer owned by this renderer, allocated once per name and freed by close()."""
+        bufs = self._buffers
+        if name not in bufs:
+            H = _hip_lib()
+            _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
+            p = C.c_void_p()
+            _hip_check(H.hipMalloc(C.byref(p), max(nbytes, 16)), "hipMalloc")
+            bufs[name] = p
+        return bufs[name]
+
+    def features_devptr(self):
+        return self._device_buffer("features", self.local_pixels * FEATURE_DTYPE.itemsize)
+
+    def features(self, stream=None):
+        """The first-hit feature buffer of the current camera: (local_pixels,) FEATURE_DTYPE. The device buffer is kept
+        (features_devptr) and is what denoise() uses by default."""
+        d = self.features_devptr()
+        _check(device_lib().ptss_render_features(self._ctx, d, C.c_void_p(stream) if stream else None))
+        out = np.empty(self.local_pixels, dtype=FEATURE_DTYPE)
+        if self.local_pixels:
+            if stream:
+                _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            self.synchronize()
+            _hip_check(_hip_lib().hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        self._have_features = True
+        return out
+
+    def denoise(self, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None, stream=None):
+        """ptss_denoise of the accumulated image -> (local_pixels, 4) uint8 RGBA. features: None (the buffer of the last
+        features() call, rendered now if there is none or the camera was set since), a FEATURE_DTYPE array to upload, or a device
+        pointer (int). dev_out: a
+        device pointer to write to (e.g. pixels_devptr()); default a buffer of its own."""
+        L = device_lib()
+        if features is None:
+            if not self._have_features:
+                self.features()
+            d_feat = self.features_devptr()
+        elif isinstance(features, int):
+            d_feat = C.c_void_p(features)
+        else:
+            f = np.ascontiguousarray(features, dtype=FEATURE_DTYPE).reshape(-1)
+            if len(f) != self.local_pixels:
+                raise ValueError("features: one entry per local pixel")
+            d_feat = self._device_buffer("features_upload", f.nbytes)
+            _hip_check(_hip_lib().hipMemcpy(d_feat, f.ctypes.data, f.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+        params = default_denoise_params(levels=levels, sigmaColor=sigma_color, sigmaNormal=sigma_normal, sigmaDepth=sigma_depth)
+        if dev_out is None:
+            dev_out = self._device_buffer("denoised", self.local_pixels * 4)
+        elif isinstance(dev_out, int):
+            dev_out = C.c_void_p(dev_out)
+        _check(L.ptss_denoise(self._ctx, d_feat, C.byref(params), dev_out, C.c_void_p(stream) if stream else None))
+        if stream:
+            _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+        return self.pixels(dev_out)
+
+    def denoise_plane(self):
+        """ptss_read_denoise_plane: (the filtered floats (local_pixels, 3) float32 that the last non-final pass of the latest
+        denoise() left, that pass's level index)."""
+        out = np.empty((self.local_pixels, 3), dtype=np.float32)
+        level = C.c_int(-1)
+        _check(device_lib().ptss_read_denoise_plane(self._ctx, out.ctypes.data_as(_f32p), out.size, C.byref(level)))
+        return out, level.value
 
     def triangle_leaves(self):
         """Leaves (16 triangles each) of the mesh image in use; 0 when the image walks every triangle."""

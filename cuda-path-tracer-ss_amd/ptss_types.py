@@ -63,9 +63,18 @@ class RayHit(C.Structure):
                 ("primitive", C.c_int), ("w1", C.c_float), ("w2", C.c_float)]
 
 
+class PixelFeature(C.Structure):
+    _fields_ = [("normal", Vec3), ("depth", C.c_float), ("albedo", Vec3), ("materialIdx", C.c_int)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint), ("levels", C.c_int), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaDepth", C.c_float)]
+
+
 assert C.sizeof(Sphere) == 20 and C.sizeof(Triangle) == 76 and C.sizeof(Material) == 76
 assert C.sizeof(PointLight) == 24 and C.sizeof(AreaLight) == 32 and C.sizeof(Camera) == 40
-assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48
+assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PixelFeature) == 32
 
 
 def struct_to_dict(s):

@@ -156,7 +156,8 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
  * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
  * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
- * ptss_occluded). Recorded on the host at launch. */
+ * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise).
+ * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
 /* Batched ray queries against the context's scene. dev_rays / dev_hits / dev_occluded are DEVICE pointers of n
@@ -170,6 +171,38 @@ int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
  * the device. ptss_launched_kernels reports the query kernel at bit 48 + any * 2 + inLds. */
 int ptss_intersect(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_ray_hit* dev_hits, size_t n, void* hipStream);
 int ptss_occluded(ptss_context* ctx, const ptss_ray_query* dev_rays, uint32_t* dev_occluded, size_t n, void* hipStream);
+
+/* First-hit feature buffer. dev_features: DEVICE pointer to one entry per local pixel, in the order of dev_pixels
+ * and ptss_local_rows. Entry p holds what ptss_intersect returns for ptss_camera_ray(camera, width, height, x, y, 0.5, 0.5) of the
+ * context's CURRENT camera with tmax = +inf — normal, distance, materialIdx — and that material's diffuseColor, every field bit for
+ * bit; a miss: normal 0, depth +inf, materialIdx -1, albedo = the scene's defaultColor. Asynchronous on hipStream (NULL: the
+ * context's stream). Like the queries it reads the scene image only and leaves no trace in frame state; it serves pixel-band shards
+ * (tileWorld > 1) for their own pixels. ptss_launched_kernels reports the feature kernel at bit 52 + inLds. */
+int ptss_render_features(ptss_context* ctx, ptss_pixel_feature* dev_features, void* hipStream);
+
+/* levels 5, sigmaColor 64, sigmaNormal 0.1, sigmaDepth 4 (the values behind the figures of DESIGN.md §3.17). */
+int ptss_default_denoise_params(ptss_denoise_params* p);
+
+/* Edge-avoiding A-trous filter of the accumulated image. Input: the context's integer accumulator (the bound one
+ * if ptss_bind_accumulator was used) times the inverseTicks of the last frame's display value — the tone-mapped mean on the 0..255
+ * scale —, then params->levels passes of the 5x5 B3-spline kernel at tap spacing 2^i, each tap weighted by material (a hard stop),
+ * normal, depth and colour of dev_features (ptss_render_features of the same camera). Output: (unsigned char)(v + 0.5f) per channel,
+ * alpha 255, into dev_out (local pixels; may be the frame's own dev_pixels). levels = 0 writes the frame's display pixels exactly.
+ * The accumulator, the float sums, the RNG records and the counters are only read or not touched: frames rendered afterwards are
+ * the frames rendered without it. Scratch (two colour planes of 16 B per pixel) is allocated by the first call with levels >= 2
+ * and freed by ptss_destroy. Asynchronous on hipStream (NULL: the context's stream); the caller orders it behind the frames whose
+ * accumulator it reads. The planes belong to the context: the denoise calls of ONE context (and ptss_read_denoise_plane) must be
+ * ordered among themselves — the same stream, or an event or a synchronise between two streams. A wrong structSize, a null pointer or levels outside 0..6 return PTSS_EINVAL without touching the device; so does a
+ * sharded context (tileWorld > 1): a band of rows has no neighbours to filter with. ptss_launched_kernels: bit 54. */
+int ptss_denoise(ptss_context* ctx, const ptss_pixel_feature* dev_features, const ptss_denoise_params* params, ptss_uchar4* dev_out,
+                 void* hipStream);
+
+/* Device -> host copy (synchronising on the stream of that call) of the filtered floats the latest ptss_denoise of this context
+ * left in its scratch: the colour plane its last NON-final pass wrote, i.e. the result of level levels - 2 (levels >= 2; the final
+ * pass writes bytes only), 3 floats per local pixel on the 0..255 scale. count = 3 * local pixels; *level (may be NULL) receives
+ * that level's index. PTSS_EINVAL when the latest call ran fewer than two levels (or there was none). With k + 1 levels it returns
+ * what a k-level call converts to bytes: how the tests compare the device's floats with ptss_probe_denoise's. */
+int ptss_read_denoise_plane(ptss_context* ctx, float* host_float3, size_t count, int* level);
 
 /* Leaves of the triangle hierarchy of the scene image in use (16 triangles each), 0 when that image walks
  * every triangle. */

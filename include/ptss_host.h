@@ -69,6 +69,12 @@ int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d
  * finite origin; margin scales its inflation term (1 = the kernels'; smaller values exist to show that a test can catch an
  * under-inflated bound). bound12 (may be NULL) receives the bound's three rows. */
 int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const float* d3, size_t n, float margin, int* out, float* bound12);
+/* ptss_denoise on the host (csrc/ptdenoise.h — the very per-tap weights and accumulation order the kernel evaluates): accum = 3
+ * uint32 per pixel, features = width * height entries, row-major. out_rgba (4 bytes per pixel) and out_float (3 floats per pixel, the
+ * filtered value before the byte conversion) may each be NULL. PTSS_HOST_EINVAL: a null input, a non-positive size, a wrong
+ * structSize or levels outside 0..6. */
+int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
+                       const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6);
 /* n raw draws and the matching (0,1] floats from a state; state advanced in place. */

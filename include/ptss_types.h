@@ -116,6 +116,27 @@ typedef struct ptss_ray_hit {
 #define PTSS_HIT_SPHERE 1
 #define PTSS_HIT_TRIANGLE 2
 
+/* What the centre ray of one pixel hits first (ptss_render_features): 32 B = one memory sector, two 16-byte rows.
+ * normal, depth, materialIdx: ptss_ray_hit.normal, .distance, .materialIdx of that ray; albedo: materials[materialIdx].diffuseColor.
+ * A miss: normal 0, depth +inf, materialIdx -1, albedo = the scene's defaultColor. */
+typedef struct ptss_pixel_feature {
+    ptss_vec3 normal;
+    float depth;
+    ptss_vec3 albedo;
+    int materialIdx;
+} ptss_pixel_feature;
+
+/* Parameters of ptss_denoise (ptss_default_denoise_params fills them in; DESIGN.md §3.17 has the weight functions). */
+typedef struct ptss_denoise_params {
+    unsigned int structSize; /* sizeof(ptss_denoise_params) as the caller compiled it */
+    int levels;              /* A-trous passes, tap spacing 2^i in pass i: 0 (the display value, unfiltered) .. 6 */
+    float sigmaColor;        /* colour tolerance of pass 0 on the 0..255 scale; halves with every pass */
+    float sigmaNormal;       /* tolerance of 1 - cos(angle between the normals) */
+    float sigmaDepth;        /* depth tolerance, in units of the depth change the local slope predicts for the tap's offset */
+} ptss_denoise_params;
+
+#define PTSS_DENOISE_MAX_LEVELS 6
+
 #if defined(__cplusplus)
 static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
               "ptss_ray_query is two 16-byte rows");
@@ -123,6 +144,9 @@ static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) == 
                   offsetof(ptss_ray_hit, materialIdx) == 28 && offsetof(ptss_ray_hit, kind) == 32 &&
                   offsetof(ptss_ray_hit, primitive) == 36 && offsetof(ptss_ray_hit, w1) == 40 && offsetof(ptss_ray_hit, w2) == 44,
               "ptss_ray_hit is three 16-byte rows");
+static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, depth) == 12 && offsetof(ptss_pixel_feature, albedo) == 16 &&
+                  offsetof(ptss_pixel_feature, materialIdx) == 28,
+              "ptss_pixel_feature is two 16-byte rows");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -130,6 +154,9 @@ _Static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) ==
                    offsetof(ptss_ray_hit, materialIdx) == 28 && offsetof(ptss_ray_hit, kind) == 32 &&
                    offsetof(ptss_ray_hit, primitive) == 36 && offsetof(ptss_ray_hit, w1) == 40 && offsetof(ptss_ray_hit, w2) == 44,
                "ptss_ray_hit is three 16-byte rows");
+_Static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, depth) == 12 && offsetof(ptss_pixel_feature, albedo) == 16 &&
+                   offsetof(ptss_pixel_feature, materialIdx) == 28,
+               "ptss_pixel_feature is two 16-byte rows");
 #endif
 
 #ifdef __cplusplus
