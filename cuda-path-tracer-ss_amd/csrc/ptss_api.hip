@@ -99,8 +99,8 @@ struct ptss_context {
     hipEvent_t evFork = nullptr;            // several lanes: the caller's stream has reached this frame
     int countParity = 0;                    // which of a lane's two count buffers the next frame uses
     uint32_t* dRngHome = nullptr;
-    unsigned long long* dTotal = nullptr;   // [0 .. kMaxLanes) ray-bounce totals per lane, [kMaxLanes .. +8) unused,
-                                            // then one word: guard timeouts (must stay 0)
+    unsigned long long* dTotal = nullptr;   // [0 .. kMaxLanes) ray-bounce totals per lane, [kMaxLanes]: records ptss_update_triangles
+                                            // rejected (kRejectedWord), [kMaxLanes + 1 .. +8) unused, then one word: guard timeouts (must stay 0)
     uint32_t* dAccumOwned = nullptr;
     uint32_t* dAccum = nullptr;  // owned or bound
     float* dFsum = nullptr;
@@ -137,8 +137,12 @@ struct ptss_context {
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
     hipStream_t denoiseStream = nullptr;
+    int numCUs = 0;                             // hipDeviceProp_t::multiProcessorCount of cfg.device (sceneState's launch caps)
+    hipStream_t updateStream = nullptr;         // the stream of the latest ptss_update_triangles (its read-backs synchronise on it)
+    bool updated = false;
 };
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
+constexpr int kRejectedWord = ptss::kMaxLanes;
 
 namespace {
 
@@ -646,6 +650,91 @@ hipError_t mallocZeroed(T** p, size_t bytes) {
     return e == hipSuccess ? hipMemset(*p, 0, bytes) : e;
 }
 
+// ---- the scene-dependent part of a context (ptss_create and ptss_set_scene) ------------------------------------------------------
+// Which images the scene gets, their blobs on the device, how the frames read each of them, and the launch caps that follow.
+// Everything else a context owns — pools, random streams, accumulator, counters — does not depend on the scene.
+struct SceneState {
+    SceneImage images[2];
+    int gridCap = 0;
+    float defaultColor[3] = {0, 0, 0};
+};
+void releaseSceneState(SceneState& st) {
+    for (SceneImage& im : st.images) {
+        (void)hipFree(im.dBlob);
+        im = SceneImage{};
+    }
+}
+// Fills `st` (empty on entry) or leaves nothing allocated. numLanes, maxBlocks0: the context's lanes and lane 0's widest grid.
+int buildSceneState(const ptss_scene_desc& scene, const ptss_render_config& cfg, int numLanes, int maxBlocks0, int numCUs, SceneState& st) {
+    // Scenes with many spheres get the chunked image (see accelEligible / packScene), and the plain one as images[1] for cameras
+    // outside its range; cfg.everySphereLoop keeps the plain one only. Scenes of many triangles and few spheres get the mesh image
+    // (meshEligible), which serves every camera (a query outside its derivation walks every triangle); everySphereLoop keeps the
+    // reference's loop over every triangle for them too.
+    const bool wantAccel = accelEligible(scene) && !cfg.everySphereLoop;
+    const bool wantMesh = !wantAccel && meshEligible(scene) && !cfg.everySphereLoop;
+    const int numImages = wantAccel ? 2 : 1;
+    std::vector<float4> blob[2];
+    try {
+        for (int i = 0; i < numImages; ++i) {
+            SceneImage& im = st.images[i];
+            packScene(scene, im.layout, blob[i], wantAccel && i == 0, wantMesh);
+            // Scene access path: images that fit the default 64 KiB dynamic-LDS window are staged in LDS (north_star); larger ones
+            // are read in place (wave-uniform scalar loads + per-lane gathers from global memory) — same kernel, same results, no
+            // size limit. (On the 38-primitive "mixed" scene reading in place measured 16 % slower, profiles/README.md r01.)
+            im.inLds = ptss::bounceLdsBytes(im.layout, true) <= 64 * 1024;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(PTSS_ENOMEM, "scene image (host)");
+    }
+    for (int i = 0; i < numImages; ++i) {
+        hipError_t e = hipMalloc(&st.images[i].dBlob, blob[i].size() * sizeof(float4));
+        if (e == hipSuccess) e = hipMemcpy(st.images[i].dBlob, blob[i].data(), blob[i].size() * sizeof(float4), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            releaseSceneState(st);
+            return createCheck(e, "scene image (device)");
+        }
+    }
+    st.defaultColor[0] = scene.defaultColor.x;
+    st.defaultColor[1] = scene.defaultColor.y;
+    st.defaultColor[2] = scene.defaultColor.z;
+    // Launches wider than 16 resident rounds stop growing: a workgroup then walks several tiles and stages the scene
+    // into LDS once for all of them. One round = CUs x workgroups per CU of THIS scene's bounce kernel (LDS image and
+    // register budget decide: 7 for the 38-primitive scenes, 3-4 for the many-sphere image), so 16 rounds =
+    // CUs x perCU workgroups per shard (kShards = 16 shards). Measured on the mixed scene (256 x 7 = 1,792 per shard):
+    // 448: -4.6 %, 896: -1.3 %, 1,280-3,584: equal, uncapped: -2 % (profiles/README.md).
+    const SceneImage& primary = st.images[0];   // (not recomputed when the frames switch to images[1])
+    const int perCU = ptss::bounceOccupancyBlocksPerCU(primary.layout, primary.inLds, primary.layout.sphereBounded != 0);
+    st.gridCap = numCUs * (perCU > 0 ? perCU : 4) * 16 / ptss::kShards;
+    // One launch per frame (ptss_kernels.hip frameKernel): only when every workgroup of the frame's grid is resident at once —
+    // its workgroups wait for each other — i.e. bounce-0 tiles <= CUs x resident workgroups per CU of THAT kernel with this
+    // scene's LDS image. The occupancy API over-reports by one workgroup per CU for kernels of more than 96 SGPRs
+    // (MI355X_MICROARCH.md, "Residency and cooperative launch"): one is kept in reserve. One lane, scene staged in LDS.
+    // A bounded image runs the bounded or the unbounded frame kernel, as the camera is in range or not: both must fit.
+    auto qualifies = [&](const SceneImage& im) {
+        if (cfg.oneLaunchFrames <= 0 || numLanes != 1 || !im.inLds) return false;   // opt-in (include/ptss.h)
+        if (ptss::meshImage(im.layout)) return false;   // the mesh image has no frame kernel
+        int perCU = ptss::frameOccupancyBlocksPerCU(im.layout, false);
+        if (im.layout.sphereBounded) perCU = std::min(perCU, ptss::frameOccupancyBlocksPerCU(im.layout, true));
+        const int resident = perCU - 1;
+        return resident >= 1 && maxBlocks0 <= numCUs * resident;
+    };
+    for (int i = 0; i < numImages; ++i) st.images[i].oneLaunch = qualifies(st.images[i]);
+#ifdef PTSS_TUNING_KNOBS   // measurement builds only (tools/build_variants.py "knobs"); the shipped library reads no environment
+    if (const char* e = getenv("PTSS_SCENE_PATH")) {
+        if (!strcmp(e, "scalar"))
+            for (int i = 0; i < numImages; ++i) st.images[i].inLds = false;
+    }
+    if (const char* e = getenv("PTSS_GRID_CAP")) st.gridCap = atoi(e);
+#endif
+    return PTSS_OK;
+}
+void adoptSceneState(ptss_context* c, const SceneState& st) {
+    for (int i = 0; i < 2; ++i) c->images[i] = st.images[i];
+    c->gridCap = st.gridCap;
+    for (int k = 0; k < 3; ++k) c->defaultColor[k] = st.defaultColor[k];
+    c->active = 0;
+}
+
 // A lane's device resources (ptss_create). releaseLane frees whatever of them exists: ptss_destroy, also after a failed create.
 int allocLane(Lane& ln, const uint32_t (&shardCount0)[ptss::kShards], bool ownStream) {
     const size_t poolBytes = (size_t)ptss::kRayPlanes * ln.regionCap * ptss::kShards * sizeof(float);
@@ -666,6 +755,29 @@ int allocLane(Lane& ln, const uint32_t (&shardCount0)[ptss::kShards], bool ownSt
     return PTSS_OK;
 }
 #undef ALLOC_TRY
+
+// curandSetupKernel (CudaTracer.cu:722-724): per-pixel subsequence via the 2^67 jump table, on stream st; returns once it has run
+// (ptss_create, ptss_reseed)
+hipError_t seedStreams(ptss_context* c, unsigned long long seed, hipStream_t st) {
+    std::vector<uint32_t> table(ptrng::kJumpTableWords);
+    ptrng::build_subsequence_table(table.data());
+    uint32_t* dTable = nullptr;
+    hipError_t e = hipMalloc(&dTable, table.size() * sizeof(uint32_t));
+    if (e != hipSuccess) return e;
+    e = hipMemcpy(dTable, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && c->numPixels > 0) e = ptss::launchRngInit(st, c->dRngHome, c->capacity, c->samples, c->tile, seed, dTable);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dTable);
+    return e;
+}
+
+// everything this context has enqueued on its own streams has run (ptss_set_scene, ptss_reseed)
+int quiesce(ptss_context* c) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (const Lane& ln : c->lanes)
+        if (ln.stream) HIP_TRY(hipStreamSynchronize(ln.stream));
+    return PTSS_OK;
+}
 
 void releaseLane(Lane& ln) {
     for (hipEvent_t ev : ln.hintEvent)
@@ -1002,9 +1114,6 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
     c->cfg = *cfg;
     c->maxIterations = cfg->maxIterations;
     c->samples = (uint32_t)spp;
-    c->defaultColor[0] = scene->defaultColor.x;
-    c->defaultColor[1] = scene->defaultColor.y;
-    c->defaultColor[2] = scene->defaultColor.z;
     // Camera(), RenderStructs.h:51-52
     c->camera.rotation = q4(1, 0, 0, 0);
     c->camera.position = v3(0, 0, 0);
@@ -1059,29 +1168,15 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         }
     }
 
-    // Scenes with many spheres get the chunked image (see accelEligible / packScene), and the plain one as images[1] for cameras
-    // outside its range; cfg.everySphereLoop keeps the plain one only
-    // outside its range; cfg.everySphereLoop keeps the plain one only. Scenes of many triangles and few spheres get the mesh image
-    // (meshEligible), which serves every camera (a query outside its derivation walks every triangle); everySphereLoop keeps the
-    // reference's loop over every triangle for them too.
-    const bool wantAccel = accelEligible(*scene) && !cfg->everySphereLoop;
-    const bool wantMesh = !wantAccel && meshEligible(*scene) && !cfg->everySphereLoop;
-    const int numImages = wantAccel ? 2 : 1;
-    std::vector<float4> blob[2];
-    for (int i = 0; i < numImages; ++i) {
-        SceneImage& im = c->images[i];
-        packScene(*scene, im.layout, blob[i], wantAccel && i == 0, wantMesh);
-        // Scene access path: images that fit the default 64 KiB dynamic-LDS window are staged in LDS (north_star); larger ones
-        // are read in place (wave-uniform scalar loads + per-lane gathers from global memory) — same kernel, same results, no
-        // size limit. (On the 38-primitive "mixed" scene reading in place measured 16 % slower, profiles/README.md r01.)
-        im.inLds = ptss::bounceLdsBytes(im.layout, true) <= 64 * 1024;
-    }
-
 #define CREATE_TRY(expr) do { if (int _rc = createCheck((expr), #expr)) return (ptss_destroy(c), _rc); } while (0)   // frees what exists
 
-    for (int i = 0; i < numImages; ++i) {
-        CREATE_TRY(hipMalloc(&c->images[i].dBlob, blob[i].size() * sizeof(float4)));
-        CREATE_TRY(hipMemcpy(c->images[i].dBlob, blob[i].data(), blob[i].size() * sizeof(float4), hipMemcpyHostToDevice));
+    {
+        hipDeviceProp_t prop;
+        CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
+        c->numCUs = prop.multiProcessorCount;
+        SceneState st;
+        if (int sceneRc = buildSceneState(*scene, *cfg, numLanes, c->lanes[0].maxBlocks, c->numCUs, st)) return (ptss_destroy(c), sceneRc);
+        adoptSceneState(c, st);
     }
     CREATE_TRY(hipMalloc(&c->dRngHome, (size_t)ptss::kHomeWords * c->capacity * c->samples * sizeof(uint32_t)));
     for (int k = 0; k < numLanes; ++k)
@@ -1102,55 +1197,10 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
     CREATE_TRY(hipEventCreate(&c->evStop));
     CREATE_TRY(hipEventCreate(&c->evEpoch));
 
-    // curandSetupKernel (CudaTracer.cu:722-724): per-pixel subsequence via the 2^67 jump table
-    {
-        std::vector<uint32_t> table(ptrng::kJumpTableWords);
-        ptrng::build_subsequence_table(table.data());
-        uint32_t* dTable = nullptr;
-        CREATE_TRY(hipMalloc(&dTable, table.size() * sizeof(uint32_t)));
-        hipError_t e1 = hipMemcpy(dTable, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-        hipError_t e2 = e1;
-        if (e1 == hipSuccess && c->numPixels > 0)
-            e2 = ptss::launchRngInit(nullptr, c->dRngHome, c->capacity, c->samples, c->tile, cfg->seed, dTable);
-        hipError_t e3 = e2 == hipSuccess ? hipEventRecord(c->evEpoch, nullptr) : e2;
-        if (e3 == hipSuccess) e3 = hipDeviceSynchronize();
-        (void)hipFree(dTable);
-        CREATE_TRY(e3);
-    }
+    CREATE_TRY(seedStreams(c, cfg->seed, nullptr));
+    CREATE_TRY(hipEventRecord(c->evEpoch, nullptr));
+    CREATE_TRY(hipDeviceSynchronize());
 
-    {
-        // Launches wider than 16 resident rounds stop growing: a workgroup then walks several tiles and stages the scene
-        // into LDS once for all of them. One round = CUs x workgroups per CU of THIS scene's bounce kernel (LDS image and
-        // register budget decide: 7 for the 38-primitive scenes, 3-4 for the many-sphere image), so 16 rounds =
-        // CUs x perCU workgroups per shard (kShards = 16 shards). Measured on the mixed scene (256 x 7 = 1,792 per shard):
-        // 448: -4.6 %, 896: -1.3 %, 1,280-3,584: equal, uncapped: -2 % (profiles/README.md).
-        hipDeviceProp_t prop;
-        CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
-        const SceneImage& primary = c->images[0];   // (not recomputed when the frames switch to images[1])
-        const int perCU = ptss::bounceOccupancyBlocksPerCU(primary.layout, primary.inLds, primary.layout.sphereBounded != 0);
-        c->gridCap = prop.multiProcessorCount * (perCU > 0 ? perCU : 4) * 16 / ptss::kShards;
-        // One launch per frame (ptss_kernels.hip frameKernel): only when every workgroup of the frame's grid is resident at once —
-        // its workgroups wait for each other — i.e. bounce-0 tiles <= CUs x resident workgroups per CU of THAT kernel with this
-        // scene's LDS image. The occupancy API over-reports by one workgroup per CU for kernels of more than 96 SGPRs
-        // (MI355X_MICROARCH.md, "Residency and cooperative launch"): one is kept in reserve. One lane, scene staged in LDS.
-        // A bounded image runs the bounded or the unbounded frame kernel, as the camera is in range or not: both must fit.
-        auto qualifies = [&](const SceneImage& im) {
-            if (cfg->oneLaunchFrames <= 0 || numLanes != 1 || !im.inLds) return false;   // opt-in (include/ptss.h)
-            if (ptss::meshImage(im.layout)) return false;   // the mesh image has no frame kernel
-            int perCU = ptss::frameOccupancyBlocksPerCU(im.layout, false);
-            if (im.layout.sphereBounded) perCU = std::min(perCU, ptss::frameOccupancyBlocksPerCU(im.layout, true));
-            const int resident = perCU - 1;
-            return resident >= 1 && c->lanes[0].maxBlocks <= prop.multiProcessorCount * resident;
-        };
-        for (int i = 0; i < numImages; ++i) c->images[i].oneLaunch = qualifies(c->images[i]);
-#ifdef PTSS_TUNING_KNOBS   // measurement builds only (tools/build_variants.py "knobs"); the shipped library reads no environment
-        if (const char* e = getenv("PTSS_SCENE_PATH")) {
-            if (!strcmp(e, "scalar"))
-                for (SceneImage& im : c->images) im.inLds = false;
-        }
-        if (const char* e = getenv("PTSS_GRID_CAP")) c->gridCap = atoi(e);
-#endif
-    }
 #undef CREATE_TRY
 
     *out = c;
@@ -1558,6 +1608,97 @@ int ptss_read_denoise_plane(ptss_context* c, float* host_float3, size_t count, i
         host_float3[3 * p + 2] = plane[p].z;
     }
     if (level) *level = c->denoiseLastLevel;
+    return PTSS_OK;
+}
+
+// ---- scene updates on a live context -----------------------------------------------------------------------------
+int ptss_set_scene(ptss_context* c, const ptss_scene_desc* scene) {
+    if (!c || !scene) return fail(PTSS_EINVAL, "null argument");
+    RC_TRY(validateScene(*scene));
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    SceneState st;   // the new blobs exist before the old ones go: on any error the context keeps its scene
+    RC_TRY(buildSceneState(*scene, c->cfg, (int)c->lanes.size(), c->lanes[0].maxBlocks, c->numCUs, st));
+    if (int rc = quiesce(c)) {
+        releaseSceneState(st);
+        return rc;
+    }
+    if (c->updated) (void)hipStreamSynchronize(c->updateStream);
+    harvestHints(c);   // (every read-back has landed) ... and the old scene's live counts say nothing about the new one's
+    for (Lane& ln : c->lanes) ln.haveHint = false;
+    for (SceneImage& im : c->images) (void)hipFree(im.dBlob);
+    adoptSceneState(c, st);
+    c->cameraDirty = true;
+    c->resetTicksThisFrame = true;
+    return PTSS_OK;
+}
+
+int ptss_update_triangles(ptss_context* c, const ptss_triangle* dev_triangles, size_t first, size_t count, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (count == 0) return PTSS_OK;
+    if (!dev_triangles) return fail(PTSS_EINVAL, "dev_triangles is null with count > 0");
+    if ((uintptr_t)dev_triangles & 3u) return fail(PTSS_EINVAL, "dev_triangles must be 4-byte aligned");
+    const size_t T = (size_t)c->images[0].layout.numTriangles;
+    if (first >= T || count > T - first) return fail(PTSS_ERANGE, "first .. first + count - 1 leaves the scene's triangles");
+    for (const SceneImage& im : c->images)
+        if (im.dBlob && im.layout.triClassed)
+            return fail(PTSS_EINVAL, "the scene image stores its triangles grouped by edge class (T <= 255), an order that depends on the "
+                                     "vertices: replace the scene with ptss_set_scene (repacking so small a scene costs microseconds)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    unsigned long long* rejected = c->dTotal + kRejectedWord;
+    for (SceneImage& im : c->images) {
+        if (!im.dBlob) continue;
+        HIP_TRY(ptss::launchSceneUpdate(st, im.dBlob, im.layout, dev_triangles, (uint32_t)first, (uint32_t)count, rejected, &c->launchedKernels));
+        rejected = nullptr;   // the second image drops the same records: counted once
+        if (ptss::meshImage(im.layout)) HIP_TRY(ptss::launchMeshRefit(st, im.dBlob, im.layout, &c->launchedKernels));
+    }
+    c->updateStream = st;
+    c->updated = true;
+    c->cameraDirty = true;   // the camera-origin rows (offPrimTri) belong to the old vertices
+    c->resetTicksThisFrame = true;
+    return PTSS_OK;
+}
+
+int ptss_update_rejected(ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->updated) HIP_TRY(hipStreamSynchronize(c->updateStream));
+    HIP_TRY(hipMemcpy(out, c->dTotal + kRejectedWord, sizeof(*out), hipMemcpyDeviceToHost));
+    return PTSS_OK;
+}
+
+int ptss_reseed(ptss_context* c, unsigned long long seed) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    RC_TRY(quiesce(c));   // no lane is still drawing from the streams
+    if (int rc = createCheck(seedStreams(c, seed, c->stream), "ptss_reseed: rngInitKernel")) return rc;
+    c->cfg.seed = seed;
+    c->resetTicksThisFrame = true;
+    return PTSS_OK;
+}
+
+int ptss_read_triangle_bounds(ptss_context* c, float* host, size_t count) {
+    if (!c || !host) return fail(PTSS_EINVAL, "null argument");
+    const SceneImage& im = c->image();
+    if (!ptss::meshImage(im.layout)) return fail(PTSS_EINVAL, "the scene image in use is not a mesh image");
+    const size_t leaves = (size_t)im.layout.mesh.numLeaves, groups = (size_t)im.layout.mesh.numGroups;
+    if (count != 12 * (leaves + groups)) return fail(PTSS_ERANGE, "count must be 12 * (leaves + groups)");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->updated) HIP_TRY(hipStreamSynchronize(c->updateStream));
+    HIP_TRY(hipMemcpy(host, im.dBlob + im.layout.mesh.offLeaf, 12 * leaves * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(host + 12 * leaves, im.dBlob + im.layout.mesh.offGroup, 12 * groups * sizeof(float), hipMemcpyDeviceToHost));
+    return PTSS_OK;
+}
+
+int ptss_read_triangle_positions(ptss_context* c, int* host, size_t count) {
+    if (!c || !host) return fail(PTSS_EINVAL, "null argument");
+    const SceneImage& im = c->image();
+    if (!ptss::meshImage(im.layout)) return fail(PTSS_EINVAL, "the scene image in use is not a mesh image");
+    if (count != (size_t)im.layout.numTriangles) return fail(PTSS_ERANGE, "count must be the scene's triangle count");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(host, im.dBlob + im.layout.offTriPos, count * sizeof(int), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }
 

@@ -246,5 +246,12 @@ hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout l
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,
                          const ptdn::Level& level, float inverseTicks, unsigned long long* launched);
+// ptss_update_triangles (ptss_update.hip). launchSceneUpdate: `count` caller records (76 B each, a device pointer) replace the
+// vertices and normals of the triangles with original indices first .. first + count - 1 (bit 55 of *launched); rejected: the
+// device counter of records left unwritten, or nullptr not to count (the second image of a context sees the same records).
+// launchMeshRefit: every leaf and group bound of a mesh image recomputed from its stored rows (bit 56).
+hipError_t launchSceneUpdate(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, const void* records, uint32_t first, uint32_t count,
+                             unsigned long long* rejected, unsigned long long* launched);
+hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, unsigned long long* launched);
 
 }  // namespace ptss

@@ -195,6 +195,25 @@ int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const
     return PTSS_HOST_OK;
 }
 
+int ptss_probe_mesh_refit(const float* tri9, size_t ntri, float* bounds12) {
+    if (!tri9 || !bounds12 || ntri == 0 || ntri > (1u << 20)) return PTSS_HOST_EINVAL;
+    const size_t leaves = (ntri + 15) / 16, groups = (leaves + 15) / 16;
+    for (size_t k = 0; k < leaves; ++k)
+        ptmesh::refitBound(tri9 + 9 * 16 * k, (int)(ntri - 16 * k < 16 ? ntri - 16 * k : 16), 16, bounds12 + 12 * k);
+    for (size_t g = 0; g < groups; ++g)
+        ptmesh::refitBound(tri9 + 9 * 256 * g, (int)(ntri - 256 * g < 256 ? ntri - 256 * g : 256), ptmesh::kRefitSlots, bounds12 + 12 * (leaves + g));
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_mesh_touch(const float* b, const float* o3, const float* d3, size_t n, float margin, int* out) {
+    if (!b || (n && (!o3 || !d3 || !out))) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        const vec3 o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
+        out[i] = ptmesh::mayTouch(v3(b[0], b[1], b[2]), b[3], v3(b[4], b[5], b[6]), b[7], b[8], b[9], b[10], b[11], o, d, margin) ? 1 : 0;
+    }
+    return PTSS_HOST_OK;
+}
+
 int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
                        const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float) {
     if (!accum || !features || !params || width <= 0 || height <= 0) return PTSS_HOST_EINVAL;

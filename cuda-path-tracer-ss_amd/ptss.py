@@ -112,6 +112,8 @@ def host_lib():
         L.ptss_probe_rng_draw.argtypes = [_u32p, _u32p, _f32p, C.c_size_t]
         L.ptss_probe_rng_jump_table.argtypes = [_u32p, C.c_size_t]
         L.ptss_camera_ray.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RayQuery)]
+        L.ptss_probe_mesh_refit.argtypes = [_f32p, C.c_size_t, _f32p]
+        L.ptss_probe_mesh_touch.argtypes = [_f32p, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int)]
         L.ptss_probe_denoise.argtypes = [_u32p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
         _host = L
     return _host
@@ -182,6 +184,12 @@ def device_lib():
         L.ptss_default_denoise_params.argtypes = [C.POINTER(DenoiseParams)]
         L.ptss_denoise.argtypes = [vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptss_read_denoise_plane.argtypes = [vp, _f32p, C.c_size_t, C.POINTER(C.c_int)]
+        L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
+        L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+        L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_reseed.argtypes = [vp, C.c_ulonglong]
+        L.ptss_read_triangle_bounds.argtypes = [vp, _f32p, C.c_size_t]
+        L.ptss_read_triangle_positions.argtypes = [vp, C.POINTER(C.c_int), C.c_size_t]
         L.ptss_error_string.argtypes = [C.c_int]
         L.ptss_error_string.restype = C.c_char_p
         L.ptss_last_error_detail.restype = C.c_char_p
@@ -281,6 +289,31 @@ def probe_mesh_bound(tris, origins, directions, margin=1.0):
     return out, bound
 
 
+def probe_mesh_refit(tris):
+    """csrc/ptmesh.h refitBound on the host: `tris` ((n, 9) floats {v0, e1, e2} in STORED order) -> (leaves + groups, 12) float32,
+    the leaves' bounds first, then the groups' — what Renderer.triangle_bounds() returns after update_triangles, bit for bit."""
+    t = np.ascontiguousarray(np.asarray(tris, dtype=np.float32).reshape(-1, 9))
+    leaves = (len(t) + 15) // 16
+    out = np.zeros((leaves + (leaves + 15) // 16, 12), dtype=np.float32)
+    rc = host_lib().ptss_probe_mesh_refit(t.ctypes.data_as(_f32p), len(t), out.ctypes.data_as(_f32p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_mesh_refit: {rc}")
+    return out
+
+
+def probe_mesh_touch(bound, origins, directions, margin=1.0):
+    """ptmesh.h mayTouch of ONE given bound (12 floats) for each ray: 1 may be accepted by a triangle inside, 0 provably not."""
+    b = np.ascontiguousarray(np.asarray(bound, dtype=np.float32).reshape(12))
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float32).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(directions, dtype=np.float32).reshape(-1, 3))
+    out = np.zeros(len(o), dtype=np.int32)
+    rc = host_lib().ptss_probe_mesh_touch(b.ctypes.data_as(_f32p), o.ctypes.data_as(_f32p), d.ctypes.data_as(_f32p), len(o), float(margin),
+                                          out.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_mesh_touch: {rc}")
+    return out
+
+
 def default_camera():
     cam = Camera()
     host_lib().ptss_camera_default(C.byref(cam))
@@ -296,6 +329,9 @@ def move_camera(cam, key):
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("direction", np.float32, 3), ("pad", np.float32)])
 HIT_DTYPE = np.dtype([("point", np.float32, 3), ("distance", np.float32), ("normal", np.float32, 3), ("materialIdx", np.int32),
                       ("kind", np.int32), ("primitive", np.int32), ("w1", np.float32), ("w2", np.float32)])
+TRIANGLE_DTYPE = np.dtype([("vertex0", np.float32, 3), ("vertex1", np.float32, 3), ("vertex2", np.float32, 3), ("normal0", np.float32, 3),
+                           ("normal1", np.float32, 3), ("normal2", np.float32, 3), ("materialIdx", np.int32)])
+assert TRIANGLE_DTYPE.itemsize == C.sizeof(Triangle)
 FEATURE_DTYPE = np.dtype([("normal", np.float32, 3), ("depth", np.float32), ("albedo", np.float32, 3), ("materialIdx", np.int32)])
 assert RAY_DTYPE.itemsize == C.sizeof(RayQuery) and HIT_DTYPE.itemsize == C.sizeof(RayHit)
 assert FEATURE_DTYPE.itemsize == C.sizeof(PixelFeature)
@@ -567,6 +603,67 @@ class Renderer:
                 out.add(("features", bool(j)))
         if v.value >> 54 & 1:
             out.add(("denoise",))
+        if v.value >> 55 & 1:
+            out.add(("update",))
+        if v.value >> 56 & 1:
+            out.add(("refit",))
+        return out
+
+    # --- scene updates (ptss_set_scene / ptss_update_triangles / ptss_reseed) -------------------------------------
+    def set_scene(self, scene):
+        """ptss_set_scene: replaces the whole scene (a ptss.Scene or anything with a .desc); the context keeps its pools, random
+        streams, camera and counters and starts a new accumulation."""
+        _check(device_lib().ptss_set_scene(self._ctx, C.byref(scene.desc)))
+        self._scene = scene
+        self._have_features = False
+
+    def update_triangles(self, triangles, first=0, stream=None):
+        """ptss_update_triangles: new vertices and normals for the triangles with original indices first .. first + n - 1.
+        triangles: an (n,) TRIANGLE_DTYPE array (uploaded; the call returns once the update has run), or a contiguous float32
+        device tensor of n x 19 words in that layout, whose pointer is passed — asynchronous on `stream` (a raw stream handle;
+        default: the tensor's current torch stream)."""
+        L = device_lib()
+        if type(triangles).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            if triangles.dtype != torch.float32 or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() % 19:
+                raise ValueError("triangles: a contiguous float32 device tensor of n x 19 words")
+            if stream is None:
+                stream = torch.cuda.current_stream(triangles.device).cuda_stream
+            _check(L.ptss_update_triangles(self._ctx, C.c_void_p(triangles.data_ptr()), first, triangles.numel() // 19, C.c_void_p(stream)))
+        else:
+            a = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+            d = self._device_buffer_at_least("triangles_upload", a.nbytes) if len(a) else None
+            if len(a):   # (every earlier upload has been consumed: this path returns only once its update has run)
+                _hip_check(_hip_lib().hipMemcpy(d, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+            _check(L.ptss_update_triangles(self._ctx, d, first, len(a), C.c_void_p(stream) if stream else None))
+            if len(a):
+                if stream:
+                    _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+                self.synchronize()
+        self._have_features = False
+
+    def reseed(self, seed):
+        """ptss_reseed: the random streams of a context created with this seed, and a reset."""
+        _check(device_lib().ptss_reseed(self._ctx, seed))
+
+    def update_rejected(self):
+        """Records update_triangles has refused (a vertex not finite or beyond 2^40) since the context was created."""
+        v = C.c_ulonglong()
+        _check(device_lib().ptss_update_rejected(self._ctx, C.byref(v)))
+        return v.value
+
+    def triangle_bounds(self):
+        """ptss_read_triangle_bounds: (leaves + groups, 12) float32, the leaves' bounds first (mesh images only)."""
+        leaves = self.triangle_leaves()
+        out = np.empty((leaves + (leaves + 15) // 16, 12), dtype=np.float32)
+        _check(device_lib().ptss_read_triangle_bounds(self._ctx, out.ctypes.data_as(_f32p), out.size))
+        return out
+
+    def triangle_positions(self, count):
+        """ptss_read_triangle_positions: the stored position of each of the scene's `count` original triangle indices."""
+        out = np.empty(count, dtype=np.int32)
+        _check(device_lib().ptss_read_triangle_positions(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
         return out
 
     # --- batched ray queries (ptss_intersect / ptss_occluded) ------------------------------------------
@@ -630,6 +727,15 @@ class Renderer:
             _hip_check(H.hipMalloc(C.byref(p), max(nbytes, 16)), "hipMalloc")
             bufs[name] = p
         return bufs[name]
+
+    def _device_buffer_at_least(self, name, nbytes):
+        """Like _device_buffer, but grown when a later call needs more."""
+        have = getattr(self, "_buffer_bytes", {})
+        if name in self._buffers and have.get(name, 0) < nbytes:
+            _hip_lib().hipFree(self._buffers.pop(name))
+        have[name] = max(have.get(name, 0), nbytes)
+        self._buffer_bytes = have
+        return self._device_buffer(name, nbytes)
 
     def features_devptr(self):
         return self._device_buffer("features", self.local_pixels * FEATURE_DTYPE.itemsize)

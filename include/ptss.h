@@ -156,8 +156,8 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
  * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
  * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
- * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise).
- * Recorded on the host at launch. */
+ * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise);
+ * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles). Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
 /* Batched ray queries against the context's scene. dev_rays / dev_hits / dev_occluded are DEVICE pointers of n
@@ -207,6 +207,47 @@ int ptss_read_denoise_plane(ptss_context* ctx, float* host_float3, size_t count,
 /* Leaves of the triangle hierarchy of the scene image in use (16 triangles each), 0 when that image walks
  * every triangle. */
 int ptss_triangle_leaves(const ptss_context* ctx, int* out);
+
+/* ---- Updating the scene of a live context ----
+ * ptss_set_scene: replaces the WHOLE scene (host path). The scene is validated and its new image(s) are packed and uploaded
+ * before the old ones are freed: on any error, allocation failure included, the context keeps its old scene untouched. The image
+ * kind may change (plain / edge-classed, mesh, many-sphere) in either direction. The call waits for the work this context has
+ * enqueued on its stream and on its lanes, then sets the reset flag and marks the camera rows stale. Pools, random streams,
+ * camera, mode, maxIterations, cumulative counters (ptss_total_ray_bounces, ptss_launched_kernels, ptss_update_rejected), a bound
+ * accumulator and the denoise planes are kept: afterwards the context behaves as a fresh ptss_create(scene, cfg) would, except
+ * for the state of its random streams (ptss_reseed) and those counters. Scene arrays are copied, as by ptss_create. */
+int ptss_set_scene(ptss_context* ctx, const ptss_scene_desc* scene);
+
+/* ptss_update_triangles: new vertex data that is ALREADY ON THE DEVICE (device path, no host round trip). dev_triangles: DEVICE
+ * pointer to `count` records in the caller's 76-byte layout; they replace the vertices and normals of the triangles with original
+ * indices first .. first + count - 1. materialIdx of the records is ignored: the number of triangles, their materials and their
+ * stored order do not change. A mesh image has every leaf and group bound refitted around the new vertices, exactly as
+ * conservatively as a freshly packed image's (csrc/ptmesh.h), but keeps the kd order of the pose the scene was packed in: a
+ * strongly deformed mesh culls worse and renders the same image; ptss_set_scene rebuilds the order. A context with two images
+ * (many spheres) has both updated. Asynchronous on hipStream (NULL: the context's stream, i.e. behind the frames already
+ * enqueued); the caller orders the call against frames and queries that read the scene, under the rules of ptss_denoise. The host
+ * side of the call marks the camera rows stale and requests a reset.
+ * A record with a vertex that is not finite or lies beyond |coordinate| <= 2^40 is NOT written — the triangle keeps its old
+ * geometry — and a device counter grows (ptss_update_rejected): the image never leaves the range its kernels were proven for.
+ * Normals are copied as given, whatever their bits.
+ * Refused without touching the device: a null context or a null pointer with count > 0 (PTSS_EINVAL); a range that leaves
+ * [0, numTriangles) (PTSS_ERANGE); an edge-classed image (T <= 255: PTSS_EINVAL — its storage order depends on the edges; use
+ * ptss_set_scene). count = 0 returns PTSS_OK. ptss_launched_kernels: bit 55 (the update), bit 56 (the refit, mesh images only). */
+int ptss_update_triangles(ptss_context* ctx, const ptss_triangle* dev_triangles, size_t first, size_t count, void* hipStream);
+/* Records ptss_update_triangles has refused since ptss_create (synchronises on the stream of the latest update). */
+int ptss_update_rejected(ptss_context* ctx, unsigned long long* out);
+
+/* Re-runs the random-stream set-up (curandSetupKernel, CudaTracer.cu:22-29) with `seed` and requests a reset: afterwards the
+ * streams are those of a context created with cfg.seed = seed, so frame N of an animation need not depend on what was rendered
+ * before it. Waits for the context's outstanding frames first; returns once the streams are seeded. */
+int ptss_reseed(ptss_context* ctx, unsigned long long seed);
+
+/* Device -> host copies (synchronising) of the mesh image in use, for tests and tools; PTSS_EINVAL when that image is not a mesh
+ * image. Bounds: 12 floats each (csrc/ptmesh.h), the leaves first, then the groups; count = 12 * (leaves + groups), leaves =
+ * ptss_triangle_leaves, groups = ceil(leaves / 16). Positions: the stored position of each original triangle index; count =
+ * the scene's triangle count. */
+int ptss_read_triangle_bounds(ptss_context* ctx, float* host, size_t count);
+int ptss_read_triangle_positions(ptss_context* ctx, int* host, size_t count);
 
 /* Diagnostic builds only (-DPTSS_DIAG=<bits>, csrc/ptss_diag.h, tools/build_variants.py): the eight counter words of that
  * build (sphere candidates per lane, scatter blocks, chunk culling, shadow-segment pairs, queue lengths); all zero in the

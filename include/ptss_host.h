@@ -69,6 +69,13 @@ int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d
  * finite origin; margin scales its inflation term (1 = the kernels'; smaller values exist to show that a test can catch an
  * under-inflated bound). bound12 (may be NULL) receives the bound's three rows. */
 int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const float* d3, size_t n, float margin, int* out, float* bound12);
+/* The REFIT of the mesh image's bounds on the host (csrc/ptmesh.h refitBound — the very arithmetic and reduction shape of
+ * meshRefitKernel, ptss_update_triangles): tri9 holds ntri triangles {v0, e1, e2} in STORED order; bounds12 receives 12 floats
+ * per bound, the ceil(ntri / 16) leaves first, then the ceil(leaves / 16) groups — what ptss_read_triangle_bounds returns after a
+ * refit, bit for bit. */
+int ptss_probe_mesh_refit(const float* tri9, size_t ntri, float* bounds12);
+/* ptmesh.h mayTouch for n rays against ONE given bound (12 floats), margin as in ptss_probe_mesh_bound. */
+int ptss_probe_mesh_touch(const float* bound12, const float* o3, const float* d3, size_t n, float margin, int* out);
 /* ptss_denoise on the host (csrc/ptdenoise.h — the very per-tap weights and accumulation order the kernel evaluates): accum = 3
  * uint32 per pixel, features = width * height entries, row-major. out_rgba (4 bytes per pixel) and out_float (3 floats per pixel, the
  * filtered value before the byte conversion) may each be NULL. PTSS_HOST_EINVAL: a null input, a non-positive size, a wrong
