@@ -20,6 +20,7 @@
 #include <cmath>
 #include "ptquant.h"
 #include "ptdenoise.h"
+#include "ptreproject.h"
 #include "ptmesh.h"
 #include "pttri.h"
 
@@ -1556,19 +1557,23 @@ int ptss_default_denoise_params(ptss_denoise_params* p) {
     return PTSS_OK;
 }
 
-int ptss_denoise(ptss_context* c, const ptss_pixel_feature* dev_features, const ptss_denoise_params* params, ptss_uchar4* dev_out,
-                 void* hipStream) {
+// ptss_denoise / ptss_denoise_history: the passes over the context's integer accumulator (fromAccumulator) or over `input`, a plane of
+// float4 colours
+static int denoisePasses(ptss_context* c, const char* what, const void* input, bool fromAccumulator, const ptss_pixel_feature* dev_features,
+                         const ptss_denoise_params* params, ptss_uchar4* dev_out, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (!dev_features || !params || !dev_out) return fail(PTSS_EINVAL, "null argument");
+    if (!dev_features || !params || !dev_out || (!fromAccumulator && !input)) return fail(PTSS_EINVAL, "null argument");
     if (params->structSize != (unsigned int)sizeof(ptss_denoise_params))
         return fail(PTSS_EINVAL, "params->structSize is not this library's sizeof(ptss_denoise_params): start from ptss_default_denoise_params");
     if (params->levels < 0 || params->levels > PTSS_DENOISE_MAX_LEVELS) return fail(PTSS_EINVAL, "levels must be in [0, 6]");
     if (!(params->sigmaColor > 0.0f) || !(params->sigmaNormal > 0.0f) || !(params->sigmaDepth >= 0.0f))
         return fail(PTSS_EINVAL, "sigmaColor and sigmaNormal must be positive, sigmaDepth not negative");
     if (((uintptr_t)dev_features & 15u) || ((uintptr_t)dev_out & 3u)) return fail(PTSS_EINVAL, "dev_features must be 16-byte aligned, dev_out 4-byte aligned");
+    if (!fromAccumulator && ((uintptr_t)input & 15u)) return fail(PTSS_EINVAL, "dev_history must be 16-byte aligned");
     if (c->tile.world > 1)
-        return fail(PTSS_EINVAL, "ptss_denoise needs the whole frame: this context is a pixel-band shard (tileWorld > 1), whose bands of rows "
-                                 "have no neighbours to filter with");
+        return fail(PTSS_EINVAL, (std::string(what) + " needs the whole frame: this context is a pixel-band shard (tileWorld > 1), whose bands of "
+                                                       "rows have no neighbours to filter with").c_str());
+    if (fromAccumulator) input = c->dAccum;
     HIP_TRY(hipSetDevice(c->cfg.device));
     hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
     const int levels = params->levels;
@@ -1586,11 +1591,60 @@ int ptss_denoise(ptss_context* c, const ptss_pixel_feature* dev_features, const 
     c->denoiseStream = st;
     for (int i = 0; i < (levels > 0 ? levels : 1); ++i) {
         const bool first = i == 0, last = i + 1 >= levels;
-        const void* src = first ? static_cast<const void*>(c->dAccum) : c->dDenoise[(i - 1) & 1];
+        const void* src = first ? input : c->dDenoise[(i - 1) & 1];
         void* dst = last ? static_cast<void*>(dev_out) : c->dDenoise[i & 1];
-        HIP_TRY(ptss::launchDenoise(st, first, last, src, dst, dev_features, width, height, ptdn::levelOf(*params, i), inverseTicks,
+        HIP_TRY(ptss::launchDenoise(st, first && fromAccumulator, last, src, dst, dev_features, width, height, ptdn::levelOf(*params, i), inverseTicks,
                                     &c->launchedKernels));
     }
+    return PTSS_OK;
+}
+
+int ptss_denoise(ptss_context* c, const ptss_pixel_feature* dev_features, const ptss_denoise_params* params, ptss_uchar4* dev_out,
+                 void* hipStream) {
+    return denoisePasses(c, "ptss_denoise", nullptr, true, dev_features, params, dev_out, hipStream);
+}
+
+// the same passes over the colours of a history: an entry is laid out as a colour-plane entry, so every pass is a denoiseKernel<false, *>
+int ptss_denoise_history(ptss_context* c, const ptss_history_entry* dev_history, const ptss_pixel_feature* dev_features,
+                         const ptss_denoise_params* params, ptss_uchar4* dev_out, void* hipStream) {
+    return denoisePasses(c, "ptss_denoise_history", dev_history, false, dev_features, params, dev_out, hipStream);
+}
+
+int ptss_default_reproject_params(ptss_reproject_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(*p);
+    p->cosNormal = 0.9f;
+    p->depthTolerance = 0.02f;
+    p->maxHistory = 64.0f;
+    p->minCoverage = 0.25f;
+    return PTSS_OK;
+}
+
+int ptss_reproject(ptss_context* c, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
+                   const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
+                   const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features_now || !dev_history_out) return fail(PTSS_EINVAL, "null argument");
+    if (dev_history_prev && (!prev_camera || !dev_features_prev)) return fail(PTSS_EINVAL, "a history needs its camera and its features");
+    if (const char* why = ptrp::paramsError(params)) return fail(PTSS_EINVAL, why);
+    if (static_cast<const void*>(dev_history_out) == static_cast<const void*>(dev_history_prev))
+        return fail(PTSS_EINVAL, "dev_history_out must not be dev_history_prev: a pixel's taps are other pixels' entries");
+    if (((uintptr_t)dev_features_now | (uintptr_t)dev_features_prev | (uintptr_t)dev_history_prev | (uintptr_t)dev_history_out) & 15u)
+        return fail(PTSS_EINVAL, "features and histories must be 16-byte aligned");
+    if (c->tile.world > 1)
+        return fail(PTSS_EINVAL, "ptss_reproject needs the whole frame: this context is a pixel-band shard (tileWorld > 1)");
+    if (c->numPixels == 0) return PTSS_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    // c and n of the accumulator as it stands: the last frame's display scale (ptss_denoise's input), nothing before the first frame
+    const int perPixel = (int)c->samples * (c->lastTicks - c->lastResetTick + 1);
+    const float inverseTicks = 1.f / (float)perPixel;
+    const float n = c->frameIndex == 0 ? 0.0f : (float)perPixel;
+    const int width = c->tile.width, height = c->tile.height;
+    const ptrp::View now = ptrp::viewOf(c->camera, width, height);
+    const ptrp::View prev = dev_history_prev ? ptrp::viewOf(*prev_camera, width, height) : now;
+    HIP_TRY(ptss::launchReproject(st, c->dAccum, dev_features_now, dev_features_prev, dev_history_prev, dev_history_out, width, height, now, prev,
+                                  ptrp::paramsOf(*params), inverseTicks, n, &c->launchedKernels));
     return PTSS_OK;
 }
 

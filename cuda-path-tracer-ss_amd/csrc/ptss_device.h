@@ -9,6 +9,7 @@
 #include "xorwow.h"
 
 namespace ptdn { struct Level; }   // ptdenoise.h
+namespace ptrp { struct View; struct Params; }   // ptreproject.h
 
 namespace ptss {
 
@@ -253,5 +254,10 @@ hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src,
 hipError_t launchSceneUpdate(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, const void* records, uint32_t first, uint32_t count,
                              unsigned long long* rejected, unsigned long long* launched);
 hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, unsigned long long* launched);
+// ptss_reproject (ptss_reproject.hip; bit 57 of *launched): accum = 3 uint32 per pixel, features = 32 B and histories = 16 B per pixel;
+// historyPrev = nullptr: no history (featuresPrev and prev are then not read)
+hipError_t launchReproject(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* featuresPrev, const void* historyPrev,
+                           void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev, const ptrp::Params& params,
+                           float inverseTicks, float n, unsigned long long* launched);
 
 }  // namespace ptss

@@ -9,6 +9,7 @@
 #include "HostOps.h"
 #include "Scene.h"
 #include "ptdenoise.h"
+#include "ptreproject.h"
 #include "ptquant.h"
 #include "ptmesh.h"
 #include "pttri.h"
@@ -214,20 +215,14 @@ int ptss_probe_mesh_touch(const float* b, const float* o3, const float* d3, size
     return PTSS_HOST_OK;
 }
 
-int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
-                       const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float) {
-    if (!accum || !features || !params || width <= 0 || height <= 0) return PTSS_HOST_EINVAL;
-    if (params->structSize != (unsigned int)sizeof(ptss_denoise_params) || params->levels < 0 || params->levels > PTSS_DENOISE_MAX_LEVELS)
-        return PTSS_HOST_EINVAL;
-    if (!(params->sigmaColor > 0.0f) || !(params->sigmaNormal > 0.0f) || !(params->sigmaDepth >= 0.0f)) return PTSS_HOST_EINVAL;
+// the passes of ptss_denoise / ptss_denoise_history, plane to plane, from the colours in plane[0]
+static int denoiseColours(std::vector<vec3> (&plane)[2], const ptss_pixel_feature* features, int width, int height, const ptss_denoise_params* params,
+                          unsigned char* out_rgba, float* out_float) {
     const size_t n = (size_t)width * (size_t)height;
-    std::vector<vec3> plane[2];
-    plane[0].resize(n);
-    for (size_t p = 0; p < n; ++p) plane[0][p] = ptdn::displayValue(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2], inverseTicks);
     auto featureAt = [&](int q) { return ptdn::Feature{features[q].normal, features[q].depth, features[q].materialIdx}; };
     auto depthAt = [&](int q) { return features[q].depth; };
     int cur = 0;
-    for (int i = 0; i < params->levels; ++i) {   // the passes of ptss_denoise, plane to plane
+    for (int i = 0; i < params->levels; ++i) {
         const ptdn::Level lv = ptdn::levelOf(*params, i);
         const std::vector<vec3>& src = plane[cur];
         std::vector<vec3>& dst = plane[1 - cur];
@@ -242,6 +237,59 @@ int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pix
         if (out_float) { out_float[3 * p] = v.x; out_float[3 * p + 1] = v.y; out_float[3 * p + 2] = v.z; }
         if (out_rgba) { out_rgba[4 * p] = ptdn::toByte(v.x); out_rgba[4 * p + 1] = ptdn::toByte(v.y); out_rgba[4 * p + 2] = ptdn::toByte(v.z); out_rgba[4 * p + 3] = 255; }
     }
+    return PTSS_HOST_OK;
+}
+
+static bool denoiseArgumentsOk(const void* input, const ptss_pixel_feature* features, int width, int height, const ptss_denoise_params* params) {
+    if (!input || !features || !params || width <= 0 || height <= 0) return false;
+    if (params->structSize != (unsigned int)sizeof(ptss_denoise_params) || params->levels < 0 || params->levels > PTSS_DENOISE_MAX_LEVELS)
+        return false;
+    return params->sigmaColor > 0.0f && params->sigmaNormal > 0.0f && params->sigmaDepth >= 0.0f;
+}
+
+int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
+                       const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float) {
+    if (!denoiseArgumentsOk(accum, features, width, height, params)) return PTSS_HOST_EINVAL;
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<vec3> plane[2];
+    plane[0].resize(n);
+    for (size_t p = 0; p < n; ++p) plane[0][p] = ptdn::displayValue(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2], inverseTicks);
+    return denoiseColours(plane, features, width, height, params, out_rgba, out_float);
+}
+
+int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pixel_feature* features, int width, int height,
+                               const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float) {
+    if (!denoiseArgumentsOk(history, features, width, height, params)) return PTSS_HOST_EINVAL;
+    const size_t n = (size_t)width * (size_t)height;
+    std::vector<vec3> plane[2];
+    plane[0].resize(n);
+    for (size_t p = 0; p < n; ++p) plane[0][p] = v3(history[p].r, history[p].g, history[p].b);
+    return denoiseColours(plane, features, width, height, params, out_rgba, out_float);
+}
+
+int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
+                         int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_feature* features_prev,
+                         const ptss_history_entry* history_prev, const ptss_reproject_params* params, ptss_history_entry* out) {
+    if (!accum || !camera_now || !features_now || !out || width <= 0 || height <= 0 || n < 0) return PTSS_HOST_EINVAL;
+    if (history_prev && (!camera_prev || !features_prev)) return PTSS_HOST_EINVAL;
+    if (ptrp::paramsError(params) || out == history_prev) return PTSS_HOST_EINVAL;
+    const ptrp::View now = ptrp::viewOf(*camera_now, width, height);
+    const ptrp::View prev = history_prev ? ptrp::viewOf(*camera_prev, width, height) : now;
+    const ptrp::Params prm = ptrp::paramsOf(*params);
+    auto materialAt = [&](int q) { return features_prev[q].materialIdx; };
+    auto geometryAt = [&](int q) { return ptrp::Geometry{features_prev[q].normal, features_prev[q].depth}; };
+    auto historyAt = [&](int q) { return ptrp::Entry{v3(history_prev[q].r, history_prev[q].g, history_prev[q].b), history_prev[q].weight}; };
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const size_t p = (size_t)y * width + x;
+            const vec3 cp = ptdn::displayValue(accum[3 * p], accum[3 * p + 1], accum[3 * p + 2], inverseTicks);
+            ptrp::Entry e{cp, (float)n};
+            if (history_prev) {
+                const ptdn::Feature fp{features_now[p].normal, features_now[p].depth, features_now[p].materialIdx};
+                e = ptrp::reprojectPixel(x, y, width, height, cp, (float)n, fp, now, prev, prm, materialAt, geometryAt, historyAt);
+            }
+            out[p] = ptss_history_entry{e.colour.x, e.colour.y, e.colour.z, e.weight};
+        }
     return PTSS_HOST_OK;
 }
 

@@ -13,6 +13,10 @@
 //                                   jitter 0.5, 0.5, through ptss_intersect) of the final camera, one line per pick
 //             [--denoise [levels]]  with --out image.tga: also image_denoised.tga, the accumulated image through ptss_render_features
 //                                   and ptss_denoise (default parameters; levels 0..6 overrides their level count)
+//             [--temporal]          with --out: the keys of --keys are delivered one at a time, --ticks frames are rendered at the start
+//                                   pose and after every key, and the image is carried from pose to pose (ptss_render_features,
+//                                   ptss_reproject with the history kept from the previous pose); --out receives the last history
+//                                   through ptss_denoise_history (default parameters) instead of the frame's own pixels
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -32,6 +36,7 @@ int main(int argc, char* argv[]) {
     unsigned long long seed = 0x5EED;
     bool quiet = false;
     int denoise = -2;   // --denoise: -2 absent, -1 the default level count, else the level count
+    bool temporal = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -56,6 +61,7 @@ int main(int argc, char* argv[]) {
             denoise = -1;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise = atoi(next());
         }
+        else if (a == "--temporal") temporal = true;
         else if (a == "--pick") {
             int x, y;
             if (sscanf(next(), "%d,%d", &x, &y) != 2) { fprintf(stderr, "bad --pick (x,y)\n"); return 2; }
@@ -94,6 +100,7 @@ int main(int argc, char* argv[]) {
     ptss_context* ctx = NULL;
     if (!picks.empty() && gpus > 0) { fprintf(stderr, "--pick needs one context (no --gpus)\n"); return 2; }
     if (denoise != -2 && (gpus > 0 || out.empty())) { fprintf(stderr, "--denoise needs --out and one context (no --gpus)\n"); return 2; }
+    if (temporal && (gpus > 0 || out.empty())) { fprintf(stderr, "--temporal needs --out and one context (no --gpus)\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -116,11 +123,46 @@ int main(int argc, char* argv[]) {
     data->quiet = quiet;
 
     bitmap.set_max_ticks(ticks);
-    for (char k : keys) bitmap.push_key((unsigned char)k);
-    bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);
+    if (temporal) {   // the loop of INTEGRATION.md: frames, features, reproject from the history kept at the previous pose, keep, move
+        const size_t n = (size_t)width * (size_t)height;
+        void *df[2] = {nullptr, nullptr}, *dh[2] = {nullptr, nullptr}, *dp = nullptr;
+        for (int k = 0; k < 2; ++k)
+            if (hipMalloc(&df[k], n * sizeof(ptss_pixel_feature)) != hipSuccess || hipMalloc(&dh[k], n * sizeof(ptss_history_entry)) != hipSuccess) {
+                fprintf(stderr, "--temporal: device buffers\n");
+                return 1;
+            }
+        if (hipMalloc(&dp, n * sizeof(ptss_uchar4)) != hipSuccess) { fprintf(stderr, "--temporal: device buffers\n"); return 1; }
+        ptss_reproject_params rp;
+        PTSS_HANDLE(ptss_default_reproject_params(&rp));
+        ptss_camera keptCamera = data->camera;
+        int cur = 0;
+        for (size_t pose = 0; pose <= keys.size(); ++pose) {
+            if (pose > 0) bitmap.push_key((unsigned char)keys[pose - 1]);
+            bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);
+            const bool have = pose > 0;
+            PTSS_HANDLE(ptss_render_features(ctx, (ptss_pixel_feature*)df[cur], NULL));
+            PTSS_HANDLE(ptss_reproject(ctx, (const ptss_pixel_feature*)df[cur], have ? &keptCamera : NULL,
+                                       have ? (const ptss_pixel_feature*)df[1 - cur] : NULL, have ? (const ptss_history_entry*)dh[1 - cur] : NULL, &rp,
+                                       (ptss_history_entry*)dh[cur], NULL));
+            keptCamera = data->camera;   // kept with its features and this output: the history of the next pose
+            cur = 1 - cur;
+        }
+        ptss_denoise_params params;
+        PTSS_HANDLE(ptss_default_denoise_params(&params));
+        PTSS_HANDLE(ptss_denoise_history(ctx, (const ptss_history_entry*)dh[1 - cur], (const ptss_pixel_feature*)df[1 - cur], &params, (ptss_uchar4*)dp, NULL));
+        PTSS_HANDLE(ptss_synchronize(ctx));
+        std::vector<ptss_uchar4> host(n);
+        if (hipMemcpy(host.data(), dp, n * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--temporal: read-back\n"); return 1; }
+        for (int k = 0; k < 2; ++k) { (void)hipFree(df[k]); (void)hipFree(dh[k]); }
+        (void)hipFree(dp);
+        if (!writeTga(out.c_str(), host.data(), width, height)) fprintf(stderr, "--temporal: cannot write %s\n", out.c_str());
+    } else {
+        for (char k : keys) bitmap.push_key((unsigned char)k);
+        bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);
+    }
 
     if (!quiet) printf("\n");
-    if (!out.empty()) {
+    if (!out.empty() && !temporal) {
         char name[160];
         strncpy(name, out.c_str(), sizeof(name) - 1);
         name[sizeof(name) - 1] = 0;

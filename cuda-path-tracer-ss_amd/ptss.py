@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ptss_types import (AreaLight, Camera, DenoiseParams, Material, PixelFeature, PointLight, RayHit, RayQuery, SceneDesc, Sphere,
-                        Triangle, UChar4, Vec3, struct_to_dict)
+from ptss_types import (AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature, PointLight, RayHit, RayQuery,
+                        ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -61,6 +61,11 @@ def query_kernels():
 def feature_kernels():
     """The feature-kernel instantiations (ptss_render_features): ("features", inLds)."""
     return {("features", lds) for lds in (False, True)}
+
+
+def reproject_kernels():
+    """The reprojection kernel (ptss_reproject): ("reproject",)."""
+    return {("reproject",)}
 
 
 _host = None
@@ -115,6 +120,9 @@ def host_lib():
         L.ptss_probe_mesh_refit.argtypes = [_f32p, C.c_size_t, _f32p]
         L.ptss_probe_mesh_touch.argtypes = [_f32p, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int)]
         L.ptss_probe_denoise.argtypes = [_u32p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
+        L.ptss_probe_denoise_history.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
+        L.ptss_probe_reproject.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
         _host = L
     return _host
 
@@ -184,6 +192,9 @@ def device_lib():
         L.ptss_default_denoise_params.argtypes = [C.POINTER(DenoiseParams)]
         L.ptss_denoise.argtypes = [vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptss_read_denoise_plane.argtypes = [vp, _f32p, C.c_size_t, C.POINTER(C.c_int)]
+        L.ptss_default_reproject_params.argtypes = [C.POINTER(ReprojectParams)]
+        L.ptss_reproject.argtypes = [vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
+        L.ptss_denoise_history.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
         L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
         L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -335,6 +346,8 @@ assert TRIANGLE_DTYPE.itemsize == C.sizeof(Triangle)
 FEATURE_DTYPE = np.dtype([("normal", np.float32, 3), ("depth", np.float32), ("albedo", np.float32, 3), ("materialIdx", np.int32)])
 assert RAY_DTYPE.itemsize == C.sizeof(RayQuery) and HIT_DTYPE.itemsize == C.sizeof(RayHit)
 assert FEATURE_DTYPE.itemsize == C.sizeof(PixelFeature)
+HISTORY_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("weight", np.float32)])
+assert HISTORY_DTYPE.itemsize == C.sizeof(HistoryEntry)
 
 
 def default_denoise_params(**overrides):
@@ -361,6 +374,55 @@ def probe_denoise(accum, inverse_ticks, features, width, height, params):
     if rc != 0:
         raise PtssError(f"ptss_probe_denoise: {rc}")
     return rgba, flt
+
+
+def probe_denoise_history(history, features, width, height, params):
+    """ptss_denoise_history on the host: the passes of probe_denoise over the colours of `history` ((H*W,) HISTORY_DTYPE)."""
+    hst = np.ascontiguousarray(history, dtype=HISTORY_DTYPE).reshape(-1)
+    f = np.ascontiguousarray(features, dtype=FEATURE_DTYPE).reshape(-1)
+    if len(hst) != width * height or len(f) != width * height:
+        raise ValueError("history and features must hold width * height pixels")
+    rgba = np.empty((len(hst), 4), dtype=np.uint8)
+    flt = np.empty((len(hst), 3), dtype=np.float32)
+    rc = host_lib().ptss_probe_denoise_history(hst.ctypes.data_as(C.c_void_p), f.ctypes.data_as(C.c_void_p), width, height, C.byref(params),
+                                               rgba.ctypes.data_as(C.c_void_p), flt.ctypes.data_as(_f32p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_denoise_history: {rc}")
+    return rgba, flt
+
+
+def default_reproject_params(**overrides):
+    """ptss_default_reproject_params, with cosNormal / depthTolerance / maxHistory / minCoverage overridden by keyword."""
+    p = ReprojectParams()
+    _check(device_lib().ptss_default_reproject_params(C.byref(p)))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+def probe_reproject(accum, inverse_ticks, n, camera_now, camera_prev, width, height, features_now, features_prev, history_prev, params=None):
+    """ptss_reproject on the host (csrc/ptreproject.h): accum (H*W, 3) uint32 with n samples per pixel behind it, the features of
+    both cameras and the previous history row-major; history_prev None = no history. Returns (H*W,) HISTORY_DTYPE."""
+    a = np.ascontiguousarray(accum, dtype=np.uint32).reshape(-1, 3)
+    fn = np.ascontiguousarray(features_now, dtype=FEATURE_DTYPE).reshape(-1)
+    if len(a) != width * height or len(fn) != width * height:
+        raise ValueError("accum and features_now must hold width * height pixels")
+    fp = hp = None
+    if history_prev is not None:
+        fp = np.ascontiguousarray(features_prev, dtype=FEATURE_DTYPE).reshape(-1)
+        hp = np.ascontiguousarray(history_prev, dtype=HISTORY_DTYPE).reshape(-1)
+        if len(fp) != width * height or len(hp) != width * height:
+            raise ValueError("features_prev and history_prev must hold width * height pixels")
+    out = np.empty(len(a), dtype=HISTORY_DTYPE)
+    rc = host_lib().ptss_probe_reproject(a.ctypes.data_as(_u32p), float(inverse_ticks), int(n), C.byref(camera_now),
+                                         C.byref(camera_prev) if camera_prev is not None else None, width, height,
+                                         fn.ctypes.data_as(C.c_void_p), fp.ctypes.data_as(C.c_void_p) if fp is not None else None,
+                                         hp.ctypes.data_as(C.c_void_p) if hp is not None else None,
+                                         C.byref(params if params is not None else default_reproject_params()), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_reproject: {rc}")
+    return out
 
 
 def make_rays(origins, directions, tmax=float("inf")):
@@ -607,6 +669,8 @@ class Renderer:
             out.add(("update",))
         if v.value >> 56 & 1:
             out.add(("refit",))
+        if v.value >> 57 & 1:
+            out.add(("reproject",))
         return out
 
     # --- scene updates (ptss_set_scene / ptss_update_triangles / ptss_reseed) -------------------------------------
@@ -778,6 +842,81 @@ class Renderer:
         elif isinstance(dev_out, int):
             dev_out = C.c_void_p(dev_out)
         _check(L.ptss_denoise(self._ctx, d_feat, C.byref(params), dev_out, C.c_void_p(stream) if stream else None))
+        if stream:
+            _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+        return self.pixels(dev_out)
+
+    def _device_input(self, name, value, dtype):
+        """A device pointer for `value`: an int is one already; an array is uploaded into the renderer's buffer `name`."""
+        if isinstance(value, int):
+            return C.c_void_p(value)
+        a = np.ascontiguousarray(value, dtype=dtype).reshape(-1)
+        if len(a) != self.local_pixels:
+            raise ValueError(f"{name}: one entry per local pixel")
+        d = self._device_buffer(name, a.nbytes)
+        _hip_check(_hip_lib().hipMemcpy(d, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+        return d
+
+    def history_devptr(self, which=0):
+        """One of the renderer's own history buffers (local_pixels HISTORY_DTYPE entries): reproject() writes number 0 by default."""
+        return self._device_buffer(f"history{which}", self.local_pixels * HISTORY_DTYPE.itemsize)
+
+    def read_history(self, devptr=None):
+        """Device -> host copy of a history buffer (default: history_devptr()) -> (local_pixels,) HISTORY_DTYPE."""
+        d = self.history_devptr() if devptr is None else (C.c_void_p(devptr) if isinstance(devptr, int) else devptr)
+        out = np.empty(self.local_pixels, dtype=HISTORY_DTYPE)
+        if self.local_pixels:
+            _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            _hip_check(_hip_lib().hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        return out
+
+    def reproject(self, prev_camera=None, prev_features=None, prev_history=None, features=None, params=None, dev_out=None, stream=None,
+                  read=True, **overrides):
+        """ptss_reproject: the history of the previous pose carried into the current frame -> (local_pixels,) HISTORY_DTYPE (None
+        with read=False: the caller keeps the device buffer). prev_history None = no history. prev_features / prev_history /
+        features: device pointers (int) the caller keeps, or arrays that are uploaded; features None = the buffer of the last
+        features() call, rendered now if the camera was set since. dev_out: a device pointer (default history_devptr()), never
+        prev_history's. params: a ReprojectParams (default_reproject_params(**overrides) otherwise)."""
+        if features is None:
+            if not self._have_features:
+                self.features()
+            d_now = self.features_devptr()
+        else:
+            d_now = self._device_input("features_upload", features, FEATURE_DTYPE)
+        d_fprev = d_hprev = None
+        if prev_history is not None:
+            if prev_camera is None or prev_features is None:
+                raise ValueError("a history needs its camera and its features")
+            d_fprev = self._device_input("prev_features_upload", prev_features, FEATURE_DTYPE)
+            d_hprev = self._device_input("prev_history_upload", prev_history, HISTORY_DTYPE)
+        if params is None:
+            params = default_reproject_params(**overrides)
+        if dev_out is None:
+            dev_out = self.history_devptr()
+        elif isinstance(dev_out, int):
+            dev_out = C.c_void_p(dev_out)
+        _check(device_lib().ptss_reproject(self._ctx, d_now, C.byref(prev_camera) if prev_camera is not None else None, d_fprev, d_hprev,
+                                           C.byref(params), dev_out, C.c_void_p(stream) if stream else None))
+        return self.read_history(dev_out) if read else None
+
+    def denoise_history(self, history=None, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None,
+                        stream=None):
+        """ptss_denoise_history: the A-trous passes over a history's colours -> (local_pixels, 4) uint8 RGBA. history: None (the
+        buffer reproject() wrote last by default, history_devptr()), a device pointer (int) or a HISTORY_DTYPE array to upload;
+        features and dev_out as in denoise()."""
+        d_hist = self.history_devptr() if history is None else self._device_input("history_upload", history, HISTORY_DTYPE)
+        if features is None:
+            if not self._have_features:
+                self.features()
+            d_feat = self.features_devptr()
+        else:
+            d_feat = self._device_input("features_upload", features, FEATURE_DTYPE)
+        params = default_denoise_params(levels=levels, sigmaColor=sigma_color, sigmaNormal=sigma_normal, sigmaDepth=sigma_depth)
+        if dev_out is None:
+            dev_out = self._device_buffer("denoised", self.local_pixels * 4)
+        elif isinstance(dev_out, int):
+            dev_out = C.c_void_p(dev_out)
+        _check(device_lib().ptss_denoise_history(self._ctx, d_hist, d_feat, C.byref(params), dev_out, C.c_void_p(stream) if stream else None))
         if stream:
             _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
         return self.pixels(dev_out)

@@ -157,7 +157,8 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
  * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
  * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise);
- * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles). Recorded on the host at launch. */
+ * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles); bit 57 for reprojectKernel (ptss_reproject).
+ * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
 /* Batched ray queries against the context's scene. dev_rays / dev_hits / dev_occluded are DEVICE pointers of n
@@ -203,6 +204,34 @@ int ptss_denoise(ptss_context* ctx, const ptss_pixel_feature* dev_features, cons
  * that level's index. PTSS_EINVAL when the latest call ran fewer than two levels (or there was none). With k + 1 levels it returns
  * what a k-level call converts to bytes: how the tests compare the device's floats with ptss_probe_denoise's. */
 int ptss_read_denoise_plane(ptss_context* ctx, float* host_float3, size_t count, int* level);
+
+/* cosNormal 0.9, depthTolerance 0.02, maxHistory 64, minCoverage 0.25 (design choices, not measurements). */
+int ptss_default_reproject_params(ptss_reproject_params* p);
+
+/* Reprojected history: carries an image across a camera move of a STATIC scene. For every pixel of the current
+ * frame: its colour c (the context's accumulator times the inverseTicks of the last frame's display value, ptss_denoise's input) and
+ * the samples per pixel n behind it (frames since the reset times samplesPerPass; 0 before the first frame); the world point its
+ * centre ray hits (dev_features_now: ptss_render_features of the context's CURRENT camera) projected into prev_camera; the four
+ * bilinear taps of dev_history_prev there, each counted only if the previous frame saw the same surface (same material, normals
+ * within cosNormal, previous depth within depthTolerance of the point's distance from prev_camera — otherwise the point was hidden
+ * then); out = the mean of c and the taps' colour h weighted n : w, w = the taps' weight capped at maxHistory (0 when the counting
+ * taps cover less than minCoverage), weight = n + w. A pixel without usable history gets (c, n) exactly. dev_history_prev = NULL
+ * means "no history": out = (c, n) for every pixel, prev_camera and dev_features_prev are ignored (and may be NULL). Moving geometry
+ * is out of scope: after ptss_update_triangles or ptss_set_scene pass NULL.
+ * dev_history_out (one entry per pixel, 16-byte aligned) must not be dev_history_prev. Asynchronous on hipStream (NULL: the
+ * context's stream); like ptss_denoise it only reads the accumulator and leaves no trace in frame state. PTSS_EINVAL without
+ * touching the device: a null context or required pointer, a wrong structSize, cosNormal outside [-1, 1], depthTolerance or
+ * maxHistory negative or not finite, minCoverage outside [0, 1], equal history pointers, a sharded context (tileWorld > 1).
+ * ptss_launched_kernels: bit 57. */
+int ptss_reproject(ptss_context* ctx, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
+                   const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
+                   const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream);
+
+/* ptss_denoise with the colours of dev_history (a ptss_reproject output) as input instead of the accumulator: the same passes, the
+ * same kernels, the same scratch and ordering rules; levels = 0 converts the history's colours to bytes. It updates what
+ * ptss_read_denoise_plane returns. */
+int ptss_denoise_history(ptss_context* ctx, const ptss_history_entry* dev_history, const ptss_pixel_feature* dev_features,
+                         const ptss_denoise_params* params, ptss_uchar4* dev_out, void* hipStream);
 
 /* Leaves of the triangle hierarchy of the scene image in use (16 triangles each), 0 when that image walks
  * every triangle. */

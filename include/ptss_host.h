@@ -82,6 +82,16 @@ int ptss_probe_mesh_touch(const float* bound12, const float* o3, const float* d3
  * structSize or levels outside 0..6. */
 int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pixel_feature* features, int width, int height,
                        const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float);
+/* The same passes with float colours as input (ptss_denoise_history on the host): the r, g, b of width * height history entries. */
+int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pixel_feature* features, int width, int height,
+                               const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float);
+/* ptss_reproject on the host (csrc/ptreproject.h — the very arithmetic the kernel evaluates), with the device call's argument
+ * checks: accum = 3 uint32 per pixel, n = samples per pixel behind it, the features of both cameras and the previous history
+ * row-major, width * height entries each. history_prev = NULL: no history (camera_prev and features_prev are then ignored).
+ * PTSS_HOST_EINVAL: a null required pointer, a non-positive size, n < 0, out == history_prev, or parameters ptss_reproject refuses. */
+int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
+                         int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_feature* features_prev,
+                         const ptss_history_entry* history_prev, const ptss_reproject_params* params, ptss_history_entry* out);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6);
 /* n raw draws and the matching (0,1] floats from a state; state advanced in place. */

@@ -137,6 +137,22 @@ typedef struct ptss_denoise_params {
 
 #define PTSS_DENOISE_MAX_LEVELS 6
 
+/* One pixel of a reprojected history (ptss_reproject): 16 B, laid out as an entry of the denoiser's colour planes.
+ * r, g, b: the colour on the display's 0..255 scale; weight: the effective number of samples per pixel behind it. */
+typedef struct ptss_history_entry {
+    float r, g, b;
+    float weight;
+} ptss_history_entry;
+
+/* Parameters of ptss_reproject (ptss_default_reproject_params fills them in; DESIGN.md §3.19 has the formulas). */
+typedef struct ptss_reproject_params {
+    unsigned int structSize; /* sizeof(ptss_reproject_params) as the caller compiled it */
+    float cosNormal;         /* a previous pixel counts only if its normal and the current one enclose at most this cosine: [-1, 1] */
+    float depthTolerance;    /* ... and only if its depth is within this fraction of the reprojected point's distance: >= 0 */
+    float maxHistory;        /* cap of the history's weight, in samples per pixel: >= 0 */
+    float minCoverage;       /* bilinear weight the counting taps must reach together, else the history is dropped: [0, 1] */
+} ptss_reproject_params;
+
 #if defined(__cplusplus)
 static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
               "ptss_ray_query is two 16-byte rows");
@@ -147,6 +163,7 @@ static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) == 
 static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, depth) == 12 && offsetof(ptss_pixel_feature, albedo) == 16 &&
                   offsetof(ptss_pixel_feature, materialIdx) == 28,
               "ptss_pixel_feature is two 16-byte rows");
+static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -157,6 +174,7 @@ _Static_assert(sizeof(ptss_ray_hit) == 48 && offsetof(ptss_ray_hit, distance) ==
 _Static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, depth) == 12 && offsetof(ptss_pixel_feature, albedo) == 16 &&
                    offsetof(ptss_pixel_feature, materialIdx) == 28,
                "ptss_pixel_feature is two 16-byte rows");
+_Static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
 #endif
 
 #ifdef __cplusplus
