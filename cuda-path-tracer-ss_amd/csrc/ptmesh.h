@@ -1,7 +1,7 @@
 // ptmesh.h — the conservative bound of the mesh image (SceneLayout::mesh): "may this ray be accepted by Triangle::intersectRay
 // (Primitives.h:25-83) for some triangle inside this leaf or group?" Written once for the gfx950 kernels (ptss_kernels.hip) and for
 // a host probe (host_capi.cpp ptss_probe_mesh_bound, tests/test_mesh_bound.py). The derivation of the predicate and of its
-// constants sits at the construction of the bounds (ptss_api.hip packScene); DESIGN.md §3.15 summarises it.
+// constants sits at the construction of the bounds (ptpack.h packMeshBounds); DESIGN.md §3.15 summarises it.
 //
 // A bound is three rows of four floats:
 //   {C, R}                  a ball that holds every vertex v0, v0 + e1, v0 + e2 of its triangles (e1, e2 as stored)
@@ -54,7 +54,7 @@ PTM_HD bool mayTouch(vec3 C, float R, vec3 a, float cosA, float sinA, float nmin
 }
 
 // The twelve floats of the bound around n triangles given as {v0, e1, e2} (nine floats each, as the image stores them), computed
-// in double from the exact float inputs and rounded outwards (host only: packScene and the probe).
+// in double from the exact float inputs and rounded outwards (host only: ptpack.h packMeshBounds and the probe).
 inline void buildBound(const float* tri9, int n, float out[12]) {
     auto up = [](double x) { float f = (float)(x * (1 + 1e-12)); return f < x * (1 + 1e-12) ? __builtin_nextafterf(f, __builtin_inff()) : f; };
     auto down = [](double x) { float f = (float)(x * (1 - 1e-12)); return (double)f > x * (1 - 1e-12) ? __builtin_nextafterf(f, -__builtin_inff()) : f; };

@@ -440,7 +440,7 @@ __device__ __forceinline__ TriHit triangleTestPrimary(const TriRows& tr, float4 
 // ---- sphere candidate masks, CudaTracer.cu:127-133 / :438-444 through Primitives.h:107-118 -------------------------
 // bit j of the result = "sphere j of this block of up to 32 passes the reference's discriminant test" — the very
 // operations of the test above (Primitives.h:109-118), four spheres per trip: the four rows are fetched with one address and immediate offsets
-// (the host pads the sphere rows to a multiple of four, packScene; a padding row's bit is dropped by the caller's `keep`
+// (the host pads the sphere rows to a multiple of four, ptpack.h layoutPlain; a padding row's bit is dropped by the caller's `keep`
 // mask), and each verdict enters the mask through the carry of one add (mask = 2 * mask + verdict: v_cmp + v_addc
 // instead of v_cmp + v_cndmask + v_or and a v_mov for the bit). That leaves the first sphere in the highest bit; one
 // v_bfrev + shift puts sphere j at bit j, which the candidate loops need (they walk in index order).
@@ -565,8 +565,8 @@ struct Hit {
     float w0, w1, w2;
 };
 
-// ---- Scenes with many spheres (SceneLayout::accelSpheres; derivation of the test and of its constants: packScene in
-// ptss_api.hip). The spheres sit in spatially sorted chunks of kChunkSpheres with a bounding sphere each. chunkMask is
+// ---- Scenes with many spheres (SceneLayout::accelSpheres; derivation of the test and of its constants: at the top of
+// ptpack.h). The spheres sit in spatially sorted chunks of kChunkSpheres with a bounding sphere each. chunkMask is
 // the wave-uniform pass over 32 chunk bounds: bit k = "this lane's ray may touch chunk k" — a conservative test that
 // only ever skips spheres whose reference discriminant is certainly negative. Each lane then walks ITS chunks (per-lane
 // gathers) with the reference's own tests. The visiting order is no longer the reference's, which matters only when two
@@ -579,7 +579,7 @@ constexpr float kAccelDirEps = 1e-5f;               // | |d|^2 - 1 | up to which
 constexpr float kAccelQ = 0.25f * (1.0f + 2e-5f) / (1.0f - kAccelMu) * (1.0f + 1e-6f);   // (1 + 2 eps) / (4 (1 - mu)), rounded up
 
 // One chunk bound's verdict ("this lane's ray may touch the chunk") shifted into `rev` through the carry, as shiftInSphere does
-// for spheres. ONE test (derivation: packScene): with t = dv - |dv| = 2 min(dv, 0) — exact, no compare, no select —
+// for spheres. ONE test (derivation: ptpack.h): with t = dv - |dv| = 2 min(dv, 0) — exact, no compare, no select —
 // vv - kAccelQ t^2 is (a lower bound of) the squared distance of the chunk's centre from the RAY, the half line t >= 0: the
 // line's distance while the closest approach lies ahead of the origin, the origin's own distance once it lies behind. The
 // chunk is skipped when that exceeds the stored bound; the compare's wave mask is handed to v_addc as its carry-in SGPR
@@ -634,7 +634,7 @@ __device__ __forceinline__ uint32_t chunkMask(const float4* bounds, int cnt, vec
 // i ^ (chunk mod kChunkSpheres), so that the 16-byte gathers of a wave spread over the LDS banks; verdicts enter through
 // the carry (shiftInSphere), so visit i lands in bit kChunkSpheres - 1 - i. chunkSlot() turns a bit of that mask back into
 // the sphere's slot inside the chunk. The traversal is order-free (ties go by original index). Where the image is staged in
-// LDS and the sphere rows start on a 256-byte boundary (they do: packScene puts them first, the dynamic LDS is aligned), a
+// LDS and the sphere rows start on a 256-byte boundary (they do: ptpack.h puts them first, the dynamic LDS is aligned), a
 // row's address is (chunk's address ^ (chunk mod 16) << 4) ^ (i << 4): ONE v_xor with a constant per row instead of add, and,
 // shift-add (round 3; -2 of 16 instructions per sphere).
 typedef __attribute__((address_space(3))) const float4 LdsRow;
@@ -975,7 +975,7 @@ __device__ __forceinline__ bool anySpheresHybrid(const float4* sc, const SceneLa
     return occluded;
 }
 
-// ---- The mesh image (SceneLayout::mesh; the bound: ptmesh.h, its derivation: ptss_api.hip packScene). The
+// ---- The mesh image (SceneLayout::mesh; the bound: ptmesh.h, its derivation: ptpack.h packMeshBounds). The
 // triangles sit in a kd order of their centroids: every kMeshLeaf consecutive positions a leaf, every kMeshLeaf leaves a group,
 // each with a conservative bound. A wave-uniform pass over the group bounds (four per trip, verdicts through the carry as in
 // chunkMask) gives every lane the groups its ray may touch; each lane then walks ITS groups, tests their leaf bounds, and walks
@@ -1013,7 +1013,7 @@ __device__ __forceinline__ uint32_t meshLeafMask(const float4* leaves, int g, in
     return m;
 }
 __device__ __forceinline__ const float4* meshLeaves(const float4* sc, const float4* cold, const SceneLayout& L) {
-    return (L.mesh.offLeaf < L.ldsVec4 ? sc : cold) + L.mesh.offLeaf;   // staged when they fit (packScene)
+    return (L.mesh.offLeaf < L.ldsVec4 ? sc : cold) + L.mesh.offLeaf;   // staged when they fit (ptpack.h layoutMesh)
 }
 template <bool kPrimary>
 __device__ __forceinline__ void closestTrianglesMesh(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, bool live,
@@ -1686,18 +1686,8 @@ __device__ __forceinline__ uint32_t frameLiveCount(const FrameBuffers& fb, int b
     return total;
 }
 
-// ---- LDS work area behind the scene image -----------------------------------------------------
-// block: [0..kWaves) wave survivor totals, [8] block base in the output region
-// per wave: the shadow-ray queue of one NEE round (kNeeLights lights x 64 lanes):
-//           7 float planes (lo.xyz, w_i.xyz, max distance) + 1 word (owner lane | slot-in-round << 8),
-//           then kNeeLights x 64 answer BYTES.
-constexpr int kNeeLights = 2;                       // lights regrouped per round
-constexpr int kQueueCap = kNeeLights * 64;
+// (the LDS work area behind the scene image — kNeeLights, kQueueCap, kWaveLdsWords, kBlockLdsVec4 — is laid out in ptscene.h)
 static_assert(kQueueCap == kQueueCapConst, "anySpheresHybrid's plane stride");
-constexpr int kWaveLdsWords = 8 * kQueueCap + kNeeLights * 64 / 4;  // answers are bytes: 24,048 -> 22,512 B per workgroup
-                                                                    // with the 38-primitive scenes, i.e. 7 workgroups per CU instead of 6
-constexpr int kBlockScratchVec4 = 4;
-constexpr int kBlockLdsVec4 = kBlockScratchVec4 + (kWaves * kWaveLdsWords + 3) / 4;
 
 }  // namespace
 
@@ -2672,9 +2662,7 @@ hipError_t launchPrimaryPrep(hipStream_t st, float4* sceneBlob, const SceneLayou
 #if PTSS_DIAG
 hipError_t readDiagCounters(unsigned long long* out8) { return hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_diag), 64); }
 #endif
-size_t bounceLdsBytes(const SceneLayout& layout, bool sceneInLds) {
-    return ((sceneInLds ? (size_t)layout.ldsVec4 : 0) + kBlockLdsVec4) * sizeof(float4);
-}
+static_assert(sizeof(float4) == kVec4Bytes, "bounceLdsBytes counts rows of float4");
 
 // ---- which instantiation runs: five scene variants, each one {kAccel, kBounded, kPairs, kMesh} of bounceKernel, the first four
 // also of frameKernel (the mesh image has none: ptss_create never qualifies it for one launch per frame).

@@ -17,7 +17,7 @@ static_assert(sizeof(ptss_triangle) == kTriWords * 4, "ptss_triangle is 19 words
 // LDS, and each thread then reads its own 19 words (an odd stride: no bank conflicts). A record with a vertex that is not finite
 // or lies beyond |coordinate| <= 2^40 — the mesh image's precondition, which implies sphereBounded's and triDetBounded's — is
 // counted and NOT written: the image never leaves the range its kernels were proven for. The material word and the key word
-// (0xFFFFFFFE - original index) of the stored rows stay as they are; the rest is what packScene writes.
+// (0xFFFFFFFE - original index) of the stored rows stay as they are; the rest is what packTriangles (ptpack.h) writes.
 __global__ __launch_bounds__(kUpdateBlock) void sceneUpdateKernel(float4* __restrict__ blob, int offTri, int offTriNormal, int offTriVert,
                                                                   int offTriPos, const uint32_t* __restrict__ records, uint32_t first,
                                                                   uint32_t count, unsigned long long* __restrict__ rejected) {
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(kUpdateBlock) void sceneUpdateKernel(float4* __rest
     float4* tri = blob + offTri + 3 * (size_t)pos;
     float4* nrm = blob + offTriNormal + 3 * (size_t)pos;
     float4* vert = blob + offTriVert + 2 * (size_t)pos;
-    // e1 = v1 - v0, e2 = v2 - v0: packScene's single float subtraction (the build contracts nothing)
+    // e1 = v1 - v0, e2 = v2 - v0: packTriangles' single float subtraction (ptpack.h) (the build contracts nothing)
     tri[0] = float4{r[0], r[1], r[2], tri[0].w};
     tri[1] = float4{r[3] - r[0], r[4] - r[1], r[5] - r[2], tri[1].w};
     tri[2] = float4{r[6] - r[0], r[7] - r[1], r[8] - r[2], 0.0f};

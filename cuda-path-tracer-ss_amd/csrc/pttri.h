@@ -8,8 +8,8 @@
 //
 // EDGE CLASSES. Every preset's walls and light panels are rectangles whose edges run along one coordinate axis
 // (Scene.cpp:323-370; of configs[2]'s 16 triangles 12 have two such edges and the other 4 one). The host records per edge
-// which components are EXACT zeros (class 0: none known; 1 / 2 / 3: only x / y / z may be non-zero — csrc/ptss_api.hip
-// packScene, compared with == 0.0f), and the class forms below leave out the products with those components. Why that is
+// which components are EXACT zeros (class 0: none known; 1 / 2 / 3: only x / y / z may be non-zero — csrc/ptpack.h
+// orderTriangles, compared with == 0.0f), and the class forms below leave out the products with those components. Why that is
 // the same arithmetic: for finite x, x * (+-0) = +-0 exactly, fma(a, b, +-0) = RN(a b) and y + (+-0) = y for y != 0, so
 //   (1) every NON-ZERO intermediate value is bit-identical in both forms;
 //   (2) an intermediate that is zero in one form is zero in the other — possibly of the other sign.

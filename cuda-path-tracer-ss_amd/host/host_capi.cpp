@@ -12,6 +12,7 @@
 #include "ptreproject.h"
 #include "ptquant.h"
 #include "ptmesh.h"
+#include "ptpack.h"
 #include "pttri.h"
 #include "xorwow.h"
 
@@ -211,6 +212,31 @@ int ptss_probe_mesh_touch(const float* b, const float* o3, const float* d3, size
     for (size_t i = 0; i < n; ++i) {
         const vec3 o = v3(o3[3 * i], o3[3 * i + 1], o3[3 * i + 2]), d = v3(d3[3 * i], d3[3 * i + 1], d3[3 * i + 2]);
         out[i] = ptmesh::mayTouch(v3(b[0], b[1], b[2]), b[3], v3(b[4], b[5], b[6]), b[7], b[8], b[9], b[10], b[11], o, d, margin) ? 1 : 0;
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_pack_scene(const ptss_scene_desc* scene, int everySphereLoop, int image, int* numImages, int* inLds, void* layout,
+                          size_t layoutBytes, float* blob, size_t blobCapacity, size_t* blobWords) {
+    if (!scene || ptpack::validateScene(*scene) || (everySphereLoop != 0 && everySphereLoop != 1)) return PTSS_HOST_EINVAL;
+    const int n = ptpack::planImages(*scene, everySphereLoop != 0).numImages;
+    if (numImages) *numImages = n;
+    if (image < 0 || image >= n || (layout && layoutBytes != sizeof(ptss::SceneLayout))) return PTSS_HOST_EINVAL;
+    if (!layout && !blob && !inLds && !blobWords) return PTSS_HOST_OK;
+    std::vector<ptpack::PackedImage> images;
+    try {
+        images = ptpack::packImages(*scene, everySphereLoop != 0);
+    } catch (const std::bad_alloc&) {
+        return PTSS_HOST_EINVAL;
+    }
+    const ptpack::PackedImage& im = images[(size_t)image];
+    const size_t words = im.blob.size() * 4;
+    if (inLds) *inLds = im.inLds ? 1 : 0;
+    if (layout) std::memcpy(layout, &im.layout, sizeof(im.layout));
+    if (blobWords) *blobWords = words;
+    if (blob) {
+        if (blobCapacity < words) return PTSS_HOST_EINVAL;
+        std::memcpy(blob, im.blob.data(), words * sizeof(float));
     }
     return PTSS_HOST_OK;
 }

@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ptss_types import (AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature, PointLight, RayHit, RayQuery,
-                        ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
+from ptss_types import (SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
+                        PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -119,6 +119,8 @@ def host_lib():
         L.ptss_camera_ray.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RayQuery)]
         L.ptss_probe_mesh_refit.argtypes = [_f32p, C.c_size_t, _f32p]
         L.ptss_probe_mesh_touch.argtypes = [_f32p, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int)]
+        L.ptss_probe_pack_scene.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
+                                            C.c_size_t, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ptss_probe_denoise.argtypes = [_u32p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
         L.ptss_probe_denoise_history.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
         L.ptss_probe_reproject.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
@@ -323,6 +325,37 @@ def probe_mesh_touch(bound, origins, directions, margin=1.0):
     if rc != 0:
         raise PtssError(f"ptss_probe_mesh_touch: {rc}")
     return out
+
+
+def probe_pack_scene_images(scene, every_sphere_loop=False):
+    """How many images (1 or 2) ptss_create builds for `scene` (a ptss.Scene or anything with a .desc)."""
+    n = C.c_int()
+    rc = host_lib().ptss_probe_pack_scene(C.byref(scene.desc), 1 if every_sphere_loop else 0, 0, C.byref(n), None, None, 0, None, 0, None)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_pack_scene: {rc}")
+    return n.value
+
+
+def probe_pack_scene(scene, every_sphere_loop=False, image=0):
+    """csrc/ptpack.h on the host: the scene image ptss_create builds for `scene` (a ptss.Scene or anything with a .desc).
+    Returns (layout: dict of SceneLayout field -> int, blob: (rows, 4) float32 — view it as int32 / uint32 for the integer tables —,
+    in_lds). The union's words appear as triClassPack0..4 and as the mesh image's numLeaves .. reserved."""
+    every = 1 if every_sphere_loop else 0
+    raw = np.zeros(len(SCENE_LAYOUT_FIELDS), dtype=np.int32)
+    in_lds, words = C.c_int(), C.c_size_t()
+    blob = np.empty(1 << 16, dtype=np.float32)   # most images fit; a larger one is packed again into a buffer of its size
+    for _ in range(2):
+        rc = host_lib().ptss_probe_pack_scene(C.byref(scene.desc), every, int(image), None, C.byref(in_lds), raw.ctypes.data_as(C.c_void_p),
+                                              raw.nbytes, blob.ctypes.data_as(_f32p), blob.size, C.byref(words))
+        if rc == 0 or words.value <= blob.size:
+            break
+        blob = np.empty(words.value, dtype=np.float32)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_pack_scene: {rc}")
+    layout = {name: int(v) for name, v in zip(SCENE_LAYOUT_FIELDS, raw)}
+    layout.update({f"triClassPack{k}": layout[f"triClassPack{k}"] & 0xFFFFFFFF for k in range(5)})   # unsigned words
+    layout.update({name: layout[f"triClassPack{k}"] for k, name in enumerate(SCENE_LAYOUT_MESH_FIELDS)})
+    return layout, blob[:words.value].reshape(-1, 4).copy(), bool(in_lds.value)
 
 
 def default_camera():

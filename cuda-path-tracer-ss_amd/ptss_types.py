@@ -81,6 +81,16 @@ class ReprojectParams(C.Structure):
                 ("minCoverage", C.c_float)]
 
 
+# The 4-byte words of csrc/ptscene.h SceneLayout, in order (ptss.probe_pack_scene decodes the layout with this list). The five
+# words of its union appear under both of their names: triClassPack0..4 (classed images) and the mesh image's dimensions.
+SCENE_LAYOUT_FIELDS = ("numSpheres", "numTriangles", "numMaterials", "numPointLights", "numAreaLights", "offSphere", "offSphereMat",
+                       "offTri", "offTriNormal", "offTriVert", "offMaterial", "offPointLight", "offAreaLight", "accelSpheres", "numChunks",
+                       "offChunk", "offSphereOrig", "offSpherePos", "offQuant", "offPrimSphere", "offPrimTri", "offPrimChunk", "totalVec4",
+                       "ldsVec4", "neeSkipSafe", "sphereBounded", "neePairs", "triDetBounded", "triClassed", "triClassPack0",
+                       "triClassPack1", "triClassPack2", "triClassPack3", "triClassPack4", "offTriPos")
+SCENE_LAYOUT_MESH_FIELDS = ("numLeaves", "numGroups", "offGroup", "offLeaf", "reserved")   # the same five words, as the mesh image reads them
+
+
 assert C.sizeof(Sphere) == 20 and C.sizeof(Triangle) == 76 and C.sizeof(Material) == 76
 assert C.sizeof(PointLight) == 24 and C.sizeof(AreaLight) == 32 and C.sizeof(Camera) == 40
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PixelFeature) == 32 and C.sizeof(HistoryEntry) == 16

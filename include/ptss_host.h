@@ -74,6 +74,15 @@ int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const
  * per bound, the ceil(ntri / 16) leaves first, then the ceil(leaves / 16) groups — what ptss_read_triangle_bounds returns after a
  * refit, bit for bit. */
 int ptss_probe_mesh_refit(const float* tri9, size_t ntri, float* bounds12);
+/* The scene image ptss_create builds for a scene (csrc/ptpack.h — the very packer libptss.so runs): image `image` (0 or 1) of the
+ * *numImages (1 or 2) the scene gets with cfg.everySphereLoop = everySphereLoop (0 or 1). *inLds: 1 if the image is staged in LDS.
+ * layout (may be NULL) receives the image's SceneLayout (csrc/ptscene.h) as raw bytes; layoutBytes must be its size (140).
+ * *blobWords = the image's float words (four per row); blob (may be NULL: a size query) receives them if blobCapacity, in words,
+ * suffices. Every out pointer may be NULL; with layout, blob, inLds and blobWords all NULL nothing is packed (the count alone).
+ * PTSS_HOST_EINVAL: a null or invalid scene, a flag or an image index out of range (*numImages is set), a wrong layoutBytes, or a
+ * blob too small (*blobWords is set). */
+int ptss_probe_pack_scene(const ptss_scene_desc* scene, int everySphereLoop, int image, int* numImages, int* inLds, void* layout,
+                          size_t layoutBytes, float* blob, size_t blobCapacity, size_t* blobWords);
 /* ptmesh.h mayTouch for n rays against ONE given bound (12 floats), margin as in ptss_probe_mesh_bound. */
 int ptss_probe_mesh_touch(const float* bound12, const float* o3, const float* d3, size_t n, float margin, int* out);
 /* ptss_denoise on the host (csrc/ptdenoise.h — the very per-tap weights and accumulation order the kernel evaluates): accum = 3

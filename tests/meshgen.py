@@ -62,6 +62,15 @@ def icosphere_obj(level, centre=(0, 0, 0), radius=1.0, normals=True):
     return "\n".join(lines) + "\n"
 
 
+def strip_obj(n):
+    """n triangles in a row across the back of the box."""
+    lines = []
+    for i in range(n + 2):
+        lines.append(f"v {-3.5 + 7.0 * (i // 2) / (n // 2 + 1):.7g} {-1.0 + 2.0 * (i % 2):.7g} -7.5")
+    lines += [f"f {i + 1} {i + 2} {i + 3}" for i in range(n)]
+    return "\n".join(lines) + "\n"
+
+
 def write(tmp_path, name, text):
     path = tmp_path / name
     path.write_text(text)

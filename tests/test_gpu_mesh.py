@@ -8,7 +8,7 @@ import pytest
 
 import oracle
 import ptss
-from meshgen import grid_obj, icosphere_obj, translate_scale, write
+from meshgen import grid_obj, icosphere_obj, strip_obj, translate_scale, write
 from ptss_types import Material
 
 pytestmark = pytest.mark.gpu
@@ -125,15 +125,6 @@ def test_image_read_in_place(tmp_path):
     s.desc.materials, s.desc.numMaterials = mats, len(mats)
     s._keep = mats
     run(s, 32, 24, 4, mode="both", lds=False)
-
-
-def strip_obj(n):
-    """n triangles in a row across the back of the box."""
-    lines = []
-    for i in range(n + 2):
-        lines.append(f"v {-3.5 + 7.0 * (i // 2) / (n // 2 + 1):.7g} {-1.0 + 2.0 * (i % 2):.7g} -7.5")
-    lines += [f"f {i + 1} {i + 2} {i + 3}" for i in range(n)]
-    return "\n".join(lines) + "\n"
 
 
 @pytest.mark.parametrize("total", [255, 256, 511, 512])

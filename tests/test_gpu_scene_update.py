@@ -295,3 +295,19 @@ def test_a_device_tensor_is_taken_in_place():
             want.close()
     finally:
         r.close()
+
+
+def test_the_uploaded_image_is_the_one_the_host_probe_packs():
+    """libptss.so uploads what ptss.probe_pack_scene reports (csrc/ptpack.h compiled twice): positions, bounds and leaves, bit for bit."""
+    scene = m530()
+    L, blob, in_lds = ptss.probe_pack_scene(scene)
+    r = ptss.Renderer(scene, 64, 64, max_iterations=1)
+    try:
+        leaves, groups = L["numLeaves"], L["numGroups"]
+        assert in_lds and r.triangle_leaves() == leaves == 34
+        positions = blob.view(np.int32).reshape(-1)[4 * L["offTriPos"]:4 * L["offTriPos"] + 530]
+        assert np.array_equal(r.triangle_positions(530), positions)
+        bounds = np.concatenate([blob[L["offLeaf"]:L["offLeaf"] + 3 * leaves], blob[L["offGroup"]:L["offGroup"] + 3 * groups]]).reshape(-1, 12)
+        assert r.triangle_bounds().tobytes() == bounds.tobytes()
+    finally:
+        r.close()

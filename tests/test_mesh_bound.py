@@ -1,4 +1,4 @@
-"""Soundness of the mesh image's cull (csrc/ptmesh.h; derivation at packScene in csrc/ptss_api.hip): a leaf or
+"""Soundness of the mesh image's cull (csrc/ptmesh.h; derivation at packMeshBounds in csrc/ptpack.h): a leaf or
 group bound may say "provably not" only for a ray that the reference's float test (Triangle::intersectRay, Primitives.h:25-83)
 accepts for none of its triangles, at any distance. Checked on the host build of the very predicate the kernels evaluate
 (ptss_probe_mesh_bound), against the general form of the triangle test (ptss_probe_triangle_forms, itself pinned to the oracle

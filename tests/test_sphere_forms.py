@@ -1,7 +1,7 @@
 """The chunked traversal decides "this sphere may be hit" (Primitives.h:115-118: discriminent = b*b - 4*c with b = 2 d.v, rejected
 when < 0) from h = d.v and c as  !(h*h < c)  instead of  !((2h)*(2h) < 4*c)  (shiftInSphereBounded, ptss_kernels.hip). The two
 verdicts are the same for every float32 h whenever c is zero, NaN, or 2^-105 <= |c| <= 2^105 — what accelEligible
-(ptss_api.hip) guarantees for c = |v|^2 - r^2 — and for infinite c together with a non-finite h (a non-finite origin).
+(csrc/ptpack.h) guarantees for c = |v|^2 - r^2 — and for infinite c together with a non-finite h (a non-finite origin).
 Checked here in float32 arithmetic on the adversarial corners and on random bit patterns. CPU only; no product code runs."""
 import numpy as np
 

@@ -2,7 +2,7 @@
 does a ray's LINE touch when the leaves are bounded by spheres (what the kernel tests) and when they are
 bounded by axis-aligned boxes, with the safety margin m both need (a bound may only skip spheres whose
 REFERENCE discriminant is certainly negative: distance to the line > r + m |v|, m^2 >= the direction's deviation from unit
-length + the float error of b*b - 4c)? CPU only, numpy; the kd split is restated from csrc/ptss_api.hip (kdSplit).
+length + the float error of b*b - 4c)? CPU only, numpy; the kd split is restated from csrc/ptpack.h (kdOrder).
 
 Result (round 3): mid-bounce rays (origins on sphere surfaces, uniform directions) touch 5.09 sphere bounds; boxes with the same
 margin 5.04 (-1 %), with a margin no analysis could justify (m = 3e-4) 4.23 (-17 %); camera rays 6.97 / 5.88 / 5.38. A box test
@@ -75,7 +75,7 @@ dc=np.stack([x,y,-np.ones(N)],1); dc/=np.linalg.norm(dc,axis=1,keepdims=True)
 stats(np.zeros((N,3)),dc,'camera rays')
 
 
-# ---- what was built instead: the RAY's distance, and near-minimal enclosing balls (csrc/ptss_api.hip enclosingBall) -------------
+# ---- what was built instead: the RAY's distance, and near-minimal enclosing balls (csrc/ptpack.h enclosingBall) -------------
 def ball(l):
     l = np.array(l); c = P[l].mean(0); rbest = 1e30; cbest = c
     for it in range(1, 513):
