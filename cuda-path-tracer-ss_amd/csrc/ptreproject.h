@@ -16,6 +16,8 @@
 // hidden), and its history entry is finite with weight > 0. Then, over the counting taps,
 //   B = sum b_q;  w = min((sum b_q weight_q) / B, maxHistory), 0 if B < minCoverage;  t = w / (n + w)
 //   out = c_p + ((sum b_q (c_q - c_p)) / B) t,  clamped per channel to [min, max] of c_p and the counting c_q;  weight = n + w
+// Moving triangles (ptss_reproject_motion): for a hit, P is replaced by prevPoint_p of a ptss_pixel_motion row
+// (ptmotion.h) — where the surface point was in the previous pose — and nothing else changes.
 // — the normalised mean h = sum b c / sum b written around c_p, as the filter's is (ptdenoise.h): a constant image stays constant
 // exactly. A rejected pixel, B = 0 or w = 0 give (c_p, n) exactly.
 #pragma once
@@ -86,17 +88,19 @@ PTM_HD vec3 eyeDirection(const View& c, int x, int y) {
     return normalize(rotate(c.rotation, start));
 }
 
-// Pixel (x, y). materialAt(q) -> int, geometryAt(q) -> Geometry (both of the PREVIOUS features), historyAt(q) -> Entry,
-// q = y * width + x; each is called only for a tap inside the frame, the material first.
-template <class MaterialAt, class GeometryAt, class HistoryAt>
+// Pixel (x, y). pointOf(d) -> vec3, the world point a HIT pixel's surface point is looked up at in the previous frame, d being the
+// pixel's eye direction (called for hits only): where that point is now (a static scene, the overload below) or where it was in the
+// previous pose (ptss_reproject_motion). materialAt(q) -> int, geometryAt(q) -> Geometry (both of the PREVIOUS
+// features), historyAt(q) -> Entry, q = y * width + x; each is called only for a tap inside the frame, the material first.
+template <class PointOf, class MaterialAt, class GeometryAt, class HistoryAt>
 PTM_HD Entry reprojectPixel(int x, int y, int width, int height, vec3 cp, float n, const ptdn::Feature& fp, const View& now, const View& prev,
-                            const Params& prm, MaterialAt materialAt, GeometryAt geometryAt, HistoryAt historyAt) {
+                            const Params& prm, PointOf pointOf, MaterialAt materialAt, GeometryAt geometryAt, HistoryAt historyAt) {
     const Entry keep{cp, n};
     const bool hit = fp.materialIdx >= 0;
     vec3 v = eyeDirection(now, x, y);
     float range = 0.0f;
     if (hit) {
-        v = madd(v, fp.depth, now.position) - prev.position;
+        v = pointOf(v) - prev.position;
         range = length(v);
     }
     const vec3 l = rotate(prev.inverse, v);
@@ -142,6 +146,14 @@ PTM_HD Entry reprojectPixel(int x, int y, int width, int height, vec3 cp, float 
     const float total = n + w;
     const vec3 out = madd(dsum / bsum, ptm::div(w, total), cp);
     return Entry{v3(ptm::clamp(out.x, lo.x, hi.x), ptm::clamp(out.y, lo.y, hi.y), ptm::clamp(out.z, lo.z, hi.z)), total};
+}
+
+// A static scene (ptss_reproject): the point is where the eye ray hits, P = fma(d_p, depth_p, o_now).
+template <class MaterialAt, class GeometryAt, class HistoryAt>
+PTM_HD Entry reprojectPixel(int x, int y, int width, int height, vec3 cp, float n, const ptdn::Feature& fp, const View& now, const View& prev,
+                            const Params& prm, MaterialAt materialAt, GeometryAt geometryAt, HistoryAt historyAt) {
+    auto pointOf = [&](vec3 d) -> vec3 { return madd(d, fp.depth, now.position); };
+    return reprojectPixel(x, y, width, height, cp, n, fp, now, prev, prm, pointOf, materialAt, geometryAt, historyAt);
 }
 
 }  // namespace ptrp

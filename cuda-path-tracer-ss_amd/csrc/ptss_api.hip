@@ -1055,6 +1055,30 @@ int ptss_render_features(ptss_context* c, ptss_pixel_feature* dev_features, void
     return PTSS_OK;
 }
 
+// ptss_render_features_motion: the same launch shape; the previous records are the caller's, read in place
+int ptss_render_features_motion(ptss_context* c, const ptss_triangle* dev_triangles_prev, size_t first, size_t count,
+                                ptss_pixel_feature* dev_features, ptss_pixel_motion* dev_motion, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features || !dev_motion) return fail(PTSS_EINVAL, "dev_features or dev_motion is null");
+    if (count > 0 && !dev_triangles_prev) return fail(PTSS_EINVAL, "dev_triangles_prev is null with count > 0");
+    if (((uintptr_t)dev_features | (uintptr_t)dev_motion) & 15u) return fail(PTSS_EINVAL, "dev_features and dev_motion must be 16-byte aligned");
+    if ((uintptr_t)dev_triangles_prev & 3u) return fail(PTSS_EINVAL, "dev_triangles_prev must be 4-byte aligned");
+    if (count > 0) {
+        const size_t T = (size_t)c->images[0].layout.numTriangles;
+        if (first >= T || count > T - first) return fail(PTSS_ERANGE, "first .. first + count - 1 leaves the scene's triangles");
+    }
+    if (c->numPixels == 0) return PTSS_OK;   // a rank whose tile is empty
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    HIP_TRY(ptss::launchFeaturesMotion(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, c->numPixels,
+                                       c->gridCap * ptss::kShards, dev_triangles_prev, count ? (uint32_t)first : 0u, (uint32_t)count, dev_motion,
+                                       &c->launchedKernels));
+    return PTSS_OK;
+}
+
 int ptss_default_denoise_params(ptss_denoise_params* p) {
     if (!p) return fail(PTSS_EINVAL, "params is null");
     p->structSize = (unsigned int)sizeof(*p);
@@ -1128,19 +1152,22 @@ int ptss_default_reproject_params(ptss_reproject_params* p) {
     return PTSS_OK;
 }
 
-int ptss_reproject(ptss_context* c, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
-                   const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
-                   const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream) {
+// ptss_reproject / ptss_reproject_motion: one set of checks, one launch; motion: the point of a hit comes from dev_motion_now
+static int reprojectCall(ptss_context* c, const char* what, bool motion, const ptss_pixel_feature* dev_features_now,
+                         const ptss_pixel_motion* dev_motion_now, const ptss_camera* prev_camera, const ptss_pixel_feature* dev_features_prev,
+                         const ptss_history_entry* dev_history_prev, const ptss_reproject_params* params, ptss_history_entry* dev_history_out,
+                         void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (!dev_features_now || !dev_history_out) return fail(PTSS_EINVAL, "null argument");
+    if (!dev_features_now || !dev_history_out || (motion && !dev_motion_now)) return fail(PTSS_EINVAL, "null argument");
     if (dev_history_prev && (!prev_camera || !dev_features_prev)) return fail(PTSS_EINVAL, "a history needs its camera and its features");
     if (const char* why = ptrp::paramsError(params)) return fail(PTSS_EINVAL, why);
     if (static_cast<const void*>(dev_history_out) == static_cast<const void*>(dev_history_prev))
         return fail(PTSS_EINVAL, "dev_history_out must not be dev_history_prev: a pixel's taps are other pixels' entries");
-    if (((uintptr_t)dev_features_now | (uintptr_t)dev_features_prev | (uintptr_t)dev_history_prev | (uintptr_t)dev_history_out) & 15u)
-        return fail(PTSS_EINVAL, "features and histories must be 16-byte aligned");
+    if (((uintptr_t)dev_features_now | (uintptr_t)dev_features_prev | (uintptr_t)dev_history_prev | (uintptr_t)dev_history_out |
+         (uintptr_t)dev_motion_now) & 15u)
+        return fail(PTSS_EINVAL, "features, motion rows and histories must be 16-byte aligned");
     if (c->tile.world > 1)
-        return fail(PTSS_EINVAL, "ptss_reproject needs the whole frame: this context is a pixel-band shard (tileWorld > 1)");
+        return fail(PTSS_EINVAL, (std::string(what) + " needs the whole frame: this context is a pixel-band shard (tileWorld > 1)").c_str());
     if (c->numPixels == 0) return PTSS_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
     hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
@@ -1151,9 +1178,28 @@ int ptss_reproject(ptss_context* c, const ptss_pixel_feature* dev_features_now, 
     const int width = c->tile.width, height = c->tile.height;
     const ptrp::View now = ptrp::viewOf(c->camera, width, height);
     const ptrp::View prev = dev_history_prev ? ptrp::viewOf(*prev_camera, width, height) : now;
-    HIP_TRY(ptss::launchReproject(st, c->dAccum, dev_features_now, dev_features_prev, dev_history_prev, dev_history_out, width, height, now, prev,
-                                  ptrp::paramsOf(*params), inverseTicks, n, &c->launchedKernels));
+    if (motion)
+        HIP_TRY(ptss::launchReprojectMotion(st, c->dAccum, dev_features_now, dev_motion_now, dev_features_prev, dev_history_prev, dev_history_out,
+                                            width, height, now, prev, ptrp::paramsOf(*params), inverseTicks, n, &c->launchedKernels));
+    else
+        HIP_TRY(ptss::launchReproject(st, c->dAccum, dev_features_now, dev_features_prev, dev_history_prev, dev_history_out, width, height, now, prev,
+                                      ptrp::paramsOf(*params), inverseTicks, n, &c->launchedKernels));
     return PTSS_OK;
+}
+
+int ptss_reproject(ptss_context* c, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
+                   const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
+                   const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream) {
+    return reprojectCall(c, "ptss_reproject", false, dev_features_now, nullptr, prev_camera, dev_features_prev, dev_history_prev, params,
+                         dev_history_out, hipStream);
+}
+
+int ptss_reproject_motion(ptss_context* c, const ptss_pixel_feature* dev_features_now, const ptss_pixel_motion* dev_motion_now,
+                          const ptss_camera* prev_camera, const ptss_pixel_feature* dev_features_prev,
+                          const ptss_history_entry* dev_history_prev, const ptss_reproject_params* params,
+                          ptss_history_entry* dev_history_out, void* hipStream) {
+    return reprojectCall(c, "ptss_reproject_motion", true, dev_features_now, dev_motion_now, prev_camera, dev_features_prev, dev_history_prev,
+                         params, dev_history_out, hipStream);
 }
 
 int ptss_read_denoise_plane(ptss_context* c, float* host_float3, size_t count, int* level) {

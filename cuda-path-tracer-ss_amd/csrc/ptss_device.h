@@ -165,6 +165,11 @@ hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneL
 // first-hit features (ptss_render_features): out = n x 32 B, one ptss_pixel_feature per local pixel
 hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
                           ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launched);
+// ... and the motion rows beside them (ptss_render_features_motion; bit 58 + inLds of *launched): prevRecords = `count` caller
+// records (76 B each, a device pointer; not read when count = 0), motionOut = n x 16 B, one ptss_pixel_motion per local pixel
+hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                                ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, const void* prevRecords, uint32_t first,
+                                uint32_t count, void* motionOut, unsigned long long* launched);
 // one pass of ptss_denoise (ptss_denoise.hip; bit 54 of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,
@@ -181,5 +186,9 @@ hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout&
 hipError_t launchReproject(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* featuresPrev, const void* historyPrev,
                            void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev, const ptrp::Params& params,
                            float inverseTicks, float n, unsigned long long* launched);
+// ptss_reproject_motion (bit 60 of *launched): the same, the world point of a hit taken from motionNow (16 B per pixel)
+hipError_t launchReprojectMotion(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* motionNow, const void* featuresPrev,
+                                 const void* historyPrev, void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev,
+                                 const ptrp::Params& params, float inverseTicks, float n, unsigned long long* launched);
 
 }  // namespace ptss

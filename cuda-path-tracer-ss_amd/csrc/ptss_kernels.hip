@@ -24,6 +24,7 @@
 // Arithmetic mirrors oracle/oracle.cpp operation for operation (ptmath.h; -ffp-contract=off);
 // every restructuring below is argued exact where it is made.
 #include "ptss_device.h"
+#include "ptmotion.h"
 #include "ptquant.h"
 #include "pttri.h"
 
@@ -2596,9 +2597,23 @@ __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__
 // ---- FIRST-HIT FEATURES (ptss_render_features) --------------------------------------------------------------
 // One lane per local pixel: the eye ray through the pixel's centre with bounce 0's operations (bounceTile, kFirst; a jitter of
 // 0.5 in place of the two random draws), then closestQuery with tmax = +inf. Like the queries it reads the scene image only.
-template <bool kSceneInLds>
+// kMotion (ptss_render_features_motion): the same trace also answers where the hit point was in the previous pose
+// (csrc/ptmotion.h), one 16-byte row per pixel. Only lanes that hit a triangle of the moved range read a previous record — nine
+// words of a 76-byte record that is only 4-byte aligned (hipcc emits two 16-byte loads and a 4-byte one, which gfx950 serves at
+// that alignment) — so a wave over static surfaces issues none; neighbouring lanes mostly hit the same or neighbouring triangles,
+// whose records share cache lines. Without kMotion the argument is empty.
+template <bool kMotion>
+struct FeatureMotion {};
+template <>
+struct FeatureMotion<true> {
+    const float* prevRecords;   // `count` records of 19 words: the previous pose of triangles first .. first + count - 1
+    uint32_t first, count;
+    float4* out;
+};
+
+template <bool kSceneInLds, bool kMotion = false>
 __global__ __launch_bounds__(kBlock) void featureKernel(const float4* __restrict__ sceneBlob, SceneLayout L, TileMap tile, EyeParams eye,
-                                                         vec3 defaultColor, float4* __restrict__ out, uint32_t n) {
+                                                         vec3 defaultColor, float4* __restrict__ out, uint32_t n, FeatureMotion<kMotion> motion) {
     extern __shared__ __attribute__((aligned(256))) float4 lds[];
     const float4* sc;
     if constexpr (kSceneInLds) {
@@ -2628,6 +2643,11 @@ __global__ __launch_bounds__(kBlock) void featureKernel(const float4* __restrict
             float4* f = out + 2 * (size_t)i;
             f[0] = float4{q.normal.x, q.normal.y, q.normal.z, q.dist};
             f[1] = float4{albedo.x, albedo.y, albedo.z, asF((uint32_t)q.materialIdx)};
+            if constexpr (kMotion) {
+                const ptmo::Motion m = ptmo::pixelMotion(d, eye.camera.position, q.kind, q.prim, q.dist, q.w1, q.w2, motion.prevRecords,
+                                                         motion.first, motion.count);
+                motion.out[i] = float4{m.prevPoint.x, m.prevPoint.y, m.prevPoint.z, asF((uint32_t)m.surface)};
+            }
         }
     }
 }
@@ -2755,9 +2775,24 @@ hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout l
     if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
     const size_t lds = sceneInLds ? (size_t)layout.ldsVec4 * sizeof(float4) : 0;
     hipLaunchKernelGGL(sceneInLds ? featureKernel<true> : featureKernel<false>, dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, tile, eye,
-                       defaultColor, static_cast<float4*>(out), n);
+                       defaultColor, static_cast<float4*>(out), n, FeatureMotion<false>{});
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) *launched |= 1ull << (52 + (sceneInLds ? 1 : 0));
+    return e;
+}
+
+// the feature kernel with the motion rows (bit 58 + inLds of *launched): the same grid
+hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                                ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, const void* prevRecords, uint32_t first,
+                                uint32_t count, void* motionOut, unsigned long long* launched) {
+    unsigned blocks = blocksFor(n, kBlock);
+    if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
+    const size_t lds = sceneInLds ? (size_t)layout.ldsVec4 * sizeof(float4) : 0;
+    const FeatureMotion<true> motion{static_cast<const float*>(prevRecords), first, count, static_cast<float4*>(motionOut)};
+    const auto kernel = sceneInLds ? featureKernel<true, true> : featureKernel<false, true>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, tile, eye, defaultColor, static_cast<float4*>(out), n, motion);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *launched |= 1ull << (58 + (sceneInLds ? 1 : 0));
     return e;
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ptmesh.h"
+#include "ptmotion.h"
 #include "ptss_device.h"
 
 namespace ptss {
@@ -29,9 +30,7 @@ __global__ __launch_bounds__(kUpdateBlock) void sceneUpdateKernel(float4* __rest
     __syncthreads();
     if (threadIdx.x >= inBlock) return;
     const float* r = reinterpret_cast<const float*>(rec + threadIdx.x * kTriWords);   // v0, v1, v2, n0, n1, n2, materialIdx (ignored)
-    bool ok = true;
-    for (int k = 0; k < 9; ++k) ok = ok && __builtin_fabsf(r[k]) <= 0x1p40f;   // false for NaN and infinities
-    if (!ok) {
+    if (!ptmo::recordAccepted(r)) {   // (false for NaN and infinities; ptss_render_features_motion asks the same question)
         if (rejected) atomicAdd(rejected, 1ull);
         return;
     }

@@ -10,6 +10,7 @@
 #include "Scene.h"
 #include "ptdenoise.h"
 #include "ptreproject.h"
+#include "ptmotion.h"
 #include "ptquant.h"
 #include "ptmesh.h"
 #include "ptpack.h"
@@ -293,9 +294,11 @@ int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pix
     return denoiseColours(plane, features, width, height, params, out_rgba, out_float);
 }
 
-int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
-                         int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_feature* features_prev,
-                         const ptss_history_entry* history_prev, const ptss_reproject_params* params, ptss_history_entry* out) {
+// ptss_probe_reproject / ptss_probe_reproject_motion: one loop; motion_now != nullptr: the point of a hit comes from its row
+static int probeReproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev, int width,
+                          int height, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                          const ptss_pixel_feature* features_prev, const ptss_history_entry* history_prev, const ptss_reproject_params* params,
+                          ptss_history_entry* out) {
     if (!accum || !camera_now || !features_now || !out || width <= 0 || height <= 0 || n < 0) return PTSS_HOST_EINVAL;
     if (history_prev && (!camera_prev || !features_prev)) return PTSS_HOST_EINVAL;
     if (ptrp::paramsError(params) || out == history_prev) return PTSS_HOST_EINVAL;
@@ -312,10 +315,46 @@ int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const
             ptrp::Entry e{cp, (float)n};
             if (history_prev) {
                 const ptdn::Feature fp{features_now[p].normal, features_now[p].depth, features_now[p].materialIdx};
-                e = ptrp::reprojectPixel(x, y, width, height, cp, (float)n, fp, now, prev, prm, materialAt, geometryAt, historyAt);
+                if (motion_now) {
+                    auto pointOf = [&](vec3) { return motion_now[p].prevPoint; };
+                    e = ptrp::reprojectPixel(x, y, width, height, cp, (float)n, fp, now, prev, prm, pointOf, materialAt, geometryAt, historyAt);
+                } else {
+                    e = ptrp::reprojectPixel(x, y, width, height, cp, (float)n, fp, now, prev, prm, materialAt, geometryAt, historyAt);
+                }
             }
             out[p] = ptss_history_entry{e.colour.x, e.colour.y, e.colour.z, e.weight};
         }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
+                         int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_feature* features_prev,
+                         const ptss_history_entry* history_prev, const ptss_reproject_params* params, ptss_history_entry* out) {
+    return probeReproject(accum, inverseTicks, n, camera_now, camera_prev, width, height, features_now, nullptr, features_prev, history_prev, params,
+                          out);
+}
+
+int ptss_probe_reproject_motion(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
+                                int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                                const ptss_pixel_feature* features_prev, const ptss_history_entry* history_prev,
+                                const ptss_reproject_params* params, ptss_history_entry* out) {
+    if (!motion_now) return PTSS_HOST_EINVAL;
+    return probeReproject(accum, inverseTicks, n, camera_now, camera_prev, width, height, features_now, motion_now, features_prev, history_prev,
+                          params, out);
+}
+
+int ptss_probe_motion(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_triangle* triangles_prev, size_t first,
+                      size_t count, size_t numTriangles, ptss_pixel_motion* out) {
+    if (n > 0 && (!rays || !hits || !out)) return PTSS_HOST_EINVAL;
+    if (count > 0 && !triangles_prev) return PTSS_HOST_EINVAL;
+    if (count > 0 && (numTriangles >= (size_t(1) << 31) || first >= numTriangles || count > numTriangles - first)) return PTSS_HOST_EINVAL;
+    const float* prev = reinterpret_cast<const float*>(triangles_prev);
+    for (size_t i = 0; i < n; ++i) {
+        const ptss_ray_hit& h = hits[i];
+        const ptmo::Motion m = ptmo::pixelMotion(rays[i].direction, rays[i].origin, h.kind, h.primitive, h.distance, h.w1, h.w2, prev,
+                                                 count ? (uint32_t)first : 0u, (uint32_t)count);
+        out[i] = ptss_pixel_motion{m.prevPoint, m.surface};
+    }
     return PTSS_HOST_OK;
 }
 

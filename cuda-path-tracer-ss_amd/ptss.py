@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from ptss_types import (SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
-                        PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
+                        PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -66,6 +66,12 @@ def feature_kernels():
 def reproject_kernels():
     """The reprojection kernel (ptss_reproject): ("reproject",)."""
     return {("reproject",)}
+
+
+def motion_kernels():
+    """The kernels of the motion path (ptss_render_features_motion / ptss_reproject_motion): ("features_motion", inLds) and
+    ("reproject_motion",)."""
+    return {("features_motion", lds) for lds in (False, True)} | {("reproject_motion",)}
 
 
 _host = None
@@ -125,6 +131,9 @@ def host_lib():
         L.ptss_probe_denoise_history.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
         L.ptss_probe_reproject.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
+        L.ptss_probe_reproject_motion.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
+        L.ptss_probe_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
         _host = L
     return _host
 
@@ -197,6 +206,8 @@ def device_lib():
         L.ptss_default_reproject_params.argtypes = [C.POINTER(ReprojectParams)]
         L.ptss_reproject.argtypes = [vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
         L.ptss_denoise_history.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
+        L.ptss_render_features_motion.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]
+        L.ptss_reproject_motion.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
         L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
         L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
         L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -381,6 +392,8 @@ assert RAY_DTYPE.itemsize == C.sizeof(RayQuery) and HIT_DTYPE.itemsize == C.size
 assert FEATURE_DTYPE.itemsize == C.sizeof(PixelFeature)
 HISTORY_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32), ("weight", np.float32)])
 assert HISTORY_DTYPE.itemsize == C.sizeof(HistoryEntry)
+MOTION_DTYPE = np.dtype([("prevPoint", np.float32, 3), ("surface", np.int32)])
+assert MOTION_DTYPE.itemsize == C.sizeof(PixelMotion)
 
 
 def default_denoise_params(**overrides):
@@ -455,6 +468,54 @@ def probe_reproject(accum, inverse_ticks, n, camera_now, camera_prev, width, hei
                                          C.byref(params if params is not None else default_reproject_params()), out.ctypes.data_as(C.c_void_p))
     if rc != 0:
         raise PtssError(f"ptss_probe_reproject: {rc}")
+    return out
+
+
+def probe_reproject_motion(accum, inverse_ticks, n, camera_now, camera_prev, width, height, features_now, motion_now, features_prev,
+                           history_prev, params=None):
+    """ptss_reproject_motion on the host: probe_reproject with the world point of every hit pixel taken from motion_now, (H*W,)
+    MOTION_DTYPE. Returns (H*W,) HISTORY_DTYPE."""
+    a = np.ascontiguousarray(accum, dtype=np.uint32).reshape(-1, 3)
+    fn = np.ascontiguousarray(features_now, dtype=FEATURE_DTYPE).reshape(-1)
+    mn = np.ascontiguousarray(motion_now, dtype=MOTION_DTYPE).reshape(-1)
+    if len(a) != width * height or len(fn) != width * height or len(mn) != width * height:
+        raise ValueError("accum, features_now and motion_now must hold width * height pixels")
+    fp = hp = None
+    if history_prev is not None:
+        fp = np.ascontiguousarray(features_prev, dtype=FEATURE_DTYPE).reshape(-1)
+        hp = np.ascontiguousarray(history_prev, dtype=HISTORY_DTYPE).reshape(-1)
+        if len(fp) != width * height or len(hp) != width * height:
+            raise ValueError("features_prev and history_prev must hold width * height pixels")
+    out = np.empty(len(a), dtype=HISTORY_DTYPE)
+    rc = host_lib().ptss_probe_reproject_motion(a.ctypes.data_as(_u32p), float(inverse_ticks), int(n), C.byref(camera_now),
+                                                C.byref(camera_prev) if camera_prev is not None else None, width, height,
+                                                fn.ctypes.data_as(C.c_void_p), mn.ctypes.data_as(C.c_void_p),
+                                                fp.ctypes.data_as(C.c_void_p) if fp is not None else None,
+                                                hp.ctypes.data_as(C.c_void_p) if hp is not None else None,
+                                                C.byref(params if params is not None else default_reproject_params()),
+                                                out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_reproject_motion: {rc}")
+    return out
+
+
+def probe_motion(rays, hits, prev_triangles=None, first=0, num_triangles=0):
+    """ptss_render_features_motion's rows on the host (csrc/ptmotion.h): rays (N, 8) float32 or (N,) RAY_DTYPE, hits (N,) HIT_DTYPE
+    (what intersect() returned for them), prev_triangles an (n,) TRIANGLE_DTYPE array — the previous pose of triangles first ..
+    first + n - 1 of a scene of num_triangles — or None: nothing moved. Returns (N,) MOTION_DTYPE."""
+    r = np.ascontiguousarray(rays)
+    r = (r.view(np.float32) if r.dtype == RAY_DTYPE else r.astype(np.float32, copy=False)).reshape(-1, 8)
+    r = np.ascontiguousarray(r)
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+    if len(r) != len(h):
+        raise ValueError("one hit per ray")
+    t = np.ascontiguousarray(prev_triangles, dtype=TRIANGLE_DTYPE).reshape(-1) if prev_triangles is not None else None
+    out = np.empty(len(h), dtype=MOTION_DTYPE)
+    rc = host_lib().ptss_probe_motion(r.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), len(h),
+                                      t.ctypes.data_as(C.c_void_p) if t is not None and len(t) else None, int(first),
+                                      len(t) if t is not None else 0, int(num_triangles), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_motion: {rc}")
     return out
 
 
@@ -704,6 +765,11 @@ class Renderer:
             out.add(("refit",))
         if v.value >> 57 & 1:
             out.add(("reproject",))
+        for j in range(2):  # the feature kernel with motion rows: bits 58 + inLds
+            if v.value >> (58 + j) & 1:
+                out.add(("features_motion", bool(j)))
+        if v.value >> 60 & 1:
+            out.add(("reproject_motion",))
         return out
 
     # --- scene updates (ptss_set_scene / ptss_update_triangles / ptss_reseed) -------------------------------------
@@ -851,6 +917,47 @@ class Renderer:
         self._have_features = True
         return out
 
+    def motion_devptr(self):
+        return self._device_buffer("motion", self.local_pixels * MOTION_DTYPE.itemsize)
+
+    def features_motion(self, prev_triangles=None, first=0, stream=None):
+        """ptss_render_features_motion: the first-hit features of the current camera AND where each pixel's surface point was in the
+        previous pose -> ((local_pixels,) FEATURE_DTYPE, (local_pixels,) MOTION_DTYPE). prev_triangles: the previous pose of the
+        triangles first .. first + n - 1 — an (n,) TRIANGLE_DTYPE array to upload, or a contiguous float32 device tensor of n x 19
+        words (as update_triangles takes them; asynchronous work is ordered on `stream`, default the tensor's current torch stream)
+        — or None: nothing moved. Both device buffers are kept (features_devptr, motion_devptr): denoise() and reproject(motion=True)
+        use them."""
+        L = device_lib()
+        d_feat, d_mot = self.features_devptr(), self.motion_devptr()
+        if type(prev_triangles).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            t = prev_triangles
+            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() % 19:
+                raise ValueError("prev_triangles: a contiguous float32 device tensor of n x 19 words")
+            if stream is None:
+                stream = torch.cuda.current_stream(t.device).cuda_stream
+            d_prev, count = C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 19
+        elif prev_triangles is None:
+            d_prev, count = None, 0
+        else:
+            a = np.ascontiguousarray(prev_triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+            d_prev, count = None, len(a)
+            if count:
+                d_prev = self._device_buffer_at_least("prev_triangles_upload", a.nbytes)
+                _hip_check(_hip_lib().hipMemcpy(d_prev, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+        _check(L.ptss_render_features_motion(self._ctx, d_prev, first, count, d_feat, d_mot, C.c_void_p(stream) if stream else None))
+        feat = np.empty(self.local_pixels, dtype=FEATURE_DTYPE)
+        mot = np.empty(self.local_pixels, dtype=MOTION_DTYPE)
+        if self.local_pixels:
+            if stream:
+                _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            self.synchronize()
+            _hip_check(_hip_lib().hipMemcpy(feat.ctypes.data, d_feat, feat.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+            _hip_check(_hip_lib().hipMemcpy(mot.ctypes.data, d_mot, mot.nbytes, 2), "hipMemcpy")
+        self._have_features = True
+        return feat, mot
+
     def denoise(self, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None, stream=None):
         """ptss_denoise of the accumulated image -> (local_pixels, 4) uint8 RGBA. features: None (the buffer of the last
         features() call, rendered now if there is none or the camera was set since), a FEATURE_DTYPE array to upload, or a device
@@ -904,12 +1011,14 @@ class Renderer:
         return out
 
     def reproject(self, prev_camera=None, prev_features=None, prev_history=None, features=None, params=None, dev_out=None, stream=None,
-                  read=True, **overrides):
+                  read=True, motion=None, **overrides):
         """ptss_reproject: the history of the previous pose carried into the current frame -> (local_pixels,) HISTORY_DTYPE (None
         with read=False: the caller keeps the device buffer). prev_history None = no history. prev_features / prev_history /
         features: device pointers (int) the caller keeps, or arrays that are uploaded; features None = the buffer of the last
         features() call, rendered now if the camera was set since. dev_out: a device pointer (default history_devptr()), never
-        prev_history's. params: a ReprojectParams (default_reproject_params(**overrides) otherwise)."""
+        prev_history's. params: a ReprojectParams (default_reproject_params(**overrides) otherwise). motion: None = ptss_reproject;
+        otherwise ptss_reproject_motion with these rows of the CURRENT pose — True (the buffer of the last features_motion() call),
+        a device pointer (int) or a MOTION_DTYPE array to upload."""
         if features is None:
             if not self._have_features:
                 self.features()
@@ -928,8 +1037,14 @@ class Renderer:
             dev_out = self.history_devptr()
         elif isinstance(dev_out, int):
             dev_out = C.c_void_p(dev_out)
-        _check(device_lib().ptss_reproject(self._ctx, d_now, C.byref(prev_camera) if prev_camera is not None else None, d_fprev, d_hprev,
-                                           C.byref(params), dev_out, C.c_void_p(stream) if stream else None))
+        cam = C.byref(prev_camera) if prev_camera is not None else None
+        if motion is None or motion is False:
+            _check(device_lib().ptss_reproject(self._ctx, d_now, cam, d_fprev, d_hprev, C.byref(params), dev_out,
+                                               C.c_void_p(stream) if stream else None))
+        else:
+            d_mot = self.motion_devptr() if motion is True else self._device_input("motion_upload", motion, MOTION_DTYPE)
+            _check(device_lib().ptss_reproject_motion(self._ctx, d_now, d_mot, cam, d_fprev, d_hprev, C.byref(params), dev_out,
+                                                      C.c_void_p(stream) if stream else None))
         return self.read_history(dev_out) if read else None
 
     def denoise_history(self, history=None, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None,

@@ -76,6 +76,13 @@ class HistoryEntry(C.Structure):
     _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("weight", C.c_float)]
 
 
+class PixelMotion(C.Structure):
+    _fields_ = [("prevPoint", Vec3), ("surface", C.c_int)]
+
+
+SURFACE_TRIANGLE = 0x40000000   # PixelMotion.surface of triangle t: this | t
+
+
 class ReprojectParams(C.Structure):
     _fields_ = [("structSize", C.c_uint), ("cosNormal", C.c_float), ("depthTolerance", C.c_float), ("maxHistory", C.c_float),
                 ("minCoverage", C.c_float)]
@@ -94,6 +101,7 @@ SCENE_LAYOUT_MESH_FIELDS = ("numLeaves", "numGroups", "offGroup", "offLeaf", "re
 assert C.sizeof(Sphere) == 20 and C.sizeof(Triangle) == 76 and C.sizeof(Material) == 76
 assert C.sizeof(PointLight) == 24 and C.sizeof(AreaLight) == 32 and C.sizeof(Camera) == 40
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PixelFeature) == 32 and C.sizeof(HistoryEntry) == 16
+assert C.sizeof(PixelMotion) == 16 and PixelMotion.surface.offset == 12
 
 
 def struct_to_dict(s):

@@ -157,7 +157,9 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
  * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
  * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise);
- * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles); bit 57 for reprojectKernel (ptss_reproject).
+ * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles); bit 57 for reprojectKernel (ptss_reproject);
+ * bit 58 + inLds for the feature kernel with motion rows (ptss_render_features_motion); bit 60 for the reprojection kernel that
+ * reads them (ptss_reproject_motion).
  * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
@@ -180,6 +182,27 @@ int ptss_occluded(ptss_context* ctx, const ptss_ray_query* dev_rays, uint32_t* d
  * context's stream). Like the queries it reads the scene image only and leaves no trace in frame state; it serves pixel-band shards
  * (tileWorld > 1) for their own pixels. ptss_launched_kernels reports the feature kernel at bit 52 + inLds. */
 int ptss_render_features(ptss_context* ctx, ptss_pixel_feature* dev_features, void* hipStream);
+
+/* First-hit features AND per-pixel motion across a pose change of the triangles, from ONE trace per pixel.
+ * dev_features receives what ptss_render_features writes, bit for bit. dev_triangles_prev: DEVICE pointer to `count` records in the
+ * caller's 76-byte layout, the PREVIOUS pose of the triangles with original indices first .. first + count - 1 — in practice the
+ * buffer handed to the ptss_update_triangles call before the latest one; only its vertices are read. count = 0: nothing moved
+ * (dev_triangles_prev may be NULL). dev_motion (one 16-byte row per local pixel, in the order of dev_features), with d the
+ * pixel-centre direction, o the camera position and the hit what ptss_intersect returns for that ray:
+ *   a miss:          prevPoint = 0, surface = -1;
+ *   a static hit     (a sphere, a triangle outside the range, or one whose previous record ptss_update_triangles would have refused —
+ *                    a vertex not finite or beyond 2^40: it never became geometry): prevPoint = fma(d, distance, o), the point
+ *                    ptss_reproject evaluates; surface = k for sphere k, PTSS_SURFACE_TRIANGLE | t for triangle t;
+ *   a moved triangle t: prevPoint = fma(e2', w2, fma(e1', w1, v0')) with v0', e1' = v1' - v0', e2' = v2' - v0' of record t - first and
+ *                    the hit's weights w1, w2 (they go with vertex1 and vertex2, as in the normal interpolation).
+ * Every image kind is served (the index is the caller's), and pixel-band shards for their own pixels. Asynchronous on hipStream
+ * (NULL: the context's stream); it reads the scene image and the caller's records only and leaves no trace in frame state. The
+ * caller orders it behind the ptss_update_triangles whose pose it traces and keeps dev_triangles_prev alive until it has run.
+ * Refused without touching the device: a null context or output pointer, a null dev_triangles_prev with count > 0, a misaligned
+ * pointer (PTSS_EINVAL); with count > 0, a range that leaves [0, numTriangles) (PTSS_ERANGE). Spheres move only through
+ * ptss_set_scene and count as static. ptss_launched_kernels: bit 58 + inLds. */
+int ptss_render_features_motion(ptss_context* ctx, const ptss_triangle* dev_triangles_prev, size_t first, size_t count,
+                                ptss_pixel_feature* dev_features, ptss_pixel_motion* dev_motion, void* hipStream);
 
 /* levels 5, sigmaColor 64, sigmaNormal 0.1, sigmaDepth 4 (the values behind the figures of DESIGN.md §3.17). */
 int ptss_default_denoise_params(ptss_denoise_params* p);
@@ -217,7 +240,7 @@ int ptss_default_reproject_params(ptss_reproject_params* p);
  * then); out = the mean of c and the taps' colour h weighted n : w, w = the taps' weight capped at maxHistory (0 when the counting
  * taps cover less than minCoverage), weight = n + w. A pixel without usable history gets (c, n) exactly. dev_history_prev = NULL
  * means "no history": out = (c, n) for every pixel, prev_camera and dev_features_prev are ignored (and may be NULL). Moving geometry
- * is out of scope: after ptss_update_triangles or ptss_set_scene pass NULL.
+ * is out of scope HERE: after ptss_set_scene pass NULL; after ptss_update_triangles pass NULL or use ptss_reproject_motion.
  * dev_history_out (one entry per pixel, 16-byte aligned) must not be dev_history_prev. Asynchronous on hipStream (NULL: the
  * context's stream); like ptss_denoise it only reads the accumulator and leaves no trace in frame state. PTSS_EINVAL without
  * touching the device: a null context or required pointer, a wrong structSize, cosNormal outside [-1, 1], depthTolerance or
@@ -226,6 +249,20 @@ int ptss_default_reproject_params(ptss_reproject_params* p);
 int ptss_reproject(ptss_context* ctx, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
                    const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
                    const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream);
+
+/* ptss_reproject across a pose change of the triangles: everything as above, except that the world point of a
+ * pixel whose centre ray hits is dev_motion_now[p].prevPoint (ptss_render_features_motion of the CURRENT camera and pose) — where
+ * that surface point was when dev_history_prev was made — instead of the hit point itself: v = prevPoint - prev_camera's position,
+ * r = |v|. Misses, every tap test (material, normal, depth against r, finite history, coverage), the clamp, the weights, the
+ * argument checks and the dev_history_prev = NULL shortcut are ptss_reproject's; dev_motion_now (16-byte aligned) is required.
+ * With motion rows of count = 0 the result is ptss_reproject's, bit for bit.
+ * A limit: the normal test compares the CURRENT normal with the previous frame's normal at the tap, so a surface that turns by
+ * more than acos(cosNormal) between two frames loses its history — the safe direction. Lighting that changed because geometry
+ * moved is carried over as it was; maxHistory bounds how long that lag lasts. ptss_launched_kernels: bit 60. */
+int ptss_reproject_motion(ptss_context* ctx, const ptss_pixel_feature* dev_features_now, const ptss_pixel_motion* dev_motion_now,
+                          const ptss_camera* prev_camera, const ptss_pixel_feature* dev_features_prev,
+                          const ptss_history_entry* dev_history_prev, const ptss_reproject_params* params,
+                          ptss_history_entry* dev_history_out, void* hipStream);
 
 /* ptss_denoise with the colours of dev_history (a ptss_reproject output) as input instead of the accumulator: the same passes, the
  * same kernels, the same scratch and ordering rules; levels = 0 converts the history's colours to bytes. It updates what

@@ -101,6 +101,19 @@ int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pix
 int ptss_probe_reproject(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
                          int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_feature* features_prev,
                          const ptss_history_entry* history_prev, const ptss_reproject_params* params, ptss_history_entry* out);
+/* ptss_reproject_motion on the host: ptss_probe_reproject with the world point of every hit pixel taken from motion_now (width *
+ * height rows, required), and the same refusals. */
+int ptss_probe_reproject_motion(const uint32_t* accum, float inverseTicks, int n, const ptss_camera* camera_now, const ptss_camera* camera_prev,
+                                int width, int height, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                                const ptss_pixel_feature* features_prev, const ptss_history_entry* history_prev,
+                                const ptss_reproject_params* params, ptss_history_entry* out);
+/* The motion row of ptss_render_features_motion on the host (csrc/ptmotion.h — the very arithmetic the kernel evaluates), for n
+ * rays: direction and origin of rays[i], and kind / primitive / distance / w1 / w2 of hits[i] (what ptss_intersect returned for that
+ * ray); triangles_prev: `count` records, the previous pose of triangles first .. first + count - 1 of a scene of numTriangles.
+ * count = 0: nothing moved (triangles_prev may be NULL). PTSS_HOST_EINVAL: a null rays, hits or out with n > 0, a null
+ * triangles_prev with count > 0, or, with count > 0, a range that leaves [0, numTriangles). */
+int ptss_probe_motion(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_triangle* triangles_prev, size_t first,
+                      size_t count, size_t numTriangles, ptss_pixel_motion* out);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6);
 /* n raw draws and the matching (0,1] floats from a state; state advanced in place. */

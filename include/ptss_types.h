@@ -153,6 +153,15 @@ typedef struct ptss_reproject_params {
     float minCoverage;       /* bilinear weight the counting taps must reach together, else the history is dropped: [0, 1] */
 } ptss_reproject_params;
 
+/* Where the surface point under a pixel's centre was in the PREVIOUS pose (ptss_render_features_motion): one
+ * 16-byte row. A miss: prevPoint 0, surface -1. */
+typedef struct ptss_pixel_motion {
+    ptss_vec3 prevPoint;
+    int surface; /* -1 miss; k for sphere k; 0x40000000 | t for triangle t (the caller's indices) */
+} ptss_pixel_motion;
+
+#define PTSS_SURFACE_TRIANGLE 0x40000000
+
 #if defined(__cplusplus)
 static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
               "ptss_ray_query is two 16-byte rows");
@@ -164,6 +173,7 @@ static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, d
                   offsetof(ptss_pixel_feature, materialIdx) == 28,
               "ptss_pixel_feature is two 16-byte rows");
 static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
+static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -175,6 +185,7 @@ _Static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, 
                    offsetof(ptss_pixel_feature, materialIdx) == 28,
                "ptss_pixel_feature is two 16-byte rows");
 _Static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
+_Static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
 #endif
 
 #ifdef __cplusplus
