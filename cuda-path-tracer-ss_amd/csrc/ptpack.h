@@ -65,7 +65,7 @@ constexpr int kAccelMinSpheres = 64;
 
 // Finite, moderate geometry: every |coordinate| <= 1e15, every sphere radius in [1e-12, 1e15] (false for NaN and infinities).
 // What the chunked traversal requires, and what lets the sphere candidate tests take their shorter form
-// (SceneLayout::sphereBounded, ptss_kernels.hip shiftInSphere<true>: r^2 well inside the normal range, no discriminant near overflow).
+// (SceneLayout::sphereBounded, ptprim.h shiftInSphere<true>: r^2 well inside the normal range, no discriminant near overflow).
 inline bool geometryBounded(const ptss_scene_desc& s) {
     auto ok = [](float v) { return std::fabs(v) <= kAccelLimit; };
     for (size_t i = 0; i < s.numSpheres; ++i) {

@@ -43,7 +43,7 @@ struct SceneLayout {
     int offPointLight;  // P x 2: {position,0},{power,0}
     int offAreaLight;   // A x 2: {power, bits(position of triangle triangleIdx)}, {bits(position of triangleIdx + 1), 0, 0, 0}
     // Sphere acceleration (scenes with many spheres; ptpack.h planImages decides): chunks of kChunkSpheres consecutive sorted spheres
-    // with a conservative bounding sphere each; a lane visits only the chunks its ray can touch (ptss_kernels.hip).
+    // with a conservative bounding sphere each; a lane visits only the chunks its ray can touch (ptaccel.h).
     int accelSpheres;   // 0: every sphere is tested by every ray (the reference's loop); 1: chunked
     int numChunks;
     int offChunk;       // numChunks x {Cx, Cy, Cz, inflated R^2}
@@ -58,7 +58,7 @@ struct SceneLayout {
                         // index, position — read only when a hit is accepted) stay in global memory
     int neeSkipSafe;    // 1: light powers and diffuse colours are finite, so zero Lambert terms are exactly +-0
     int sphereBounded;  // 1: every |coordinate| <= 1e15 and every sphere radius in [1e-12, 1e15]: the sphere candidate tests may take
-                        //    the two-instructions-shorter discriminant form (ptss_kernels.hip shiftInSphere<true>) while the camera is in range
+                        //    the two-instructions-shorter discriminant form (ptprim.h shiftInSphere<true>) while the camera is in range
     int neePairs;       // 1: at least two lights and at least four of five primitives reflect diffusely (diffAvg > 0): a lit point then
                         //    nearly always needs both of its shadow segments, and the kernels that test the pair together (shared origin
                         //    terms, pairAnyHit) pay: +4.8 % on configs[1]'s scene; with specular-only materials about the scene many entries
@@ -75,7 +75,7 @@ struct SceneLayout {
     union {
         uint32_t triClassPack[5];  // positions [begin(c), begin(c + 1)) hold the triangles of class code c = class(e1) * 4 + class(e2): the 17 begins
                                    // (begin(16) = T) as BYTES, four per word — five scalar registers instead of seventeen (classed scenes have
-                                   // T <= 255); a loop header extracts its two bounds with two s_bfe (ptss_kernels.hip classBegin)
+                                   // T <= 255); a loop header extracts its two bounds with two s_bfe (ptprim.h classBegin)
         struct {
             // Mesh image (ptpack.h meshEligible): the triangles stored in a kd order of their centroids, every
             // kMeshLeaf consecutive positions a LEAF and every kMeshLeaf^2 a GROUP, each with a conservative bound of three rows

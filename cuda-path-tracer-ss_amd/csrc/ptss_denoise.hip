@@ -60,7 +60,7 @@ hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src,
     hipLaunchKernelGGL(table[(first ? 2 : 0) + (last ? 1 : 0)], grid, dim3(kDenoiseTileX * kDenoiseTileY), 0, st, src, dst,
                        static_cast<const float4*>(features), width, height, level, inverseTicks);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << 54;
+    if (e == hipSuccess) markLaunched(launched, PTSS_KERNEL_DENOISE);
     return e;
 }
 

@@ -23,7 +23,7 @@ namespace ptss {
 // ceil(tiles / kShards) * kBlock always suffices. Inside a region the rays of one tile (kBlock consecutive slots) form a
 // BLOCK of kRayPlanes planes of kBlock words: word (slot, plane p) = ((slot / kBlock) * kRayPlanes + p) * kBlock +
 // slot % kBlock. Lane i of a wave touches word i of a plane — 256-B contiguous wave accesses — and a plane's offset
-// inside the block is a compile-time constant (addressing: ptss_kernels.hip, tileBlock / slotWord).
+// inside the block is a compile-time constant (addressing: ptraypool.h, tileBlock / slotWord).
 enum RayPlane : int {
     kOx = 0, kOy, kOz,        // origin
     kDx, kDy, kDz,            // direction
@@ -144,6 +144,9 @@ struct FrameBuffers {
 };
 
 // ---- launchers (ptss_kernels.hip) --------------------------------------------------------------
+// Every launcher that takes `launched` records the instantiation it enqueued there, once the launch has succeeded: bit `base + index`
+// of ptss_launched_kernels, base one of the PTSS_KERNEL_* ranges (ptss_types.h), index the instantiation's place in its range.
+inline void markLaunched(unsigned long long* launched, int base, int index = 0) { *launched |= 1ull << (base + index); }
 hipError_t launchRngInit(hipStream_t st, uint32_t* rngHome, uint32_t plane, uint32_t samples, TileMap tile, uint64_t seed,
                          const uint32_t* jumpTable);
 hipError_t launchDisplay(hipStream_t st, const FrameBuffers& fb);
@@ -165,28 +168,28 @@ hipError_t launchQuery(hipStream_t st, bool any, const float4* sceneBlob, SceneL
 // first-hit features (ptss_render_features): out = n x 32 B, one ptss_pixel_feature per local pixel
 hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
                           ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launched);
-// ... and the motion rows beside them (ptss_render_features_motion; bit 58 + inLds of *launched): prevRecords = `count` caller
+// ... and the motion rows beside them (ptss_render_features_motion; PTSS_KERNEL_FEATURES_MOTION + inLds of *launched): prevRecords = `count` caller
 // records (76 B each, a device pointer; not read when count = 0), motionOut = n x 16 B, one ptss_pixel_motion per local pixel
 hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
                                 ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, const void* prevRecords, uint32_t first,
                                 uint32_t count, void* motionOut, unsigned long long* launched);
-// one pass of ptss_denoise (ptss_denoise.hip; bit 54 of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
+// one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,
                          const ptdn::Level& level, float inverseTicks, unsigned long long* launched);
 // ptss_update_triangles (ptss_update.hip). launchSceneUpdate: `count` caller records (76 B each, a device pointer) replace the
-// vertices and normals of the triangles with original indices first .. first + count - 1 (bit 55 of *launched); rejected: the
+// vertices and normals of the triangles with original indices first .. first + count - 1 (PTSS_KERNEL_UPDATE of *launched); rejected: the
 // device counter of records left unwritten, or nullptr not to count (the second image of a context sees the same records).
-// launchMeshRefit: every leaf and group bound of a mesh image recomputed from its stored rows (bit 56).
+// launchMeshRefit: every leaf and group bound of a mesh image recomputed from its stored rows (PTSS_KERNEL_REFIT).
 hipError_t launchSceneUpdate(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, const void* records, uint32_t first, uint32_t count,
                              unsigned long long* rejected, unsigned long long* launched);
 hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, unsigned long long* launched);
-// ptss_reproject (ptss_reproject.hip; bit 57 of *launched): accum = 3 uint32 per pixel, features = 32 B and histories = 16 B per pixel;
+// ptss_reproject (ptss_reproject.hip; PTSS_KERNEL_REPROJECT of *launched): accum = 3 uint32 per pixel, features = 32 B and histories = 16 B per pixel;
 // historyPrev = nullptr: no history (featuresPrev and prev are then not read)
 hipError_t launchReproject(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* featuresPrev, const void* historyPrev,
                            void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev, const ptrp::Params& params,
                            float inverseTicks, float n, unsigned long long* launched);
-// ptss_reproject_motion (bit 60 of *launched): the same, the world point of a hit taken from motionNow (16 B per pixel)
+// ptss_reproject_motion (PTSS_KERNEL_REPROJECT_MOTION of *launched): the same, the world point of a hit taken from motionNow (16 B per pixel)
 hipError_t launchReprojectMotion(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* motionNow, const void* featuresPrev,
                                  const void* historyPrev, void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev,
                                  const ptrp::Params& params, float inverseTicks, float n, unsigned long long* launched);

@@ -1,7 +1,8 @@
 // ptss_diag.h — diagnostic counters of the bounce kernel. They exist only in -DPTSS_DIAG=<bits> builds
 // (tools/build_variants.py: chist, shist, cullstat, pairstat, qhist); with PTSS_DIAG == 0 every hook below is an empty
-// statement and the shipped kernel carries no counter. Included by ptss_kernels.hip inside its anonymous namespace, after
-// the chunk-bound helpers it uses. The host reads the eight words with ptss_debug_counters().
+// statement and the shipped kernel carries no counter. Included by ptaccel.h inside its anonymous namespace, after the
+// chunk-bound helpers it uses, so the counters are local to the one translation unit (ptss_kernels.hip) that includes the
+// layers. The host reads the eight words with ptss_debug_counters().
 #pragma once
 
 #if PTSS_DIAG

@@ -72,7 +72,7 @@ static hipError_t launchReprojectKernel(hipStream_t st, const uint32_t* accum, c
                        static_cast<const float4*>(featuresPrev), static_cast<const float4*>(historyPrev), static_cast<float4*>(historyOut),
                        width, height, now, prev, params, inverseTicks, n, motion);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << (kMotion ? 60 : 57);
+    if (e == hipSuccess) markLaunched(launched, kMotion ? PTSS_KERNEL_REPROJECT_MOTION : PTSS_KERNEL_REPROJECT);
     return e;
 }
 

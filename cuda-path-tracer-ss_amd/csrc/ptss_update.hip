@@ -154,7 +154,7 @@ hipError_t launchSceneUpdate(hipStream_t st, float4* sceneBlob, const SceneLayou
     hipLaunchKernelGGL(sceneUpdateKernel, dim3((count + kUpdateBlock - 1) / kUpdateBlock), dim3(kUpdateBlock), 0, st, sceneBlob, L.offTri,
                        L.offTriNormal, L.offTriVert, L.offTriPos, static_cast<const uint32_t*>(records), first, count, rejected);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << 55;
+    if (e == hipSuccess) markLaunched(launched, PTSS_KERNEL_UPDATE);
     return e;
 }
 
@@ -162,7 +162,7 @@ hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout&
     hipLaunchKernelGGL(meshRefitKernel, dim3((unsigned)((L.mesh.numGroups + 3) / 4)), dim3(256), 0, st, sceneBlob, L.numTriangles, L.offTri,
                        L.mesh.numLeaves, L.mesh.numGroups, L.mesh.offLeaf, L.mesh.offGroup);
     const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) *launched |= 1ull << 56;
+    if (e == hipSuccess) markLaunched(launched, PTSS_KERNEL_REFIT);
     return e;
 }
 

@@ -1,0 +1,34 @@
+// ptwave.h — layer 0 of the device code of ptss_kernels.hip: bit casts, the wave-level votes and the lane-mask helpers every
+// later layer uses (ptraypool.h, ptprim.h, ptaccel.h, pthit.h, ptshade.h). Restates no reference line: the reference has no
+// wave-level code. Like every layer header it is private to the one translation unit that includes it (anonymous namespace).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ptmath.h"
+
+namespace ptss {
+using namespace ptv;   // vec3, quat and their operators (ptmath.h), for every layer and for the kernels
+namespace {
+
+__device__ __forceinline__ float asF(uint32_t u) { return __builtin_bit_cast(float, u); }
+__device__ __forceinline__ uint32_t asU(float f) { return __builtin_bit_cast(uint32_t, f); }
+__device__ __forceinline__ vec3 xyz(float4 v) { return vec3{v.x, v.y, v.z}; }
+// "does any lane of the wave say yes": a ballot compared with zero stays in scalar registers (s_and / s_cmp / s_cbranch);
+// hipcc's __any() round-trips the mask through a VGPR (v_cndmask + v_cmp) — two VALU instructions per triangle test
+__device__ __forceinline__ bool waveAny(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
+// "every active lane says yes" (p must be one direct compare, see maskOf)
+__device__ __forceinline__ bool waveAll(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }
+// orders this wave's LDS traffic for the compiler; within one wave the LDS executes in order
+__device__ __forceinline__ void waveLdsFence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+// Lane predicates travel as 64-bit wave masks (one v_cmp each, combined with scalar ANDs, carried over the wave-uniform
+// branch in SGPRs, turned back into a lane predicate for free by inverse_ballot). As bools they made hipcc round-trip
+// through a VGPR — v_cndmask + v_cmp — every time a compound condition met a ballot: twice per triangle.
+__device__ __forceinline__ unsigned long long maskOf(bool directCompare) { return __builtin_amdgcn_ballot_w64(directCompare); }
+
+__device__ __forceinline__ uint32_t lowBits(int cnt) { return (cnt >= 32) ? 0xffffffffu : ((1u << cnt) - 1u); }
+__device__ __forceinline__ uint32_t lowBitsClamped(int cnt) { return (cnt <= 0) ? 0u : lowBits(cnt); }
+
+}  // namespace
+}  // namespace ptss

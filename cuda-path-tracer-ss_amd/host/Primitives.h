@@ -1,6 +1,6 @@
 // Primitives.h — host faces of the two primitive records (reference: CudaTracer/Primitives.h:6-23
 // Triangle, :86-96 Sphere). Only the data + constructors live on the host; the intersectors
-// (Primitives.h:25-83, :107-175) are device code in csrc/ptss_kernels.hip.
+// (Primitives.h:25-83, :107-175) are device code in csrc/ptprim.h.
 #pragma once
 #include "RenderStructs.h"
 

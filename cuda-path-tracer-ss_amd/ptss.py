@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ptss_types import (SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
+from ptss_types import (KERNEL_BITS, SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
                         PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,42 +36,70 @@ class RenderConfig(C.Structure):
                 ("lanesFreeRun", C.c_int), ("oneLaunchFrames", C.c_int)]
 
 
-# scene variants of the bounce / frame kernels, in the order of their bit in ptss_launched_kernels (include/ptss.h)
+# scene variants of the bounce / frame kernels, in the order of their bit in ptss_launched_kernels (include/ptss_types.h)
 KERNEL_VARIANTS = ("accel", "bounded+pairs", "bounded", "plain")
+
+
+def _bounce(variant, j):   # a bounce kernel's place in its variant's eight: last * 4 + inLds * 2 + first
+    return ("bounce", variant, bool(j & 4), bool(j & 2), bool(j & 1))
+
+
+# the instantiation behind offset j of each range of ptss_types.KERNEL_BITS
+_KERNEL_NAMES = {
+    "BOUNCE": lambda j: _bounce(KERNEL_VARIANTS[j // 8], j % 8),
+    "FRAME": lambda j: ("frame", KERNEL_VARIANTS[j]),
+    "BOUNCE_MESH": lambda j: _bounce("mesh", j),
+    "QUERY": lambda j: ("query", "any" if j & 2 else "closest", bool(j & 1)),
+    "FEATURES": lambda j: ("features", bool(j)),
+    "DENOISE": lambda j: ("denoise",),
+    "UPDATE": lambda j: ("update",),
+    "REFIT": lambda j: ("refit",),
+    "REPROJECT": lambda j: ("reproject",),
+    "FEATURES_MOTION": lambda j: ("features_motion", bool(j)),
+    "REPROJECT_MOTION": lambda j: ("reproject_motion",),
+}
+# bit of ptss_launched_kernels -> the name launched_kernels() reports for it
+KERNEL_OF_BIT = {base + j: _KERNEL_NAMES[rng](j) for rng, (base, width) in KERNEL_BITS.items() for j in range(width)}
+
+
+def _kernels_of(*ranges):
+    return {KERNEL_OF_BIT[KERNEL_BITS[r][0] + j] for r in ranges for j in range(KERNEL_BITS[r][1])}
+
+
+def decode_launched_kernels(mask):
+    """The names of the bits set in a ptss_launched_kernels mask; a bit no kernel owns names nothing."""
+    return {name for bit, name in KERNEL_OF_BIT.items() if mask >> bit & 1}
 
 
 def all_kernels():
     """Every instantiation ptss_launched_kernels can report: ("bounce", variant, last, inLds, first) and ("frame", variant)."""
-    out = {("frame", v) for v in KERNEL_VARIANTS}
-    for v in KERNEL_VARIANTS:
-        out |= {("bounce", v, last, lds, first) for last in (False, True) for lds in (False, True) for first in (False, True)}
-    return out
+    return _kernels_of("BOUNCE", "FRAME")
 
 
 def mesh_kernels():
     """The bounce-kernel instantiations of the mesh image (no frame kernel): ("bounce", "mesh", last, inLds, first)."""
-    return {("bounce", "mesh", last, lds, first) for last in (False, True) for lds in (False, True) for first in (False, True)}
+    return _kernels_of("BOUNCE_MESH")
 
 
 def query_kernels():
     """The query-kernel instantiations (ptss_intersect / ptss_occluded): ("query", "closest" | "any", inLds)."""
-    return {("query", kind, lds) for kind in ("closest", "any") for lds in (False, True)}
+    return _kernels_of("QUERY")
 
 
 def feature_kernels():
     """The feature-kernel instantiations (ptss_render_features): ("features", inLds)."""
-    return {("features", lds) for lds in (False, True)}
+    return _kernels_of("FEATURES")
 
 
 def reproject_kernels():
     """The reprojection kernel (ptss_reproject): ("reproject",)."""
-    return {("reproject",)}
+    return _kernels_of("REPROJECT")
 
 
 def motion_kernels():
     """The kernels of the motion path (ptss_render_features_motion / ptss_reproject_motion): ("features_motion", inLds) and
     ("reproject_motion",)."""
-    return {("features_motion", lds) for lds in (False, True)} | {("reproject_motion",)}
+    return _kernels_of("FEATURES_MOTION", "REPROJECT_MOTION")
 
 
 _host = None
@@ -741,36 +769,7 @@ class Renderer:
         """The kernel instantiations this context has launched since it was created, as all_kernels() names them."""
         v = C.c_ulonglong()
         _check(device_lib().ptss_launched_kernels(self._ctx, C.byref(v)))
-        out = set()
-        for i, name in enumerate(KERNEL_VARIANTS):
-            for j in range(8):
-                if v.value >> (i * 8 + j) & 1:
-                    out.add(("bounce", name, bool(j & 4), bool(j & 2), bool(j & 1)))
-            if v.value >> (32 + i) & 1:
-                out.add(("frame", name))
-        for j in range(8):  # the mesh image's bounce kernels: bits 40 + last * 4 + inLds * 2 + first
-            if v.value >> (40 + j) & 1:
-                out.add(("bounce", "mesh", bool(j & 4), bool(j & 2), bool(j & 1)))
-        for j in range(4):  # the query kernel: bits 48 + any * 2 + inLds
-            if v.value >> (48 + j) & 1:
-                out.add(("query", "any" if j & 2 else "closest", bool(j & 1)))
-        for j in range(2):  # the feature kernel: bits 52 + inLds
-            if v.value >> (52 + j) & 1:
-                out.add(("features", bool(j)))
-        if v.value >> 54 & 1:
-            out.add(("denoise",))
-        if v.value >> 55 & 1:
-            out.add(("update",))
-        if v.value >> 56 & 1:
-            out.add(("refit",))
-        if v.value >> 57 & 1:
-            out.add(("reproject",))
-        for j in range(2):  # the feature kernel with motion rows: bits 58 + inLds
-            if v.value >> (58 + j) & 1:
-                out.add(("features_motion", bool(j)))
-        if v.value >> 60 & 1:
-            out.add(("reproject_motion",))
-        return out
+        return decode_launched_kernels(v.value)
 
     # --- scene updates (ptss_set_scene / ptss_update_triangles / ptss_reseed) -------------------------------------
     def set_scene(self, scene):

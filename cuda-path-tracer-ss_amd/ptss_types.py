@@ -83,6 +83,23 @@ class PixelMotion(C.Structure):
 SURFACE_TRIANGLE = 0x40000000   # PixelMotion.surface of triangle t: this | t
 
 
+# The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
+# bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
+KERNEL_BITS = {
+    "BOUNCE": (0, 32),
+    "FRAME": (32, 4),
+    "BOUNCE_MESH": (40, 8),
+    "QUERY": (48, 4),
+    "FEATURES": (52, 2),
+    "DENOISE": (54, 1),
+    "UPDATE": (55, 1),
+    "REFIT": (56, 1),
+    "REPROJECT": (57, 1),
+    "FEATURES_MOTION": (58, 2),
+    "REPROJECT_MOTION": (60, 1),
+}
+
+
 class ReprojectParams(C.Structure):
     _fields_ = [("structSize", C.c_uint), ("cosNormal", C.c_float), ("depthTolerance", C.c_float), ("maxHistory", C.c_float),
                 ("minCoverage", C.c_float)]

@@ -152,14 +152,12 @@ int ptss_frame_lanes(const ptss_context* ctx, int* out);
 int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
 
 /* Which kernel instantiations this context has enqueued since ptss_create, as a bitmask (tests/test_gpu_kernel_coverage.py):
- * bit v*8 + last*4 + inLds*2 + first for the bounce kernel of scene variant v (0 many-sphere chunks, 1 bounded sphere test with
- * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test), last / first bounce of the frame, scene image
- * staged in LDS or read in place; bit 32 + v for the one-launch frame kernel of variant v; bit 40 + last*4 + inLds*2 + first for
- * the bounce kernel of the mesh image (which has no frame kernel); bit 48 + any*2 + inLds for the query kernel (ptss_intersect,
- * ptss_occluded); bit 52 + inLds for the feature kernel (ptss_render_features); bit 54 for the denoise kernel (ptss_denoise);
- * bit 55 for sceneUpdateKernel and bit 56 for meshRefitKernel (ptss_update_triangles); bit 57 for reprojectKernel (ptss_reproject);
- * bit 58 + inLds for the feature kernel with motion rows (ptss_render_features_motion); bit 60 for the reprojection kernel that
- * reads them (ptss_reproject_motion).
+ * every kernel owns a range of bits, PTSS_KERNEL_x .. PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x - 1 (ptss_types.h, which also says how the
+ * instantiations of a kernel are numbered inside its range): PTSS_KERNEL_BOUNCE and PTSS_KERNEL_BOUNCE_MESH for the bounce kernels,
+ * PTSS_KERNEL_FRAME for the one-launch frame kernels, PTSS_KERNEL_QUERY (ptss_intersect, ptss_occluded), PTSS_KERNEL_FEATURES
+ * (ptss_render_features), PTSS_KERNEL_DENOISE (ptss_denoise), PTSS_KERNEL_UPDATE and PTSS_KERNEL_REFIT (ptss_update_triangles),
+ * PTSS_KERNEL_REPROJECT (ptss_reproject), PTSS_KERNEL_FEATURES_MOTION (ptss_render_features_motion) and
+ * PTSS_KERNEL_REPROJECT_MOTION (ptss_reproject_motion).
  * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
@@ -171,7 +169,7 @@ int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
  * shortening), else 0. Asynchronous on hipStream (NULL: the context's stream). They read the scene image only, never the
  * per-camera rows, and leave no trace in frame state: they may run between frames or on another stream while frames run.
  * n = 0 returns PTSS_OK; a null context or null pointers with n > 0 return PTSS_EINVAL, n >= 2^31 PTSS_ERANGE, without touching
- * the device. ptss_launched_kernels reports the query kernel at bit 48 + any * 2 + inLds. */
+ * the device. ptss_launched_kernels reports the query kernel at PTSS_KERNEL_QUERY + any * 2 + inLds. */
 int ptss_intersect(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_ray_hit* dev_hits, size_t n, void* hipStream);
 int ptss_occluded(ptss_context* ctx, const ptss_ray_query* dev_rays, uint32_t* dev_occluded, size_t n, void* hipStream);
 
@@ -180,7 +178,7 @@ int ptss_occluded(ptss_context* ctx, const ptss_ray_query* dev_rays, uint32_t* d
  * context's CURRENT camera with tmax = +inf — normal, distance, materialIdx — and that material's diffuseColor, every field bit for
  * bit; a miss: normal 0, depth +inf, materialIdx -1, albedo = the scene's defaultColor. Asynchronous on hipStream (NULL: the
  * context's stream). Like the queries it reads the scene image only and leaves no trace in frame state; it serves pixel-band shards
- * (tileWorld > 1) for their own pixels. ptss_launched_kernels reports the feature kernel at bit 52 + inLds. */
+ * (tileWorld > 1) for their own pixels. ptss_launched_kernels reports the feature kernel at PTSS_KERNEL_FEATURES + inLds. */
 int ptss_render_features(ptss_context* ctx, ptss_pixel_feature* dev_features, void* hipStream);
 
 /* First-hit features AND per-pixel motion across a pose change of the triangles, from ONE trace per pixel.
@@ -200,7 +198,7 @@ int ptss_render_features(ptss_context* ctx, ptss_pixel_feature* dev_features, vo
  * caller orders it behind the ptss_update_triangles whose pose it traces and keeps dev_triangles_prev alive until it has run.
  * Refused without touching the device: a null context or output pointer, a null dev_triangles_prev with count > 0, a misaligned
  * pointer (PTSS_EINVAL); with count > 0, a range that leaves [0, numTriangles) (PTSS_ERANGE). Spheres move only through
- * ptss_set_scene and count as static. ptss_launched_kernels: bit 58 + inLds. */
+ * ptss_set_scene and count as static. ptss_launched_kernels: PTSS_KERNEL_FEATURES_MOTION + inLds. */
 int ptss_render_features_motion(ptss_context* ctx, const ptss_triangle* dev_triangles_prev, size_t first, size_t count,
                                 ptss_pixel_feature* dev_features, ptss_pixel_motion* dev_motion, void* hipStream);
 
@@ -217,7 +215,7 @@ int ptss_default_denoise_params(ptss_denoise_params* p);
  * and freed by ptss_destroy. Asynchronous on hipStream (NULL: the context's stream); the caller orders it behind the frames whose
  * accumulator it reads. The planes belong to the context: the denoise calls of ONE context (and ptss_read_denoise_plane) must be
  * ordered among themselves — the same stream, or an event or a synchronise between two streams. A wrong structSize, a null pointer or levels outside 0..6 return PTSS_EINVAL without touching the device; so does a
- * sharded context (tileWorld > 1): a band of rows has no neighbours to filter with. ptss_launched_kernels: bit 54. */
+ * sharded context (tileWorld > 1): a band of rows has no neighbours to filter with. ptss_launched_kernels: PTSS_KERNEL_DENOISE. */
 int ptss_denoise(ptss_context* ctx, const ptss_pixel_feature* dev_features, const ptss_denoise_params* params, ptss_uchar4* dev_out,
                  void* hipStream);
 
@@ -245,7 +243,7 @@ int ptss_default_reproject_params(ptss_reproject_params* p);
  * context's stream); like ptss_denoise it only reads the accumulator and leaves no trace in frame state. PTSS_EINVAL without
  * touching the device: a null context or required pointer, a wrong structSize, cosNormal outside [-1, 1], depthTolerance or
  * maxHistory negative or not finite, minCoverage outside [0, 1], equal history pointers, a sharded context (tileWorld > 1).
- * ptss_launched_kernels: bit 57. */
+ * ptss_launched_kernels: PTSS_KERNEL_REPROJECT. */
 int ptss_reproject(ptss_context* ctx, const ptss_pixel_feature* dev_features_now, const ptss_camera* prev_camera,
                    const ptss_pixel_feature* dev_features_prev, const ptss_history_entry* dev_history_prev,
                    const ptss_reproject_params* params, ptss_history_entry* dev_history_out, void* hipStream);
@@ -258,7 +256,7 @@ int ptss_reproject(ptss_context* ctx, const ptss_pixel_feature* dev_features_now
  * With motion rows of count = 0 the result is ptss_reproject's, bit for bit.
  * A limit: the normal test compares the CURRENT normal with the previous frame's normal at the tap, so a surface that turns by
  * more than acos(cosNormal) between two frames loses its history — the safe direction. Lighting that changed because geometry
- * moved is carried over as it was; maxHistory bounds how long that lag lasts. ptss_launched_kernels: bit 60. */
+ * moved is carried over as it was; maxHistory bounds how long that lag lasts. ptss_launched_kernels: PTSS_KERNEL_REPROJECT_MOTION. */
 int ptss_reproject_motion(ptss_context* ctx, const ptss_pixel_feature* dev_features_now, const ptss_pixel_motion* dev_motion_now,
                           const ptss_camera* prev_camera, const ptss_pixel_feature* dev_features_prev,
                           const ptss_history_entry* dev_history_prev, const ptss_reproject_params* params,
@@ -298,7 +296,7 @@ int ptss_set_scene(ptss_context* ctx, const ptss_scene_desc* scene);
  * Normals are copied as given, whatever their bits.
  * Refused without touching the device: a null context or a null pointer with count > 0 (PTSS_EINVAL); a range that leaves
  * [0, numTriangles) (PTSS_ERANGE); an edge-classed image (T <= 255: PTSS_EINVAL — its storage order depends on the edges; use
- * ptss_set_scene). count = 0 returns PTSS_OK. ptss_launched_kernels: bit 55 (the update), bit 56 (the refit, mesh images only). */
+ * ptss_set_scene). count = 0 returns PTSS_OK. ptss_launched_kernels: PTSS_KERNEL_UPDATE (the update), PTSS_KERNEL_REFIT (the refit, mesh images only). */
 int ptss_update_triangles(ptss_context* ctx, const ptss_triangle* dev_triangles, size_t first, size_t count, void* hipStream);
 /* Records ptss_update_triangles has refused since ptss_create (synchronises on the stream of the latest update). */
 int ptss_update_rejected(ptss_context* ctx, unsigned long long* out);

@@ -162,6 +162,38 @@ typedef struct ptss_pixel_motion {
 
 #define PTSS_SURFACE_TRIANGLE 0x40000000
 
+/* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
+ * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
+ * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
+ * and no frame kernel), the frame kernels their variant, the query kernel any*2 + inLds, the feature kernels inLds.
+ * cuda-path-tracer-ss_amd/ptss_types.py mirrors the table; a new kernel takes bits from the free ones (36-39, 61-63). */
+enum ptss_kernel_bit {
+    PTSS_KERNEL_BOUNCE = 0,            /* bounceKernel of the four variants that also have a frame kernel */
+    PTSS_KERNEL_FRAME = 32,            /* frameKernel: a whole frame in one launch */
+    PTSS_KERNEL_BOUNCE_MESH = 40,      /* bounceKernel of the mesh image */
+    PTSS_KERNEL_QUERY = 48,            /* queryKernel (ptss_intersect, ptss_occluded) */
+    PTSS_KERNEL_FEATURES = 52,         /* featureKernel (ptss_render_features) */
+    PTSS_KERNEL_DENOISE = 54,          /* denoiseKernel (ptss_denoise, ptss_denoise_history) */
+    PTSS_KERNEL_UPDATE = 55,           /* sceneUpdateKernel (ptss_update_triangles) */
+    PTSS_KERNEL_REFIT = 56,            /* meshRefitKernel (ptss_update_triangles on a mesh image) */
+    PTSS_KERNEL_REPROJECT = 57,        /* reprojectKernel (ptss_reproject) */
+    PTSS_KERNEL_FEATURES_MOTION = 58,  /* featureKernel with motion rows (ptss_render_features_motion) */
+    PTSS_KERNEL_REPROJECT_MOTION = 60  /* reprojectKernel reading motion rows (ptss_reproject_motion) */
+};
+enum ptss_kernel_width {
+    PTSS_KERNEL_WIDTH_BOUNCE = 32,
+    PTSS_KERNEL_WIDTH_FRAME = 4,
+    PTSS_KERNEL_WIDTH_BOUNCE_MESH = 8,
+    PTSS_KERNEL_WIDTH_QUERY = 4,
+    PTSS_KERNEL_WIDTH_FEATURES = 2,
+    PTSS_KERNEL_WIDTH_DENOISE = 1,
+    PTSS_KERNEL_WIDTH_UPDATE = 1,
+    PTSS_KERNEL_WIDTH_REFIT = 1,
+    PTSS_KERNEL_WIDTH_REPROJECT = 1,
+    PTSS_KERNEL_WIDTH_FEATURES_MOTION = 2,
+    PTSS_KERNEL_WIDTH_REPROJECT_MOTION = 1
+};
+
 #if defined(__cplusplus)
 static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
               "ptss_ray_query is two 16-byte rows");

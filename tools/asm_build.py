@@ -1,5 +1,5 @@
-"""tools/asm_build.py <tag> [--edit none|cnd64] [-DNAME=V ...] — builds lib/libptss_<tag>.so with the bounce kernels' gfx950
-assembly passed through a text edit between the compiler and the assembler (measurement builds: what would a different
+"""tools/asm_build.py <tag> [--edit none|cnd64] [-DNAME=V ...] — builds lib/libptss_<tag>.so with the gfx950 assembly of
+ptss_kernels.hip (the kernels, with the layer headers ptwave.h .. ptshade.h they are built from) passed through a text edit between the compiler and the assembler (measurement builds: what would a different
 instruction choice be worth?).  edit=cnd64: VOP2 `v_cndmask_b32_e32 d, a, b, vcc` -> VOP3 `v_cndmask_b32_e64 d, a, b, vcc`.
 Pipeline = hipcc's own (hipcc -###): device cc1 -> .s -> [edit] -> assembler -> lld -> clang-offload-bundler -> host cc1
 with -fcuda-include-gpubinary -> link with the ordinary object of ptss_api.hip."""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""tools/isa_compare.py before.s after.s — compares the kernels of two gfx950 assembly dumps of ptss_kernels.hip (hipcc with the
-shipped flags, --cuda-device-only -S; tools/isa_dump.sh has the command line) instruction by instruction, after normalising
-symbol, label and comment text and dropping directives. Prints the summary kept as profiles/*/isa_compare.txt."""
+"""tools/isa_compare.py before.s after.s — compares the kernels of two gfx950 assembly dumps of one csrc/*.hip file (ptss_kernels.hip:
+the kernels and launches, compiled as one translation unit over the layer headers ptwave.h .. ptshade.h; or one of the short kernel
+files), made by hipcc with the shipped flags and --cuda-device-only -S (tools/isa_dump.sh has the command line), instruction by
+instruction, after normalising symbol, label and comment text and dropping directives. Prints the summary kept as
+profiles/*/isa_compare.txt."""
 import re
 import sys
 

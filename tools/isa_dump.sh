@@ -1,6 +1,7 @@
 #!/bin/bash
 # tools/isa_dump.sh [<template-args, e.g. 010010> [out.s]] [extra -D flags] — gfx950 assembly of one bounceKernel instantiation
-# (digits = kLast kSceneInLds kFirst kAccel kBounded kPairs [kMesh]) with the shipped flags; prints VGPR/SGPR/scratch and instruction-class counts.
+# (digits = kLast kSceneInLds kFirst kAccel kBounded kPairs [kMesh]; ptss_kernels.hip compiles as one translation unit over its layer
+# headers ptwave.h .. ptshade.h) with the shipped flags; prints VGPR/SGPR/scratch and instruction-class counts.
 # Runs in this container (hipcc cross-compiles); used to read the hot loops, never by the product or the tests.
 args=${1:-010010}; out=${2:-/tmp/isa/k_$args.s}; shift; shift
 mkdir -p /tmp/isa
