@@ -18,6 +18,7 @@
 #include <algorithm>
 #include "ptdenoise.h"
 #include "ptreproject.h"
+#include "ptspecular.h"
 #include "ptpack.h"
 
 using namespace ptv;
@@ -132,6 +133,7 @@ struct ptss_context {
     hipEvent_t evEpoch = nullptr;
     unsigned int timeoutsSeen = 0;   // ptss_guard_timeouts value already reported as PTSS_ETIMEOUT
     unsigned long long launchedKernels = 0;   // bounce / frame kernel instantiations enqueued since ptss_create (ptss_launched_kernels)
+    unsigned long long specularFeatureLaunches[2] = {0, 0};   // ptss_render_features_specular launches: [0] in place, [1] in LDS
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -1076,6 +1078,31 @@ int ptss_render_features_motion(ptss_context* c, const ptss_triangle* dev_triang
     HIP_TRY(ptss::launchFeaturesMotion(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, c->numPixels,
                                        c->gridCap * ptss::kShards, dev_triangles_prev, count ? (uint32_t)first : 0u, (uint32_t)count, dev_motion,
                                        &c->launchedKernels));
+    return PTSS_OK;
+}
+
+// ptss_render_features_specular: ptss_render_features' image, camera and grid; the chain of csrc/ptspecular.h behind the first hit
+int ptss_render_features_specular(ptss_context* c, int maxSteps, ptss_pixel_feature* dev_features, uint32_t* dev_steps, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features) return fail(PTSS_EINVAL, "dev_features is null");
+    if (maxSteps < 0 || maxSteps > ptsp::kMaxSteps) return fail(PTSS_EINVAL, "maxSteps must be in [0, 8]");
+    if (((uintptr_t)dev_features & 15u) || ((uintptr_t)dev_steps & 3u))
+        return fail(PTSS_EINVAL, "dev_features must be 16-byte aligned, dev_steps 4-byte aligned");
+    if (c->numPixels == 0) return PTSS_OK;   // a rank whose tile is empty
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    HIP_TRY(ptss::launchFeaturesSpecular(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, dev_steps,
+                                         c->numPixels, maxSteps, c->gridCap * ptss::kShards, c->specularFeatureLaunches));
+    return PTSS_OK;
+}
+
+int ptss_specular_feature_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->specularFeatureLaunches[0];
+    out2[1] = c->specularFeatureLaunches[1];
     return PTSS_OK;
 }
 

@@ -173,6 +173,11 @@ hipError_t launchFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout l
 hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
                                 ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, const void* prevRecords, uint32_t first,
                                 uint32_t count, void* motionOut, unsigned long long* launched);
+// features behind mirrors and glass (ptss_render_features_specular; csrc/ptspecular.h): out as launchFeatures', steps = n uint32 or nullptr,
+// maxSteps 0 .. ptsp::kMaxSteps. No bit of ptss_launched_kernels: launches[0] (in place) or launches[1] (in LDS) is incremented
+hipError_t launchFeaturesSpecular(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                                  ptss_vec3 defaultColor, void* out, void* steps, uint32_t n, int maxSteps, int maxBlocks,
+                                  unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

@@ -29,6 +29,7 @@
 // counters (ptss_diag.h) are local to it.
 #include "ptss_device.h"
 #include "ptmotion.h"
+#include "ptspecular.h"
 #include "pthit.h"
 #include "ptshade.h"
 
@@ -914,6 +915,86 @@ __global__ __launch_bounds__(kBlock) void featureKernel(const float4* __restrict
     }
 }
 
+// ---- FEATURES BEHIND MIRRORS AND GLASS (ptss_render_features_specular) ---------------------------------------
+// featureKernel's launch shape and eye ray; then the centre ray is carried through the delta lobes of what it meets
+// (csrc/ptspecular.h: perfect reflection and refraction, chosen from the material alone) for at most maxSteps steps, one closestQuery
+// per link of the chain. The features are those of the LAST surface hit, depth the float32 sum of the chain's hit distances in
+// chain order (a path length); a chain that ends in a miss writes featureKernel's miss row. steps (may be null): the links
+// followed, 0 .. maxSteps. A lane whose chain has ended goes on as a dead lane of closestQuery; the loop ends for the whole wave,
+// by a ballot, once no lane is live. Per lane only the ray, the running depth and the last hit's normal and material index
+// live across a query: the material words are read from the staged image when the step needs them.
+template <bool kSceneInLds>
+__global__ __launch_bounds__(kBlock) void specularFeatureKernel(const float4* __restrict__ sceneBlob, SceneLayout L, TileMap tile, EyeParams eye,
+                                                                 vec3 defaultColor, float4* __restrict__ out, uint32_t* __restrict__ steps, uint32_t n,
+                                                                 int maxSteps) {
+    extern __shared__ __attribute__((aligned(256))) float4 lds[];
+    const float4* sc;
+    if constexpr (kSceneInLds) {
+        for (int k = threadIdx.x; k < L.ldsVec4; k += kBlock) lds[k] = sceneBlob[k];
+        __syncthreads();
+        sc = lds;
+    } else {
+        sc = sceneBlob;
+    }
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const bool inFrame = i < n;
+        vec3 o = eye.camera.position, d = v3(0, 0, 0);
+        if (inFrame) {
+            const PixelCoord pc = locate(tile, i);
+            const float jitteredX = pc.x + 0.5f;
+            const float jitteredY = pc.gy + 0.5f;
+            const vec3 start = v3(((jitteredX * eye.invW) - 0.5f) * eye.s,
+                                  1 * ((jitteredY * eye.invH) - 0.5f) * eye.s * eye.aspect, 1.0f) *
+                               eye.camera.zNear;
+            d = normalize(rotate(eye.camera.rotation, start));
+        }
+        bool live = inFrame;
+        vec3 normal = v3(0, 0, 0);
+        float depth = ptm::inf();
+        int materialIdx = -1;
+        bool hit = false;   // the chain ended on a surface
+        uint32_t taken = 0;
+        for (int k = 0; k <= maxSteps; ++k) {
+            if (!waveAny(live)) break;
+            const QueryHit q = closestQuery(sc, sceneBlob, L, o, d, ptm::inf(), live);
+            if (live) {
+                live = false;
+                hit = q.kind != 0;
+                if (!hit) {   // the chain leaves the scene: the miss row
+                    normal = v3(0, 0, 0);
+                    depth = ptm::inf();
+                    materialIdx = -1;
+                } else {
+                    normal = q.normal;
+                    depth = (k == 0) ? q.dist : depth + q.dist;
+                    materialIdx = q.materialIdx;
+                    if (k < maxSteps) {
+                        const float4* mat = sc + L.offMaterial + 5 * q.materialIdx;
+                        const float4 misc = loadRow16(mat + 4);   // specularExponent, indexOfRefraction, flags
+                        const ptsp::Material m{loadRow16(mat).w, loadRow16(mat + 1).w, loadRow16(mat + 2).w, misc.x, misc.y, (int)asU(misc.z)};
+                        const ptsp::Step s = ptsp::step(m, d, q.point, q.normal);
+                        if (s.follows) {
+                            o = s.o;
+                            d = s.d;
+                            ++taken;
+                            live = true;
+                        }
+                    }
+                }
+            }
+        }
+        if (inFrame) {
+            vec3 albedo = defaultColor;
+            if (hit) albedo = xyz(loadRow16(sc + L.offMaterial + 5 * materialIdx));
+            float4* f = out + 2 * (size_t)i;
+            f[0] = float4{normal.x, normal.y, normal.z, depth};
+            f[1] = float4{albedo.x, albedo.y, albedo.z, asF((uint32_t)materialIdx)};
+            if (steps) steps[i] = taken;
+        }
+    }
+}
+
 // =================================================================================================
 static inline unsigned blocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
 
@@ -1080,6 +1161,22 @@ hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLa
                                 uint32_t count, void* motionOut, unsigned long long* launched) {
     return launchFeatureKernel<true>(st, sceneBlob, layout, sceneInLds, tile, eye, defaultColor, out, n, maxBlocks,
                                      {static_cast<const float*>(prevRecords), first, count, static_cast<float4*>(motionOut)}, launched);
+}
+
+// the specular-chain feature kernel: featureKernel's grid. It owns no bit of *launched; launches[inLds] counts instead
+// (ptss_specular_feature_launches)
+hipError_t launchFeaturesSpecular(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
+                                  ptss_vec3 defaultColor, void* out, void* steps, uint32_t n, int maxSteps, int maxBlocks,
+                                  unsigned long long* launches) {
+    unsigned blocks = blocksFor(n, kBlock);
+    if (maxBlocks > 0 && blocks > (unsigned)maxBlocks) blocks = (unsigned)maxBlocks;
+    const size_t lds = sceneInLds ? (size_t)layout.ldsVec4 * sizeof(float4) : 0;
+    const auto kernel = sceneInLds ? specularFeatureKernel<true> : specularFeatureKernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, tile, eye, defaultColor, static_cast<float4*>(out),
+                       static_cast<uint32_t*>(steps), n, maxSteps);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) ++launches[sceneInLds ? 1 : 0];
+    return e;
 }
 
 hipError_t launchFlush(hipStream_t st, const FrameBuffers& fb, int numBounces, const FlushTargets& targets) {

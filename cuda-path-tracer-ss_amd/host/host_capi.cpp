@@ -11,6 +11,7 @@
 #include "ptdenoise.h"
 #include "ptreproject.h"
 #include "ptmotion.h"
+#include "ptspecular.h"
 #include "ptquant.h"
 #include "ptmesh.h"
 #include "ptpack.h"
@@ -356,6 +357,32 @@ int ptss_probe_motion(const ptss_ray_query* rays, const ptss_ray_hit* hits, size
         out[i] = ptss_pixel_motion{m.prevPoint, m.surface};
     }
     return PTSS_HOST_OK;
+}
+
+static ptsp::Material specularMaterial(const ptss_material& m) {
+    return ptsp::Material{m.diffAvg, m.specAvg, m.refrAvg, m.specularExponent, m.indexOfRefraction, (int)(unsigned char)m.flags};
+}
+
+int ptss_probe_specular_step(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_material* materials, size_t numMaterials,
+                             ptss_ray_query* next, int* follows) {
+    if (n > 0 && (!rays || !hits || !next || !follows)) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i)
+        if (hits[i].kind != PTSS_HIT_MISS && (!materials || hits[i].materialIdx < 0 || (size_t)hits[i].materialIdx >= numMaterials))
+            return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        const ptss_ray_hit& h = hits[i];
+        follows[i] = 0;
+        if (h.kind == PTSS_HIT_MISS) continue;
+        const ptsp::Step s = ptsp::step(specularMaterial(materials[h.materialIdx]), rays[i].direction, h.point, h.normal);
+        if (!s.follows) continue;
+        follows[i] = 1;
+        next[i] = ptss_ray_query{s.o, ptm::inf(), s.d, 0.0f};
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_specular_class(const ptss_material* material) {
+    return material ? (int)ptsp::classify(specularMaterial(*material)) : -1;
 }
 
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6) {

@@ -13,6 +13,9 @@
 //                                   jitter 0.5, 0.5, through ptss_intersect) of the final camera, one line per pick
 //             [--denoise [levels]]  with --out image.tga: also image_denoised.tga, the accumulated image through ptss_render_features
 //                                   and ptss_denoise (default parameters; levels 0..6 overrides their level count)
+//             [--specular-features N]  with --denoise: the filter is guided by the features BEHIND mirrors and glass, the centre ray
+//                                   carried through at most N (0..8) perfect reflections and refractions
+//                                   (ptss_render_features_specular); 0 writes the bytes of plain --denoise
 //             [--temporal]          with --out: the keys of --keys are delivered one at a time, --ticks frames are rendered at the start
 //                                   pose and after every key, and the image is carried from pose to pose (ptss_render_features,
 //                                   ptss_reproject with the history kept from the previous pose); --out receives the last history
@@ -36,6 +39,7 @@ int main(int argc, char* argv[]) {
     unsigned long long seed = 0x5EED;
     bool quiet = false;
     int denoise = -2;   // --denoise: -2 absent, -1 the default level count, else the level count
+    int specularSteps = -1;   // --specular-features: -1 absent (first-hit features), else maxSteps
     bool temporal = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -61,6 +65,7 @@ int main(int argc, char* argv[]) {
             denoise = -1;
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoise = atoi(next());
         }
+        else if (a == "--specular-features") specularSteps = atoi(next());
         else if (a == "--temporal") temporal = true;
         else if (a == "--pick") {
             int x, y;
@@ -100,6 +105,7 @@ int main(int argc, char* argv[]) {
     ptss_context* ctx = NULL;
     if (!picks.empty() && gpus > 0) { fprintf(stderr, "--pick needs one context (no --gpus)\n"); return 2; }
     if (denoise != -2 && (gpus > 0 || out.empty())) { fprintf(stderr, "--denoise needs --out and one context (no --gpus)\n"); return 2; }
+    if (specularSteps != -1 && (denoise == -2 || specularSteps < 0 || specularSteps > 8)) { fprintf(stderr, "--specular-features needs --denoise and a step count 0..8\n"); return 2; }
     if (temporal && (gpus > 0 || out.empty())) { fprintf(stderr, "--temporal needs --out and one context (no --gpus)\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
@@ -178,7 +184,11 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "--denoise: device buffers\n");
             return 1;
         }
-        PTSS_HANDLE(ptss_render_features(ctx, (ptss_pixel_feature*)df, NULL));
+        if (specularSteps >= 0) {
+            PTSS_HANDLE(ptss_render_features_specular(ctx, specularSteps, (ptss_pixel_feature*)df, NULL, NULL));
+        } else {
+            PTSS_HANDLE(ptss_render_features(ctx, (ptss_pixel_feature*)df, NULL));
+        }
         PTSS_HANDLE(ptss_denoise(ctx, (const ptss_pixel_feature*)df, &params, (ptss_uchar4*)dp, NULL));
         PTSS_HANDLE(ptss_synchronize(ctx));
         std::vector<ptss_uchar4> host(n);

@@ -162,6 +162,8 @@ def host_lib():
         L.ptss_probe_reproject_motion.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
         L.ptss_probe_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.ptss_probe_specular_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
+        L.ptss_probe_specular_class.argtypes = [C.c_void_p]
         _host = L
     return _host
 
@@ -236,6 +238,8 @@ def device_lib():
         L.ptss_denoise_history.argtypes = [vp, vp, vp, C.POINTER(DenoiseParams), vp, vp]
         L.ptss_render_features_motion.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp, vp]
         L.ptss_reproject_motion.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
+        L.ptss_render_features_specular.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.ptss_specular_feature_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
         L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
         L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -545,6 +549,44 @@ def probe_motion(rays, hits, prev_triangles=None, first=0, num_triangles=0):
     if rc != 0:
         raise PtssError(f"ptss_probe_motion: {rc}")
     return out
+
+
+SPECULAR_CLASSES = ("terminal", "transmit", "mirror")   # csrc/ptspecular.h Class 0, 1, 2
+
+
+def _material_table(materials):
+    """(pointer, count) of a materials table: a scene description (anything with .materials and .numMaterials) or a sequence of Material."""
+    if hasattr(materials, "numMaterials"):
+        return C.cast(materials.materials, C.c_void_p), int(materials.numMaterials), materials
+    arr = (Material * max(len(materials), 1))(*materials)
+    return C.cast(arr, C.c_void_p), len(materials), arr
+
+
+def specular_class(material):
+    """The class csrc/ptspecular.h gives a Material: "terminal", "transmit" or "mirror"."""
+    return SPECULAR_CLASSES[host_lib().ptss_probe_specular_class(C.byref(material))]
+
+
+def probe_specular_step(rays, hits, materials):
+    """One step of ptss_render_features_specular's chain on the host (csrc/ptspecular.h): rays (N, 8) float32 or (N,) RAY_DTYPE, hits
+    (N,) HIT_DTYPE (what intersect() returned for them), materials a scene description (scene.desc) or a sequence of Material.
+    Returns (next (N, 8) float32 — the continued rays, tmax +inf; the rows that do not continue are the input rows, untouched —,
+    follows (N,) bool)."""
+    r = np.ascontiguousarray(rays)
+    r = (r.view(np.float32) if r.dtype == RAY_DTYPE else r.astype(np.float32, copy=False)).reshape(-1, 8)
+    r = np.ascontiguousarray(r)
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+    if len(r) != len(h):
+        raise ValueError("one hit per ray")
+    ptr, count, keep = _material_table(materials)
+    nxt = r.copy()
+    follows = np.zeros(len(h), dtype=np.int32)
+    rc = host_lib().ptss_probe_specular_step(r.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), len(h), ptr, count,
+                                             nxt.ctypes.data_as(C.c_void_p), follows.ctypes.data_as(C.POINTER(C.c_int)))
+    del keep
+    if rc != 0:
+        raise PtssError(f"ptss_probe_specular_step: {rc}")
+    return nxt, follows != 0
 
 
 def make_rays(origins, directions, tmax=float("inf")):
@@ -956,6 +998,35 @@ class Renderer:
             _hip_check(_hip_lib().hipMemcpy(mot.ctypes.data, d_mot, mot.nbytes, 2), "hipMemcpy")
         self._have_features = True
         return feat, mot
+
+    def features_specular_devptr(self):
+        return self._device_buffer("features_specular", self.local_pixels * FEATURE_DTYPE.itemsize)
+
+    def features_specular(self, max_steps, steps=False, stream=None):
+        """ptss_render_features_specular: the features behind mirrors and glass — the centre ray carried through at most max_steps
+        (0..8) perfect reflections and refractions; depth is the chain's path length -> (local_pixels,) FEATURE_DTYPE, with
+        steps=True also the steps taken per pixel, (local_pixels,) uint32. The device buffer is a separate one
+        (features_specular_devptr): hand it, or the returned array, to denoise(features=...) / denoise_history(features=...);
+        reproject() keeps using the first-hit features of features()."""
+        d = self.features_specular_devptr()
+        d_steps = self._device_buffer("specular_steps", self.local_pixels * 4) if steps else None
+        _check(device_lib().ptss_render_features_specular(self._ctx, int(max_steps), d, d_steps, C.c_void_p(stream) if stream else None))
+        out = np.empty(self.local_pixels, dtype=FEATURE_DTYPE)
+        taken = np.zeros(self.local_pixels, dtype=np.uint32)
+        if self.local_pixels:
+            if stream:
+                _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            self.synchronize()
+            _hip_check(_hip_lib().hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+            if steps:
+                _hip_check(_hip_lib().hipMemcpy(taken.ctypes.data, d_steps, taken.nbytes, 2), "hipMemcpy")
+        return (out, taken) if steps else out
+
+    def specular_feature_launches(self):
+        """ptss_specular_feature_launches: (launches with the scene image read in place, launches with it staged in LDS)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_specular_feature_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
 
     def denoise(self, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None, stream=None):
         """ptss_denoise of the accumulated image -> (local_pixels, 4) uint8 RGBA. features: None (the buffer of the last

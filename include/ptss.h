@@ -202,6 +202,26 @@ int ptss_render_features(ptss_context* ctx, ptss_pixel_feature* dev_features, vo
 int ptss_render_features_motion(ptss_context* ctx, const ptss_triangle* dev_triangles_prev, size_t first, size_t count,
                                 ptss_pixel_feature* dev_features, ptss_pixel_motion* dev_motion, void* hipStream);
 
+/* Features BEHIND mirrors and glass. The centre ray of every local pixel is carried through the delta lobes of the
+ * surfaces it meets — perfect reflection, refraction; which one is decided from the material alone, csrc/ptspecular.h — for at most
+ * maxSteps (0 .. 8) steps, to the first surface that is neither a mirror nor glass. dev_features (the layout and order of
+ * ptss_render_features) receives normal, materialIdx and albedo of the LAST surface of that chain, and as depth the float32 sum of the
+ * chain's hit distances in chain order; a chain that leaves the scene writes the miss row (normal 0, depth +inf, materialIdx -1,
+ * defaultColor). dev_steps (may be NULL): one uint32 per local pixel, the steps taken, 0 .. maxSteps. Every link is what
+ * ptss_intersect returns for the ray ptss_probe_specular_step (ptss_host.h) continues with, bit for bit; maxSteps = 0 writes what
+ * ptss_render_features writes, bit for bit.
+ * The depth is a PATH LENGTH (a virtual depth), not the distance of a point on the centre ray: these features are for ptss_denoise and
+ * ptss_denoise_history only. ptss_reproject and ptss_reproject_motion rebuild a world point from the depth along the centre ray and
+ * still need the first-hit features of ptss_render_features.
+ * Asynchronous on hipStream (NULL: the context's stream). It reads the scene image only and leaves no trace in frame state; it serves
+ * pixel-band shards (tileWorld > 1) for their own pixels. Refused with PTSS_EINVAL without touching the device: a null context or
+ * dev_features, maxSteps outside 0..8, a dev_features that is not 16-byte aligned or a dev_steps that is not 4-byte aligned.
+ * The kernel owns no bit of ptss_launched_kernels, which this call leaves as it is; ptss_specular_feature_launches counts its launches
+ * since ptss_create instead: out2[0] with the scene image read in place, out2[1] with the image staged in LDS. */
+int ptss_render_features_specular(ptss_context* ctx, int maxSteps, ptss_pixel_feature* dev_features, uint32_t* dev_steps /* may be NULL */,
+                                  void* hipStream);
+int ptss_specular_feature_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] in place, [1] in LDS */
+
 /* levels 5, sigmaColor 64, sigmaNormal 0.1, sigmaDepth 4 (the values behind the figures of DESIGN.md §3.17). */
 int ptss_default_denoise_params(ptss_denoise_params* p);
 

@@ -114,6 +114,16 @@ int ptss_probe_reproject_motion(const uint32_t* accum, float inverseTicks, int n
  * triangles_prev with count > 0, or, with count > 0, a range that leaves [0, numTriangles). */
 int ptss_probe_motion(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_triangle* triangles_prev, size_t first,
                       size_t count, size_t numTriangles, ptss_pixel_motion* out);
+/* One step of ptss_render_features_specular's chain on the host (csrc/ptspecular.h — the very arithmetic the kernel evaluates), for
+ * n rays: direction of rays[i], and kind / point / normal / materialIdx of hits[i] (what ptss_intersect returned for that ray).
+ * follows[i] = 1 when the chain continues through the hit's material (a mirror, or glass that refracts or reflects totally), and
+ * next[i] is then the continued ray with tmax = +inf and pad = 0; follows[i] = 0 (a miss, a terminal material, total internal reflection
+ * without a specular lobe, a direction that is not finite) leaves next[i] untouched. PTSS_HOST_EINVAL: a null pointer with n > 0, or a
+ * hit whose materialIdx is outside [0, numMaterials) (nothing has then been written). */
+int ptss_probe_specular_step(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_material* materials, size_t numMaterials,
+                             ptss_ray_query* next, int* follows);
+/* The class csrc/ptspecular.h gives a material: 0 terminal, 1 transmit, 2 mirror; -1 for a null pointer. */
+int ptss_probe_specular_class(const ptss_material* material);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
 int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsigned int* out6);
 /* n raw draws and the matching (0,1] floats from a state; state advanced in place. */
