@@ -4,6 +4,7 @@
   libptss_host.so   g++                            host/*.cpp        host mirror (Scene, camera, TGA, probes)
   ptss_main         g++ (host only) + libptss      host/main.cpp     headless drop-in of the reference's main(); --gpus N: one
                     + librccl                                       context per GPU, one ncclGather (host/MultiGpu.cpp)
+  ptss_mathcheck, ptss_guardcheck   hipcc           tests/csrc/*.hip  device-side checks of the math fast paths (GPU tests run them)
 (The CPU oracle — test infrastructure — has its own recipe, oracle/build.py; nothing here refers to it.)
 
 Both sides of the parity contract are compiled with -ffp-contract=off and without fast-math
@@ -94,15 +95,25 @@ def build_mathcheck(force=False):
     return out
 
 
+def build_guardcheck(force=False):
+    """ptss_guardcheck: the helpers whose range guards are proven once, against the guarded forms and IEEE (tests/test_gpu_guards.py)."""
+    out = os.path.join(LIBDIR, "ptss_guardcheck")
+    src = os.path.join(ROOT, "tests", "csrc", "guards_device.hip")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if force or _newer(out, [src] + _headers()):
+        _run([hipcc] + [f for f in HIP_FLAGS if f != "-fPIC"] + ["-I", INC, "-I", CSRC, src, "-o", out])
+    return out
+
+
 def build_all(force=False):
-    return [build_host(force), build_device(force), build_main(force), build_mathcheck(force)]
+    return [build_host(force), build_device(force), build_main(force), build_mathcheck(force), build_guardcheck(force)]
 
 
 if __name__ == "__main__":
     force = "--force" in sys.argv
     what = [a for a in sys.argv[1:] if not a.startswith("-")]
     table = {"host": build_host, "device": build_device, "main": build_main,
-             "mathcheck": build_mathcheck}
+             "mathcheck": build_mathcheck, "guardcheck": build_guardcheck}
     if not what:
         build_all(force)
     for w in what:

@@ -116,6 +116,84 @@ PTM_HD float rcp_in_range(float x) {
 }
 PTM_HD uint32_t f2u(float x) { return __builtin_bit_cast(uint32_t, x); }
 PTM_HD float u2f(uint32_t x) { return __builtin_bit_cast(float, x); }
+
+// ---- range facts of the fast paths, for callers that prove a guard ONCE instead of paying it at every operation -------------------
+// (tests/test_guard_ranges.py runs every claim below as a check; tests/csrc/guards_device.hip compares each rewritten helper with
+// the guarded form and with the IEEE operation on the device.)
+constexpr float kSqrtLo = 2.5243549e-29f /* 2^-95 */, kSqrtHi = 7.9228163e28f /* 2^96 */;      // ptm::sqrt's fast range [lo, hi)
+constexpr float kRcpLo = 2.3509887e-38f /* 2^-125 */, kRcpHi = 8.5070592e37f /* 2^126 */;      // ptm::rcp's, of |x|
+constexpr float kDivLo = 8.6736174e-19f /* 2^-60 */, kDivHi = 1.1529215e18f /* 2^60 */;        // ptm::div's, of |a| and |b|
+// One window of distance2 = |lightPoint - point|^2 for a light sample (bounceTile, step 2). It has to cover
+//   sqrt(distance2)                       distance2 in [2^-95, 2^96)
+//   the divisor distance of w_i           sqrt is monotone and sqrt(2^+-120) = 2^+-60 exactly: distance2 in [2^-120, 2^120)
+//   the divisor 4 pi distance2 of L_i     RN(kFourPi * x) is monotone in x: x in [kLightD2Lo, kLightD2Hi), the smallest floats whose
+//                                         product reaches 2^-60 / 2^60
+// and the third interval lies inside the other two, so it IS the window.
+constexpr float kFourPi = 4 * kPi;                    // the constant addLambertTerm multiplies by (CudaTracer.cu:362)
+constexpr float kLightD2Lo = 0x1.45f306p-64f;         // RN(kFourPi * kLightD2Lo) = 2^-60, one ulp below gives less
+constexpr float kLightD2Hi = 0x1.45f306p+56f;         // RN(kFourPi * kLightD2Hi) = 2^60,  one ulp below gives less
+// Both ends in ONE compare: non-negative floats order as their bit patterns do, so kLightD2Lo <= x < kLightD2Hi is
+// bits(x) - bits(lo) < bits(hi) - bits(lo) in unsigned arithmetic (a smaller x wraps round to a huge difference; negative values, -0,
+// infinities and NaNs have patterns of at least 0x7f800000, whose difference 0x5fdd067d is outside the span as well).
+constexpr uint32_t kLightD2LoBits = 0x1fa2f983u, kLightD2Span = 0x3c000000u;   // bits(kLightD2Lo), bits(kLightD2Hi) - bits(kLightD2Lo)
+PTM_HD bool in_light_window(float distance2) { return f2u(distance2) - kLightD2LoBits < kLightD2Span; }
+// Wave-uniform on the device: `inRange` holds in every active lane. On the host: the value itself.
+PTM_HD bool every_lane(bool inRange) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return allLanes(lanes(inRange));
+#else
+    return inRange;
+#endif
+}
+PTM_HD bool every_lane(bool a, bool b) {   // (two direct compares, combined as masks: see lanes())
+#if defined(__HIP_DEVICE_COMPILE__)
+    return allLanes(lanes(a) & lanes(b));
+#else
+    return a && b;
+#endif
+}
+// A numerator the unguarded Markstein sequence may take over a divisor b in [2^-60, 2^60), b > 0: |a| in the division's range, or a = +0
+// — then q0 = +0 * r = +0, the remainder fma(-b, +0, +0) = -0 + +0 = +0 and q = fma(+0, r, +0) = +0, which is IEEE's +0 / b. A
+// numerator of -0 gives +0 from the same sequence (the remainder is +0 again, and +0 * r + -0 = +0) where IEEE gives -0: it stays on
+// the guarded path. The divisors of the callers are positive (distance and 4 pi distance2 inside the light-sample window). Scene
+// constants are classified with this once, at ptss_create / ptss_set_scene.
+PTM_HD bool fast_numerator(float a) {
+    const float aa = abs(a);
+    return f2u(a) == 0u || (aa >= kDivLo && aa < kDivHi);
+}
+PTM_HD bool fast_divisor(float b) { return abs(b) >= kDivLo && abs(b) < kDivHi; }   // (sign-symmetric for numerators in range)
+PTM_HD bool fast_rcp_operand(float x) { return abs(x) >= kRcpLo && abs(x) < kRcpHi; }
+// The fast path of sqrt alone, for a caller that has established 2^-95 <= x < 2^96. Same five instructions, same bits.
+PTM_HD float sqrt_in_range(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float y = __builtin_amdgcn_rsqf(x);
+    const float s = x * y;
+    const float h = 0.5f * y;
+    const float r = __builtin_fmaf(-s, s, x);
+    return __builtin_fmaf(r, h, s);
+#else
+    return __builtin_sqrtf(x);
+#endif
+}
+// s = sqrt(x) and inv = 1 / s under ONE guard (glm's normalize: v * (1 / sqrt(dot(v, v)))). x in sqrt's range [2^-95, 2^96) confines
+// s to [2^-47.5, 2^48], well inside rcp's range [2^-125, 2^126): both fast cores. Otherwise both IEEE operations — which is what the
+// two guarded functions return for such an x, in whichever range the IEEE root falls (rcp's fast path equals 1.0f / s wherever it is
+// taken). NaN fails `lo` and takes the IEEE pair, as before.
+PTM_HD void sqrt_rcp(float x, float& s, float& inv) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    s = sqrt_in_range(x);
+    inv = rcp_in_range(s);
+    const bool lo = x >= kSqrtLo, hi = x < kSqrtHi;
+    if (__builtin_expect(!allLanes(lanes(lo) & lanes(hi)), 0)) {
+        const float si = __builtin_sqrtf(x);
+        s = (lo && hi) ? s : si;
+        inv = (lo && hi) ? inv : 1.0f / si;
+    }
+#else
+    s = __builtin_sqrtf(x);
+    inv = 1.0f / s;
+#endif
+}
 PTM_HD float inf() { return u2f(0x7f800000u); }
 PTM_HD float qnan() { return u2f(0x7fc00000u); }
 
@@ -170,6 +248,26 @@ PTM_HD void div3(float ax, float ay, float az, float b, float& qx, float& qy, fl
     qx = ax / b;
     qy = ay / b;
     qz = az / b;
+#endif
+}
+// The same three quotients for a caller that has ALREADY established fast_divisor(b), b > 0, and fast_numerator of each numerator.
+PTM_HD void div3_in_range(float ax, float ay, float az, float b, float& qx, float& qy, float& qz) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = rcp_core(b);
+    qx = div_core(ax, b, r);
+    qy = div_core(ay, b, r);
+    qz = div_core(az, b, r);
+#else
+    qx = ax / b;
+    qy = ay / b;
+    qz = az / b;
+#endif
+}
+PTM_HD float div_in_range_operands(float a, float b) {   // one quotient, both operands established in [2^-60, 2^60)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return div_core(a, b, rcp_core(b));
+#else
+    return a / b;
 #endif
 }
 // glm::max(a,b) = (a < b) ? b : a ; glm::min(a,b) = (b < a) ? b : a  (ordered compares, NaN-stable)
@@ -336,15 +434,20 @@ PTM_HD vec3 cross(vec3 a, vec3 b) {
     return vec3{ptm::fma(a.y, b.z, -(a.z * b.y)), ptm::fma(a.z, b.x, -(a.x * b.z)), ptm::fma(a.x, b.y, -(a.y * b.x))};
 }
 // glm::normalize(v) = v * inversesqrt(dot(v,v))
-PTM_HD vec3 normalize(vec3 v) { return v * ptm::rcp(ptm::sqrt(dot(v, v))); }
+// (one range guard, on dot(v, v), decides the root and the reciprocal together: ptm::sqrt_rcp)
+PTM_HD vec3 normalize(vec3 v) {
+    float len, inv;
+    ptm::sqrt_rcp(dot(v, v), len, inv);
+    return v * inv;
+}
 PTM_HD float length(vec3 v) { return ptm::sqrt(dot(v, v)); }
 
 PTM_HD quat q4(float w, float x, float y, float z) { return quat{x, y, z, w}; }
 // glm::normalize(quat): identity when the length is not positive
 PTM_HD quat normalize(quat q) {
-    float len = ptm::sqrt(ptm::fma(q.w, q.w, ptm::fma(q.z, q.z, ptm::fma(q.y, q.y, q.x * q.x))));
+    float len, inv;   // one range guard for both, as in normalize(vec3); a length of 0 (or -0, or below sqrt's range) takes the IEEE pair
+    ptm::sqrt_rcp(ptm::fma(q.w, q.w, ptm::fma(q.z, q.z, ptm::fma(q.y, q.y, q.x * q.x))), len, inv);
     if (len <= 0.0f) return q4(1, 0, 0, 0);
-    float inv = ptm::rcp(len);
     return q4(q.w * inv, q.x * inv, q.y * inv, q.z * inv);
 }
 // glm quat * vec3:  v + 2w (u x v) + 2 (u x (u x v))

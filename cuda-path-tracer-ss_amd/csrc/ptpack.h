@@ -365,6 +365,23 @@ inline void setFlags(const ptss_scene_desc& s, SceneLayout& L) {
     L.triClassed = (L.triDetBounded && L.sphereBounded && L.numTriangles <= 255) ? 1 : 0;   // (the class bounds travel as bytes)
 }
 
+// The range guards this scene's constants satisfy (ptscene.h GuardFlag; the membership functions are ptmath.h's). Not part of the
+// image: the verdict travels in FrameBuffers::guardFlags.
+inline uint32_t sceneGuardFlags(const ptss_scene_desc& s) {
+    uint32_t flags = ptss::kGuardLightPowers | ptss::kGuardRefraction | ptss::kGuardPhongExponent;
+    auto fast3 = [](const ptss_vec3& v) { return ptm::fast_numerator(v.x) && ptm::fast_numerator(v.y) && ptm::fast_numerator(v.z); };
+    for (size_t i = 0; i < s.numPointLights; ++i)
+        if (!fast3(s.pointLights[i].power)) flags &= ~(uint32_t)ptss::kGuardLightPowers;
+    for (size_t i = 0; i < s.numAreaLights; ++i)
+        if (!fast3(s.areaLights[i].power)) flags &= ~(uint32_t)ptss::kGuardLightPowers;
+    for (size_t i = 0; i < s.numMaterials; ++i) {
+        const float n = s.materials[i].indexOfRefraction, e = s.materials[i].specularExponent;
+        if (!ptm::fast_divisor(n)) flags &= ~(uint32_t)ptss::kGuardRefraction;
+        if (!(e == ptm::inf() || ptm::fast_rcp_operand(e + 1))) flags &= ~(uint32_t)ptss::kGuardPhongExponent;
+    }
+    return flags;
+}
+
 // Storage order of the triangles: the caller's, or — SceneLayout::triClassed — grouped by edge class (pttri.h), the caller's
 // order kept inside a group, with the class begins as bytes in triClassPack; or — the mesh image — the kd order of the centroids.
 // Returns triOrder[position] = original index.

@@ -27,6 +27,15 @@ constexpr int kChunkSpheres = PTSS_CHUNK;
 static_assert((kChunkSpheres & (kChunkSpheres - 1)) == 0, "chunk size must be a power of two");   // spheres per chunk of the many-sphere traversal
 constexpr int kWaves = kBlock / 64;
 
+// ---- range guards proven once per scene (FrameBuffers::guardFlags; ptpack.h sceneGuardFlags decides at ptss_create / ptss_set_scene) ----
+// A set bit lets the kernels run the unguarded fast division / reciprocal on that scene constant; a clear bit leaves the guarded code.
+enum GuardFlag : uint32_t {
+    kGuardLightPowers = 1u,    // every component of every light power is +0.0 or has |p| in [2^-60, 2^60): numerators of L_i (addLambertTerm)
+    kGuardRefraction = 2u,     // every material's index of refraction has |n| in [2^-60, 2^60): n1 / n2 in scatter (the other operand is 1)
+    kGuardPhongExponent = 4u,  // every material's specularExponent is +inf (its Phong sampler never runs) or has |exponent + 1| in
+                               // [2^-125, 2^126): rcp(exponent + 1) in scatter
+};
+
 // ---- scene blob: one contiguous array of float4 staged into LDS by every workgroup --------------
 // (scene records are read by all lanes at the same index -> LDS broadcast reads)
 struct SceneLayout {

@@ -10,10 +10,41 @@
 namespace ptss {
 namespace {
 
-// one light's Lambert term, CudaTracer.cu:360-366 / :379-385
+// The geometry of one light sample, the head of lineOfSight (CudaTracer.cu:423-432): distance2 = |offset|^2, distance = sqrt(distance2),
+// w_i = offset / distance. When every active lane's distance2 lies in the light-sample window [kLightD2Lo, kLightD2Hi) of ptmath.h
+// and every offset component has a magnitude of at least 2^-60, the root and the three divisions of w_i run without their own range
+// guards (2 + 8 compares); addLambertTerm tests the same window again for the divisor 4 pi distance2 (one compare, instead of a verdict
+// held in scalar registers across the shadow passes):
+//   * the window's ends are derived in ptmath.h from the three operations' ranges;
+//   * the numerators need no upper test: distance2 = fma(z, z, fma(y, y, x * x)) is a sum of non-negative terms rounded three times,
+//     so distance2 >= c^2 (1 - 2^-24)^3 for each component c (c^2 cannot underflow when |c| >= 2^-60), and distance2 < kLightD2Hi
+//     < 2^57 gives |c| < 2^28.5 (1 + 2^-22) < 2^60;
+//   * their lower tests are one v_min3_f32 of the magnitudes and one compare (a NaN component makes distance2 NaN, which fails the
+//     window).
+// A wave that fails the test runs the guarded operations, exactly as before; inside the window both give the same bits.
+__device__ __forceinline__ void lightSample(vec3 offset, float& distance2, float& distance, vec3& w_i) {
+    distance2 = dot(offset, offset);
+    const float least = __builtin_fminf(__builtin_fminf(ptm::abs(offset.x), ptm::abs(offset.y)), ptm::abs(offset.z));
+    PTSS_DIAG_GUARD_LIGHT(offset, distance2, least);
+    if (__builtin_expect(ptm::every_lane(ptm::in_light_window(distance2), least >= ptm::kDivLo), 1)) {
+        distance = ptm::sqrt_in_range(distance2);
+        ptm::div3_in_range(offset.x, offset.y, offset.z, distance, w_i.x, w_i.y, w_i.z);
+    } else {
+        distance = ptm::sqrt(distance2);
+        w_i = offset / distance;
+    }
+}
+
+// one light's Lambert term, CudaTracer.cu:360-366 / :379-385. powersProven: the scene's kGuardLightPowers. With it and every active
+// lane's distance2 in the light-sample window, the divisor 4 pi distance2 is in [2^-60, 2^60) and positive, every power component is
+// +0 or in range (ptm::fast_numerator says why +0 may stay), and the three quotients need no guard.
 __device__ __forceinline__ void addLambertTerm(vec3& radiance, float cosI, vec3 power, float distance2,
-                                               float4 diffuse /* colour, diffAvg */) {
-    const vec3 L_i = power / (float)(4 * ptm::kPi * distance2);
+                                               float4 diffuse /* colour, diffAvg */, bool powersProven) {
+    const float divisor = (float)(ptm::kFourPi * distance2);
+    vec3 L_i;
+    PTSS_DIAG_GUARD_POWER(power, divisor);
+    if (powersProven && ptm::every_lane(ptm::in_light_window(distance2))) ptm::div3_in_range(power.x, power.y, power.z, divisor, L_i.x, L_i.y, L_i.z);
+    else L_i = power / divisor;
     radiance.x += cosI * L_i.x * diffuse.x * diffuse.w * ptm::kInvPi;
     radiance.y += cosI * L_i.y * diffuse.y * diffuse.w * ptm::kInvPi;
     radiance.z += cosI * L_i.z * diffuse.z * diffuse.w * ptm::kInvPi;
@@ -35,7 +66,8 @@ __device__ __forceinline__ quat rotateVectorToVector(vec3 source, vec3 target) {
 // elevation, Beckmann the first for the elevation and the second for the azimuth).
 enum LobeKind { kLobeNone = 0, kLobeLambert = 1, kLobePhong = 2, kLobeBeckmann = 3 };
 
-__device__ __forceinline__ vec3 scatter(const float4* mat, RayRegs& ray, vec3 point, vec3 normal, float cosI) {
+// guardFlags: FrameBuffers::guardFlags — the scene constants among the operands below whose range guard was settled at ptss_create.
+__device__ __forceinline__ vec3 scatter(const float4* mat, RayRegs& ray, vec3 point, vec3 normal, float cosI, uint32_t guardFlags) {
     const float4 mDiffuse = mat[0];   // diffuseColor, diffAvg
     const float4 mSpecular = mat[1];  // specularColor, specAvg
     const float4 mMisc = mat[4];      // specularExponent, indexOfRefraction, flags
@@ -82,7 +114,9 @@ __device__ __forceinline__ vec3 scatter(const float4* mat, RayRegs& ray, vec3 po
         float fresnelReflective = 1.0f;
         PTSS_DIAG_SCATTER(2, readsFresnel);  // Snell / Fresnel terms
         if (readsFresnel) {
-            n = ptm::div(n1, n2);    // computeSinT2AndRefractiveIndexes :491-493
+            PTSS_DIAG_GUARD_DIV(7, n1, n2);
+            // computeSinT2AndRefractiveIndexes :491-493. One operand is 1, the other the material's index: kGuardRefraction settles both
+            n = (guardFlags & kGuardRefraction) ? ptm::div_in_range_operands(n1, n2) : ptm::div(n1, n2);
             sinT2 = n * n * (1.0f - cosI * cosI);
         }
         if (readsFresnel && !(sinT2 > 1.0f)) {   // computeFresnelForReflectance :457-472
@@ -149,7 +183,10 @@ __device__ __forceinline__ vec3 scatter(const float4* mat, RayRegs& ray, vec3 po
             ptm::sincos(theta, a, y);  // m = (sinTheta * cosPhi, cosTheta, sinTheta * sinPhi), :567-569
         } else {
             azimuth = u1 * 2 * ptm::kPi;                                                      // :536, :550
-            y = (kind == kLobeLambert) ? ptm::sqrt(u2) : ptm::pow(u2, ptm::rcp(mMisc.x + 1));  // :537-538, :551-552
+            // :537-538, :551-552. u2 = k 2^-32 + 2^-33 rounded lies in [2^-33, 1], inside sqrt's fast range [2^-95, 2^96): no guard.
+            // exponent + 1 of a lane that samples the Phong lobe (exponent != inf, above) is in rcp's range under kGuardPhongExponent.
+            if (kind == kLobeLambert) y = ptm::sqrt_in_range(u2);
+            else y = ptm::pow(u2, (guardFlags & kGuardPhongExponent) ? ptm::rcp_in_range(mMisc.x + 1) : ptm::rcp(mMisc.x + 1));
             a = ptm::sqrt(1 - y * y);                                                          // :539, :553
         }
         float sn, cs;

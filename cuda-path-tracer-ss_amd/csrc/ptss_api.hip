@@ -84,6 +84,7 @@ struct SceneImage {
     ptss::SceneLayout layout{};
     bool inLds = true;       // staged in LDS (true) or read through scalar loads (false)
     bool oneLaunch = false;  // the frame is traced by ONE launch (frameKernel)
+    uint32_t guardFlags = 0; // range guards the scene's constants satisfy (ptpack.h sceneGuardFlags); the same for both images of a scene
 };
 
 struct ptss_context {
@@ -197,6 +198,7 @@ int buildSceneState(const ptss_scene_desc& scene, const ptss_render_config& cfg,
         SceneImage& im = st.images[i];
         im.layout = packed[(size_t)i].layout;
         im.inLds = packed[(size_t)i].inLds;
+        im.guardFlags = ptpack::sceneGuardFlags(scene);
         const std::vector<ptpack::Row>& blob = packed[(size_t)i].blob;
         hipError_t e = hipMalloc(&im.dBlob, blob.size() * sizeof(float4));
         if (e == hipSuccess) e = hipMemcpy(im.dBlob, blob.data(), blob.size() * sizeof(float4), hipMemcpyHostToDevice);
@@ -335,6 +337,7 @@ ptss::FrameBuffers frameBuffers(const ptss_context* c, int laneIdx, ptss_uchar4*
     fb.defaultColor[0] = c->defaultColor[0];
     fb.defaultColor[1] = c->defaultColor[1];
     fb.defaultColor[2] = c->defaultColor[2];
+    fb.guardFlags = c->image().guardFlags;
     fb.laneIndex = (uint32_t)laneIdx;
     fb.laneCount = (uint32_t)c->lanes.size();
     fb.frameRays = c->numPixels * c->samples;
@@ -1012,6 +1015,12 @@ int ptss_frame_lanes(const ptss_context* c, int* out) {
 int ptss_launched_kernels(const ptss_context* c, unsigned long long* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     *out = c->launchedKernels;
+    return PTSS_OK;
+}
+
+int ptss_guard_flags(const ptss_context* c, unsigned int* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->image().guardFlags;
     return PTSS_OK;
 }
 

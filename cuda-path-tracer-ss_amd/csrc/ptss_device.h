@@ -121,6 +121,7 @@ struct FrameBuffers {
                              // 0 in a sharded context (the guard is a whole-frame quantity; DESIGN.md "Sharding")
     float inverseTicks;      // 1.f / (ticks - lastResetTick + 1)
     float defaultColor[3];
+    uint32_t guardFlags;     // GuardFlag bits (ptscene.h) of the scene the frame renders: which range guards hold for its constants
     // frame lanes (laneCount = 1: everything below is inert)
     uint32_t laneIndex, laneCount;
     uint32_t frameRays;              // rays all lanes together start a pass with (numPixels x samples): bounce 0's guard

@@ -1,5 +1,5 @@
 // ptss_diag.h — diagnostic counters of the bounce kernel. They exist only in -DPTSS_DIAG=<bits> builds
-// (tools/build_variants.py: chist, shist, cullstat, pairstat, qhist); with PTSS_DIAG == 0 every hook below is an empty
+// (tools/build_variants.py: chist, shist, cullstat, pairstat, qhist; bit 5 ad hoc: gstat=PTSS_DIAG=32); with PTSS_DIAG == 0 every hook below is an empty
 // statement and the shipped kernel carries no counter. Included by ptaccel.h inside its anonymous namespace, after the
 // chunk-bound helpers it uses, so the counters are local to the one translation unit (ptss_kernels.hip) that includes the
 // layers. The host reads the eight words with ptss_debug_counters().
@@ -106,4 +106,40 @@ __device__ __forceinline__ void diagCull(const float4* sc, const SceneLayout& L,
     } while (0)
 #else
 #define PTSS_DIAG_QUEUE(queued) do {} while (0)
+#endif
+
+// bit 5 — range guards of the shading code (tools/guard_stat.py): per guarded site, the waves that reach it and the waves in which
+// the per-operation guards (sqrt's, div3's: the tests every operation made before the light-sample window) send at least one lane
+// to the IEEE sequence. Words: 0 light samples, 1 ... whose sqrt(distance2) escapes, 2 ... whose offset / distance escapes,
+// 3 ... that fail the one window of lightSample; 4 Lambert terms, 5 ... whose power / (4 pi distance2) escapes, 6 ... because of a
+// numerator alone (the divisor is in range); 7 n1 / n2 of scatter that escapes.
+#if PTSS_DIAG & 32
+__device__ __forceinline__ void diagGuard(int site, unsigned long long inRange) {
+    const unsigned long long active = __ballot(true);
+    if ((inRange & active) != active && __lane_id() == (unsigned)(__ffsll((long long)active) - 1)) atomicAdd(&g_diag[site], 1ull);
+}
+__device__ __forceinline__ void diagGuardCount(int site) {
+    if (__lane_id() == (unsigned)(__ffsll((long long)__ballot(true)) - 1)) atomicAdd(&g_diag[site], 1ull);
+}
+__device__ __forceinline__ unsigned long long diagDivLanes(float x) { return __ballot(ptm::abs(x) >= ptm::kDivLo && ptm::abs(x) < ptm::kDivHi); }
+#define PTSS_DIAG_GUARD_LIGHT(offset, d2, least)                                                                                   \
+    do {                                                                                                                           \
+        diagGuardCount(0);                                                                                                         \
+        diagGuard(1, __ballot((d2) >= ptm::kSqrtLo && (d2) < ptm::kSqrtHi));                                                       \
+        diagGuard(2, diagDivLanes(__builtin_sqrtf(d2)) & diagDivLanes((offset).x) & diagDivLanes((offset).y) & diagDivLanes((offset).z)); \
+        diagGuard(3, __ballot((d2) >= ptm::kLightD2Lo && (d2) < ptm::kLightD2Hi && (least) >= ptm::kDivLo));                       \
+    } while (0)
+#define PTSS_DIAG_GUARD_POWER(power, divisor)                                                                                      \
+    do {                                                                                                                           \
+        diagGuardCount(4);                                                                                                         \
+        const unsigned long long _den = diagDivLanes(divisor);                                                                     \
+        const unsigned long long _num = diagDivLanes((power).x) & diagDivLanes((power).y) & diagDivLanes((power).z);               \
+        diagGuard(5, _den & _num);                                                                                                 \
+        diagGuard(6, _num | ~_den);                                                                                                \
+    } while (0)
+#define PTSS_DIAG_GUARD_DIV(site, a, b) diagGuard(site, diagDivLanes(a) & diagDivLanes(b))
+#else
+#define PTSS_DIAG_GUARD_LIGHT(offset, d2, least) do {} while (0)
+#define PTSS_DIAG_GUARD_POWER(power, divisor) do {} while (0)
+#define PTSS_DIAG_GUARD_DIV(site, a, b) do {} while (0)
 #endif

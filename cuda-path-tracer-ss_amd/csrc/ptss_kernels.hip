@@ -278,7 +278,9 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                         const float u1 = ptrng::uniform(ray.rng);
                         const float u2 = ptrng::uniform(ray.rng);
                         const float u3 = ptrng::uniform(ray.rng);
-                        const float inverseTotal = ptm::rcp(u1 + u2 + u3);  // 1 / (u1+u2+u3), :403
+                        // 1 / (u1+u2+u3), :403. Each uniform is k 2^-32 + 2^-33 rounded, in [2^-33, 1]: the sum lies in [2^-32, 3],
+                        // inside the reciprocal's fast range [2^-125, 2^126) — no guard
+                        const float inverseTotal = ptm::rcp_in_range(u1 + u2 + u3);
                         const float weight0 = u1 * inverseTotal, weight1 = u2 * inverseTotal, weight2 = u3 * inverseTotal;
                         // triangleIdx or triangleIdx + 1, :408 — as stored positions (the triangles may be stored grouped by class)
                         const int tri = (ptrng::uniform(ray.rng) > .5f) ? (int)asU(light.w) : (int)asU(sc[L.offAreaLight + 2 * (li - L.numPointLights) + 1].x);
@@ -289,9 +291,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                     }
                     // head of lineOfSight :423-432
                     const vec3 offset = lightPoint - point;
-                    distance2[k] = dot(offset, offset);
-                    distance = ptm::sqrt(distance2[k]);
-                    w_i = offset / distance;
+                    lightSample(offset, distance2[k], distance, w_i);
                     cosL[k] = ptm::max(0.0f, dot(normal, w_i));
                     const bool zeroTerm = L.neeSkipSafe && (distance2[k] > 0.0f) && (distance2[k] < ptm::inf()) &&
                                           (cosL[k] == 0.0f || mat[0].w == 0.0f);
@@ -420,7 +420,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                 if (need[k] && wqAnswer[k * 64 + lane] == 0) {
                     const vec3 power = (li < L.numPointLights) ? xyz(loadRow16(sc + L.offPointLight + 2 * li + 1))
                                                                : xyz(loadRow16(sc + L.offAreaLight + 2 * (li - L.numPointLights)));
-                    addLambertTerm(radiance, cosL[k], power, distance2[k], mat[0]);
+                    addLambertTerm(radiance, cosL[k], power, distance2[k], mat[0], (fb.guardFlags & kGuardLightPowers) != 0u);
                 }
             }
             waveLdsFence();
@@ -437,7 +437,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
                 vec3 directRadiance = v3(0, 0, 0) + xyz(mat[3]);
                 if (lit) directRadiance = directRadiance + radiance;
                 vec3 indirectRadiance = v3(1, 1, 1);
-                if (!kLast && !(PTSS_ABLATE & 4)) indirectRadiance = scatter(mat, ray, point, normal, cosI);
+                if (!kLast && !(PTSS_ABLATE & 4)) indirectRadiance = scatter(mat, ray, point, normal, cosI, fb.guardFlags);
                 if (inside) {  // Beer-Lambert, :179-185
                     const float4 ab = mat[2];
                     ray.T = ray.T * v3(ptm::exp(-h.distance * ab.x), ptm::exp(-h.distance * ab.y),

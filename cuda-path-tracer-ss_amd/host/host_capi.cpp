@@ -121,6 +121,33 @@ int ptss_tile_rows(int height, int band_rows, int rank, int world, int* rows, in
     return n;
 }
 
+int ptss_probe_guard(int op, const float* x, unsigned int* out, size_t n) {
+    if (!x || !out || op < 0 || op > 3) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        switch (op) {
+            case 0: out[i] = ptm::fast_numerator(x[i]) ? 1u : 0u; break;
+            case 1: out[i] = ptm::fast_divisor(x[i]) ? 1u : 0u; break;
+            case 2: out[i] = ptm::fast_rcp_operand(x[i]) ? 1u : 0u; break;
+            default: out[i] = ptm::in_light_window(x[i]) ? 1u : 0u; break;
+        }
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_guard_constants(float* out9) {
+    if (!out9) return PTSS_HOST_EINVAL;
+    const float k[9] = {ptm::kSqrtLo, ptm::kSqrtHi, ptm::kRcpLo, ptm::kRcpHi, ptm::kDivLo, ptm::kDivHi, ptm::kLightD2Lo, ptm::kLightD2Hi,
+                        ptm::kFourPi};
+    for (int i = 0; i < 9; ++i) out9[i] = k[i];
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_scene_guard_flags(const ptss_scene_desc* scene, unsigned int* out) {
+    if (!scene || !out) return PTSS_HOST_EINVAL;
+    *out = ptpack::sceneGuardFlags(*scene);
+    return PTSS_HOST_OK;
+}
+
 int ptss_probe_math(int op, const float* x, const float* y, float* out, size_t n) {
     if (!x || !out) return PTSS_HOST_EINVAL;
     for (size_t i = 0; i < n; ++i) {

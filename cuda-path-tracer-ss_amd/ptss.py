@@ -143,6 +143,9 @@ def host_lib():
         L.ptss_tile_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.ptss_probe_math.argtypes = [C.c_int, _f32p, _f32p, _f32p, C.c_size_t]
         L.ptss_probe_quantize.argtypes = [_f32p, C.POINTER(C.c_uint), C.c_size_t]
+        L.ptss_probe_guard.argtypes = [C.c_int, _f32p, C.POINTER(C.c_uint), C.c_size_t]
+        L.ptss_probe_guard_constants.argtypes = [_f32p]
+        L.ptss_probe_scene_guard_flags.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint)]
         L.ptss_probe_triangle_forms.argtypes = [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_size_t, C.POINTER(C.c_int), _f32p, _f32p]
         L.ptss_probe_quant_table.argtypes = [_f32p]
         L.ptss_probe_rng_init.argtypes = [C.c_ulonglong, C.c_uint, _u32p]
@@ -225,6 +228,7 @@ def device_lib():
         L.ptss_guard_timeouts.argtypes = [vp, C.POINTER(C.c_uint)]
         L.ptss_bounce_kernel_time.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
         L.ptss_launched_kernels.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_guard_flags.argtypes = [vp, C.POINTER(C.c_uint)]
         L.ptss_debug_counters.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_triangle_leaves.argtypes = [vp, C.POINTER(C.c_int)]
         L.ptss_intersect.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -812,6 +816,13 @@ class Renderer:
         v = C.c_ulonglong()
         _check(device_lib().ptss_launched_kernels(self._ctx, C.byref(v)))
         return decode_launched_kernels(v.value)
+
+    def guard_flags(self):
+        """ptss_guard_flags: the range guards the current scene's constants satisfy (bit 0 light powers, 1 refraction indices,
+        2 Phong exponents), decided at creation and at every set_scene."""
+        v = C.c_uint()
+        _check(device_lib().ptss_guard_flags(self._ctx, C.byref(v)))
+        return v.value
 
     # --- scene updates (ptss_set_scene / ptss_update_triangles / ptss_reseed) -------------------------------------
     def set_scene(self, scene):

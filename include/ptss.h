@@ -161,6 +161,12 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
+/* Which range guards of the shading code the current scene's constants satisfy, decided once at ptss_create / ptss_set_scene
+ * (DESIGN.md §3.8): bit 0 every light-power component is +0.0 or has a magnitude in [2^-60, 2^60), bit 1 every index of refraction has,
+ * bit 2 every specularExponent is +inf or has |exponent + 1| in [2^-125, 2^126). A set bit lets the kernels divide by / into that
+ * constant without testing its range again; a clear bit leaves the guarded code. The images are the same either way. */
+int ptss_guard_flags(const ptss_context* ctx, unsigned int* out);
+
 /* Batched ray queries against the context's scene. dev_rays / dev_hits / dev_occluded are DEVICE pointers of n
  * entries on the context's device. ptss_intersect: what the reference's intersectScene loop (CudaTracer.cu:120-141) returns for
  * ray (origin, direction) with `distance` starting at tmax — spheres 0..S-1, then triangles 0..T-1 — bit for bit, for every input

@@ -54,6 +54,14 @@ int ptss_tile_rows(int height, int band_rows, int rank, int world, int* rows, in
 
 /* Probes (tests only). op: 0 sin, 1 cos, 2 tan, 3 atan, 4 log, 5 exp, 6 pow(x,y), 7 sqrt */
 int ptss_probe_math(int op, const float* x, const float* y, float* out, size_t n);
+/* The range facts behind the guard-free fast paths of the shading code (csrc/ptmath.h; tests/test_guard_ranges.py).
+ * ptss_probe_guard: out[i] = 1 or 0 for x[i] under op 0 fast_numerator, 1 fast_divisor, 2 fast_rcp_operand, 3 in_light_window (the
+ * one-compare integer form of kLightD2Lo <= x < kLightD2Hi). ptss_probe_guard_constants: out9 = kSqrtLo, kSqrtHi, kRcpLo, kRcpHi,
+ * kDivLo, kDivHi, kLightD2Lo, kLightD2Hi, kFourPi. ptss_probe_scene_guard_flags: what ptss_create decides for a scene
+ * (csrc/ptpack.h sceneGuardFlags; the bits of ptss_guard_flags). */
+int ptss_probe_guard(int op, const float* x, unsigned int* out, size_t n);
+int ptss_probe_guard_constants(float* out9);
+int ptss_probe_scene_guard_flags(const ptss_scene_desc* scene, unsigned int* out);
 /* 8-bit tone-mapped sample of a radiance value, literal (CudaTracer.cu:72-85), and the 257 thresholds T[0..256] of its
  * table form (csrc/ptquant.h): T[k] = smallest float whose sample is >= k (T[0] = -inf, T[256] = NaN). Returns PTSS_HOST_EINVAL if not monotone. */
 int ptss_probe_quantize(const float* x, unsigned int* out, size_t n);
