@@ -90,7 +90,6 @@ __device__ __forceinline__ uint32_t chunkMask(const float4* bounds, int cnt, vec
 // LDS and the sphere rows start on a 256-byte boundary (they do: ptpack.h puts them first, the dynamic LDS is aligned), a
 // row's address is (chunk's address ^ (chunk mod 16) << 4) ^ (i << 4): ONE v_xor with a constant per row instead of add, and,
 // shift-add (round 3; -2 of 16 instructions per sphere).
-typedef __attribute__((address_space(3))) const float4 LdsRow;
 __device__ __forceinline__ uint32_t chunkCandidates(const float4* spheres /* sc + L.offSphere */, int base, int chunk, vec3 o, vec3 d) {
     static_assert(kChunkSpheres * sizeof(float4) <= 256, "a chunk's rows must not straddle the 256-byte window the XOR walks");
     uint32_t rev = 0;

@@ -24,7 +24,7 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
     if constexpr (kAccel) closestSpheresRegrouped<kPrimary>(sc, cold, L, o, d, live, h, ws);
     for (int base = 0; base < (kAccel ? 0 : L.numSpheres); base += 32) {
         const int cnt = (L.numSpheres - base < 32) ? (L.numSpheres - base) : 32;
-        uint32_t mask = sphereCandidates<kPrimary, kBounded>(sc + (kPrimary ? L.offPrimSphere : L.offSphere) + base, cnt, o, d);
+        uint32_t mask = sphereCandidates<kPrimary, kBounded>(sc, (kPrimary ? L.offPrimSphere : L.offSphere) + base, cnt, o, d);
         mask &= live ? lowBits(cnt) : 0u;
         PTSS_DIAG_CANDIDATES(mask, live, 0);
         while (mask != 0) {
@@ -63,9 +63,12 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
         // CALLER's order with the guarded general test below: the reference's sequential rule, NaNs included.
         if (classedQueryOk(o, d)) {
             TriBest best{h.distance, kNoTriangle, 0.0f, 0.0f};
+            // one vector byte address for the triangle rows (the head and the weights block of a body read through the same
+            // register) and, at bounce 0, one for the camera-origin rows: ptwave.h vectorRow
+            uint32_t triAt = vectorRow(sc, L.offTri), primAt = vectorRow(sc, L.offPrimTri);
 #define PTSS_CLOSEST_BODY(c1, c2, t) \
-    triangleClassed<kPrimary, c1, c2, true>(sc + L.offTri + 3 * t, sc + L.offPrimTri + 2 * t, 0u, o, d, liveMask, best);
-            PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_CLOSEST_BODY);
+    triangleClassed<kPrimary, c1, c2, true>(rowAt(sc, triAt), rowAt(sc, primAt), 0u, o, d, liveMask, best);
+            PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_CLOSEST_BODY, (triAt += 3 * kRowBytes, primAt += 2 * kRowBytes));
 #undef PTSS_CLOSEST_BODY
             if (waveAny(best.key != kNoTriangle)) {
                 const int* posOf = reinterpret_cast<const int*>(sc + L.offTriPos);
@@ -98,8 +101,9 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
     } else if (L.triDetBounded && waveAll(dot(d, d) < 0x1p30f)) {
         // the caller's order, the general body, the sequential rule; the reciprocal's range guard proven once per query
         TriBest best{h.distance, kNoTriangle, 0.0f, 0.0f};
-        for (int i = 0; i < L.numTriangles; ++i)
-            triangleClassed<kPrimary, 0, 0, false>(sc + L.offTri + 3 * i, sc + L.offPrimTri + 2 * i, (uint32_t)i, o, d, liveMask, best);
+        uint32_t triAt = vectorRow(sc, L.offTri), primAt = vectorRow(sc, L.offPrimTri);   // as above
+        for (int i = 0; i < L.numTriangles; ++i, triAt += 3 * kRowBytes, primAt += 2 * kRowBytes)
+            triangleClassed<kPrimary, 0, 0, false>(rowAt(sc, triAt), rowAt(sc, primAt), (uint32_t)i, o, d, liveMask, best);
         if (best.key != kNoTriangle) {
             h.distance = best.dist;
             h.kind = 2;
@@ -136,10 +140,11 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
 __device__ __forceinline__ void anyTriangleLoop(const float4* sc, const SceneLayout& L, vec3 lo, vec3 w_i, float distance, unsigned long long& need,
                                                 unsigned long long& blocked) {
     if (L.triClassed && classedQueryOk(lo, w_i)) {
+        uint32_t triAt = vectorRow(sc, L.offTri);   // one vector byte address through all the class loops (ptwave.h)
 #define PTSS_ANY_BODY(c1, c2, t)   \
     if (need == 0ull) break;      \
-    triangleClassedAny<c1, c2>(sc + L.offTri + 3 * t, lo, w_i, distance, need, blocked);
-        PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_ANY_BODY);
+    triangleClassedAny<c1, c2>(rowAt(sc, triAt), lo, w_i, distance, need, blocked);
+        PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_ANY_BODY, triAt += 3 * kRowBytes);
 #undef PTSS_ANY_BODY
         return;
     }
@@ -169,7 +174,7 @@ __device__ __forceinline__ bool anyHit(const float4* sc, const SceneLayout& L, v
     if constexpr (kAccel) occluded = anySphereChunked(sc, L, lo, w_i, distance, live);
     for (int base = 0; base < (kAccel ? 0 : L.numSpheres); base += 32) {
         const int cnt = (L.numSpheres - base < 32) ? (L.numSpheres - base) : 32;
-        uint32_t mask = sphereCandidatesPairs<kBounded>(sc + L.offSphere + base, cnt, lo, w_i);
+        uint32_t mask = sphereCandidatesPairs<kBounded>(sc, L.offSphere + base, cnt, lo, w_i);
         mask &= (live && !occluded) ? lowBits(cnt) : 0u;
         PTSS_DIAG_CANDIDATES(mask, live, 4);
         while (mask != 0) {
@@ -292,10 +297,11 @@ __device__ __forceinline__ void pairAnyHit(const float4* sc, const SceneLayout& 
     const int triSteps = kSplit ? ((L.numTriangles + g - 1) >> shift) : L.numTriangles;
     if constexpr (!kSplit) {   // every lane at the same triangle: one loop per edge class (grouped storage), origin part shared
         if (L.triClassed && classedQueryOk(lo, wA) && waveAll(dot(wB, wB) < 0x1p30f)) {
+            uint32_t triAt = vectorRow(sc, L.offTri);   // one vector byte address through all the class loops (ptwave.h)
 #define PTSS_PAIR_BODY(c1, c2, t)            \
     if ((needA | needB) == 0ull) break;     \
-    triangleClassedPair<c1, c2>(sc + L.offTri + 3 * t, lo, wA, dA, wB, dB, needA, needB, blockedA, blockedB);
-            PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_PAIR_BODY);
+    triangleClassedPair<c1, c2>(rowAt(sc, triAt), lo, wA, dA, wB, dB, needA, needB, blockedA, blockedB);
+            PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_PAIR_BODY, triAt += 3 * kRowBytes);
 #undef PTSS_PAIR_BODY
             occA = occA || __builtin_amdgcn_inverse_ballot_w64(blockedA);
             occB = occB || __builtin_amdgcn_inverse_ballot_w64(blockedB);

@@ -176,16 +176,21 @@ __device__ __forceinline__ int classBegin(ClassBounds& b) {
     asm volatile("" : "+s"(b.w[kCode / 4]));
     return (int)((b.w[kCode / 4] >> (8 * (kCode % 4))) & 255u);
 }
-#define PTSS_FOR_TRIANGLES_BY_CLASS(L, BODY)                                                                        \
+// The thirteen loops visit the stored positions 0 .. T - 1 in order, each once (begin(0) = 0, begin(16) = T, the codes 5, 10 and 15
+// are empty: pttri.h triangleClass), so ONE running row address serves them all: STEP is evaluated after each triangle and advances
+// the caller's vector byte addresses (ptwave.h vectorRow) by one triangle; the loop bounds stay scalar. A BODY that leaves a loop
+// with `break` leaves the addresses behind — only the any-hit bodies do, on a condition (nothing left to answer) that stays true and
+// makes every later loop leave before it reads a row.
+#define PTSS_FOR_TRIANGLES_BY_CLASS(L, BODY, STEP)                                                                  \
     do {                                                                                                            \
         ClassBounds _cb = classBounds(L);                                                                           \
-        PTSS_TRI_CLASS_LOOP(_cb, 0, 0, BODY) PTSS_TRI_CLASS_LOOP(_cb, 0, 1, BODY) PTSS_TRI_CLASS_LOOP(_cb, 0, 2, BODY) PTSS_TRI_CLASS_LOOP(_cb, 0, 3, BODY) \
-        PTSS_TRI_CLASS_LOOP(_cb, 1, 0, BODY) PTSS_TRI_CLASS_LOOP(_cb, 1, 2, BODY) PTSS_TRI_CLASS_LOOP(_cb, 1, 3, BODY)      \
-        PTSS_TRI_CLASS_LOOP(_cb, 2, 0, BODY) PTSS_TRI_CLASS_LOOP(_cb, 2, 1, BODY) PTSS_TRI_CLASS_LOOP(_cb, 2, 3, BODY)      \
-        PTSS_TRI_CLASS_LOOP(_cb, 3, 0, BODY) PTSS_TRI_CLASS_LOOP(_cb, 3, 1, BODY) PTSS_TRI_CLASS_LOOP(_cb, 3, 2, BODY)      \
+        PTSS_TRI_CLASS_LOOP(_cb, 0, 0, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 0, 1, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 0, 2, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 0, 3, BODY, STEP) \
+        PTSS_TRI_CLASS_LOOP(_cb, 1, 0, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 1, 2, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 1, 3, BODY, STEP)      \
+        PTSS_TRI_CLASS_LOOP(_cb, 2, 0, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 2, 1, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 2, 3, BODY, STEP)      \
+        PTSS_TRI_CLASS_LOOP(_cb, 3, 0, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 3, 1, BODY, STEP) PTSS_TRI_CLASS_LOOP(_cb, 3, 2, BODY, STEP)      \
     } while (0)
-#define PTSS_TRI_CLASS_LOOP(cb, c1, c2, BODY) \
-    for (int t = classBegin<(c1) * 4 + (c2)>(cb), tEnd = classBegin<(c1) * 4 + (c2) + 1>(cb); t < tEnd; ++t) { BODY(c1, c2, t) }
+#define PTSS_TRI_CLASS_LOOP(cb, c1, c2, BODY, STEP) \
+    for (int t = classBegin<(c1) * 4 + (c2)>(cb), tEnd = classBegin<(c1) * 4 + (c2) + 1>(cb); t < tEnd; ++t, STEP) { BODY(c1, c2, t) }
 
 // the any-hit form of the same bodies (lineOfSight is an OR over independent tests: any order)
 template <int kC1, int kC2>
@@ -353,11 +358,13 @@ __device__ __forceinline__ void shiftInSpherePrimary(uint32_t& rev, float4 pv, v
     }
 }
 template <bool kPrimary, bool kBounded>
-__device__ __forceinline__ uint32_t sphereCandidates(const float4* rows, int cnt, vec3 o, vec3 d) {
+__device__ __forceinline__ uint32_t sphereCandidates(const float4* image, int firstRow, int cnt, vec3 o, vec3 d) {
     const int trips = (cnt + 3) >> 2;  // wave-uniform, 1..8
     uint32_t rev = 0;
-    for (int g = 0; g < trips; ++g) {
-        const float4 r0 = rows[4 * g], r1 = rows[4 * g + 1], r2 = rows[4 * g + 2], r3 = rows[4 * g + 3];
+    uint32_t at = vectorRow(image, firstRow);   // the trip's four rows through one vector address (ptwave.h)
+    for (int g = 0; g < trips; ++g, at += 4 * kRowBytes) {
+        const float4* p = rowAt(image, at);
+        const float4 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
         if constexpr (kPrimary) {
             shiftInSpherePrimary<kBounded>(rev, r0, d);
             shiftInSpherePrimary<kBounded>(rev, r1, d);
@@ -375,11 +382,13 @@ __device__ __forceinline__ uint32_t sphereCandidates(const float4* rows, int cnt
 // two spheres per trip: for the shadow passes, where the registers are needed elsewhere (four rows in flight there
 // push the 72-VGPR kernel into scratch)
 template <bool kBounded>
-__device__ __forceinline__ uint32_t sphereCandidatesPairs(const float4* rows, int cnt, vec3 o, vec3 d) {
+__device__ __forceinline__ uint32_t sphereCandidatesPairs(const float4* image, int firstRow, int cnt, vec3 o, vec3 d) {
     const int trips = (cnt + 1) >> 1;  // 1..16
     uint32_t rev = 0;
-    for (int g = 0; g < trips; ++g) {
-        const float4 r0 = rows[2 * g], r1 = rows[2 * g + 1];
+    uint32_t at = vectorRow(image, firstRow);
+    for (int g = 0; g < trips; ++g, at += 2 * kRowBytes) {
+        const float4* p = rowAt(image, at);
+        const float4 r0 = p[0], r1 = p[1];
         shiftInSphere<kBounded>(rev, r0, o, d);
         shiftInSphere<kBounded>(rev, r1, o, d);
     }

@@ -2,6 +2,7 @@
 // a ray in registers (RayRegs: the reference's Ray, RenderStructs.h, plus its XORWOW state), and the addressing, loads and
 // stores of the ray pools (ptss_device.h "ray pools"), plain or past the L1 (kCoherent). Restates no reference arithmetic.
 #pragma once
+#include "ptlocate.h"
 #include "ptss_device.h"
 #include "ptwave.h"
 
@@ -14,14 +15,19 @@ struct PixelCoord {
 };
 
 __device__ __forceinline__ PixelCoord locate(const TileMap& t, uint32_t local) {
-    const int lx = (int)(local % (uint32_t)t.width);
-    const int ly = (int)(local / (uint32_t)t.width);
-    const int band = ly / t.bandRows, within = ly % t.bandRows;
-    PixelCoord p;
-    p.x = lx;
-    p.gy = (band * t.world + t.rank) * t.bandRows + within;
-    p.globalIndex = (uint32_t)p.gy * (uint32_t)t.width + (uint32_t)lx;
-    return p;
+    const ptloc::Coord c = ptloc::locate(t.width, t.rank, t.world, t.bandRows, local);
+    return PixelCoord{c.x, c.gy, c.globalIndex};
+}
+// The same for a wave whose lanes hold the consecutive local pixels first, first + 1, ... (bounce 0): the divisions once, on
+// wave-uniform values (`first` must be wave-uniform: scalar registers), then an add, a compare and three selects per lane
+// (ptlocate.h). A strip that crosses more than one row end (width < 64) takes locate() per lane; the choice is wave-uniform.
+__device__ __forceinline__ ptloc::WaveOrigin locateWave(const TileMap& t, uint32_t first) {
+    return ptloc::waveOrigin(t.width, t.rank, t.world, t.bandRows, first);
+}
+__device__ __forceinline__ PixelCoord locateLane(const TileMap& t, const ptloc::WaveOrigin& w, uint32_t first, uint32_t lane) {
+    if (!w.oneWrap) return locate(t, first + lane);
+    const ptloc::Coord c = ptloc::laneCoord(w, t.width, lane);
+    return PixelCoord{c.x, c.gy, c.globalIndex};
 }
 
 // Ray::pixelOffset as carried by a ray: local pixel in the low 26 bits, sample lane (0..S-1, S <= 64) above.

@@ -200,7 +200,9 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
         if constexpr (kFirst) {
             if (valid) {
                 const uint32_t pixel = firstPixel;
-                const PixelCoord pc = locate(tile, pixel);
+                // the wave's lanes hold 64 consecutive local pixels: located once per wave (ptraypool.h locateWave)
+                const uint32_t waveFirst = __builtin_amdgcn_readfirstlane(firstPixel - lane);
+                const PixelCoord pc = locateLane(tile, locateWave(tile, waveFirst), waveFirst, lane);
                 loadHome(fb.rngHome, firstLane * fb.plane + pixel, ray.rng);
                 const float jitteredX = pc.x + ptrng::uniform(ray.rng);
                 const float jitteredY = pc.gy + ptrng::uniform(ray.rng);

@@ -27,6 +27,31 @@ __device__ __forceinline__ void waveLdsFence() { __builtin_amdgcn_fence(__ATOMIC
 // through a VGPR — v_cndmask + v_cmp — every time a compound condition met a ballot: twice per triangle.
 __device__ __forceinline__ unsigned long long maskOf(bool directCompare) { return __builtin_amdgcn_ballot_w64(directCompare); }
 
+// A wave-uniform row of the scene image, addressed through a VECTOR register. The loops over primitives read rows that every lane
+// shares; left to itself the compiler keeps such an address in a scalar register, bumps it with s_add and copies it into a VGPR in
+// front of every group of LDS reads (ds_read takes vector addresses only) — one v_mov v, s per triangle head, one per weights block,
+// one per sphere trip, each at the SGPR-operand issue cost (4.2 against 2.3 SIMD-cycles, tools/microbench/vgpr_banks.hip).
+// vectorRow makes the address of row `row` of the image opaque to the uniformity analysis ONCE per query: the LDS byte address
+// where the image is staged in LDS (decided at compile time wherever the image's address space is known), the byte offset into the
+// image otherwise (global_load takes scalar base + vector offset). The loop advances it with a plain v_add_u32 (32, 48 and 64 are
+// inline constants) and every read of a trip goes through rowAt with immediate offsets. Only addressing changes.
+typedef __attribute__((address_space(3))) const float4 LdsRow;
+constexpr uint32_t kRowBytes = 16u;   // one float4 row of the scene image
+__device__ __forceinline__ uint32_t vectorRow(const float4* image, int row) {
+    uint32_t at = (uint32_t)row * kRowBytes;
+#if __HIP_DEVICE_COMPILE__   // (the host pass only parses device functions; it has no LDS address space)
+    if (__builtin_amdgcn_is_shared(image)) at += (uint32_t)(uintptr_t)(LdsRow*)image;
+#endif
+    asm volatile("" : "+v"(at));
+    return at;
+}
+__device__ __forceinline__ const float4* rowAt(const float4* image, uint32_t at) {
+#if __HIP_DEVICE_COMPILE__
+    if (__builtin_amdgcn_is_shared(image)) return (const float4*)(LdsRow*)(uintptr_t)at;
+#endif
+    return reinterpret_cast<const float4*>(reinterpret_cast<const char*>(image) + at);
+}
+
 __device__ __forceinline__ uint32_t lowBits(int cnt) { return (cnt >= 32) ? 0xffffffffu : ((1u << cnt) - 1u); }
 __device__ __forceinline__ uint32_t lowBitsClamped(int cnt) { return (cnt <= 0) ? 0u : lowBits(cnt); }
 

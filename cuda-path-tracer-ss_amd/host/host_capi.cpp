@@ -13,6 +13,7 @@
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
+#include "ptlocate.h"
 #include "ptmesh.h"
 #include "ptpack.h"
 #include "pttri.h"
@@ -185,6 +186,24 @@ int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d
             PTSS_TRI_CASE(3, 0) PTSS_TRI_CASE(3, 1) PTSS_TRI_CASE(3, 2)
 #undef PTSS_TRI_CASE
             default: triangleForm<0, 0>(t, o3 + 3 * i, d3 + 3 * i, limit[i], primary != 0, out); break;
+        }
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_wave_locate(int width, int rank, int world, int bandRows, unsigned int firstBegin, size_t n, int* wave3, int* lane3, int* fast) {
+    if (!wave3 || !lane3 || !fast || width <= 0 || bandRows <= 0 || world <= 0 || rank < 0 || rank >= world) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t first = firstBegin + (uint32_t)i;
+        const ptloc::WaveOrigin w = ptloc::waveOrigin(width, rank, world, bandRows, first);
+        fast[i] = w.oneWrap ? 1 : 0;
+        for (uint32_t k = 0; k < ptloc::kStrip; ++k) {
+            const ptloc::Coord ref = ptloc::locate(width, rank, world, bandRows, first + k);
+            const ptloc::Coord got = w.oneWrap ? ptloc::laneCoord(w, width, k) : ref;   // (the kernel's fallback: locate per lane)
+            int* a = wave3 + 3 * (i * ptloc::kStrip + k);
+            int* b = lane3 + 3 * (i * ptloc::kStrip + k);
+            a[0] = got.x; a[1] = got.gy; a[2] = (int)got.globalIndex;
+            b[0] = ref.x; b[1] = ref.gy; b[2] = (int)ref.globalIndex;
         }
     }
     return PTSS_HOST_OK;

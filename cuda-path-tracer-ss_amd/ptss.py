@@ -148,6 +148,8 @@ def host_lib():
         L.ptss_probe_scene_guard_flags.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint)]
         L.ptss_probe_triangle_forms.argtypes = [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_size_t, C.POINTER(C.c_int), _f32p, _f32p]
         L.ptss_probe_quant_table.argtypes = [_f32p]
+        L.ptss_probe_wave_locate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int)]
         L.ptss_probe_rng_init.argtypes = [C.c_ulonglong, C.c_uint, _u32p]
         L.ptss_scene_add_obj.argtypes = [C.c_void_p, C.c_char_p, _f32p, C.c_int, C.POINTER(C.c_size_t)]
         L.ptss_probe_mesh_bound.argtypes = [_f32p, C.c_size_t, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int), _f32p]

@@ -71,6 +71,11 @@ int ptss_probe_quant_table(float* out257);
  * camera-origin precomputes of bounce 0. cls[i] = the class; per form six floats: accepted (0/1), dist, b0, b1, b2, det. */
 int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d3, const float* limit, int primary, size_t n, int* cls,
                               float* general6, float* classed6);
+/* Pixel order of a tile (csrc/ptlocate.h — the very functions bounce 0 calls): for each of the n strips of 64 consecutive local
+ * pixels that start at firstBegin, firstBegin + 1, ..., the frame position {x, gy, globalIndex} of every pixel of the strip as the
+ * per-wave form gives it (wave3: waveOrigin + laneCoord, or locate per pixel where the strip crosses more than one row end) and as
+ * locate() gives it (lane3), 64 x 3 ints per strip; fast[i] = 1 where strip i took the per-wave form. */
+int ptss_probe_wave_locate(int width, int rank, int world, int bandRows, unsigned int firstBegin, size_t n, int* wave3, int* lane3, int* fast);
 /* The mesh image's leaf / group bound (csrc/ptmesh.h — the very predicate the kernels evaluate): builds ONE bound around the
  * ntri triangles {v0, e1, e2} (nine floats each, as stored) and answers for each of n rays (origin, direction) whether it may be
  * accepted by a triangle inside (out[i] = 1) or provably is not (0). The predicate holds for |d|^2 within 1e-5 of 1 and a
