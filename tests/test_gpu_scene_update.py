@@ -2,7 +2,8 @@
 (device-side vertex data, sceneUpdateKernel + meshRefitKernel), ptss_reseed and the read-backs. Frames are 48 x 32 at one sample
 per tick, 3 frames per leg; "equals the oracle" means accumulator, display pixels, live counts and the RNG records of sampled
 pixels are array_equal. Queries are compared with a FRESH context created on the updated scene with everySphereLoop = 1 (the
-reference's loops over every primitive), in every field of every ray."""
+reference's loops over every primitive), in every field of every ray. Every context here is single-lane with one launch per bounce;
+tests/test_gpu_live_context.py runs the same calls on live contexts of every other configuration, across changes of image kind."""
 import numpy as np
 import pytest
 
