@@ -17,6 +17,7 @@
 #include "ptss_device.h"
 #include <algorithm>
 #include "ptdenoise.h"
+#include "ptupsample.h"
 #include "ptreproject.h"
 #include "ptspecular.h"
 #include "ptpack.h"
@@ -135,6 +136,7 @@ struct ptss_context {
     unsigned int timeoutsSeen = 0;   // ptss_guard_timeouts value already reported as PTSS_ETIMEOUT
     unsigned long long launchedKernels = 0;   // bounce / frame kernel instantiations enqueued since ptss_create (ptss_launched_kernels)
     unsigned long long specularFeatureLaunches[2] = {0, 0};   // ptss_render_features_specular launches: [0] in place, [1] in LDS
+    unsigned long long upsampleLaunches = 0;                  // ptss_upsample launches
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -1112,6 +1114,70 @@ int ptss_specular_feature_launches(const ptss_context* c, unsigned long long* ou
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->specularFeatureLaunches[0];
     out2[1] = c->specularFeatureLaunches[1];
+    return PTSS_OK;
+}
+
+// ptss_render_features_scaled: ptss_render_features' launch for the frame of factor * width x factor * height — the tile map and the eye
+// constants a context of that size would hold (ptss_create, eyeParams), so the entries are that context's, byte for byte
+int ptss_render_features_scaled(ptss_context* c, int factor, ptss_pixel_feature* dev_features_hi, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_features_hi) return fail(PTSS_EINVAL, "dev_features_hi is null");
+    if (factor < 1 || factor > ptup::kMaxFactor) return fail(PTSS_EINVAL, "factor must be in [1, 4]");
+    if ((uintptr_t)dev_features_hi & 15u) return fail(PTSS_EINVAL, "dev_features_hi must be 16-byte aligned");
+    const unsigned long long n = (unsigned long long)(factor * factor) * c->numPixels;
+    if (n >= (1ull << 31)) return fail(PTSS_ERANGE, "factor^2 * local pixels must stay below 2^31");
+    if (n == 0) return PTSS_OK;   // a rank whose tile is empty
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    const int fW = factor * c->tile.width, fH = factor * c->tile.height;
+    const ptss::TileMap tile{fW, fH, factor * c->tile.localRows, c->tile.rank, c->tile.world, factor * c->tile.bandRows};
+    const ptss::EyeParams eye{c->camera, -2 * ptm::tan(c->camera.fieldOfView * 0.5f), (float)fH / (float)fW, 1.0f / fW, 1.0f / fH};
+    HIP_TRY(ptss::launchFeatures(st, im.dBlob, im.layout, im.inLds, tile, eye, defaultColor, dev_features_hi, (uint32_t)n,
+                                 c->gridCap * ptss::kShards, &c->launchedKernels));
+    return PTSS_OK;
+}
+
+int ptss_default_upsample_params(ptss_upsample_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(*p);
+    p->factor = 2;
+    p->sigmaNormal = 0.1f;
+    p->sigmaDepth = 4.0f;
+    return PTSS_OK;
+}
+
+// ptss_upsample: one launch over the hi-res frame; it reads its arguments only
+int ptss_upsample(ptss_context* c, const ptss_uchar4* dev_lo, const ptss_pixel_feature* dev_features_lo, const ptss_pixel_feature* dev_features_hi,
+                  const ptss_upsample_params* params, ptss_uchar4* dev_out_hi, ptss_history_entry* dev_out_hi_float, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_lo || !dev_features_lo || !dev_features_hi || !dev_out_hi) return fail(PTSS_EINVAL, "null argument");
+    if (const char* why = ptup::paramsError(params)) return fail(PTSS_EINVAL, why);
+    if (((uintptr_t)dev_lo | (uintptr_t)dev_out_hi) & 3u) return fail(PTSS_EINVAL, "dev_lo and dev_out_hi must be 4-byte aligned");
+    if (((uintptr_t)dev_features_lo | (uintptr_t)dev_features_hi | (uintptr_t)dev_out_hi_float) & 15u)
+        return fail(PTSS_EINVAL, "features and dev_out_hi_float must be 16-byte aligned");
+    if (static_cast<const void*>(dev_out_hi) == static_cast<const void*>(dev_lo))
+        return fail(PTSS_EINVAL, "dev_out_hi must not be dev_lo: a pixel's taps are other pixels' inputs");
+    if (c->tile.world > 1)
+        return fail(PTSS_EINVAL, "ptss_upsample needs the whole frame: this context is a pixel-band shard (tileWorld > 1), whose bands of rows "
+                                 "have no neighbours to interpolate with");
+    const int factor = params->factor;
+    if ((unsigned long long)(factor * factor) * c->numPixels >= (1ull << 31))
+        return fail(PTSS_ERANGE, "factor^2 * pixels must stay below 2^31");
+    if ((long long)factor * c->tile.height > ptup::kMaxHiRows) return fail(PTSS_ERANGE, "factor * height must not exceed 524,280 rows");
+    if (c->numPixels == 0) return PTSS_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchUpsample(st, dev_lo, dev_features_lo, dev_features_hi, dev_out_hi, dev_out_hi_float, c->tile.width, c->tile.height, factor,
+                                 ptup::levelOf(*params), &c->upsampleLaunches));
+    return PTSS_OK;
+}
+
+int ptss_upsample_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->upsampleLaunches;
     return PTSS_OK;
 }
 

@@ -199,5 +199,9 @@ hipError_t launchReproject(hipStream_t st, const uint32_t* accum, const void* fe
 hipError_t launchReprojectMotion(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* motionNow, const void* featuresPrev,
                                  const void* historyPrev, void* historyOut, int width, int height, const ptrp::View& now, const ptrp::View& prev,
                                  const ptrp::Params& params, float inverseTicks, float n, unsigned long long* launched);
+// ptss_upsample (ptss_upsample.hip; csrc/ptupsample.h): lo = width x height RGBA words, features = 32 B per pixel of their frame, outHi = one RGBA
+// word and outFloat (or nullptr) 16 B per pixel of the factor times larger frame. No bit of ptss_launched_kernels: *launches is incremented
+hipError_t launchUpsample(hipStream_t st, const void* lo, const void* featuresLo, const void* featuresHi, void* outHi, void* outFloat, int width,
+                          int height, int factor, const ptdn::Level& level, unsigned long long* launches);
 
 }  // namespace ptss

@@ -10,6 +10,7 @@
 #include "Scene.h"
 #include "ptdenoise.h"
 #include "ptreproject.h"
+#include "ptupsample.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -339,6 +340,42 @@ int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pix
     plane[0].resize(n);
     for (size_t p = 0; p < n; ++p) plane[0][p] = v3(history[p].r, history[p].g, history[p].b);
     return denoiseColours(plane, features, width, height, params, out_rgba, out_float);
+}
+
+int ptss_probe_upsample(const unsigned char* lo_rgba, const ptss_pixel_feature* features_lo, int width, int height,
+                        const ptss_pixel_feature* features_hi, const ptss_upsample_params* params, unsigned char* out_rgba, float* out_float4) {
+    if (!lo_rgba || !features_lo || !features_hi || !out_rgba || width <= 0 || height <= 0) return PTSS_HOST_EINVAL;
+    if (ptup::paramsError(params) || out_rgba == lo_rgba) return PTSS_HOST_EINVAL;
+    const int f = params->factor;
+    if ((unsigned long long)width * (unsigned long long)height * (unsigned long long)(f * f) >= (1ull << 31)) return PTSS_HOST_EINVAL;
+    const ptdn::Level lv = ptup::levelOf(*params);
+    const int hiW = width * f, hiH = height * f;
+    auto colourAt = [&](int q) {
+        uint32_t w;
+        std::memcpy(&w, lo_rgba + 4 * (size_t)q, 4);
+        return w;
+    };
+    auto featureAt = [&](int q) { return ptdn::Feature{features_lo[q].normal, features_lo[q].depth, features_lo[q].materialIdx}; };
+    auto depthAt = [&](int X, int Y) { return features_hi[(size_t)Y * hiW + X].depth; };
+    for (int Y = 0; Y < hiH; ++Y)
+        for (int X = 0; X < hiW; ++X) {
+            const size_t p = (size_t)Y * hiW + X;
+            const ptdn::Feature fp{features_hi[p].normal, features_hi[p].depth, features_hi[p].materialIdx};
+            const ptup::Result r = ptup::upsamplePixel(X, Y, width, height, f, lv, fp, colourAt, featureAt, depthAt);
+            const uint32_t px = ptup::packBytes(r.colour);
+            std::memcpy(out_rgba + 4 * p, &px, 4);
+            if (out_float4) { out_float4[4 * p] = r.colour.x; out_float4[4 * p + 1] = r.colour.y; out_float4[4 * p + 2] = r.colour.z; out_float4[4 * p + 3] = r.weight; }
+        }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_upsample_axis(int X, int factor, int* x0, int* k, float* fx) {
+    if (X < 0 || factor < 1 || factor > ptup::kMaxFactor || !x0 || !k || !fx) return PTSS_HOST_EINVAL;
+    const ptup::Axis a = ptup::axisOf(X, factor);
+    *x0 = a.x0;
+    *k = a.k;
+    *fx = a.f1;
+    return PTSS_HOST_OK;
 }
 
 // ptss_probe_reproject / ptss_probe_reproject_motion: one loop; motion_now != nullptr: the point of a hit comes from its row

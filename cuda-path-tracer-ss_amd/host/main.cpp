@@ -20,6 +20,9 @@
 //                                   pose and after every key, and the image is carried from pose to pose (ptss_render_features,
 //                                   ptss_reproject with the history kept from the previous pose); --out receives the last history
 //                                   through ptss_denoise_history (default parameters) instead of the frame's own pixels
+//             [--upscale F]         with --out image.tga: also image_upscaled.tga, F (1..4) times the size in each direction: the run traces at
+//                                   --size; the frame's pixels — with --temporal the filtered history --out receives, with --denoise the
+//                                   denoised image — go through ptss_render_features, ptss_render_features_scaled and ptss_upsample
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -41,6 +44,7 @@ int main(int argc, char* argv[]) {
     int denoise = -2;   // --denoise: -2 absent, -1 the default level count, else the level count
     int specularSteps = -1;   // --specular-features: -1 absent (first-hit features), else maxSteps
     bool temporal = false;
+    int upscale = 0;   // --upscale: 0 absent, else the factor
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -67,6 +71,7 @@ int main(int argc, char* argv[]) {
         }
         else if (a == "--specular-features") specularSteps = atoi(next());
         else if (a == "--temporal") temporal = true;
+        else if (a == "--upscale") upscale = atoi(next());
         else if (a == "--pick") {
             int x, y;
             if (sscanf(next(), "%d,%d", &x, &y) != 2) { fprintf(stderr, "bad --pick (x,y)\n"); return 2; }
@@ -107,6 +112,7 @@ int main(int argc, char* argv[]) {
     if (denoise != -2 && (gpus > 0 || out.empty())) { fprintf(stderr, "--denoise needs --out and one context (no --gpus)\n"); return 2; }
     if (specularSteps != -1 && (denoise == -2 || specularSteps < 0 || specularSteps > 8)) { fprintf(stderr, "--specular-features needs --denoise and a step count 0..8\n"); return 2; }
     if (temporal && (gpus > 0 || out.empty())) { fprintf(stderr, "--temporal needs --out and one context (no --gpus)\n"); return 2; }
+    if (upscale != 0 && (gpus > 0 || out.empty() || upscale < 1 || upscale > 4)) { fprintf(stderr, "--upscale needs --out, one context (no --gpus) and a factor 1..4\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -127,6 +133,39 @@ int main(int argc, char* argv[]) {
     data->maxIterations = bounces;
     data->resetTicksThisFrame = true;
     data->quiet = quiet;
+
+    // --upscale: devLo, a display image of the frame's size, rebuilt at `upscale` times the size with the first-hit
+    // features of the final camera at both sizes; written beside --out. 0 on success
+    auto writeUpscaled = [&](const void* devLo) -> int {
+        ptss_upsample_params up;
+        PTSS_HANDLE(ptss_default_upsample_params(&up));
+        up.factor = upscale;
+        const size_t n = (size_t)width * (size_t)height, nHi = n * (size_t)(upscale * upscale);
+        void *dfLo = nullptr, *dfHi = nullptr, *dpHi = nullptr;
+        std::vector<ptss_uchar4> host(nHi);
+        const char* failed = nullptr;
+        if (hipMalloc(&dfLo, n * sizeof(ptss_pixel_feature)) != hipSuccess || hipMalloc(&dfHi, nHi * sizeof(ptss_pixel_feature)) != hipSuccess ||
+            hipMalloc(&dpHi, nHi * sizeof(ptss_uchar4)) != hipSuccess) {
+            failed = "device buffers";
+        } else {
+            PTSS_HANDLE(ptss_render_features(ctx, (ptss_pixel_feature*)dfLo, NULL));
+            PTSS_HANDLE(ptss_render_features_scaled(ctx, upscale, (ptss_pixel_feature*)dfHi, NULL));
+            PTSS_HANDLE(ptss_upsample(ctx, (const ptss_uchar4*)devLo, (const ptss_pixel_feature*)dfLo, (const ptss_pixel_feature*)dfHi, &up,
+                                      (ptss_uchar4*)dpHi, NULL, NULL));
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            if (hipMemcpy(host.data(), dpHi, nHi * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) failed = "read-back";
+        }
+        (void)hipFree(dfLo);   // (hipFree(nullptr) is a no-op)
+        (void)hipFree(dfHi);
+        (void)hipFree(dpHi);
+        std::string name = out;
+        const size_t dot = name.rfind(".tga");
+        if (dot != std::string::npos && dot + 4 == name.size()) name.erase(dot);
+        name += "_upscaled.tga";
+        if (!failed && !writeTga(name.c_str(), host.data(), width * upscale, height * upscale)) failed = "cannot write the file";
+        if (failed) fprintf(stderr, "--upscale: %s (%s)\n", failed, name.c_str());
+        return failed ? 1 : 0;
+    };
 
     bitmap.set_max_ticks(ticks);
     if (temporal) {   // the loop of INTEGRATION.md: frames, features, reproject from the history kept at the previous pose, keep, move
@@ -159,6 +198,7 @@ int main(int argc, char* argv[]) {
         PTSS_HANDLE(ptss_synchronize(ctx));
         std::vector<ptss_uchar4> host(n);
         if (hipMemcpy(host.data(), dp, n * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--temporal: read-back\n"); return 1; }
+        if (upscale != 0 && denoise == -2 && writeUpscaled(dp) != 0) return 1;
         for (int k = 0; k < 2; ++k) { (void)hipFree(df[k]); (void)hipFree(dh[k]); }
         (void)hipFree(dp);
         if (!writeTga(out.c_str(), host.data(), width, height)) fprintf(stderr, "--temporal: cannot write %s\n", out.c_str());
@@ -196,6 +236,7 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "--denoise: read-back\n");
             return 1;
         }
+        if (upscale != 0 && writeUpscaled(dp) != 0) return 1;
         (void)hipFree(df);
         (void)hipFree(dp);
         std::string name = out;
@@ -204,6 +245,7 @@ int main(int argc, char* argv[]) {
         name += "_denoised.tga";
         if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--denoise: cannot write %s\n", name.c_str());
     }
+    if (upscale != 0 && denoise == -2 && !temporal && writeUpscaled(bitmap.devPixels) != 0) return 1;
     if (!picks.empty()) {   // picking: the pixel-centre ray of the final camera through ptss_intersect
         std::vector<ptss_ray_query> q;
         for (const auto& p : picks) q.push_back(cameraRay(data->camera, width, height, p.first, p.second, 0.5f, 0.5f));

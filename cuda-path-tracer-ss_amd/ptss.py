@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from ptss_types import (KERNEL_BITS, SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
-                        PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, Vec3, struct_to_dict)
+                        PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, UpsampleParams, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -166,6 +166,8 @@ def host_lib():
                                            C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
         L.ptss_probe_reproject_motion.argtypes = [_u32p, C.c_float, C.c_int, C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReprojectParams), C.c_void_p]
+        L.ptss_probe_upsample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(UpsampleParams), C.c_void_p, _f32p]
+        L.ptss_probe_upsample_axis.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _f32p]
         L.ptss_probe_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
         L.ptss_probe_specular_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
         L.ptss_probe_specular_class.argtypes = [C.c_void_p]
@@ -246,6 +248,10 @@ def device_lib():
         L.ptss_reproject_motion.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
         L.ptss_render_features_specular.argtypes = [vp, C.c_int, vp, vp, vp]
         L.ptss_specular_feature_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
+        L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
+        L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
+        L.ptss_upsample_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
         L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
         L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
@@ -475,6 +481,55 @@ def probe_denoise_history(history, features, width, height, params):
     return rgba, flt
 
 
+def default_upsample_params(**overrides):
+    """ptss_default_upsample_params, with factor / sigmaNormal / sigmaDepth overridden by keyword."""
+    p = UpsampleParams()
+    _check(device_lib().ptss_default_upsample_params(C.byref(p)))
+    for k, v in overrides.items():
+        if v is not None:
+            setattr(p, k, v)
+    return p
+
+
+UPSAMPLE_MAX_FACTOR = 4   # PTSS_UPSAMPLE_MAX_FACTOR (include/ptss_types.h)
+
+
+def _upsample_factor(factor):
+    """The factor of features_scaled() / upsample(), refused here before any buffer is sized from it."""
+    factor = int(factor)
+    if not 1 <= factor <= UPSAMPLE_MAX_FACTOR:
+        raise ValueError(f"factor must be in 1..{UPSAMPLE_MAX_FACTOR}")
+    return factor
+
+
+def probe_upsample_axis(X, factor):
+    """csrc/ptupsample.h axisOf on the host: (x0, k, fx) of hi-res coordinate X at `factor`."""
+    x0, k, fx = C.c_int(), C.c_int(), C.c_float()
+    rc = host_lib().ptss_probe_upsample_axis(int(X), int(factor), C.byref(x0), C.byref(k), C.byref(fx))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_upsample_axis: {rc}")
+    return x0.value, k.value, fx.value
+
+
+def probe_upsample(lo_rgba, features_lo, width, height, features_hi, params):
+    """ptss_upsample on the host (csrc/ptupsample.h): lo_rgba (H*W, 4) uint8, features_lo (H*W,) and features_hi (f*H*f*W,)
+    FEATURE_DTYPE, row-major. Returns (rgba (f*H*f*W, 4) uint8, floats (f*H*f*W,) HISTORY_DTYPE: the value before the byte
+    conversion and the taps' weight sum)."""
+    a = np.ascontiguousarray(lo_rgba, dtype=np.uint8).reshape(-1, 4)
+    fl = np.ascontiguousarray(features_lo, dtype=FEATURE_DTYPE).reshape(-1)
+    fh = np.ascontiguousarray(features_hi, dtype=FEATURE_DTYPE).reshape(-1)
+    n_hi = width * height * params.factor * params.factor
+    if len(a) != width * height or len(fl) != width * height or len(fh) != n_hi:
+        raise ValueError("lo_rgba and features_lo must hold width * height pixels, features_hi factor^2 times as many")
+    rgba = np.empty((n_hi, 4), dtype=np.uint8)
+    flt = np.empty(n_hi, dtype=HISTORY_DTYPE)
+    rc = host_lib().ptss_probe_upsample(a.ctypes.data_as(C.c_void_p), fl.ctypes.data_as(C.c_void_p), width, height, fh.ctypes.data_as(C.c_void_p),
+                                        C.byref(params), rgba.ctypes.data_as(C.c_void_p), flt.ctypes.data_as(_f32p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_upsample: {rc}")
+    return rgba, flt
+
+
 def default_reproject_params(**overrides):
     """ptss_default_reproject_params, with cosNormal / depthTolerance / maxHistory / minCoverage overridden by keyword."""
     p = ReprojectParams()
@@ -681,6 +736,7 @@ class Renderer:
         self._own_pixels = None
         self._buffers = {}            # device buffers of features() / denoise(), by name; freed by close()
         self._have_features = False   # the features buffer holds the CURRENT camera's features
+        self._have_scaled = set()     # factors whose features_scaled buffer holds the current camera's (and scene's) features
         self.ticks = 1  # GPUAnimBitmap::idle_func's static counter starts at 1 (CudaUtils.h:146)
 
     def close(self):
@@ -736,6 +792,7 @@ class Renderer:
     def set_camera(self, cam):
         _check(device_lib().ptss_set_camera(self._ctx, C.byref(cam)))
         self._have_features = False   # denoise(features=None) renders them again for the new camera
+        self._have_scaled = set()
 
     def get_camera(self):
         cam = Camera()
@@ -833,6 +890,7 @@ class Renderer:
         _check(device_lib().ptss_set_scene(self._ctx, C.byref(scene.desc)))
         self._scene = scene
         self._have_features = False
+        self._have_scaled = set()
 
     def update_triangles(self, triangles, first=0, stream=None):
         """ptss_update_triangles: new vertices and normals for the triangles with original indices first .. first + n - 1.
@@ -859,6 +917,7 @@ class Renderer:
                     _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
                 self.synchronize()
         self._have_features = False
+        self._have_scaled = set()
 
     def reseed(self, seed):
         """ptss_reseed: the random streams of a context created with this seed, and a reset."""
@@ -1040,6 +1099,87 @@ class Renderer:
         out = (C.c_ulonglong * 2)()
         _check(device_lib().ptss_specular_feature_launches(self._ctx, out))
         return int(out[0]), int(out[1])
+
+    # --- rendering below display size (ptss_render_features_scaled / ptss_upsample) ---------------------------
+    def features_scaled_devptr(self, factor):
+        return self._device_buffer(f"features_x{int(factor)}", self.local_pixels * factor * factor * FEATURE_DTYPE.itemsize)
+
+    def features_scaled(self, factor, stream=None):
+        """ptss_render_features_scaled: the first-hit features of the current camera for the frame of factor * width x factor * height
+        -> (factor^2 * local_pixels,) FEATURE_DTYPE, factor hi-res rows per local row. The device buffer is kept per factor
+        (features_scaled_devptr) and is what upsample() uses by default."""
+        factor = _upsample_factor(factor)
+        d = self.features_scaled_devptr(factor)
+        _check(device_lib().ptss_render_features_scaled(self._ctx, factor, d, C.c_void_p(stream) if stream else None))
+        out = np.empty(self.local_pixels * factor * factor, dtype=FEATURE_DTYPE)
+        if self.local_pixels:
+            if stream:
+                _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            self.synchronize()
+            _hip_check(_hip_lib().hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        self._have_scaled.add(factor)
+        return out
+
+    def upsample(self, lo=None, features_lo=None, features_hi=None, factor=2, sigma_normal=None, sigma_depth=None, dev_out=None, floats=False,
+                 stream=None):
+        """ptss_upsample -> (factor^2 * local_pixels, 4) uint8 RGBA of the factor times larger frame; with floats=True also the
+        (factor^2 * local_pixels,) HISTORY_DTYPE floats before the byte conversion (weight = the taps' weight sum). lo: None (the
+        context's pixels, pixels_devptr()), a device pointer (int) or an (local_pixels, 4) uint8 array to upload — e.g. what
+        denoise() returned. features_lo: as denoise()'s features (None: rendered on demand); features_hi: None (features_scaled(factor),
+        rendered now unless the buffer holds this camera's), a device pointer (int) or an array to upload."""
+        factor = _upsample_factor(factor)
+        params = default_upsample_params(factor=factor, sigmaNormal=sigma_normal, sigmaDepth=sigma_depth)
+        n_hi = self.local_pixels * factor ** 2
+        if lo is None:
+            d_lo = self.pixels_devptr()
+        elif isinstance(lo, int):
+            d_lo = C.c_void_p(lo)
+        else:
+            a = np.ascontiguousarray(lo, dtype=np.uint8).reshape(-1, 4)
+            if len(a) != self.local_pixels:
+                raise ValueError("lo: one RGBA pixel per local pixel")
+            d_lo = self._device_buffer("upsample_lo_upload", a.nbytes)
+            _hip_check(_hip_lib().hipMemcpy(d_lo, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+        if features_lo is None:
+            if not self._have_features:
+                self.features()
+            d_flo = self.features_devptr()
+        else:
+            d_flo = self._device_input("features_upload", features_lo, FEATURE_DTYPE)
+        if features_hi is None:
+            if factor not in self._have_scaled:
+                self.features_scaled(factor)
+            d_fhi = self.features_scaled_devptr(factor)
+        elif isinstance(features_hi, int):
+            d_fhi = C.c_void_p(features_hi)
+        else:
+            f = np.ascontiguousarray(features_hi, dtype=FEATURE_DTYPE).reshape(-1)
+            if len(f) != n_hi:
+                raise ValueError("features_hi: factor^2 entries per local pixel")
+            d_fhi = self._device_buffer_at_least("features_hi_upload", f.nbytes)
+            _hip_check(_hip_lib().hipMemcpy(d_fhi, f.ctypes.data, f.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+        if dev_out is None:
+            dev_out = self._device_buffer_at_least("upsampled", max(n_hi, 1) * 4)
+        elif isinstance(dev_out, int):
+            dev_out = C.c_void_p(dev_out)
+        d_flt = self._device_buffer_at_least("upsampled_float", max(n_hi, 1) * HISTORY_DTYPE.itemsize) if floats else None
+        _check(device_lib().ptss_upsample(self._ctx, d_lo, d_flo, d_fhi, C.byref(params), dev_out, d_flt, C.c_void_p(stream) if stream else None))
+        rgba = np.empty((n_hi, 4), dtype=np.uint8)
+        flt = np.empty(n_hi, dtype=HISTORY_DTYPE)
+        if n_hi:
+            if stream:
+                _hip_check(_hip_lib().hipDeviceSynchronize(), "hipDeviceSynchronize")
+            self.synchronize()
+            _hip_check(_hip_lib().hipMemcpy(rgba.ctypes.data, dev_out, rgba.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+            if floats:
+                _hip_check(_hip_lib().hipMemcpy(flt.ctypes.data, d_flt, flt.nbytes, 2), "hipMemcpy")
+        return (rgba, flt) if floats else rgba
+
+    def upsample_launches(self):
+        """ptss_upsample_launches: accepted ptss_upsample calls that launched, since the context was created."""
+        v = C.c_ulonglong()
+        _check(device_lib().ptss_upsample_launches(self._ctx, C.byref(v)))
+        return v.value
 
     def denoise(self, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None, stream=None):
         """ptss_denoise of the accumulated image -> (local_pixels, 4) uint8 RGBA. features: None (the buffer of the last

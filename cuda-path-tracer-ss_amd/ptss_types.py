@@ -105,6 +105,10 @@ class ReprojectParams(C.Structure):
                 ("minCoverage", C.c_float)]
 
 
+class UpsampleParams(C.Structure):
+    _fields_ = [("structSize", C.c_uint), ("factor", C.c_int), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float)]
+
+
 # The 4-byte words of csrc/ptscene.h SceneLayout, in order (ptss.probe_pack_scene decodes the layout with this list). The five
 # words of its union appear under both of their names: triClassPack0..4 (classed images) and the mesh image's dimensions.
 SCENE_LAYOUT_FIELDS = ("numSpheres", "numTriangles", "numMaterials", "numPointLights", "numAreaLights", "offSphere", "offSphereMat",

@@ -228,6 +228,41 @@ int ptss_render_features_specular(ptss_context* ctx, int maxSteps, ptss_pixel_fe
                                   void* hipStream);
 int ptss_specular_feature_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] in place, [1] in LDS */
 
+/* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
+ * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
+ * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in
+ * ptss_render_features — byte for byte what ptss_render_features of a context created at the larger size writes; factor = 1 writes
+ * what ptss_render_features writes. dev_features_hi: factor^2 * local pixels entries, hi-res rows in the order of the local rows
+ * (ptss_local_rows), `factor` hi-res rows per local row: a pixel-band shard (tileWorld > 1) gets the hi-res rows that cover its
+ * own rows. The kernel is ptss_render_features' with the larger frame's shape and eye constants: ptss_launched_kernels reports it
+ * at PTSS_KERNEL_FEATURES + inLds. Asynchronous on hipStream (NULL: the context's stream); it reads the scene image only and leaves
+ * no trace in frame state. Refused without touching the device: a null context or pointer, a factor outside 1 .. 4, a pointer that
+ * is not 16-byte aligned (PTSS_EINVAL); factor^2 * local pixels >= 2^31 (PTSS_ERANGE). */
+int ptss_render_features_scaled(ptss_context* ctx, int factor, ptss_pixel_feature* dev_features_hi, void* hipStream);
+
+/* factor 2, sigmaNormal 0.1, sigmaDepth 4 (the denoiser's tolerances: design choices, not measurements). */
+int ptss_default_upsample_params(ptss_upsample_params* p);
+
+/* Guided upsampling: an image of the context's size rebuilt at params->factor times that size, its edges taken
+ * from the features of the larger frame, which are exact, and not from the noisy colour. dev_lo: any display-scale RGBA image of
+ * the context's size — the frame's dev_pixels, or the output of ptss_denoise / ptss_denoise_history. dev_features_lo:
+ * ptss_render_features (or _specular) of the same camera; dev_features_hi: ptss_render_features_scaled at params->factor. For every
+ * hi-res pixel the four lo-res pixels around its centre are weighted bilinearly, and by material (a hard stop), normal and depth
+ * against the hi-res pixel's own feature; the result is their normalised sum, clamped to the taps that counted. A hi-res pixel none
+ * of whose taps counts (a surface the small frame did not see) takes the nearest lo-res pixel's colour, with weight 0.
+ * dev_out_hi (factor^2 * width * height pixels, row 0 = bottom) receives (unsigned char)(v + 0.5f) per channel, alpha 255;
+ * dev_out_hi_float (may be NULL) the floats before that conversion and, as weight, the sum of the taps' weights. factor = 1 copies
+ * dev_lo with alpha 255. Asynchronous on hipStream (NULL: the context's stream); the caller orders it behind whatever wrote its
+ * inputs. It reads its arguments only and leaves no trace in frame state. PTSS_EINVAL without touching the device and without
+ * counting: a null context or required pointer, a wrong structSize, a factor outside 1 .. 4, a sigma that is not finite and
+ * positive, a misaligned pointer (4 B for the pixels, 16 B for features and floats), dev_out_hi == dev_lo, a sharded context
+ * (tileWorld > 1: a band of rows has no neighbours); PTSS_ERANGE likewise for factor^2 * pixels >= 2^31 or factor * height > 524,280 rows (the launch grid). The kernel owns no bit of ptss_launched_kernels, which this call leaves as
+ * it is; ptss_upsample_launches counts its launches since ptss_create instead. */
+int ptss_upsample(ptss_context* ctx, const ptss_uchar4* dev_lo, const ptss_pixel_feature* dev_features_lo,
+                  const ptss_pixel_feature* dev_features_hi, const ptss_upsample_params* params, ptss_uchar4* dev_out_hi,
+                  ptss_history_entry* dev_out_hi_float /* may be NULL */, void* hipStream);
+int ptss_upsample_launches(const ptss_context* ctx, unsigned long long* out);
+
 /* levels 5, sigmaColor 64, sigmaNormal 0.1, sigmaDepth 4 (the values behind the figures of DESIGN.md §3.17). */
 int ptss_default_denoise_params(ptss_denoise_params* p);
 

@@ -107,6 +107,17 @@ int ptss_probe_denoise(const uint32_t* accum, float inverseTicks, const ptss_pix
 /* The same passes with float colours as input (ptss_denoise_history on the host): the r, g, b of width * height history entries. */
 int ptss_probe_denoise_history(const ptss_history_entry* history, const ptss_pixel_feature* features, int width, int height,
                                const ptss_denoise_params* params, unsigned char* out_rgba, float* out_float);
+/* ptss_upsample on the host (csrc/ptupsample.h — the very tap geometry, weights and accumulation order the kernel evaluates), with
+ * the device call's argument checks: lo_rgba = 4 bytes per pixel of a width x height image, features_lo its features, features_hi
+ * those of the params->factor times larger frame, all row-major. out_rgba: 4 bytes per hi-res pixel; out_float4 (may be NULL): r, g,
+ * b before the byte conversion and the taps' weight sum. PTSS_HOST_EINVAL: a null required pointer, a non-positive size, a hi-res
+ * frame of 2^31 pixels or more, out_rgba == lo_rgba, or parameters ptss_upsample refuses. */
+int ptss_probe_upsample(const unsigned char* lo_rgba, const ptss_pixel_feature* features_lo, int width, int height,
+                        const ptss_pixel_feature* features_hi, const ptss_upsample_params* params, unsigned char* out_rgba, float* out_float4);
+/* The tap geometry of one axis (csrc/ptupsample.h axisOf) for hi-res coordinate X at `factor`: *x0 the lower tap (-1 .. size - 1),
+ * *k the centre's distance from it in half hi-res pixels, *fx = k / (2 factor), the weight of tap x0 + 1. PTSS_HOST_EINVAL: X < 0,
+ * a factor outside 1 .. 4 or a null pointer. */
+int ptss_probe_upsample_axis(int X, int factor, int* x0, int* k, float* fx);
 /* ptss_reproject on the host (csrc/ptreproject.h — the very arithmetic the kernel evaluates), with the device call's argument
  * checks: accum = 3 uint32 per pixel, n = samples per pixel behind it, the features of both cameras and the previous history
  * row-major, width * height entries each. history_prev = NULL: no history (camera_prev and features_prev are then ignored).

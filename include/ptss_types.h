@@ -153,6 +153,16 @@ typedef struct ptss_reproject_params {
     float minCoverage;       /* bilinear weight the counting taps must reach together, else the history is dropped: [0, 1] */
 } ptss_reproject_params;
 
+/* Parameters of ptss_upsample (ptss_default_upsample_params fills them in; DESIGN.md §3.22 has the formulas). */
+typedef struct ptss_upsample_params {
+    unsigned int structSize; /* sizeof(ptss_upsample_params) as the caller compiled it */
+    int factor;              /* hi-res pixels per lo-res pixel and axis: 1 .. 4 */
+    float sigmaNormal;       /* tolerance of 1 - cos(angle between the normals): finite, > 0 */
+    float sigmaDepth;        /* depth tolerance, in units of the depth change the hi-res slope predicts for the tap's offset: finite, > 0 */
+} ptss_upsample_params;
+
+#define PTSS_UPSAMPLE_MAX_FACTOR 4
+
 /* Where the surface point under a pixel's centre was in the PREVIOUS pose (ptss_render_features_motion): one
  * 16-byte row. A miss: prevPoint 0, surface -1. */
 typedef struct ptss_pixel_motion {
