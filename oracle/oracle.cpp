@@ -4,12 +4,13 @@
 // cpu_baseline leg may load this library. The product (libptss.so) never calls it and has no CPU
 // fallback.
 //
-// PARITY STATUS: "parity unpinned by the reference" — the reference ships no tests, golden vectors
-// or fixtures for this path, it cannot be compiled here (needs nvcc, cuRAND,
-// Thrust, glm, GLUT/GLEW: SURVEY.md §8c), and even on CUDA it is not reproducible (clock64() seed,
-// unstable partition, uninitialised roughness). What pins this oracle instead: analytic known-answer
-// tests (tests/test_oracle_kat.py), rocRAND's independent XORWOW tables (tests/test_xorwow.py), libm
-// bounds on the shared math (tests/test_ptmath.py) and committed golden vectors (tests/golden/).
+// PARITY STATUS: the reference ships no tests, golden vectors or fixtures for this path and cannot be compiled here as CUDA, but
+// its own sources are compiled for the CPU (oracle/build.py build_ref -> oracle/_ref/libref_probe.so, where the reference exists)
+// and tests/test_reference_functions.py / _frames.py hold every function below and the frame loop against them: decisions equal,
+// floats within 3 x (the compiled reference's own distance from a float64 model) + 1 ulp. Not pinned: CUDA's libm
+// and fma contraction, the clock64() seed, and the glm the reference runs on there is this repository's stand-in. Further pins:
+// analytic known-answer tests (tests/test_oracle_kat.py), rocRAND's independent XORWOW tables (tests/test_xorwow.py), libm bounds
+// on the shared math (tests/test_ptmath.py) and committed golden vectors (tests/golden/).
 //
 // It follows, function by function (all paths relative to /root/reference/CudaTracer/):
 //   generateFrame                       CudaTracer.cu:587-647
@@ -821,6 +822,181 @@ void oracle_probe_eye_ray(int x, int y, int width, int height, const ptss_camera
     const Ray r = computeEyeRay(x, y, width, height, *cam, st);
     out6[0] = r.origin.x; out6[1] = r.origin.y; out6[2] = r.origin.z;
     out6[3] = r.direction.x; out6[4] = r.direction.y; out6[5] = r.direction.z;
+}
+
+// ---- batched probes with the contract of oracle/ref_probe.cpp's ref_* (tests/test_reference_functions.py) --------------------------
+// The same arrays in, the same arrays out, over THIS file's functions; scene probes take a context for its scene tables.
+namespace {
+inline vec3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
+inline void st3(float* p, const vec3& v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+inline void stState(uint32_t* p, const CurandState& s) {
+    for (int i = 0; i < 5; ++i) p[i] = s.v[i];
+    p[5] = s.d;
+}
+inline void stHit(float* out8, float d, const SurfaceElement& se) {
+    out8[0] = d;
+    st3(out8 + 1, se.point);
+    st3(out8 + 4, se.normal);
+    out8[7] = (float)se.materialIdx;
+}
+}  // namespace
+
+void oracle_fn_sphere(int n, const float* sph4, const float* ray6, const float* tmax, int updateSurfel, int* hit, float* out8) {
+    for (int i = 0; i < n; ++i) {
+        ptss_sphere sp;
+        sp.position = ld3(sph4 + 4 * i);
+        sp.radius = sph4[4 * i + 3];
+        sp.materialIdx = 7;
+        SurfaceElement se;
+        memset(&se, 0, sizeof(se));
+        float d = tmax[i];
+        hit[i] = sphereIntersectRay(sp, makeRay(ld3(ray6 + 6 * i), ld3(ray6 + 6 * i + 3)), d, se, updateSurfel != 0) ? 1 : 0;
+        stHit(out8 + 8 * i, d, se);
+    }
+}
+void oracle_fn_triangle(int n, const float* tri18, const float* ray6, const float* tmax, int updateSurfel, int* hit, float* out8) {
+    for (int i = 0; i < n; ++i) {
+        const float* t = tri18 + 18 * i;
+        ptss_triangle tri;
+        tri.vertex0 = ld3(t); tri.vertex1 = ld3(t + 3); tri.vertex2 = ld3(t + 6);
+        tri.normal0 = ld3(t + 9); tri.normal1 = ld3(t + 12); tri.normal2 = ld3(t + 15);
+        tri.materialIdx = 3;
+        SurfaceElement se;
+        memset(&se, 0, sizeof(se));
+        float d = tmax[i];
+        hit[i] = triangleIntersectRay(tri, makeRay(ld3(ray6 + 6 * i), ld3(ray6 + 6 * i + 3)), d, se, updateSurfel != 0) ? 1 : 0;
+        stHit(out8 + 8 * i, d, se);
+    }
+}
+// the two loops of pathTraceOne over the context's scene, `distance` starting at tmax
+void oracle_fn_closest_hit(const oracle_ctx* c, int n, const float* ray6, const float* tmax, int* kind, int* prim, float* out8) {
+    for (int i = 0; i < n; ++i) {
+        const Ray ray = makeRay(ld3(ray6 + 6 * i), ld3(ray6 + 6 * i + 3));
+        float d = tmax[i];
+        SurfaceElement se;
+        memset(&se, 0, sizeof(se));
+        kind[i] = 0;
+        prim[i] = -1;
+        for (size_t k = 0; k < c->data.spheres.size(); ++k)
+            if (sphereIntersectRay(c->data.spheres[k], ray, d, se)) { kind[i] = 1; prim[i] = (int)k; }
+        for (size_t k = 0; k < c->data.triangles.size(); ++k)
+            if (triangleIntersectRay(c->data.triangles[k], ray, d, se)) { kind[i] = 2; prim[i] = (int)k; }
+        if (!kind[i]) se.materialIdx = -1;
+        stHit(out8 + 8 * i, d, se);
+    }
+}
+void oracle_fn_line_of_sight(const oracle_ctx* c, int n, const float* normal, const float* p0, const float* p1, int* visible, float* out4) {
+    for (int i = 0; i < n; ++i) {
+        vec3 w_i = v3(0, 0, 0);
+        float d2 = 0;
+        visible[i] = lineOfSight(c->data, ld3(normal + 3 * i), ld3(p0 + 3 * i), ld3(p1 + 3 * i), w_i, d2) ? 1 : 0;
+        st3(out4 + 4 * i, w_i);
+        out4[4 * i + 3] = d2;
+    }
+}
+void oracle_fn_fresnel(int n, const float* refrIndex, const float* cosIin, float* out6) {
+    for (int i = 0; i < n; ++i) {
+        float cosI = cosIin[i], sinT2, n1, n2, nn;
+        computeSinT2AndRefractiveIndexes(refrIndex[i], cosI, sinT2, n1, n2, nn);
+        float* o = out6 + 6 * i;
+        o[0] = cosI; o[1] = sinT2; o[2] = n1; o[3] = n2; o[4] = nn;
+        o[5] = computeFresnelForReflectance(cosI, sinT2, n1, n2, nn);
+    }
+}
+void oracle_fn_refl_surfel(int n, const float* dir, const float* point, const float* normal, const float* cosI, float* out6) {
+    for (int i = 0; i < n; ++i) {
+        Ray ray = makeRay(v3(0, 0, 0), ld3(dir + 3 * i));
+        SurfaceElement se;
+        se.point = ld3(point + 3 * i); se.normal = ld3(normal + 3 * i); se.materialIdx = 0;
+        reflRay(ray, se, cosI[i]);
+        st3(out6 + 6 * i, ray.origin);
+        st3(out6 + 6 * i + 3, ray.direction);
+    }
+}
+void oracle_fn_refl_normal(int n, const float* dir, const float* point, const float* normal, float* out6) {
+    for (int i = 0; i < n; ++i) {
+        Ray ray = makeRay(v3(0, 0, 0), ld3(dir + 3 * i));
+        reflRay(ray, ld3(point + 3 * i), ld3(normal + 3 * i));
+        st3(out6 + 6 * i, ray.origin);
+        st3(out6 + 6 * i + 3, ray.direction);
+    }
+}
+void oracle_fn_refr(int n, const float* dir, const float* point, const float* normal, const float* cosI, const float* sinT2,
+                    const float* nn, int* active, float* out6) {
+    for (int i = 0; i < n; ++i) {
+        Ray ray = makeRay(v3(0, 0, 0), ld3(dir + 3 * i));
+        SurfaceElement se;
+        se.point = ld3(point + 3 * i); se.normal = ld3(normal + 3 * i); se.materialIdx = 0;
+        refrRay(ray, se, cosI[i], sinT2[i], nn[i]);
+        active[i] = ray.active ? 1 : 0;
+        st3(out6 + 6 * i, ray.origin);
+        st3(out6 + 6 * i + 3, ray.direction);
+    }
+}
+void oracle_fn_rotate_v2v(int n, const float* source, const float* target, float* out4) {
+    for (int i = 0; i < n; ++i) {
+        const quat q = rotateVectorToVector(ld3(source + 3 * i), ld3(target + 3 * i));
+        out4[4 * i] = q.x; out4[4 * i + 1] = q.y; out4[4 * i + 2] = q.z; out4[4 * i + 3] = q.w;
+    }
+}
+void oracle_fn_sampler(int kind, int n, const float* axis, const float* param, unsigned long long seed, float* out3, uint32_t* state6) {
+    for (int i = 0; i < n; ++i) {
+        CurandState st;
+        curand_init(seed, (uint32_t)i, &st);
+        const vec3 a = ld3(axis + 3 * i);
+        const vec3 d = kind == 0 ? randomDirectionLambert(a, st) : kind == 1 ? randomDirectionPhong(a, param[i], st) : randomDirectionBeckmann(a, param[i], st);
+        st3(out3 + 3 * i, d);
+        stState(state6 + 6 * i, st);
+    }
+}
+void oracle_fn_area_light_point(const oracle_ctx* c, int n, const int* light, unsigned long long seed, float* out3, uint32_t* state6) {
+    for (int i = 0; i < n; ++i) {
+        CurandState st;
+        curand_init(seed, (uint32_t)i, &st);
+        st3(out3 + 3 * i, getAreaLightPoint(c->data.areaLights[light[i]], c->data.triangles, st));
+        stState(state6 + 6 * i, st);
+    }
+}
+void oracle_fn_shade(const oracle_ctx* c, int n, const float* point, const float* normal, const int* materialIdx, unsigned long long seed,
+                     float* out3, uint32_t* state6) {
+    for (int i = 0; i < n; ++i) {
+        CurandState st;
+        curand_init(seed, (uint32_t)i, &st);
+        SurfaceElement se;
+        se.point = ld3(point + 3 * i); se.normal = ld3(normal + 3 * i); se.materialIdx = materialIdx[i];
+        st3(out3 + 3 * i, shade(c->data, se, c->data.materials[materialIdx[i]], st));
+        stState(state6 + 6 * i, st);
+    }
+}
+void oracle_fn_eye_ray(int n, const int* x, const int* y, int width, int height, const ptss_camera* cam, unsigned long long seed, float* out6,
+                       uint32_t* state6) {
+    for (int i = 0; i < n; ++i) {
+        CurandState st;
+        curand_init(seed, (uint32_t)(y[i] * width + x[i]), &st);
+        const Ray r = computeEyeRay(x[i], y[i], width, height, *cam, st);
+        st3(out6 + 6 * i, r.origin);
+        st3(out6 + 6 * i + 3, r.direction);
+        stState(state6 + 6 * i, st);
+    }
+}
+void oracle_fn_scatter(int n, const float* dir, const float* point, const float* normal, const ptss_material* materials, const float* cosI,
+                       const float* /*distance*/, unsigned long long seed, int* active, float* out9, uint32_t* state6) {
+    for (int i = 0; i < n; ++i) {
+        CurandState st;
+        curand_init(seed, (uint32_t)i, &st);
+        Ray ray = makeRay(v3(0, 0, 0), ld3(dir + 3 * i));
+        SurfaceElement se;
+        se.point = ld3(point + 3 * i); se.normal = ld3(normal + 3 * i); se.materialIdx = 0;
+        const vec3 col = computeIndirectRadianceAndScatter(ray, se, materials[i], cosI[i], st);
+        active[i] = ray.active ? 1 : 0;
+        st3(out9 + 9 * i, ray.origin);
+        st3(out9 + 9 * i + 3, ray.direction);
+        st3(out9 + 9 * i + 6, col);
+        stState(state6 + 6 * i, st);
+    }
+}
+void oracle_fn_tonemap(int n, const float* radiance, uint32_t* out) {
+    for (int i = 0; i < n; ++i) out[i] = quantizeSample(radiance[i]);
 }
 
 }  // extern "C"
