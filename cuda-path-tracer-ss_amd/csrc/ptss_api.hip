@@ -143,7 +143,9 @@ struct ptss_context {
     hipStream_t denoiseStream = nullptr;
     int numCUs = 0;                             // hipDeviceProp_t::multiProcessorCount of cfg.device (sceneState's launch caps)
     hipStream_t updateStream = nullptr;         // the stream of the latest ptss_update_triangles (its read-backs synchronise on it)
-    bool updated = false;
+    bool updated = false;                       // (ptss_resort_triangles records its stream here as well)
+    ptss::ResortScratch resortScratch;          // ptss_resort_triangles' device scratch, allocated by its first launching call
+    unsigned long long resortLaunches = 0;      // ptss_resort_triangles calls that launched
 };
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 constexpr int kRejectedWord = ptss::kMaxLanes;
@@ -742,6 +744,7 @@ int ptss_destroy(ptss_context* c) {
     (void)hipFree(c->dFsum);
     (void)hipFree(c->dStaged);
     for (float4* plane : c->dDenoise) (void)hipFree(plane);
+    ptss::releaseResortScratch(c->resortScratch);
     delete c;
     return PTSS_OK;
 }
@@ -1369,6 +1372,33 @@ int ptss_update_triangles(ptss_context* c, const ptss_triangle* dev_triangles, s
     return PTSS_OK;
 }
 
+// The kd order rebuilt on the device (csrc/ptorder.h, ptss_resort.hip). Only a mesh image has one: a context never holds a
+// mesh image beside a second image (planImages), so at most one image is re-sorted.
+int ptss_resort_triangles(ptss_context* c, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    SceneImage* mesh = nullptr;
+    for (SceneImage& im : c->images)
+        if (im.dBlob && ptss::meshImage(im.layout)) mesh = &im;
+    if (!mesh) return PTSS_OK;   // no kd order to rebuild: nothing launched, nothing counted
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    // the scratch exists before anything is launched: on failure the image is untouched
+    if (int rc = createCheck(ptss::reserveResortScratch(c->resortScratch, mesh->layout.numTriangles), "ptss_resort_triangles: scratch")) return rc;
+    HIP_TRY(ptss::launchResort(st, mesh->dBlob, mesh->layout, c->resortScratch));
+    ++c->resortLaunches;
+    HIP_TRY(ptss::launchMeshRefit(st, mesh->dBlob, mesh->layout, &c->launchedKernels));
+    c->updateStream = st;
+    c->updated = true;
+    c->cameraDirty = true;   // the camera-origin rows (offPrimTri) are indexed by stored position
+    return PTSS_OK;          // the same scene: no reset
+}
+
+int ptss_resort_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->resortLaunches;
+    return PTSS_OK;
+}
+
 int ptss_update_rejected(ptss_context* c, unsigned long long* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device));
@@ -1408,6 +1438,7 @@ int ptss_read_triangle_positions(ptss_context* c, int* host, size_t count) {
     if (count != (size_t)im.layout.numTriangles) return fail(PTSS_ERANGE, "count must be the scene's triangle count");
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->updated) HIP_TRY(hipStreamSynchronize(c->updateStream));
     HIP_TRY(hipMemcpy(host, im.dBlob + im.layout.offTriPos, count * sizeof(int), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }

@@ -190,6 +190,26 @@ hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src,
 hipError_t launchSceneUpdate(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, const void* records, uint32_t first, uint32_t count,
                              unsigned long long* rejected, unsigned long long* launched);
 hipError_t launchMeshRefit(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, unsigned long long* launched);
+// ptss_resort_triangles (ptss_resort.hip; csrc/ptorder.h): the triangle rows of a mesh image put into the kd order of their current vertices,
+// offTriPos and the area lights' stored positions rewritten. No bit of ptss_launched_kernels (the caller counts the call); the caller refits
+// the bounds behind it (launchMeshRefit). The scratch — one allocation, about 178 B per triangle plus the sort's temporary — belongs to the
+// context: reserveResortScratch allocates it, or replaces it when the triangle count has changed, BEFORE anything is launched (hipErrorOutOfMemory: nothing was touched).
+struct ResortScratch {
+    char* base = nullptr;
+    int capacity = 0;                 // triangles
+    float4* rows = nullptr;           // 8 per triangle: the gathered rows
+    unsigned long long* keysIn = nullptr, *keysOut = nullptr;
+    int2* seg = nullptr;              // per position: its segment [lo, hi)
+    uint32_t* codes = nullptr;        // 3 x T: the centroid codes by original index, axis by axis
+    int* iota = nullptr, *order = nullptr, *newPos = nullptr;
+    uint32_t* extent = nullptr;       // 6 per leaf-sized slot: a segment's minima and complemented maxima
+    size_t extentBytes = 0;
+    void* temp = nullptr;             // the sort's temporary
+    size_t tempBytes = 0;
+};
+hipError_t reserveResortScratch(ResortScratch& scratch, int numTriangles);
+void releaseResortScratch(ResortScratch& scratch);
+hipError_t launchResort(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, const ResortScratch& scratch);
 // ptss_reproject (ptss_reproject.hip; PTSS_KERNEL_REPROJECT of *launched): accum = 3 uint32 per pixel, features = 32 B and histories = 16 B per pixel;
 // historyPrev = nullptr: no history (featuresPrev and prev are then not read)
 hipError_t launchReproject(hipStream_t st, const uint32_t* accum, const void* featuresNow, const void* featuresPrev, const void* historyPrev,

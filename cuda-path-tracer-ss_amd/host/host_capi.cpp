@@ -16,6 +16,7 @@
 #include "ptquant.h"
 #include "ptlocate.h"
 #include "ptmesh.h"
+#include "ptorder.h"
 #include "ptpack.h"
 #include "pttri.h"
 #include "xorwow.h"
@@ -255,6 +256,19 @@ int ptss_probe_mesh_refit(const float* tri9, size_t ntri, float* bounds12) {
         ptmesh::refitBound(tri9 + 9 * 256 * g, (int)(ntri - 256 * g < 256 ? ntri - 256 * g : 256), ptmesh::kRefitSlots, bounds12 + 12 * (leaves + g));
     return PTSS_HOST_OK;
 }
+
+static int probeKdOrder(const ptss_triangle* triangles, size_t n, int* position, bool canonicalZero) {
+    if (!triangles || !position || n == 0 || n > (1u << 20)) return PTSS_HOST_EINVAL;
+    std::vector<float> v(9 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const ptss_vec3* p[3] = {&triangles[i].vertex0, &triangles[i].vertex1, &triangles[i].vertex2};
+        for (int k = 0; k < 3; ++k) { v[9 * i + 3 * k] = p[k]->x; v[9 * i + 3 * k + 1] = p[k]->y; v[9 * i + 3 * k + 2] = p[k]->z; }
+    }
+    ptorder::kdPositions(v.data(), (int)n, position, canonicalZero);
+    return PTSS_HOST_OK;
+}
+int ptss_probe_kd_order(const ptss_triangle* triangles, size_t n, int* position) { return probeKdOrder(triangles, n, position, true); }
+int ptss_probe_kd_order_signed_zero(const ptss_triangle* triangles, size_t n, int* position) { return probeKdOrder(triangles, n, position, false); }
 
 int ptss_probe_mesh_touch(const float* b, const float* o3, const float* d3, size_t n, float margin, int* out) {
     if (!b || (n && (!o3 || !d3 || !out))) return PTSS_HOST_EINVAL;

@@ -158,6 +158,8 @@ def host_lib():
         L.ptss_camera_ray.argtypes = [C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RayQuery)]
         L.ptss_probe_mesh_refit.argtypes = [_f32p, C.c_size_t, _f32p]
         L.ptss_probe_mesh_touch.argtypes = [_f32p, _f32p, _f32p, C.c_size_t, C.c_float, C.POINTER(C.c_int)]
+        L.ptss_probe_kd_order.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        L.ptss_probe_kd_order_signed_zero.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         L.ptss_probe_pack_scene.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p,
                                             C.c_size_t, _f32p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ptss_probe_denoise.argtypes = [_u32p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.POINTER(DenoiseParams), C.c_void_p, _f32p]
@@ -255,6 +257,8 @@ def device_lib():
         L.ptss_set_scene.argtypes = [vp, C.POINTER(SceneDesc)]
         L.ptss_update_triangles.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
         L.ptss_update_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_resort_triangles.argtypes = [vp, vp]
+        L.ptss_resort_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_reseed.argtypes = [vp, C.c_ulonglong]
         L.ptss_read_triangle_bounds.argtypes = [vp, _f32p, C.c_size_t]
         L.ptss_read_triangle_positions.argtypes = [vp, C.POINTER(C.c_int), C.c_size_t]
@@ -366,6 +370,20 @@ def probe_mesh_refit(tris):
     rc = host_lib().ptss_probe_mesh_refit(t.ctypes.data_as(_f32p), len(t), out.ctypes.data_as(_f32p))
     if rc != 0:
         raise PtssError(f"ptss_probe_mesh_refit: {rc}")
+    return out
+
+
+def probe_kd_order(triangles, signed_zero=False):
+    """csrc/ptorder.h on the host: the stored position of each original index under the kd order Renderer.resort_triangles()
+    rebuilds — an (n,) TRIANGLE_DTYPE array (only the vertices are read) -> (n,) int32. Every 16 consecutive positions hold what
+    the packer puts into that leaf. signed_zero: float codes that keep -0.0 below +0.0 (not the packer's order; for tests)."""
+    a = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    out = np.empty(len(a), dtype=np.int32)
+    L = host_lib()
+    fn = L.ptss_probe_kd_order_signed_zero if signed_zero else L.ptss_probe_kd_order
+    rc = fn(a.ctypes.data, len(a), out.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_kd_order: {rc}")
     return out
 
 
@@ -918,6 +936,18 @@ class Renderer:
                 self.synchronize()
         self._have_features = False
         self._have_scaled = set()
+
+    def resort_triangles(self, stream=None):
+        """ptss_resort_triangles: the kd order of a live mesh image rebuilt on the device from its current vertices (behind
+        update_triangles, before the next frame). Asynchronous on `stream` (a raw stream handle; default: the context's stream).
+        No reset: accumulation continues. Images without a kd order: nothing happens."""
+        _check(device_lib().ptss_resort_triangles(self._ctx, C.c_void_p(stream) if stream else None))
+
+    def resort_launches(self):
+        """ptss_resort_launches: resort_triangles calls that launched, since the context was created."""
+        v = C.c_ulonglong()
+        _check(device_lib().ptss_resort_launches(self._ctx, C.byref(v)))
+        return v.value
 
     def reseed(self, seed):
         """ptss_reseed: the random streams of a context created with this seed, and a reset."""

@@ -362,6 +362,30 @@ int ptss_update_triangles(ptss_context* ctx, const ptss_triangle* dev_triangles,
 /* Records ptss_update_triangles has refused since ptss_create (synchronises on the stream of the latest update). */
 int ptss_update_rejected(ptss_context* ctx, unsigned long long* out);
 
+/* ptss_resort_triangles: the kd order of a live mesh image rebuilt ON THE DEVICE from the vertices the image holds now (DESIGN.md
+ * §3.23) — the other half of an animation loop: ptss_update_triangles refits the bounds but keeps the order of the pose the scene
+ * was packed in. Afterwards every leaf (16 consecutive stored positions) holds the triangles a fresh pack of the current pose would
+ * put there (csrc/ptorder.h restates the packer's rule level by level; ptss_probe_kd_order is the same code on the host), a
+ * triangle's material and original index travel with it, the area lights name their triangles' new positions, and every bound is
+ * refitted. A triangle whose record ptss_update_triangles refused is sorted by the vertices it kept. The image keeps its address
+ * and layout; images render the same, only the culling changes. No host round trip and no wait: asynchronous on hipStream (NULL: the
+ * context's stream); the caller orders it against frames, queries and feature passes that read the scene, under the rules of
+ * ptss_update_triangles — in an animation loop it sits behind the update and before the next frame. The host side marks the camera
+ * rows stale; it requests NO reset (the scene is the same scene: accumulation continues) and ptss_read_triangle_bounds /
+ * ptss_read_triangle_positions synchronise with its stream.
+ * Scratch: about 178 bytes per triangle (8 gathered rows 128, two 8-byte key arrays, segment 8, centroid codes 12, three index arrays
+ * 12, extents 1.5) plus the radix sort's temporary, one device allocation made by the first call that launches, replaced if
+ * ptss_set_scene brings another number of triangles, freed by ptss_destroy. It is allocated before anything is launched: PTSS_ENOMEM leaves the
+ * image untouched. Every call of a context works in that one scratch: two calls on different streams are ordered against each
+ * other by the caller as well.
+ * Measured on one MI355X: 0.49 / 1.1 / 4.7 ms at 5,134 / 81,934 / 1,046,542 triangles, against 1.2 / 21 / 514 ms for
+ * ptss_set_scene of the same pose — below it at every size measured, so no crossover is known down to 5,134 triangles.
+ * Images without a kd order — plain, edge-classed, many-sphere, and every image of an everySphereLoop context: PTSS_OK, nothing
+ * launched, nothing counted. A null context: PTSS_EINVAL. ptss_launched_kernels gains PTSS_KERNEL_REFIT (the refit that ran); the
+ * sort's own kernels take no bit: ptss_resort_launches counts the calls that launched since ptss_create. */
+int ptss_resort_triangles(ptss_context* ctx, void* hipStream);
+int ptss_resort_launches(const ptss_context* ctx, unsigned long long* out);
+
 /* Re-runs the random-stream set-up (curandSetupKernel, CudaTracer.cu:22-29) with `seed` and requests a reset: afterwards the
  * streams are those of a context created with cfg.seed = seed, so frame N of an animation need not depend on what was rendered
  * before it. Waits for the context's outstanding frames first; returns once the streams are seeded. */

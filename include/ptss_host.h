@@ -87,6 +87,14 @@ int ptss_probe_mesh_bound(const float* tri9, size_t ntri, const float* o3, const
  * per bound, the ceil(ntri / 16) leaves first, then the ceil(leaves / 16) groups — what ptss_read_triangle_bounds returns after a
  * refit, bit for bit. */
 int ptss_probe_mesh_refit(const float* tri9, size_t ntri, float* bounds12);
+/* The kd order of n triangles as ptss_resort_triangles rebuilds it (csrc/ptorder.h — the very centroid, key, axis and split code
+ * the kernels run, level by level): position[i] = the stored position of original index i. Only the vertices are read; they must
+ * be finite. Every 16 consecutive positions hold what the packer's kd order (csrc/ptpack.h) puts into that leaf; inside a leaf the
+ * original indices ascend. PTSS_HOST_EINVAL: a null pointer, n = 0 or n > 2^20. */
+int ptss_probe_kd_order(const ptss_triangle* triangles, size_t n, int* position);
+/* The same rule with float codes that keep -0.0 below +0.0 — NOT the packer's order, whose comparator ties the two zeros: it exists
+ * so that a test can show that the canonical zero of ptss_probe_kd_order matters (tests/test_resort_cpu.py). */
+int ptss_probe_kd_order_signed_zero(const ptss_triangle* triangles, size_t n, int* position);
 /* The scene image ptss_create builds for a scene (csrc/ptpack.h — the very packer libptss.so runs): image `image` (0 or 1) of the
  * *numImages (1 or 2) the scene gets with cfg.everySphereLoop = everySphereLoop (0 or 1). *inLds: 1 if the image is staged in LDS.
  * layout (may be NULL) receives the image's SceneLayout (csrc/ptscene.h) as raw bytes; layoutBytes must be its size (140).
