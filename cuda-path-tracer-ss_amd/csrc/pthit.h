@@ -1,7 +1,8 @@
 // pthit.h — layer 3 of the device code of ptss_kernels.hip: the drivers that answer a whole query. closestHit is intersectScene
 // (CudaTracer.cu:121-141) for a path's ray; anyHit, anyHitSplit and pairAnyHit are lineOfSight's loops (CudaTracer.cu:437-452) for
 // shadow segments — one per lane, split over lanes, or two per surface point; closestQuery is intersectScene in the caller's order
-// for ptss_intersect and ptss_render_features.
+// for ptss_intersect and ptss_render_features; anyQuery is lineOfSight's loop on whichever image, for ptss_occluded and the shadow
+// segments of ptss_trace_paths.
 #pragma once
 #include "ptaccel.h"
 
@@ -434,6 +435,22 @@ __device__ __forceinline__ QueryHit closestQuery(const float4* sc, const float4*
     }
     if (kind == 1) w1 = w2 = 0.0f;
     return QueryHit{point, normal, dist, materialIdx, kind, prim, w1, w2};
+}
+
+// ---- Is the segment (o, d, tmax) of each live lane blocked, on ANY image and for every input (ptss_occluded; the shadow segments of
+// ptss_trace_paths): lineOfSight's loop (CudaTracer.cu:434-452) is an OR over independent tests, so anyHit's order-free loops answer it
+// for the images whose sphere tests are the literal ones (plain, mesh); the sorted many-sphere image's chunk tests assume origins in
+// the scene's range, so there the same loop walks every STORED sphere row instead of the chunks (the sorted spheres and their padding
+// copies: any order and repeats answer an OR) — literal discriminant masks, then the reference's test.
+__device__ __forceinline__ bool anyQuery(const float4* sc, const float4* __restrict__ sceneBlob, const SceneLayout& L, bool mesh, vec3 o, vec3 d,
+                                         float tmax, bool live) {
+    if (L.accelSpheres) {
+        SceneLayout Ls = L;
+        Ls.numSpheres = L.numChunks * kChunkSpheres;
+        return anyHit<false, false, false>(sc, Ls, o, d, tmax, live);
+    }
+    if (mesh) return anyHit<false, false, true>(sc, L, o, d, tmax, live, sceneBlob);
+    return anyHit<false, false, false>(sc, L, o, d, tmax, live);
 }
 
 }  // namespace

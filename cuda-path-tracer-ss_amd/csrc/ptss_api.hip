@@ -137,6 +137,8 @@ struct ptss_context {
     unsigned long long launchedKernels = 0;   // bounce / frame kernel instantiations enqueued since ptss_create (ptss_launched_kernels)
     unsigned long long specularFeatureLaunches[2] = {0, 0};   // ptss_render_features_specular launches: [0] in place, [1] in LDS
     unsigned long long upsampleLaunches = 0;                  // ptss_upsample launches
+    unsigned long long pathLaunches[2] = {0, 0};              // ptss_trace_paths launches: [0] in place, [1] in LDS
+    uint32_t* dPathJumpTable = nullptr;                       // ptss_seed_path_rng's 2^67 jump table, uploaded by its first launching call
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -745,6 +747,7 @@ int ptss_destroy(ptss_context* c) {
     (void)hipFree(c->dStaged);
     for (float4* plane : c->dDenoise) (void)hipFree(plane);
     ptss::releaseResortScratch(c->resortScratch);
+    (void)hipFree(c->dPathJumpTable);
     delete c;
     return PTSS_OK;
 }
@@ -1117,6 +1120,62 @@ int ptss_specular_feature_launches(const ptss_context* c, unsigned long long* ou
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->specularFeatureLaunches[0];
     out2[1] = c->specularFeatureLaunches[1];
+    return PTSS_OK;
+}
+
+// ptss_seed_path_rng: the streams of a path query, seeded as the context's own are (seedStreams). The jump table stays on the device
+// from the first call on, so that later calls are asynchronous.
+int ptss_seed_path_rng(ptss_context* c, ptss_path_rng* dev_rng, size_t n, unsigned long long seed, unsigned long long firstSequence,
+                       unsigned int skip, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (skip > 64u) return fail(PTSS_EINVAL, "skip must be in [0, 64]");
+    if (n == 0) return PTSS_OK;
+    if (!dev_rng) return fail(PTSS_EINVAL, "dev_rng is null with n > 0");
+    if ((uintptr_t)dev_rng & 3u) return fail(PTSS_EINVAL, "dev_rng must be 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (firstSequence > (1ull << 32) || firstSequence + n > (1ull << 32)) return fail(PTSS_ERANGE, "firstSequence + n must not exceed 2^32");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (!c->dPathJumpTable) {
+        std::vector<uint32_t> table(ptrng::kJumpTableWords);
+        ptrng::build_subsequence_table(table.data());
+        uint32_t* dTable = nullptr;
+        HIP_TRY(hipMalloc(&dTable, table.size() * sizeof(uint32_t)));
+        const hipError_t e = hipMemcpy(dTable, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(dTable);
+            return fail(PTSS_EHIP, "upload of the jump table", e);
+        }
+        c->dPathJumpTable = dTable;
+    }
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchPathRngSeed(st, dev_rng, (uint32_t)n, seed, (uint32_t)firstSequence, skip, c->dPathJumpTable));
+    return PTSS_OK;
+}
+
+// ptss_trace_paths: the queries' scene image (images[0], exact for every ray), the scene's guard flags and default colour, no frame state
+int ptss_trace_paths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng, ptss_path_result* dev_results, size_t n,
+                     unsigned int maxIterations, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (maxIterations < 1u || maxIterations > (unsigned)ptss::kMaxBounces) return fail(PTSS_EINVAL, "maxIterations must be in [1, 64]");
+    if (n == 0) return PTSS_OK;
+    if (!dev_rays || !dev_rng || !dev_results) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if ((((uintptr_t)dev_rays | (uintptr_t)dev_results) & 15u) || ((uintptr_t)dev_rng & 3u))
+        return fail(PTSS_EINVAL, "rays and results must be 16-byte aligned, dev_rng 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    HIP_TRY(ptss::launchPathQuery(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_rng, dev_results, (uint32_t)n, (int)maxIterations, defaultColor,
+                                  im.guardFlags, c->gridCap * ptss::kShards, c->pathLaunches));
+    return PTSS_OK;
+}
+
+int ptss_path_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->pathLaunches[0];
+    out2[1] = c->pathLaunches[1];
     return PTSS_OK;
 }
 

@@ -179,6 +179,12 @@ hipError_t launchFeaturesMotion(hipStream_t st, const float4* sceneBlob, SceneLa
 hipError_t launchFeaturesSpecular(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, TileMap tile, EyeParams eye,
                                   ptss_vec3 defaultColor, void* out, void* steps, uint32_t n, int maxSteps, int maxBlocks,
                                   unsigned long long* launches);
+// batched path queries (ptss_paths.hip; ptss_seed_path_rng / ptss_trace_paths): rng = n x 24 B (ptss_path_rng), rays = n x 32 B, out = n x 16 B
+// (ptss_path_result); firstSequence + n <= 2^32; maxIterations 1 .. kMaxBounces. No bit of ptss_launched_kernels: launches[0] (in place) or
+// launches[1] (in LDS) is incremented by launchPathQuery
+hipError_t launchPathRngSeed(hipStream_t st, void* rng, uint32_t n, uint64_t seed, uint32_t firstSequence, uint32_t skip, const uint32_t* jumpTable);
+hipError_t launchPathQuery(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* rng, void* out,
+                           uint32_t n, int maxIterations, ptss_vec3 defaultColor, uint32_t guardFlags, int maxBlocks, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

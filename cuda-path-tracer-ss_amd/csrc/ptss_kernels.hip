@@ -26,7 +26,8 @@
 //
 // The device code below the kernels sits in layer headers, each including only earlier ones: ptwave.h -> ptraypool.h, ptprim.h ->
 // ptaccel.h -> pthit.h -> ptshade.h. This file holds the kernels and their launches, and stays ONE translation unit: the diagnostic
-// counters (ptss_diag.h) are local to it.
+// counters (ptss_diag.h) are local to it. (ptss_paths.hip, the path-query kernels, is a second translation unit over the same layers,
+// with copies of its own.)
 #include "ptss_device.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
@@ -834,18 +835,7 @@ __global__ __launch_bounds__(kBlock) void queryKernel(const float4* __restrict__
         const vec3 o = xyz(r0), d = xyz(r1);
         const float tmax = r0.w;
         if constexpr (kAny) {
-            bool blocked;
-            if (L.accelSpheres) {
-                // every STORED sphere row (the sorted spheres and their padding copies: any order and repeats answer an OR) through
-                // the plain image's loop, literal discriminant masks then the reference's test
-                SceneLayout Ls = L;
-                Ls.numSpheres = L.numChunks * kChunkSpheres;
-                blocked = anyHit<false, false, false>(sc, Ls, o, d, tmax, live);
-            } else if (mesh) {
-                blocked = anyHit<false, false, true>(sc, L, o, d, tmax, live, sceneBlob);
-            } else {
-                blocked = anyHit<false, false, false>(sc, L, o, d, tmax, live);
-            }
+            const bool blocked = anyQuery(sc, sceneBlob, L, mesh, o, d, tmax, live);   // (pthit.h: the dispatch by image kind)
             if (live) reinterpret_cast<uint32_t*>(out)[i] = blocked ? 1u : 0u;
         } else {
             const QueryHit q = closestQuery(sc, sceneBlob, L, o, d, tmax, live);

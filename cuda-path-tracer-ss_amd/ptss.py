@@ -12,8 +12,9 @@ import os
 
 import numpy as np
 
-from ptss_types import (KERNEL_BITS, SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, HistoryEntry, Material, PixelFeature,
-                        PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle, UChar4, UpsampleParams, Vec3, struct_to_dict)
+from ptss_types import (KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams,
+                        HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
+                        UChar4, UpsampleParams, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -250,6 +251,9 @@ def device_lib():
         L.ptss_reproject_motion.argtypes = [vp, vp, vp, C.POINTER(Camera), vp, vp, C.POINTER(ReprojectParams), vp, vp]
         L.ptss_render_features_specular.argtypes = [vp, C.c_int, vp, vp, vp]
         L.ptss_specular_feature_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_seed_path_rng.argtypes = [vp, vp, C.c_size_t, C.c_ulonglong, C.c_ulonglong, C.c_uint, vp]
+        L.ptss_trace_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint, vp]
+        L.ptss_path_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1021,6 +1025,102 @@ class Renderer:
             if d_out:
                 H.hipFree(d_out)
         return out
+
+    # --- batched path queries (ptss_seed_path_rng / ptss_trace_paths) ------------------------------------
+    def seed_path_rng(self, n, seed, first_sequence=0, skip=0, device=None):
+        """ptss_seed_path_rng: n XORWOW states, entry i that of curand_init(seed, first_sequence + i, 0) after `skip` draws ->
+        (n,) PATH_RNG_DTYPE. device: a torch device (or True for the context's) -> an (n, 6) int32 tensor on it instead, seeded on
+        the current torch stream and left there for trace_paths."""
+        L = device_lib()
+        n = int(n)
+        if device is not None:
+            import sys
+            torch = sys.modules.get("torch")
+            if torch is None:
+                raise ValueError("device=...: import torch first")
+            dev = torch.device("cuda", self.cfg.device) if device is True else torch.device(device)
+            out = torch.empty((n, 6), dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_seed_path_rng(self._ctx, C.c_void_p(out.data_ptr()) if n else None, n, seed, first_sequence, skip, C.c_void_p(stream)))
+            return out
+        out = np.empty(n, dtype=PATH_RNG_DTYPE)
+        if n == 0:
+            _check(L.ptss_seed_path_rng(self._ctx, None, 0, seed, first_sequence, skip, None))
+            return out
+        H = _hip_lib()
+        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
+        d = C.c_void_p()
+        _hip_check(H.hipMalloc(C.byref(d), out.nbytes), "hipMalloc")
+        try:
+            _check(L.ptss_seed_path_rng(self._ctx, d, n, seed, first_sequence, skip, None))
+            self.synchronize()
+            _hip_check(H.hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        finally:
+            H.hipFree(d)
+        return out
+
+    def trace_paths(self, rays, rng, max_iterations):
+        """ptss_trace_paths: radiance along the caller's rays. rays: (N, 8) float32 or (N,) RAY_DTYPE (tmax is ignored); rng: (N,)
+        PATH_RNG_DTYPE or (N, 6) uint32, one stream per ray -> ((N,) PATH_RESULT_DTYPE, (N,) PATH_RNG_DTYPE: the streams afterwards,
+        to be handed to the next call). Or torch: rays a contiguous (N, 8) float32 device tensor and rng a contiguous (N, 6) int32
+        tensor on the same device, which is UPDATED IN PLACE -> an (N, 4) float32 tensor (radiance; column 3 holds the bits of
+        `bounces`), on the current stream."""
+        L = device_lib()
+        if type(rays).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+                raise ValueError("rays: a contiguous (N, 8) float32 device tensor")
+            n = rays.shape[0]
+            if (type(rng).__module__.split(".")[0] != "torch" or rng.dtype != torch.int32 or tuple(rng.shape) != (n, 6) or not rng.is_contiguous() or
+                    rng.device != rays.device):
+                raise ValueError("rng: a contiguous (N, 6) int32 tensor on the rays' device")
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check(L.ptss_trace_paths(self._ctx, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), C.c_void_p(out.data_ptr()), n,
+                                      int(max_iterations), C.c_void_p(stream)))
+            return out
+        a = np.asarray(rays)
+        if a.dtype == RAY_DTYPE:
+            a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 8:
+            raise ValueError("rays: (N, 8) float32 or (N,) RAY_DTYPE")
+        n = a.shape[0]
+        s = np.asarray(rng)
+        if s.dtype == PATH_RNG_DTYPE:
+            s = np.ascontiguousarray(s).view(np.uint32).reshape(-1, 6)
+        s = np.ascontiguousarray(s, dtype=np.uint32)
+        if s.shape != (n, 6):
+            raise ValueError("rng: (N,) PATH_RNG_DTYPE or (N, 6) uint32, one state per ray")
+        out = np.empty(n, dtype=PATH_RESULT_DTYPE)
+        after = np.empty(n, dtype=PATH_RNG_DTYPE)
+        if n == 0:
+            _check(L.ptss_trace_paths(self._ctx, None, None, None, 0, int(max_iterations), None))
+            return out, after
+        H = _hip_lib()
+        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
+        bufs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        try:
+            for b, nbytes in zip(bufs, (a.nbytes, s.nbytes, out.nbytes)):
+                _hip_check(H.hipMalloc(C.byref(b), nbytes), "hipMalloc")
+            _hip_check(H.hipMemcpy(bufs[0], a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+            _hip_check(H.hipMemcpy(bufs[1], s.ctypes.data, s.nbytes, 1), "hipMemcpy")
+            _check(L.ptss_trace_paths(self._ctx, bufs[0], bufs[1], bufs[2], n, int(max_iterations), None))
+            self.synchronize()
+            _hip_check(H.hipMemcpy(out.ctypes.data, bufs[2], out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+            _hip_check(H.hipMemcpy(after.ctypes.data, bufs[1], after.nbytes, 2), "hipMemcpy")
+        finally:
+            for b in bufs:
+                if b:
+                    H.hipFree(b)
+        return out, after
+
+    def path_launches(self):
+        """ptss_path_launches: (ptss_trace_paths launches with the scene image read in place, with it staged in LDS)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_path_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
 
     # --- first-hit features and the denoiser (ptss_render_features / ptss_denoise) ---------------------
     def _device_buffer(self, name, nbytes):

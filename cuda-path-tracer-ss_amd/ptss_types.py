@@ -1,6 +1,8 @@
 """ctypes mirrors of include/ptss_types.h (field order = the reference's RenderStructs.h / Primitives.h)."""
 import ctypes as C
 
+import numpy as np
+
 
 class Vec3(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
@@ -83,6 +85,19 @@ class PixelMotion(C.Structure):
 SURFACE_TRIANGLE = 0x40000000   # PixelMotion.surface of triangle t: this | t
 
 
+class PathRng(C.Structure):   # ptss_path_rng: one XORWOW state, in the order of ptss_read_rng_state
+    _fields_ = [("v", C.c_uint32 * 5), ("d", C.c_uint32)]
+
+
+class PathResult(C.Structure):   # ptss_path_result: linear radiance0 and the iterations entered
+    _fields_ = [("radiance", Vec3), ("bounces", C.c_uint32)]
+
+
+# the same two rows as numpy record types (Renderer.seed_path_rng / trace_paths)
+PATH_RNG_DTYPE = np.dtype([("v", np.uint32, 5), ("d", np.uint32)])
+PATH_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("bounces", np.uint32)])
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -123,6 +138,8 @@ assert C.sizeof(Sphere) == 20 and C.sizeof(Triangle) == 76 and C.sizeof(Material
 assert C.sizeof(PointLight) == 24 and C.sizeof(AreaLight) == 32 and C.sizeof(Camera) == 40
 assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PixelFeature) == 32 and C.sizeof(HistoryEntry) == 16
 assert C.sizeof(PixelMotion) == 16 and PixelMotion.surface.offset == 12
+assert C.sizeof(PathRng) == 24 == PATH_RNG_DTYPE.itemsize and PathRng.d.offset == 20 == PATH_RNG_DTYPE.fields["d"][1]
+assert C.sizeof(PathResult) == 16 == PATH_RESULT_DTYPE.itemsize and PathResult.bounces.offset == 12 == PATH_RESULT_DTYPE.fields["bounces"][1]
 
 
 def struct_to_dict(s):

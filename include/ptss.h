@@ -228,6 +228,38 @@ int ptss_render_features_specular(ptss_context* ctx, int maxSteps, ptss_pixel_fe
                                   void* hipStream);
 int ptss_specular_feature_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] in place, [1] in LDS */
 
+/* Batched path queries: the path tracer started from the caller's rays, the third member of the query family.
+ * ptss_seed_path_rng writes one XORWOW state per entry: dev_rng[i] = the state of curand_init(seed, firstSequence + i, 0) after `skip`
+ * (0 .. 64) draws, through the jump table the context's own streams are seeded with. A caller who keeps dev_rng across
+ * ptss_trace_paths calls continues the streams: a probe accumulates progressively without any library state.
+ * ptss_trace_paths runs ray i as the thread body of the reference's pathTraceKernel (CudaTracer.cu:106-206), called maxIterations
+ * (1 .. 64) times or until the ray goes inactive, with stream dev_rng[i]: it starts from radiance0 = 0, radiance1 = 1 and distance
+ * +inf — the row's tmax is IGNORED (the struct is ptss_ray_query so that ptss_camera_ray's output can be passed as it is) —, takes the
+ * closest hit over spheres then triangles; a miss adds defaultColor * radiance1 and ends the path; a hit adds the emittance, runs
+ * shade() when cosI = dot(-d, normal) > 0 (point lights, then area lights, in index order; four draws per area light whether or not
+ * it is visible), scatters — except in iteration maxIterations - 1, whose indirect factor is (1, 1, 1) —, applies Beer-Lambert when
+ * inside, then updates radiance0 and radiance1 in the reference's order. dev_results[i].radiance = the final radiance0, LINEAR: no
+ * tone map and no clamp, NaN and inf stored as they come; .bounces = the iterations the ray entered; dev_rng[i] receives the stream's
+ * state afterwards. Fed a frame's own eye rays and streams (ptss_camera_ray with the pixel's two jitter draws; ptss_seed_path_rng(seed,
+ * 0, skip = 2) in pixel order) the call reproduces that frame's linear radiance (ptss_read_float_accumulator after the first frame)
+ * and final stream states bit for bit — as long as the frame's loop guard never fires: every path runs on its own here, so the
+ * reference's "stop once at most 128 rays are alive frame-wide" (CudaTracer.cu:622) does not exist, which is the documented behaviour
+ * of a tileWorld > 1 context.
+ * Both calls are asynchronous on hipStream (NULL: the context's stream). ptss_trace_paths reads the scene image only, never the
+ * per-camera rows, leaves no trace in frame state, may run between frames or beside them on another stream, serves sharded contexts,
+ * and is ordered by the caller against ptss_update_triangles, ptss_resort_triangles and ptss_set_scene under their rules. The first
+ * ptss_seed_path_rng of a context uploads the jump table (100 KiB, synchronously).
+ * Refused without touching the device and without counting: a null context, or a null pointer with n > 0 (PTSS_EINVAL); a pointer that
+ * is not aligned — 16 bytes for rays and results, 4 for dev_rng — (PTSS_EINVAL); maxIterations outside 1 .. 64 or skip above 64
+ * (PTSS_EINVAL); n >= 2^31, or firstSequence + n above 2^32 (PTSS_ERANGE). n = 0 returns PTSS_OK.
+ * Neither kernel owns a bit of ptss_launched_kernels, which these calls leave as it is; ptss_path_launches counts the ptss_trace_paths
+ * launches since ptss_create instead: out2[0] with the scene image read in place, out2[1] with the image staged in LDS. */
+int ptss_seed_path_rng(ptss_context* ctx, ptss_path_rng* dev_rng, size_t n, unsigned long long seed, unsigned long long firstSequence,
+                       unsigned int skip, void* hipStream);
+int ptss_trace_paths(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng /* in/out */, ptss_path_result* dev_results,
+                     size_t n, unsigned int maxIterations, void* hipStream);
+int ptss_path_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] scene read in place, [1] staged in LDS */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

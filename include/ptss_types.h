@@ -172,6 +172,20 @@ typedef struct ptss_pixel_motion {
 
 #define PTSS_SURFACE_TRIANGLE 0x40000000
 
+/* One random stream of a batched path query (ptss_seed_path_rng / ptss_trace_paths): the XORWOW state in the order
+ * of ptss_read_rng_state. 24 B, 4-byte aligned. */
+typedef struct ptss_path_rng {
+    uint32_t v[5];
+    uint32_t d;
+} ptss_path_rng;
+
+/* What ptss_trace_paths returns for one ray: one 16-byte row. radiance: the path's radiance0, linear (no tone map, no clamp; NaN and
+ * inf as they come); bounces: the iterations the ray entered, 0 .. maxIterations. */
+typedef struct ptss_path_result {
+    ptss_vec3 radiance;
+    uint32_t bounces;
+} ptss_path_result;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -216,6 +230,8 @@ static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, d
               "ptss_pixel_feature is two 16-byte rows");
 static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
 static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
+static_assert(sizeof(ptss_path_rng) == 24 && offsetof(ptss_path_rng, d) == 20, "ptss_path_rng is six 32-bit words: v[0..4], d");
+static_assert(sizeof(ptss_path_result) == 16 && offsetof(ptss_path_result, bounces) == 12, "ptss_path_result is one 16-byte row");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -228,6 +244,8 @@ _Static_assert(sizeof(ptss_pixel_feature) == 32 && offsetof(ptss_pixel_feature, 
                "ptss_pixel_feature is two 16-byte rows");
 _Static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, weight) == 12, "ptss_history_entry is one 16-byte row");
 _Static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
+_Static_assert(sizeof(ptss_path_rng) == 24 && offsetof(ptss_path_rng, d) == 20, "ptss_path_rng is six 32-bit words: v[0..4], d");
+_Static_assert(sizeof(ptss_path_result) == 16 && offsetof(ptss_path_result, bounces) == 12, "ptss_path_result is one 16-byte row");
 #endif
 
 #ifdef __cplusplus
