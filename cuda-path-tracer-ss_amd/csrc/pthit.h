@@ -15,8 +15,15 @@ namespace {
 // fails the discriminant test never changes `distance`, so visiting only the candidates, in the
 // same order, accepts exactly what the reference's full loop accepts — but the square-root path
 // runs a few times per lane instead of once per sphere for the whole wave.
+// kPrimary on a plain bounded image (kStrips): `strip` is the word of the wave's 64 pixels (ptstrip.h) — bits 0-31 the stored spheres,
+// bits 32-63 the stored triangles its eye rays can reach at all; wave-uniform, all ones where the caller has no words. A clear bit
+// says that the reference's test rejects that primitive for every ray of the strip, and a rejected primitive
+// changes nothing: the sphere trips and triangle bodies of clear bits are skipped on scalar tests, the accepted hits are the same.
 template <bool kPrimary, bool kAccel, bool kBounded, bool kMesh = false>
-__device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, bool live, uint32_t* ws) {
+__device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, const SceneLayout& L, vec3 o, vec3 d, bool live, uint32_t* ws,
+                                          unsigned long long strip = ~0ull) {
+    constexpr bool kStrips = kPrimary && !kAccel && kBounded && !kMesh;
+    const uint32_t stripSpheres = kStrips ? (uint32_t)strip : ~0u, stripTriangles = kStrips ? (uint32_t)(strip >> 32) : ~0u;
     Hit h;
     h.distance = ptm::inf();
     h.kind = 0;
@@ -25,8 +32,8 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
     if constexpr (kAccel) closestSpheresRegrouped<kPrimary>(sc, cold, L, o, d, live, h, ws);
     for (int base = 0; base < (kAccel ? 0 : L.numSpheres); base += 32) {
         const int cnt = (L.numSpheres - base < 32) ? (L.numSpheres - base) : 32;
-        uint32_t mask = sphereCandidates<kPrimary, kBounded>(sc, (kPrimary ? L.offPrimSphere : L.offSphere) + base, cnt, o, d);
-        mask &= live ? lowBits(cnt) : 0u;
+        uint32_t mask = sphereCandidates<kPrimary, kBounded, kStrips>(sc, (kPrimary ? L.offPrimSphere : L.offSphere) + base, cnt, o, d, stripSpheres);
+        mask &= live ? (lowBits(cnt) & stripSpheres) : 0u;   // (more than 32 spheres: no words, all ones for every block)
         PTSS_DIAG_CANDIDATES(mask, live, 0);
         while (mask != 0) {
             const int j = __builtin_ctz(mask);
@@ -67,8 +74,9 @@ __device__ __forceinline__ Hit closestHit(const float4* sc, const float4* cold, 
             // one vector byte address for the triangle rows (the head and the weights block of a body read through the same
             // register) and, at bounce 0, one for the camera-origin rows: ptwave.h vectorRow
             uint32_t triAt = vectorRow(sc, L.offTri), primAt = vectorRow(sc, L.offPrimTri);
-#define PTSS_CLOSEST_BODY(c1, c2, t) \
-    triangleClassed<kPrimary, c1, c2, true>(rowAt(sc, triAt), rowAt(sc, primAt), 0u, o, d, liveMask, best);
+#define PTSS_CLOSEST_BODY(c1, c2, t)                                                                   \
+    if (!kStrips || ((stripTriangles >> ((uint32_t)(t) & 31u)) & 1u) != 0u) /* t < 32 wherever a bit is clear */ \
+        triangleClassed<kPrimary, c1, c2, true>(rowAt(sc, triAt), rowAt(sc, primAt), 0u, o, d, liveMask, best);
             PTSS_FOR_TRIANGLES_BY_CLASS(L, PTSS_CLOSEST_BODY, (triAt += 3 * kRowBytes, primAt += 2 * kRowBytes));
 #undef PTSS_CLOSEST_BODY
             if (waveAny(best.key != kNoTriangle)) {

@@ -357,12 +357,21 @@ __device__ __forceinline__ void shiftInSpherePrimary(uint32_t& rev, float4 pv, v
         shiftInMayHit(rev, b * b, 4 * pv.w);
     }
 }
-template <bool kPrimary, bool kBounded>
-__device__ __forceinline__ uint32_t sphereCandidates(const float4* image, int firstRow, int cnt, vec3 o, vec3 d) {
+// kStrips (bounce 0 with strip words, pthit.h closestHit): `wanted` is wave-uniform, bit j set unless sphere j is known to be rejected for
+// every lane; a trip whose four bits are clear shifts four "no" verdicts in instead of testing (the caller drops the clear bits of
+// the other trips from the finished mask).
+template <bool kPrimary, bool kBounded, bool kStrips = false>
+__device__ __forceinline__ uint32_t sphereCandidates(const float4* image, int firstRow, int cnt, vec3 o, vec3 d, uint32_t wanted = ~0u) {
     const int trips = (cnt + 3) >> 2;  // wave-uniform, 1..8
     uint32_t rev = 0;
     uint32_t at = vectorRow(image, firstRow);   // the trip's four rows through one vector address (ptwave.h)
     for (int g = 0; g < trips; ++g, at += 4 * kRowBytes) {
+        if constexpr (kStrips) {
+            if (((wanted >> (4 * g)) & 15u) == 0u) {
+                rev <<= 4;
+                continue;
+            }
+        }
         const float4* p = rowAt(image, at);
         const float4 r0 = p[0], r1 = p[1], r2 = p[2], r3 = p[3];
         if constexpr (kPrimary) {

@@ -21,6 +21,7 @@
 #include "ptreproject.h"
 #include "ptspecular.h"
 #include "ptpack.h"
+#include "ptstrip.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -113,7 +114,10 @@ struct ptss_context {
     hipEvent_t evDisplay[2] = {nullptr, nullptr};   // displayKernel of the last frame of each parity has run (stagedTwice only)
     uint32_t capacity = 0, numPixels = 0;  // capacity: stride of the per-pixel planes (rngHome)
     uint32_t samples = 1;                    // cfg.samplesPerPass (sample lanes per pixel)
-    bool cameraDirty = true;           // primary-ray precomputes must be refreshed
+    bool cameraDirty = true;           // primary-ray precomputes must be refreshed (camera-origin rows and strip words)
+    unsigned long long* dStrips = nullptr;   // capacity / 64 strip words (csrc/ptstrip.h), rewritten together with the camera-origin rows
+    bool stripsOn = false;                   // the current image and camera are ones bounce 0 culls on: dStrips holds their words
+    bool stripsRead = false;                 // the latest frame's bounce 0 read them (ptss_read_strip_words)
     float defaultColor[3] = {0, 0, 0};
     // ProgramData (CudaTracer.h:32-42)
     ptss_camera camera{};
@@ -411,7 +415,7 @@ void selectImage(ptss_context* c) {
 
 ptss::EyeParams eyeParams(const ptss_context* c) {   // {camera, s (CudaTracer.cu:334), aspect, invW, invH}
     return {c->camera, -2 * ptm::tan(c->camera.fieldOfView * 0.5f), (float)c->tile.height / (float)c->tile.width, 1.0f / c->tile.width,
-            1.0f / c->tile.height};
+            1.0f / c->tile.height, nullptr};
 }
 
 // harvest the newest finished live-count readbacks (never blocks)
@@ -713,6 +717,7 @@ int ptss_create(const ptss_scene_desc* scene, const ptss_render_config* cfg, pts
         if (c->stagedTwice)
             for (int q = 0; q < 2; ++q) CREATE_TRY(hipEventCreateWithFlags(&c->evDisplay[q], hipEventDisableTiming));
     }
+    CREATE_TRY(hipMalloc(&c->dStrips, (size_t)(c->capacity / ptloc::kStrip) * sizeof(unsigned long long)));
     CREATE_TRY(hipEventCreate(&c->evStart));
     CREATE_TRY(hipEventCreate(&c->evStop));
     CREATE_TRY(hipEventCreate(&c->evEpoch));
@@ -745,6 +750,7 @@ int ptss_destroy(ptss_context* c) {
     (void)hipFree(c->dAccumOwned);
     (void)hipFree(c->dFsum);
     (void)hipFree(c->dStaged);
+    (void)hipFree(c->dStrips);
     for (float4* plane : c->dDenoise) (void)hipFree(plane);
     ptss::releaseResortScratch(c->resortScratch);
     (void)hipFree(c->dPathJumpTable);
@@ -780,17 +786,25 @@ int ptss_generate_frame(ptss_context* c, ptss_uchar4* pixels, int ticks) {
     if (c->cfg.syncEachFrame) HIP_TRY(hipEventRecord(c->evStart, st));  // :611
 
     const int numIterations = c->usePathTracer ? (int)c->maxIterations : 1;  // :620
-    const ptss::EyeParams eye = eyeParams(c);
+    ptss::EyeParams eye = eyeParams(c);
+    // the shorter sphere candidate test: bounded geometry AND a camera within the same range (ray origins are the camera or points on primitives)
+    const bool bounded = c->image().layout.sphereBounded != 0 && cameraInRange(c->camera);
     if (c->cameraDirty) {  // origin-only parts of the primary-ray tests (computeEyeRaysKernel :614 itself is fused into bounce 0)
         forkNeeded = true;
         HIP_TRY(ptss::launchPrimaryPrep(st, c->image().dBlob, c->image().layout, c->camera.position));
+        // ... and which primitives each 64-pixel strip's eye rays can reach (csrc/ptstrip.h): the same inputs — this camera, this image
+        // — and so the same trigger. Every call that changes either raises it: ptss_set_camera, selectImage, ptss_set_scene,
+        // ptss_update_triangles, ptss_resort_triangles (ptss_reseed touches neither)
+        c->stripsOn = ptstrip::eligible(c->image().layout, bounded);
+        if (c->stripsOn) HIP_TRY(ptss::launchStripMasks(st, c->dStrips, c->capacity, c->numPixels, c->image().dBlob, c->image().layout, c->tile, eye));
         c->cameraDirty = false;
     }
+    // only the bounce kernels' bounce 0 reads the words; the one-launch frame kernel (frames of a few tiles) visits everything
+    if (c->stripsOn && !(c->image().oneLaunch && K == 1)) eye.strips = c->dStrips;
+    c->stripsRead = eye.strips != nullptr;
     harvestHints(c);
     RC_TRY(forkLanes(c, forkNeeded));
     if (c->cfg.timeKernels) drainKernelEvents(c, false);
-    // the shorter sphere candidate test: bounded geometry AND a camera within the same range (ray origins are the camera or points on primitives)
-    const bool bounded = c->image().layout.sphereBounded != 0 && cameraInRange(c->camera);
     RC_TRY(c->image().oneLaunch && K == 1 ? traceOneLaunch(c, fbs[0], numIterations, bounded, eye) : traceBounces(c, fbs, numIterations, bounded, eye));
     RC_TRY(flushAndJoin(c, fbs, numIterations));
     if (c->samples > 1) {
@@ -816,6 +830,23 @@ int ptss_set_camera(ptss_context* c, const ptss_camera* camera) {
     c->camera = *camera;
     c->cameraDirty = true;
     c->resetTicksThisFrame = true;
+    return PTSS_OK;
+}
+
+int ptss_read_strip_words(ptss_context* c, unsigned long long* host_words, size_t capacity, size_t* count, int* enabled) {
+    if (!c || !host_words || !count || !enabled) return fail(PTSS_EINVAL, "null argument");
+    const size_t n = c->capacity / ptloc::kStrip;
+    *count = n;
+    if (capacity < n) return fail(PTSS_EINVAL, "host_words holds fewer words than the context has strips");
+    const bool on = c->stripsRead && !c->cameraDirty;
+    *enabled = on ? 1 : 0;
+    if (!on) {
+        for (size_t i = 0; i < n; ++i) host_words[i] = ptstrip::kAll;
+        return PTSS_OK;
+    }
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(host_words, c->dStrips, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }
 

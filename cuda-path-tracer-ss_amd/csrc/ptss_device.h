@@ -78,6 +78,8 @@ struct EyeParams {  // computeEyeRay constants evaluated once on the host with p
     float s;        // -2 * tan(fov/2)
     float aspect;   // H / W
     float invW, invH;
+    const unsigned long long* strips;   // bounce 0 of a bounce kernel: the strip words of this camera (ptstrip.h; word waveFirst >> 6), or nullptr:
+                                        // every primitive is visited. The last member: no other kernel argument moves
 };
 
 // ---- frame lanes: one frame traced as K independent ray populations on K streams of one device -----------------
@@ -153,6 +155,9 @@ hipError_t launchRngInit(hipStream_t st, uint32_t* rngHome, uint32_t plane, uint
 hipError_t launchDisplay(hipStream_t st, const FrameBuffers& fb);
 hipError_t launchClear(hipStream_t st, const FrameBuffers& fb);
 hipError_t launchPrimaryPrep(hipStream_t st, float4* sceneBlob, const SceneLayout& layout, ptss_vec3 origin);
+// the strip words of a camera (ptstrip.h): masks = plane / 64 words, one per 64 local pixels of the context's plane
+hipError_t launchStripMasks(hipStream_t st, unsigned long long* masks, uint32_t plane, uint32_t numPixels, const float4* sceneBlob,
+                            const SceneLayout& layout, TileMap tile, EyeParams eye);
 hipError_t launchBounce(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int bounce,
                         bool isLast, bool sceneInLds, bool bounded, int gridBlocks, TileMap tile, EyeParams eye, unsigned long long* launched);
 hipError_t launchFrame(hipStream_t st, const FrameBuffers& fb, const float4* sceneBlob, SceneLayout layout, int numBounces, bool bounded, int gridBlocks,

@@ -33,6 +33,7 @@
 #include "ptspecular.h"
 #include "pthit.h"
 #include "ptshade.h"
+#include "ptstrip.h"
 
 #include <array>
 #include <utility>
@@ -125,6 +126,18 @@ __global__ void primaryPrepKernel(float4* __restrict__ blob, SceneLayout L, vec3
     }
 }
 
+// Which primitives the eye rays of each 64-pixel strip of the context's plane can reach (ptstrip.h), one thread per strip; rerun
+// with primaryPrepKernel, whenever the camera or the scene image changes. Reads the stored sphere and triangle rows, not the
+// camera-origin rows primaryPrepKernel writes: the two launches do not depend on each other.
+__global__ void stripMaskKernel(unsigned long long* __restrict__ masks, uint32_t numStrips, uint32_t numPixels, const float4* __restrict__ blob,
+                                SceneLayout L, TileMap tile, EyeParams eye) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= numStrips) return;
+    const ptstrip::View view{eye.camera, eye.s, eye.aspect, eye.invW, eye.invH};
+    const ptstrip::Tile t{tile.width, tile.rank, tile.world, tile.bandRows};
+    masks[i] = ptstrip::stripMask(view, t, numPixels, i * ptloc::kStrip, reinterpret_cast<const float*>(blob), L);
+}
+
 // kSceneInLds = true : the scene blob is staged into LDS once per workgroup and read by broadcast
 //                      (ds_read, same address in every lane; per-lane gathers in the candidate loops).
 // kSceneInLds = false: the blob is read in place (scalar loads where the address is wave-uniform);
@@ -198,6 +211,13 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
         ray.o = ray.d = ray.L0 = ray.T = v3(0, 0, 0);
         ray.pix = 0;
         ray.active = false;
+        // bounce 0: which primitives this wave's 64 pixels can reach (ptstrip.h), one word per tile at a wave-uniform address. No words
+        // (nullptr): every bit set, every primitive visited
+        unsigned long long strip = ptstrip::kAll;
+        if constexpr (kFirst && !kAccel && kBounded && !kMesh) {
+            const uint32_t waveFirst = __builtin_amdgcn_readfirstlane(firstPixel - lane);   // < fb.plane, a multiple of 64
+            if (eye.strips != nullptr) strip = eye.strips[waveFirst >> 6];
+        }
         if constexpr (kFirst) {
             if (valid) {
                 const uint32_t pixel = firstPixel;
@@ -227,7 +247,7 @@ __device__ __forceinline__ void bounceTile(const FrameBuffers& fb, const SceneLa
         h.kind = 2; h.idx = (int)(pixOf(ray.pix) % (uint32_t)L.numTriangles); h.distance = 1.0f + ray.d.x;
         h.w0 = 0.3f; h.w1 = 0.3f; h.w2 = 0.4f;
 #else
-        const Hit h = closestHit<kFirst, kAccel, kBounded, kMesh>(sc, sceneBlob, L, ray.o, ray.d, valid, reinterpret_cast<uint32_t*>(wq));
+        const Hit h = closestHit<kFirst, kAccel, kBounded, kMesh>(sc, sceneBlob, L, ray.o, ray.d, valid, reinterpret_cast<uint32_t*>(wq), strip);
 #endif
         const bool hit = valid && h.kind != 0;
         if constexpr (!kFirst) {
@@ -1011,6 +1031,14 @@ hipError_t launchPrimaryPrep(hipStream_t st, float4* sceneBlob, const SceneLayou
     const int n = layout.numSpheres > layout.numTriangles ? layout.numSpheres : layout.numTriangles;
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(primaryPrepKernel, dim3(blocksFor((uint32_t)n, 64)), dim3(64), 0, st, sceneBlob, layout, origin);
+    return hipGetLastError();
+}
+
+hipError_t launchStripMasks(hipStream_t st, unsigned long long* masks, uint32_t plane, uint32_t numPixels, const float4* sceneBlob,
+                            const SceneLayout& layout, TileMap tile, EyeParams eye) {
+    const uint32_t numStrips = plane / ptloc::kStrip;
+    if (numStrips == 0) return hipSuccess;
+    hipLaunchKernelGGL(stripMaskKernel, dim3(blocksFor(numStrips, 64)), dim3(64), 0, st, masks, numStrips, numPixels, sceneBlob, layout, tile, eye);
     return hipGetLastError();
 }
 

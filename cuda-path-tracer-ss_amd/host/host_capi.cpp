@@ -18,6 +18,7 @@
 #include "ptmesh.h"
 #include "ptorder.h"
 #include "ptpack.h"
+#include "ptstrip.h"
 #include "pttri.h"
 #include "xorwow.h"
 
@@ -208,6 +209,44 @@ int ptss_probe_wave_locate(int width, int rank, int world, int bandRows, unsigne
             b[0] = ref.x; b[1] = ref.gy; b[2] = (int)ref.globalIndex;
         }
     }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_strip_masks(const ptss_scene_desc* scene, const ptss_camera* camera, int width, int height, int bandRows, int rank, int world,
+                           unsigned long long* masks, size_t capacity, size_t* numStrips, int* enabled, int* triPos) {
+    if (!scene || !camera || !masks || !numStrips || !enabled || width <= 0 || height <= 0 || bandRows <= 0 || world <= 0 || rank < 0 || rank >= world ||
+        ptpack::validateScene(*scene))
+        return PTSS_HOST_EINVAL;
+    int rows = 0;
+    for (int y = 0; y < height; ++y)
+        if ((y / bandRows) % world == rank) ++rows;
+    const uint32_t numPixels = (uint32_t)width * (uint32_t)rows;
+    const uint32_t plane = numPixels == 0 ? (uint32_t)ptss::kBlock : ((numPixels + ptss::kBlock - 1) / ptss::kBlock) * ptss::kBlock;   // ptss_create's capacity
+    const size_t n = plane / ptloc::kStrip;
+    *numStrips = n;
+    if (capacity < n) return PTSS_HOST_EINVAL;
+    std::vector<ptpack::PackedImage> images;
+    try {
+        images = ptpack::packImages(*scene, false);
+    } catch (const std::bad_alloc&) {
+        return PTSS_HOST_EINVAL;
+    }
+    // the image the frames of this camera use (ptss_api.hip selectImage), and whether bounce 0 culls on it (ptss_generate_frame)
+    const bool inRange = ptpack::cameraInRange(*camera);
+    const ptpack::PackedImage& im = images[(images.size() > 1 && !inRange) ? 1 : 0];
+    const bool on = ptstrip::eligible(im.layout, im.layout.sphereBounded != 0 && inRange);
+    *enabled = on ? 1 : 0;
+    if (triPos && im.layout.numTriangles > 0) {
+        if (im.layout.triClassed || ptss::meshImage(im.layout))
+            std::memcpy(triPos, &im.blob[(size_t)im.layout.offTriPos], sizeof(int) * (size_t)im.layout.numTriangles);
+        else
+            for (int t = 0; t < im.layout.numTriangles; ++t) triPos[t] = t;
+    }
+    const ptstrip::View view{*camera, -2 * ptm::tan(camera->fieldOfView * 0.5f), (float)height / (float)width, 1.0f / width, 1.0f / height};   // eyeParams
+    const ptstrip::Tile tile{width, rank, world, bandRows};
+    for (size_t i = 0; i < n; ++i)
+        masks[i] = on ? ptstrip::stripMask(view, tile, numPixels, (uint32_t)(i * ptloc::kStrip), reinterpret_cast<const float*>(im.blob.data()), im.layout)
+                      : ptstrip::kAll;
     return PTSS_HOST_OK;
 }
 

@@ -174,6 +174,8 @@ def host_lib():
         L.ptss_probe_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
         L.ptss_probe_specular_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
         L.ptss_probe_specular_class.argtypes = [C.c_void_p]
+        L.ptss_probe_strip_masks.argtypes = [C.POINTER(SceneDesc), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_void_p]
         _host = L
     return _host
 
@@ -264,6 +266,7 @@ def device_lib():
         L.ptss_resort_triangles.argtypes = [vp, vp]
         L.ptss_resort_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_reseed.argtypes = [vp, C.c_ulonglong]
+        L.ptss_read_strip_words.argtypes = [vp, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.ptss_read_triangle_bounds.argtypes = [vp, _f32p, C.c_size_t]
         L.ptss_read_triangle_positions.argtypes = [vp, C.POINTER(C.c_int), C.c_size_t]
         L.ptss_error_string.argtypes = [C.c_int]
@@ -707,6 +710,23 @@ def camera_rays(cam, width, height, jitter=(0.5, 0.5)):
     return out
 
 
+def probe_strip_masks(scene, cam, width, height, band_rows=8, rank=0, world=1):
+    """ptss_probe_strip_masks: (masks, enabled, tri_pos) — the uint64 word of every 64-pixel strip of the rank's local pixel plane
+    (bits 0-31 stored spheres, 32-63 stored triangles), whether ptss_generate_frame would use them, and the stored position of each
+    triangle (csrc/ptstrip.h on the host)."""
+    desc = scene.desc if hasattr(scene, "desc") else scene
+    rows = len(tile_rows(height, band_rows, rank, world))
+    cap = max((width * rows + 255) // 256, 1) * 4
+    masks = np.zeros(cap, dtype=np.uint64)
+    tri_pos = np.zeros(max(int(desc.numTriangles), 1), dtype=np.int32)
+    n, on = C.c_size_t(), C.c_int()
+    rc = host_lib().ptss_probe_strip_masks(C.byref(desc), C.byref(cam), width, height, band_rows, rank, world, masks.ctypes.data_as(C.c_void_p), cap,
+                                           C.byref(n), C.byref(on), tri_pos.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_strip_masks: {rc}")
+    return masks[:n.value], bool(on.value), tri_pos[:int(desc.numTriangles)]
+
+
 def tile_rows(height, band_rows, rank, world):
     n = host_lib().ptss_tile_rows(height, band_rows, rank, world, None, 0)
     if n < 0:
@@ -952,6 +972,14 @@ class Renderer:
         v = C.c_ulonglong()
         _check(device_lib().ptss_resort_launches(self._ctx, C.byref(v)))
         return v.value
+
+    def strip_words(self):
+        """ptss_read_strip_words: (words, enabled) — the uint64 strip words bounce 0 of the latest frame read (csrc/ptstrip.h), and whether it did."""
+        cap = max((self.local_pixels + 255) // 256, 1) * 4
+        words = np.zeros(cap, dtype=np.uint64)
+        n, on = C.c_size_t(), C.c_int()
+        _check(device_lib().ptss_read_strip_words(self._ctx, words.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(on)))
+        return words[:n.value], bool(on.value)
 
     def reseed(self, seed):
         """ptss_reseed: the random streams of a context created with this seed, and a reset."""

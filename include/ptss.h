@@ -161,6 +161,15 @@ int ptss_guard_timeouts(ptss_context* ctx, unsigned int* out);
  * Recorded on the host at launch. */
 int ptss_launched_kernels(const ptss_context* ctx, unsigned long long* out);
 
+/* The strip words of the latest ptss_generate_frame (csrc/ptstrip.h): one 64-bit word per 64 consecutive local pixels
+ * of the context's pixel plane (*count of them: the local pixels rounded up to 256, over 64), bits 0-31 the stored spheres and bits 32-63
+ * the stored triangles bounce 0 visits for that strip. *enabled = 1 when that frame's bounce 0 read them; 0 (and every word all ones)
+ * when it visited every primitive: an image or camera outside the cull's domain, the one-launch frame kernel, or no frame since the
+ * camera or the scene last changed. host_words holds `capacity` words (PTSS_EINVAL when that is fewer than *count, which is still set).
+ * Synchronises the context's stream. For tests and diagnostics: the words are a pure function of camera, scene and frame shape
+ * (ptss_probe_strip_masks, ptss_host.h, computes the same ones on the host). */
+int ptss_read_strip_words(ptss_context* ctx, unsigned long long* host_words, size_t capacity, size_t* count, int* enabled);
+
 /* Which range guards of the shading code the current scene's constants satisfy, decided once at ptss_create / ptss_set_scene
  * (DESIGN.md §3.8): bit 0 every light-power component is +0.0 or has a magnitude in [2^-60, 2^60), bit 1 every index of refraction has,
  * bit 2 every specularExponent is +inf or has |exponent + 1| in [2^-125, 2^126). A set bit lets the kernels divide by / into that

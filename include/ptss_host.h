@@ -76,6 +76,15 @@ int ptss_probe_triangle_forms(const float* tri9, const float* o3, const float* d
  * per-wave form gives it (wave3: waveOrigin + laneCoord, or locate per pixel where the strip crosses more than one row end) and as
  * locate() gives it (lane3), 64 x 3 ints per strip; fast[i] = 1 where strip i took the per-wave form. */
 int ptss_probe_wave_locate(int width, int rank, int world, int bandRows, unsigned int firstBegin, size_t n, int* wave3, int* lane3, int* fast);
+/* The strip words of bounce 0 (csrc/ptstrip.h — the very functions stripMaskKernel calls, compiled for the host): packs `scene` as
+ * ptss_create does and fills masks[0 .. *numStrips) with the word of every 64-pixel strip of the local pixel plane of rank `rank` of
+ * `world` (bands of bandRows rows of a width x height frame) under `camera`: bits 0-31 the stored spheres, bits 32-63 the stored
+ * triangles the strip's eye rays can reach. *enabled = 1 where ptss_generate_frame would hand the words to bounce 0 (a plain,
+ * bounded, edge-classed image of at most 32 spheres and 32 triangles, the camera in range), else 0 and every word all ones.
+ * triPos (may be NULL) receives the stored position of each of the scene's triangles; spheres are stored in the caller's order.
+ * capacity: words `masks` can hold; PTSS_HOST_EINVAL when that is too few. */
+int ptss_probe_strip_masks(const ptss_scene_desc* scene, const ptss_camera* camera, int width, int height, int bandRows, int rank, int world,
+                           unsigned long long* masks, size_t capacity, size_t* numStrips, int* enabled, int* triPos);
 /* The mesh image's leaf / group bound (csrc/ptmesh.h — the very predicate the kernels evaluate): builds ONE bound around the
  * ntri triangles {v0, e1, e2} (nine floats each, as stored) and answers for each of n rays (origin, direction) whether it may be
  * accepted by a triangle inside (out[i] = 1) or provably is not (0). The predicate holds for |d|^2 within 1e-5 of 1 and a
