@@ -22,6 +22,7 @@
 #include "ptspecular.h"
 #include "ptpack.h"
 #include "ptstrip.h"
+#include "ptcamera.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -103,7 +104,8 @@ struct ptss_context {
     int countParity = 0;                    // which of a lane's two count buffers the next frame uses
     uint32_t* dRngHome = nullptr;
     unsigned long long* dTotal = nullptr;   // [0 .. kMaxLanes) ray-bounce totals per lane, [kMaxLanes]: records ptss_update_triangles
-                                            // rejected (kRejectedWord), [kMaxLanes + 1 .. +8) unused, then one word: guard timeouts (must stay 0)
+                                            // rejected (kRejectedWord), [kMaxLanes + 1]: index entries the film calls dropped (kFilmRejectedWord),
+                                            // [kMaxLanes + 2 .. +8) unused, then one word: guard timeouts (must stay 0)
     uint32_t* dAccumOwned = nullptr;
     uint32_t* dAccum = nullptr;  // owned or bound
     float* dFsum = nullptr;
@@ -143,6 +145,9 @@ struct ptss_context {
     unsigned long long upsampleLaunches = 0;                  // ptss_upsample launches
     unsigned long long pathLaunches[2] = {0, 0};              // ptss_trace_paths launches: [0] in place, [1] in LDS
     uint32_t* dPathJumpTable = nullptr;                       // ptss_seed_path_rng's 2^67 jump table, uploaded by its first launching call
+    unsigned long long filmLaunches[3] = {0, 0, 0};           // ptss_generate_rays, ptss_accumulate_paths, ptss_ray_features calls that launched
+    hipStream_t filmStream = nullptr;                         // the stream of the latest film call with an index (ptss_film_rejected synchronises on it)
+    bool filmIndexed = false;
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -155,6 +160,7 @@ struct ptss_context {
 };
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 constexpr int kRejectedWord = ptss::kMaxLanes;
+constexpr int kFilmRejectedWord = ptss::kMaxLanes + 1;
 
 namespace {
 
@@ -1207,6 +1213,84 @@ int ptss_path_launches(const ptss_context* c, unsigned long long* out2) {
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->pathLaunches[0];
     out2[1] = c->pathLaunches[1];
+    return PTSS_OK;
+}
+
+// ---- the film of a path query (ptss_film.hip). Like the queries: images[0] at most, no frame state, the caller's stream ----
+int ptss_generate_rays(ptss_context* c, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index, size_t n, ptss_path_rng* dev_rng,
+                       ptss_ray_query* dev_rays, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptcam::cameraError(film)) return fail(PTSS_EINVAL, what);
+    const unsigned long long filmPixels = (unsigned long long)film->width * (unsigned long long)film->height;
+    if (filmPixels >= (1ull << 31)) return fail(PTSS_ERANGE, "width * height must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_rng || !dev_rays) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (((uintptr_t)dev_rays & 15u) || (((uintptr_t)dev_rng | (uintptr_t)dev_index) & 3u))
+        return fail(PTSS_EINVAL, "rays must be 16-byte aligned, dev_rng and dev_index 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchFilmRays(st, ptcam::filmOf(*film), dev_index ? 0u : (uint32_t)firstPixel, dev_index, (uint32_t)n, dev_rng, dev_rays,
+                                 c->dTotal + kFilmRejectedWord, &c->filmLaunches[0]));
+    if (dev_index) {
+        c->filmStream = st;
+        c->filmIndexed = true;
+    }
+    return PTSS_OK;
+}
+
+int ptss_accumulate_paths(ptss_context* c, const ptss_path_result* dev_results, const uint32_t* dev_index, size_t firstPixel, size_t n,
+                          ptss_film_entry* dev_film, size_t filmPixels, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_results || !dev_film) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if ((((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) || (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u))
+        return fail(PTSS_EINVAL, "results, film and history must be 16-byte aligned, dev_index and dev_pixels 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
+    HIP_TRY(ptss::launchFilmAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film, (uint32_t)filmPixels,
+                                       dev_pixels, dev_history, quantTable, c->dTotal + kFilmRejectedWord, &c->filmLaunches[1]));
+    if (dev_index) {
+        c->filmStream = st;
+        c->filmIndexed = true;
+    }
+    return PTSS_OK;
+}
+
+int ptss_ray_features(ptss_context* c, const ptss_ray_query* dev_rays, ptss_pixel_feature* dev_features, size_t n, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (n == 0) return PTSS_OK;
+    if (!dev_rays || !dev_features) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (((uintptr_t)dev_rays | (uintptr_t)dev_features) & 15u) return fail(PTSS_EINVAL, "rays and features must be 16-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
+    HIP_TRY(ptss::launchRayFeatures(st, im.dBlob, im.layout, im.inLds, dev_rays, defaultColor, dev_features, (uint32_t)n, c->gridCap * ptss::kShards,
+                                    &c->filmLaunches[2]));
+    return PTSS_OK;
+}
+
+int ptss_film_launches(const ptss_context* c, unsigned long long* out3) {
+    if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out3[k] = c->filmLaunches[k];
+    return PTSS_OK;
+}
+
+int ptss_film_rejected(ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->filmIndexed) HIP_TRY(hipStreamSynchronize(c->filmStream));
+    HIP_TRY(hipMemcpy(out, c->dTotal + kFilmRejectedWord, sizeof(*out), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }
 

@@ -12,6 +12,7 @@
 
 namespace ptdn { struct Level; }   // ptdenoise.h
 namespace ptrp { struct View; struct Params; }   // ptreproject.h
+namespace ptcam { struct Film; }   // ptcamera.h
 
 namespace ptss {
 
@@ -190,6 +191,17 @@ hipError_t launchFeaturesSpecular(hipStream_t st, const float4* sceneBlob, Scene
 hipError_t launchPathRngSeed(hipStream_t st, void* rng, uint32_t n, uint64_t seed, uint32_t firstSequence, uint32_t skip, const uint32_t* jumpTable);
 hipError_t launchPathQuery(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* rng, void* out,
                            uint32_t n, int maxIterations, ptss_vec3 defaultColor, uint32_t guardFlags, int maxBlocks, unsigned long long* launches);
+// the film of a path query (ptss_film.hip; ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features): index = n uint32 or nullptr (then
+// pixel firstPixel + i, and firstPixel + n <= the film's pixels), rng = n x 24 B, rays = n x 32 B, results = n x 16 B, film = filmPixels x 16 B
+// (ptss_film_entry), pixels / history = filmPixels entries or nullptr, features = n x 32 B. rejected: the device counter of dropped index
+// entries. No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+hipError_t launchFilmRays(hipStream_t st, const ptcam::Film& film, uint32_t firstPixel, const uint32_t* index, uint32_t n, void* rng, void* rays,
+                          unsigned long long* rejected, unsigned long long* launches);
+hipError_t launchFilmAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
+                                uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable, unsigned long long* rejected,
+                                unsigned long long* launches);
+hipError_t launchRayFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays,
+                             ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

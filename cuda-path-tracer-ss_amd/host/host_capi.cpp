@@ -11,6 +11,7 @@
 #include "ptdenoise.h"
 #include "ptreproject.h"
 #include "ptupsample.h"
+#include "ptcamera.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -549,6 +550,73 @@ int ptss_probe_rng_draw(unsigned int* state6, unsigned int* raw, float* uni, siz
 int ptss_probe_rng_jump_table(unsigned int* out, size_t words) {
     if (!out || words != (size_t)ptrng::kJumpTableWords) return PTSS_HOST_EINVAL;
     std::memcpy(out, jumpTable(), words * sizeof(uint32_t));
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index, size_t n, ptss_path_rng* rng,
+                         ptss_ray_query* rays, unsigned long long* rejected) {
+    if (ptcam::cameraError(film)) return PTSS_HOST_EINVAL;
+    const unsigned long long filmPixels = (unsigned long long)film->width * (unsigned long long)film->height;
+    if (filmPixels >= (1ull << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n > 0 && (!rng || !rays)) return PTSS_HOST_EINVAL;
+    if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
+    const ptcam::Film F = ptcam::filmOf(*film);
+    unsigned long long dropped = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned long long p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) {
+            ++dropped;
+            continue;
+        }
+        float jx = 0.5f, jy = 0.5f, u1 = 0.0f, u2 = 0.0f;
+        if (F.jitter) {
+            ptrng::State st;
+            for (int w = 0; w < 5; ++w) st.v[w] = rng[i].v[w];
+            st.d = rng[i].d;
+            jx = ptrng::uniform(st);
+            jy = ptrng::uniform(st);
+            if (F.kind == PTSS_FILM_THIN_LENS) {
+                u1 = ptrng::uniform(st);
+                u2 = ptrng::uniform(st);
+            }
+            for (int w = 0; w < 5; ++w) rng[i].v[w] = st.v[w];
+            rng[i].d = st.d;
+        }
+        rays[i] = ptcam::filmRay(F, (int)(p % (unsigned long long)F.width), (int)(p / (unsigned long long)F.width), jx, jy, u1, u2);
+    }
+    if (rejected) *rejected = dropped;
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_accumulate(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_film_entry* film,
+                          size_t filmPixels, ptss_uchar4* pixels, ptss_history_entry* history, unsigned long long* rejected) {
+    if (filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n > 0 && (!results || !film)) return PTSS_HOST_EINVAL;
+    if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
+    unsigned long long dropped = 0;
+    for (size_t i = 0; i < n; ++i) {   // the sums
+        const size_t p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) {
+            ++dropped;
+            continue;
+        }
+        film[p].r += ptq::quantize_literal(results[i].radiance.x);
+        film[p].g += ptq::quantize_literal(results[i].radiance.y);
+        film[p].b += ptq::quantize_literal(results[i].radiance.z);
+        film[p].samples += 1u;
+    }
+    for (size_t i = 0; i < n; ++i) {   // every pixel touched, resolved from its final sums
+        const size_t p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) continue;
+        const ptss_film_entry e = film[p];
+        const float inv = 1.f / (float)e.samples;
+        if (pixels) pixels[p] = ptss_uchar4{(unsigned char)(e.r * inv + 0.5f), (unsigned char)(e.g * inv + 0.5f), (unsigned char)(e.b * inv + 0.5f), 255};
+        if (history) {
+            const vec3 c = ptdn::displayValue(e.r, e.g, e.b, inv);
+            history[p] = ptss_history_entry{c.x, c.y, c.z, (float)e.samples};
+        }
+    }
+    if (rejected) *rejected = dropped;
     return PTSS_HOST_OK;
 }
 

@@ -23,6 +23,11 @@
 //             [--upscale F]         with --out image.tga: also image_upscaled.tga, F (1..4) times the size in each direction: the run traces at
 //                                   --size; the frame's pixels — with --temporal the filtered history --out receives, with --denoise the
 //                                   denoised image — go through ptss_render_features, ptss_render_features_scaled and ptss_upsample
+//             [--film pinhole|thinlens|equirect [--lens radius,focus]]   the screenshot rendered through the film of a path query instead
+//                                   of the frame loop: per tick ptss_generate_rays, ptss_trace_paths, ptss_accumulate_paths over the whole
+//                                   --size film, streams from ptss_seed_path_rng(--seed); --keys move the camera before the first tick.
+//                                   pinhole writes the frame loop's image (while that loop's guard stays silent). With --denoise:
+//                                   image_denoised.tga through ptss_ray_features and ptss_denoise_history
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,6 +50,8 @@ int main(int argc, char* argv[]) {
     int specularSteps = -1;   // --specular-features: -1 absent (first-hit features), else maxSteps
     bool temporal = false;
     int upscale = 0;   // --upscale: 0 absent, else the factor
+    std::string film;  // --film: the camera model, empty = the frame loop
+    float lensRadius = 0.05f, focusDistance = 5.0f;   // --lens
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -72,6 +79,8 @@ int main(int argc, char* argv[]) {
         else if (a == "--specular-features") specularSteps = atoi(next());
         else if (a == "--temporal") temporal = true;
         else if (a == "--upscale") upscale = atoi(next());
+        else if (a == "--film") film = next();
+        else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
             if (sscanf(next(), "%d,%d", &x, &y) != 2) { fprintf(stderr, "bad --pick (x,y)\n"); return 2; }
@@ -113,6 +122,12 @@ int main(int argc, char* argv[]) {
     if (specularSteps != -1 && (denoise == -2 || specularSteps < 0 || specularSteps > 8)) { fprintf(stderr, "--specular-features needs --denoise and a step count 0..8\n"); return 2; }
     if (temporal && (gpus > 0 || out.empty())) { fprintf(stderr, "--temporal needs --out and one context (no --gpus)\n"); return 2; }
     if (upscale != 0 && (gpus > 0 || out.empty() || upscale < 1 || upscale > 4)) { fprintf(stderr, "--upscale needs --out, one context (no --gpus) and a factor 1..4\n"); return 2; }
+    const int filmKind = film == "pinhole" ? PTSS_FILM_PINHOLE : film == "thinlens" ? PTSS_FILM_THIN_LENS : film == "equirect" ? PTSS_FILM_EQUIRECT : -1;
+    if (!film.empty() && (filmKind < 0 || gpus > 0 || out.empty() || temporal || upscale != 0 || specularSteps != -1 || samples != 1 || bounces < 1 || bounces > 64)) {
+        fprintf(stderr, "--film needs pinhole, thinlens or equirect, --out, one context (no --gpus), 1..64 bounces, one sample per pass and none of "
+                        "--temporal, --upscale, --specular-features\n");
+        return 2;
+    }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -202,6 +217,57 @@ int main(int argc, char* argv[]) {
         for (int k = 0; k < 2; ++k) { (void)hipFree(df[k]); (void)hipFree(dh[k]); }
         (void)hipFree(dp);
         if (!writeTga(out.c_str(), host.data(), width, height)) fprintf(stderr, "--temporal: cannot write %s\n", out.c_str());
+    } else if (!film.empty()) {   // the loop of INTEGRATION.md §2g: generate, trace, accumulate, once per tick
+        *GPUAnimBitmap::get_bitmap_ptr() = &bitmap;   // (saveScreenshot reads the display buffer through it)
+        for (char k : keys) moveCamera(data->camera, (unsigned char)k);
+        PTSS_HANDLE(ptss_set_camera(ctx, &data->camera));
+        ptss_film_camera fc;
+        memset(&fc, 0, sizeof(fc));
+        fc.structSize = (unsigned int)sizeof(fc);
+        fc.kind = filmKind;
+        fc.camera = data->camera;
+        fc.width = width;
+        fc.height = height;
+        fc.lensRadius = lensRadius;
+        fc.focusDistance = focusDistance;
+        fc.jitter = 1;
+        const size_t n = (size_t)width * (size_t)height;
+        void *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dFilm = nullptr, *dHist = nullptr, *dFeat = nullptr, *dOut = nullptr;
+        const bool filter = denoise != -2;
+        if (hipMalloc(&dRng, n * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dRays, n * sizeof(ptss_ray_query)) != hipSuccess ||
+            hipMalloc(&dRes, n * sizeof(ptss_path_result)) != hipSuccess || hipMalloc(&dFilm, n * sizeof(ptss_film_entry)) != hipSuccess ||
+            hipMemset(dFilm, 0, n * sizeof(ptss_film_entry)) != hipSuccess ||
+            (filter && (hipMalloc(&dHist, n * sizeof(ptss_history_entry)) != hipSuccess || hipMalloc(&dFeat, n * sizeof(ptss_pixel_feature)) != hipSuccess ||
+                        hipMalloc(&dOut, n * sizeof(ptss_uchar4)) != hipSuccess))) {
+            fprintf(stderr, "--film: device buffers\n");
+            return 1;
+        }
+        PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
+        for (int t = 0; t < ticks; ++t) {
+            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            PTSS_HANDLE(ptss_trace_paths(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, NULL));
+            PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
+                                              (ptss_history_entry*)dHist, NULL));
+        }
+        if (filter && ticks > 0) {   // the features of the film's pixel centres, then the filter over the film's display values
+            ptss_denoise_params params;
+            PTSS_HANDLE(ptss_default_denoise_params(&params));
+            if (denoise >= 0) params.levels = denoise;
+            fc.jitter = 0;
+            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dRays, (ptss_pixel_feature*)dFeat, n, NULL));
+            PTSS_HANDLE(ptss_denoise_history(ctx, (const ptss_history_entry*)dHist, (const ptss_pixel_feature*)dFeat, &params, (ptss_uchar4*)dOut, NULL));
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            std::vector<ptss_uchar4> host(n);
+            if (hipMemcpy(host.data(), dOut, n * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--film --denoise: read-back\n"); return 1; }
+            std::string name = out;
+            const size_t dot = name.rfind(".tga");
+            if (dot != std::string::npos && dot + 4 == name.size()) name.erase(dot);
+            name += "_denoised.tga";
+            if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
+        }
+        PTSS_HANDLE(ptss_synchronize(ctx));
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);
@@ -214,7 +280,7 @@ int main(int argc, char* argv[]) {
         name[sizeof(name) - 1] = 0;
         saveScreenshot(name, width, height);
     }
-    if (denoise != -2) {   // the denoised twin of the screenshot: features of the final camera, then the filter
+    if (denoise != -2 && film.empty()) {   // the denoised twin of the screenshot: features of the final camera, then the filter
         ptss_denoise_params params;
         PTSS_HANDLE(ptss_default_denoise_params(&params));
         if (denoise >= 0) params.levels = denoise;

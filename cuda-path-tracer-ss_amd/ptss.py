@@ -12,8 +12,8 @@ import os
 
 import numpy as np
 
-from ptss_types import (KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, SCENE_LAYOUT_FIELDS, SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams,
-                        HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
+from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, SCENE_LAYOUT_FIELDS,
+                        SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -176,6 +176,9 @@ def host_lib():
         L.ptss_probe_specular_class.argtypes = [C.c_void_p]
         L.ptss_probe_strip_masks.argtypes = [C.POINTER(SceneDesc), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_void_p]
+        L.ptss_probe_film_rays.argtypes = [C.POINTER(FilmCamera), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_ulonglong)]
         _host = L
     return _host
 
@@ -256,6 +259,11 @@ def device_lib():
         L.ptss_seed_path_rng.argtypes = [vp, vp, C.c_size_t, C.c_ulonglong, C.c_ulonglong, C.c_uint, vp]
         L.ptss_trace_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint, vp]
         L.ptss_path_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_generate_rays.argtypes = [vp, C.POINTER(FilmCamera), C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+        L.ptss_accumulate_paths.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+        L.ptss_ray_features.argtypes = [vp, vp, vp, C.c_size_t, vp]
+        L.ptss_film_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_film_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -463,6 +471,93 @@ HISTORY_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32
 assert HISTORY_DTYPE.itemsize == C.sizeof(HistoryEntry)
 MOTION_DTYPE = np.dtype([("prevPoint", np.float32, 3), ("surface", np.int32)])
 assert MOTION_DTYPE.itemsize == C.sizeof(PixelMotion)
+
+
+# ---- the film of a path query (ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features) ----
+def film_camera(kind, width, height, camera=None, lens_radius=0.0, focus_distance=1.0, jitter=1):
+    """A ptss_film_camera. kind: FILM_PINHOLE, FILM_THIN_LENS, FILM_EQUIRECT or "pinhole" / "thinlens" / "equirect"; camera: a Camera
+    (default_camera() otherwise); lens_radius, focus_distance: the thin lens only; jitter: 1 draws from the ray's stream, 0 draws nothing."""
+    kinds = {"pinhole": FILM_PINHOLE, "thinlens": FILM_THIN_LENS, "thin_lens": FILM_THIN_LENS, "equirect": FILM_EQUIRECT}
+    f = FilmCamera()
+    f.structSize = C.sizeof(FilmCamera)
+    f.kind = kinds[kind] if isinstance(kind, str) else int(kind)
+    C.memmove(C.byref(f.camera), C.byref(camera if camera is not None else default_camera()), C.sizeof(Camera))
+    f.width, f.height = int(width), int(height)
+    f.lensRadius, f.focusDistance = float(lens_radius), float(focus_distance)
+    f.jitter = int(jitter)
+    return f
+
+
+def film_draws(film):
+    """The uniforms a film's model takes from a ray's stream: pinhole 2, thin lens 4, equirect 2; none with jitter = 0."""
+    return 0 if not film.jitter else (4 if film.kind == FILM_THIN_LENS else 2)
+
+
+def _rng_words(rng):
+    s = np.asarray(rng)
+    if s.dtype == PATH_RNG_DTYPE:
+        s = np.ascontiguousarray(s).view(np.uint32).reshape(-1, 6)
+    s = np.array(s, dtype=np.uint32, order="C")   # a copy: advanced in place
+    if s.ndim != 2 or s.shape[1] != 6:
+        raise ValueError("rng: (N,) PATH_RNG_DTYPE or (N, 6) uint32")
+    return s
+
+
+def _film_index(index, n):
+    if index is None:
+        return None
+    i = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1)
+    if len(i) != n:
+        raise ValueError("index: one film pixel per ray")
+    return i
+
+
+def _rows(value, dtype, words, word_dtype, what, copy=False):
+    """`value` as an (N, words) array of word_dtype: a record array of `dtype` or the plain rows."""
+    a = np.asarray(value)
+    if a.dtype == dtype:
+        a = np.ascontiguousarray(a).view(word_dtype).reshape(-1, words)
+    a = np.array(a, dtype=word_dtype, order="C") if copy else np.ascontiguousarray(a, dtype=word_dtype)
+    if a.ndim != 2 or a.shape[1] != words:
+        raise ValueError(f"{what}: (N,) records or (N, {words}) {np.dtype(word_dtype).name}")
+    return a
+
+
+def probe_film_rays(film, rng, first_pixel=0, index=None, rays=None):
+    """ptss_generate_rays on the host (csrc/ptcamera.h; the specification of the device's rays) -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE:
+    the streams afterwards, number of index entries dropped). rays: the buffer's content beforehand (zeros otherwise): an entry whose
+    index leaves the film keeps it."""
+    s = _rng_words(rng)
+    n = len(s)
+    idx = _film_index(index, n)
+    out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
+    if len(out) != n:
+        raise ValueError("rays: one row per stream")
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_film_rays(C.byref(film), int(first_pixel), idx.ctypes.data_as(C.c_void_p) if idx is not None else None, n,
+                                         s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_film_rays: {rc}")
+    return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1), int(rejected.value)
+
+
+def probe_accumulate(results, film, first_pixel=0, index=None, pixels=None, history=None):
+    """ptss_accumulate_paths on the host, with the literal tone map -> (film afterwards (P,) FILM_DTYPE, pixels (P, 4) uint8 or None,
+    history (P,) HISTORY_DTYPE or None, number of index entries dropped). film: (P,) FILM_DTYPE or (P, 4) uint32 (not modified);
+    pixels / history: None (not written), True (zeros beforehand) or the buffer's content beforehand."""
+    r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+    n = len(r)
+    idx = _film_index(index, n)
+    f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
+    px = None if pixels is None else (np.zeros((len(f), 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
+    hs = None if history is None else (np.zeros((len(f), 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_accumulate(r.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if idx is not None else None, int(first_pixel),
+                                          n, f.ctypes.data_as(C.c_void_p), len(f), px.ctypes.data_as(C.c_void_p) if px is not None else None,
+                                          hs.ctypes.data_as(C.c_void_p) if hs is not None else None, C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_accumulate: {rc}")
+    return (f.view(FILM_DTYPE).reshape(-1), px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None, int(rejected.value))
 
 
 def default_denoise_params(**overrides):
@@ -1149,6 +1244,142 @@ class Renderer:
         out = (C.c_ulonglong * 2)()
         _check(device_lib().ptss_path_launches(self._ctx, out))
         return int(out[0]), int(out[1])
+
+    # --- the film of a path query (ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features) ------------------
+    def _round_trip(self, arrays, call, read):
+        """Uploads `arrays` (None entries stay NULL), runs call(device pointers) on the context's stream, waits, downloads those at `read`."""
+        H = _hip_lib()
+        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
+        bufs = [C.c_void_p() if a is not None else None for a in arrays]
+        try:
+            for b, a in zip(bufs, arrays):
+                if a is not None:
+                    _hip_check(H.hipMalloc(C.byref(b), max(a.nbytes, 16)), "hipMalloc")
+                    _hip_check(H.hipMemcpy(b, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
+            call(bufs)
+            self.synchronize()
+            for k in read:
+                a, b = arrays[k], bufs[k]
+                if a is not None:
+                    _hip_check(H.hipMemcpy(a.ctypes.data, b, a.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
+        finally:
+            for b in bufs:
+                if b:
+                    H.hipFree(b)
+
+    @staticmethod
+    def _torch_ptr(t, what, dtype, columns, device=None, n=None):
+        """The device pointer of torch tensor `t`, checked: contiguous, on `device`, dtype `dtype` (a name), shape (n, columns)."""
+        if (type(t).__module__.split(".")[0] != "torch" or str(t.dtype) != "torch." + dtype or not t.is_contiguous() or not t.is_cuda or
+                (device is not None and t.device != device) or t.dim() != (2 if columns else 1) or (columns and t.shape[1] != columns) or
+                (n is not None and t.shape[0] != n)):
+            raise ValueError(f"{what}: a contiguous {dtype} device tensor of shape ({'N' if n is None else n}{', %d' % columns if columns else ''})")
+        return C.c_void_p(t.data_ptr())
+
+    def generate_rays(self, film, rng, first_pixel=0, index=None, rays=None):
+        """ptss_generate_rays: the eye rays of film pixels index[i] (first_pixel + i without an index) from streams rng[i].
+        numpy: rng (N,) PATH_RNG_DTYPE or (N, 6) uint32 -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE: the streams afterwards); rays: the
+        buffer's content beforehand (zeros otherwise; an entry whose index leaves the film keeps it). torch: rng a contiguous (N, 6)
+        int32 device tensor, UPDATED IN PLACE, index an (N,) int32 tensor or None, rays an (N, 8) float32 tensor to write (a new one
+        otherwise) -> rays, on the current stream."""
+        L = device_lib()
+        if type(rng).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n = rng.shape[0]
+            d_rng = self._torch_ptr(rng, "rng", "int32", 6)
+            if rays is None:
+                rays = torch.zeros((n, 8), dtype=torch.float32, device=rng.device)
+            d_rays = self._torch_ptr(rays, "rays", "float32", 8, rng.device, n)
+            d_idx = self._torch_ptr(index, "index", "int32", 0, rng.device, n) if index is not None else None
+            stream = torch.cuda.current_stream(rng.device).cuda_stream
+            _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, C.c_void_p(stream)))
+            return rays
+        s = _rng_words(rng)
+        n = len(s)
+        idx = _film_index(index, n)
+        out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
+        if len(out) != n:
+            raise ValueError("rays: one row per stream")
+        if n == 0:
+            _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), None, 0, None, None, None))
+        else:
+            self._round_trip([idx, s, out], lambda d: _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d[0], n, d[1], d[2], None)),
+                             read=(1, 2))
+        return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1)
+
+    def accumulate_paths(self, results, film, first_pixel=0, index=None, pixels=None, history=None):
+        """ptss_accumulate_paths: the samples of `results` added to the film, the touched pixels resolved.
+        numpy: results (N,) PATH_RESULT_DTYPE or (N, 4) float32; film (P,) FILM_DTYPE or (P, 4) uint32 (not modified); pixels / history:
+        None (NULL), True (zeros beforehand) or the buffer's content beforehand -> (film afterwards (P,) FILM_DTYPE, pixels (P, 4) uint8
+        or None, history (P,) HISTORY_DTYPE or None). torch: results (N, 4) float32, film (P, 4) int32 UPDATED IN PLACE, index (N,) int32
+        or None, pixels (P, 4) uint8 or None, history (P, 4) float32 or None, all on one device -> None, on the current stream."""
+        L = device_lib()
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_film = self._torch_ptr(film, "film", "int32", 4, dev)
+            P = film.shape[0]
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
+            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
+            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_accumulate_paths(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, P, d_px, d_hs, C.c_void_p(stream)))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        idx = _film_index(index, n)
+        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
+        P = len(f)
+        px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
+        hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True
+                                           else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+        if (px is not None and len(px) != P) or (hs is not None and len(hs) != P):
+            raise ValueError("pixels and history: one entry per film pixel")
+        if n == 0:
+            _check(L.ptss_accumulate_paths(self._ctx, None, None, int(first_pixel), 0, None, P, None, None, None))
+        else:
+            self._round_trip([r, idx, f, px, hs],
+                             lambda d: _check(L.ptss_accumulate_paths(self._ctx, d[0], d[1], int(first_pixel), n, d[2], P, d[3], d[4], None)),
+                             read=(2, 3, 4))
+        return f.view(FILM_DTYPE).reshape(-1), px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+    def ray_features(self, rays):
+        """ptss_ray_features: the first-hit feature row of every ray. rays: (N, 8) float32 or (N,) RAY_DTYPE -> (N,) FEATURE_DTYPE; or
+        a contiguous (N, 8) float32 device tensor -> an (N, 8) float32 tensor (word 7 holds the bits of materialIdx), on the current
+        stream."""
+        L = device_lib()
+        if type(rays).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            d_rays = self._torch_ptr(rays, "rays", "float32", 8)
+            n = rays.shape[0]
+            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            _check(L.ptss_ray_features(self._ctx, d_rays, C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
+            return out
+        a = _rows(rays, RAY_DTYPE, 8, np.float32, "rays")
+        n = len(a)
+        out = np.zeros(n, dtype=FEATURE_DTYPE)
+        if n == 0:
+            _check(L.ptss_ray_features(self._ctx, None, None, 0, None))
+        else:
+            self._round_trip([a, out], lambda d: _check(L.ptss_ray_features(self._ctx, d[0], d[1], n, None)), read=(1,))
+        return out
+
+    def film_launches(self):
+        """ptss_film_launches: (generate_rays, accumulate_paths, ray_features calls that launched since the context was created)."""
+        out = (C.c_ulonglong * 3)()
+        _check(device_lib().ptss_film_launches(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def film_rejected(self):
+        """ptss_film_rejected: the index entries the film calls dropped since the context was created (synchronises)."""
+        out = C.c_ulonglong(0)
+        _check(device_lib().ptss_film_rejected(self._ctx, C.byref(out)))
+        return int(out.value)
 
     # --- first-hit features and the denoiser (ptss_render_features / ptss_denoise) ---------------------
     def _device_buffer(self, name, nbytes):

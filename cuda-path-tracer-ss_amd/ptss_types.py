@@ -98,6 +98,21 @@ PATH_RNG_DTYPE = np.dtype([("v", np.uint32, 5), ("d", np.uint32)])
 PATH_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("bounces", np.uint32)])
 
 
+class FilmCamera(C.Structure):   # ptss_film_camera: the camera model of a film (ptss_generate_rays)
+    _fields_ = [("structSize", C.c_uint), ("kind", C.c_int), ("camera", Camera), ("width", C.c_int), ("height", C.c_int),
+                ("lensRadius", C.c_float), ("focusDistance", C.c_float), ("jitter", C.c_int)]
+
+
+FILM_PINHOLE, FILM_THIN_LENS, FILM_EQUIRECT = 0, 1, 2   # PTSS_FILM_*
+
+
+class FilmEntry(C.Structure):   # ptss_film_entry: the 8-bit sample sums of one film pixel and their count
+    _fields_ = [("r", C.c_uint32), ("g", C.c_uint32), ("b", C.c_uint32), ("samples", C.c_uint32)]
+
+
+FILM_DTYPE = np.dtype([("r", np.uint32), ("g", np.uint32), ("b", np.uint32), ("samples", np.uint32)])
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -140,6 +155,8 @@ assert C.sizeof(RayQuery) == 32 and C.sizeof(RayHit) == 48 and C.sizeof(PixelFea
 assert C.sizeof(PixelMotion) == 16 and PixelMotion.surface.offset == 12
 assert C.sizeof(PathRng) == 24 == PATH_RNG_DTYPE.itemsize and PathRng.d.offset == 20 == PATH_RNG_DTYPE.fields["d"][1]
 assert C.sizeof(PathResult) == 16 == PATH_RESULT_DTYPE.itemsize and PathResult.bounces.offset == 12 == PATH_RESULT_DTYPE.fields["bounces"][1]
+assert C.sizeof(FilmCamera) == 68 and FilmCamera.camera.offset == 8 and FilmCamera.width.offset == 48 and FilmCamera.jitter.offset == 64
+assert C.sizeof(FilmEntry) == 16 == FILM_DTYPE.itemsize and FilmEntry.samples.offset == 12 == FILM_DTYPE.fields["samples"][1]
 
 
 def struct_to_dict(s):

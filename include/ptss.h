@@ -269,6 +269,63 @@ int ptss_trace_paths(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_pat
                      size_t n, unsigned int maxIterations, void* hipStream);
 int ptss_path_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] scene read in place, [1] staged in LDS */
 
+/* The film of a path query: eye rays made on the device, samples accumulated as a frame accumulates them, features
+ * of arbitrary rays. A film is film->width x film->height pixels of its own (independent of the context's frame), pixel
+ * p = (x, y) = (p % width, p / width), row 0 at the bottom.
+ *
+ * ptss_generate_rays: dev_rays[i] = the eye ray of film pixel p = dev_index ? dev_index[i] : firstPixel + i, made from stream dev_rng[i],
+ * which is stored back advanced by the model's draws (uniforms of (0, 1], curand_uniform's). csrc/ptcamera.h fixes every operation and
+ * its order; its host build (ptss_probe_film_rays, ptss_host.h) is the specification and the device agrees with it byte for byte.
+ * With s = -2 tan(fov / 2), aspect = H / W, invW = 1 / W, invH = 1 / H evaluated once on the host, X = x + jx, Y = y + jy and
+ * start = (((X invW) - 0.5) s, ((Y invH) - 0.5) s aspect, 1) zNear:
+ *   PTSS_FILM_PINHOLE    draws jx, jy (computeEyeRaysKernel's order). origin = position, direction = normalize(rotate(rotation, start)):
+ *                        ptss_camera_ray(camera, width, height, x, y, jx, jy), bit for bit.
+ *   PTSS_FILM_THIN_LENS  draws jx, jy, u1, u2. Focus point f = start * (focusDistance / |start.z|) (camera space, on the plane
+ *                        |z| = focusDistance); lens point l = lensRadius sqrt(u1) (cos 2 pi u2, sin 2 pi u2, 0);
+ *                        origin = position + rotate(rotation, l), direction = normalize(rotate(rotation, f - l)). At lensRadius = 0 the
+ *                        rays are a pinhole's up to rounding, not bit for bit.
+ *   PTSS_FILM_EQUIRECT   draws jx, jy. lon = ((X invW) - 0.5) 2 pi, lat = ((Y invH) - 0.5) pi, camera-space direction
+ *                        (sin lon cos lat, sin lat, -cos lon cos lat), rotated and normalised; origin = position. The film's centre looks
+ *                        along rotate(rotation, (0, 0, -1)), where the centre ray of the reference's pinhole cameras (zNear < 0) looks, and
+ *                        +x, +y have the pinhole's senses. fieldOfView and zNear are not read.
+ * jitter = 0: no draw is made and no stream is read or written (dev_rng must still be given): jx = jy = 0.5 and the lens point is the
+ * lens centre. Every ray has
+ * tmax = +inf, pad = 0. An index entry >= width * height writes no ray, leaves its stream as it is and is counted.
+ *
+ * ptss_accumulate_paths: for ray i, pixel p as above, the three channels of dev_results[i].radiance go through the frame's own 8-bit tone map
+ * (writeToPixelsKernel, CudaTracer.cu:72-85, in the table form a frame uses, with the context's thresholds; NaN gives 0, +inf 255) and
+ * are added to dev_film[p].r, .g, .b; .samples grows by 1. Then, for every pixel touched, with inv = 1.f / (float)samples:
+ * dev_pixels[p] = {(unsigned char)(r * inv + 0.5f), .. g, .. b, 255} (may be NULL) and dev_history[p] = {(float)r * inv, .. g, .. b,
+ * (float)samples} (may be NULL): the display pixel of a frame and the entry ptss_denoise_history, ptss_reproject and ptss_upsample take.
+ * Without an index every ray has a pixel of its own: one kernel, a plain read-modify-write. With an index several rays may share a
+ * pixel: the sums are integer atomics, order-free and exact, and the touched pixels are resolved by a second launch behind the first.
+ * Index entries >= filmPixels are dropped and counted. The caller zero-fills a new film; samples must stay below 2^24 (exact as a float).
+ * A pinhole film of the context's size, fed ptss_seed_path_rng(seed, 0, skip = 0) streams and run generate -> ptss_trace_paths ->
+ * accumulate once per frame, reproduces the frame loop's accumulator, display pixels and stream states bit for bit, frame after frame,
+ * under ptss_trace_paths' condition (the frame's loop guard never fires).
+ *
+ * ptss_ray_features: dev_features[i] = what ptss_render_features documents, for ray i: ptss_intersect's normal, distance and materialIdx
+ * with tmax = +inf (the row's tmax is ignored), that material's diffuseColor; the same miss row. Of jitter = 0 rays it is the feature
+ * buffer of a film.
+ *
+ * All three are asynchronous on hipStream (NULL: the context's stream), read the scene image at most, leave no trace in frame state and
+ * serve sharded contexts. Refused without touching the device and without counting: a null context, a null required pointer with n > 0,
+ * a wrong structSize, an unknown kind, a jitter other than 0 or 1, a film size that is not positive, a thin lens with lensRadius < 0,
+ * focusDistance <= 0 or either not finite, a pointer that is not aligned — 16 bytes for rays, results, film, features and history, 4 for
+ * streams, indices and pixels — (PTSS_EINVAL); n >= 2^31, width * height (filmPixels) >= 2^31, or, without an index, firstPixel + n
+ * above the film's pixels (PTSS_ERANGE). n = 0 returns PTSS_OK.
+ * No kernel here owns a bit of ptss_launched_kernels, which these calls leave as it is. ptss_film_launches: the calls of each kind that
+ * launched since ptss_create. ptss_film_rejected: the index entries dropped since ptss_create; it synchronises with the latest call that
+ * took an index. */
+int ptss_generate_rays(ptss_context* ctx, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index /* may be NULL */, size_t n,
+                       ptss_path_rng* dev_rng /* in/out */, ptss_ray_query* dev_rays, void* hipStream);
+int ptss_accumulate_paths(ptss_context* ctx, const ptss_path_result* dev_results, const uint32_t* dev_index /* may be NULL */, size_t firstPixel,
+                          size_t n, ptss_film_entry* dev_film, size_t filmPixels, ptss_uchar4* dev_pixels /* may be NULL */,
+                          ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_ray_features(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_pixel_feature* dev_features, size_t n, void* hipStream);
+int ptss_film_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] generate, [1] accumulate, [2] features */
+int ptss_film_rejected(ptss_context* ctx, unsigned long long* out);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

@@ -171,6 +171,19 @@ int ptss_probe_rng_init(unsigned long long seed, unsigned int subsequence, unsig
 int ptss_probe_rng_draw(unsigned int* state6, unsigned int* raw, float* uni, size_t n);
 /* The 32 subsequence jump matrices A^(2^(67+k)) as 32*160*5 words (images of unit vectors). */
 int ptss_probe_rng_jump_table(unsigned int* out, size_t words);
+/* ptss_generate_rays on the host (csrc/ptcamera.h — the very operations the kernel evaluates, in their order; this build is the
+ * specification): rays[i] = the eye ray of film pixel index ? index[i] : firstPixel + i from stream rng[i], advanced in place by the
+ * model's draws (pinhole 2, thin lens 4, equirect 2; jitter = 0: none). An index entry >= width * height writes nothing and is counted
+ * in *rejected (may be NULL; set, not added to). PTSS_HOST_EINVAL: whatever ptss_generate_rays refuses, alignment aside. */
+int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index /* may be NULL */, size_t n,
+                         ptss_path_rng* rng /* in/out */, ptss_ray_query* rays, unsigned long long* rejected);
+/* ptss_accumulate_paths on the host, with the LITERAL tone map (csrc/ptquant.h quantize_literal; CudaTracer.cu:72-85): the sums of all
+ * n rays first, duplicates included, then every touched pixel resolved into pixels and history (each may be NULL) from its final sums.
+ * *rejected (may be NULL; set, not added to): index entries >= filmPixels. PTSS_HOST_EINVAL: whatever ptss_accumulate_paths refuses,
+ * alignment aside. */
+int ptss_probe_accumulate(const ptss_path_result* results, const uint32_t* index /* may be NULL */, size_t firstPixel, size_t n,
+                          ptss_film_entry* film, size_t filmPixels, ptss_uchar4* pixels, ptss_history_entry* history,
+                          unsigned long long* rejected);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,31 @@ typedef struct ptss_path_result {
     uint32_t bounces;
 } ptss_path_result;
 
+/* The camera of a film (ptss_generate_rays): which model makes the eye ray of a film pixel, and from what.
+ * kind: PTSS_FILM_*; camera: position and rotation for every model, zNear and fieldOfView for the pinhole and the thin lens only;
+ * width, height: the film's own size, independent of any context's; lensRadius >= 0, focusDistance > 0: the thin lens only;
+ * jitter: 1 draws the sample position (and the lens point) from the ray's stream, 0 draws nothing (pixel centre, lens centre). */
+typedef struct ptss_film_camera {
+    unsigned int structSize; /* sizeof(ptss_film_camera) as the caller compiled it */
+    int kind;
+    ptss_camera camera;
+    int width, height;
+    float lensRadius;
+    float focusDistance;
+    int jitter;
+} ptss_film_camera;
+
+#define PTSS_FILM_PINHOLE 0
+#define PTSS_FILM_THIN_LENS 1
+#define PTSS_FILM_EQUIRECT 2
+
+/* One pixel of a film (ptss_accumulate_paths): the sums of the tone-mapped 8-bit samples (writeToPixelsKernel's totalPixelColors entry)
+ * and how many there are. 16 B, 16-byte aligned access; a new film is all zero; samples < 2^24. */
+typedef struct ptss_film_entry {
+    uint32_t r, g, b;
+    uint32_t samples;
+} ptss_film_entry;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -232,6 +257,10 @@ static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, w
 static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
 static_assert(sizeof(ptss_path_rng) == 24 && offsetof(ptss_path_rng, d) == 20, "ptss_path_rng is six 32-bit words: v[0..4], d");
 static_assert(sizeof(ptss_path_result) == 16 && offsetof(ptss_path_result, bounces) == 12, "ptss_path_result is one 16-byte row");
+static_assert(sizeof(ptss_film_camera) == 68 && offsetof(ptss_film_camera, camera) == 8 && offsetof(ptss_film_camera, width) == 48 &&
+                  offsetof(ptss_film_camera, lensRadius) == 56 && offsetof(ptss_film_camera, jitter) == 64,
+              "ptss_film_camera is seventeen 32-bit words");
+static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, samples) == 12, "ptss_film_entry is one 16-byte row");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -246,6 +275,10 @@ _Static_assert(sizeof(ptss_history_entry) == 16 && offsetof(ptss_history_entry, 
 _Static_assert(sizeof(ptss_pixel_motion) == 16 && offsetof(ptss_pixel_motion, surface) == 12, "ptss_pixel_motion is one 16-byte row");
 _Static_assert(sizeof(ptss_path_rng) == 24 && offsetof(ptss_path_rng, d) == 20, "ptss_path_rng is six 32-bit words: v[0..4], d");
 _Static_assert(sizeof(ptss_path_result) == 16 && offsetof(ptss_path_result, bounces) == 12, "ptss_path_result is one 16-byte row");
+_Static_assert(sizeof(ptss_film_camera) == 68 && offsetof(ptss_film_camera, camera) == 8 && offsetof(ptss_film_camera, width) == 48 &&
+                   offsetof(ptss_film_camera, lensRadius) == 56 && offsetof(ptss_film_camera, jitter) == 64,
+               "ptss_film_camera is seventeen 32-bit words");
+_Static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, samples) == 12, "ptss_film_entry is one 16-byte row");
 #endif
 
 #ifdef __cplusplus
