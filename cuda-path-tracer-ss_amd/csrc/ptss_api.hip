@@ -145,6 +145,9 @@ struct ptss_context {
     unsigned long long upsampleLaunches = 0;                  // ptss_upsample launches
     unsigned long long pathLaunches[2] = {0, 0};              // ptss_trace_paths launches: [0] in place, [1] in LDS
     uint32_t* dPathJumpTable = nullptr;                       // ptss_seed_path_rng's 2^67 jump table, uploaded by its first launching call
+    unsigned long long refillLaunches[2] = {0, 0};            // ptss_trace_paths_opt launches with PTSS_PATHS_REFILL: [0] in place, [1] in LDS
+    unsigned long long* dPathRefill = nullptr;                // their queue head and counters (ptss_device.h launchPathRefill), allocated by the first
+    hipStream_t refillStream = nullptr;                       // the stream of the latest of them (ptss_path_refill_stats synchronises on it)
     unsigned long long filmLaunches[3] = {0, 0, 0};           // ptss_generate_rays, ptss_accumulate_paths, ptss_ray_features calls that launched
     hipStream_t filmStream = nullptr;                         // the stream of the latest film call with an index (ptss_film_rejected synchronises on it)
     bool filmIndexed = false;
@@ -760,6 +763,7 @@ int ptss_destroy(ptss_context* c) {
     for (float4* plane : c->dDenoise) (void)hipFree(plane);
     ptss::releaseResortScratch(c->resortScratch);
     (void)hipFree(c->dPathJumpTable);
+    (void)hipFree(c->dPathRefill);
     delete c;
     return PTSS_OK;
 }
@@ -1189,11 +1193,13 @@ int ptss_seed_path_rng(ptss_context* c, ptss_path_rng* dev_rng, size_t n, unsign
     return PTSS_OK;
 }
 
-// ptss_trace_paths: the queries' scene image (images[0], exact for every ray), the scene's guard flags and default colour, no frame state
-int ptss_trace_paths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng, ptss_path_result* dev_results, size_t n,
-                     unsigned int maxIterations, void* hipStream) {
+// ptss_trace_paths / ptss_trace_paths_opt: the queries' scene image (images[0], exact for every ray), the scene's guard flags and default
+// colour, no frame state. options == nullptr: ptss_trace_paths itself
+static int tracePaths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng, ptss_path_result* dev_results, size_t n,
+                      unsigned int maxIterations, const ptss_path_options* options, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (maxIterations < 1u || maxIterations > (unsigned)ptss::kMaxBounces) return fail(PTSS_EINVAL, "maxIterations must be in [1, 64]");
+    const bool refill = options && options->schedule == PTSS_PATHS_REFILL;
     if (n == 0) return PTSS_OK;
     if (!dev_rays || !dev_rng || !dev_results) return fail(PTSS_EINVAL, "null buffer with n > 0");
     if ((((uintptr_t)dev_rays | (uintptr_t)dev_results) & 15u) || ((uintptr_t)dev_rng & 3u))
@@ -1204,8 +1210,62 @@ int ptss_trace_paths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_
     HIP_TRY(hipSetDevice(c->cfg.device));
     hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
-    HIP_TRY(ptss::launchPathQuery(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_rng, dev_results, (uint32_t)n, (int)maxIterations, defaultColor,
-                                  im.guardFlags, c->gridCap * ptss::kShards, c->pathLaunches));
+    if (!refill) {
+        HIP_TRY(ptss::launchPathQuery(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_rng, dev_results, (uint32_t)n, (int)maxIterations, defaultColor,
+                                      im.guardFlags, c->gridCap * ptss::kShards, c->pathLaunches));
+        return PTSS_OK;
+    }
+    if (!c->dPathRefill) {   // the head and the counters: zero from here on, in stream order with this and every later refill call
+        unsigned long long* d = nullptr;
+        HIP_TRY(hipMalloc(&d, ptss::kPathRefillWords * sizeof(unsigned long long)));
+        const hipError_t e = hipMemsetAsync(d, 0, ptss::kPathRefillWords * sizeof(unsigned long long), st);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            return fail(PTSS_EHIP, "clearing the refill counters", e);
+        }
+        c->dPathRefill = d;
+    }
+    c->refillStream = st;
+    HIP_TRY(ptss::launchPathRefill(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_rng, dev_results, (uint32_t)n, (int)maxIterations, defaultColor,
+                                   im.guardFlags, options->maxWorkgroups, c->numCUs, c->dPathRefill, c->refillLaunches));
+    return PTSS_OK;
+}
+
+int ptss_trace_paths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng, ptss_path_result* dev_results, size_t n,
+                     unsigned int maxIterations, void* hipStream) {
+    return tracePaths(c, dev_rays, dev_rng, dev_results, n, maxIterations, nullptr, hipStream);
+}
+
+int ptss_default_path_options(ptss_path_options* o) {
+    if (!o) return fail(PTSS_EINVAL, "options is null");
+    o->structSize = (unsigned int)sizeof(ptss_path_options);
+    o->schedule = PTSS_PATHS_LANE_PER_RAY;
+    o->maxWorkgroups = 0;
+    o->reserved = 0;
+    return PTSS_OK;
+}
+
+int ptss_trace_paths_opt(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng, ptss_path_result* dev_results, size_t n,
+                         unsigned int maxIterations, const ptss_path_options* options, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!options) return fail(PTSS_EINVAL, "options is null");
+    if (options->structSize != sizeof(ptss_path_options)) return fail(PTSS_EINVAL, "options->structSize is not sizeof(ptss_path_options)");
+    if (options->schedule != PTSS_PATHS_LANE_PER_RAY && options->schedule != PTSS_PATHS_REFILL) return fail(PTSS_EINVAL, "unknown schedule");
+    if (options->maxWorkgroups < 0) return fail(PTSS_EINVAL, "maxWorkgroups must not be negative");
+    if (options->reserved != 0) return fail(PTSS_EINVAL, "reserved must be 0");
+    return tracePaths(c, dev_rays, dev_rng, dev_results, n, maxIterations, options, hipStream);
+}
+
+// [0], [1]: host counts; [2..4]: the device counters, behind everything the latest refill call's stream holds
+int ptss_path_refill_stats(ptss_context* c, unsigned long long* out5) {
+    if (!c || !out5) return fail(PTSS_EINVAL, "null argument");
+    out5[0] = c->refillLaunches[0];
+    out5[1] = c->refillLaunches[1];
+    out5[2] = out5[3] = out5[4] = 0;
+    if (!c->dPathRefill) return PTSS_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->refillStream));
+    HIP_TRY(hipMemcpy(out5 + 2, c->dPathRefill + 1, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }
 

@@ -191,6 +191,14 @@ hipError_t launchFeaturesSpecular(hipStream_t st, const float4* sceneBlob, Scene
 hipError_t launchPathRngSeed(hipStream_t st, void* rng, uint32_t n, uint64_t seed, uint32_t firstSequence, uint32_t skip, const uint32_t* jumpTable);
 hipError_t launchPathQuery(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* rng, void* out,
                            uint32_t n, int maxIterations, ptss_vec3 defaultColor, uint32_t guardFlags, int maxBlocks, unsigned long long* launches);
+// ... with the refill schedule (ptss_trace_paths_opt, PTSS_PATHS_REFILL): the same buffers and bytes. maxWorkgroups >= 0 caps
+// the grid (0: the resident workgroups of the instantiation on numCUs compute units). state: kPathRefillWords 64-bit device words of the
+// context, [0] the queue head, set on `st` in front of the kernel, [1..3] wave iterations, lane iterations, dequeues (cumulative). Its own
+// launches[0] / launches[1]
+constexpr int kPathRefillWords = 4;
+hipError_t launchPathRefill(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* rng, void* out,
+                            uint32_t n, int maxIterations, ptss_vec3 defaultColor, uint32_t guardFlags, int maxWorkgroups, int numCUs,
+                            unsigned long long* state, unsigned long long* launches);
 // the film of a path query (ptss_film.hip; ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features): index = n uint32 or nullptr (then
 // pixel firstPixel + i, and firstPixel + n <= the film's pixels), rng = n x 24 B, rays = n x 32 B, results = n x 16 B, film = filmPixels x 16 B
 // (ptss_film_entry), pixels / history = filmPixels entries or nullptr, features = n x 32 B. rejected: the device counter of dropped index

@@ -28,6 +28,7 @@
 //                                   --size film, streams from ptss_seed_path_rng(--seed); --keys move the camera before the first tick.
 //                                   pinhole writes the frame loop's image (while that loop's guard stays silent). With --denoise:
 //                                   image_denoised.tga through ptss_ray_features and ptss_denoise_history
+//             [--refill]            with --film: the trace through ptss_trace_paths_opt with PTSS_PATHS_REFILL (the same bytes)
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -52,6 +53,7 @@ int main(int argc, char* argv[]) {
     int upscale = 0;   // --upscale: 0 absent, else the factor
     std::string film;  // --film: the camera model, empty = the frame loop
     float lensRadius = 0.05f, focusDistance = 5.0f;   // --lens
+    bool refill = false;   // --refill: the film's trace with the refill schedule
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -80,6 +82,7 @@ int main(int argc, char* argv[]) {
         else if (a == "--temporal") temporal = true;
         else if (a == "--upscale") upscale = atoi(next());
         else if (a == "--film") film = next();
+        else if (a == "--refill") refill = true;
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -128,6 +131,7 @@ int main(int argc, char* argv[]) {
                         "--temporal, --upscale, --specular-features\n");
         return 2;
     }
+    if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -231,6 +235,9 @@ int main(int argc, char* argv[]) {
         fc.lensRadius = lensRadius;
         fc.focusDistance = focusDistance;
         fc.jitter = 1;
+        ptss_path_options pathOptions;
+        PTSS_HANDLE(ptss_default_path_options(&pathOptions));
+        if (refill) pathOptions.schedule = PTSS_PATHS_REFILL;
         const size_t n = (size_t)width * (size_t)height;
         void *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dFilm = nullptr, *dHist = nullptr, *dFeat = nullptr, *dOut = nullptr;
         const bool filter = denoise != -2;
@@ -245,7 +252,8 @@ int main(int argc, char* argv[]) {
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
             PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
-            PTSS_HANDLE(ptss_trace_paths(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, NULL));
+            PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
+                                             NULL));
             PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
                                               (ptss_history_entry*)dHist, NULL));
         }

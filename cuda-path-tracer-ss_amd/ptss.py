@@ -12,7 +12,8 @@ import os
 
 import numpy as np
 
-from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, SCENE_LAYOUT_FIELDS,
+from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, PATHS_LANE_PER_RAY, PATHS_REFILL,
+                        PathOptions, SCENE_LAYOUT_FIELDS,
                         SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 
@@ -259,6 +260,9 @@ def device_lib():
         L.ptss_seed_path_rng.argtypes = [vp, vp, C.c_size_t, C.c_ulonglong, C.c_ulonglong, C.c_uint, vp]
         L.ptss_trace_paths.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint, vp]
         L.ptss_path_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_path_options.argtypes = [C.POINTER(PathOptions)]
+        L.ptss_trace_paths_opt.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint, C.POINTER(PathOptions), vp]
+        L.ptss_path_refill_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_generate_rays.argtypes = [vp, C.POINTER(FilmCamera), C.c_size_t, vp, C.c_size_t, vp, vp, vp]
         L.ptss_accumulate_paths.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
         L.ptss_ray_features.argtypes = [vp, vp, vp, C.c_size_t, vp]
@@ -471,6 +475,18 @@ HISTORY_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32
 assert HISTORY_DTYPE.itemsize == C.sizeof(HistoryEntry)
 MOTION_DTYPE = np.dtype([("prevPoint", np.float32, 3), ("surface", np.int32)])
 assert MOTION_DTYPE.itemsize == C.sizeof(PixelMotion)
+
+
+# ---- the schedule of a path query (ptss_trace_paths_opt) ----
+def path_options(schedule=PATHS_LANE_PER_RAY, max_workgroups=0):
+    """A ptss_path_options. schedule: PATHS_LANE_PER_RAY, PATHS_REFILL or "lane_per_ray" / "refill"; max_workgroups: the refill grid's
+    cap, 0 = the library's choice."""
+    o = PathOptions()
+    o.structSize = C.sizeof(PathOptions)
+    o.schedule = {"lane_per_ray": PATHS_LANE_PER_RAY, "refill": PATHS_REFILL}.get(schedule, schedule)
+    o.maxWorkgroups = int(max_workgroups)
+    o.reserved = 0
+    return o
 
 
 # ---- the film of a path query (ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features; DESIGN.md §3.26) ----
@@ -1182,13 +1198,20 @@ class Renderer:
             H.hipFree(d)
         return out
 
-    def trace_paths(self, rays, rng, max_iterations):
-        """ptss_trace_paths: radiance along the caller's rays. rays: (N, 8) float32 or (N,) RAY_DTYPE (tmax is ignored); rng: (N,)
+    def trace_paths(self, rays, rng, max_iterations, schedule=None, max_workgroups=0):
+        """ptss_trace_paths: radiance along the caller's rays. schedule: None (ptss_trace_paths itself) or PATHS_LANE_PER_RAY /
+        PATHS_REFILL / their names (ptss_trace_paths_opt with max_workgroups; the refill calls of one context are ordered by the caller).
+        rays: (N, 8) float32 or (N,) RAY_DTYPE (tmax is ignored); rng: (N,)
         PATH_RNG_DTYPE or (N, 6) uint32, one stream per ray -> ((N,) PATH_RESULT_DTYPE, (N,) PATH_RNG_DTYPE: the streams afterwards,
         to be handed to the next call). Or torch: rays a contiguous (N, 8) float32 device tensor and rng a contiguous (N, 6) int32
         tensor on the same device, which is UPDATED IN PLACE -> an (N, 4) float32 tensor (radiance; column 3 holds the bits of
         `bounces`), on the current stream."""
         L = device_lib()
+        if schedule is None:
+            trace = lambda a, b, c, count, stream: L.ptss_trace_paths(self._ctx, a, b, c, count, int(max_iterations), stream)
+        else:
+            options = path_options(schedule, max_workgroups)
+            trace = lambda a, b, c, count, stream: L.ptss_trace_paths_opt(self._ctx, a, b, c, count, int(max_iterations), C.byref(options), stream)
         if type(rays).__module__.split(".")[0] == "torch":
             import sys
             torch = sys.modules["torch"]
@@ -1200,8 +1223,7 @@ class Renderer:
                 raise ValueError("rng: a contiguous (N, 6) int32 tensor on the rays' device")
             out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
             stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(L.ptss_trace_paths(self._ctx, C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), C.c_void_p(out.data_ptr()), n,
-                                      int(max_iterations), C.c_void_p(stream)))
+            _check(trace(C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
             return out
         a = np.asarray(rays)
         if a.dtype == RAY_DTYPE:
@@ -1219,7 +1241,7 @@ class Renderer:
         out = np.empty(n, dtype=PATH_RESULT_DTYPE)
         after = np.empty(n, dtype=PATH_RNG_DTYPE)
         if n == 0:
-            _check(L.ptss_trace_paths(self._ctx, None, None, None, 0, int(max_iterations), None))
+            _check(trace(None, None, None, 0, None))
             return out, after
         H = _hip_lib()
         _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
@@ -1229,7 +1251,7 @@ class Renderer:
                 _hip_check(H.hipMalloc(C.byref(b), nbytes), "hipMalloc")
             _hip_check(H.hipMemcpy(bufs[0], a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
             _hip_check(H.hipMemcpy(bufs[1], s.ctypes.data, s.nbytes, 1), "hipMemcpy")
-            _check(L.ptss_trace_paths(self._ctx, bufs[0], bufs[1], bufs[2], n, int(max_iterations), None))
+            _check(trace(bufs[0], bufs[1], bufs[2], n, None))
             self.synchronize()
             _hip_check(H.hipMemcpy(out.ctypes.data, bufs[2], out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
             _hip_check(H.hipMemcpy(after.ctypes.data, bufs[1], after.nbytes, 2), "hipMemcpy")
@@ -1244,6 +1266,13 @@ class Renderer:
         out = (C.c_ulonglong * 2)()
         _check(device_lib().ptss_path_launches(self._ctx, out))
         return int(out[0]), int(out[1])
+
+    def path_refill_stats(self):
+        """ptss_path_refill_stats: (refill launches with the scene image read in place, staged in LDS, wave iterations, lane iterations,
+        dequeues) since the context was created; synchronises with the stream of the latest refill call."""
+        out = (C.c_ulonglong * 5)()
+        _check(device_lib().ptss_path_refill_stats(self._ctx, out))
+        return tuple(int(v) for v in out)
 
     # --- the film of a path query (ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features) ------------------
     def _round_trip(self, arrays, call, read):

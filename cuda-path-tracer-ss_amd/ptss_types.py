@@ -98,6 +98,13 @@ PATH_RNG_DTYPE = np.dtype([("v", np.uint32, 5), ("d", np.uint32)])
 PATH_RESULT_DTYPE = np.dtype([("radiance", np.float32, 3), ("bounces", np.uint32)])
 
 
+class PathOptions(C.Structure):   # ptss_path_options: how ptss_trace_paths_opt schedules a batch
+    _fields_ = [("structSize", C.c_uint), ("schedule", C.c_int), ("maxWorkgroups", C.c_int), ("reserved", C.c_int)]
+
+
+PATHS_LANE_PER_RAY, PATHS_REFILL = 0, 1   # PTSS_PATHS_*
+
+
 class FilmCamera(C.Structure):   # ptss_film_camera: the camera model of a film (ptss_generate_rays)
     _fields_ = [("structSize", C.c_uint), ("kind", C.c_int), ("camera", Camera), ("width", C.c_int), ("height", C.c_int),
                 ("lensRadius", C.c_float), ("focusDistance", C.c_float), ("jitter", C.c_int)]

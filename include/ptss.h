@@ -269,6 +269,28 @@ int ptss_trace_paths(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_pat
                      size_t n, unsigned int maxIterations, void* hipStream);
 int ptss_path_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] scene read in place, [1] staged in LDS */
 
+/* ptss_trace_paths with a choice of schedule. ptss_default_path_options: structSize, PTSS_PATHS_LANE_PER_RAY, 0, 0.
+ * PTSS_PATHS_LANE_PER_RAY: the call IS ptss_trace_paths (the same launch, counted in ptss_path_launches).
+ * PTSS_PATHS_REFILL: a lane whose path has ended takes the next unclaimed ray of the batch from a device-side queue, so a wave no longer
+ * runs dead lanes until the longest of its 64 paths has ended. Every output byte, results and streams, is what ptss_trace_paths writes
+ * for the same inputs, for every input and every maxWorkgroups. It pays on small scenes with long paths (DESIGN.md §3.27 has the
+ * measurements); the default stays LANE_PER_RAY. maxWorkgroups caps the grid (0: as many workgroups as the device holds at once); a
+ * small cap leaves part of the device to frames running beside the query.
+ * ORDERING: the queue's head is one device word of the context, set on hipStream in front of the kernel. The PTSS_PATHS_REFILL calls of
+ * one context must therefore be ordered among themselves by the caller — the same stream, or an event or a synchronise between two
+ * streams (the rule of ptss_denoise's planes and ptss_resort_triangles' scratch). Plain ptss_trace_paths calls, queries, feature passes
+ * and frames may run beside a refill call on other streams. The first refill call of a context allocates the word (hipMalloc).
+ * Refused with PTSS_EINVAL / PTSS_ERANGE without touching the device and without counting: everything ptss_trace_paths refuses, a null
+ * options, a wrong structSize, an unknown schedule, a negative maxWorkgroups, a non-zero reserved. n = 0 returns PTSS_OK, nothing launched.
+ * Refill launches are not counted in ptss_path_launches and own no bit of ptss_launched_kernels. ptss_path_refill_stats, since
+ * ptss_create: out5[0] refill launches with the scene image read in place, [1] staged in LDS (host counts); [2] wave iterations (the
+ * iterations the waves ran), [3] lane iterations (the live lanes summed over them = the sum of .bounces), [4] dequeues (device counts:
+ * the call synchronises with the stream of the latest refill call). [3] / (64 [2]) is the lane occupancy. */
+int ptss_default_path_options(ptss_path_options* options);
+int ptss_trace_paths_opt(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_path_rng* dev_rng /* in/out */, ptss_path_result* dev_results,
+                         size_t n, unsigned int maxIterations, const ptss_path_options* options, void* hipStream);
+int ptss_path_refill_stats(ptss_context* ctx, unsigned long long* out5);
+
 /* The film of a path query: eye rays made on the device, samples accumulated as a frame accumulates them, features
  * of arbitrary rays. A film is film->width x film->height pixels of its own (independent of the context's frame), pixel
  * p = (x, y) = (p % width, p / width), row 0 at the bottom.

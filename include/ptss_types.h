@@ -186,6 +186,17 @@ typedef struct ptss_path_result {
     uint32_t bounces;
 } ptss_path_result;
 
+/* How ptss_trace_paths_opt schedules a batch (ptss_default_path_options fills it in). */
+#define PTSS_PATHS_LANE_PER_RAY 0 /* ptss_trace_paths' schedule: one lane per ray for the ray's whole life */
+#define PTSS_PATHS_REFILL 1       /* a lane whose path has ended takes the next unclaimed ray of the batch */
+typedef struct ptss_path_options {
+    unsigned int structSize; /* sizeof(ptss_path_options) as the caller compiled it */
+    int schedule;            /* PTSS_PATHS_* */
+    int maxWorkgroups;       /* REFILL: cap on the grid, 0 = the library's choice (the resident workgroups); >= 0. Also the way to leave
+                                part of the device to frames running beside the query. LANE_PER_RAY: not read */
+    int reserved;            /* 0 */
+} ptss_path_options;
+
 /* The camera of a film (ptss_generate_rays): which model makes the eye ray of a film pixel, and from what.
  * kind: PTSS_FILM_*; camera: position and rotation for every model, zNear and fieldOfView for the pinhole and the thin lens only;
  * width, height: the film's own size, independent of any context's; lensRadius >= 0, focusDistance > 0: the thin lens only;
@@ -261,6 +272,9 @@ static_assert(sizeof(ptss_film_camera) == 68 && offsetof(ptss_film_camera, camer
                   offsetof(ptss_film_camera, lensRadius) == 56 && offsetof(ptss_film_camera, jitter) == 64,
               "ptss_film_camera is seventeen 32-bit words");
 static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, samples) == 12, "ptss_film_entry is one 16-byte row");
+static_assert(sizeof(ptss_path_options) == 16 && offsetof(ptss_path_options, schedule) == 4 && offsetof(ptss_path_options, maxWorkgroups) == 8 &&
+                  offsetof(ptss_path_options, reserved) == 12,
+              "ptss_path_options is four 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -279,6 +293,9 @@ _Static_assert(sizeof(ptss_film_camera) == 68 && offsetof(ptss_film_camera, came
                    offsetof(ptss_film_camera, lensRadius) == 56 && offsetof(ptss_film_camera, jitter) == 64,
                "ptss_film_camera is seventeen 32-bit words");
 _Static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, samples) == 12, "ptss_film_entry is one 16-byte row");
+_Static_assert(sizeof(ptss_path_options) == 16 && offsetof(ptss_path_options, schedule) == 4 && offsetof(ptss_path_options, maxWorkgroups) == 8 &&
+                   offsetof(ptss_path_options, reserved) == 12,
+               "ptss_path_options is four 32-bit words");
 #endif
 
 #ifdef __cplusplus

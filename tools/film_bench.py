@@ -12,7 +12,8 @@ Each against its algorithmic bytes (what the call must read and write once: stre
 entry 16 B in and out, a pixel 4 B, a history entry 16 B, an index entry 4 B per launch that reads it, a feature row 32 B) and against
 a device-to-device copy moving the same number of bytes (half read, half written), timed in the same run.
   round        generate + ptss_trace_paths + accumulate (pixels on) against one S = 1 ptss_generate_frame and against ptss_trace_paths
-               alone, on "mixed" and "mesh": what the film adds to a path query.
+               alone, on "mixed" and "mesh": what the film adds to a path query. And the round once more with the trace on the refill
+               schedule (ptss_trace_paths_opt, PTSS_PATHS_REFILL).
 No figure is fixed in advance. Written to stdout and out.json."""
 import json
 import os
@@ -125,16 +126,24 @@ def main():
             out = r.trace_paths(d_rays, d_rng, iterations)
             r.accumulate_paths(out, d_film, pixels=d_px)
 
+        def whole_refill():
+            r.generate_rays(film, d_rng, rays=d_rays)
+            out = r.trace_paths(d_rays, d_rng, iterations, schedule="refill")
+            r.accumulate_paths(out, d_film, pixels=d_px)
+
         frame = timed(lambda: r.generate_frame())
         rounds = timed(whole)
+        refill = timed(whole_refill)
         paths = timed(lambda: r.trace_paths(d_rays, d_rng, iterations))
         res = {"maxIterations": iterations, "frame_ms": frame, "round_ms": rounds, "paths_ms": paths, "round_over_frame": rounds["median"] / frame["median"],
-               "round_over_paths": rounds["median"] / paths["median"], "film_adds_ms": rounds["median"] - paths["median"]}
+               "round_over_paths": rounds["median"] / paths["median"], "film_adds_ms": rounds["median"] - paths["median"], "refill_round_ms": refill,
+               "refill_round_over_frame": refill["median"] / frame["median"], "refill_round_over_round": refill["median"] / rounds["median"]}
         results[f"round/{name}"] = res
         print(f"round {name}, {iterations} iterations: frame {frame['median']:.3f} ms [{frame['min']:.3f}, {frame['max']:.3f}]; generate + trace + "
               f"accumulate {rounds['median']:.3f} ms [{rounds['min']:.3f}, {rounds['max']:.3f}] = {res['round_over_frame']:.2f} x frame; trace alone "
               f"{paths['median']:.3f} ms [{paths['min']:.3f}, {paths['max']:.3f}]: the film adds {res['film_adds_ms']:.3f} ms = "
-              f"{100 * (res['round_over_paths'] - 1):.1f} %", flush=True)
+              f"{100 * (res['round_over_paths'] - 1):.1f} %; the round with the refill trace {refill['median']:.3f} ms [{refill['min']:.3f}, "
+              f"{refill['max']:.3f}] = {res['refill_round_over_frame']:.2f} x frame = {res['refill_round_over_round']:.2f} x the round", flush=True)
         r.close()
     out = {"runs": runs, "window_ms": window_ms, "unit": "ms per call", "size": f"{W}x{H}", "device": torch.cuda.get_device_name(0), "results": results}
     if out_path:
