@@ -1,0 +1,326 @@
+// ptss_adaptive.hip — the kernels behind ptss_accumulate_paths_stats and ptss_plan_samples (include/ptss.h): a film
+// that also keeps the second moment of its tone-mapped samples, and the plan that turns film and moments into the next round's index
+// without a host round trip (csrc/ptadaptive.h has the arithmetic; its host build is the specification).
+//
+// The accumulate kernels write the bytes the kernels of ptss_film.hip write (the same ptq::quantize_fast, the same table, resolveEntry
+// restated here so that file's code objects stay as they are). With an index, the lanes of a wave that hold one pixel side by side — a
+// plan's index is sorted, so all of them do — are summed on chip first and the run's head lane alone issues the atomics.
+//
+// The scan is reduce / scan of the tile sums / downsweep: three launches, no workgroup waits for another. The weight is computed inside
+// both loads; no weight array exists.
+#include "ptss_device.h"
+#include "ptadaptive.h"
+#include "ptdenoise.h"
+#include "ptquant.h"
+
+namespace ptss {
+
+using ptad::u64;
+
+constexpr int kStatsBlock = 256;
+constexpr int kScanBlock = 256;
+constexpr int kScanPerLane = ptad::kScanTile / kScanBlock;   // 8 pixels per lane, 64 apart inside a wave's 512
+constexpr int kScanWaves = kScanBlock / 64;
+constexpr int kSumsBlock = 1024;                             // the one workgroup that scans the tile sums
+static_assert(kScanPerLane * kScanBlock == ptad::kScanTile && kScanBlock % 64 == 0, "a tile is whole waves of whole rounds");
+
+__device__ __forceinline__ uint32_t laneId() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// dropped entries of one wave, counted with one atomic (ptss_film.hip's countDropped)
+__device__ __forceinline__ void countDroppedStats(bool dropped, unsigned long long* rejected) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(dropped);
+    if (m == 0ull) return;
+    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (dropped && before == 0u) atomicAdd(rejected, (unsigned long long)__popcll(m));
+}
+
+// finishPath's display pixel and ptdn::displayValue of one film entry (ptss_film.hip's resolveEntry, restated)
+__device__ __forceinline__ void resolveStatsEntry(uint4 e, uint32_t p, ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
+    const float inv = ptm::rcp((float)e.w);   // 1.f / (float)samples, correctly rounded
+    if (pixels) {
+        const uint32_t px = (uint32_t)(unsigned char)(e.x * inv + 0.5f) | ((uint32_t)(unsigned char)(e.y * inv + 0.5f) << 8) |
+                            ((uint32_t)(unsigned char)(e.z * inv + 0.5f) << 16) | (255u << 24);
+        reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
+    }
+    if (history) {
+        const ptv::vec3 c = ptdn::displayValue(e.x, e.y, e.z, inv);
+        history[p] = float4{c.x, c.y, c.z, (float)e.w};
+    }
+}
+
+// without an index: ray i belongs to pixel firstPixel + i alone — a plain read-modify-write of the entry and of the moment
+__global__ __launch_bounds__(kStatsBlock) void statsAccumulateKernel(const float4* __restrict__ results, uint32_t firstPixel, uint32_t n,
+                                                                     uint4* __restrict__ film, u64* __restrict__ moments,
+                                                                     ptss_uchar4* __restrict__ pixels, float4* __restrict__ history,
+                                                                     const float* __restrict__ quantT) {
+    const uint32_t i = blockIdx.x * kStatsBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 r = results[i];
+    const uint32_t p = firstPixel + i;
+    const uint32_t qr = ptq::quantize_fast(r.x, quantT), qg = ptq::quantize_fast(r.y, quantT), qb = ptq::quantize_fast(r.z, quantT);
+    uint4 e = film[p];
+    e.x += qr;
+    e.y += qg;
+    e.z += qb;
+    e.w += 1u;
+    film[p] = e;
+    moments[p] += (u64)ptad::squares(qr, qg, qb);
+    resolveStatsEntry(e, p, pixels, history);
+}
+
+// with an index: the runs of equal, in-range pixels inside a wave are summed by a segmented reduction towards the run's first lane,
+// which alone issues the atomics (four 32-bit, one 64-bit). A run is split at the wave's edge, and duplicates that are not neighbours
+// meet in the atomics, so the sums are exact for every index. 64 samples of a wave fit 16 bits per channel (64 * 255) and 32 bits of
+// squares (64 * 195,075): three words travel — r | g << 16, b | count << 16, the squares.
+__global__ __launch_bounds__(kStatsBlock) void statsScatterKernel(const float4* __restrict__ results, const uint32_t* __restrict__ index, uint32_t n,
+                                                                  uint32_t* __restrict__ film, u64* __restrict__ moments, uint32_t filmPixels,
+                                                                  const float* __restrict__ quantT, unsigned long long* __restrict__ rejected) {
+    const uint32_t i = blockIdx.x * kStatsBlock + threadIdx.x;
+    const bool inBatch = i < n;
+    const uint32_t p = inBatch ? index[i] : 0u;
+    const bool ok = inBatch && p < filmPixels;
+    countDroppedStats(inBatch && !ok, rejected);
+    const uint32_t key = ok ? p : 0xffffffffu;   // (a film has fewer than 2^31 pixels) lanes without a pixel carry zeros and never lead a store
+    uint32_t rg = 0u, bc = 0u, sq = 0u;
+    if (ok) {
+        const float4 r = results[i];
+        const uint32_t qr = ptq::quantize_fast(r.x, quantT), qg = ptq::quantize_fast(r.y, quantT), qb = ptq::quantize_fast(r.z, quantT);
+        rg = qr | (qg << 16);
+        bc = qb | (1u << 16);
+        sq = ptad::squares(qr, qg, qb);
+    }
+    const uint32_t lane = laneId();
+    const uint32_t before = (uint32_t)__shfl_up((int)key, 1, 64);
+    const bool head = lane == 0u || key != before;
+    const unsigned long long heads = __builtin_amdgcn_ballot_w64(head);
+    // heads strictly above this lane, bit k - 1 = lane + k: lane + d joins while none of lanes lane + 1 .. lane + d starts a run
+    const unsigned long long above = lane < 63u ? heads >> (lane + 1u) : ~0ull;
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const uint32_t rg2 = (uint32_t)__shfl_down((int)rg, d, 64), bc2 = (uint32_t)__shfl_down((int)bc, d, 64),
+                       sq2 = (uint32_t)__shfl_down((int)sq, d, 64);
+        const bool joins = lane + d < 64u && (above & ((1ull << d) - 1ull)) == 0ull;
+        if (joins) {
+            rg += rg2;
+            bc += bc2;
+            sq += sq2;
+        }
+    }
+    if (!(head && ok)) return;
+    uint32_t* e = film + 4 * (size_t)p;
+    atomicAdd(e + 0, rg & 0xffffu);
+    atomicAdd(e + 1, rg >> 16);
+    atomicAdd(e + 2, bc & 0xffffu);
+    atomicAdd(e + 3, bc >> 16);
+    atomicAdd(moments + p, (unsigned long long)sq);
+}
+
+// every run of the index resolves its pixel once per wave; runs that share a pixel store the same bytes
+__global__ __launch_bounds__(kStatsBlock) void statsResolveKernel(const uint32_t* __restrict__ index, uint32_t n, const uint4* __restrict__ film,
+                                                                  uint32_t filmPixels, ptss_uchar4* __restrict__ pixels,
+                                                                  float4* __restrict__ history) {
+    const uint32_t i = blockIdx.x * kStatsBlock + threadIdx.x;
+    const uint32_t p = i < n ? index[i] : 0xffffffffu;
+    const uint32_t before = (uint32_t)__shfl_up((int)p, 1, 64);
+    if (p >= filmPixels || (laneId() != 0u && p == before)) return;
+    resolveStatsEntry(film[p], p, pixels, history);
+}
+
+// ---- the plan ------------------------------------------------------------------------------------------------------------------------------
+struct PlanArgs {
+    const uint4* film;
+    const u64* moments;
+    uint32_t filmPixels;
+    uint32_t minSamples, maxSamples;
+    float threshold;
+};
+
+// the weight of pixel p (0 beyond the film), its kind added to the three counters
+__device__ __forceinline__ uint32_t loadWeight(const PlanArgs& a, uint32_t p, uint32_t& active, uint32_t& unsampled, uint32_t& capped) {
+    if (p >= a.filmPixels) return 0u;
+    const uint4 e = a.film[p];
+    uint32_t kind;
+    const uint32_t w = ptad::weight(e.x, e.y, e.z, e.w, a.moments[p], a.minSamples, a.maxSamples, a.threshold, &kind);
+    active += kind & ptad::kActive ? 1u : 0u;
+    unsampled += kind & ptad::kUnsampled ? 1u : 0u;
+    capped += kind & ptad::kCapped ? 1u : 0u;
+    return w;
+}
+
+__device__ __forceinline__ uint32_t waveSum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+// inclusive sum over the lanes of a wave
+__device__ __forceinline__ uint32_t waveScan(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// pixel k of lane `lane` of wave `wave` of tile `tile`: a wave owns 512 consecutive pixels, a round of it 64
+__device__ __forceinline__ uint32_t scanPixel(uint32_t tile, uint32_t wave, uint32_t k, uint32_t lane) {
+    return tile * (uint32_t)ptad::kScanTile + wave * (64u * kScanPerLane) + k * 64u + lane;   // < 2^31 + 2048
+}
+
+// step 1: the sum of a tile's weights (at most 2048 * 2^19 = 2^30) and its three counts -> work[3 tile .. 3 tile + 2]
+__global__ __launch_bounds__(kScanBlock) void planReduceKernel(PlanArgs a, u64* __restrict__ work) {
+    __shared__ uint32_t part[kScanWaves][4];
+    const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
+    uint32_t sum = 0u, active = 0u, unsampled = 0u, capped = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) sum += loadWeight(a, scanPixel(blockIdx.x, wave, k, lane), active, unsampled, capped);
+    sum = waveSum(sum);
+    active = waveSum(active);
+    unsampled = waveSum(unsampled);
+    capped = waveSum(capped);
+    if (lane == 0u) {
+        part[wave][0] = sum;
+        part[wave][1] = active;
+        part[wave][2] = unsampled;
+        part[wave][3] = capped;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t[4] = {0u, 0u, 0u, 0u};
+        for (int w = 0; w < kScanWaves; ++w)
+            for (int c = 0; c < 4; ++c) t[c] += part[w][c];
+        u64* out = work + (size_t)ptad::kWorkspacePerTile * blockIdx.x;
+        out[0] = (u64)t[0];
+        out[1] = (u64)t[1] | ((u64)t[2] << 32);
+        out[2] = (u64)t[3];
+    }
+}
+
+// step 2, one workgroup: the tile sums become the sums of the tiles in front of each (exclusive), 1024 tiles per pass with a carry;
+// the totals go to *info
+__global__ __launch_bounds__(kSumsBlock) void planTileSumsKernel(u64* __restrict__ work, uint32_t tiles, ptss_plan_info* __restrict__ info) {
+    __shared__ u64 waveTotal[kSumsBlock / 64];
+    __shared__ u64 counts[3];
+    const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
+    if (threadIdx.x < 3u) counts[threadIdx.x] = 0ull;
+    u64 carry = 0ull;
+    u64 active = 0ull, unsampled = 0ull, capped = 0ull;
+    for (uint32_t base = 0u; base < tiles; base += (uint32_t)kSumsBlock) {   // (uniform bounds: every lane takes every pass)
+        const uint32_t t = base + threadIdx.x;
+        u64* w = work + (size_t)ptad::kWorkspacePerTile * t;
+        u64 own = 0ull;
+        if (t < tiles) {
+            own = w[0];
+            active += w[1] & 0xffffffffull;
+            unsampled += w[1] >> 32;
+            capped += w[2];
+        }
+        u64 v = own;   // inclusive over the wave
+#pragma unroll
+        for (uint32_t d = 1u; d < 64u; d <<= 1) {
+            const u64 o = (u64)__shfl_up((long long)v, d, 64);
+            if (lane >= d) v += o;
+        }
+        __syncthreads();   // the previous pass has read waveTotal
+        if (lane == 63u) waveTotal[wave] = v;
+        __syncthreads();
+        u64 front = carry, all = carry;
+        for (uint32_t k = 0u; k < (uint32_t)(kSumsBlock / 64); ++k) {
+            if (k < wave) front += waveTotal[k];
+            all += waveTotal[k];
+        }
+        if (t < tiles) w[0] = front + v - own;
+        carry = all;
+    }
+    if (!info) return;
+    __syncthreads();
+    atomicAdd(&counts[0], active);   // LDS atomics: integer, exact in any order
+    atomicAdd(&counts[1], unsampled);
+    atomicAdd(&counts[2], capped);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        info->totalWeight = carry;
+        info->activePixels = (uint32_t)counts[0];
+        info->unsampledPixels = (uint32_t)counts[1];
+        info->cappedPixels = (uint32_t)counts[2];
+        info->uniform = carry == 0ull ? 1u : 0u;
+        info->reserved[0] = info->reserved[1] = 0u;
+    }
+}
+
+// step 3: the weights again, scanned inside the tile (32-bit: a tile's sum is at most 2^30) on top of the sum of the tiles in front
+__global__ __launch_bounds__(kScanBlock) void planDownsweepKernel(PlanArgs a, const u64* __restrict__ work, u64* __restrict__ cdf) {
+    __shared__ uint32_t waveTotal[kScanWaves];
+    const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
+    uint32_t incl[kScanPerLane];
+    uint32_t running = 0u, unused0 = 0u, unused1 = 0u, unused2 = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) {
+        const uint32_t w = loadWeight(a, scanPixel(blockIdx.x, wave, k, lane), unused0, unused1, unused2);
+        incl[k] = running + waveScan(w, lane);
+        running = (uint32_t)__shfl((int)incl[k], 63, 64);   // the wave's sum so far
+    }
+    if (lane == 0u) waveTotal[wave] = running;
+    __syncthreads();
+    u64 front = work[(size_t)ptad::kWorkspacePerTile * blockIdx.x];
+    for (uint32_t k = 0u; k < wave; ++k) front += (u64)waveTotal[k];
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) {
+        const uint32_t p = scanPixel(blockIdx.x, wave, k, lane);
+        if (p < a.filmPixels) cdf[p] = front + (u64)incl[k];
+    }
+}
+
+// step 4: entry i names the pixel under its target; neighbouring lanes search neighbouring targets
+__global__ __launch_bounds__(kStatsBlock) void planIndexKernel(const u64* __restrict__ cdf, uint32_t filmPixels, uint32_t n, uint32_t* __restrict__ index) {
+    const uint32_t i = blockIdx.x * kStatsBlock + threadIdx.x;
+    if (i >= n) return;
+    const u64 total = cdf[filmPixels - 1u];
+    index[i] = total == 0ull ? ptad::uniformPixel((u64)i, (u64)n, (u64)filmPixels)
+                             : ptad::pixelOf(cdf, filmPixels, ptad::target((u64)i, (u64)n, total));
+}
+
+static inline unsigned statsBlocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
+
+hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
+                                 unsigned long long* moments, uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable,
+                                 unsigned long long* rejected, unsigned long long* launches) {
+    const dim3 grid(statsBlocksFor(n, kStatsBlock)), block(kStatsBlock);
+    if (!index) {
+        hipLaunchKernelGGL(statsAccumulateKernel, grid, block, 0, st, static_cast<const float4*>(results), firstPixel, n, static_cast<uint4*>(film),
+                           moments, pixels, static_cast<float4*>(history), quantTable);
+    } else {
+        hipLaunchKernelGGL(statsScatterKernel, grid, block, 0, st, static_cast<const float4*>(results), index, n, static_cast<uint32_t*>(film),
+                           moments, filmPixels, quantTable, rejected);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        if (pixels || history)
+            hipLaunchKernelGGL(statsResolveKernel, grid, block, 0, st, index, n, static_cast<const uint4*>(film), filmPixels, pixels,
+                               static_cast<float4*>(history));
+    }
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) ++*launches;
+    return e;
+}
+
+hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
+                             const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
+                             unsigned long long* launches) {
+    const PlanArgs a{static_cast<const uint4*>(film), moments, filmPixels, params.minSamples, params.maxSamples, params.threshold};
+    const uint32_t tiles = (uint32_t)ptad::scanTiles(filmPixels);
+    u64* work = cdf + filmPixels;   // the entries behind the film's own: kWorkspacePerTile words per tile
+    hipLaunchKernelGGL(planReduceKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(planTileSumsKernel, dim3(1), dim3(kSumsBlock), 0, st, work, tiles, info);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(planDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(planIndexKernel, dim3(statsBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
+    e = hipGetLastError();
+    if (e == hipSuccess) ++*launches;
+    return e;
+}
+
+}  // namespace ptss

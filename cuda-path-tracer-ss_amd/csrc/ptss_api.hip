@@ -23,6 +23,7 @@
 #include "ptpack.h"
 #include "ptstrip.h"
 #include "ptcamera.h"
+#include "ptadaptive.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -151,6 +152,7 @@ struct ptss_context {
     unsigned long long filmLaunches[3] = {0, 0, 0};           // ptss_generate_rays, ptss_accumulate_paths, ptss_ray_features calls that launched
     hipStream_t filmStream = nullptr;                         // the stream of the latest film call with an index (ptss_film_rejected synchronises on it)
     bool filmIndexed = false;
+    unsigned long long adaptiveLaunches[2] = {0, 0};          // ptss_accumulate_paths_stats, ptss_plan_samples calls that launched
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -1351,6 +1353,75 @@ int ptss_film_rejected(ptss_context* c, unsigned long long* out) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (c->filmIndexed) HIP_TRY(hipStreamSynchronize(c->filmStream));
     HIP_TRY(hipMemcpy(out, c->dTotal + kFilmRejectedWord, sizeof(*out), hipMemcpyDeviceToHost));
+    return PTSS_OK;
+}
+
+// ---- adaptive film sampling (ptss_adaptive.hip; csrc/ptadaptive.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_accumulate_paths_stats(ptss_context* c, const ptss_path_result* dev_results, const uint32_t* dev_index, size_t firstPixel, size_t n,
+                                ptss_film_entry* dev_film, unsigned long long* dev_moments, size_t filmPixels, ptss_uchar4* dev_pixels,
+                                ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_results || !dev_film || !dev_moments) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if ((((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) || (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u) ||
+        ((uintptr_t)dev_moments & 7u))
+        return fail(PTSS_EINVAL, "results, film and history must be 16-byte aligned, dev_moments 8-byte, dev_index and dev_pixels 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
+    HIP_TRY(ptss::launchStatsAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film, dev_moments,
+                                        (uint32_t)filmPixels, dev_pixels, dev_history, quantTable, c->dTotal + kFilmRejectedWord,
+                                        &c->adaptiveLaunches[0]));
+    if (dev_index) {
+        c->filmStream = st;
+        c->filmIndexed = true;
+    }
+    return PTSS_OK;
+}
+
+int ptss_default_plan_params(ptss_plan_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_plan_params);
+    p->minSamples = 8u;
+    p->maxSamples = ptad::kSampleLimit;
+    p->threshold = 0.5f;
+    return PTSS_OK;
+}
+
+int ptss_plan_cdf_entries(size_t filmPixels, size_t* entries) {
+    if (!entries) return fail(PTSS_EINVAL, "entries is null");
+    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    *entries = (size_t)ptad::cdfEntries(filmPixels);
+    return PTSS_OK;
+}
+
+int ptss_plan_samples(ptss_context* c, const ptss_film_entry* dev_film, const unsigned long long* dev_moments, size_t filmPixels,
+                      const ptss_plan_params* params, size_t n, unsigned long long* dev_cdf, uint32_t* dev_index, ptss_plan_info* dev_info,
+                      void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptad::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_film || !dev_moments || !dev_cdf || !dev_index) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (((uintptr_t)dev_film & 15u) || (((uintptr_t)dev_moments | (uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u))
+        return fail(PTSS_EINVAL, "film must be 16-byte aligned, dev_moments, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchPlanSamples(st, dev_film, dev_moments, (uint32_t)filmPixels, *params, (uint32_t)n, dev_cdf, dev_index, dev_info,
+                                    &c->adaptiveLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_adaptive_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->adaptiveLaunches[0];
+    out2[1] = c->adaptiveLaunches[1];
     return PTSS_OK;
 }
 

@@ -210,6 +210,16 @@ hipError_t launchFilmAccumulate(hipStream_t st, const void* results, const uint3
                                 unsigned long long* launches);
 hipError_t launchRayFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays,
                              ptss_vec3 defaultColor, void* out, uint32_t n, int maxBlocks, unsigned long long* launches);
+// adaptive film sampling (ptss_adaptive.hip; ptss_accumulate_paths_stats / ptss_plan_samples). launchStatsAccumulate:
+// launchFilmAccumulate's buffers and bytes plus moments = filmPixels x 8 B, each ray's squared bytes added. launchPlanSamples: cdf =
+// ptad::cdfEntries(filmPixels) x 8 B (the film's running sums, then the scan's workspace), index = n uint32 out, info = 32 B or nullptr.
+// No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
+                                 unsigned long long* moments, uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable,
+                                 unsigned long long* rejected, unsigned long long* launches);
+hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
+                             const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
+                             unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

@@ -12,6 +12,7 @@
 #include "ptreproject.h"
 #include "ptupsample.h"
 #include "ptcamera.h"
+#include "ptadaptive.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -618,6 +619,55 @@ int ptss_probe_accumulate(const ptss_path_result* results, const uint32_t* index
     }
     if (rejected) *rejected = dropped;
     return PTSS_HOST_OK;
+}
+
+int ptss_probe_accumulate_stats(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_film_entry* film,
+                                unsigned long long* moments, size_t filmPixels, ptss_uchar4* pixels, ptss_history_entry* history,
+                                unsigned long long* rejected) {
+    if (n > 0 && !moments) return PTSS_HOST_EINVAL;
+    const int rc = ptss_probe_accumulate(results, index, firstPixel, n, film, filmPixels, pixels, history, rejected);
+    if (rc != PTSS_HOST_OK) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) continue;
+        moments[p] += ptad::squares(ptq::quantize_literal(results[i].radiance.x), ptq::quantize_literal(results[i].radiance.y),
+                                    ptq::quantize_literal(results[i].radiance.z));
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_plan_samples(const ptss_film_entry* film, const unsigned long long* moments, size_t filmPixels, const ptss_plan_params* params,
+                            size_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info) {
+    if (ptad::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!film || !moments || !cdf || !index) return PTSS_HOST_EINVAL;
+    ptss_plan_info found{};
+    unsigned long long sum = 0;
+    for (size_t p = 0; p < filmPixels; ++p) {
+        uint32_t kind;
+        sum += ptad::weight(film[p].r, film[p].g, film[p].b, film[p].samples, moments[p], params->minSamples, params->maxSamples,
+                            params->threshold, &kind);
+        cdf[p] = sum;
+        found.activePixels += (kind & ptad::kActive) ? 1u : 0u;
+        found.unsampledPixels += (kind & ptad::kUnsampled) ? 1u : 0u;
+        found.cappedPixels += (kind & ptad::kCapped) ? 1u : 0u;
+    }
+    found.totalWeight = sum;
+    found.uniform = sum == 0ull ? 1u : 0u;
+    for (size_t i = 0; i < n; ++i)
+        index[i] = sum == 0ull ? ptad::uniformPixel(i, n, filmPixels) : ptad::pixelOf(cdf, (uint32_t)filmPixels, ptad::target(i, n, sum));
+    if (info) *info = found;
+    return PTSS_HOST_OK;
+}
+
+uint32_t ptss_probe_plan_weight(const ptss_film_entry* entry, unsigned long long moment, const ptss_plan_params* params) {
+    if (!entry || ptad::paramsError(params)) return 0xffffffffu;
+    return ptad::weight(entry->r, entry->g, entry->b, entry->samples, moment, params->minSamples, params->maxSamples, params->threshold, nullptr);
+}
+
+unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long long n, unsigned long long total) {
+    return n ? ptad::target(i, n, total) : 0ull;
 }
 
 }  // extern "C"

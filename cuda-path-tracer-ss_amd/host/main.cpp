@@ -29,6 +29,10 @@
 //                                   pinhole writes the frame loop's image (while that loop's guard stays silent). With --denoise:
 //                                   image_denoised.tga through ptss_ray_features and ptss_denoise_history
 //             [--refill]            with --film: the trace through ptss_trace_paths_opt with PTSS_PATHS_REFILL (the same bytes)
+//             [--adaptive ROUNDS[,threshold]]   with --film: the --ticks uniform rounds keep second moments (ptss_accumulate_paths_stats;
+//                                   the same bytes), then ROUNDS planned rounds of width * height rays each go where ptss_plan_samples
+//                                   sends them (minSamples = --ticks, default maxSamples; threshold overrides the default's). Prints
+//                                   the final ptss_plan_info. ROUNDS = 0 writes the bytes of the run without the flag
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -54,6 +58,8 @@ int main(int argc, char* argv[]) {
     std::string film;  // --film: the camera model, empty = the frame loop
     float lensRadius = 0.05f, focusDistance = 5.0f;   // --lens
     bool refill = false;   // --refill: the film's trace with the refill schedule
+    int adaptive = -1;     // --adaptive: -1 absent, else the planned rounds behind the uniform ones
+    float adaptiveThreshold = -1.f;   // ... and the plan's threshold when given
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -83,6 +89,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--upscale") upscale = atoi(next());
         else if (a == "--film") film = next();
         else if (a == "--refill") refill = true;
+        else if (a == "--adaptive") {
+            const int got = sscanf(next(), "%d,%f", &adaptive, &adaptiveThreshold);
+            if (got < 1 || adaptive < 0 || (got == 2 && !(adaptiveThreshold >= 0.f && adaptiveThreshold < 1e30f))) { fprintf(stderr, "bad --adaptive (rounds[,threshold])\n"); return 2; }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -132,6 +142,7 @@ int main(int argc, char* argv[]) {
         return 2;
     }
     if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
+    if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -240,6 +251,7 @@ int main(int argc, char* argv[]) {
         if (refill) pathOptions.schedule = PTSS_PATHS_REFILL;
         const size_t n = (size_t)width * (size_t)height;
         void *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dFilm = nullptr, *dHist = nullptr, *dFeat = nullptr, *dOut = nullptr;
+        void *dMoments = nullptr, *dCdf = nullptr, *dIndex = nullptr, *dInfo = nullptr;   // --adaptive
         const bool filter = denoise != -2;
         if (hipMalloc(&dRng, n * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dRays, n * sizeof(ptss_ray_query)) != hipSuccess ||
             hipMalloc(&dRes, n * sizeof(ptss_path_result)) != hipSuccess || hipMalloc(&dFilm, n * sizeof(ptss_film_entry)) != hipSuccess ||
@@ -249,13 +261,50 @@ int main(int argc, char* argv[]) {
             fprintf(stderr, "--film: device buffers\n");
             return 1;
         }
+        size_t cdfEntries = 0;
+        if (adaptive >= 0) {
+            PTSS_HANDLE(ptss_plan_cdf_entries(n, &cdfEntries));
+            if (hipMalloc(&dMoments, n * sizeof(unsigned long long)) != hipSuccess || hipMemset(dMoments, 0, n * sizeof(unsigned long long)) != hipSuccess ||
+                hipMalloc(&dCdf, cdfEntries * sizeof(unsigned long long)) != hipSuccess || hipMalloc(&dIndex, n * sizeof(uint32_t)) != hipSuccess ||
+                hipMalloc(&dInfo, sizeof(ptss_plan_info)) != hipSuccess) {
+                fprintf(stderr, "--adaptive: device buffers\n");
+                return 1;
+            }
+        }
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
             PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
             PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
                                              NULL));
-            PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
-                                              (ptss_history_entry*)dHist, NULL));
+            if (adaptive >= 0) {
+                PTSS_HANDLE(ptss_accumulate_paths_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm,
+                                                        (unsigned long long*)dMoments, n, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            } else {
+                PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
+                                                  (ptss_history_entry*)dHist, NULL));
+            }
+        }
+        if (adaptive >= 0) {   // the planned rounds: ray slot i keeps stream i whatever pixel the plan gives it
+            ptss_plan_params plan;
+            PTSS_HANDLE(ptss_default_plan_params(&plan));
+            plan.minSamples = ticks > 0 ? (uint32_t)ticks : 1u;
+            if (plan.maxSamples < plan.minSamples) plan.maxSamples = plan.minSamples;
+            if (adaptiveThreshold >= 0.f) plan.threshold = adaptiveThreshold;
+            for (int t = 0; t <= adaptive; ++t) {   // (the last plan only reports what the rounds left)
+                PTSS_HANDLE(ptss_plan_samples(ctx, (const ptss_film_entry*)dFilm, (const unsigned long long*)dMoments, n, &plan, n,
+                                              (unsigned long long*)dCdf, (uint32_t*)dIndex, (ptss_plan_info*)dInfo, NULL));
+                if (t == adaptive) break;
+                PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, (const uint32_t*)dIndex, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+                PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
+                                                 NULL));
+                PTSS_HANDLE(ptss_accumulate_paths_stats(ctx, (const ptss_path_result*)dRes, (const uint32_t*)dIndex, 0, n, (ptss_film_entry*)dFilm,
+                                                        (unsigned long long*)dMoments, n, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            }
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            ptss_plan_info info;
+            if (hipMemcpy(&info, dInfo, sizeof(info), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--adaptive: read-back\n"); return 1; }
+            printf("adaptive: rounds %d totalWeight %llu activePixels %u unsampledPixels %u cappedPixels %u uniform %u\n", adaptive, info.totalWeight,
+                   info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
         if (filter && ticks > 0) {   // the features of the film's pixel centres, then the filter over the film's display values
             ptss_denoise_params params;
@@ -275,7 +324,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, PATHS_LANE_PER_RAY, PATHS_REFILL,
-                        PathOptions, SCENE_LAYOUT_FIELDS,
+                        PathOptions, PlanInfo, PlanParams, SCENE_LAYOUT_FIELDS,
                         SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 
@@ -180,6 +180,14 @@ def host_lib():
         L.ptss_probe_film_rays.argtypes = [C.POINTER(FilmCamera), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.ptss_probe_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_accumulate_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_plan_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(PlanParams), C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.POINTER(PlanInfo)]
+        L.ptss_probe_plan_weight.argtypes = [C.POINTER(FilmEntry), C.c_ulonglong, C.POINTER(PlanParams)]
+        L.ptss_probe_plan_weight.restype = C.c_uint32
+        L.ptss_probe_plan_target.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
+        L.ptss_probe_plan_target.restype = C.c_ulonglong
         _host = L
     return _host
 
@@ -268,6 +276,11 @@ def device_lib():
         L.ptss_ray_features.argtypes = [vp, vp, vp, C.c_size_t, vp]
         L.ptss_film_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_film_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_accumulate_paths_stats.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, vp, vp, vp]
+        L.ptss_default_plan_params.argtypes = [C.POINTER(PlanParams)]
+        L.ptss_plan_cdf_entries.argtypes = [C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ptss_plan_samples.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(PlanParams), C.c_size_t, vp, vp, vp, vp]
+        L.ptss_adaptive_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -574,6 +587,71 @@ def probe_accumulate(results, film, first_pixel=0, index=None, pixels=None, hist
     if rc != 0:
         raise PtssError(f"ptss_probe_accumulate: {rc}")
     return (f.view(FILM_DTYPE).reshape(-1), px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None, int(rejected.value))
+
+
+# ---- adaptive film sampling (ptss_accumulate_paths_stats / ptss_plan_samples) ----
+def plan_params(min_samples=8, max_samples=1 << 23, threshold=0.5):
+    """A ptss_plan_params; the defaults are ptss_default_plan_params' (design choices, not measurements)."""
+    p = PlanParams()
+    p.structSize = C.sizeof(PlanParams)
+    p.minSamples, p.maxSamples, p.threshold = int(min_samples), int(max_samples), float(threshold)
+    return p
+
+
+def plan_info_dict(info):
+    """A PlanInfo (or its four 64-bit words) as a dict."""
+    if not isinstance(info, PlanInfo):
+        info = PlanInfo.from_buffer_copy(np.ascontiguousarray(info).tobytes())
+    return dict(totalWeight=int(info.totalWeight), activePixels=int(info.activePixels), unsampledPixels=int(info.unsampledPixels),
+                cappedPixels=int(info.cappedPixels), uniform=int(info.uniform))
+
+
+def _moments(moments, P):
+    m = np.array(moments, dtype=np.uint64, order="C").reshape(-1)   # a copy
+    if len(m) != P:
+        raise ValueError("moments: one uint64 per film pixel")
+    return m
+
+
+def probe_accumulate_stats(results, film, moments, first_pixel=0, index=None, pixels=None, history=None):
+    """ptss_accumulate_paths_stats on the host, with the literal tone map -> (film, moments (P,) uint64, pixels, history, dropped):
+    probe_accumulate's arguments and results, with the moments beforehand (not modified) and afterwards."""
+    r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+    n = len(r)
+    idx = _film_index(index, n)
+    f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
+    m = _moments(moments, len(f))
+    px = None if pixels is None else (np.zeros((len(f), 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
+    hs = None if history is None else (np.zeros((len(f), 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_accumulate_stats(r.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if idx is not None else None,
+                                                int(first_pixel), n, f.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), len(f),
+                                                px.ctypes.data_as(C.c_void_p) if px is not None else None,
+                                                hs.ctypes.data_as(C.c_void_p) if hs is not None else None, C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_accumulate_stats: {rc}")
+    return (f.view(FILM_DTYPE).reshape(-1), m, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None, int(rejected.value))
+
+
+def probe_plan_samples(film, moments, n, params=None):
+    """ptss_plan_samples on the host (csrc/ptadaptive.h; the specification of the device's plan) -> (cdf (P,) uint64, index (n,) uint32,
+    info: a dict). film: (P,) FILM_DTYPE or (P, 4) uint32; moments: (P,) uint64."""
+    f = _rows(film, FILM_DTYPE, 4, np.uint32, "film")
+    m = _moments(moments, len(f))
+    params = params if params is not None else plan_params()
+    cdf, index, info = np.zeros(len(f), dtype=np.uint64), np.zeros(int(n), dtype=np.uint32), PlanInfo()
+    rc = host_lib().ptss_probe_plan_samples(f.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), len(f), C.byref(params), int(n),
+                                            cdf.ctypes.data_as(C.c_void_p), index.ctypes.data_as(C.c_void_p), C.byref(info))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_plan_samples: {rc}")
+    return cdf, index, plan_info_dict(info)
+
+
+def plan_cdf_entries(film_pixels):
+    """ptss_plan_cdf_entries: the 64-bit entries dev_cdf must hold for a film of that many pixels."""
+    out = C.c_size_t(0)
+    _check(device_lib().ptss_plan_cdf_entries(int(film_pixels), C.byref(out)))
+    return int(out.value)
 
 
 def default_denoise_params(**overrides):
@@ -1397,6 +1475,83 @@ class Renderer:
         else:
             self._round_trip([a, out], lambda d: _check(L.ptss_ray_features(self._ctx, d[0], d[1], n, None)), read=(1,))
         return out
+
+    def accumulate_paths_stats(self, results, film, moments, first_pixel=0, index=None, pixels=None, history=None):
+        """ptss_accumulate_paths_stats: accumulate_paths, with the second moments kept as well.
+        numpy: accumulate_paths' arguments and moments (P,) uint64 (not modified) -> (film, moments afterwards, pixels, history).
+        torch: moments a contiguous (P,) int64 device tensor UPDATED IN PLACE like the film -> None, on the current stream."""
+        L = device_lib()
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_film = self._torch_ptr(film, "film", "int32", 4, dev)
+            P = film.shape[0]
+            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P)
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
+            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
+            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_accumulate_paths_stats(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, d_mom, P, d_px, d_hs, C.c_void_p(stream)))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        idx = _film_index(index, n)
+        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
+        P = len(f)
+        m = _moments(moments, P)
+        px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
+        hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True
+                                           else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+        if (px is not None and len(px) != P) or (hs is not None and len(hs) != P):
+            raise ValueError("pixels and history: one entry per film pixel")
+        if n == 0:
+            _check(L.ptss_accumulate_paths_stats(self._ctx, None, None, int(first_pixel), 0, None, None, P, None, None, None))
+        else:
+            self._round_trip([r, idx, f, m, px, hs],
+                             lambda d: _check(L.ptss_accumulate_paths_stats(self._ctx, d[0], d[1], int(first_pixel), n, d[2], d[3], P, d[4], d[5], None)),
+                             read=(2, 3, 4, 5))
+        return f.view(FILM_DTYPE).reshape(-1), m, px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+    def plan_samples(self, film, moments, n, params=None, cdf=None, index=None, info=None):
+        """ptss_plan_samples: the next round's index from film and moments.
+        numpy: film (P,) FILM_DTYPE or (P, 4) uint32, moments (P,) uint64 -> (cdf (P,) uint64, index (n,) uint32, info: a dict).
+        torch: film (P, 4) int32, moments (P,) int64, cdf a (plan_cdf_entries(P),) int64 tensor, index an (n,) int32 tensor and info a
+        (4,) int64 tensor or None, all contiguous on one device, WRITTEN IN PLACE -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else plan_params()
+        n = int(n)
+        if type(film).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, P = film.device, film.shape[0]
+            d_film = self._torch_ptr(film, "film", "int32", 4)
+            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P)
+            d_cdf = self._torch_ptr(cdf, "cdf", "int64", 0, dev, plan_cdf_entries(P))
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n)
+            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_plan_samples(self._ctx, d_film, d_mom, P, C.byref(params), n, d_cdf, d_idx, d_info, C.c_void_p(stream)))
+            return None
+        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film")
+        P = len(f)
+        m = _moments(moments, P)
+        work = np.zeros(plan_cdf_entries(P), dtype=np.uint64)
+        out, found = np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
+        if n == 0:
+            _check(L.ptss_plan_samples(self._ctx, None, None, P, C.byref(params), 0, None, None, None, None))
+        else:
+            self._round_trip([f, m, work, out, found],
+                             lambda d: _check(L.ptss_plan_samples(self._ctx, d[0], d[1], P, C.byref(params), n, d[2], d[3], d[4], None)),
+                             read=(2, 3, 4))
+        return work[:P], out, plan_info_dict(found)
+
+    def adaptive_launches(self):
+        """ptss_adaptive_launches: (accumulate_paths_stats, plan_samples calls that launched since the context was created)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_adaptive_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
 
     def film_launches(self):
         """ptss_film_launches: (generate_rays, accumulate_paths, ray_features calls that launched since the context was created)."""

@@ -120,6 +120,15 @@ class FilmEntry(C.Structure):   # ptss_film_entry: the 8-bit sample sums of one 
 FILM_DTYPE = np.dtype([("r", np.uint32), ("g", np.uint32), ("b", np.uint32), ("samples", np.uint32)])
 
 
+class PlanParams(C.Structure):   # ptss_plan_params: how ptss_plan_samples weighs a film pixel
+    _fields_ = [("structSize", C.c_uint), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32), ("threshold", C.c_float)]
+
+
+class PlanInfo(C.Structure):   # ptss_plan_info: what a plan found
+    _fields_ = [("totalWeight", C.c_ulonglong), ("activePixels", C.c_uint32), ("unsampledPixels", C.c_uint32), ("cappedPixels", C.c_uint32),
+                ("uniform", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -164,6 +173,7 @@ assert C.sizeof(PathRng) == 24 == PATH_RNG_DTYPE.itemsize and PathRng.d.offset =
 assert C.sizeof(PathResult) == 16 == PATH_RESULT_DTYPE.itemsize and PathResult.bounces.offset == 12 == PATH_RESULT_DTYPE.fields["bounces"][1]
 assert C.sizeof(FilmCamera) == 68 and FilmCamera.camera.offset == 8 and FilmCamera.width.offset == 48 and FilmCamera.jitter.offset == 64
 assert C.sizeof(FilmEntry) == 16 == FILM_DTYPE.itemsize and FilmEntry.samples.offset == 12 == FILM_DTYPE.fields["samples"][1]
+assert C.sizeof(PlanParams) == 16 and PlanParams.threshold.offset == 12 and C.sizeof(PlanInfo) == 32 and PlanInfo.uniform.offset == 20
 
 
 def struct_to_dict(s):

@@ -348,6 +348,56 @@ int ptss_ray_features(ptss_context* ctx, const ptss_ray_query* dev_rays, ptss_pi
 int ptss_film_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] generate, [1] accumulate, [2] features */
 int ptss_film_rejected(ptss_context* ctx, unsigned long long* out);
 
+/* Adaptive film sampling: a film that also keeps the second moment of its samples, and a plan that turns film and
+ * moments into the next round's index on the device. One round is
+ *     ptss_generate_rays(index) -> ptss_trace_paths -> ptss_accumulate_paths_stats(index) -> ptss_plan_samples -> the next index,
+ * with no host round trip. Ray slot i keeps stream dev_rng[i] whatever pixel the index gives it: streams belong to slots, not to pixels.
+ * Choosing sample counts from the samples themselves biases the estimate (a pixel whose first samples happen to agree is left early);
+ * that is a known property of the scheme and is not corrected here.
+ *
+ * dev_moments: one unsigned long long per film pixel, 8-byte aligned, zero for a new film: the sum, over the samples accumulated into the
+ * pixel, of qr^2 + qg^2 + qb^2, where q* are the three tone-mapped bytes ptss_accumulate_paths adds to the film entry (at most 195,075
+ * per sample: no overflow below 2^24 samples).
+ *
+ * ptss_accumulate_paths_stats: ptss_accumulate_paths' arguments, refusals and bytes — dev_film, dev_pixels and dev_history come out
+ * exactly as that call writes them, dropped index entries are counted in ptss_film_rejected — plus dev_moments[p] += the ray's squared
+ * bytes; dev_moments null or not 8-byte aligned: PTSS_EINVAL. Without an index: one kernel, a plain read-modify-write of the 16-byte
+ * entry and the 8-byte moment. With an index: the lanes of a wave that hold one pixel side by side (all of them, for a plan's sorted
+ * index) are summed on chip and the run's first lane alone issues the atomics, four 32-bit and one 64-bit; duplicates that are not
+ * neighbours meet in the atomics, so the sums are exact for every index. The touched pixels are resolved by a second launch.
+ *
+ * ptss_plan_samples: dev_index[0 .. n) = a budget of exactly n rays spread over the film's pixels in proportion to an integer weight.
+ *   weight (csrc/ptadaptive.h; N = samples, S = the sums, Q = the moment; unsigned 64-bit wrapping arithmetic):
+ *     N < minSamples: 2^19 (unsampled: it outranks every measured pixel). N >= maxSamples: 0 (capped). Otherwise D = max(N Q - |S|^2, 0),
+ *     se = sqrt((float)D) / ((float)N sqrt((float)N)) — the standard error of the pixel's mean on the 0..255 scale, every operation
+ *     correctly rounded f32 — and w = se > threshold ? (uint32_t)min(se * 1024.f, 524287.f) : 0.
+ *   dev_cdf[p] = w_0 + .. + w_p for p < filmPixels (at most 2^50); the entries from filmPixels up to ptss_plan_cdf_entries(filmPixels)
+ *     are the call's workspace, so the call keeps no state.
+ *   total = dev_cdf[filmPixels - 1] > 0: t_i = floor((i total + total / 2) / n) and dev_index[i] = the smallest p with dev_cdf[p] > t_i.
+ *   total = 0 (every pixel converged or capped): the same rule with every weight 1, dev_index[i] = (i filmPixels + filmPixels / 2) / n.
+ *   The index is non-decreasing, never names a pixel of weight 0 while total > 0, and names pixel p count_p times with
+ *   |count_p total - n w_p| < total. dev_info (may be NULL) is written by the device.
+ * The host build of csrc/ptadaptive.h (ptss_probe_plan_samples) is the specification; the device agrees with it byte for byte, also
+ * for moments that do not belong to the film.
+ * Refused without touching the device and without counting: a null context, params or required pointer, a wrong structSize,
+ * minSamples = 0, maxSamples outside [1, 2^23] or below minSamples, a threshold that is negative or not finite, a pointer that is not
+ * aligned — 16 bytes for the film, 8 for moments, cdf and info, 4 for the index — (PTSS_EINVAL); filmPixels = 0 or >= 2^31, n >= 2^31
+ * (PTSS_ERANGE). n = 0 returns PTSS_OK and launches nothing.
+ *
+ * Both calls are asynchronous on hipStream (NULL: the context's stream), leave no trace in frame state, own no bit of
+ * ptss_launched_kernels and serve sharded contexts. ptss_adaptive_launches: the calls of each kind that launched since ptss_create
+ * (ptss_film_launches does not count them). ptss_default_plan_params: minSamples 8, maxSamples 2^23, threshold 0.5 — design choices,
+ * not measurements. */
+int ptss_accumulate_paths_stats(ptss_context* ctx, const ptss_path_result* dev_results, const uint32_t* dev_index /* may be NULL */,
+                                size_t firstPixel, size_t n, ptss_film_entry* dev_film, unsigned long long* dev_moments, size_t filmPixels,
+                                ptss_uchar4* dev_pixels /* may be NULL */, ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_default_plan_params(ptss_plan_params* params);
+int ptss_plan_cdf_entries(size_t filmPixels, size_t* entries); /* >= filmPixels */
+int ptss_plan_samples(ptss_context* ctx, const ptss_film_entry* dev_film, const unsigned long long* dev_moments, size_t filmPixels,
+                      const ptss_plan_params* params, size_t n, unsigned long long* dev_cdf, uint32_t* dev_index /* n entries out */,
+                      ptss_plan_info* dev_info /* may be NULL */, void* hipStream);
+int ptss_adaptive_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] stats accumulates, [1] plans */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

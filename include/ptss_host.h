@@ -185,6 +185,21 @@ int ptss_probe_accumulate(const ptss_path_result* results, const uint32_t* index
                           ptss_film_entry* film, size_t filmPixels, ptss_uchar4* pixels, ptss_history_entry* history,
                           unsigned long long* rejected);
 
+/* ptss_accumulate_paths_stats on the host, with the LITERAL tone map: ptss_probe_accumulate's film, pixels and history, and
+ * moments[p] += qr^2 + qg^2 + qb^2 of every ray kept (csrc/ptadaptive.h squares). PTSS_HOST_EINVAL: ptss_probe_accumulate's, or a
+ * null moments with n > 0. */
+int ptss_probe_accumulate_stats(const ptss_path_result* results, const uint32_t* index /* may be NULL */, size_t firstPixel, size_t n,
+                                ptss_film_entry* film, unsigned long long* moments, size_t filmPixels, ptss_uchar4* pixels,
+                                ptss_history_entry* history, unsigned long long* rejected);
+/* ptss_plan_samples on the host (csrc/ptadaptive.h — the very operations the kernels evaluate; this build is the specification):
+ * cdf[0 .. filmPixels) the running sums of the weights, index[0 .. n) the plan, *info (may be NULL) what it found.
+ * PTSS_HOST_EINVAL: whatever ptss_plan_samples refuses, alignment aside. */
+int ptss_probe_plan_samples(const ptss_film_entry* film, const unsigned long long* moments, size_t filmPixels, const ptss_plan_params* params,
+                            size_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info);
+/* The weight csrc/ptadaptive.h gives one pixel (the plan's first step) and target i of n over a total (its third). */
+uint32_t ptss_probe_plan_weight(const ptss_film_entry* entry, unsigned long long moment, const ptss_plan_params* params);
+unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long long n, unsigned long long total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,25 @@ typedef struct ptss_film_entry {
     uint32_t samples;
 } ptss_film_entry;
 
+/* How ptss_plan_samples weighs a film pixel (ptss.h). minSamples >= 1: a pixel with fewer samples cannot be judged yet
+ * and outranks every measured one; maxSamples in [minSamples, 2^23]: a pixel with that many gets no more; threshold >= 0, finite: the
+ * standard error of the pixel's mean, in display steps (0..255), at or below which the pixel counts as converged. */
+typedef struct ptss_plan_params {
+    unsigned int structSize; /* sizeof(ptss_plan_params) as the caller compiled it */
+    uint32_t minSamples;
+    uint32_t maxSamples;
+    float threshold;
+} ptss_plan_params;
+
+/* What a plan found (ptss_plan_samples writes it on the device). totalWeight: the sum of the weights, at most 2^50; activePixels: weight
+ * > 0; unsampledPixels: below minSamples; cappedPixels: at or above maxSamples; uniform: 1 when the total was 0 and the budget was spread
+ * evenly instead. 32 B, 8-byte aligned. */
+typedef struct ptss_plan_info {
+    unsigned long long totalWeight;
+    uint32_t activePixels, unsampledPixels, cappedPixels, uniform;
+    uint32_t reserved[2];
+} ptss_plan_info;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -275,6 +294,11 @@ static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, samples
 static_assert(sizeof(ptss_path_options) == 16 && offsetof(ptss_path_options, schedule) == 4 && offsetof(ptss_path_options, maxWorkgroups) == 8 &&
                   offsetof(ptss_path_options, reserved) == 12,
               "ptss_path_options is four 32-bit words");
+static_assert(sizeof(ptss_plan_params) == 16 && offsetof(ptss_plan_params, minSamples) == 4 && offsetof(ptss_plan_params, threshold) == 12,
+              "ptss_plan_params is four 32-bit words");
+static_assert(sizeof(ptss_plan_info) == 32 && offsetof(ptss_plan_info, activePixels) == 8 && offsetof(ptss_plan_info, uniform) == 20 &&
+                  offsetof(ptss_plan_info, reserved) == 24,
+              "ptss_plan_info is four 64-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -296,6 +320,11 @@ _Static_assert(sizeof(ptss_film_entry) == 16 && offsetof(ptss_film_entry, sample
 _Static_assert(sizeof(ptss_path_options) == 16 && offsetof(ptss_path_options, schedule) == 4 && offsetof(ptss_path_options, maxWorkgroups) == 8 &&
                    offsetof(ptss_path_options, reserved) == 12,
                "ptss_path_options is four 32-bit words");
+_Static_assert(sizeof(ptss_plan_params) == 16 && offsetof(ptss_plan_params, minSamples) == 4 && offsetof(ptss_plan_params, threshold) == 12,
+               "ptss_plan_params is four 32-bit words");
+_Static_assert(sizeof(ptss_plan_info) == 32 && offsetof(ptss_plan_info, activePixels) == 8 && offsetof(ptss_plan_info, uniform) == 20 &&
+                   offsetof(ptss_plan_info, reserved) == 24,
+               "ptss_plan_info is four 64-bit words");
 #endif
 
 #ifdef __cplusplus
