@@ -24,6 +24,7 @@
 #include "ptstrip.h"
 #include "ptcamera.h"
 #include "ptadaptive.h"
+#include "ptlinear.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -153,6 +154,7 @@ struct ptss_context {
     hipStream_t filmStream = nullptr;                         // the stream of the latest film call with an index (ptss_film_rejected synchronises on it)
     bool filmIndexed = false;
     unsigned long long adaptiveLaunches[2] = {0, 0};          // ptss_accumulate_paths_stats, ptss_plan_samples calls that launched
+    unsigned long long linearLaunches[2] = {0, 0};            // ptss_accumulate_paths_linear, ptss_resolve_linear calls that launched
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -1422,6 +1424,68 @@ int ptss_adaptive_launches(const ptss_context* c, unsigned long long* out2) {
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->adaptiveLaunches[0];
     out2[1] = c->adaptiveLaunches[1];
+    return PTSS_OK;
+}
+
+// ---- the linear film (ptss_linear.hip; csrc/ptlinear.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_linear_params(ptss_linear_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_linear_params);
+    p->scaleLog2 = 20;
+    p->clampMax = 65536.f;
+    p->exposure = 1.f;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+int ptss_accumulate_paths_linear(ptss_context* c, const ptss_path_result* dev_results, const uint32_t* dev_index, size_t firstPixel, size_t n,
+                                 ptss_linear_entry* dev_film, size_t filmPixels, const ptss_linear_params* params, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_results || !dev_film) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if ((((uintptr_t)dev_results | (uintptr_t)dev_film) & 15u) || ((uintptr_t)dev_index & 3u))
+        return fail(PTSS_EINVAL, "results and film must be 16-byte aligned, dev_index 4-byte aligned");
+    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
+    if (!c->images[0].dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    HIP_TRY(ptss::launchLinearAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film,
+                                         (uint32_t)filmPixels, *params, c->dTotal + kFilmRejectedWord, &c->linearLaunches[0]));
+    if (dev_index) {
+        c->filmStream = st;
+        c->filmIndexed = true;
+    }
+    return PTSS_OK;
+}
+
+int ptss_resolve_linear(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                        ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (count == 0) return PTSS_OK;
+    if (!dev_film) return fail(PTSS_EINVAL, "null film with count > 0");
+    if ((((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_pixels & 3u))
+        return fail(PTSS_EINVAL, "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned");
+    if (firstPixel >= (size_t(1) << 31) || count >= (size_t(1) << 31) || firstPixel + count >= (size_t(1) << 31))
+        return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
+    HIP_TRY(ptss::launchLinearResolve(st, dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTable, dev_linear, dev_pixels, dev_history,
+                                      &c->linearLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_linear_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->linearLaunches[0];
+    out2[1] = c->linearLaunches[1];
     return PTSS_OK;
 }
 

@@ -220,6 +220,15 @@ hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint
 hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
                              const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
                              unsigned long long* launches);
+// the linear film (ptss_linear.hip; ptss_accumulate_paths_linear / ptss_resolve_linear). launchLinearAccumulate:
+// launchFilmAccumulate's results, index and counter, film = filmPixels x 32 B (ptss_linear_entry). launchLinearResolve: pixels firstPixel ..
+// firstPixel + count of the film into linear / history (16 B per pixel) and pixels, each or nullptr (not all three). params: checked by the
+// caller (ptlin::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+hipError_t launchLinearAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
+                                  uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
+                                  unsigned long long* launches);
+hipError_t launchLinearResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                               const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

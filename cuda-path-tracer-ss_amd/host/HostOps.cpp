@@ -77,3 +77,18 @@ bool writeTga(const char* filename, const ptss_uchar4* rgba, int width, int heig
     ok = (std::fclose(f) == 0) && ok;
     return ok;
 }
+
+// PFM: "PF", "width height", "-1.0" (little-endian), then three floats per pixel, bottom row first — the film's own order
+bool writePfm(const char* filename, const ptss_history_entry* rgbw, int width, int height) {
+    std::FILE* f = std::fopen(filename, "wb");
+    if (!f) return false;
+    std::vector<float> body((size_t)width * height * 3);
+    for (size_t i = 0; i < (size_t)width * height; ++i) {
+        body[3 * i + 0] = rgbw[i].r;
+        body[3 * i + 1] = rgbw[i].g;
+        body[3 * i + 2] = rgbw[i].b;
+    }
+    bool ok = std::fprintf(f, "PF\n%d %d\n-1.0\n", width, height) > 0 && std::fwrite(body.data(), sizeof(float), body.size(), f) == body.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok;
+}

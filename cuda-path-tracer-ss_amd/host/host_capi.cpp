@@ -13,6 +13,7 @@
 #include "ptupsample.h"
 #include "ptcamera.h"
 #include "ptadaptive.h"
+#include "ptlinear.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -668,6 +669,49 @@ uint32_t ptss_probe_plan_weight(const ptss_film_entry* entry, unsigned long long
 
 unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long long n, unsigned long long total) {
     return n ? ptad::target(i, n, total) : 0ull;
+}
+
+int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
+                                 size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected) {
+    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n > 0 && (!results || !film)) return PTSS_HOST_EINVAL;
+    if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
+    const ptlin::Scale sc = ptlin::scaleOf(*params);
+    unsigned long long dropped = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) {
+            ++dropped;
+            continue;
+        }
+        ptlin::u64 q[3];
+        const uint32_t flag = ptlin::sampleToFixed(results[i].radiance.x, results[i].radiance.y, results[i].radiance.z, sc, q);
+        film[p].r += q[0];
+        film[p].g += q[1];
+        film[p].b += q[2];
+        film[p].samples += 1u;
+        film[p].clamped += flag;
+    }
+    if (rejected) *rejected = dropped;
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_resolve_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                              ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history) {
+    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (count == 0) return PTSS_HOST_OK;
+    if (!film || firstPixel >= (size_t(1) << 31) || count >= (size_t(1) << 31) || firstPixel + count >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    const ptlin::Scale sc = ptlin::scaleOf(*params);
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        float lin[4], hist[4];
+        uint32_t px;
+        ptlin::resolve(film[p].r, film[p].g, film[p].b, film[p].samples, sc, nullptr, lin, &px, hist);
+        if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
+        if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
+        if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
+    }
+    return PTSS_HOST_OK;
 }
 
 }  // extern "C"

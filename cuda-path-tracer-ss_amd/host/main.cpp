@@ -33,6 +33,9 @@
 //                                   the same bytes), then ROUNDS planned rounds of width * height rays each go where ptss_plan_samples
 //                                   sends them (minSamples = --ticks, default maxSamples; threshold overrides the default's). Prints
 //                                   the final ptss_plan_info. ROUNDS = 0 writes the bytes of the run without the flag
+//             [--linear [exposure]] with --film: the samples go into a linear film (ptss_accumulate_paths_linear, default parameters) and
+//                                   ptss_resolve_linear with that exposure (default 1) makes the screenshot, image.pfm — the linear means,
+//                                   unexposed — beside it and, with --denoise, the history the filter takes. Not with --adaptive
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -60,6 +63,7 @@ int main(int argc, char* argv[]) {
     bool refill = false;   // --refill: the film's trace with the refill schedule
     int adaptive = -1;     // --adaptive: -1 absent, else the planned rounds behind the uniform ones
     float adaptiveThreshold = -1.f;   // ... and the plan's threshold when given
+    float linear = -1.f;   // --linear: -1 absent, else the exposure of the resolve
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -92,6 +96,11 @@ int main(int argc, char* argv[]) {
         else if (a == "--adaptive") {
             const int got = sscanf(next(), "%d,%f", &adaptive, &adaptiveThreshold);
             if (got < 1 || adaptive < 0 || (got == 2 && !(adaptiveThreshold >= 0.f && adaptiveThreshold < 1e30f))) { fprintf(stderr, "bad --adaptive (rounds[,threshold])\n"); return 2; }
+        }
+        else if (a == "--linear") {
+            linear = 1.f;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) linear = (float)atof(next());
+            if (!(linear >= 0.f && linear < 1e30f)) { fprintf(stderr, "bad --linear (exposure)\n"); return 2; }
         }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
@@ -143,6 +152,7 @@ int main(int argc, char* argv[]) {
     }
     if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
     if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
+    if (linear >= 0.f && (film.empty() || adaptive >= 0)) { fprintf(stderr, "--linear needs --film and no --adaptive\n"); return 2; }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -252,6 +262,9 @@ int main(int argc, char* argv[]) {
         const size_t n = (size_t)width * (size_t)height;
         void *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dFilm = nullptr, *dHist = nullptr, *dFeat = nullptr, *dOut = nullptr;
         void *dMoments = nullptr, *dCdf = nullptr, *dIndex = nullptr, *dInfo = nullptr;   // --adaptive
+        void *dLinear = nullptr, *dMeans = nullptr;   // --linear
+        ptss_linear_params linearParams;
+        PTSS_HANDLE(ptss_default_linear_params(&linearParams));
         const bool filter = denoise != -2;
         if (hipMalloc(&dRng, n * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dRays, n * sizeof(ptss_ray_query)) != hipSuccess ||
             hipMalloc(&dRes, n * sizeof(ptss_path_result)) != hipSuccess || hipMalloc(&dFilm, n * sizeof(ptss_film_entry)) != hipSuccess ||
@@ -271,12 +284,22 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
         }
+        if (linear >= 0.f) {
+            linearParams.exposure = linear;
+            if (hipMalloc(&dLinear, n * sizeof(ptss_linear_entry)) != hipSuccess || hipMemset(dLinear, 0, n * sizeof(ptss_linear_entry)) != hipSuccess ||
+                hipMalloc(&dMeans, n * sizeof(ptss_history_entry)) != hipSuccess) {
+                fprintf(stderr, "--linear: device buffers\n");
+                return 1;
+            }
+        }
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
             PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
             PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
                                              NULL));
-            if (adaptive >= 0) {
+            if (linear >= 0.f) {
+                PTSS_HANDLE(ptss_accumulate_paths_linear(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_linear_entry*)dLinear, n, &linearParams, NULL));
+            } else if (adaptive >= 0) {
                 PTSS_HANDLE(ptss_accumulate_paths_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm,
                                                         (unsigned long long*)dMoments, n, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             } else {
@@ -306,6 +329,18 @@ int main(int argc, char* argv[]) {
             printf("adaptive: rounds %d totalWeight %llu activePixels %u unsampledPixels %u cappedPixels %u uniform %u\n", adaptive, info.totalWeight,
                    info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
+        if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
+            PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
+                                            (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            std::vector<ptss_history_entry> means(n);
+            if (hipMemcpy(means.data(), dMeans, n * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--linear: read-back\n"); return 1; }
+            std::string name = out;
+            const size_t dot = name.rfind(".tga");
+            if (dot != std::string::npos && dot + 4 == name.size()) name.erase(dot);
+            name += ".pfm";
+            if (!writePfm(name.c_str(), means.data(), width, height)) fprintf(stderr, "--linear: cannot write %s\n", name.c_str());
+        }
         if (filter && ticks > 0) {   // the features of the film's pixel centres, then the filter over the film's display values
             ptss_denoise_params params;
             PTSS_HANDLE(ptss_default_denoise_params(&params));
@@ -324,7 +359,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, PATHS_LANE_PER_RAY, PATHS_REFILL,
+from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS, KERNEL_BITS, LINEAR_DTYPE, LinearEntry, LinearParams, PATH_RESULT_DTYPE, PATH_RNG_DTYPE, PATHS_LANE_PER_RAY, PATHS_REFILL,
                         PathOptions, PlanInfo, PlanParams, SCENE_LAYOUT_FIELDS,
                         SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
@@ -188,6 +188,9 @@ def host_lib():
         L.ptss_probe_plan_weight.restype = C.c_uint32
         L.ptss_probe_plan_target.argtypes = [C.c_ulonglong, C.c_ulonglong, C.c_ulonglong]
         L.ptss_probe_plan_target.restype = C.c_ulonglong
+        L.ptss_probe_accumulate_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LinearParams),
+                                                   C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_resolve_linear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_void_p, C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -281,6 +284,10 @@ def device_lib():
         L.ptss_plan_cdf_entries.argtypes = [C.c_size_t, C.POINTER(C.c_size_t)]
         L.ptss_plan_samples.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(PlanParams), C.c_size_t, vp, vp, vp, vp]
         L.ptss_adaptive_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_linear_params.argtypes = [C.POINTER(LinearParams)]
+        L.ptss_accumulate_paths_linear.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(LinearParams), vp]
+        L.ptss_resolve_linear.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp]
+        L.ptss_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -652,6 +659,65 @@ def plan_cdf_entries(film_pixels):
     out = C.c_size_t(0)
     _check(device_lib().ptss_plan_cdf_entries(int(film_pixels), C.byref(out)))
     return int(out.value)
+
+
+# ---- the linear film (ptss_accumulate_paths_linear / ptss_resolve_linear) ----
+def linear_params(scale_log2=20, clamp_max=65536.0, exposure=1.0):
+    """A ptss_linear_params; the defaults are ptss_default_linear_params' (design choices, not measurements)."""
+    p = LinearParams()
+    p.structSize = C.sizeof(LinearParams)
+    p.scaleLog2, p.clampMax, p.exposure, p.reserved = int(scale_log2), float(clamp_max), float(exposure), 0
+    return p
+
+
+def _linear_outputs(P, linear, pixels, history):
+    """The three outputs of a resolve: None (NULL), True (zeros beforehand) or the buffer's content beforehand, as (P, 4) rows."""
+    ln = None if linear is None else (np.zeros((P, 4), dtype=np.float32) if linear is True else _rows(linear, HISTORY_DTYPE, 4, np.float32, "linear", copy=True))
+    px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
+    hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+    if any(a is not None and len(a) != P for a in (ln, px, hs)):
+        raise ValueError("linear, pixels and history: one entry per film pixel")
+    return ln, px, hs
+
+
+def _linear_range(P, first_pixel, count):
+    first_pixel = int(first_pixel)
+    count = P - first_pixel if count is None else int(count)
+    if first_pixel < 0 or count < 0 or first_pixel + count > P:
+        raise ValueError("first_pixel + count leaves the film")
+    return first_pixel, count
+
+
+def probe_accumulate_linear(results, film, first_pixel=0, index=None, params=None):
+    """ptss_accumulate_paths_linear on the host (csrc/ptlinear.h; the specification of the device's film) -> (film afterwards (P,)
+    LINEAR_DTYPE, number of index entries dropped). film: (P,) LINEAR_DTYPE or (P, 4) uint64 (not modified)."""
+    r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+    n = len(r)
+    idx = _film_index(index, n)
+    f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True)
+    params = params if params is not None else linear_params()
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_accumulate_linear(r.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if idx is not None else None,
+                                                 int(first_pixel), n, f.ctypes.data_as(C.c_void_p), len(f), C.byref(params), C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_accumulate_linear: {rc}")
+    return f.view(LINEAR_DTYPE).reshape(-1), int(rejected.value)
+
+
+def probe_resolve_linear(film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+    """ptss_resolve_linear on the host, with the literal tone map -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample
+    count, pixels (P, 4) uint8, history (P,) HISTORY_DTYPE), each None when not asked for. film: (P,) LINEAR_DTYPE or (P, 4) uint64;
+    count: None = to the film's end; linear / pixels / history: None (not written), True (zeros beforehand) or the content beforehand."""
+    f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
+    P = len(f)
+    first_pixel, count = _linear_range(P, first_pixel, count)
+    ln, px, hs = _linear_outputs(P, linear, pixels, history)
+    params = params if params is not None else linear_params()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = host_lib().ptss_probe_resolve_linear(ptr(f), first_pixel, count, C.byref(params), ptr(ln), ptr(px), ptr(hs))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_resolve_linear: {rc}")
+    return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
 
 def default_denoise_params(**overrides):
@@ -1551,6 +1617,75 @@ class Renderer:
         """ptss_adaptive_launches: (accumulate_paths_stats, plan_samples calls that launched since the context was created)."""
         out = (C.c_ulonglong * 2)()
         _check(device_lib().ptss_adaptive_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
+
+    # --- the linear film (ptss_accumulate_paths_linear / ptss_resolve_linear) ------------------
+    def accumulate_paths_linear(self, results, film, first_pixel=0, index=None, params=None):
+        """ptss_accumulate_paths_linear: the linear radiance of `results` added to the fixed-point film.
+        numpy: results (N,) PATH_RESULT_DTYPE or (N, 4) float32; film (P,) LINEAR_DTYPE or (P, 4) uint64 (not modified) -> the film
+        afterwards, (P,) LINEAR_DTYPE. torch: results (N, 4) float32, film (P, 4) int64 UPDATED IN PLACE, index (N,) int32 or None, all
+        on one device -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_film = self._torch_ptr(film, "film", "int64", 4, dev)
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_accumulate_paths_linear(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, film.shape[0], C.byref(params), C.c_void_p(stream)))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        idx = _film_index(index, n)
+        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True)
+        P = len(f)
+        if n == 0:
+            _check(L.ptss_accumulate_paths_linear(self._ctx, None, None, int(first_pixel), 0, None, P, C.byref(params), None))
+        else:
+            self._round_trip([r, idx, f],
+                             lambda d: _check(L.ptss_accumulate_paths_linear(self._ctx, d[0], d[1], int(first_pixel), n, d[2], P, C.byref(params), None)),
+                             read=(2,))
+        return f.view(LINEAR_DTYPE).reshape(-1)
+
+    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+        """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
+        numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64; linear / pixels / history: None (NULL), True (zeros beforehand) or the buffer's
+        content beforehand -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample count, pixels (P, 4) uint8, history (P,)
+        HISTORY_DTYPE), each None when NULL. torch: film (P, 4) int64, linear (P, 4) float32 or None, pixels (P, 4) uint8 or None,
+        history (P, 4) float32 or None, all on one device, WRITTEN IN PLACE -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        if type(film).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, P = film.device, film.shape[0]
+            first_pixel, count = _linear_range(P, first_pixel, count)
+            d_film = self._torch_ptr(film, "film", "int64", 4)
+            d_ln = self._torch_ptr(linear, "linear", "float32", 4, dev, P) if linear is not None else None
+            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
+            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_resolve_linear(self._ctx, d_film, first_pixel, count, C.byref(params), d_ln, d_px, d_hs, C.c_void_p(stream)))
+            return None
+        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
+        P = len(f)
+        first_pixel, count = _linear_range(P, first_pixel, count)
+        ln, px, hs = _linear_outputs(P, linear, pixels, history)
+        if count == 0:
+            _check(L.ptss_resolve_linear(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
+        else:
+            self._round_trip([f, ln, px, hs],
+                             lambda d: _check(L.ptss_resolve_linear(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None)),
+                             read=(1, 2, 3))
+        return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+    def linear_launches(self):
+        """ptss_linear_launches: (accumulate_paths_linear, resolve_linear calls that launched since the context was created)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_linear_launches(self._ctx, out))
         return int(out[0]), int(out[1])
 
     def film_launches(self):

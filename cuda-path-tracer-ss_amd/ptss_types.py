@@ -129,6 +129,17 @@ class PlanInfo(C.Structure):   # ptss_plan_info: what a plan found
                 ("uniform", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class LinearEntry(C.Structure):   # ptss_linear_entry: the fixed-point radiance sums of one linear-film pixel and their counts
+    _fields_ = [("r", C.c_ulonglong), ("g", C.c_ulonglong), ("b", C.c_ulonglong), ("samples", C.c_uint32), ("clamped", C.c_uint32)]
+
+
+LINEAR_DTYPE = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("samples", np.uint32), ("clamped", np.uint32)])
+
+
+class LinearParams(C.Structure):   # ptss_linear_params: how a linear film counts and shows radiance
+    _fields_ = [("structSize", C.c_uint), ("scaleLog2", C.c_int), ("clampMax", C.c_float), ("exposure", C.c_float), ("reserved", C.c_uint)]
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -174,6 +185,8 @@ assert C.sizeof(PathResult) == 16 == PATH_RESULT_DTYPE.itemsize and PathResult.b
 assert C.sizeof(FilmCamera) == 68 and FilmCamera.camera.offset == 8 and FilmCamera.width.offset == 48 and FilmCamera.jitter.offset == 64
 assert C.sizeof(FilmEntry) == 16 == FILM_DTYPE.itemsize and FilmEntry.samples.offset == 12 == FILM_DTYPE.fields["samples"][1]
 assert C.sizeof(PlanParams) == 16 and PlanParams.threshold.offset == 12 and C.sizeof(PlanInfo) == 32 and PlanInfo.uniform.offset == 20
+assert C.sizeof(LinearEntry) == 32 == LINEAR_DTYPE.itemsize and LinearEntry.samples.offset == 24 == LINEAR_DTYPE.fields["samples"][1]
+assert LinearEntry.clamped.offset == 28 == LINEAR_DTYPE.fields["clamped"][1] and C.sizeof(LinearParams) == 20 and LinearParams.reserved.offset == 16
 
 
 def struct_to_dict(s):

@@ -398,6 +398,47 @@ int ptss_plan_samples(ptss_context* ctx, const ptss_film_entry* dev_film, const 
                       ptss_plan_info* dev_info /* may be NULL */, void* hipStream);
 int ptss_adaptive_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] stats accumulates, [1] plans */
 
+/* The linear film: ptss_trace_paths' radiance accumulated as it is — not tone-mapped sample by sample — for probes,
+ * light-map texels, panoramas and every use whose exposure is chosen afterwards. A pixel holds 64-bit unsigned fixed-point sums
+ * (ptss_linear_entry), so the film is exact and the same bytes for every order of the samples, for every index, duplicates included, and
+ * for every split of a batch into calls. csrc/ptlinear.h has the arithmetic; its host build (ptss_probe_accumulate_linear,
+ * ptss_probe_resolve_linear) is the specification and the device agrees with it byte for byte.
+ *
+ * ptss_accumulate_paths_linear: for ray i, pixel p as in ptss_accumulate_paths, each channel x of dev_results[i].radiance becomes
+ *   q = (u64) round-to-nearest-even(clamp'(x) * 2^scaleLog2), clamp': NaN -> 0, x < 0 (-inf and -0 included) -> 0, x > clampMax (+inf
+ *   included) -> clampMax,
+ * and is added to dev_film[p].r, .g, .b; .samples grows by 1, and .clamped by 1 when a channel was NaN or above clampMax (negative
+ * channels do not count). q <= 2^40, so the sums stay below 2^63 while samples < 2^23. Without an index: one kernel, a plain
+ * read-modify-write of the 32-byte entry. With an index: the lanes of a wave that hold one pixel side by side are summed on chip and
+ * the run's first lane alone issues four 64-bit integer atomics (r, g, b, samples | clamped << 32). Index entries >= filmPixels are
+ * dropped and counted in ptss_film_rejected. The caller zero-fills a new film. Nothing is resolved by this call.
+ *
+ * ptss_resolve_linear: for pixels firstPixel .. firstPixel + count of dev_film (the caller guarantees they exist), with N = samples:
+ *   N = 0: dev_linear[p] = (0, 0, 0, 0), dev_pixels[p] = (0, 0, 0, 255), dev_history[p] = (0, 0, 0, 0). Otherwise, per channel,
+ *   m = (sum + N / 2) / N in unsigned 64-bit integers, mean = (float)m * 2^-scaleLog2 (round to nearest even, then an exact multiply),
+ *   e = mean * exposure; dev_linear[p] = {mean_r, mean_g, mean_b, (float)N} (unexposed), dev_pixels[p] = the frame's 8-bit tone map of e
+ *   (the context's thresholds) with alpha 255 — the tone map of the mean, not the mean of tone maps —, dev_history[p] =
+ *   {255 pow(clamp(e, 0, 1), 1 / 2.2) per channel, (float)N}: the entry ptss_denoise_history, ptss_reproject and ptss_upsample take.
+ * Each of the three outputs may be NULL; all three NULL is PTSS_OK with nothing launched. One streaming kernel.
+ *
+ * Both calls are asynchronous on hipStream (NULL: the context's stream), leave no trace in frame state, own no bit of
+ * ptss_launched_kernels and serve sharded contexts. Refused without touching the device and without counting: everything
+ * ptss_accumulate_paths refuses; null params, a wrong structSize, scaleLog2 outside 0 .. 32, a clampMax that is not finite and positive
+ * or has clampMax * 2^scaleLog2 > 2^40, an exposure that is negative or not finite, a non-zero reserved, a pointer that is not aligned
+ * — 16 bytes for results, film, linear and history, 4 for index and pixels — (PTSS_EINVAL, also with n = 0 or count = 0 for the
+ * parameters); the ranges ptss_accumulate_paths refuses, firstPixel + count >= 2^31 (PTSS_ERANGE). n = 0 and count = 0 return PTSS_OK.
+ * ptss_linear_launches: the calls of each kind that launched since ptss_create. ptss_default_linear_params: scaleLog2 20, clampMax
+ * 65536, exposure 1 — design choices, not measurements. A caller who also wants ptss_plan_samples keeps calling
+ * ptss_accumulate_paths_stats on the same results: the plan is defined on display steps. */
+int ptss_default_linear_params(ptss_linear_params* params);
+int ptss_accumulate_paths_linear(ptss_context* ctx, const ptss_path_result* dev_results, const uint32_t* dev_index /* may be NULL */,
+                                 size_t firstPixel, size_t n, ptss_linear_entry* dev_film, size_t filmPixels, const ptss_linear_params* params,
+                                 void* hipStream);
+int ptss_resolve_linear(ptss_context* ctx, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                        ptss_history_entry* dev_linear /* may be NULL */, ptss_uchar4* dev_pixels /* may be NULL */,
+                        ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_linear_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] accumulates, [1] resolves */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

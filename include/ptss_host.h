@@ -200,6 +200,17 @@ int ptss_probe_plan_samples(const ptss_film_entry* film, const unsigned long lon
 uint32_t ptss_probe_plan_weight(const ptss_film_entry* entry, unsigned long long moment, const ptss_plan_params* params);
 unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long long n, unsigned long long total);
 
+/* ptss_accumulate_paths_linear on the host (csrc/ptlinear.h — the very operations the kernels evaluate; this build is the
+ * specification): every ray's fixed-point sample added to film[p], duplicates included. *rejected (may be NULL; set, not added to):
+ * index entries >= filmPixels. PTSS_HOST_EINVAL: whatever ptss_accumulate_paths_linear refuses, alignment aside. */
+int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t* index /* may be NULL */, size_t firstPixel, size_t n,
+                                 ptss_linear_entry* film, size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected);
+/* ptss_resolve_linear on the host, with the LITERAL tone map (like ptss_probe_accumulate it needs no thresholds): pixels firstPixel ..
+ * firstPixel + count of film into linear, pixels and history (each may be NULL). PTSS_HOST_EINVAL: whatever ptss_resolve_linear
+ * refuses, alignment aside. */
+int ptss_probe_resolve_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                              ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
+
 #ifdef __cplusplus
 }
 #endif

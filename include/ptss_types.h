@@ -241,6 +241,26 @@ typedef struct ptss_plan_info {
     uint32_t reserved[2];
 } ptss_plan_info;
 
+/* One pixel of a linear film (ptss_accumulate_paths_linear): the sums of the samples' linear radiance as unsigned
+ * fixed point with ptss_linear_params.scaleLog2 fraction bits, how many samples there are, and how many of them had a channel that was
+ * NaN or above clampMax. 32 B, 16-byte aligned access; a new film is all zero; samples < 2^23 keeps the sums below 2^63. */
+typedef struct ptss_linear_entry {
+    unsigned long long r, g, b;
+    uint32_t samples;
+    uint32_t clamped;
+} ptss_linear_entry;
+
+/* How a linear film counts and shows radiance (ptss.h). scaleLog2 in [0, 32]: the fraction bits of the sums; clampMax > 0, finite, with
+ * clampMax * 2^scaleLog2 <= 2^40: a channel above it counts as clampMax; exposure >= 0, finite: what ptss_resolve_linear multiplies the
+ * mean by in front of the tone map (the linear means stay unexposed). */
+typedef struct ptss_linear_params {
+    unsigned int structSize; /* sizeof(ptss_linear_params) as the caller compiled it */
+    int scaleLog2;
+    float clampMax;
+    float exposure;
+    unsigned int reserved;   /* 0 */
+} ptss_linear_params;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -299,6 +319,12 @@ static_assert(sizeof(ptss_plan_params) == 16 && offsetof(ptss_plan_params, minSa
 static_assert(sizeof(ptss_plan_info) == 32 && offsetof(ptss_plan_info, activePixels) == 8 && offsetof(ptss_plan_info, uniform) == 20 &&
                   offsetof(ptss_plan_info, reserved) == 24,
               "ptss_plan_info is four 64-bit words");
+static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g) == 8 && offsetof(ptss_linear_entry, samples) == 24 &&
+                  offsetof(ptss_linear_entry, clamped) == 28,
+              "ptss_linear_entry is two 16-byte rows");
+static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
+                  offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
+              "ptss_linear_params is five 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -325,6 +351,12 @@ _Static_assert(sizeof(ptss_plan_params) == 16 && offsetof(ptss_plan_params, minS
 _Static_assert(sizeof(ptss_plan_info) == 32 && offsetof(ptss_plan_info, activePixels) == 8 && offsetof(ptss_plan_info, uniform) == 20 &&
                    offsetof(ptss_plan_info, reserved) == 24,
                "ptss_plan_info is four 64-bit words");
+_Static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g) == 8 && offsetof(ptss_linear_entry, samples) == 24 &&
+                   offsetof(ptss_linear_entry, clamped) == 28,
+               "ptss_linear_entry is two 16-byte rows");
+_Static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
+                   offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
+               "ptss_linear_params is five 32-bit words");
 #endif
 
 #ifdef __cplusplus
