@@ -2,15 +2,15 @@
 // that also keeps the second moment of its tone-mapped samples, and the plan that turns film and moments into the next round's index
 // without a host round trip (csrc/ptadaptive.h has the arithmetic; its host build is the specification).
 //
-// The accumulate kernels write the bytes the kernels of ptss_film.hip write (the same ptq::quantize_fast, the same table, resolveEntry
-// restated here so that file's code objects stay as they are). With an index, the lanes of a wave that hold one pixel side by side — a
-// plan's index is sorted, so all of them do — are summed on chip first and the run's head lane alone issues the atomics.
+// The accumulate kernels write the bytes the kernels of ptss_film.hip write (the same ptq::quantize_fast, the same table, the same
+// resolveEntry: csrc/ptfilm.h). With an index, the lanes of a wave that hold one pixel side by side — a plan's index is sorted, so all
+// of them do — are summed on chip first (ptfilm.h sumRunsToHead) and the run's head lane alone issues the atomics.
 //
 // The scan is reduce / scan of the tile sums / downsweep: three launches, no workgroup waits for another. The weight is computed inside
 // both loads; no weight array exists.
 #include "ptss_device.h"
 #include "ptadaptive.h"
-#include "ptdenoise.h"
+#include "ptfilm.h"
 #include "ptquant.h"
 
 namespace ptss {
@@ -23,30 +23,6 @@ constexpr int kScanPerLane = ptad::kScanTile / kScanBlock;   // 8 pixels per lan
 constexpr int kScanWaves = kScanBlock / 64;
 constexpr int kSumsBlock = 1024;                             // the one workgroup that scans the tile sums
 static_assert(kScanPerLane * kScanBlock == ptad::kScanTile && kScanBlock % 64 == 0, "a tile is whole waves of whole rounds");
-
-__device__ __forceinline__ uint32_t laneId() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// dropped entries of one wave, counted with one atomic (ptss_film.hip's countDropped)
-__device__ __forceinline__ void countDroppedStats(bool dropped, unsigned long long* rejected) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(dropped);
-    if (m == 0ull) return;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (dropped && before == 0u) atomicAdd(rejected, (unsigned long long)__popcll(m));
-}
-
-// finishPath's display pixel and ptdn::displayValue of one film entry (ptss_film.hip's resolveEntry, restated)
-__device__ __forceinline__ void resolveStatsEntry(uint4 e, uint32_t p, ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    const float inv = ptm::rcp((float)e.w);   // 1.f / (float)samples, correctly rounded
-    if (pixels) {
-        const uint32_t px = (uint32_t)(unsigned char)(e.x * inv + 0.5f) | ((uint32_t)(unsigned char)(e.y * inv + 0.5f) << 8) |
-                            ((uint32_t)(unsigned char)(e.z * inv + 0.5f) << 16) | (255u << 24);
-        reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    }
-    if (history) {
-        const ptv::vec3 c = ptdn::displayValue(e.x, e.y, e.z, inv);
-        history[p] = float4{c.x, c.y, c.z, (float)e.w};
-    }
-}
 
 // without an index: ray i belongs to pixel firstPixel + i alone — a plain read-modify-write of the entry and of the moment
 __global__ __launch_bounds__(kStatsBlock) void statsAccumulateKernel(const float4* __restrict__ results, uint32_t firstPixel, uint32_t n,
@@ -65,7 +41,7 @@ __global__ __launch_bounds__(kStatsBlock) void statsAccumulateKernel(const float
     e.w += 1u;
     film[p] = e;
     moments[p] += (u64)ptad::squares(qr, qg, qb);
-    resolveStatsEntry(e, p, pixels, history);
+    resolveEntry(e, p, pixels, history);
 }
 
 // with an index: the runs of equal, in-range pixels inside a wave are summed by a segmented reduction towards the run's first lane,
@@ -79,7 +55,7 @@ __global__ __launch_bounds__(kStatsBlock) void statsScatterKernel(const float4* 
     const bool inBatch = i < n;
     const uint32_t p = inBatch ? index[i] : 0u;
     const bool ok = inBatch && p < filmPixels;
-    countDroppedStats(inBatch && !ok, rejected);
+    countDropped(inBatch && !ok, rejected);
     const uint32_t key = ok ? p : 0xffffffffu;   // (a film has fewer than 2^31 pixels) lanes without a pixel carry zeros and never lead a store
     uint32_t rg = 0u, bc = 0u, sq = 0u;
     if (ok) {
@@ -89,23 +65,15 @@ __global__ __launch_bounds__(kStatsBlock) void statsScatterKernel(const float4* 
         bc = qb | (1u << 16);
         sq = ptad::squares(qr, qg, qb);
     }
-    const uint32_t lane = laneId();
-    const uint32_t before = (uint32_t)__shfl_up((int)key, 1, 64);
-    const bool head = lane == 0u || key != before;
-    const unsigned long long heads = __builtin_amdgcn_ballot_w64(head);
-    // heads strictly above this lane, bit k - 1 = lane + k: lane + d joins while none of lanes lane + 1 .. lane + d starts a run
-    const unsigned long long above = lane < 63u ? heads >> (lane + 1u) : ~0ull;
-#pragma unroll
-    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+    const bool head = sumRunsToHead(key, [&](uint32_t d, bool joins) {
         const uint32_t rg2 = (uint32_t)__shfl_down((int)rg, d, 64), bc2 = (uint32_t)__shfl_down((int)bc, d, 64),
                        sq2 = (uint32_t)__shfl_down((int)sq, d, 64);
-        const bool joins = lane + d < 64u && (above & ((1ull << d) - 1ull)) == 0ull;
         if (joins) {
             rg += rg2;
             bc += bc2;
             sq += sq2;
         }
-    }
+    });
     if (!(head && ok)) return;
     uint32_t* e = film + 4 * (size_t)p;
     atomicAdd(e + 0, rg & 0xffffu);
@@ -123,7 +91,7 @@ __global__ __launch_bounds__(kStatsBlock) void statsResolveKernel(const uint32_t
     const uint32_t p = i < n ? index[i] : 0xffffffffu;
     const uint32_t before = (uint32_t)__shfl_up((int)p, 1, 64);
     if (p >= filmPixels || (laneId() != 0u && p == before)) return;
-    resolveStatsEntry(film[p], p, pixels, history);
+    resolveEntry(film[p], p, pixels, history);
 }
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------------------
@@ -281,12 +249,10 @@ __global__ __launch_bounds__(kStatsBlock) void planIndexKernel(const u64* __rest
                              : ptad::pixelOf(cdf, filmPixels, ptad::target((u64)i, (u64)n, total));
 }
 
-static inline unsigned statsBlocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
-
 hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
                                  unsigned long long* moments, uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable,
                                  unsigned long long* rejected, unsigned long long* launches) {
-    const dim3 grid(statsBlocksFor(n, kStatsBlock)), block(kStatsBlock);
+    const dim3 grid(filmBlocksFor(n, kStatsBlock)), block(kStatsBlock);
     if (!index) {
         hipLaunchKernelGGL(statsAccumulateKernel, grid, block, 0, st, static_cast<const float4*>(results), firstPixel, n, static_cast<uint4*>(film),
                            moments, pixels, static_cast<float4*>(history), quantTable);
@@ -317,7 +283,7 @@ hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned lo
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(planDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(planIndexKernel, dim3(statsBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
+    hipLaunchKernelGGL(planIndexKernel, dim3(filmBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
     e = hipGetLastError();
     if (e == hipSuccess) ++*launches;
     return e;

@@ -1077,19 +1077,23 @@ int ptss_guard_flags(const ptss_context* c, unsigned int* out) {
     return PTSS_OK;
 }
 
+// the calls on the caller's stream (queries, features, film): counts and indices travel as 32-bit words, and a null stream is the context's
+static inline bool fits31(unsigned long long v) { return v < (1ull << 31); }
+static inline hipStream_t streamOf(const ptss_context* c, void* hipStream) { return hipStream ? static_cast<hipStream_t>(hipStream) : c->stream; }
+
 // ptss_intersect / ptss_occluded: the context's own scene image (images[0]; the query kernel is exact on every image, so the
 // camera's range plays no part), no frame state, the caller's stream
 static int rayQuery(ptss_context* c, bool any, const ptss_ray_query* rays, void* out, size_t n, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (n == 0) return PTSS_OK;
     if (!rays || !out) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     if (((uintptr_t)rays | (uintptr_t)out) & (any ? 3u : 15u) || (uintptr_t)rays & 15u)
         return fail(PTSS_EINVAL, "rays and hits must be 16-byte aligned, verdicts 4-byte aligned");
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     HIP_TRY(ptss::launchQuery(st, any, im.dBlob, im.layout, im.inLds, rays, out, (uint32_t)n, c->gridCap * ptss::kShards,
                               &c->launchedKernels));
     return PTSS_OK;
@@ -1112,7 +1116,7 @@ int ptss_render_features(ptss_context* c, ptss_pixel_feature* dev_features, void
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     HIP_TRY(ptss::launchFeatures(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, c->numPixels,
                                  c->gridCap * ptss::kShards, &c->launchedKernels));
@@ -1135,7 +1139,7 @@ int ptss_render_features_motion(ptss_context* c, const ptss_triangle* dev_triang
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     HIP_TRY(ptss::launchFeaturesMotion(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, c->numPixels,
                                        c->gridCap * ptss::kShards, dev_triangles_prev, count ? (uint32_t)first : 0u, (uint32_t)count, dev_motion,
@@ -1154,7 +1158,7 @@ int ptss_render_features_specular(ptss_context* c, int maxSteps, ptss_pixel_feat
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     HIP_TRY(ptss::launchFeaturesSpecular(st, im.dBlob, im.layout, im.inLds, c->tile, eyeParams(c), defaultColor, dev_features, dev_steps,
                                          c->numPixels, maxSteps, c->gridCap * ptss::kShards, c->specularFeatureLaunches));
@@ -1177,7 +1181,7 @@ int ptss_seed_path_rng(ptss_context* c, ptss_path_rng* dev_rng, size_t n, unsign
     if (n == 0) return PTSS_OK;
     if (!dev_rng) return fail(PTSS_EINVAL, "dev_rng is null with n > 0");
     if ((uintptr_t)dev_rng & 3u) return fail(PTSS_EINVAL, "dev_rng must be 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     if (firstSequence > (1ull << 32) || firstSequence + n > (1ull << 32)) return fail(PTSS_ERANGE, "firstSequence + n must not exceed 2^32");
     HIP_TRY(hipSetDevice(c->cfg.device));
     if (!c->dPathJumpTable) {
@@ -1192,7 +1196,7 @@ int ptss_seed_path_rng(ptss_context* c, ptss_path_rng* dev_rng, size_t n, unsign
         }
         c->dPathJumpTable = dTable;
     }
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     HIP_TRY(ptss::launchPathRngSeed(st, dev_rng, (uint32_t)n, seed, (uint32_t)firstSequence, skip, c->dPathJumpTable));
     return PTSS_OK;
 }
@@ -1208,11 +1212,11 @@ static int tracePaths(ptss_context* c, const ptss_ray_query* dev_rays, ptss_path
     if (!dev_rays || !dev_rng || !dev_results) return fail(PTSS_EINVAL, "null buffer with n > 0");
     if ((((uintptr_t)dev_rays | (uintptr_t)dev_results) & 15u) || ((uintptr_t)dev_rng & 3u))
         return fail(PTSS_EINVAL, "rays and results must be 16-byte aligned, dev_rng 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     if (!refill) {
         HIP_TRY(ptss::launchPathQuery(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_rng, dev_results, (uint32_t)n, (int)maxIterations, defaultColor,
@@ -1281,50 +1285,75 @@ int ptss_path_launches(const ptss_context* c, unsigned long long* out2) {
 }
 
 // ---- the film of a path query (ptss_film.hip). Like the queries: images[0] at most, no frame state, the caller's stream ----
-int ptss_generate_rays(ptss_context* c, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index, size_t n, ptss_path_rng* dev_rng,
-                       ptss_ray_query* dev_rays, void* hipStream) {
-    if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (const char* what = ptcam::cameraError(film)) return fail(PTSS_EINVAL, what);
-    const unsigned long long filmPixels = (unsigned long long)film->width * (unsigned long long)film->height;
-    if (filmPixels >= (1ull << 31)) return fail(PTSS_ERANGE, "width * height must be below 2^31");
+// What the film calls share behind their own ctx and params checks, in the order each of them checks it: the film's size, n == 0 (nothing
+// to do: PTSS_OK with go == false), the call's own verdict on its buffers (`badBuffers`: null first, then alignment; evaluated by the caller,
+// reported here), n, firstPixel + n against the film where there is no index, the scene image where the call reads it, device and stream.
+struct FilmCall {
+    bool go = false;
+    hipStream_t st = nullptr;
+    uint32_t firstPixel = 0, n = 0, filmPixels = 0;   // firstPixel as the launch takes it: 0 with an index
+    const float* quantTable = nullptr;                // the frame's own thresholds (frameBuffers); with a scene image only
+};
+
+static const float* quantTableOf(const SceneImage& im) { return reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant); }
+
+static int filmCall(ptss_context* c, FilmCall* f, unsigned long long filmPixels, const char* filmTooLarge, size_t n, const char* badBuffers,
+                    const uint32_t* dev_index, size_t firstPixel, bool readsImage, void* hipStream) {
+    if (!fits31(filmPixels)) return fail(PTSS_ERANGE, filmTooLarge);
     if (n == 0) return PTSS_OK;
-    if (!dev_rng || !dev_rays) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if (((uintptr_t)dev_rays & 15u) || (((uintptr_t)dev_rng | (uintptr_t)dev_index) & 3u))
-        return fail(PTSS_EINVAL, "rays must be 16-byte aligned, dev_rng and dev_index 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (badBuffers) return fail(PTSS_EINVAL, badBuffers);
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
+    const SceneImage& im = c->images[0];
+    if (readsImage && !im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
-    HIP_TRY(ptss::launchFilmRays(st, ptcam::filmOf(*film), dev_index ? 0u : (uint32_t)firstPixel, dev_index, (uint32_t)n, dev_rng, dev_rays,
-                                 c->dTotal + kFilmRejectedWord, &c->filmLaunches[0]));
+    *f = FilmCall{true, streamOf(c, hipStream), dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, (uint32_t)filmPixels,
+                  readsImage ? quantTableOf(im) : nullptr};
+    return PTSS_OK;
+}
+
+// a launch with an index may count rejected entries: ptss_film_rejected synchronises on its stream
+static void noteFilmIndex(ptss_context* c, const uint32_t* dev_index, hipStream_t st) {
     if (dev_index) {
         c->filmStream = st;
         c->filmIndexed = true;
     }
+}
+
+static const char* const kNullBuffer = "null buffer with n > 0";
+
+int ptss_generate_rays(ptss_context* c, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index, size_t n, ptss_path_rng* dev_rng,
+                       ptss_ray_query* dev_rays, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptcam::cameraError(film)) return fail(PTSS_EINVAL, what);
+    const char* bad = !dev_rng || !dev_rays ? kNullBuffer
+                      : ((uintptr_t)dev_rays & 15u) || (((uintptr_t)dev_rng | (uintptr_t)dev_index) & 3u)
+                          ? "rays must be 16-byte aligned, dev_rng and dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, (unsigned long long)film->width * (unsigned long long)film->height, "width * height must be below 2^31", n, bad, dev_index,
+                    firstPixel, false, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchFilmRays(f.st, ptcam::filmOf(*film), f.firstPixel, dev_index, f.n, dev_rng, dev_rays, c->dTotal + kFilmRejectedWord,
+                                 &c->filmLaunches[0]));
+    noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
 
 int ptss_accumulate_paths(ptss_context* c, const ptss_path_result* dev_results, const uint32_t* dev_index, size_t firstPixel, size_t n,
                           ptss_film_entry* dev_film, size_t filmPixels, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
-    if (n == 0) return PTSS_OK;
-    if (!dev_results || !dev_film) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if ((((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) || (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u))
-        return fail(PTSS_EINVAL, "results, film and history must be 16-byte aligned, dev_index and dev_pixels 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
-    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
-    const SceneImage& im = c->images[0];
-    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
-    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
-    HIP_TRY(ptss::launchFilmAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film, (uint32_t)filmPixels,
-                                       dev_pixels, dev_history, quantTable, c->dTotal + kFilmRejectedWord, &c->filmLaunches[1]));
-    if (dev_index) {
-        c->filmStream = st;
-        c->filmIndexed = true;
-    }
+    const char* bad = !dev_results || !dev_film ? kNullBuffer
+                      : (((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) ||
+                              (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u)
+                          ? "results, film and history must be 16-byte aligned, dev_index and dev_pixels 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchFilmAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, f.filmPixels, dev_pixels, dev_history, f.quantTable,
+                                       c->dTotal + kFilmRejectedWord, &c->filmLaunches[1]));
+    noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
 
@@ -1333,11 +1362,11 @@ int ptss_ray_features(ptss_context* c, const ptss_ray_query* dev_rays, ptss_pixe
     if (n == 0) return PTSS_OK;
     if (!dev_rays || !dev_features) return fail(PTSS_EINVAL, "null buffer with n > 0");
     if (((uintptr_t)dev_rays | (uintptr_t)dev_features) & 15u) return fail(PTSS_EINVAL, "rays and features must be 16-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     HIP_TRY(ptss::launchRayFeatures(st, im.dBlob, im.layout, im.inLds, dev_rays, defaultColor, dev_features, (uint32_t)n, c->gridCap * ptss::kShards,
                                     &c->filmLaunches[2]));
@@ -1363,26 +1392,17 @@ int ptss_accumulate_paths_stats(ptss_context* c, const ptss_path_result* dev_res
                                 ptss_film_entry* dev_film, unsigned long long* dev_moments, size_t filmPixels, ptss_uchar4* dev_pixels,
                                 ptss_history_entry* dev_history, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
-    if (n == 0) return PTSS_OK;
-    if (!dev_results || !dev_film || !dev_moments) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if ((((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) || (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u) ||
-        ((uintptr_t)dev_moments & 7u))
-        return fail(PTSS_EINVAL, "results, film and history must be 16-byte aligned, dev_moments 8-byte, dev_index and dev_pixels 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
-    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
-    const SceneImage& im = c->images[0];
-    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
-    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
-    HIP_TRY(ptss::launchStatsAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film, dev_moments,
-                                        (uint32_t)filmPixels, dev_pixels, dev_history, quantTable, c->dTotal + kFilmRejectedWord,
-                                        &c->adaptiveLaunches[0]));
-    if (dev_index) {
-        c->filmStream = st;
-        c->filmIndexed = true;
-    }
+    const char* bad = !dev_results || !dev_film || !dev_moments ? kNullBuffer
+                      : (((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_history) & 15u) ||
+                              (((uintptr_t)dev_index | (uintptr_t)dev_pixels) & 3u) || ((uintptr_t)dev_moments & 7u)
+                          ? "results, film and history must be 16-byte aligned, dev_moments 8-byte, dev_index and dev_pixels 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchStatsAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, dev_moments, f.filmPixels, dev_pixels, dev_history,
+                                        f.quantTable, c->dTotal + kFilmRejectedWord, &c->adaptiveLaunches[0]));
+    noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
 
@@ -1397,7 +1417,7 @@ int ptss_default_plan_params(ptss_plan_params* p) {
 
 int ptss_plan_cdf_entries(size_t filmPixels, size_t* entries) {
     if (!entries) return fail(PTSS_EINVAL, "entries is null");
-    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
     *entries = (size_t)ptad::cdfEntries(filmPixels);
     return PTSS_OK;
 }
@@ -1407,14 +1427,14 @@ int ptss_plan_samples(ptss_context* c, const ptss_film_entry* dev_film, const un
                       void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (const char* what = ptad::paramsError(params)) return fail(PTSS_EINVAL, what);
-    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
     if (n == 0) return PTSS_OK;
     if (!dev_film || !dev_moments || !dev_cdf || !dev_index) return fail(PTSS_EINVAL, "null buffer with n > 0");
     if (((uintptr_t)dev_film & 15u) || (((uintptr_t)dev_moments | (uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u))
         return fail(PTSS_EINVAL, "film must be 16-byte aligned, dev_moments, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     HIP_TRY(ptss::launchPlanSamples(st, dev_film, dev_moments, (uint32_t)filmPixels, *params, (uint32_t)n, dev_cdf, dev_index, dev_info,
                                     &c->adaptiveLaunches[1]));
     return PTSS_OK;
@@ -1442,22 +1462,16 @@ int ptss_accumulate_paths_linear(ptss_context* c, const ptss_path_result* dev_re
                                  ptss_linear_entry* dev_film, size_t filmPixels, const ptss_linear_params* params, void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
-    if (filmPixels >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "filmPixels must be below 2^31");
-    if (n == 0) return PTSS_OK;
-    if (!dev_results || !dev_film) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if ((((uintptr_t)dev_results | (uintptr_t)dev_film) & 15u) || ((uintptr_t)dev_index & 3u))
-        return fail(PTSS_EINVAL, "results and film must be 16-byte aligned, dev_index 4-byte aligned");
-    if (n >= (size_t(1) << 31)) return fail(PTSS_ERANGE, "n must be below 2^31");
-    if (!dev_index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + n leaves the film");
-    if (!c->images[0].dBlob) return fail(PTSS_EINVAL, "context has no scene image");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
-    HIP_TRY(ptss::launchLinearAccumulate(st, dev_results, dev_index, dev_index ? 0u : (uint32_t)firstPixel, (uint32_t)n, dev_film,
-                                         (uint32_t)filmPixels, *params, c->dTotal + kFilmRejectedWord, &c->linearLaunches[0]));
-    if (dev_index) {
-        c->filmStream = st;
-        c->filmIndexed = true;
-    }
+    const char* bad = !dev_results || !dev_film ? kNullBuffer
+                      : (((uintptr_t)dev_results | (uintptr_t)dev_film) & 15u) || ((uintptr_t)dev_index & 3u)
+                          ? "results and film must be 16-byte aligned, dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchLinearAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, f.filmPixels, *params,
+                                         c->dTotal + kFilmRejectedWord, &c->linearLaunches[0]));
+    noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
 
@@ -1469,16 +1483,14 @@ int ptss_resolve_linear(ptss_context* c, const ptss_linear_entry* dev_film, size
     if (!dev_film) return fail(PTSS_EINVAL, "null film with count > 0");
     if ((((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_pixels & 3u))
         return fail(PTSS_EINVAL, "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned");
-    if (firstPixel >= (size_t(1) << 31) || count >= (size_t(1) << 31) || firstPixel + count >= (size_t(1) << 31))
+    if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count))
         return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
-    const float* quantTable = reinterpret_cast<const float*>(im.dBlob + im.layout.offQuant);   // the frame's own thresholds (frameBuffers)
-    HIP_TRY(ptss::launchLinearResolve(st, dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTable, dev_linear, dev_pixels, dev_history,
-                                      &c->linearLaunches[1]));
+    HIP_TRY(ptss::launchLinearResolve(streamOf(c, hipStream), dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTableOf(im), dev_linear,
+                                      dev_pixels, dev_history, &c->linearLaunches[1]));
     return PTSS_OK;
 }
 
@@ -1497,12 +1509,12 @@ int ptss_render_features_scaled(ptss_context* c, int factor, ptss_pixel_feature*
     if (factor < 1 || factor > ptup::kMaxFactor) return fail(PTSS_EINVAL, "factor must be in [1, 4]");
     if ((uintptr_t)dev_features_hi & 15u) return fail(PTSS_EINVAL, "dev_features_hi must be 16-byte aligned");
     const unsigned long long n = (unsigned long long)(factor * factor) * c->numPixels;
-    if (n >= (1ull << 31)) return fail(PTSS_ERANGE, "factor^2 * local pixels must stay below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "factor^2 * local pixels must stay below 2^31");
     if (n == 0) return PTSS_OK;   // a rank whose tile is empty
     const SceneImage& im = c->images[0];
     if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const ptss_vec3 defaultColor{c->defaultColor[0], c->defaultColor[1], c->defaultColor[2]};
     const int fW = factor * c->tile.width, fH = factor * c->tile.height;
     const ptss::TileMap tile{fW, fH, factor * c->tile.localRows, c->tile.rank, c->tile.world, factor * c->tile.bandRows};
@@ -1536,12 +1548,12 @@ int ptss_upsample(ptss_context* c, const ptss_uchar4* dev_lo, const ptss_pixel_f
         return fail(PTSS_EINVAL, "ptss_upsample needs the whole frame: this context is a pixel-band shard (tileWorld > 1), whose bands of rows "
                                  "have no neighbours to interpolate with");
     const int factor = params->factor;
-    if ((unsigned long long)(factor * factor) * c->numPixels >= (1ull << 31))
+    if (!fits31((unsigned long long)(factor * factor) * c->numPixels))
         return fail(PTSS_ERANGE, "factor^2 * pixels must stay below 2^31");
     if ((long long)factor * c->tile.height > ptup::kMaxHiRows) return fail(PTSS_ERANGE, "factor * height must not exceed 524,280 rows");
     if (c->numPixels == 0) return PTSS_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     HIP_TRY(ptss::launchUpsample(st, dev_lo, dev_features_lo, dev_features_hi, dev_out_hi, dev_out_hi_float, c->tile.width, c->tile.height, factor,
                                  ptup::levelOf(*params), &c->upsampleLaunches));
     return PTSS_OK;
@@ -1581,7 +1593,7 @@ static int denoisePasses(ptss_context* c, const char* what, const void* input, b
                                                        "rows have no neighbours to filter with").c_str());
     if (fromAccumulator) input = c->dAccum;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     const int levels = params->levels;
     if (levels >= 2)
         for (float4*& plane : c->dDenoise)
@@ -1644,7 +1656,7 @@ static int reprojectCall(ptss_context* c, const char* what, bool motion, const p
         return fail(PTSS_EINVAL, (std::string(what) + " needs the whole frame: this context is a pixel-band shard (tileWorld > 1)").c_str());
     if (c->numPixels == 0) return PTSS_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     // c and n of the accumulator as it stands: the last frame's display scale (ptss_denoise's input), nothing before the first frame
     const int perPixel = (int)c->samples * (c->lastTicks - c->lastResetTick + 1);
     const float inverseTicks = 1.f / (float)perPixel;
@@ -1726,7 +1738,7 @@ int ptss_update_triangles(ptss_context* c, const ptss_triangle* dev_triangles, s
             return fail(PTSS_EINVAL, "the scene image stores its triangles grouped by edge class (T <= 255), an order that depends on the "
                                      "vertices: replace the scene with ptss_set_scene (repacking so small a scene costs microseconds)");
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     unsigned long long* rejected = c->dTotal + kRejectedWord;
     for (SceneImage& im : c->images) {
         if (!im.dBlob) continue;
@@ -1750,7 +1762,7 @@ int ptss_resort_triangles(ptss_context* c, void* hipStream) {
         if (im.dBlob && ptss::meshImage(im.layout)) mesh = &im;
     if (!mesh) return PTSS_OK;   // no kd order to rebuild: nothing launched, nothing counted
     HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = hipStream ? static_cast<hipStream_t>(hipStream) : c->stream;
+    hipStream_t st = streamOf(c, hipStream);
     // the scratch exists before anything is launched: on failure the image is untouched
     if (int rc = createCheck(ptss::reserveResortScratch(c->resortScratch, mesh->layout.numTriangles), "ptss_resort_triangles: scratch")) return rc;
     HIP_TRY(ptss::launchResort(st, mesh->dBlob, mesh->layout, c->resortScratch));

@@ -8,21 +8,13 @@
 // 4-byte words at a 4-byte aligned address (ptss_path_rng), read and written as pathQueryKernel reads and writes them.
 #include "ptss_device.h"
 #include "ptcamera.h"
-#include "ptdenoise.h"
+#include "ptfilm.h"
 #include "ptquant.h"
 #include "pthit.h"
 
 namespace ptss {
 
 constexpr int kFilmBlock = 256;
-
-// dropped entries of one wave, counted with one atomic: `dropped` is the lane's own verdict
-__device__ __forceinline__ void countDropped(bool dropped, unsigned long long* rejected) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(dropped);
-    if (m == 0ull) return;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));   // dropped lanes below this one
-    if (dropped && before == 0u) atomicAdd(rejected, (unsigned long long)__popcll(m));
-}
 
 // ptss_generate_rays: ray i = the eye ray of film pixel p = index ? index[i] : firstPixel + i, from stream rng[i], which is stored
 // back advanced by the model's draws. p >= filmPixels: nothing is written (ray and stream stay as they are), the entry is counted.
@@ -56,20 +48,6 @@ __global__ __launch_bounds__(kFilmBlock) void filmRayKernel(ptcam::Film F, uint3
     const ptss_ray_query q = ptcam::filmRay(F, (int)(p % (uint32_t)F.width), (int)(p / (uint32_t)F.width), jx, jy, u1, u2);
     rays[2 * (size_t)i] = float4{q.origin.x, q.origin.y, q.origin.z, q.tmax};
     rays[2 * (size_t)i + 1] = float4{q.direction.x, q.direction.y, q.direction.z, q.pad};
-}
-
-// finishPath's display pixel and ptdn::displayValue of one film entry
-__device__ __forceinline__ void resolveEntry(uint4 e, uint32_t p, ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    const float inv = ptm::rcp((float)e.w);   // 1.f / (float)samples, correctly rounded
-    if (pixels) {
-        const uint32_t px = (uint32_t)(unsigned char)(e.x * inv + 0.5f) | ((uint32_t)(unsigned char)(e.y * inv + 0.5f) << 8) |
-                            ((uint32_t)(unsigned char)(e.z * inv + 0.5f) << 16) | (255u << 24);
-        reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    }
-    if (history) {
-        const vec3 c = ptdn::displayValue(e.x, e.y, e.z, inv);
-        history[p] = float4{c.x, c.y, c.z, (float)e.w};
-    }
 }
 
 // ptss_accumulate_paths without an index: ray i belongs to pixel firstPixel + i alone — finishPath's read-modify-write (S = 1)
@@ -151,8 +129,6 @@ __global__ __launch_bounds__(kBlock) void rayFeatureKernel(const float4* __restr
         }
     }
 }
-
-static inline unsigned filmBlocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
 
 hipError_t launchFilmRays(hipStream_t st, const ptcam::Film& film, uint32_t firstPixel, const uint32_t* index, uint32_t n, void* rng, void* rays,
                           unsigned long long* rejected, unsigned long long* launches) {

@@ -3,8 +3,9 @@
 // display pixels and history entries (csrc/ptlinear.h has the arithmetic; its host build is the specification).
 //
 // With an index, the lanes of a wave that hold one pixel side by side are summed on chip first and the run's head lane alone issues the
-// atomics: ptss_adaptive.hip's segmented reduction, restated here so that file's code objects stay as they are.
+// atomics (csrc/ptfilm.h sumRunsToHead, the reduction ptss_adaptive.hip uses).
 #include "ptss_device.h"
+#include "ptfilm.h"
 #include "ptlinear.h"
 
 namespace ptss {
@@ -12,16 +13,6 @@ namespace ptss {
 using ptlin::u64;
 
 constexpr int kLinearBlock = 256;
-
-__device__ __forceinline__ uint32_t linearLaneId() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
-// dropped entries of one wave, counted with one atomic (ptss_film.hip's countDropped)
-__device__ __forceinline__ void countDroppedLinear(bool dropped, unsigned long long* rejected) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(dropped);
-    if (m == 0ull) return;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (dropped && before == 0u) atomicAdd(rejected, (unsigned long long)__popcll(m));
-}
 
 // a film entry as the two 16-byte rows it is read and written in: {r, g}, {b, samples | clamped << 32}
 struct LinearRows {
@@ -57,7 +48,7 @@ __global__ __launch_bounds__(kLinearBlock) void linearScatterKernel(const float4
     const bool inBatch = i < n;
     const uint32_t p = inBatch ? index[i] : 0u;
     const bool ok = inBatch && p < filmPixels;
-    countDroppedLinear(inBatch && !ok, rejected);
+    countDropped(inBatch && !ok, rejected);
     const uint32_t key = ok ? p : 0xffffffffu;   // (a film has fewer than 2^31 pixels) lanes without a pixel carry zeros and never lead a store
     u64 q[3] = {0ull, 0ull, 0ull};
     uint32_t counts = 0u;
@@ -65,25 +56,17 @@ __global__ __launch_bounds__(kLinearBlock) void linearScatterKernel(const float4
         const float4 r = results[i];
         counts = 1u | (ptlin::sampleToFixed(r.x, r.y, r.z, sc, q) << 16);
     }
-    const uint32_t lane = linearLaneId();
-    const uint32_t before = (uint32_t)__shfl_up((int)key, 1, 64);
-    const bool head = lane == 0u || key != before;
-    const unsigned long long heads = __builtin_amdgcn_ballot_w64(head);
-    // heads strictly above this lane, bit k - 1 = lane + k: lane + d joins while none of lanes lane + 1 .. lane + d starts a run
-    const unsigned long long above = lane < 63u ? heads >> (lane + 1u) : ~0ull;
-#pragma unroll
-    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+    const bool head = sumRunsToHead(key, [&](uint32_t d, bool joins) {
         const u64 r2 = (u64)__shfl_down((long long)q[0], d, 64), g2 = (u64)__shfl_down((long long)q[1], d, 64),
                   b2 = (u64)__shfl_down((long long)q[2], d, 64);
         const uint32_t c2 = (uint32_t)__shfl_down((int)counts, d, 64);
-        const bool joins = lane + d < 64u && (above & ((1ull << d) - 1ull)) == 0ull;
         if (joins) {
             q[0] += r2;
             q[1] += g2;
             q[2] += b2;
             counts += c2;
         }
-    }
+    });
     if (!(head && ok)) return;
     u64* e = film + 4 * (size_t)p;
     atomicAdd(e + 0, q[0]);
@@ -108,12 +91,10 @@ __global__ __launch_bounds__(kLinearBlock) void linearResolveKernel(const ulongl
     if (history) history[p] = float4{hist[0], hist[1], hist[2], hist[3]};
 }
 
-static inline unsigned linearBlocksFor(uint32_t n) { return (n + kLinearBlock - 1) / kLinearBlock; }
-
 hipError_t launchLinearAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
                                   uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
                                   unsigned long long* launches) {
-    const dim3 grid(linearBlocksFor(n)), block(kLinearBlock);
+    const dim3 grid(filmBlocksFor(n, kLinearBlock)), block(kLinearBlock);
     const ptlin::Scale sc = ptlin::scaleOf(params);
     if (!index)
         hipLaunchKernelGGL(linearAccumulateKernel, grid, block, 0, st, static_cast<const float4*>(results), firstPixel, n,
@@ -128,7 +109,7 @@ hipError_t launchLinearAccumulate(hipStream_t st, const void* results, const uin
 
 hipError_t launchLinearResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
                                const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches) {
-    hipLaunchKernelGGL(linearResolveKernel, dim3(linearBlocksFor(count)), dim3(kLinearBlock), 0, st, static_cast<const ulonglong2*>(film),
+    hipLaunchKernelGGL(linearResolveKernel, dim3(filmBlocksFor(count, kLinearBlock)), dim3(kLinearBlock), 0, st, static_cast<const ulonglong2*>(film),
                        firstPixel, count, ptlin::scaleOf(params), quantTable, static_cast<float4*>(linear), pixels, static_cast<float4*>(history));
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) ++*launches;

@@ -203,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void pathRefillKernel(const float4* __restr
     const bool mesh = meshImage(L);
     const float4* td = mesh ? sceneBlob : sc;
     const int numLights = L.numPointLights + L.numAreaLights;
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint32_t lane = laneId();
 
     uint32_t i = blockIdx.x * kBlock + threadIdx.x;   // the ray this lane runs
     RayRegs ray;
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(kBlock) void pathRefillKernel(const float4* __restr
                 next = h;
                 end = drained ? n : h + kRefillChunk;
             }
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(dead >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dead, 0u));
+            const uint32_t rank = rankBelow(dead);
             const uint32_t mine = next + rank;
             if (!ray.active && mine < end) {
                 i = mine;

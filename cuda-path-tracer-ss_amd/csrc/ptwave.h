@@ -19,6 +19,11 @@ __device__ __forceinline__ vec3 xyz(float4 v) { return vec3{v.x, v.y, v.z}; }
 __device__ __forceinline__ bool waveAny(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 // "every active lane says yes" (p must be one direct compare, see maskOf)
 __device__ __forceinline__ bool waveAll(bool p) { return __builtin_amdgcn_ballot_w64(p) == __builtin_amdgcn_ballot_w64(true); }
+// the set bits of a 64-bit wave mask below this lane (v_mbcnt_lo / v_mbcnt_hi), and the lane's own number in its wave
+__device__ __forceinline__ uint32_t rankBelow(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+__device__ __forceinline__ uint32_t laneId() { return rankBelow(~0ull); }
 // orders this wave's LDS traffic for the compiler; within one wave the LDS executes in order
 __device__ __forceinline__ void waveLdsFence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 

@@ -559,6 +559,25 @@ def _rows(value, dtype, words, word_dtype, what, copy=False):
     return a
 
 
+def _output_rows(P, value, what):
+    """An optional output of a film call as (P, 4) rows: None (NULL), True (zeros beforehand) or the buffer's content beforehand (a copy).
+    "pixels" are bytes, every other output HISTORY_DTYPE."""
+    if value is None:
+        return None
+    if what == "pixels":
+        return np.zeros((P, 4), dtype=np.uint8) if value is True else np.array(value, dtype=np.uint8, order="C").reshape(-1, 4)
+    return np.zeros((P, 4), dtype=np.float32) if value is True else _rows(value, HISTORY_DTYPE, 4, np.float32, what, copy=True)
+
+
+def _film_outputs(P, **outputs):
+    """_output_rows of each named output, in order, each of them one entry per film pixel."""
+    rows = [_output_rows(P, value, what) for what, value in outputs.items()]
+    if any(a is not None and len(a) != P for a in rows):
+        names = list(outputs)
+        raise ValueError(f"{', '.join(names[:-1])} and {names[-1]}: one entry per film pixel")
+    return rows
+
+
 def probe_film_rays(film, rng, first_pixel=0, index=None, rays=None):
     """ptss_generate_rays on the host (csrc/ptcamera.h; the specification of the device's rays) -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE:
     the streams afterwards, number of index entries dropped). rays: the buffer's content beforehand (zeros otherwise): an entry whose
@@ -585,8 +604,7 @@ def probe_accumulate(results, film, first_pixel=0, index=None, pixels=None, hist
     n = len(r)
     idx = _film_index(index, n)
     f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
-    px = None if pixels is None else (np.zeros((len(f), 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
-    hs = None if history is None else (np.zeros((len(f), 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+    px, hs = _output_rows(len(f), pixels, "pixels"), _output_rows(len(f), history, "history")
     rejected = C.c_ulonglong(0)
     rc = host_lib().ptss_probe_accumulate(r.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if idx is not None else None, int(first_pixel),
                                           n, f.ctypes.data_as(C.c_void_p), len(f), px.ctypes.data_as(C.c_void_p) if px is not None else None,
@@ -628,8 +646,7 @@ def probe_accumulate_stats(results, film, moments, first_pixel=0, index=None, pi
     idx = _film_index(index, n)
     f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
     m = _moments(moments, len(f))
-    px = None if pixels is None else (np.zeros((len(f), 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
-    hs = None if history is None else (np.zeros((len(f), 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
+    px, hs = _output_rows(len(f), pixels, "pixels"), _output_rows(len(f), history, "history")
     rejected = C.c_ulonglong(0)
     rc = host_lib().ptss_probe_accumulate_stats(r.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p) if idx is not None else None,
                                                 int(first_pixel), n, f.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), len(f),
@@ -670,16 +687,6 @@ def linear_params(scale_log2=20, clamp_max=65536.0, exposure=1.0):
     return p
 
 
-def _linear_outputs(P, linear, pixels, history):
-    """The three outputs of a resolve: None (NULL), True (zeros beforehand) or the buffer's content beforehand, as (P, 4) rows."""
-    ln = None if linear is None else (np.zeros((P, 4), dtype=np.float32) if linear is True else _rows(linear, HISTORY_DTYPE, 4, np.float32, "linear", copy=True))
-    px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
-    hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
-    if any(a is not None and len(a) != P for a in (ln, px, hs)):
-        raise ValueError("linear, pixels and history: one entry per film pixel")
-    return ln, px, hs
-
-
 def _linear_range(P, first_pixel, count):
     first_pixel = int(first_pixel)
     count = P - first_pixel if count is None else int(count)
@@ -711,7 +718,7 @@ def probe_resolve_linear(film, first_pixel=0, count=None, params=None, linear=Tr
     f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
     P = len(f)
     first_pixel, count = _linear_range(P, first_pixel, count)
-    ln, px, hs = _linear_outputs(P, linear, pixels, history)
+    ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
     params = params if params is not None else linear_params()
     ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
     rc = host_lib().ptss_probe_resolve_linear(ptr(f), first_pixel, count, C.byref(params), ptr(ln), ptr(px), ptr(hs))
@@ -1481,6 +1488,39 @@ class Renderer:
                              read=(1, 2))
         return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1)
 
+    _NO_MOMENTS = object()   # _accumulate's `moments` for a film that keeps none
+
+    def _accumulate(self, call, film_dtype, word, results, film, first_pixel, index, moments=_NO_MOMENTS, pixels=None, history=None):
+        """The body of accumulate_paths, accumulate_paths_stats and accumulate_paths_linear. film_dtype, word: the film's record and the
+        type of its four words (a torch film holds them signed); call(results, index, first_pixel, n, film, P, moments, pixels, history,
+        stream): the C call, over device pointers or None. torch -> None; numpy -> (film, moments or None, pixels, history) afterwards."""
+        keeps_moments = moments is not self._NO_MOMENTS
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_film = self._torch_ptr(film, "film", "int%d" % (8 * np.dtype(word).itemsize), 4, dev)
+            P = film.shape[0]
+            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P) if keeps_moments else None
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
+            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
+            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
+            call(d_res, d_idx, int(first_pixel), n, d_film, P, d_mom, d_px, d_hs, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        idx = _film_index(index, n)
+        f = _rows(film, film_dtype, 4, word, "film", copy=True)
+        P = len(f)
+        m = _moments(moments, P) if keeps_moments else None
+        px, hs = _film_outputs(P, pixels=pixels, history=history)
+        if n == 0:
+            call(None, None, int(first_pixel), 0, None, P, None, None, None, None)
+        else:
+            self._round_trip([r, idx, f, m, px, hs], lambda d: call(d[0], d[1], int(first_pixel), n, d[2], P, d[3], d[4], d[5], None), read=(2, 3, 4, 5))
+        return f.view(film_dtype).reshape(-1), m, px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
     def accumulate_paths(self, results, film, first_pixel=0, index=None, pixels=None, history=None):
         """ptss_accumulate_paths: the samples of `results` added to the film, the touched pixels resolved.
         numpy: results (N,) PATH_RESULT_DTYPE or (N, 4) float32; film (P,) FILM_DTYPE or (P, 4) uint32 (not modified); pixels / history:
@@ -1488,36 +1528,9 @@ class Renderer:
         or None, history (P,) HISTORY_DTYPE or None). torch: results (N, 4) float32, film (P, 4) int32 UPDATED IN PLACE, index (N,) int32
         or None, pixels (P, 4) uint8 or None, history (P, 4) float32 or None, all on one device -> None, on the current stream."""
         L = device_lib()
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_film = self._torch_ptr(film, "film", "int32", 4, dev)
-            P = film.shape[0]
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
-            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
-            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_accumulate_paths(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, P, d_px, d_hs, C.c_void_p(stream)))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        idx = _film_index(index, n)
-        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
-        P = len(f)
-        px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
-        hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True
-                                           else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
-        if (px is not None and len(px) != P) or (hs is not None and len(hs) != P):
-            raise ValueError("pixels and history: one entry per film pixel")
-        if n == 0:
-            _check(L.ptss_accumulate_paths(self._ctx, None, None, int(first_pixel), 0, None, P, None, None, None))
-        else:
-            self._round_trip([r, idx, f, px, hs],
-                             lambda d: _check(L.ptss_accumulate_paths(self._ctx, d[0], d[1], int(first_pixel), n, d[2], P, d[3], d[4], None)),
-                             read=(2, 3, 4))
-        return f.view(FILM_DTYPE).reshape(-1), px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+        out = self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths(self._ctx, res, idx, first, n, f, P, px, hs, st)),
+                               FILM_DTYPE, np.uint32, results, film, first_pixel, index, pixels=pixels, history=history)
+        return None if out is None else (out[0], out[2], out[3])
 
     def ray_features(self, rays):
         """ptss_ray_features: the first-hit feature row of every ray. rays: (N, 8) float32 or (N,) RAY_DTYPE -> (N,) FEATURE_DTYPE; or
@@ -1547,38 +1560,8 @@ class Renderer:
         numpy: accumulate_paths' arguments and moments (P,) uint64 (not modified) -> (film, moments afterwards, pixels, history).
         torch: moments a contiguous (P,) int64 device tensor UPDATED IN PLACE like the film -> None, on the current stream."""
         L = device_lib()
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_film = self._torch_ptr(film, "film", "int32", 4, dev)
-            P = film.shape[0]
-            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P)
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
-            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
-            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_accumulate_paths_stats(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, d_mom, P, d_px, d_hs, C.c_void_p(stream)))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        idx = _film_index(index, n)
-        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film", copy=True)
-        P = len(f)
-        m = _moments(moments, P)
-        px = None if pixels is None else (np.zeros((P, 4), dtype=np.uint8) if pixels is True else np.array(pixels, dtype=np.uint8, order="C").reshape(-1, 4))
-        hs = None if history is None else (np.zeros((P, 4), dtype=np.float32) if history is True
-                                           else _rows(history, HISTORY_DTYPE, 4, np.float32, "history", copy=True))
-        if (px is not None and len(px) != P) or (hs is not None and len(hs) != P):
-            raise ValueError("pixels and history: one entry per film pixel")
-        if n == 0:
-            _check(L.ptss_accumulate_paths_stats(self._ctx, None, None, int(first_pixel), 0, None, None, P, None, None, None))
-        else:
-            self._round_trip([r, idx, f, m, px, hs],
-                             lambda d: _check(L.ptss_accumulate_paths_stats(self._ctx, d[0], d[1], int(first_pixel), n, d[2], d[3], P, d[4], d[5], None)),
-                             read=(2, 3, 4, 5))
-        return f.view(FILM_DTYPE).reshape(-1), m, px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+        return self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths_stats(self._ctx, res, idx, first, n, f, m, P, px, hs, st)),
+                                FILM_DTYPE, np.uint32, results, film, first_pixel, index, moments, pixels, history)
 
     def plan_samples(self, film, moments, n, params=None, cdf=None, index=None, info=None):
         """ptss_plan_samples: the next round's index from film and moments.
@@ -1627,28 +1610,9 @@ class Renderer:
         on one device -> None, on the current stream."""
         L = device_lib()
         params = params if params is not None else linear_params()
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_film = self._torch_ptr(film, "film", "int64", 4, dev)
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_accumulate_paths_linear(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, film.shape[0], C.byref(params), C.c_void_p(stream)))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        idx = _film_index(index, n)
-        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True)
-        P = len(f)
-        if n == 0:
-            _check(L.ptss_accumulate_paths_linear(self._ctx, None, None, int(first_pixel), 0, None, P, C.byref(params), None))
-        else:
-            self._round_trip([r, idx, f],
-                             lambda d: _check(L.ptss_accumulate_paths_linear(self._ctx, d[0], d[1], int(first_pixel), n, d[2], P, C.byref(params), None)),
-                             read=(2,))
-        return f.view(LINEAR_DTYPE).reshape(-1)
+        out = self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths_linear(self._ctx, res, idx, first, n, f, P, C.byref(params), st)),
+                               LINEAR_DTYPE, np.uint64, results, film, first_pixel, index)
+        return None if out is None else out[0]
 
     def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
@@ -1673,7 +1637,7 @@ class Renderer:
         f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
         P = len(f)
         first_pixel, count = _linear_range(P, first_pixel, count)
-        ln, px, hs = _linear_outputs(P, linear, pixels, history)
+        ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
         if count == 0:
             _check(L.ptss_resolve_linear(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
         else:

@@ -19,14 +19,23 @@ LAYER_HEADERS = ("ptwave.h", "ptraypool.h", "ptprim.h", "ptaccel.h", "pthit.h", 
 FREE_BITS = (36, 37, 38, 39, 61, 62, 63)
 
 
-@pytest.mark.parametrize("header", LAYER_HEADERS)
-def test_layer_header_compiles_alone(header, tmp_path):
+def _compiles_alone(header, tmp_path):
     src = tmp_path / "one.hip"
     src.write_text('#include "%s"\n' % header)
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     r = subprocess.run([hipcc, "-std=c++17", "-fsyntax-only", "--cuda-device-only", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function",
                         "-I", os.path.join(ROOT, "include"), "-I", CSRC, str(src)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+@pytest.mark.parametrize("header", LAYER_HEADERS)
+def test_layer_header_compiles_alone(header, tmp_path):
+    _compiles_alone(header, tmp_path)
+
+
+def test_film_header_compiles_alone(tmp_path):
+    """ptfilm.h, what the three film kernel files share, is no layer (it sits on ptwave.h and ptdenoise.h) but private in the same way."""
+    _compiles_alone("ptfilm.h", tmp_path)
 
 
 def test_layer_headers_include_only_earlier_layers():
