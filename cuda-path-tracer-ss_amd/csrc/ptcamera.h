@@ -71,11 +71,17 @@ inline Film filmOf(const ptss_film_camera& f) {
 
 PTM_HD int draws(int kind, int jitter) { return jitter ? (kind == PTSS_FILM_THIN_LENS ? 4 : 2) : 0; }
 
+// where on the film the sample of pixel (x, y) lies, in pixels: the X, Y every model starts from (ptss_generate_rays_positions hands them out)
+PTM_HD void samplePosition(int x, int y, float jx, float jy, float& X, float& Y) {
+    X = x + jx;
+    Y = y + jy;
+}
+
 // the eye ray of pixel (x, y); jx, jy, u1, u2: the stream's draws in that order (0.5, 0.5 and anything with jitter = 0: u1, u2 are
 // then not read)
 PTM_HD ptss_ray_query filmRay(const Film& F, int x, int y, float jx, float jy, float u1, float u2) {
-    const float jitteredX = x + jx;
-    const float jitteredY = y + jy;
+    float jitteredX, jitteredY;
+    samplePosition(x, y, jx, jy, jitteredX, jitteredY);
     vec3 o = F.camera.position;
     vec3 v;
     if (F.kind == PTSS_FILM_EQUIRECT) {

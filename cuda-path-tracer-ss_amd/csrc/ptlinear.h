@@ -61,6 +61,15 @@ PTM_HD float meanOf(u64 sum, u64 N, float down) {
     return (float)m * down;
 }
 
+// channel c of an entry shown from its mean: linear[c] = the mean itself, byte c of *word = the tone map of the exposed mean, hist[c] = its
+// display value 0..255 (ptsplat.h resolves with the same expressions)
+PTM_HD void showMean(float mean, int c, const Scale& sc, const float* T, float* linear, uint32_t* word, float* hist) {
+    const float e = mean * sc.exposure;
+    linear[c] = mean;
+    *word |= ptq::quantize_fast(e, T) << (8 * c);
+    hist[c] = 255.f * ptm::pow(ptm::clamp(e, 0.f, 1.f), ptm::kGamma);
+}
+
 // one film entry resolved. linear: the unexposed means and (float)N; px: the display pixel, the tone map of the exposed mean (uchar4 as
 // one word, w = 255); hist: the display value 0..255 of the exposed mean and (float)N
 PTM_HD void resolve(u64 r, u64 g, u64 b, uint32_t samples, const Scale& sc, const float* T, float* linear, uint32_t* px, float* hist) {
@@ -73,13 +82,7 @@ PTM_HD void resolve(u64 r, u64 g, u64 b, uint32_t samples, const Scale& sc, cons
     const u64 N = (u64)samples;
     const u64 sum[3] = {r, g, b};
     uint32_t word = 255u << 24;
-    for (int c = 0; c < 3; ++c) {
-        const float mean = meanOf(sum[c], N, sc.down);
-        const float e = mean * sc.exposure;
-        linear[c] = mean;
-        word |= ptq::quantize_fast(e, T) << (8 * c);
-        hist[c] = 255.f * ptm::pow(ptm::clamp(e, 0.f, 1.f), ptm::kGamma);
-    }
+    for (int c = 0; c < 3; ++c) showMean(meanOf(sum[c], N, sc.down), c, sc, T, linear, &word, hist);
     linear[3] = hist[3] = (float)samples;
     *px = word;
 }

@@ -25,6 +25,7 @@
 #include "ptcamera.h"
 #include "ptadaptive.h"
 #include "ptlinear.h"
+#include "ptsplat.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -107,7 +108,8 @@ struct ptss_context {
     uint32_t* dRngHome = nullptr;
     unsigned long long* dTotal = nullptr;   // [0 .. kMaxLanes) ray-bounce totals per lane, [kMaxLanes]: records ptss_update_triangles
                                             // rejected (kRejectedWord), [kMaxLanes + 1]: index entries the film calls dropped (kFilmRejectedWord),
-                                            // [kMaxLanes + 2 .. +8) unused, then one word: guard timeouts (must stay 0)
+                                            // [kMaxLanes + 2], [+ 3]: samples the splat calls dropped and clamped (kSplatCountersWord),
+                                            // [kMaxLanes + 4 .. +8) unused, then one word: guard timeouts (must stay 0)
     uint32_t* dAccumOwned = nullptr;
     uint32_t* dAccum = nullptr;  // owned or bound
     float* dFsum = nullptr;
@@ -155,6 +157,9 @@ struct ptss_context {
     bool filmIndexed = false;
     unsigned long long adaptiveLaunches[2] = {0, 0};          // ptss_accumulate_paths_stats, ptss_plan_samples calls that launched
     unsigned long long linearLaunches[2] = {0, 0};            // ptss_accumulate_paths_linear, ptss_resolve_linear calls that launched
+    unsigned long long splatLaunches[3] = {0, 0, 0};          // ptss_splat_paths, ptss_splat_paths_homed, ptss_resolve_splat calls that launched
+    hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
+    bool splatCounted = false;
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
     int denoiseLastPlane = -1;                  // the plane the last non-final pass of the latest ptss_denoise wrote (-1: none), and its
     int denoiseLastLevel = -1;                  // level; on denoiseStream (ptss_read_denoise_plane)
@@ -168,6 +173,7 @@ struct ptss_context {
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 constexpr int kRejectedWord = ptss::kMaxLanes;
 constexpr int kFilmRejectedWord = ptss::kMaxLanes + 1;
+constexpr int kSplatCountersWord = ptss::kMaxLanes + 2;   // two words: samples the splat calls dropped, samples they clamped
 
 namespace {
 
@@ -1334,8 +1340,8 @@ int ptss_generate_rays(ptss_context* c, const ptss_film_camera* film, size_t fir
     RC_TRY(filmCall(c, &f, (unsigned long long)film->width * (unsigned long long)film->height, "width * height must be below 2^31", n, bad, dev_index,
                     firstPixel, false, hipStream));
     if (!f.go) return PTSS_OK;
-    HIP_TRY(ptss::launchFilmRays(f.st, ptcam::filmOf(*film), f.firstPixel, dev_index, f.n, dev_rng, dev_rays, c->dTotal + kFilmRejectedWord,
-                                 &c->filmLaunches[0]));
+    HIP_TRY(ptss::launchFilmRays(f.st, ptcam::filmOf(*film), f.firstPixel, dev_index, f.n, dev_rng, dev_rays, nullptr,
+                                 c->dTotal + kFilmRejectedWord, &c->filmLaunches[0]));
     noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
@@ -1498,6 +1504,117 @@ int ptss_linear_launches(const ptss_context* c, unsigned long long* out2) {
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->linearLaunches[0];
     out2[1] = c->linearLaunches[1];
+    return PTSS_OK;
+}
+
+// ---- the filtered linear film (ptss_splat.hip; csrc/ptsplat.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_splat_filter(ptss_splat_filter* f) {
+    if (!f) return fail(PTSS_EINVAL, "filter is null");
+    f->structSize = (unsigned int)sizeof(ptss_splat_filter);
+    f->kind = PTSS_SPLAT_TENT;
+    f->radius = 1.f;
+    f->alpha = 2.f;
+    f->reserved = 0u;
+    return PTSS_OK;
+}
+
+int ptss_generate_rays_positions(ptss_context* c, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index, size_t n,
+                                 ptss_path_rng* dev_rng, ptss_ray_query* dev_rays, ptss_film_position* dev_positions, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptcam::cameraError(film)) return fail(PTSS_EINVAL, what);
+    if (!dev_positions) return fail(PTSS_EINVAL, "dev_positions is null (ptss_generate_rays makes rays without positions)");
+    const char* bad = !dev_rng || !dev_rays ? kNullBuffer
+                      : ((uintptr_t)dev_rays & 15u) || ((uintptr_t)dev_positions & 7u) || (((uintptr_t)dev_rng | (uintptr_t)dev_index) & 3u)
+                          ? "rays must be 16-byte aligned, dev_positions 8-byte, dev_rng and dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, (unsigned long long)film->width * (unsigned long long)film->height, "width * height must be below 2^31", n, bad, dev_index,
+                    firstPixel, false, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchFilmRays(f.st, ptcam::filmOf(*film), f.firstPixel, dev_index, f.n, dev_rng, dev_rays, dev_positions,
+                                 c->dTotal + kFilmRejectedWord, &c->filmLaunches[0]));
+    noteFilmIndex(c, dev_index, f.st);
+    return PTSS_OK;
+}
+
+// what the two splat calls check in front of filmCall: ctx, filter, params, the film's sides
+static int splatArguments(const ptss_context* c, const ptss_splat_filter* filter, const ptss_linear_params* params, int width, int height) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptspl::filterError(filter)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (width < 1 || height < 1 || width > ptspl::kMaxFilmSide || height > ptspl::kMaxFilmSide)
+        return fail(PTSS_ERANGE, "width and height must be in [1, 2^22]");
+    return PTSS_OK;
+}
+
+static const char* splatBuffersError(const ptss_path_result* dev_results, const ptss_film_position* dev_positions, const ptss_splat_entry* dev_film) {
+    return !dev_results || !dev_positions || !dev_film ? kNullBuffer
+           : (((uintptr_t)dev_results | (uintptr_t)dev_film) & 15u) || ((uintptr_t)dev_positions & 7u)
+               ? "results and film must be 16-byte aligned, dev_positions 8-byte aligned"
+               : nullptr;
+}
+
+// the device counters of a splat: ptss_splat_stats synchronises on the stream of the latest one
+static void noteSplat(ptss_context* c, hipStream_t st) {
+    c->splatStream = st;
+    c->splatCounted = true;
+}
+
+int ptss_splat_paths(ptss_context* c, const ptss_path_result* dev_results, const ptss_film_position* dev_positions, size_t n,
+                     ptss_splat_entry* dev_film, int width, int height, const ptss_splat_filter* filter, const ptss_linear_params* params,
+                     void* hipStream) {
+    RC_TRY(splatArguments(c, filter, params, width, height));
+    FilmCall f;   // (positions take the place of an index: n is not bound by the film)
+    RC_TRY(filmCall(c, &f, (unsigned long long)width * (unsigned long long)height, "width * height must be below 2^31", n,
+                    splatBuffersError(dev_results, dev_positions, dev_film), reinterpret_cast<const uint32_t*>(dev_positions), 0, false, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchSplatScatter(f.st, dev_results, dev_positions, f.n, dev_film, width, height, *filter, *params, c->dTotal + kSplatCountersWord,
+                                     &c->splatLaunches[0]));
+    noteSplat(c, f.st);
+    return PTSS_OK;
+}
+
+int ptss_splat_paths_homed(ptss_context* c, const ptss_path_result* dev_results, const ptss_film_position* dev_positions, size_t firstPixel, size_t n,
+                           ptss_splat_entry* dev_film, int width, int height, const ptss_splat_filter* filter, const ptss_linear_params* params,
+                           void* hipStream) {
+    RC_TRY(splatArguments(c, filter, params, width, height));
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, (unsigned long long)width * (unsigned long long)height, "width * height must be below 2^31", n,
+                    splatBuffersError(dev_results, dev_positions, dev_film), nullptr, firstPixel, false, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchSplatHomed(f.st, dev_results, dev_positions, f.firstPixel, f.n, dev_film, width, height, *filter, *params,
+                                   c->dTotal + kSplatCountersWord, &c->splatLaunches[1]));
+    noteSplat(c, f.st);
+    return PTSS_OK;
+}
+
+int ptss_resolve_splat(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                       ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (count == 0) return PTSS_OK;
+    if (!dev_film) return fail(PTSS_EINVAL, "null film with count > 0");
+    if ((((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_pixels & 3u))
+        return fail(PTSS_EINVAL, "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned");
+    if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count))
+        return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchSplatResolve(streamOf(c, hipStream), dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTableOf(im), dev_linear,
+                                     dev_pixels, dev_history, &c->splatLaunches[2]));
+    return PTSS_OK;
+}
+
+int ptss_splat_stats(ptss_context* c, unsigned long long* out5) {
+    if (!c || !out5) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out5[k] = c->splatLaunches[k];
+    out5[3] = out5[4] = 0;
+    if (!c->splatCounted) return PTSS_OK;
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(hipStreamSynchronize(c->splatStream));
+    HIP_TRY(hipMemcpy(out5 + 3, c->dTotal + kSplatCountersWord, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PTSS_OK;
 }
 

@@ -203,8 +203,9 @@ hipError_t launchPathRefill(hipStream_t st, const float4* sceneBlob, SceneLayout
 // pixel firstPixel + i, and firstPixel + n <= the film's pixels), rng = n x 24 B, rays = n x 32 B, results = n x 16 B, film = filmPixels x 16 B
 // (ptss_film_entry), pixels / history = filmPixels entries or nullptr, features = n x 32 B. rejected: the device counter of dropped index
 // entries. No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+// positions: n x 8 B (ptss_film_position) written as well, or nullptr (ptss_generate_rays' own kernel, as it was)
 hipError_t launchFilmRays(hipStream_t st, const ptcam::Film& film, uint32_t firstPixel, const uint32_t* index, uint32_t n, void* rng, void* rays,
-                          unsigned long long* rejected, unsigned long long* launches);
+                          void* positions, unsigned long long* rejected, unsigned long long* launches);
 hipError_t launchFilmAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
                                 uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable, unsigned long long* rejected,
                                 unsigned long long* launches);
@@ -229,6 +230,18 @@ hipError_t launchLinearAccumulate(hipStream_t st, const void* results, const uin
                                   unsigned long long* launches);
 hipError_t launchLinearResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
                                const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
+// the filtered linear film (ptss_splat.hip; ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat). results = n x
+// 16 B, positions = n x 8 B, film = width x height x 32 B (ptss_splat_entry). launchSplatHomed: sample i is homed at pixel firstPixel + i,
+// n > 0 and firstPixel + n <= width * height. counters: two device words, samples dropped and samples clamped. filter and params: checked
+// by the caller (ptspl::filterError, ptlin::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+hipError_t launchSplatScatter(hipStream_t st, const void* results, const void* positions, uint32_t n, void* film, int width, int height,
+                              const ptss_splat_filter& filter, const ptss_linear_params& params, unsigned long long* counters,
+                              unsigned long long* launches);
+hipError_t launchSplatHomed(hipStream_t st, const void* results, const void* positions, uint32_t firstPixel, uint32_t n, void* film, int width,
+                            int height, const ptss_splat_filter& filter, const ptss_linear_params& params, unsigned long long* counters,
+                            unsigned long long* launches);
+hipError_t launchSplatResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

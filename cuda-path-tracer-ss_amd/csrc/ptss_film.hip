@@ -18,15 +18,21 @@ constexpr int kFilmBlock = 256;
 
 // ptss_generate_rays: ray i = the eye ray of film pixel p = index ? index[i] : firstPixel + i, from stream rng[i], which is stored
 // back advanced by the model's draws. p >= filmPixels: nothing is written (ray and stream stay as they are), the entry is counted.
-__global__ __launch_bounds__(kFilmBlock) void filmRayKernel(ptcam::Film F, uint32_t filmPixels, uint32_t firstPixel,
-                                                            const uint32_t* __restrict__ index, uint32_t n, uint32_t* __restrict__ rng,
-                                                            float4* __restrict__ rays, unsigned long long* __restrict__ rejected) {
+// kPositions (ptss_generate_rays_positions): positions[i] = the sample's place on the film (ptcam::samplePosition), {NaN, NaN} for a
+// dropped entry.
+template <bool kPositions>
+__device__ __forceinline__ void filmRayBody(const ptcam::Film& F, uint32_t filmPixels, uint32_t firstPixel, const uint32_t* __restrict__ index,
+                                            uint32_t n, uint32_t* __restrict__ rng, float4* __restrict__ rays, float2* __restrict__ positions,
+                                            unsigned long long* __restrict__ rejected) {
     const uint32_t i = blockIdx.x * kFilmBlock + threadIdx.x;
     const bool inBatch = i < n;
     uint32_t p = 0;
     if (inBatch) p = index ? index[i] : firstPixel + i;
     const bool ok = inBatch && p < filmPixels;
     if (index) countDropped(inBatch && !ok, rejected);   // (without an index the caller has checked the range)
+    if constexpr (kPositions) {
+        if (inBatch && !ok) positions[i] = float2{ptm::qnan(), ptm::qnan()};
+    }
     if (!ok) return;
     float jx = 0.5f, jy = 0.5f, u1 = 0.0f, u2 = 0.0f;
     if (F.jitter) {
@@ -45,9 +51,28 @@ __global__ __launch_bounds__(kFilmBlock) void filmRayKernel(ptcam::Film F, uint3
         for (int w = 0; w < 5; ++w) s[w] = st.v[w];
         s[5] = st.d;
     }
-    const ptss_ray_query q = ptcam::filmRay(F, (int)(p % (uint32_t)F.width), (int)(p / (uint32_t)F.width), jx, jy, u1, u2);
+    const int x = (int)(p % (uint32_t)F.width), y = (int)(p / (uint32_t)F.width);
+    const ptss_ray_query q = ptcam::filmRay(F, x, y, jx, jy, u1, u2);
     rays[2 * (size_t)i] = float4{q.origin.x, q.origin.y, q.origin.z, q.tmax};
     rays[2 * (size_t)i + 1] = float4{q.direction.x, q.direction.y, q.direction.z, q.pad};
+    if constexpr (kPositions) {
+        float X, Y;
+        ptcam::samplePosition(x, y, jx, jy, X, Y);
+        positions[i] = float2{X, Y};
+    }
+}
+
+__global__ __launch_bounds__(kFilmBlock) void filmRayKernel(ptcam::Film F, uint32_t filmPixels, uint32_t firstPixel,
+                                                            const uint32_t* __restrict__ index, uint32_t n, uint32_t* __restrict__ rng,
+                                                            float4* __restrict__ rays, unsigned long long* __restrict__ rejected) {
+    filmRayBody<false>(F, filmPixels, firstPixel, index, n, rng, rays, nullptr, rejected);
+}
+
+__global__ __launch_bounds__(kFilmBlock) void filmRayPositionsKernel(ptcam::Film F, uint32_t filmPixels, uint32_t firstPixel,
+                                                                     const uint32_t* __restrict__ index, uint32_t n, uint32_t* __restrict__ rng,
+                                                                     float4* __restrict__ rays, float2* __restrict__ positions,
+                                                                     unsigned long long* __restrict__ rejected) {
+    filmRayBody<true>(F, filmPixels, firstPixel, index, n, rng, rays, positions, rejected);
 }
 
 // ptss_accumulate_paths without an index: ray i belongs to pixel firstPixel + i alone — finishPath's read-modify-write (S = 1)
@@ -131,9 +156,15 @@ __global__ __launch_bounds__(kBlock) void rayFeatureKernel(const float4* __restr
 }
 
 hipError_t launchFilmRays(hipStream_t st, const ptcam::Film& film, uint32_t firstPixel, const uint32_t* index, uint32_t n, void* rng, void* rays,
-                          unsigned long long* rejected, unsigned long long* launches) {
-    hipLaunchKernelGGL(filmRayKernel, dim3(filmBlocksFor(n, kFilmBlock)), dim3(kFilmBlock), 0, st, film, (uint32_t)film.width * (uint32_t)film.height,
-                       firstPixel, index, n, static_cast<uint32_t*>(rng), static_cast<float4*>(rays), rejected);
+                          void* positions, unsigned long long* rejected, unsigned long long* launches) {
+    const dim3 grid(filmBlocksFor(n, kFilmBlock)), block(kFilmBlock);
+    const uint32_t filmPixels = (uint32_t)film.width * (uint32_t)film.height;
+    if (!positions)
+        hipLaunchKernelGGL(filmRayKernel, grid, block, 0, st, film, filmPixels, firstPixel, index, n, static_cast<uint32_t*>(rng),
+                           static_cast<float4*>(rays), rejected);
+    else
+        hipLaunchKernelGGL(filmRayPositionsKernel, grid, block, 0, st, film, filmPixels, firstPixel, index, n, static_cast<uint32_t*>(rng),
+                           static_cast<float4*>(rays), static_cast<float2*>(positions), rejected);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) ++*launches;
     return e;

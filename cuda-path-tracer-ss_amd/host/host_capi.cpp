@@ -14,6 +14,7 @@
 #include "ptcamera.h"
 #include "ptadaptive.h"
 #include "ptlinear.h"
+#include "ptsplat.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -555,8 +556,9 @@ int ptss_probe_rng_jump_table(unsigned int* out, size_t words) {
     return PTSS_HOST_OK;
 }
 
-int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index, size_t n, ptss_path_rng* rng,
-                         ptss_ray_query* rays, unsigned long long* rejected) {
+// ptss_probe_film_rays and, with positions, ptss_probe_film_positions
+static int probeFilmRays(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index, size_t n, ptss_path_rng* rng, ptss_ray_query* rays,
+                         ptss_film_position* positions, unsigned long long* rejected) {
     if (ptcam::cameraError(film)) return PTSS_HOST_EINVAL;
     const unsigned long long filmPixels = (unsigned long long)film->width * (unsigned long long)film->height;
     if (filmPixels >= (1ull << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
@@ -568,6 +570,7 @@ int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const 
         const unsigned long long p = index ? index[i] : firstPixel + i;
         if (p >= filmPixels) {
             ++dropped;
+            if (positions) positions[i] = ptss_film_position{ptm::qnan(), ptm::qnan()};
             continue;
         }
         float jx = 0.5f, jy = 0.5f, u1 = 0.0f, u2 = 0.0f;
@@ -584,10 +587,23 @@ int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const 
             for (int w = 0; w < 5; ++w) rng[i].v[w] = st.v[w];
             rng[i].d = st.d;
         }
-        rays[i] = ptcam::filmRay(F, (int)(p % (unsigned long long)F.width), (int)(p / (unsigned long long)F.width), jx, jy, u1, u2);
+        const int x = (int)(p % (unsigned long long)F.width), y = (int)(p / (unsigned long long)F.width);
+        rays[i] = ptcam::filmRay(F, x, y, jx, jy, u1, u2);
+        if (positions) ptcam::samplePosition(x, y, jx, jy, positions[i].x, positions[i].y);
     }
     if (rejected) *rejected = dropped;
     return PTSS_HOST_OK;
+}
+
+int ptss_probe_film_rays(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index, size_t n, ptss_path_rng* rng,
+                         ptss_ray_query* rays, unsigned long long* rejected) {
+    return probeFilmRays(film, firstPixel, index, n, rng, rays, nullptr, rejected);
+}
+
+int ptss_probe_film_positions(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index, size_t n, ptss_path_rng* rng,
+                              ptss_ray_query* rays, ptss_film_position* positions, unsigned long long* rejected) {
+    if (!positions) return PTSS_HOST_EINVAL;
+    return probeFilmRays(film, firstPixel, index, n, rng, rays, positions, rejected);
 }
 
 int ptss_probe_accumulate(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_film_entry* film,
@@ -707,6 +723,69 @@ int ptss_probe_resolve_linear(const ptss_linear_entry* film, size_t firstPixel, 
         float lin[4], hist[4];
         uint32_t px;
         ptlin::resolve(film[p].r, film[p].g, film[p].b, film[p].samples, sc, nullptr, lin, &px, hist);
+        if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
+        if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
+        if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_splat_paths(const ptss_path_result* results, const ptss_film_position* positions, const size_t* firstPixel, size_t n,
+                           ptss_splat_entry* film, int width, int height, const ptss_splat_filter* filter, const ptss_linear_params* params,
+                           unsigned long long* dropped, unsigned long long* clamped) {
+    if (ptspl::filterError(filter) || ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (width < 1 || height < 1 || width > ptspl::kMaxFilmSide || height > ptspl::kMaxFilmSide) return PTSS_HOST_EINVAL;
+    const unsigned long long filmPixels = (unsigned long long)width * (unsigned long long)height;
+    if (filmPixels >= (1ull << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n > 0 && (!results || !positions || !film)) return PTSS_HOST_EINVAL;
+    if (firstPixel && (*firstPixel > filmPixels || n > filmPixels - *firstPixel)) return PTSS_HOST_EINVAL;
+    const ptspl::Filter F = ptspl::filterOf(*filter);
+    const ptlin::Scale sc = ptlin::scaleOf(*params);
+    unsigned long long nDropped = 0, nClamped = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const float X = positions[i].x, Y = positions[i].y;
+        bool drop = ptspl::outside(X, F.radius, width) || ptspl::outside(Y, F.radius, height);
+        if (firstPixel) {
+            const unsigned long long home = *firstPixel + i;
+            drop = ptspl::stray(X, Y, (int)(home % (unsigned long long)width), (int)(home / (unsigned long long)width));
+        }
+        if (drop) {
+            ++nDropped;
+            continue;
+        }
+        ptlin::u64 q[3];
+        nClamped += ptlin::sampleToFixed(results[i].radiance.x, results[i].radiance.y, results[i].radiance.z, sc, q);
+        const int x0 = ptspl::firstTap(F, X), y0 = ptspl::firstTap(F, Y);
+        for (int y = y0; y <= y0 + 2 * F.reach; ++y) {
+            if (y < 0 || y >= height) continue;
+            const uint32_t wy = ptspl::axisWeight(F, Y, y);
+            for (int x = x0; x <= x0 + 2 * F.reach; ++x) {
+                if (x < 0 || x >= width) continue;
+                const uint32_t W = ptspl::tapWeight(ptspl::axisWeight(F, X, x), wy);
+                if (W == 0u) continue;
+                ptss_splat_entry& e = film[(size_t)y * (size_t)width + (size_t)x];
+                e.r += ptspl::contribution(q[0], W);
+                e.g += ptspl::contribution(q[1], W);
+                e.b += ptspl::contribution(q[2], W);
+                e.weight += W;
+            }
+        }
+    }
+    if (dropped) *dropped = nDropped;
+    if (clamped) *clamped = nClamped;
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_resolve_splat(const ptss_splat_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history) {
+    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (count == 0) return PTSS_HOST_OK;
+    if (!film || firstPixel >= (size_t(1) << 31) || count >= (size_t(1) << 31) || firstPixel + count >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    const ptlin::Scale sc = ptlin::scaleOf(*params);
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        float lin[4], hist[4];
+        uint32_t px;
+        ptspl::resolve(film[p].r, film[p].g, film[p].b, film[p].weight, sc, nullptr, lin, &px, hist);
         if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
         if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
         if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};

@@ -36,6 +36,9 @@
 //             [--linear [exposure]] with --film: the samples go into a linear film (ptss_accumulate_paths_linear, default parameters) and
 //                                   ptss_resolve_linear with that exposure (default 1) makes the screenshot, image.pfm — the linear means,
 //                                   unexposed — beside it and, with --denoise, the history the filter takes. Not with --adaptive
+//             [--filter box|tent|gaussian[,radius[,alpha]]]   with --linear: the film is a filtered one — rounds go through
+//                                   ptss_generate_rays_positions, the trace, ptss_splat_paths_homed and, at the end, ptss_resolve_splat
+//                                   (radius default 1, alpha default 2). Without it the program's bytes are those of --linear alone
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -64,6 +67,7 @@ int main(int argc, char* argv[]) {
     int adaptive = -1;     // --adaptive: -1 absent, else the planned rounds behind the uniform ones
     float adaptiveThreshold = -1.f;   // ... and the plan's threshold when given
     float linear = -1.f;   // --linear: -1 absent, else the exposure of the resolve
+    std::string splat;     // --filter: the reconstruction filter of the linear film, empty = none (a box by pixel index)
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -102,6 +106,7 @@ int main(int argc, char* argv[]) {
             if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) linear = (float)atof(next());
             if (!(linear >= 0.f && linear < 1e30f)) { fprintf(stderr, "bad --linear (exposure)\n"); return 2; }
         }
+        else if (a == "--filter") splat = next();
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -153,6 +158,18 @@ int main(int argc, char* argv[]) {
     if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
     if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
     if (linear >= 0.f && (film.empty() || adaptive >= 0)) { fprintf(stderr, "--linear needs --film and no --adaptive\n"); return 2; }
+    ptss_splat_filter splatFilter;
+    PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
+    if (!splat.empty()) {
+        const size_t comma = splat.find(',');
+        const std::string kind = splat.substr(0, comma);
+        splatFilter.kind = kind == "box" ? PTSS_SPLAT_BOX : kind == "tent" ? PTSS_SPLAT_TENT : kind == "gaussian" ? PTSS_SPLAT_GAUSSIAN : -1;
+        const int got = comma == std::string::npos ? 0 : sscanf(splat.c_str() + comma + 1, "%f,%f", &splatFilter.radius, &splatFilter.alpha);
+        if (linear < 0.f || splatFilter.kind < 0 || (comma != std::string::npos && got < 1)) {
+            fprintf(stderr, "--filter needs --linear and box, tent or gaussian[,radius[,alpha]]\n");
+            return 2;
+        }
+    }
     for (const auto& p : picks)
         if (p.first < 0 || p.first >= width || p.second < 0 || p.second >= height) { fprintf(stderr, "--pick outside the frame\n"); return 2; }
     if (gpus > 0) {   // one context, stream and display tile per GPU; RCCL communicator over them
@@ -262,7 +279,8 @@ int main(int argc, char* argv[]) {
         const size_t n = (size_t)width * (size_t)height;
         void *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dFilm = nullptr, *dHist = nullptr, *dFeat = nullptr, *dOut = nullptr;
         void *dMoments = nullptr, *dCdf = nullptr, *dIndex = nullptr, *dInfo = nullptr;   // --adaptive
-        void *dLinear = nullptr, *dMeans = nullptr;   // --linear
+        void *dLinear = nullptr, *dMeans = nullptr;   // --linear (with --filter dLinear holds ptss_splat_entry, the same 32 bytes per pixel)
+        void* dPos = nullptr;                         // --filter
         ptss_linear_params linearParams;
         PTSS_HANDLE(ptss_default_linear_params(&linearParams));
         const bool filter = denoise != -2;
@@ -291,13 +309,22 @@ int main(int argc, char* argv[]) {
                 fprintf(stderr, "--linear: device buffers\n");
                 return 1;
             }
+            static_assert(sizeof(ptss_splat_entry) == sizeof(ptss_linear_entry), "one film buffer serves both");
+            if (!splat.empty() && hipMalloc(&dPos, n * sizeof(ptss_film_position)) != hipSuccess) { fprintf(stderr, "--filter: device buffers\n"); return 1; }
         }
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
-            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            if (dPos) {
+                PTSS_HANDLE(ptss_generate_rays_positions(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, (ptss_film_position*)dPos, NULL));
+            } else {
+                PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            }
             PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
                                              NULL));
-            if (linear >= 0.f) {
+            if (dPos) {
+                PTSS_HANDLE(ptss_splat_paths_homed(ctx, (const ptss_path_result*)dRes, (const ptss_film_position*)dPos, 0, n, (ptss_splat_entry*)dLinear,
+                                                   width, height, &splatFilter, &linearParams, NULL));
+            } else if (linear >= 0.f) {
                 PTSS_HANDLE(ptss_accumulate_paths_linear(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_linear_entry*)dLinear, n, &linearParams, NULL));
             } else if (adaptive >= 0) {
                 PTSS_HANDLE(ptss_accumulate_paths_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm,
@@ -330,8 +357,13 @@ int main(int argc, char* argv[]) {
                    info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
         if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
-            PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
-                                            (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            if (dPos) {
+                PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
+                                               (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            } else {
+                PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
+                                                (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            }
             PTSS_HANDLE(ptss_synchronize(ctx));
             std::vector<ptss_history_entry> means(n);
             if (hipMemcpy(means.data(), dMeans, n * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--linear: read-back\n"); return 1; }
@@ -359,7 +391,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

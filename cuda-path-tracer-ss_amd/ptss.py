@@ -16,6 +16,7 @@ from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS,
                         PathOptions, PlanInfo, PlanParams, SCENE_LAYOUT_FIELDS,
                         SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
+from ptss_types import POSITION_DTYPE, SPLAT_BOX, SPLAT_DTYPE, SPLAT_GAUSSIAN, SPLAT_TENT, FilmPosition, SplatEntry, SplatFilter
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -191,6 +192,11 @@ def host_lib():
         L.ptss_probe_accumulate_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LinearParams),
                                                    C.POINTER(C.c_ulonglong)]
         L.ptss_probe_resolve_linear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptss_probe_film_positions.argtypes = [C.POINTER(FilmCamera), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_splat_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                             C.POINTER(SplatFilter), C.POINTER(LinearParams), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_resolve_splat.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_void_p, C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -288,6 +294,13 @@ def device_lib():
         L.ptss_accumulate_paths_linear.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(LinearParams), vp]
         L.ptss_resolve_linear.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp]
         L.ptss_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_splat_filter.argtypes = [C.POINTER(SplatFilter)]
+        L.ptss_generate_rays_positions.argtypes = [vp, C.POINTER(FilmCamera), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]
+        L.ptss_splat_paths.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, C.c_int, C.POINTER(SplatFilter), C.POINTER(LinearParams), vp]
+        L.ptss_splat_paths_homed.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, C.c_int, C.POINTER(SplatFilter),
+                                             C.POINTER(LinearParams), vp]
+        L.ptss_resolve_splat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp]
+        L.ptss_splat_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -715,16 +728,90 @@ def probe_resolve_linear(film, first_pixel=0, count=None, params=None, linear=Tr
     """ptss_resolve_linear on the host, with the literal tone map -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample
     count, pixels (P, 4) uint8, history (P,) HISTORY_DTYPE), each None when not asked for. film: (P,) LINEAR_DTYPE or (P, 4) uint64;
     count: None = to the film's end; linear / pixels / history: None (not written), True (zeros beforehand) or the content beforehand."""
-    f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
+    return _probe_resolve("ptss_probe_resolve_linear", LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+
+
+def _probe_resolve(name, film_dtype, film, first_pixel, count, params, linear, pixels, history):
+    """The body of probe_resolve_linear and probe_resolve_splat: one host call over a film of 32-byte entries."""
+    f = _rows(film, film_dtype, 4, np.uint64, "film")
     P = len(f)
     first_pixel, count = _linear_range(P, first_pixel, count)
     ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
     params = params if params is not None else linear_params()
     ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    rc = host_lib().ptss_probe_resolve_linear(ptr(f), first_pixel, count, C.byref(params), ptr(ln), ptr(px), ptr(hs))
+    rc = getattr(host_lib(), name)(ptr(f), first_pixel, count, C.byref(params), ptr(ln), ptr(px), ptr(hs))
     if rc != 0:
-        raise PtssError(f"ptss_probe_resolve_linear: {rc}")
+        raise PtssError(f"{name}: {rc}")
     return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+
+# ---- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat; DESIGN.md §3.30) ----
+_SPLAT_KINDS = {"box": SPLAT_BOX, "tent": SPLAT_TENT, "gaussian": SPLAT_GAUSSIAN}
+
+
+def splat_filter(kind="tent", radius=1.0, alpha=2.0):
+    """A ptss_splat_filter; kind: "box", "tent", "gaussian" or a PTSS_SPLAT_* value; the defaults are ptss_default_splat_filter's (design
+    choices, not measurements)."""
+    f = SplatFilter()
+    f.structSize = C.sizeof(SplatFilter)
+    f.kind, f.radius, f.alpha, f.reserved = int(_SPLAT_KINDS.get(kind, kind)), float(radius), float(alpha), 0
+    return f
+
+
+def _positions(positions, n):
+    a = np.asarray(positions)
+    if a.dtype == POSITION_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 2)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape != (n, 2):
+        raise ValueError("positions: one (x, y) per result, (N,) POSITION_DTYPE or (N, 2) float32")
+    return a
+
+
+def probe_film_positions(film, rng, first_pixel=0, index=None, rays=None):
+    """ptss_generate_rays_positions on the host -> probe_film_rays' ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE, ...) with the positions, (N,)
+    POSITION_DTYPE, in front of the dropped count: (rays, streams, positions, dropped)."""
+    s = _rng_words(rng)
+    n = len(s)
+    idx = _film_index(index, n)
+    out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
+    if len(out) != n:
+        raise ValueError("rays: one row per stream")
+    pos = np.zeros((n, 2), dtype=np.float32)
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_film_positions(C.byref(film), int(first_pixel), idx.ctypes.data_as(C.c_void_p) if idx is not None else None, n,
+                                              s.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p),
+                                              C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_film_positions: {rc}")
+    return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1), pos.view(POSITION_DTYPE).reshape(-1), int(rejected.value)
+
+
+def probe_splat_paths(results, positions, film, width, height, filter=None, params=None, homed_first_pixel=None):
+    """ptss_splat_paths (homed_first_pixel = None) or ptss_splat_paths_homed on the host (csrc/ptsplat.h; the specification of the
+    device's film) -> (film afterwards (P,) SPLAT_DTYPE, samples dropped, samples clamped). film: (width * height,) SPLAT_DTYPE or
+    (P, 4) uint64 (not modified)."""
+    r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+    n = len(r)
+    pos = _positions(positions, n)
+    f = _rows(film, SPLAT_DTYPE, 4, np.uint64, "film", copy=True)
+    if len(f) != int(width) * int(height):
+        raise ValueError("film: width * height entries")
+    filter = filter if filter is not None else splat_filter()
+    params = params if params is not None else linear_params()
+    first = C.byref(C.c_size_t(int(homed_first_pixel))) if homed_first_pixel is not None else None
+    dropped, clamped = C.c_ulonglong(0), C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_splat_paths(r.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p), first, n, f.ctypes.data_as(C.c_void_p),
+                                           int(width), int(height), C.byref(filter), C.byref(params), C.byref(dropped), C.byref(clamped))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_splat_paths: {rc}")
+    return f.view(SPLAT_DTYPE).reshape(-1), int(dropped.value), int(clamped.value)
+
+
+def probe_resolve_splat(film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+    """ptss_resolve_splat on the host, with the literal tone map: probe_resolve_linear's arguments and results over a (P,) SPLAT_DTYPE
+    film; the weight of linear and history is the summed filter weight (1 per whole sample)."""
+    return _probe_resolve("ptss_probe_resolve_splat", SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels, history)
 
 
 def default_denoise_params(**overrides):
@@ -1456,8 +1543,10 @@ class Renderer:
             raise ValueError(f"{what}: a contiguous {dtype} device tensor of shape ({'N' if n is None else n}{', %d' % columns if columns else ''})")
         return C.c_void_p(t.data_ptr())
 
-    def generate_rays(self, film, rng, first_pixel=0, index=None, rays=None):
+    def generate_rays(self, film, rng, first_pixel=0, index=None, rays=None, positions=None):
         """ptss_generate_rays: the eye rays of film pixels index[i] (first_pixel + i without an index) from streams rng[i].
+        positions (ptss_generate_rays_positions): numpy: True -> a third result, the samples' places on the film, (N,) POSITION_DTYPE;
+        torch: an (N, 2) float32 tensor to write.
         numpy: rng (N,) PATH_RNG_DTYPE or (N, 6) uint32 -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE: the streams afterwards); rays: the
         buffer's content beforehand (zeros otherwise; an entry whose index leaves the film keeps it). torch: rng a contiguous (N, 6)
         int32 device tensor, UPDATED IN PLACE, index an (N,) int32 tensor or None, rays an (N, 8) float32 tensor to write (a new one
@@ -1473,7 +1562,11 @@ class Renderer:
             d_rays = self._torch_ptr(rays, "rays", "float32", 8, rng.device, n)
             d_idx = self._torch_ptr(index, "index", "int32", 0, rng.device, n) if index is not None else None
             stream = torch.cuda.current_stream(rng.device).cuda_stream
-            _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, C.c_void_p(stream)))
+            if positions is not None:
+                d_pos = self._torch_ptr(positions, "positions", "float32", 2, rng.device, n)
+                _check(L.ptss_generate_rays_positions(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, d_pos, C.c_void_p(stream)))
+            else:
+                _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, C.c_void_p(stream)))
             return rays
         s = _rng_words(rng)
         n = len(s)
@@ -1481,6 +1574,11 @@ class Renderer:
         out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
         if len(out) != n:
             raise ValueError("rays: one row per stream")
+        if positions is not None:
+            pos = np.zeros((n, 2), dtype=np.float32)
+            self._round_trip([idx, s, out, pos], lambda d: _check(L.ptss_generate_rays_positions(self._ctx, C.byref(film), int(first_pixel), d[0], n,
+                                                                                                   d[1], d[2], d[3], None)), read=(1, 2, 3))
+            return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1), pos.view(POSITION_DTYPE).reshape(-1)
         if n == 0:
             _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), None, 0, None, None, None))
         else:
@@ -1620,7 +1718,10 @@ class Renderer:
         content beforehand -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample count, pixels (P, 4) uint8, history (P,)
         HISTORY_DTYPE), each None when NULL. torch: film (P, 4) int64, linear (P, 4) float32 or None, pixels (P, 4) uint8 or None,
         history (P, 4) float32 or None, all on one device, WRITTEN IN PLACE -> None, on the current stream."""
-        L = device_lib()
+        return self._resolve(device_lib().ptss_resolve_linear, LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+
+    def _resolve(self, call, film_dtype, film, first_pixel, count, params, linear, pixels, history):
+        """The body of resolve_linear and resolve_splat: `call` over a film of 32-byte entries."""
         params = params if params is not None else linear_params()
         if type(film).__module__.split(".")[0] == "torch":
             import sys
@@ -1632,19 +1733,70 @@ class Renderer:
             d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
             d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
             stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_resolve_linear(self._ctx, d_film, first_pixel, count, C.byref(params), d_ln, d_px, d_hs, C.c_void_p(stream)))
+            _check(call(self._ctx, d_film, first_pixel, count, C.byref(params), d_ln, d_px, d_hs, C.c_void_p(stream)))
             return None
-        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
+        f = _rows(film, film_dtype, 4, np.uint64, "film")
         P = len(f)
         first_pixel, count = _linear_range(P, first_pixel, count)
         ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
         if count == 0:
-            _check(L.ptss_resolve_linear(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
+            _check(call(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
         else:
             self._round_trip([f, ln, px, hs],
-                             lambda d: _check(L.ptss_resolve_linear(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None)),
+                             lambda d: _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None)),
                              read=(1, 2, 3))
         return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+    # --- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat) ------------------
+    def splat_paths(self, results, positions, film, width, height, filter=None, params=None, homed_first_pixel=None):
+        """ptss_splat_paths, or with homed_first_pixel ptss_splat_paths_homed (sample i was aimed at pixel homed_first_pixel + i): the
+        linear radiance of `results` spread around `positions` by the filter.
+        numpy: results (N,) PATH_RESULT_DTYPE or (N, 4) float32; positions (N,) POSITION_DTYPE or (N, 2) float32; film (width * height,)
+        SPLAT_DTYPE or (P, 4) uint64 (not modified) -> the film afterwards, (P,) SPLAT_DTYPE. torch: results (N, 4) float32, positions
+        (N, 2) float32, film (P, 4) int64 UPDATED IN PLACE, all on one device -> None, on the current stream."""
+        L = device_lib()
+        filter = filter if filter is not None else splat_filter()
+        params = params if params is not None else linear_params()
+        width, height = int(width), int(height)
+
+        def call(res, pos, n, f, st):
+            if homed_first_pixel is None:
+                _check(L.ptss_splat_paths(self._ctx, res, pos, n, f, width, height, C.byref(filter), C.byref(params), st))
+            else:
+                _check(L.ptss_splat_paths_homed(self._ctx, res, pos, int(homed_first_pixel), n, f, width, height, C.byref(filter), C.byref(params), st))
+
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_pos = self._torch_ptr(positions, "positions", "float32", 2, dev, n)
+            d_film = self._torch_ptr(film, "film", "int64", 4, dev, width * height)
+            call(d_res, d_pos, n, d_film, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        pos = _positions(positions, n)
+        f = _rows(film, SPLAT_DTYPE, 4, np.uint64, "film", copy=True)
+        if len(f) != width * height:
+            raise ValueError("film: width * height entries")
+        if n == 0:
+            call(None, None, 0, None, None)
+        else:
+            self._round_trip([r, pos, f], lambda d: call(d[0], d[1], n, d[2], None), read=(2,))
+        return f.view(SPLAT_DTYPE).reshape(-1)
+
+    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+        """ptss_resolve_splat: resolve_linear's arguments and results over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64); the
+        weight of linear and history is the summed filter weight."""
+        return self._resolve(device_lib().ptss_resolve_splat, SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+
+    def splat_stats(self):
+        """ptss_splat_stats: (scatter launches, homed launches, resolves, samples dropped, samples clamped) since the context was
+        created; synchronises with the stream of the latest splat."""
+        out = (C.c_ulonglong * 5)()
+        _check(device_lib().ptss_splat_stats(self._ctx, out))
+        return tuple(int(v) for v in out)
 
     def linear_launches(self):
         """ptss_linear_launches: (accumulate_paths_linear, resolve_linear calls that launched since the context was created)."""

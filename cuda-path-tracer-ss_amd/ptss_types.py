@@ -140,6 +140,25 @@ class LinearParams(C.Structure):   # ptss_linear_params: how a linear film count
     _fields_ = [("structSize", C.c_uint), ("scaleLog2", C.c_int), ("clampMax", C.c_float), ("exposure", C.c_float), ("reserved", C.c_uint)]
 
 
+class FilmPosition(C.Structure):   # ptss_film_position: where a sample lies on the film, in pixels
+    _fields_ = [("x", C.c_float), ("y", C.c_float)]
+
+
+POSITION_DTYPE = np.dtype([("x", np.float32), ("y", np.float32)])
+SPLAT_BOX, SPLAT_TENT, SPLAT_GAUSSIAN = 0, 1, 2
+
+
+class SplatFilter(C.Structure):   # ptss_splat_filter: the reconstruction filter of a filtered linear film
+    _fields_ = [("structSize", C.c_uint), ("kind", C.c_int), ("radius", C.c_float), ("alpha", C.c_float), ("reserved", C.c_uint)]
+
+
+class SplatEntry(C.Structure):   # ptss_splat_entry: the weighted fixed-point sums of one filtered-film pixel and the sum of the weights
+    _fields_ = [("r", C.c_ulonglong), ("g", C.c_ulonglong), ("b", C.c_ulonglong), ("weight", C.c_ulonglong)]
+
+
+SPLAT_DTYPE = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("weight", np.uint64)])
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -187,6 +206,8 @@ assert C.sizeof(FilmEntry) == 16 == FILM_DTYPE.itemsize and FilmEntry.samples.of
 assert C.sizeof(PlanParams) == 16 and PlanParams.threshold.offset == 12 and C.sizeof(PlanInfo) == 32 and PlanInfo.uniform.offset == 20
 assert C.sizeof(LinearEntry) == 32 == LINEAR_DTYPE.itemsize and LinearEntry.samples.offset == 24 == LINEAR_DTYPE.fields["samples"][1]
 assert LinearEntry.clamped.offset == 28 == LINEAR_DTYPE.fields["clamped"][1] and C.sizeof(LinearParams) == 20 and LinearParams.reserved.offset == 16
+assert C.sizeof(FilmPosition) == 8 == POSITION_DTYPE.itemsize and C.sizeof(SplatFilter) == 20 and SplatFilter.reserved.offset == 16
+assert C.sizeof(SplatEntry) == 32 == SPLAT_DTYPE.itemsize and SplatEntry.weight.offset == 24 == SPLAT_DTYPE.fields["weight"][1]
 
 
 def struct_to_dict(s):

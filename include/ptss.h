@@ -439,6 +439,55 @@ int ptss_resolve_linear(ptss_context* ctx, const ptss_linear_entry* dev_film, si
                         ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
 int ptss_linear_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] accumulates, [1] resolves */
 
+/* The filtered linear film: the linear film's fixed-point samples, spread over the pixels around the sample's position
+ * by a box, a tent or a Gaussian pixel filter (ptss_splat_filter) whose weights are integers. Every contribution is an integer, so a
+ * film (ptss_splat_entry, zero-filled by the caller) is exact and the same bytes for every order of the samples, every split of a batch
+ * into calls and both kernel forms. csrc/ptsplat.h has the arithmetic; its host build (ptss_probe_splat_paths, ptss_probe_resolve_splat)
+ * is the specification and the device agrees with it byte for byte.
+ *
+ * ptss_generate_rays_positions: ptss_generate_rays — the same rays and streams — and dev_positions[i] = (x + jx, y + jy), where sample i
+ * lies on the film in pixels (the pixel's centre with jitter = 0). An index entry >= width * height writes no ray and no stream, is
+ * counted in ptss_film_rejected, and gets the position (NaN, NaN), which every splat drops. dev_positions: required, 8-byte aligned.
+ * It counts in ptss_film_launches()[0].
+ *
+ * A sample at (X, Y) and pixel (i, j): d = X - (i + 0.5), the per-axis profile f(d) in float32 — box: 1 for -R <= d < R; tent:
+ * max(0, 1 - |d| / R); Gaussian: max(0, exp(-alpha d^2) - exp(-alpha R^2)) for |d| < R — wq = (uint32_t)(f * 65536 + 0.5) per axis, the
+ * tap's weight W = (wqx * wqy + 32768) >> 16, and the entry of pixel (i, j) gains (q * W + 32768) >> 16 per channel, q the linear film's
+ * fixed-point sample (ptss_linear_params: scaleLog2, clampMax), and W in weight. Taps outside the film and taps with W = 0 add nothing.
+ *
+ * ptss_splat_paths: any positions in any order, integer atomics. A sample with a coordinate that is not finite or outside
+ * [-R, width + R] (resp. height) is dropped and counted.
+ * ptss_splat_paths_homed: the caller states that sample i was aimed at pixel firstPixel + i (ptss_generate_rays_positions without an
+ * index); a sample whose position is outside that pixel's closed square [hx, hx + 1] x [hy, hy + 1] (NaN included) is dropped and
+ * counted. One thread per output pixel gathers its taps; no atomics, one plain read-modify-write per pixel: two calls on one film must
+ * be ordered by the caller. The film's bytes equal ptss_splat_paths' on the same samples.
+ * ptss_resolve_splat: for pixels firstPixel .. firstPixel + count, Wt = weight: Wt = 0 gives ptss_resolve_linear's N = 0 row; otherwise
+ * per channel m = floor((S * 2^16 + Wt / 2) / Wt) exactly, mean = (float)m * 2^-scaleLog2, and the outputs of ptss_resolve_linear from
+ * that mean, with (float)Wt * 2^-16 as the sample weight. With the box at radius 0.5 the film resolves to ptss_resolve_linear's bytes.
+ *
+ * All calls are asynchronous on hipStream (NULL: the context's), leave no trace in frame state, own no bit of ptss_launched_kernels and
+ * serve sharded contexts. Refused without touching the device and without counting (PTSS_EINVAL): a null ctx, filter, params or
+ * required buffer, a wrong structSize, an unknown kind, a radius outside [0.5, 2], a Gaussian's alpha that is not finite and positive,
+ * a non-zero reserved, whatever ptss_accumulate_paths_linear refuses about params, a pointer that is not aligned (16 bytes for
+ * results, film, linear and history, 8 for positions, 4 for pixels); (PTSS_ERANGE): width or height outside [1, 2^22], width * height
+ * or n >= 2^31, firstPixel + n beyond the film. n = 0 and count = 0 return PTSS_OK with nothing launched.
+ * ptss_splat_stats: [0] scatter launches, [1] homed launches, [2] resolves (counted on the host), [3] samples dropped, [4] samples kept
+ * with a clamped channel (counted on the device: the call synchronises with the stream of the latest splat). ptss_default_splat_filter:
+ * tent, radius 1, alpha 2 — design choices, not measurements. */
+int ptss_default_splat_filter(ptss_splat_filter* filter);
+int ptss_generate_rays_positions(ptss_context* ctx, const ptss_film_camera* film, size_t firstPixel, const uint32_t* dev_index /* may be NULL */,
+                                 size_t n, ptss_path_rng* dev_rng, ptss_ray_query* dev_rays, ptss_film_position* dev_positions, void* hipStream);
+int ptss_splat_paths(ptss_context* ctx, const ptss_path_result* dev_results, const ptss_film_position* dev_positions, size_t n,
+                     ptss_splat_entry* dev_film, int width, int height, const ptss_splat_filter* filter, const ptss_linear_params* params,
+                     void* hipStream);
+int ptss_splat_paths_homed(ptss_context* ctx, const ptss_path_result* dev_results, const ptss_film_position* dev_positions, size_t firstPixel,
+                           size_t n, ptss_splat_entry* dev_film, int width, int height, const ptss_splat_filter* filter,
+                           const ptss_linear_params* params, void* hipStream);
+int ptss_resolve_splat(ptss_context* ctx, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                       ptss_history_entry* dev_linear /* may be NULL */, ptss_uchar4* dev_pixels /* may be NULL */,
+                       ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_splat_stats(ptss_context* ctx, unsigned long long* out5);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

@@ -211,6 +211,24 @@ int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t
 int ptss_probe_resolve_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
                               ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
 
+/* ptss_generate_rays_positions on the host: ptss_probe_film_rays' arguments, rays and streams, and positions[i] = where the sample
+ * lies on the film (csrc/ptcamera.h samplePosition: the x + jx, y + jy the ray is made from); {NaN, NaN} for an index entry that leaves
+ * the film. PTSS_HOST_EINVAL: ptss_probe_film_rays', or null positions. */
+int ptss_probe_film_positions(const ptss_film_camera* film, size_t firstPixel, const uint32_t* index /* may be NULL */, size_t n,
+                              ptss_path_rng* rng /* in/out */, ptss_ray_query* rays, ptss_film_position* positions,
+                              unsigned long long* rejected);
+/* ptss_splat_paths on the host (csrc/ptsplat.h — the very operations the kernels evaluate; this build is the specification): a
+ * straight loop over samples and their taps. firstPixel == NULL: the scatter form's drop rule (a coordinate that is not finite or outside
+ * [-R, extent + R]); else sample i is homed at pixel *firstPixel + i and a sample outside its home's closed square is dropped
+ * (ptss_splat_paths_homed). *dropped and *clamped (each may be NULL; set, not added to): samples dropped, and samples kept with a channel
+ * that was NaN or above clampMax. PTSS_HOST_EINVAL: whatever the two calls refuse, alignment aside. */
+int ptss_probe_splat_paths(const ptss_path_result* results, const ptss_film_position* positions, const size_t* firstPixel /* may be NULL */,
+                           size_t n, ptss_splat_entry* film, int width, int height, const ptss_splat_filter* filter,
+                           const ptss_linear_params* params, unsigned long long* dropped, unsigned long long* clamped);
+/* ptss_resolve_splat on the host, with the LITERAL tone map: ptss_probe_resolve_linear's outputs from a filtered film. */
+int ptss_probe_resolve_splat(const ptss_splat_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
+
 #ifdef __cplusplus
 }
 #endif

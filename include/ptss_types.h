@@ -261,6 +261,35 @@ typedef struct ptss_linear_params {
     unsigned int reserved;   /* 0 */
 } ptss_linear_params;
 
+/* Where on the film a sample lies, in pixels (ptss_generate_rays_positions): pixel (i, j) owns [i, i + 1) x [j, j + 1),
+ * its centre is (i + 0.5, j + 0.5). 8 B, 8-byte aligned access. */
+typedef struct ptss_film_position {
+    float x, y;
+} ptss_film_position;
+
+/* The reconstruction filter of a filtered linear film (ptss_splat_paths). kind: PTSS_SPLAT_*; radius in [0.5, 2], in
+ * pixels: the filter is separable and zero from radius on; alpha > 0, finite: the Gaussian's exp(-alpha d^2) (the other kinds do not
+ * read it). */
+typedef struct ptss_splat_filter {
+    unsigned int structSize; /* sizeof(ptss_splat_filter) as the caller compiled it */
+    int kind;
+    float radius;
+    float alpha;
+    unsigned int reserved;   /* 0 */
+} ptss_splat_filter;
+
+#define PTSS_SPLAT_BOX 0
+#define PTSS_SPLAT_TENT 1
+#define PTSS_SPLAT_GAUSSIAN 2
+
+/* One pixel of a filtered linear film: the weighted sums of the samples' fixed-point radiance (ptss_linear_params.scaleLog2 fraction
+ * bits) and the sum of the weights, a weight of 1 being 65536. 32 B, 16-byte aligned access; a new film is all zero; fewer than 2^23
+ * taps per pixel keep the sums below 2^63. */
+typedef struct ptss_splat_entry {
+    unsigned long long r, g, b;
+    unsigned long long weight;
+} ptss_splat_entry;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -325,6 +354,12 @@ static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g) 
 static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
                   offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
               "ptss_linear_params is five 32-bit words");
+static_assert(sizeof(ptss_film_position) == 8 && offsetof(ptss_film_position, y) == 4, "ptss_film_position is two floats");
+static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, kind) == 4 && offsetof(ptss_splat_filter, radius) == 8 &&
+                  offsetof(ptss_splat_filter, alpha) == 12 && offsetof(ptss_splat_filter, reserved) == 16,
+              "ptss_splat_filter is five 32-bit words");
+static_assert(sizeof(ptss_splat_entry) == 32 && offsetof(ptss_splat_entry, g) == 8 && offsetof(ptss_splat_entry, weight) == 24,
+              "ptss_splat_entry is two 16-byte rows");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -357,6 +392,12 @@ _Static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g)
 _Static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
                    offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
                "ptss_linear_params is five 32-bit words");
+_Static_assert(sizeof(ptss_film_position) == 8 && offsetof(ptss_film_position, y) == 4, "ptss_film_position is two floats");
+_Static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, kind) == 4 && offsetof(ptss_splat_filter, radius) == 8 &&
+                   offsetof(ptss_splat_filter, alpha) == 12 && offsetof(ptss_splat_filter, reserved) == 16,
+               "ptss_splat_filter is five 32-bit words");
+_Static_assert(sizeof(ptss_splat_entry) == 32 && offsetof(ptss_splat_entry, g) == 8 && offsetof(ptss_splat_entry, weight) == 24,
+               "ptss_splat_entry is two 16-byte rows");
 #endif
 
 #ifdef __cplusplus
