@@ -26,6 +26,7 @@
 #include "ptadaptive.h"
 #include "ptlinear.h"
 #include "ptsplat.h"
+#include "ptmeter.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -158,6 +159,7 @@ struct ptss_context {
     unsigned long long adaptiveLaunches[2] = {0, 0};          // ptss_accumulate_paths_stats, ptss_plan_samples calls that launched
     unsigned long long linearLaunches[2] = {0, 0};            // ptss_accumulate_paths_linear, ptss_resolve_linear calls that launched
     unsigned long long splatLaunches[3] = {0, 0, 0};          // ptss_splat_paths, ptss_splat_paths_homed, ptss_resolve_splat calls that launched
+    unsigned long long meterLaunches[3] = {0, 0, 0};          // meter histograms, ptss_meter_exposure, metered resolves that launched
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
@@ -1615,6 +1617,103 @@ int ptss_splat_stats(ptss_context* c, unsigned long long* out5) {
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(hipStreamSynchronize(c->splatStream));
     HIP_TRY(hipMemcpy(out5 + 3, c->dTotal + kSplatCountersWord, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PTSS_OK;
+}
+
+// ---- the meter of the two linear films (ptss_meter.hip; csrc/ptmeter.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_meter_params(ptss_meter_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_meter_params);
+    p->key = 0.18f;
+    p->lowPermille = 100u;
+    p->highPermille = 20u;
+    p->rate = 1.f;
+    p->minExposure = 1.f / 65536.f;
+    p->maxExposure = 65536.f;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+// What the calls over a range of a film share behind their own ctx and params checks, in ptss_resolve_linear's order: count == 0 (nothing
+// to do: PTSS_OK with go == false), the call's own verdict on its buffers (FilmCall's `badBuffers`), the range, the scene image where the
+// call reads it, device and stream. FilmCall's firstPixel and n are the range; filmPixels stays 0
+static int rangeCall(ptss_context* c, FilmCall* f, size_t firstPixel, size_t count, const char* badBuffers, bool readsImage, void* hipStream) {
+    if (count == 0) return PTSS_OK;
+    if (badBuffers) return fail(PTSS_EINVAL, badBuffers);
+    if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count)) return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
+    const SceneImage& im = c->images[0];
+    if (readsImage && !im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    *f = FilmCall{true, streamOf(c, hipStream), (uint32_t)firstPixel, (uint32_t)count, 0u, readsImage ? quantTableOf(im) : nullptr};
+    return PTSS_OK;
+}
+
+static int meterFilm(ptss_context* c, const void* dev_film, bool splat, size_t firstPixel, size_t count, uint32_t* dev_histogram, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    const char* bad = !dev_film || !dev_histogram ? "null film or histogram with count > 0"
+                      : ((uintptr_t)dev_film & 15u) || ((uintptr_t)dev_histogram & 3u) ? "film must be 16-byte aligned, dev_histogram 4-byte aligned"
+                                                                                         : nullptr;
+    FilmCall f;
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, false, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchMeterHistogram(f.st, dev_film, splat, f.firstPixel, f.n, dev_histogram, &c->meterLaunches[0]));
+    return PTSS_OK;
+}
+
+int ptss_meter_linear(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, uint32_t* dev_histogram, void* hipStream) {
+    return meterFilm(c, dev_film, false, firstPixel, count, dev_histogram, hipStream);
+}
+
+int ptss_meter_splat(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, uint32_t* dev_histogram, void* hipStream) {
+    return meterFilm(c, dev_film, true, firstPixel, count, dev_histogram, hipStream);
+}
+
+int ptss_meter_exposure(ptss_context* c, const uint32_t* dev_histogram, const ptss_linear_params* params, const ptss_meter_params* meter,
+                        ptss_meter_state* dev_state, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptmeter::paramsError(meter)) return fail(PTSS_EINVAL, what);
+    if (!dev_histogram || !dev_state) return fail(PTSS_EINVAL, "null histogram or state");
+    if (((uintptr_t)dev_histogram & 3u) || ((uintptr_t)dev_state & 7u)) return fail(PTSS_EINVAL, "dev_histogram must be 4-byte aligned, dev_state 8-byte aligned");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchMeterExposure(streamOf(c, hipStream), dev_histogram, *params, *meter, dev_state, &c->meterLaunches[1]));
+    return PTSS_OK;
+}
+
+static int resolveMetered(ptss_context* c, const void* dev_film, bool splat, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                          const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history,
+                          void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    const char* bad = !dev_film || !dev_state ? "null film or state with count > 0"
+                      : (((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_state & 7u) ||
+                              ((uintptr_t)dev_pixels & 3u)
+                          ? "film, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
+    HIP_TRY(ptss::launchResolveMetered(f.st, dev_film, splat, f.firstPixel, f.n, *params, dev_state, f.quantTable, dev_linear, dev_pixels, dev_history,
+                                       &c->meterLaunches[2]));
+    return PTSS_OK;
+}
+
+int ptss_resolve_linear_metered(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                                const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                                ptss_history_entry* dev_history, void* hipStream) {
+    return resolveMetered(c, dev_film, false, firstPixel, count, params, dev_state, dev_linear, dev_pixels, dev_history, hipStream);
+}
+
+int ptss_resolve_splat_metered(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                               const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                               ptss_history_entry* dev_history, void* hipStream) {
+    return resolveMetered(c, dev_film, true, firstPixel, count, params, dev_state, dev_linear, dev_pixels, dev_history, hipStream);
+}
+
+int ptss_meter_launches(const ptss_context* c, unsigned long long* out3) {
+    if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out3[k] = c->meterLaunches[k];
     return PTSS_OK;
 }
 

@@ -242,6 +242,18 @@ hipError_t launchSplatHomed(hipStream_t st, const void* results, const void* pos
                             unsigned long long* launches);
 hipError_t launchSplatResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
                               const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
+// the meter of the two linear films (ptss_meter.hip; ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure and the metered resolves;
+// DESIGN.md §3.31). film = 32 B per pixel, a ptss_splat_entry where `splat`; histogram = PTSS_METER_BINS x 4 B, added to; state = 48 B,
+// read and written by launchMeterExposure, read by launchResolveMetered, whose other arguments are launchLinearResolve's. params and
+// meter: checked by the caller (ptlin::paramsError, ptmeter::paramsError). No bit of ptss_launched_kernels: *launches is incremented once
+// per call that launched
+hipError_t launchMeterHistogram(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, uint32_t* histogram,
+                                unsigned long long* launches);
+hipError_t launchMeterExposure(hipStream_t st, const uint32_t* histogram, const ptss_linear_params& params, const ptss_meter_params& meter,
+                               ptss_meter_state* state, unsigned long long* launches);
+hipError_t launchResolveMetered(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                                const ptss_meter_state* state, const float* quantTable, void* linear, ptss_uchar4* pixels, void* history,
+                                unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

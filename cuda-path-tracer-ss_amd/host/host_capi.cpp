@@ -15,6 +15,7 @@
 #include "ptadaptive.h"
 #include "ptlinear.h"
 #include "ptsplat.h"
+#include "ptmeter.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -790,6 +791,49 @@ int ptss_probe_resolve_splat(const ptss_splat_entry* film, size_t firstPixel, si
         if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
         if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
     }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_meter_bin(const unsigned long long* entry4, int splat, int* bin, unsigned long long* luminance) {
+    if (!entry4 || !bin) return PTSS_HOST_EINVAL;
+    const ptlin::u64 r = entry4[0], g = entry4[1], b = entry4[2], w = splat ? entry4[3] : (entry4[3] & 0xffffffffull);
+    *bin = splat ? ptmeter::binOfSplat(r, g, b, w) : ptmeter::binOfLinear(r, g, b, (uint32_t)w);
+    if (luminance) {
+        *luminance = 0ull;
+        if (w != 0ull)
+            *luminance = splat ? ptmeter::luminance(ptmeter::splatMean(r, w), ptmeter::splatMean(g, w), ptmeter::splatMean(b, w))
+                               : ptmeter::luminance(ptmeter::linearMean(r, w), ptmeter::linearMean(g, w), ptmeter::linearMean(b, w));
+    }
+    return PTSS_HOST_OK;
+}
+
+static bool meterRangeOk(const void* film, size_t firstPixel, size_t count, const uint32_t* histogram) {
+    return film && histogram && firstPixel < (size_t(1) << 31) && count < (size_t(1) << 31) && firstPixel + count < (size_t(1) << 31);
+}
+
+int ptss_probe_meter_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, uint32_t* histogram) {
+    if (count == 0) return PTSS_HOST_OK;
+    if (!meterRangeOk(film, firstPixel, count, histogram)) return PTSS_HOST_EINVAL;
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        const int bin = ptmeter::binOfLinear(film[p].r, film[p].g, film[p].b, film[p].samples);
+        if (bin != ptmeter::kNoBin) histogram[bin] += 1u;
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_meter_splat(const ptss_splat_entry* film, size_t firstPixel, size_t count, uint32_t* histogram) {
+    if (count == 0) return PTSS_HOST_OK;
+    if (!meterRangeOk(film, firstPixel, count, histogram)) return PTSS_HOST_EINVAL;
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        const int bin = ptmeter::binOfSplat(film[p].r, film[p].g, film[p].b, film[p].weight);
+        if (bin != ptmeter::kNoBin) histogram[bin] += 1u;
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_meter_exposure(const uint32_t* histogram, const ptss_linear_params* params, const ptss_meter_params* meter, ptss_meter_state* state) {
+    if (ptlin::paramsError(params) || ptmeter::paramsError(meter) || !histogram || !state) return PTSS_HOST_EINVAL;
+    ptmeter::update(histogram, ptmeter::ruleOf(*meter, *params), state);
     return PTSS_HOST_OK;
 }
 

@@ -39,6 +39,10 @@
 //             [--filter box|tent|gaussian[,radius[,alpha]]]   with --linear: the film is a filtered one — rounds go through
 //                                   ptss_generate_rays_positions, the trace, ptss_splat_paths_homed and, at the end, ptss_resolve_splat
 //                                   (radius default 1, alpha default 2). Without it the program's bytes are those of --linear alone
+//             [--auto-exposure [key[,rate]]]   with --linear, with or without --filter: the exposure is metered on the device (DESIGN.md
+//                                   §3.31) — after each round ptss_meter_linear (ptss_meter_splat) into a zeroed histogram,
+//                                   ptss_meter_exposure (default parameters; key default 0.18, rate default 1) and the metered resolve, --linear's
+//                                   exposure compensating. Prints the final ptss_meter_state. Without it every byte written is today's
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -68,6 +72,8 @@ int main(int argc, char* argv[]) {
     float adaptiveThreshold = -1.f;   // ... and the plan's threshold when given
     float linear = -1.f;   // --linear: -1 absent, else the exposure of the resolve
     std::string splat;     // --filter: the reconstruction filter of the linear film, empty = none (a box by pixel index)
+    bool autoExposure = false;   // --auto-exposure: the linear film's exposure is metered on the device
+    float meterKey = -1.f, meterRate = -1.f;   // ... its key and rate when given
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -107,6 +113,16 @@ int main(int argc, char* argv[]) {
             if (!(linear >= 0.f && linear < 1e30f)) { fprintf(stderr, "bad --linear (exposure)\n"); return 2; }
         }
         else if (a == "--filter") splat = next();
+        else if (a == "--auto-exposure") {
+            autoExposure = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) {
+                const int got = sscanf(next(), "%f,%f", &meterKey, &meterRate);
+                if (got < 1 || !(meterKey > 0.f && meterKey < 1e30f) || (got == 2 && !(meterRate >= 0.f && meterRate <= 1.f))) {
+                    fprintf(stderr, "bad --auto-exposure (key[,rate])\n");
+                    return 2;
+                }
+            }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -158,6 +174,7 @@ int main(int argc, char* argv[]) {
     if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
     if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
     if (linear >= 0.f && (film.empty() || adaptive >= 0)) { fprintf(stderr, "--linear needs --film and no --adaptive\n"); return 2; }
+    if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -281,6 +298,11 @@ int main(int argc, char* argv[]) {
         void *dMoments = nullptr, *dCdf = nullptr, *dIndex = nullptr, *dInfo = nullptr;   // --adaptive
         void *dLinear = nullptr, *dMeans = nullptr;   // --linear (with --filter dLinear holds ptss_splat_entry, the same 32 bytes per pixel)
         void* dPos = nullptr;                         // --filter
+        void *dBins = nullptr, *dMeter = nullptr;     // --auto-exposure: one histogram per round, and the meter's state
+        ptss_meter_params meterParams;
+        PTSS_HANDLE(ptss_default_meter_params(&meterParams));
+        if (meterKey > 0.f) meterParams.key = meterKey;
+        if (meterRate >= 0.f) meterParams.rate = meterRate;
         ptss_linear_params linearParams;
         PTSS_HANDLE(ptss_default_linear_params(&linearParams));
         const bool filter = denoise != -2;
@@ -312,6 +334,25 @@ int main(int argc, char* argv[]) {
             static_assert(sizeof(ptss_splat_entry) == sizeof(ptss_linear_entry), "one film buffer serves both");
             if (!splat.empty() && hipMalloc(&dPos, n * sizeof(ptss_film_position)) != hipSuccess) { fprintf(stderr, "--filter: device buffers\n"); return 1; }
         }
+        if (autoExposure) {   // every round meters into a histogram of its own, zeroed here: nothing is cleared between the rounds' launches
+            const size_t rounds = ticks > 0 ? (size_t)ticks : 1;
+            if (hipMalloc(&dBins, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dMeter, sizeof(ptss_meter_state)) != hipSuccess ||
+                hipMemset(dBins, 0, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMemset(dMeter, 0, sizeof(ptss_meter_state)) != hipSuccess ||
+                hipDeviceSynchronize() != hipSuccess) {
+                fprintf(stderr, "--auto-exposure: device buffers\n");
+                return 1;
+            }
+        }
+        auto meteredResolve = [&]() -> int {   // the exposure is the state's, --linear's compensating
+            if (dPos) {
+                PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
+                                                       (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            } else {
+                PTSS_HANDLE(ptss_resolve_linear_metered(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
+                                                        (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+            }
+            return 0;
+        };
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
             if (dPos) {
@@ -332,6 +373,16 @@ int main(int argc, char* argv[]) {
             } else {
                 PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
                                                   (ptss_history_entry*)dHist, NULL));
+            }
+            if (autoExposure) {   // meter, update, metered resolve: the round's exposure never leaves the device
+                uint32_t* bins = (uint32_t*)dBins + (size_t)t * PTSS_METER_BINS;
+                if (dPos) {
+                    PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, bins, NULL));
+                } else {
+                    PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, bins, NULL));
+                }
+                PTSS_HANDLE(ptss_meter_exposure(ctx, bins, &linearParams, &meterParams, (ptss_meter_state*)dMeter, NULL));
+                if (meteredResolve()) return 1;
             }
         }
         if (adaptive >= 0) {   // the planned rounds: ray slot i keeps stream i whatever pixel the plan gives it
@@ -357,7 +408,14 @@ int main(int argc, char* argv[]) {
                    info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
         if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
-            if (dPos) {
+            if (autoExposure) {   // (the last round's metered resolve stands; without a round the new state's exposure, 0, shows black)
+                if (ticks <= 0 && meteredResolve()) return 1;
+                PTSS_HANDLE(ptss_synchronize(ctx));
+                ptss_meter_state state;
+                if (hipMemcpy(&state, dMeter, sizeof(state), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--auto-exposure: read-back\n"); return 1; }
+                printf("auto-exposure: exposure %.9g target %.9g meanLog2 %.9g updates %u metered %llu black %llu counted %llu sumLog %llu\n", state.exposure,
+                       state.target, state.meanLog2, state.updates, state.metered, state.black, state.counted, state.sumLog);
+            } else if (dPos) {
                 PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
                                                (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             } else {
@@ -391,7 +449,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

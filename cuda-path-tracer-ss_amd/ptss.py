@@ -17,6 +17,7 @@ from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS,
                         SCENE_LAYOUT_MESH_FIELDS, AreaLight, Camera, DenoiseParams, FilmCamera, FilmEntry, HistoryEntry, Material, PixelFeature, PixelMotion, PointLight, RayHit, RayQuery, ReprojectParams, SceneDesc, Sphere, Triangle,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 from ptss_types import POSITION_DTYPE, SPLAT_BOX, SPLAT_DTYPE, SPLAT_GAUSSIAN, SPLAT_TENT, FilmPosition, SplatEntry, SplatFilter
+from ptss_types import METER_BINS, METER_BLOCK, METER_GRID_CAP, METER_STATE_DTYPE, MeterParams, MeterState
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -197,6 +198,10 @@ def host_lib():
         L.ptss_probe_splat_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.c_int, C.c_int,
                                              C.POINTER(SplatFilter), C.POINTER(LinearParams), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         L.ptss_probe_resolve_splat.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptss_probe_meter_bin.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_meter_linear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.ptss_probe_meter_splat.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        L.ptss_probe_meter_exposure.argtypes = [C.c_void_p, C.POINTER(LinearParams), C.POINTER(MeterParams), C.c_void_p]
         _host = L
     return _host
 
@@ -301,6 +306,13 @@ def device_lib():
                                              C.POINTER(LinearParams), vp]
         L.ptss_resolve_splat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp]
         L.ptss_splat_stats.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_meter_params.argtypes = [C.POINTER(MeterParams)]
+        L.ptss_meter_linear.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp]
+        L.ptss_meter_splat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, vp]
+        L.ptss_meter_exposure.argtypes = [vp, vp, C.POINTER(LinearParams), C.POINTER(MeterParams), vp, vp]
+        L.ptss_resolve_linear_metered.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp, vp]
+        L.ptss_resolve_splat_metered.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp, vp]
+        L.ptss_meter_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -812,6 +824,81 @@ def probe_resolve_splat(film, first_pixel=0, count=None, params=None, linear=Tru
     """ptss_resolve_splat on the host, with the literal tone map: probe_resolve_linear's arguments and results over a (P,) SPLAT_DTYPE
     film; the weight of linear and history is the summed filter weight (1 per whole sample)."""
     return _probe_resolve("ptss_probe_resolve_splat", SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+
+
+# ---- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure; DESIGN.md §3.31) ----
+def meter_params(key=0.18, low_permille=100, high_permille=20, rate=1.0, min_exposure=2.0 ** -16, max_exposure=2.0 ** 16):
+    """A ptss_meter_params; the defaults are ptss_default_meter_params' (design choices, not measurements)."""
+    p = MeterParams()
+    p.structSize = C.sizeof(MeterParams)
+    p.key, p.lowPermille, p.highPermille, p.rate = float(key), int(low_permille), int(high_permille), float(rate)
+    p.minExposure, p.maxExposure, p.reserved = float(min_exposure), float(max_exposure), 0
+    return p
+
+
+def _histogram(histogram):
+    """A meter's histogram as (METER_BINS,) uint32, a copy: None = zeros."""
+    h = np.zeros(METER_BINS, dtype=np.uint32) if histogram is None else np.array(histogram, dtype=np.uint32, order="C").reshape(-1)
+    if len(h) != METER_BINS:
+        raise ValueError("histogram: METER_BINS uint32 counts")
+    return h
+
+
+def _meter_state(state):
+    """A meter's state as (1,) METER_STATE_DTYPE, a copy: None = a new state."""
+    if state is None:
+        return np.zeros(1, dtype=METER_STATE_DTYPE)
+    if isinstance(state, MeterState):
+        return np.frombuffer(bytes(state), dtype=METER_STATE_DTYPE).copy()
+    s = np.array(state, dtype=METER_STATE_DTYPE, order="C").reshape(-1)
+    if len(s) != 1:
+        raise ValueError("state: one METER_STATE_DTYPE record")
+    return s
+
+
+def probe_meter_bin(entry, splat=False):
+    """The bin csrc/ptmeter.h gives one film entry -> (bin, or -1 for a pixel that is not metered; its fixed-point luminance Y). entry: a
+    LINEAR_DTYPE record (splat: SPLAT_DTYPE) or its four uint64 words."""
+    e = np.ascontiguousarray(entry).view(np.uint64).reshape(-1) if np.asarray(entry).dtype.fields else np.array(entry, dtype=np.uint64).reshape(-1)
+    if len(e) != 4:
+        raise ValueError("entry: one film entry, four 64-bit words")
+    b, y = C.c_int(0), C.c_ulonglong(0)
+    if host_lib().ptss_probe_meter_bin(e.ctypes.data_as(C.c_void_p), 1 if splat else 0, C.byref(b), C.byref(y)) != 0:
+        raise PtssError("ptss_probe_meter_bin")
+    return int(b.value), int(y.value)
+
+
+def _probe_meter(name, film_dtype, film, first_pixel, count, histogram):
+    f = _rows(film, film_dtype, 4, np.uint64, "film")
+    first_pixel, count = _linear_range(len(f), first_pixel, count)
+    h = _histogram(histogram)
+    rc = getattr(host_lib(), name)(f.ctypes.data_as(C.c_void_p), first_pixel, count, h.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"{name}: {rc}")
+    return h
+
+
+def probe_meter_linear(film, first_pixel=0, count=None, histogram=None):
+    """ptss_meter_linear on the host (csrc/ptmeter.h; the specification of the device's histogram) -> the histogram afterwards,
+    (METER_BINS,) uint32. film: (P,) LINEAR_DTYPE or (P, 4) uint64; histogram: the counts beforehand (not modified; None = zeros)."""
+    return _probe_meter("ptss_probe_meter_linear", LINEAR_DTYPE, film, first_pixel, count, histogram)
+
+
+def probe_meter_splat(film, first_pixel=0, count=None, histogram=None):
+    """ptss_meter_splat on the host: probe_meter_linear over a (P,) SPLAT_DTYPE film."""
+    return _probe_meter("ptss_probe_meter_splat", SPLAT_DTYPE, film, first_pixel, count, histogram)
+
+
+def probe_meter_exposure(histogram, state=None, params=None, meter=None):
+    """ptss_meter_exposure on the host -> the state afterwards, (1,) METER_STATE_DTYPE. state: the state beforehand (not modified; None = a
+    new one); params: the film's linear_params; meter: a meter_params."""
+    h, s = _histogram(histogram), _meter_state(state)
+    params = params if params is not None else linear_params()
+    meter = meter if meter is not None else meter_params()
+    rc = host_lib().ptss_probe_meter_exposure(h.ctypes.data_as(C.c_void_p), C.byref(params), C.byref(meter), s.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_meter_exposure: {rc}")
+    return s
 
 
 def default_denoise_params(**overrides):
@@ -1712,23 +1799,32 @@ class Renderer:
                                LINEAR_DTYPE, np.uint64, results, film, first_pixel, index)
         return None if out is None else out[0]
 
-    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
         numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64; linear / pixels / history: None (NULL), True (zeros beforehand) or the buffer's
         content beforehand -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample count, pixels (P, 4) uint8, history (P,)
         HISTORY_DTYPE), each None when NULL. torch: film (P, 4) int64, linear (P, 4) float32 or None, pixels (P, 4) uint8 or None,
-        history (P, 4) float32 or None, all on one device, WRITTEN IN PLACE -> None, on the current stream."""
-        return self._resolve(device_lib().ptss_resolve_linear, LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+        history (P, 4) float32 or None, all on one device, WRITTEN IN PLACE -> None, on the current stream.
+        metered: a meter's state (numpy: a METER_STATE_DTYPE record; torch: a (6,) int64 device tensor) -> ptss_resolve_linear_metered:
+        the exposure is the state's times params.exposure. Without it ptss_resolve_linear is called."""
+        L = device_lib()
+        return self._resolve(L.ptss_resolve_linear, L.ptss_resolve_linear_metered, LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels,
+                             history, metered)
 
-    def _resolve(self, call, film_dtype, film, first_pixel, count, params, linear, pixels, history):
-        """The body of resolve_linear and resolve_splat: `call` over a film of 32-byte entries."""
+    def _resolve(self, plain, with_state, film_dtype, film, first_pixel, count, params, linear, pixels, history, metered):
+        """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, or `with_state` where `metered` is a state."""
         params = params if params is not None else linear_params()
+        if metered is None:
+            call = plain
+        else:
+            call = lambda ctx, f, first, n, par, ln, px, hs, st: with_state(ctx, f, first, n, par, d_state, ln, px, hs, st)
         if type(film).__module__.split(".")[0] == "torch":
             import sys
             torch = sys.modules["torch"]
             dev, P = film.device, film.shape[0]
             first_pixel, count = _linear_range(P, first_pixel, count)
             d_film = self._torch_ptr(film, "film", "int64", 4)
+            d_state = self._torch_ptr(metered, "metered", "int64", 0, dev, 6) if metered is not None else None
             d_ln = self._torch_ptr(linear, "linear", "float32", 4, dev, P) if linear is not None else None
             d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
             d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
@@ -1739,12 +1835,16 @@ class Renderer:
         P = len(f)
         first_pixel, count = _linear_range(P, first_pixel, count)
         ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
+        state = _meter_state(metered) if metered is not None else None
+        d_state = None
         if count == 0:
             _check(call(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
         else:
-            self._round_trip([f, ln, px, hs],
-                             lambda d: _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None)),
-                             read=(1, 2, 3))
+            def run(d):
+                nonlocal d_state
+                d_state = d[4]
+                _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None))
+            self._round_trip([f, ln, px, hs, state], run, read=(1, 2, 3))
         return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
     # --- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat) ------------------
@@ -1786,10 +1886,71 @@ class Renderer:
             self._round_trip([r, pos, f], lambda d: call(d[0], d[1], n, d[2], None), read=(2,))
         return f.view(SPLAT_DTYPE).reshape(-1)
 
-    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True):
+    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None):
         """ptss_resolve_splat: resolve_linear's arguments and results over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64); the
-        weight of linear and history is the summed filter weight."""
-        return self._resolve(device_lib().ptss_resolve_splat, SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels, history)
+        weight of linear and history is the summed filter weight. metered: as in resolve_linear (ptss_resolve_splat_metered)."""
+        L = device_lib()
+        return self._resolve(L.ptss_resolve_splat, L.ptss_resolve_splat_metered, SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels,
+                             history, metered)
+
+    # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
+    def _meter(self, call, film_dtype, film, first_pixel, count, histogram):
+        """The body of meter_linear and meter_splat."""
+        if type(film).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, P = film.device, film.shape[0]
+            first_pixel, count = _linear_range(P, first_pixel, count)
+            d_film = self._torch_ptr(film, "film", "int64", 4)
+            d_hist = self._torch_ptr(histogram, "histogram", "int32", 0, dev, METER_BINS)
+            _check(call(self._ctx, d_film, first_pixel, count, d_hist, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        f = _rows(film, film_dtype, 4, np.uint64, "film")
+        first_pixel, count = _linear_range(len(f), first_pixel, count)
+        h = _histogram(histogram)
+        if count == 0:
+            _check(call(self._ctx, None, first_pixel, 0, None, None))
+        else:
+            self._round_trip([f, h], lambda d: _check(call(self._ctx, d[0], first_pixel, count, d[1], None)), read=(1,))
+        return h
+
+    def meter_linear(self, film, first_pixel=0, count=None, histogram=None):
+        """ptss_meter_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film counted into a
+        luminance histogram. numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64; histogram: the counts beforehand (not modified; None =
+        zeros) -> the histogram afterwards, (METER_BINS,) uint32. torch: film (P, 4) int64, histogram a (METER_BINS,) int32 device tensor
+        UPDATED IN PLACE -> None, on the current stream."""
+        return self._meter(device_lib().ptss_meter_linear, LINEAR_DTYPE, film, first_pixel, count, histogram)
+
+    def meter_splat(self, film, first_pixel=0, count=None, histogram=None):
+        """ptss_meter_splat: meter_linear over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64)."""
+        return self._meter(device_lib().ptss_meter_splat, SPLAT_DTYPE, film, first_pixel, count, histogram)
+
+    def meter_exposure(self, histogram, state=None, params=None, meter=None):
+        """ptss_meter_exposure: one update of a meter's state from a histogram. numpy: histogram (METER_BINS,) uint32; state: the state
+        beforehand (not modified; None = a new one) -> the state afterwards, (1,) METER_STATE_DTYPE. torch: histogram a (METER_BINS,)
+        int32 device tensor, state a (6,) int64 device tensor (zeros = new) UPDATED IN PLACE -> None, on the current stream.
+        params: the film's linear_params; meter: a meter_params."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        meter = meter if meter is not None else meter_params()
+        if type(histogram).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev = histogram.device
+            d_hist = self._torch_ptr(histogram, "histogram", "int32", 0, None, METER_BINS)
+            d_state = self._torch_ptr(state, "state", "int64", 0, dev, 6)
+            _check(L.ptss_meter_exposure(self._ctx, d_hist, C.byref(params), C.byref(meter), d_state, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        h, s = _histogram(histogram), _meter_state(state)
+        self._round_trip([h, s], lambda d: _check(L.ptss_meter_exposure(self._ctx, d[0], C.byref(params), C.byref(meter), d[1], None)), read=(1,))
+        return s
+
+    def meter_launches(self):
+        """ptss_meter_launches: (meter_linear / meter_splat, meter_exposure, metered resolve calls that launched since the context was
+        created)."""
+        out = (C.c_ulonglong * 3)()
+        _check(device_lib().ptss_meter_launches(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def splat_stats(self):
         """ptss_splat_stats: (scatter launches, homed launches, resolves, samples dropped, samples clamped) since the context was

@@ -157,6 +157,23 @@ class SplatEntry(C.Structure):   # ptss_splat_entry: the weighted fixed-point su
 
 
 SPLAT_DTYPE = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("weight", np.uint64)])
+METER_BINS = 329   # PTSS_METER_BINS: the 32-bit counts of a meter's histogram
+# the launch shape of the histogram kernels (csrc/ptmeter.h kBlock, kGridCap): a film of more than their product makes the grid stride
+METER_BLOCK, METER_GRID_CAP = 1024, 256
+
+
+class MeterParams(C.Structure):   # ptss_meter_params: how a histogram becomes an exposure
+    _fields_ = [("structSize", C.c_uint), ("key", C.c_float), ("lowPermille", C.c_uint), ("highPermille", C.c_uint), ("rate", C.c_float),
+                ("minExposure", C.c_float), ("maxExposure", C.c_float), ("reserved", C.c_uint)]
+
+
+class MeterState(C.Structure):   # ptss_meter_state: a meter's exposure and the integers of its latest update
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("meanLog2", C.c_float), ("updates", C.c_uint32), ("metered", C.c_ulonglong),
+                ("black", C.c_ulonglong), ("counted", C.c_ulonglong), ("sumLog", C.c_ulonglong)]
+
+
+METER_STATE_DTYPE = np.dtype([("exposure", np.float32), ("target", np.float32), ("meanLog2", np.float32), ("updates", np.uint32),
+                              ("metered", np.uint64), ("black", np.uint64), ("counted", np.uint64), ("sumLog", np.uint64)])
 
 
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
@@ -208,6 +225,8 @@ assert C.sizeof(LinearEntry) == 32 == LINEAR_DTYPE.itemsize and LinearEntry.samp
 assert LinearEntry.clamped.offset == 28 == LINEAR_DTYPE.fields["clamped"][1] and C.sizeof(LinearParams) == 20 and LinearParams.reserved.offset == 16
 assert C.sizeof(FilmPosition) == 8 == POSITION_DTYPE.itemsize and C.sizeof(SplatFilter) == 20 and SplatFilter.reserved.offset == 16
 assert C.sizeof(SplatEntry) == 32 == SPLAT_DTYPE.itemsize and SplatEntry.weight.offset == 24 == SPLAT_DTYPE.fields["weight"][1]
+assert C.sizeof(MeterParams) == 32 and MeterParams.reserved.offset == 28 and C.sizeof(MeterState) == 48 == METER_STATE_DTYPE.itemsize
+assert MeterState.metered.offset == 16 == METER_STATE_DTYPE.fields["metered"][1] and MeterState.sumLog.offset == 40 == METER_STATE_DTYPE.fields["sumLog"][1]
 
 
 def struct_to_dict(s):

@@ -488,6 +488,56 @@ int ptss_resolve_splat(ptss_context* ctx, const ptss_splat_entry* dev_film, size
                        ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
 int ptss_splat_stats(ptss_context* ctx, unsigned long long* out5);
 
+/* Metering a linear or a filtered linear film on the device: a luminance histogram of the film's pixel means, the
+ * exposure it asks for, with temporal adaptation, kept in device memory, and the two resolves taking their exposure from there — the
+ * loop generate, trace, accumulate, meter, resolve never returns to the host. csrc/ptmeter.h has the arithmetic; its host build
+ * (ptss_probe_meter_bin, ptss_probe_meter_linear, ptss_probe_meter_splat, ptss_probe_meter_exposure) is the specification and the device
+ * agrees with it byte for byte.
+ *
+ * ptss_meter_linear / ptss_meter_splat: for pixels firstPixel .. firstPixel + count of dev_film (the caller guarantees they exist), a
+ * pixel with samples = 0 (weight = 0) is not metered; otherwise per channel m = the integer mean of the resolve — (sum + N / 2) / N, or
+ * the filtered film's floor((S * 2^16 + Wt / 2) / Wt) — Y = (54 m_r + 183 m_g + 19 m_b + 128) >> 8, and dev_histogram[bin] gains 1:
+ * bin 0 for Y = 0, else 1 + 8 e + sub with e = floor(log2 Y) and sub the three bits below Y's leading one (Y shifted up where e < 3).
+ * A film the library filled has Y <= 2^40, bin <= 321; anything from 2^41 on counts in bin 328. dev_histogram: PTSS_METER_BINS
+ * 32-bit counts the caller has zero-filled; the counts carry across calls (tiles, shards and rounds may meter into one histogram) and
+ * wrap like any unsigned integer. Integer counts: the same bytes for every split into calls and every launch shape.
+ *
+ * ptss_meter_exposure: one update of *dev_state from dev_histogram (read, not cleared). With T = the counts of bins 1 .., lo = T *
+ * lowPermille / 1000 and hi = T - T * highPermille / 1000, the ranks [lo, hi) of the non-black pixels in order of their bins are
+ * averaged: sumLog = the sum over those ranks of the bin centre 2 (bin - 1) + 1 (in 1/16 stop), C = hi - lo, meanLog2 = sumLog / (C * 16)
+ * - scaleLog2, target = clamp(key * exp(-meanLog2 * ln 2), minExposure, maxExposure); a new state (updates = 0) takes exposure = target,
+ * any other exposure = clamp(fma(target - exposure, rate, exposure), minExposure, maxExposure). T = 0: target = exposure = the
+ * previous exposure, 1 for a new state. updates grows by one, saturating. params: the film's ptss_linear_params (scaleLog2 is read).
+ *
+ * ptss_resolve_linear_metered / ptss_resolve_splat_metered: ptss_resolve_linear / ptss_resolve_splat with the exposure
+ * dev_state->exposure * params->exposure (one float32 multiply; params->exposure compensates, default 1). No address depends on the
+ * state: a state the caller filled with garbage gives garbage pixels, never a fault.
+ *
+ * All of them are asynchronous on hipStream (NULL: the context's), leave no trace in frame state, own no bit of ptss_launched_kernels
+ * and serve sharded contexts like the film calls. Refused without touching the device and without counting (PTSS_EINVAL): a null ctx,
+ * params or meter params, a wrong structSize, whatever ptss_resolve_linear refuses about params, a key that is not finite and positive,
+ * permilles above 999 together, a rate outside [0, 1], exposure bounds that are negative, not finite or min > max, a non-zero reserved, a
+ * null film, histogram or state, a pointer that is not aligned — 16 bytes for film, linear and history, 8 for the state, 4 for the
+ * histogram and pixels; (PTSS_ERANGE): firstPixel + count >= 2^31. count = 0 returns PTSS_OK with nothing launched.
+ * ptss_meter_launches: the calls of each kind that launched since ptss_create. ptss_default_meter_params: key 0.18, lowPermille 100,
+ * highPermille 20, rate 1, minExposure 2^-16, maxExposure 2^16 — design choices, not measurements. */
+int ptss_default_meter_params(ptss_meter_params* params);
+int ptss_meter_linear(ptss_context* ctx, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, uint32_t* dev_histogram,
+                      void* hipStream);
+int ptss_meter_splat(ptss_context* ctx, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, uint32_t* dev_histogram,
+                     void* hipStream);
+int ptss_meter_exposure(ptss_context* ctx, const uint32_t* dev_histogram, const ptss_linear_params* params, const ptss_meter_params* meter,
+                        ptss_meter_state* dev_state /* in/out */, void* hipStream);
+int ptss_resolve_linear_metered(ptss_context* ctx, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count,
+                                const ptss_linear_params* params, const ptss_meter_state* dev_state,
+                                ptss_history_entry* dev_linear /* may be NULL */, ptss_uchar4* dev_pixels /* may be NULL */,
+                                ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_resolve_splat_metered(ptss_context* ctx, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count,
+                               const ptss_linear_params* params, const ptss_meter_state* dev_state,
+                               ptss_history_entry* dev_linear /* may be NULL */, ptss_uchar4* dev_pixels /* may be NULL */,
+                               ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
+int ptss_meter_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] histograms, [1] exposure updates, [2] metered resolves */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

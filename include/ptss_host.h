@@ -229,6 +229,18 @@ int ptss_probe_splat_paths(const ptss_path_result* results, const ptss_film_posi
 int ptss_probe_resolve_splat(const ptss_splat_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,
                              ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
 
+/* The meter on the host (csrc/ptmeter.h — the very operations the kernels evaluate; this build is the specification).
+ * ptss_probe_meter_bin: the bin of one film entry given as its four 64-bit words (splat = 0: a ptss_linear_entry, the low half of word 3
+ * its samples; else a ptss_splat_entry); *bin = -1 for a pixel that is not metered; *luminance (may be NULL): Y, 0 where not metered. */
+int ptss_probe_meter_bin(const unsigned long long* entry4, int splat, int* bin, unsigned long long* luminance);
+/* ptss_meter_linear / ptss_meter_splat on the host: a straight loop over pixels firstPixel .. firstPixel + count, added to histogram.
+ * PTSS_HOST_EINVAL: whatever the calls refuse, alignment aside. */
+int ptss_probe_meter_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, uint32_t* histogram);
+int ptss_probe_meter_splat(const ptss_splat_entry* film, size_t firstPixel, size_t count, uint32_t* histogram);
+/* ptss_meter_exposure on the host: one update of *state. PTSS_HOST_EINVAL: whatever ptss_meter_exposure refuses, alignment aside. */
+int ptss_probe_meter_exposure(const uint32_t* histogram, const ptss_linear_params* params, const ptss_meter_params* meter,
+                              ptss_meter_state* state /* in/out */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,36 @@ typedef struct ptss_splat_entry {
     unsigned long long weight;
 } ptss_splat_entry;
 
+/* Metering a linear or a filtered linear film (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure). A histogram
+ * is PTSS_METER_BINS 32-bit counts, zero-filled by the caller: bin 0 counts black pixels, bin 1 + 8 e + sub the pixels whose fixed-point
+ * luminance Y has floor(log2 Y) = e (0 .. 40) and whose next three bits are sub: an eighth of a stop per bin. */
+#define PTSS_METER_BINS 329
+
+/* How a histogram becomes an exposure (ptss.h). key > 0, finite: the exposed mean luminance aimed at; lowPermille, highPermille, at most
+ * 999 together: the darkest and brightest thousandths of the non-black pixels left out of the mean; rate in [0, 1]: the share of the way
+ * towards the target one update goes (1: all of it); 0 <= minExposure <= maxExposure, finite: what target and exposure are clamped to. */
+typedef struct ptss_meter_params {
+    unsigned int structSize; /* sizeof(ptss_meter_params) as the caller compiled it */
+    float key;
+    unsigned int lowPermille;
+    unsigned int highPermille;
+    float rate;
+    float minExposure;
+    float maxExposure;
+    unsigned int reserved;   /* 0 */
+} ptss_meter_params;
+
+/* The state of a meter, in device memory (ptss_meter_exposure reads and writes it, the metered resolves read exposure). 48 B, 8-byte
+ * aligned access; all zero = new. exposure: what the metered resolves multiply by; target: the exposure the latest histogram asked for;
+ * meanLog2: the mean log2 luminance it found; updates: the updates so far, saturating. The integers of the latest update: metered = the
+ * non-black pixels counted (T), black = bin 0, counted = the ranks the percentile cuts left (C), sumLog = their bin centres summed, in
+ * 1/16 stop. */
+typedef struct ptss_meter_state {
+    float exposure, target, meanLog2;
+    uint32_t updates;
+    unsigned long long metered, black, counted, sumLog;
+} ptss_meter_state;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -360,6 +390,12 @@ static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, kin
               "ptss_splat_filter is five 32-bit words");
 static_assert(sizeof(ptss_splat_entry) == 32 && offsetof(ptss_splat_entry, g) == 8 && offsetof(ptss_splat_entry, weight) == 24,
               "ptss_splat_entry is two 16-byte rows");
+static_assert(sizeof(ptss_meter_params) == 32 && offsetof(ptss_meter_params, key) == 4 && offsetof(ptss_meter_params, rate) == 16 &&
+                  offsetof(ptss_meter_params, maxExposure) == 24 && offsetof(ptss_meter_params, reserved) == 28,
+              "ptss_meter_params is eight 32-bit words");
+static_assert(sizeof(ptss_meter_state) == 48 && offsetof(ptss_meter_state, updates) == 12 && offsetof(ptss_meter_state, metered) == 16 &&
+                  offsetof(ptss_meter_state, sumLog) == 40,
+              "ptss_meter_state is four 32-bit and four 64-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -398,6 +434,12 @@ _Static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, ki
                "ptss_splat_filter is five 32-bit words");
 _Static_assert(sizeof(ptss_splat_entry) == 32 && offsetof(ptss_splat_entry, g) == 8 && offsetof(ptss_splat_entry, weight) == 24,
                "ptss_splat_entry is two 16-byte rows");
+_Static_assert(sizeof(ptss_meter_params) == 32 && offsetof(ptss_meter_params, key) == 4 && offsetof(ptss_meter_params, rate) == 16 &&
+                   offsetof(ptss_meter_params, maxExposure) == 24 && offsetof(ptss_meter_params, reserved) == 28,
+               "ptss_meter_params is eight 32-bit words");
+_Static_assert(sizeof(ptss_meter_state) == 48 && offsetof(ptss_meter_state, updates) == 12 && offsetof(ptss_meter_state, metered) == 16 &&
+                   offsetof(ptss_meter_state, sumLog) == 40,
+               "ptss_meter_state is four 32-bit and four 64-bit words");
 #endif
 
 #ifdef __cplusplus
