@@ -27,6 +27,7 @@
 #include "ptlinear.h"
 #include "ptsplat.h"
 #include "ptmeter.h"
+#include "ptglare.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -160,6 +161,7 @@ struct ptss_context {
     unsigned long long linearLaunches[2] = {0, 0};            // ptss_accumulate_paths_linear, ptss_resolve_linear calls that launched
     unsigned long long splatLaunches[3] = {0, 0, 0};          // ptss_splat_paths, ptss_splat_paths_homed, ptss_resolve_splat calls that launched
     unsigned long long meterLaunches[3] = {0, 0, 0};          // meter histograms, ptss_meter_exposure, metered resolves that launched
+    unsigned long long glareLaunches[3] = {0, 0, 0};          // glare builds, the kernels they launched, glare resolves that launched
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
@@ -1714,6 +1716,89 @@ int ptss_resolve_splat_metered(ptss_context* c, const ptss_splat_entry* dev_film
 int ptss_meter_launches(const ptss_context* c, unsigned long long* out3) {
     if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
     for (int k = 0; k < 3; ++k) out3[k] = c->meterLaunches[k];
+    return PTSS_OK;
+}
+
+// ---- glare for the two linear films (ptss_glare.hip; csrc/ptglare.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_glare_params(ptss_glare_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_glare_params);
+    p->levels = 6;
+    p->mode = PTSS_GLARE_MIX;
+    p->threshold = 0.f;
+    p->strength = 0.1f;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+int ptss_glare_layout(int width, int height, int levels, ptss_glare_level out[8], size_t* entries) {
+    if (!out || !entries) return fail(PTSS_EINVAL, "null argument");
+    if (levels < 1 || levels > ptglare::kMaxLevels) return fail(PTSS_EINVAL, "levels must be in [1, 8]");
+    if (const char* what = ptglare::sidesError(width, height)) return fail(PTSS_ERANGE, what);
+    *entries = ptglare::layoutOf(width, height, levels, out);
+    return PTSS_OK;
+}
+
+// what the glare calls check first: ctx, the film's parameters, the glare's, the film's kind and its sides
+static int glareArguments(const ptss_context* c, const ptss_linear_params* params, const ptss_glare_params* glare, int filmKind, int width, int height) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptglare::paramsError(glare, *params)) return fail(PTSS_EINVAL, what);
+    if (filmKind != PTSS_GLARE_FILM_LINEAR && filmKind != PTSS_GLARE_FILM_SPLAT) return fail(PTSS_EINVAL, "unknown film kind");
+    if (const char* what = ptglare::sidesError(width, height)) return fail(PTSS_ERANGE, what);
+    return PTSS_OK;
+}
+
+int ptss_glare_build(ptss_context* c, const void* dev_film, int filmKind, int width, int height, const ptss_linear_params* params,
+                     const ptss_glare_params* glare, ptss_glare_entry* dev_pyramid, void* hipStream) {
+    RC_TRY(glareArguments(c, params, glare, filmKind, width, height));
+    if (!dev_film || !dev_pyramid) return fail(PTSS_EINVAL, "null film or pyramid");
+    if (((uintptr_t)dev_film | (uintptr_t)dev_pyramid) & 15u) return fail(PTSS_EINVAL, "film and pyramid must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchGlareBuild(streamOf(c, hipStream), dev_film, filmKind == PTSS_GLARE_FILM_SPLAT, width, height, *params, *glare, dev_pyramid,
+                                   c->glareLaunches));
+    return PTSS_OK;
+}
+
+static int resolveGlare(ptss_context* c, const void* dev_film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params, int width,
+                        int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid, const ptss_meter_state* dev_state,
+                        ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    RC_TRY(glareArguments(c, params, glare, filmKind, width, height));
+    const char* bad = !dev_film || !dev_pyramid ? "null film or pyramid with count > 0"
+                      : (((uintptr_t)dev_film | (uintptr_t)dev_pyramid | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) ||
+                              ((uintptr_t)dev_state & 7u) || ((uintptr_t)dev_pixels & 3u)
+                          ? "film, pyramid, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned"
+                          : nullptr;
+    const unsigned long long filmPixels = (unsigned long long)width * (unsigned long long)height;   // below 2^31
+    if (count != 0 && !bad && (firstPixel > filmPixels || count > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + count leaves the film");
+    FilmCall f;
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
+    HIP_TRY(ptss::launchResolveGlare(f.st, dev_film, filmKind == PTSS_GLARE_FILM_SPLAT, f.firstPixel, f.n, *params, width, height, *glare, dev_pyramid,
+                                     dev_state, f.quantTable, dev_linear, dev_pixels, dev_history, &c->glareLaunches[2]));
+    return PTSS_OK;
+}
+
+int ptss_resolve_linear_glare(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                              int width, int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid,
+                              const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                              ptss_history_entry* dev_history, void* hipStream) {
+    return resolveGlare(c, dev_film, PTSS_GLARE_FILM_LINEAR, firstPixel, count, params, width, height, glare, dev_pyramid, dev_state, dev_linear,
+                        dev_pixels, dev_history, hipStream);
+}
+
+int ptss_resolve_splat_glare(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             int width, int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid,
+                             const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                             ptss_history_entry* dev_history, void* hipStream) {
+    return resolveGlare(c, dev_film, PTSS_GLARE_FILM_SPLAT, firstPixel, count, params, width, height, glare, dev_pyramid, dev_state, dev_linear,
+                        dev_pixels, dev_history, hipStream);
+}
+
+int ptss_glare_launches(const ptss_context* c, unsigned long long* out3) {
+    if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out3[k] = c->glareLaunches[k];
     return PTSS_OK;
 }
 

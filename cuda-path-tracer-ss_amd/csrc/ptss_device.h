@@ -254,6 +254,16 @@ hipError_t launchMeterExposure(hipStream_t st, const uint32_t* histogram, const 
 hipError_t launchResolveMetered(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
                                 const ptss_meter_state* state, const float* quantTable, void* linear, ptss_uchar4* pixels, void* history,
                                 unsigned long long* launches);
+// glare for the two linear films (ptss_glare.hip; ptss_glare_build and the glare resolves). film = width x height x 32 B, a
+// ptss_splat_entry where `splat`; pyramid = the entries ptglare::layoutOf counts, 32 B each. launchGlareBuild: launches[0] is incremented
+// once when every kernel of the build launched, launches[1] by each kernel that did. launchResolveGlare: launchLinearResolve's arguments,
+// state = 48 B or nullptr, pyramid read at level 1 only; *launches is incremented. params and glare: checked by the caller
+// (ptlin::paramsError, ptglare::paramsError, ptglare::sidesError). No bit of ptss_launched_kernels
+hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int width, int height, const ptss_linear_params& params,
+                            const ptss_glare_params& glare, void* pyramid, unsigned long long* launches);
+hipError_t launchResolveGlare(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                              int width, int height, const ptss_glare_params& glare, const void* pyramid, const ptss_meter_state* state,
+                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

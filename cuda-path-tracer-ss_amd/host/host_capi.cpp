@@ -16,6 +16,7 @@
 #include "ptlinear.h"
 #include "ptsplat.h"
 #include "ptmeter.h"
+#include "ptglare.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -834,6 +835,102 @@ int ptss_probe_meter_splat(const ptss_splat_entry* film, size_t firstPixel, size
 int ptss_probe_meter_exposure(const uint32_t* histogram, const ptss_linear_params* params, const ptss_meter_params* meter, ptss_meter_state* state) {
     if (ptlin::paramsError(params) || ptmeter::paramsError(meter) || !histogram || !state) return PTSS_HOST_EINVAL;
     ptmeter::update(histogram, ptmeter::ruleOf(*meter, *params), state);
+    return PTSS_HOST_OK;
+}
+
+int ptss_glare_layout(int width, int height, int levels, ptss_glare_level out[8], size_t* entries) {
+    if (!out || !entries || levels < 1 || levels > ptglare::kMaxLevels || ptglare::sidesError(width, height)) return PTSS_HOST_EINVAL;
+    *entries = ptglare::layoutOf(width, height, levels, out);
+    return PTSS_HOST_OK;
+}
+
+// word 3 of a film entry as the glare operations take it: the samples of a linear entry, the weight of a filtered one
+static ptlin::u64 glareWeightOf(const unsigned long long* entry4, bool splat) { return splat ? entry4[3] : (entry4[3] & 0xffffffffull); }
+
+static bool glareArgumentsOk(const void* film, int filmKind, int width, int height, const ptss_linear_params* params, const ptss_glare_params* glare,
+                             const void* pyramid) {
+    if (ptlin::paramsError(params) || ptglare::paramsError(glare, *params) || ptglare::sidesError(width, height)) return false;
+    return film && pyramid && (filmKind == PTSS_GLARE_FILM_LINEAR || filmKind == PTSS_GLARE_FILM_SPLAT);
+}
+
+int ptss_probe_glare_build(const void* film, int filmKind, int width, int height, const ptss_linear_params* params, const ptss_glare_params* glare,
+                           ptss_glare_entry* pyramid) {
+    if (!glareArgumentsOk(film, filmKind, width, height, params, glare, pyramid)) return PTSS_HOST_EINVAL;
+    const bool splat = filmKind == PTSS_GLARE_FILM_SPLAT;
+    const unsigned long long* words = static_cast<const unsigned long long*>(film);
+    const ptglare::Rule R = ptglare::ruleOf(*glare, *params);
+    const int L = glare->levels;
+    ptss_glare_level lv[ptglare::kMaxLevels];
+    ptglare::layoutOf(width, height, L, lv);
+    // the downs: level 1 from the film's thresholded means, level k from level k - 1
+    for (int k = 1; k <= L; ++k) {
+        ptss_glare_entry* dst = pyramid + lv[k - 1].first;
+        const int w = lv[k - 1].width, h = lv[k - 1].height;
+        const int sw = k == 1 ? width : lv[k - 2].width, sh = k == 1 ? height : lv[k - 2].height;
+        const ptss_glare_entry* src = k == 1 ? nullptr : pyramid + lv[k - 2].first;
+        for (int j = 0; j < h; ++j)
+            for (int i = 0; i < w; ++i) {
+                ptlin::u64 d[3];
+                if (k == 1)
+                    ptglare::downTexel(i, j, sw, sh, [&](int x, int y, ptlin::u64* v) {
+                        const unsigned long long* e = words + 4 * ((size_t)y * (size_t)sw + (size_t)x);
+                        ptglare::sourceOf(e[0], e[1], e[2], glareWeightOf(e, splat), splat, R.threshold, v);
+                    }, d);
+                else
+                    ptglare::downTexel(i, j, sw, sh, [&](int x, int y, ptlin::u64* v) {
+                        const ptss_glare_entry& e = src[(size_t)y * (size_t)sw + (size_t)x];
+                        v[0] = e.r, v[1] = e.g, v[2] = e.b;
+                    }, d);
+                dst[(size_t)j * (size_t)w + (size_t)i] = ptss_glare_entry{d[0], d[1], d[2], 0ull};
+            }
+    }
+    // the ups, in place from the coarsest level
+    for (int k = L - 1; k >= 1; --k) {
+        ptss_glare_entry* dst = pyramid + lv[k - 1].first;
+        const ptss_glare_entry* src = pyramid + lv[k].first;
+        const int w = lv[k - 1].width, h = lv[k - 1].height, cw = lv[k].width, ch = lv[k].height;
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                ptlin::u64 u[3];
+                ptglare::upTexel(x, y, cw, ch, [&](int i, int j, ptlin::u64* v) {
+                    const ptss_glare_entry& e = src[(size_t)j * (size_t)cw + (size_t)i];
+                    v[0] = e.r, v[1] = e.g, v[2] = e.b;
+                }, u);
+                ptss_glare_entry& e = dst[(size_t)y * (size_t)w + (size_t)x];
+                e.r += u[0], e.g += u[1], e.b += u[2];
+            }
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params, int width, int height,
+                             const ptss_glare_params* glare, const ptss_glare_entry* pyramid, const ptss_meter_state* state,
+                             ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history) {
+    if (ptlin::paramsError(params) || ptglare::paramsError(glare, *params) || ptglare::sidesError(width, height)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_GLARE_FILM_LINEAR && filmKind != PTSS_GLARE_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if (count == 0) return PTSS_HOST_OK;
+    const size_t filmPixels = (size_t)width * (size_t)height;
+    if (!film || !pyramid || firstPixel > filmPixels || count > filmPixels - firstPixel) return PTSS_HOST_EINVAL;
+    const bool splat = filmKind == PTSS_GLARE_FILM_SPLAT;
+    const unsigned long long* words = static_cast<const unsigned long long*>(film);
+    const ptglare::Rule R = ptglare::ruleOf(*glare, *params);
+    ptlin::Scale sc = ptlin::scaleOf(*params);
+    if (state) sc.exposure = state->exposure * sc.exposure;
+    const int cw = ptglare::halfOf(width), ch = ptglare::halfOf(height);
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        ptlin::u64 up[3];
+        ptglare::upTexel((int)(p % (size_t)width), (int)(p / (size_t)width), cw, ch, [&](int i, int j, ptlin::u64* v) {
+            const ptss_glare_entry& e = pyramid[(size_t)j * (size_t)cw + (size_t)i];
+            v[0] = e.r, v[1] = e.g, v[2] = e.b;
+        }, up);
+        const unsigned long long* e = words + 4 * p;
+        float lin[4], hist[4];
+        uint32_t px;
+        ptglare::resolve(e[0], e[1], e[2], glareWeightOf(e, splat), splat, up, R, sc, nullptr, lin, &px, hist);
+        if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
+        if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
+        if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
+    }
     return PTSS_HOST_OK;
 }
 

@@ -43,6 +43,10 @@
 //                                   §3.31) — after each round ptss_meter_linear (ptss_meter_splat) into a zeroed histogram,
 //                                   ptss_meter_exposure (default parameters; key default 0.18, rate default 1) and the metered resolve, --linear's
 //                                   exposure compensating. Prints the final ptss_meter_state. Without it every byte written is today's
+//             [--glare [strength[,threshold[,levels]]]]   with --linear, with or without --filter, --auto-exposure and --refill: highlights bleed
+//                                    — after the last round ptss_glare_build over the film (default parameters; strength default
+//                                   0.1, threshold default 0, levels default 6) and ptss_resolve_linear_glare (ptss_resolve_splat_glare), with the
+//                                   meter's state where --auto-exposure keeps one. Without it every byte written is today's
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -74,6 +78,9 @@ int main(int argc, char* argv[]) {
     std::string splat;     // --filter: the reconstruction filter of the linear film, empty = none (a box by pixel index)
     bool autoExposure = false;   // --auto-exposure: the linear film's exposure is metered on the device
     float meterKey = -1.f, meterRate = -1.f;   // ... its key and rate when given
+    bool glare = false;                        // --glare: the final resolve of the linear film adds the glare pyramid
+    float glareStrength = -1.f, glareThreshold = -1.f;   // ... its strength, threshold and levels when given
+    int glareLevels = -1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -119,6 +126,17 @@ int main(int argc, char* argv[]) {
                 const int got = sscanf(next(), "%f,%f", &meterKey, &meterRate);
                 if (got < 1 || !(meterKey > 0.f && meterKey < 1e30f) || (got == 2 && !(meterRate >= 0.f && meterRate <= 1.f))) {
                     fprintf(stderr, "bad --auto-exposure (key[,rate])\n");
+                    return 2;
+                }
+            }
+        }
+        else if (a == "--glare") {
+            glare = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) {
+                const int got = sscanf(next(), "%f,%f,%d", &glareStrength, &glareThreshold, &glareLevels);
+                if (got < 1 || !(glareStrength >= 0.f && glareStrength <= 1.f) || (got >= 2 && !(glareThreshold >= 0.f && glareThreshold < 1e30f)) ||
+                    (got == 3 && (glareLevels < 1 || glareLevels > PTSS_GLARE_MAX_LEVELS))) {
+                    fprintf(stderr, "bad --glare (strength[,threshold[,levels]])\n");
                     return 2;
                 }
             }
@@ -175,6 +193,7 @@ int main(int argc, char* argv[]) {
     if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
     if (linear >= 0.f && (film.empty() || adaptive >= 0)) { fprintf(stderr, "--linear needs --film and no --adaptive\n"); return 2; }
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
+    if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -343,6 +362,18 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
         }
+        void* dPyramid = nullptr;   // --glare
+        ptss_glare_params glareParams;
+        PTSS_HANDLE(ptss_default_glare_params(&glareParams));
+        if (glareStrength >= 0.f) glareParams.strength = glareStrength;
+        if (glareThreshold >= 0.f) glareParams.threshold = glareThreshold;
+        if (glareLevels >= 1) glareParams.levels = glareLevels;
+        if (glare) {
+            ptss_glare_level levels[PTSS_GLARE_MAX_LEVELS];
+            size_t entries = 0;
+            PTSS_HANDLE(ptss_glare_layout(width, height, glareParams.levels, levels, &entries));
+            if (hipMalloc(&dPyramid, entries * sizeof(ptss_glare_entry)) != hipSuccess) { fprintf(stderr, "--glare: device buffers\n"); return 1; }
+        }
         auto meteredResolve = [&]() -> int {   // the exposure is the state's, --linear's compensating
             if (dPos) {
                 PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
@@ -415,10 +446,24 @@ int main(int argc, char* argv[]) {
                 if (hipMemcpy(&state, dMeter, sizeof(state), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--auto-exposure: read-back\n"); return 1; }
                 printf("auto-exposure: exposure %.9g target %.9g meanLog2 %.9g updates %u metered %llu black %llu counted %llu sumLog %llu\n", state.exposure,
                        state.target, state.meanLog2, state.updates, state.metered, state.black, state.counted, state.sumLog);
-            } else if (dPos) {
+            }
+            if (glare) {   // the pyramid of the finished film, and the resolve that adds it: at the meter's exposure where there is one
+                const ptss_meter_state* state = autoExposure ? (const ptss_meter_state*)dMeter : NULL;
+                PTSS_HANDLE(ptss_glare_build(ctx, dLinear, dPos ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, width, height, &linearParams, &glareParams,
+                                             (ptss_glare_entry*)dPyramid, NULL));
+                if (dPos) {
+                    PTSS_HANDLE(ptss_resolve_splat_glare(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, width, height, &glareParams,
+                                                         (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
+                                                         (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                } else {
+                    PTSS_HANDLE(ptss_resolve_linear_glare(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, width, height, &glareParams,
+                                                          (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
+                                                          (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                }
+            } else if (!autoExposure && dPos) {
                 PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
                                                (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
-            } else {
+            } else if (!autoExposure) {
                 PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
                                                 (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             }
@@ -449,7 +494,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

@@ -18,6 +18,8 @@ from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 from ptss_types import POSITION_DTYPE, SPLAT_BOX, SPLAT_DTYPE, SPLAT_GAUSSIAN, SPLAT_TENT, FilmPosition, SplatEntry, SplatFilter
 from ptss_types import METER_BINS, METER_BLOCK, METER_GRID_CAP, METER_STATE_DTYPE, MeterParams, MeterState
+from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SPLAT, GLARE_MAX_LEVELS, GLARE_MIX, GLARE_TAIL_ENTRIES, GLARE_TILE, GlareLevel,
+                        GlareParams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -202,6 +204,10 @@ def host_lib():
         L.ptss_probe_meter_linear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         L.ptss_probe_meter_splat.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         L.ptss_probe_meter_exposure.argtypes = [C.c_void_p, C.POINTER(LinearParams), C.POINTER(MeterParams), C.c_void_p]
+        L.ptss_glare_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(GlareLevel), C.POINTER(C.c_size_t)]
+        L.ptss_probe_glare_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LinearParams), C.POINTER(GlareParams), C.c_void_p]
+        L.ptss_probe_resolve_glare.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_int, C.c_int,
+                                               C.POINTER(GlareParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -313,6 +319,13 @@ def device_lib():
         L.ptss_resolve_linear_metered.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp, vp]
         L.ptss_resolve_splat_metered.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp, vp]
         L.ptss_meter_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_glare_params.argtypes = [C.POINTER(GlareParams)]
+        L.ptss_glare_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(GlareLevel), C.POINTER(C.c_size_t)]
+        L.ptss_glare_build.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LinearParams), C.POINTER(GlareParams), vp, vp]
+        L.ptss_resolve_linear_glare.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_int, C.c_int, C.POINTER(GlareParams), vp, vp,
+                                                vp, vp, vp, vp]
+        L.ptss_resolve_splat_glare.argtypes = L.ptss_resolve_linear_glare.argtypes
+        L.ptss_glare_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -899,6 +912,82 @@ def probe_meter_exposure(histogram, state=None, params=None, meter=None):
     if rc != 0:
         raise PtssError(f"ptss_probe_meter_exposure: {rc}")
     return s
+
+
+# ---- glare for the two linear films (ptss_glare_build and the glare resolves) ----
+_GLARE_MODES = {"add": GLARE_ADD, "mix": GLARE_MIX}
+_GLARE_FILMS = {"linear": GLARE_FILM_LINEAR, "splat": GLARE_FILM_SPLAT}
+
+
+def glare_params(levels=6, mode="mix", threshold=0.0, strength=0.1):
+    """A ptss_glare_params; mode: "add", "mix" or a PTSS_GLARE_* value; the defaults are ptss_default_glare_params' (design choices, not
+    measurements)."""
+    p = GlareParams()
+    p.structSize = C.sizeof(GlareParams)
+    p.levels, p.mode, p.threshold, p.strength, p.reserved = int(levels), int(_GLARE_MODES.get(mode, mode)), float(threshold), float(strength), 0
+    return p
+
+
+def glare_layout(width, height, levels):
+    """ptss_glare_layout (the host library's) -> ([(width, height, first entry) of level 1 .. levels], entries in all)."""
+    out, n = (GlareLevel * GLARE_MAX_LEVELS)(), C.c_size_t(0)
+    if host_lib().ptss_glare_layout(int(width), int(height), int(levels), out, C.byref(n)) != 0:
+        raise PtssError("ptss_glare_layout")
+    return [(out[k].width, out[k].height, int(out[k].first)) for k in range(int(levels))], int(n.value)
+
+
+def _glare_film(film, film_kind, width, height):
+    """A film for a glare call as (width * height, 4) uint64 rows, and its PTSS_GLARE_FILM_* value. film_kind: "linear", "splat", a value,
+    or None: what the film's dtype says (plain rows count as linear)."""
+    if film_kind is None:
+        film_kind = GLARE_FILM_SPLAT if np.asarray(film).dtype == SPLAT_DTYPE else GLARE_FILM_LINEAR
+    kind = int(_GLARE_FILMS.get(film_kind, film_kind))
+    f = _rows(film, SPLAT_DTYPE if kind == GLARE_FILM_SPLAT else LINEAR_DTYPE, 4, np.uint64, "film")
+    if len(f) != int(width) * int(height):
+        raise ValueError("film: width * height entries")
+    return f, kind
+
+
+def _glare_pyramid(pyramid, entries):
+    """A pyramid as (entries, 4) uint64 rows."""
+    a = _rows(pyramid, GLARE_DTYPE, 4, np.uint64, "pyramid")
+    if len(a) < entries:
+        raise ValueError("pyramid: the entries glare_layout counts")
+    return a
+
+
+def probe_glare_build(film, width, height, params=None, glare=None, film_kind=None):
+    """ptss_glare_build on the host (csrc/ptglare.h; the specification of the device's pyramid) -> the pyramid, (entries,) GLARE_DTYPE:
+    u_1 .. u_L as glare_layout places them. film: (width * height,) LINEAR_DTYPE or SPLAT_DTYPE, or (P, 4) uint64 with film_kind."""
+    f, kind = _glare_film(film, film_kind, width, height)
+    params = params if params is not None else linear_params()
+    glare = glare if glare is not None else glare_params()
+    out = np.zeros((max(glare_layout(width, height, glare.levels)[1], 1), 4), dtype=np.uint64)
+    rc = host_lib().ptss_probe_glare_build(f.ctypes.data_as(C.c_void_p), kind, int(width), int(height), C.byref(params), C.byref(glare),
+                                           out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_glare_build: {rc}")
+    return out.view(GLARE_DTYPE).reshape(-1)
+
+
+def probe_resolve_glare(film, width, height, pyramid, first_pixel=0, count=None, params=None, glare=None, state=None, linear=True, pixels=True,
+                        history=True, film_kind=None):
+    """ptss_resolve_linear_glare / ptss_resolve_splat_glare on the host, with the literal tone map -> probe_resolve_linear's results.
+    pyramid: what probe_glare_build or Renderer.glare_build gave for this film and `glare`; state: a meter's state or None."""
+    f, kind = _glare_film(film, film_kind, width, height)
+    P = len(f)
+    first_pixel, count = _linear_range(P, first_pixel, count)
+    params = params if params is not None else linear_params()
+    glare = glare if glare is not None else glare_params()
+    pyr = _glare_pyramid(pyramid, glare_layout(width, height, glare.levels)[1])
+    ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
+    st = _meter_state(state) if state is not None else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = host_lib().ptss_probe_resolve_glare(ptr(f), kind, first_pixel, count, C.byref(params), int(width), int(height), C.byref(glare), ptr(pyr),
+                                             ptr(st), ptr(ln), ptr(px), ptr(hs))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_resolve_glare: {rc}")
+    return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
 
 def default_denoise_params(**overrides):
@@ -1799,22 +1888,31 @@ class Renderer:
                                LINEAR_DTYPE, np.uint64, results, film, first_pixel, index)
         return None if out is None else out[0]
 
-    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None):
+    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
         numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64; linear / pixels / history: None (NULL), True (zeros beforehand) or the buffer's
         content beforehand -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample count, pixels (P, 4) uint8, history (P,)
         HISTORY_DTYPE), each None when NULL. torch: film (P, 4) int64, linear (P, 4) float32 or None, pixels (P, 4) uint8 or None,
         history (P, 4) float32 or None, all on one device, WRITTEN IN PLACE -> None, on the current stream.
         metered: a meter's state (numpy: a METER_STATE_DTYPE record; torch: a (6,) int64 device tensor) -> ptss_resolve_linear_metered:
-        the exposure is the state's times params.exposure. Without it ptss_resolve_linear is called."""
+        the exposure is the state's times params.exposure. Without it ptss_resolve_linear is called.
+        glare: (width, height, a glare_params, the pyramid glare_build gave for this film and those parameters; torch: an (entries, 4)
+        int64 device tensor) -> ptss_resolve_linear_glare, with `metered` as its state or NULL."""
         L = device_lib()
         return self._resolve(L.ptss_resolve_linear, L.ptss_resolve_linear_metered, LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels,
-                             history, metered)
+                             history, metered, L.ptss_resolve_linear_glare, glare)
 
-    def _resolve(self, plain, with_state, film_dtype, film, first_pixel, count, params, linear, pixels, history, metered):
-        """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, or `with_state` where `metered` is a state."""
+    def _resolve(self, plain, with_state, film_dtype, film, first_pixel, count, params, linear, pixels, history, metered, with_glare=None, glare=None):
+        """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, `with_state` where `metered` is a state, or
+        `with_glare` where `glare` is (width, height, glare_params, pyramid)."""
         params = params if params is not None else linear_params()
-        if metered is None:
+        d_pyr = pyr = None
+        if glare is not None:
+            g_width, g_height, g_params, g_pyramid = glare
+            g_entries = glare_layout(g_width, g_height, g_params.levels)[1]
+            call = lambda ctx, f, first, n, par, ln, px, hs, st: with_glare(ctx, f, first, n, par, int(g_width), int(g_height), C.byref(g_params),
+                                                                           d_pyr, d_state, ln, px, hs, st)
+        elif metered is None:
             call = plain
         else:
             call = lambda ctx, f, first, n, par, ln, px, hs, st: with_state(ctx, f, first, n, par, d_state, ln, px, hs, st)
@@ -1825,6 +1923,10 @@ class Renderer:
             first_pixel, count = _linear_range(P, first_pixel, count)
             d_film = self._torch_ptr(film, "film", "int64", 4)
             d_state = self._torch_ptr(metered, "metered", "int64", 0, dev, 6) if metered is not None else None
+            if glare is not None:
+                if P != int(g_width) * int(g_height):
+                    raise ValueError("film: width * height entries")
+                d_pyr = self._torch_ptr(g_pyramid, "pyramid", "int64", 4, dev, g_entries)
             d_ln = self._torch_ptr(linear, "linear", "float32", 4, dev, P) if linear is not None else None
             d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
             d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
@@ -1837,14 +1939,18 @@ class Renderer:
         ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
         state = _meter_state(metered) if metered is not None else None
         d_state = None
+        if glare is not None:
+            if P != int(g_width) * int(g_height):
+                raise ValueError("film: width * height entries")
+            pyr = _glare_pyramid(g_pyramid, g_entries)
         if count == 0:
             _check(call(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
         else:
             def run(d):
-                nonlocal d_state
-                d_state = d[4]
+                nonlocal d_state, d_pyr
+                d_state, d_pyr = d[4], d[5]
                 _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None))
-            self._round_trip([f, ln, px, hs, state], run, read=(1, 2, 3))
+            self._round_trip([f, ln, px, hs, state, pyr], run, read=(1, 2, 3))
         return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
     # --- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat) ------------------
@@ -1886,12 +1992,46 @@ class Renderer:
             self._round_trip([r, pos, f], lambda d: call(d[0], d[1], n, d[2], None), read=(2,))
         return f.view(SPLAT_DTYPE).reshape(-1)
 
-    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None):
+    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None):
         """ptss_resolve_splat: resolve_linear's arguments and results over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64); the
-        weight of linear and history is the summed filter weight. metered: as in resolve_linear (ptss_resolve_splat_metered)."""
+        weight of linear and history is the summed filter weight. metered: as in resolve_linear (ptss_resolve_splat_metered); glare: as in
+        resolve_linear (ptss_resolve_splat_glare)."""
         L = device_lib()
         return self._resolve(L.ptss_resolve_splat, L.ptss_resolve_splat_metered, SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels,
-                             history, metered)
+                             history, metered, L.ptss_resolve_splat_glare, glare)
+
+    # --- glare for the two linear films (ptss_glare_build; the resolves take glare=) ------------------
+    def glare_build(self, film, width, height, params=None, glare=None, film_kind=None, pyramid=None):
+        """ptss_glare_build: the glare pyramid of a whole film. numpy: film (width * height,) LINEAR_DTYPE or SPLAT_DTYPE, or (P, 4)
+        uint64 with film_kind "linear" / "splat" -> the pyramid, (entries,) GLARE_DTYPE: u_1 .. u_L as glare_layout places them. torch:
+        film (P, 4) int64, film_kind given ("linear" where None), pyramid an (entries, 4) int64 device tensor WRITTEN IN PLACE -> None,
+        on the current stream. params: the film's linear_params; glare: a glare_params."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        glare = glare if glare is not None else glare_params()
+        width, height = int(width), int(height)
+        if type(film).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev = film.device
+            kind = int(_GLARE_FILMS.get(film_kind, GLARE_FILM_LINEAR if film_kind is None else film_kind))
+            d_film = self._torch_ptr(film, "film", "int64", 4, None, width * height)
+            d_pyr = self._torch_ptr(pyramid, "pyramid", "int64", 4, dev, glare_layout(width, height, glare.levels)[1])
+            _check(L.ptss_glare_build(self._ctx, d_film, kind, width, height, C.byref(params), C.byref(glare), d_pyr,
+                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        f, kind = _glare_film(film, film_kind, width, height)
+        out = np.zeros((glare_layout(width, height, glare.levels)[1], 4), dtype=np.uint64)
+        self._round_trip([f, out], lambda d: _check(L.ptss_glare_build(self._ctx, d[0], kind, width, height, C.byref(params), C.byref(glare), d[1], None)),
+                         read=(1,))
+        return out.view(GLARE_DTYPE).reshape(-1)
+
+    def glare_launches(self):
+        """ptss_glare_launches: (glare_build calls, the kernels they launched, glare resolves that launched since the context was
+        created)."""
+        out = (C.c_ulonglong * 3)()
+        _check(device_lib().ptss_glare_launches(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

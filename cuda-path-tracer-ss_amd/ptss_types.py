@@ -176,6 +176,23 @@ METER_STATE_DTYPE = np.dtype([("exposure", np.float32), ("target", np.float32), 
                               ("metered", np.uint64), ("black", np.uint64), ("counted", np.uint64), ("sumLog", np.uint64)])
 
 
+# glare for the two linear films (include/ptss_types.h PTSS_GLARE_*; csrc/ptglare.h kTile, kTailEntries: the shapes of ptss_glare.hip)
+GLARE_MAX_LEVELS, GLARE_ADD, GLARE_MIX, GLARE_FILM_LINEAR, GLARE_FILM_SPLAT = 8, 0, 1, 0, 1
+GLARE_TILE, GLARE_TAIL_ENTRIES = 16, 2730
+
+
+class GlareParams(C.Structure):   # ptss_glare_params: the pyramid's levels, how it joins the mean, what counts as a highlight
+    _fields_ = [("structSize", C.c_uint), ("levels", C.c_int), ("mode", C.c_int), ("threshold", C.c_float), ("strength", C.c_float),
+                ("reserved", C.c_uint)]
+
+
+class GlareLevel(C.Structure):   # ptss_glare_level: one level of a pyramid
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("first", C.c_ulonglong)]
+
+
+GLARE_DTYPE = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("zero", np.uint64)])   # ptss_glare_entry
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -227,6 +244,7 @@ assert C.sizeof(FilmPosition) == 8 == POSITION_DTYPE.itemsize and C.sizeof(Splat
 assert C.sizeof(SplatEntry) == 32 == SPLAT_DTYPE.itemsize and SplatEntry.weight.offset == 24 == SPLAT_DTYPE.fields["weight"][1]
 assert C.sizeof(MeterParams) == 32 and MeterParams.reserved.offset == 28 and C.sizeof(MeterState) == 48 == METER_STATE_DTYPE.itemsize
 assert MeterState.metered.offset == 16 == METER_STATE_DTYPE.fields["metered"][1] and MeterState.sumLog.offset == 40 == METER_STATE_DTYPE.fields["sumLog"][1]
+assert C.sizeof(GlareParams) == 24 and GlareParams.reserved.offset == 20 and C.sizeof(GlareLevel) == 16 and GLARE_DTYPE.itemsize == 32
 
 
 def struct_to_dict(s):

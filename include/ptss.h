@@ -538,6 +538,47 @@ int ptss_resolve_splat_metered(ptss_context* ctx, const ptss_splat_entry* dev_fi
                                ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
 int ptss_meter_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] histograms, [1] exposure updates, [2] metered resolves */
 
+/* Glare for the two linear films: highlights that bleed, taken between the film and the tone map, where the energy
+ * above display white still exists. csrc/ptglare.h has the arithmetic; its host build (ptss_probe_glare_build,
+ * ptss_probe_resolve_glare) is the specification and the device equals it byte for byte. Everything in front of the resolve's float steps
+ * is unsigned 64-bit integer work, so a pyramid is the same bytes whatever kernels built it.
+ *
+ * ptss_glare_layout: the levels of a pyramid over a width x height film, out[k - 1] for level k = 1 .. levels: (w + 1) / 2 x (h + 1) / 2
+ * of the level below, level 0 being the film; the levels lie one behind the other, *entries ptss_glare_entry in all.
+ *
+ * ptss_glare_build: the whole film. Per pixel and channel m = the integer mean of the resolve (0 for a pixel without samples), t =
+ * glare->threshold in the film's fixed point, the source b = m > t ? m - t : 0. d_k(i, j) = (the 4 x 4 texels 2i-1 .. 2i+2 x 2j-1 .. 2j+2
+ * of level k - 1, weights (1, 3, 3, 1) per axis, coordinates clamped, + 32) >> 6; then from the coarsest level u_L = d_L, u_k = d_k +
+ * up(u_{k+1}), up at x = 2i taking 3 a[i] + a[i-1], at x = 2i + 1 taking 3 a[i] + a[i+1], the axes multiplied, (sum + 8) >> 4. Afterwards
+ * dev_pyramid holds u_1 .. u_L. One launch for the film, one per large level and direction, and one for all the small levels together.
+ *
+ * ptss_resolve_linear_glare / ptss_resolve_splat_glare: ptss_resolve_linear / ptss_resolve_splat of pixels firstPixel .. firstPixel +
+ * count with g = (up(u_1) + L / 2) / L, s = (uint32_t)(strength * 65536 + 0.5) and m' = (m * k + g * s + 32768) >> 16 shown in place of m:
+ * k = 65536 (PTSS_GLARE_ADD) or 65536 - s (PTSS_GLARE_MIX). The weight of linear and history stays the pixel's own; a pixel without
+ * samples that receives no glare is the plain resolve's empty row, so strength = 0 gives the plain resolve's bytes. dev_state: NULL, or
+ * a meter's state: the exposure is state->exposure * params->exposure. glare must be what the pyramid was built with (levels above all).
+ *
+ * Refused before the device is touched, nothing counted. PTSS_EINVAL: a null ctx, film, pyramid, params or glare, a wrong structSize,
+ * whatever ptss_resolve_linear refuses about params, levels outside [1, 8], an unknown mode or film kind, a strength outside [0, 1], a
+ * threshold that is negative, not finite or with threshold * 2^scaleLog2 > 2^40, a non-zero reserved, a film, pyramid, linear or history
+ * pointer that is not 16-byte aligned, a state that is not 8-byte, pixels that are not 4-byte aligned. PTSS_ERANGE: width or height
+ * outside [1, 2^22], width * height >= 2^31, firstPixel + count beyond the film. count = 0 returns PTSS_OK.
+ * ptss_default_glare_params: levels 6, PTSS_GLARE_MIX, threshold 0, strength 0.1 (design choices, not measurements). */
+int ptss_default_glare_params(ptss_glare_params* params);
+int ptss_glare_layout(int width, int height, int levels, ptss_glare_level out[8], size_t* entries);
+int ptss_glare_build(ptss_context* ctx, const void* dev_film, int filmKind /* PTSS_GLARE_FILM_LINEAR | PTSS_GLARE_FILM_SPLAT */, int width,
+                     int height, const ptss_linear_params* params, const ptss_glare_params* glare, ptss_glare_entry* dev_pyramid,
+                     void* hipStream);
+int ptss_resolve_linear_glare(ptss_context* ctx, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count,
+                              const ptss_linear_params* params, int width, int height, const ptss_glare_params* glare,
+                              const ptss_glare_entry* dev_pyramid, const ptss_meter_state* dev_state /* may be NULL */,
+                              ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream);
+int ptss_resolve_splat_glare(ptss_context* ctx, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count,
+                             const ptss_linear_params* params, int width, int height, const ptss_glare_params* glare,
+                             const ptss_glare_entry* dev_pyramid, const ptss_meter_state* dev_state /* may be NULL */,
+                             ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream);
+int ptss_glare_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] builds, [1] kernels launched inside them, [2] glare resolves */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

@@ -241,6 +241,20 @@ int ptss_probe_meter_splat(const ptss_splat_entry* film, size_t firstPixel, size
 int ptss_probe_meter_exposure(const uint32_t* histogram, const ptss_linear_params* params, const ptss_meter_params* meter,
                               ptss_meter_state* state /* in/out */);
 
+/* Glare on the host (csrc/ptglare.h — the very operations the kernels evaluate; this build is the specification).
+ * ptss_glare_layout: ptss.h's, with PTSS_HOST_EINVAL for every refusal.
+ * ptss_probe_glare_build: ptss_glare_build as straight loops: the downs level by level, then the ups in place from the coarsest level.
+ * film: width * height entries of 32 B, a ptss_splat_entry where filmKind is PTSS_GLARE_FILM_SPLAT; pyramid: the entries
+ * ptss_glare_layout counts, all of them written. PTSS_HOST_EINVAL: whatever ptss_glare_build refuses, alignment aside. */
+int ptss_glare_layout(int width, int height, int levels, ptss_glare_level out[8], size_t* entries);
+int ptss_probe_glare_build(const void* film, int filmKind, int width, int height, const ptss_linear_params* params,
+                           const ptss_glare_params* glare, ptss_glare_entry* pyramid);
+/* ptss_resolve_linear_glare / ptss_resolve_splat_glare on the host, with the literal tone map: pixels firstPixel .. firstPixel + count.
+ * state may be NULL (the exposure is params->exposure), linear / pixels / history each may be NULL. */
+int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params, int width,
+                             int height, const ptss_glare_params* glare, const ptss_glare_entry* pyramid, const ptss_meter_state* state,
+                             ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,38 @@ typedef struct ptss_meter_state {
     unsigned long long metered, black, counted, sumLog;
 } ptss_meter_state;
 
+/* Glare for the two linear films (ptss_glare_build and the glare resolves): a pyramid of rounded integer averages of
+ * what a film's integer pixel means hold above a threshold, added to or mixed with the means in front of the tone map. */
+#define PTSS_GLARE_MAX_LEVELS 8
+#define PTSS_GLARE_ADD 0          /* m' = m + strength * g */
+#define PTSS_GLARE_MIX 1          /* m' = (1 - strength) * m + strength * g */
+#define PTSS_GLARE_FILM_LINEAR 0  /* the film is ptss_linear_entry */
+#define PTSS_GLARE_FILM_SPLAT 1   /* the film is ptss_splat_entry */
+
+/* levels in [1, 8]: the pyramid's levels, each half the one below, rounded up; mode: PTSS_GLARE_*; threshold >= 0, finite, in the film's
+ * radiance units with threshold * 2^scaleLog2 <= 2^40: what is taken off every channel of a mean (what is left, never negative, is the
+ * pyramid's source); strength in [0, 1]: 0 leaves the plain resolve's bytes. */
+typedef struct ptss_glare_params {
+    unsigned int structSize; /* sizeof(ptss_glare_params) as the caller compiled it */
+    int levels;
+    int mode;
+    float threshold;
+    float strength;
+    unsigned int reserved;   /* 0 */
+} ptss_glare_params;
+
+/* One texel of a glare pyramid, in the film's fixed point. 32 B, 16-byte aligned access; the fourth word is always written as 0. */
+typedef struct ptss_glare_entry {
+    unsigned long long r, g, b;
+    unsigned long long zero;
+} ptss_glare_entry;
+
+/* Where level k (1 .. levels; out[k - 1]) of a pyramid lies: width x height entries in rows, the first at entry `first` (ptss_glare_layout). */
+typedef struct ptss_glare_level {
+    int width, height;
+    unsigned long long first;
+} ptss_glare_level;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -396,6 +428,13 @@ static_assert(sizeof(ptss_meter_params) == 32 && offsetof(ptss_meter_params, key
 static_assert(sizeof(ptss_meter_state) == 48 && offsetof(ptss_meter_state, updates) == 12 && offsetof(ptss_meter_state, metered) == 16 &&
                   offsetof(ptss_meter_state, sumLog) == 40,
               "ptss_meter_state is four 32-bit and four 64-bit words");
+static_assert(sizeof(ptss_glare_params) == 24 && offsetof(ptss_glare_params, levels) == 4 && offsetof(ptss_glare_params, threshold) == 12 &&
+                  offsetof(ptss_glare_params, reserved) == 20,
+              "ptss_glare_params is six 32-bit words");
+static_assert(sizeof(ptss_glare_entry) == 32 && offsetof(ptss_glare_entry, g) == 8 && offsetof(ptss_glare_entry, zero) == 24,
+              "ptss_glare_entry is two 16-byte rows");
+static_assert(sizeof(ptss_glare_level) == 16 && offsetof(ptss_glare_level, height) == 4 && offsetof(ptss_glare_level, first) == 8,
+              "ptss_glare_level is two 32-bit words and one 64-bit word");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -440,6 +479,13 @@ _Static_assert(sizeof(ptss_meter_params) == 32 && offsetof(ptss_meter_params, ke
 _Static_assert(sizeof(ptss_meter_state) == 48 && offsetof(ptss_meter_state, updates) == 12 && offsetof(ptss_meter_state, metered) == 16 &&
                    offsetof(ptss_meter_state, sumLog) == 40,
                "ptss_meter_state is four 32-bit and four 64-bit words");
+_Static_assert(sizeof(ptss_glare_params) == 24 && offsetof(ptss_glare_params, levels) == 4 && offsetof(ptss_glare_params, threshold) == 12 &&
+                   offsetof(ptss_glare_params, reserved) == 20,
+               "ptss_glare_params is six 32-bit words");
+_Static_assert(sizeof(ptss_glare_entry) == 32 && offsetof(ptss_glare_entry, g) == 8 && offsetof(ptss_glare_entry, zero) == 24,
+               "ptss_glare_entry is two 16-byte rows");
+_Static_assert(sizeof(ptss_glare_level) == 16 && offsetof(ptss_glare_level, height) == 4 && offsetof(ptss_glare_level, first) == 8,
+               "ptss_glare_level is two 32-bit words and one 64-bit word");
 #endif
 
 #ifdef __cplusplus
