@@ -25,6 +25,7 @@
 #include "ptcamera.h"
 #include "ptadaptive.h"
 #include "ptlinear.h"
+#include "ptlinstats.h"
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
@@ -159,6 +160,7 @@ struct ptss_context {
     bool filmIndexed = false;
     unsigned long long adaptiveLaunches[2] = {0, 0};          // ptss_accumulate_paths_stats, ptss_plan_samples calls that launched
     unsigned long long linearLaunches[2] = {0, 0};            // ptss_accumulate_paths_linear, ptss_resolve_linear calls that launched
+    unsigned long long linStatsLaunches[2] = {0, 0};          // ptss_accumulate_paths_linear_stats, ptss_plan_samples_linear calls that launched
     unsigned long long splatLaunches[3] = {0, 0, 0};          // ptss_splat_paths, ptss_splat_paths_homed, ptss_resolve_splat calls that launched
     unsigned long long meterLaunches[3] = {0, 0, 0};          // meter histograms, ptss_meter_exposure, metered resolves that launched
     unsigned long long glareLaunches[3] = {0, 0, 0};          // glare builds, the kernels they launched, glare resolves that launched
@@ -1508,6 +1510,63 @@ int ptss_linear_launches(const ptss_context* c, unsigned long long* out2) {
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->linearLaunches[0];
     out2[1] = c->linearLaunches[1];
+    return PTSS_OK;
+}
+
+// ---- adaptive sampling on the linear film (ptss_linstats.hip, ptss_adaptive.hip; csrc/ptlinstats.h). Like the film calls:
+// no frame state, the caller's stream ----
+int ptss_default_linear_plan_params(ptss_linear_plan_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_linear_plan_params);
+    p->minSamples = 8u;
+    p->maxSamples = ptad::kSampleLimit;
+    p->threshold = 0.02f;
+    p->floor = 0.015625f;
+    p->reserved[0] = p->reserved[1] = p->reserved[2] = 0u;
+    return PTSS_OK;
+}
+
+int ptss_accumulate_paths_linear_stats(ptss_context* c, const ptss_path_result* dev_results, const uint32_t* dev_index, size_t firstPixel, size_t n,
+                                       ptss_linear_entry* dev_film, ptss_linear_moment* dev_moments, size_t filmPixels,
+                                       const ptss_linear_params* params, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    const char* bad = !dev_results || !dev_moments ? kNullBuffer
+                      : (((uintptr_t)dev_results | (uintptr_t)dev_film | (uintptr_t)dev_moments) & 15u) || ((uintptr_t)dev_index & 3u)
+                          ? "results, film and moments must be 16-byte aligned, dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchLinStatsAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, dev_moments, f.filmPixels, *params,
+                                           c->dTotal + kFilmRejectedWord, &c->linStatsLaunches[0]));
+    noteFilmIndex(c, dev_index, f.st);
+    return PTSS_OK;
+}
+
+int ptss_plan_samples_linear(ptss_context* c, const ptss_linear_moment* dev_moments, size_t filmPixels, const ptss_linear_params* params,
+                             const ptss_linear_plan_params* plan, size_t n, unsigned long long* dev_cdf, uint32_t* dev_index,
+                             ptss_plan_info* dev_info, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptls::paramsError(plan, params)) return fail(PTSS_EINVAL, what);
+    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_moments || !dev_cdf || !dev_index) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (((uintptr_t)dev_moments & 15u) || (((uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u))
+        return fail(PTSS_EINVAL, "moments must be 16-byte aligned, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = streamOf(c, hipStream);
+    HIP_TRY(ptss::launchPlanSamplesLinear(st, dev_moments, (uint32_t)filmPixels, *params, *plan, (uint32_t)n, dev_cdf, dev_index, dev_info,
+                                          &c->linStatsLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_linear_stats_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->linStatsLaunches[0];
+    out2[1] = c->linStatsLaunches[1];
     return PTSS_OK;
 }
 

@@ -221,6 +221,16 @@ hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint
 hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
                              const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
                              unsigned long long* launches);
+// adaptive sampling on the linear film (ptss_linstats.hip, ptss_adaptive.hip; ptss_accumulate_paths_linear_stats / ptss_plan_samples_linear;
+// DESIGN.md §3.33). launchLinStatsAccumulate: launchLinearAccumulate's buffers and bytes, film or nullptr, plus moments = filmPixels x 32 B
+// (ptss_linear_moment). launchPlanSamplesLinear: launchPlanSamples' cdf, index and info over those moments; both params checked by the caller
+// (ptlin::paramsError, ptls::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+hipError_t launchLinStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
+                                    void* moments, uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
+                                    unsigned long long* launches);
+hipError_t launchPlanSamplesLinear(hipStream_t st, const void* moments, uint32_t filmPixels, const ptss_linear_params& film,
+                                   const ptss_linear_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index,
+                                   ptss_plan_info* info, unsigned long long* launches);
 // the linear film (ptss_linear.hip; ptss_accumulate_paths_linear / ptss_resolve_linear). launchLinearAccumulate:
 // launchFilmAccumulate's results, index and counter, film = filmPixels x 32 B (ptss_linear_entry). launchLinearResolve: pixels firstPixel ..
 // firstPixel + count of the film into linear / history (16 B per pixel) and pixels, each or nullptr (not all three). params: checked by the

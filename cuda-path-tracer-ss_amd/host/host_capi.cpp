@@ -14,6 +14,7 @@
 #include "ptcamera.h"
 #include "ptadaptive.h"
 #include "ptlinear.h"
+#include "ptlinstats.h"
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
@@ -713,6 +714,70 @@ int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t
     }
     if (rejected) *rejected = dropped;
     return PTSS_HOST_OK;
+}
+
+int ptss_probe_accumulate_linear_stats(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
+                                       ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
+                                       unsigned long long* rejected) {
+    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n > 0 && (!results || !moments)) return PTSS_HOST_EINVAL;
+    if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
+    const ptlin::Scale sc = ptlin::scaleOf(*params);
+    unsigned long long dropped = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const size_t p = index ? index[i] : firstPixel + i;
+        if (p >= filmPixels) {
+            ++dropped;
+            continue;
+        }
+        ptlin::u64 q[3];
+        const uint32_t flag = ptlin::sampleToFixed(results[i].radiance.x, results[i].radiance.y, results[i].radiance.z, sc, q);
+        const ptls::Sample s = ptls::sampleOf(q[0], q[1], q[2]);
+        moments[p].sumY += s.y;
+        moments[p].sqLo += s.lo;
+        moments[p].sqHi += s.hi;
+        moments[p].samples += 1ull;
+        if (film) {
+            film[p].r += q[0];
+            film[p].g += q[1];
+            film[p].b += q[2];
+            film[p].samples += 1u;
+            film[p].clamped += flag;
+        }
+    }
+    if (rejected) *rejected = dropped;
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_plan_samples_linear(const ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
+                                   const ptss_linear_plan_params* plan, size_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info) {
+    if (ptlin::paramsError(params) || ptls::paramsError(plan, params)) return PTSS_HOST_EINVAL;
+    if (filmPixels == 0 || filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!moments || !cdf || !index) return PTSS_HOST_EINVAL;
+    const ptls::Rule rule = ptls::ruleOf(*plan, *params);
+    ptss_plan_info found{};
+    unsigned long long sum = 0;
+    for (size_t p = 0; p < filmPixels; ++p) {
+        uint32_t kind;
+        sum += ptls::weight(moments[p].sumY, moments[p].sqLo, moments[p].sqHi, moments[p].samples, rule, &kind);
+        cdf[p] = sum;
+        found.activePixels += (kind & ptad::kActive) ? 1u : 0u;
+        found.unsampledPixels += (kind & ptad::kUnsampled) ? 1u : 0u;
+        found.cappedPixels += (kind & ptad::kCapped) ? 1u : 0u;
+    }
+    found.totalWeight = sum;
+    found.uniform = sum == 0ull ? 1u : 0u;
+    for (size_t i = 0; i < n; ++i)
+        index[i] = sum == 0ull ? ptad::uniformPixel(i, n, filmPixels) : ptad::pixelOf(cdf, (uint32_t)filmPixels, ptad::target(i, n, sum));
+    if (info) *info = found;
+    return PTSS_HOST_OK;
+}
+
+uint32_t ptss_probe_linear_plan_weight(const ptss_linear_moment* moment, const ptss_linear_params* params, const ptss_linear_plan_params* plan) {
+    if (!moment || ptlin::paramsError(params) || ptls::paramsError(plan, params)) return 0xffffffffu;
+    return ptls::weight(moment->sumY, moment->sqLo, moment->sqHi, moment->samples, ptls::ruleOf(*plan, *params), nullptr);
 }
 
 int ptss_probe_resolve_linear(const ptss_linear_entry* film, size_t firstPixel, size_t count, const ptss_linear_params* params,

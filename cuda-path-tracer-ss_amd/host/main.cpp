@@ -36,6 +36,12 @@
 //             [--linear [exposure]] with --film: the samples go into a linear film (ptss_accumulate_paths_linear, default parameters) and
 //                                   ptss_resolve_linear with that exposure (default 1) makes the screenshot, image.pfm — the linear means,
 //                                   unexposed — beside it and, with --denoise, the history the filter takes. Not with --adaptive
+//             [--adaptive-linear ROUNDS[,threshold[,floor]]]   with --linear, with or without --filter, --auto-exposure, --glare and
+//                                   --refill: the --ticks uniform rounds keep luminance moments
+//                                   (ptss_accumulate_paths_linear_stats; the same film bytes), then ROUNDS planned rounds of width * height rays
+//                                   each go where ptss_plan_samples_linear sends them (minSamples = --ticks; threshold and floor override the
+//                                   defaults'). With --filter the moments are kept by index pixel, beside ptss_splat_paths. Prints the final
+//                                   ptss_plan_info. ROUNDS = 0 writes the bytes of the run without the flag
 //             [--filter box|tent|gaussian[,radius[,alpha]]]   with --linear: the film is a filtered one — rounds go through
 //                                   ptss_generate_rays_positions, the trace, ptss_splat_paths_homed and, at the end, ptss_resolve_splat
 //                                   (radius default 1, alpha default 2). Without it the program's bytes are those of --linear alone
@@ -75,6 +81,8 @@ int main(int argc, char* argv[]) {
     int adaptive = -1;     // --adaptive: -1 absent, else the planned rounds behind the uniform ones
     float adaptiveThreshold = -1.f;   // ... and the plan's threshold when given
     float linear = -1.f;   // --linear: -1 absent, else the exposure of the resolve
+    int adaptiveLinear = -1;                                       // --adaptive-linear: -1 absent, else the planned rounds behind the uniform ones
+    float adaptiveLinearThreshold = -1.f, adaptiveLinearFloor = -1.f;   // ... and the plan's threshold and floor when given
     std::string splat;     // --filter: the reconstruction filter of the linear film, empty = none (a box by pixel index)
     bool autoExposure = false;   // --auto-exposure: the linear film's exposure is metered on the device
     float meterKey = -1.f, meterRate = -1.f;   // ... its key and rate when given
@@ -113,6 +121,14 @@ int main(int argc, char* argv[]) {
         else if (a == "--adaptive") {
             const int got = sscanf(next(), "%d,%f", &adaptive, &adaptiveThreshold);
             if (got < 1 || adaptive < 0 || (got == 2 && !(adaptiveThreshold >= 0.f && adaptiveThreshold < 1e30f))) { fprintf(stderr, "bad --adaptive (rounds[,threshold])\n"); return 2; }
+        }
+        else if (a == "--adaptive-linear") {
+            const int got = sscanf(next(), "%d,%f,%f", &adaptiveLinear, &adaptiveLinearThreshold, &adaptiveLinearFloor);
+            if (got < 1 || adaptiveLinear < 0 || (got >= 2 && !(adaptiveLinearThreshold >= 0.f && adaptiveLinearThreshold < 1e30f)) ||
+                (got == 3 && !(adaptiveLinearFloor > 0.f && adaptiveLinearFloor < 1e30f))) {
+                fprintf(stderr, "bad --adaptive-linear (rounds[,threshold[,floor]])\n");
+                return 2;
+            }
         }
         else if (a == "--linear") {
             linear = 1.f;
@@ -192,6 +208,7 @@ int main(int argc, char* argv[]) {
     if (refill && film.empty()) { fprintf(stderr, "--refill needs --film\n"); return 2; }
     if (adaptive >= 0 && film.empty()) { fprintf(stderr, "--adaptive needs --film\n"); return 2; }
     if (linear >= 0.f && (film.empty() || adaptive >= 0)) { fprintf(stderr, "--linear needs --film and no --adaptive\n"); return 2; }
+    if (adaptiveLinear >= 0 && linear < 0.f) { fprintf(stderr, "--adaptive-linear needs --film and --linear\n"); return 2; }
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
     ptss_splat_filter splatFilter;
@@ -343,6 +360,21 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
         }
+        ptss_linear_plan_params linearPlan;
+        PTSS_HANDLE(ptss_default_linear_plan_params(&linearPlan));
+        if (adaptiveLinear >= 0) {   // (dMoments holds ptss_linear_moment here: --adaptive and --linear exclude each other)
+            PTSS_HANDLE(ptss_plan_cdf_entries(n, &cdfEntries));
+            if (hipMalloc(&dMoments, n * sizeof(ptss_linear_moment)) != hipSuccess || hipMemset(dMoments, 0, n * sizeof(ptss_linear_moment)) != hipSuccess ||
+                hipMalloc(&dCdf, cdfEntries * sizeof(unsigned long long)) != hipSuccess || hipMalloc(&dIndex, n * sizeof(uint32_t)) != hipSuccess ||
+                hipMalloc(&dInfo, sizeof(ptss_plan_info)) != hipSuccess) {
+                fprintf(stderr, "--adaptive-linear: device buffers\n");
+                return 1;
+            }
+            linearPlan.minSamples = ticks > 0 ? (uint32_t)ticks : 1u;
+            if (linearPlan.maxSamples < linearPlan.minSamples) linearPlan.maxSamples = linearPlan.minSamples;
+            if (adaptiveLinearThreshold >= 0.f) linearPlan.threshold = adaptiveLinearThreshold;
+            if (adaptiveLinearFloor > 0.f) linearPlan.floor = adaptiveLinearFloor;
+        }
         if (linear >= 0.f) {
             linearParams.exposure = linear;
             if (hipMalloc(&dLinear, n * sizeof(ptss_linear_entry)) != hipSuccess || hipMemset(dLinear, 0, n * sizeof(ptss_linear_entry)) != hipSuccess ||
@@ -354,7 +386,7 @@ int main(int argc, char* argv[]) {
             if (!splat.empty() && hipMalloc(&dPos, n * sizeof(ptss_film_position)) != hipSuccess) { fprintf(stderr, "--filter: device buffers\n"); return 1; }
         }
         if (autoExposure) {   // every round meters into a histogram of its own, zeroed here: nothing is cleared between the rounds' launches
-            const size_t rounds = ticks > 0 ? (size_t)ticks : 1;
+            const size_t rounds = (ticks > 0 ? (size_t)ticks : 1) + (adaptiveLinear > 0 ? (size_t)adaptiveLinear : 0);
             if (hipMalloc(&dBins, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dMeter, sizeof(ptss_meter_state)) != hipSuccess ||
                 hipMemset(dBins, 0, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMemset(dMeter, 0, sizeof(ptss_meter_state)) != hipSuccess ||
                 hipDeviceSynchronize() != hipSuccess) {
@@ -384,6 +416,16 @@ int main(int argc, char* argv[]) {
             }
             return 0;
         };
+        auto meterRound = [&](int round) -> int {   // meter, update, metered resolve: the round's exposure never leaves the device
+            uint32_t* bins = (uint32_t*)dBins + (size_t)round * PTSS_METER_BINS;
+            if (dPos) {
+                PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, bins, NULL));
+            } else {
+                PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, bins, NULL));
+            }
+            PTSS_HANDLE(ptss_meter_exposure(ctx, bins, &linearParams, &meterParams, (ptss_meter_state*)dMeter, NULL));
+            return meteredResolve();
+        };
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
         for (int t = 0; t < ticks; ++t) {
             if (dPos) {
@@ -396,6 +438,13 @@ int main(int argc, char* argv[]) {
             if (dPos) {
                 PTSS_HANDLE(ptss_splat_paths_homed(ctx, (const ptss_path_result*)dRes, (const ptss_film_position*)dPos, 0, n, (ptss_splat_entry*)dLinear,
                                                    width, height, &splatFilter, &linearParams, NULL));
+                if (adaptiveLinear >= 0) {   // the moments by home pixel, beside the filtered film
+                    PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, NULL, (ptss_linear_moment*)dMoments, n,
+                                                                   &linearParams, NULL));
+                }
+            } else if (adaptiveLinear >= 0) {
+                PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_linear_entry*)dLinear,
+                                                               (ptss_linear_moment*)dMoments, n, &linearParams, NULL));
             } else if (linear >= 0.f) {
                 PTSS_HANDLE(ptss_accumulate_paths_linear(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_linear_entry*)dLinear, n, &linearParams, NULL));
             } else if (adaptive >= 0) {
@@ -405,16 +454,37 @@ int main(int argc, char* argv[]) {
                 PTSS_HANDLE(ptss_accumulate_paths(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_film_entry*)dFilm, n, (ptss_uchar4*)bitmap.devPixels,
                                                   (ptss_history_entry*)dHist, NULL));
             }
-            if (autoExposure) {   // meter, update, metered resolve: the round's exposure never leaves the device
-                uint32_t* bins = (uint32_t*)dBins + (size_t)t * PTSS_METER_BINS;
+            if (autoExposure && meterRound(t)) return 1;
+        }
+        if (adaptiveLinear >= 0) {   // the planned rounds on the linear film: ray slot i keeps stream i whatever pixel the plan gives it
+            for (int t = 0; t <= adaptiveLinear; ++t) {   // (the last plan only reports what the rounds left)
+                PTSS_HANDLE(ptss_plan_samples_linear(ctx, (const ptss_linear_moment*)dMoments, n, &linearParams, &linearPlan, n, (unsigned long long*)dCdf,
+                                                     (uint32_t*)dIndex, (ptss_plan_info*)dInfo, NULL));
+                if (t == adaptiveLinear) break;
                 if (dPos) {
-                    PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, bins, NULL));
+                    PTSS_HANDLE(ptss_generate_rays_positions(ctx, &fc, 0, (const uint32_t*)dIndex, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays,
+                                                             (ptss_film_position*)dPos, NULL));
                 } else {
-                    PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, bins, NULL));
+                    PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, (const uint32_t*)dIndex, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
                 }
-                PTSS_HANDLE(ptss_meter_exposure(ctx, bins, &linearParams, &meterParams, (ptss_meter_state*)dMeter, NULL));
-                if (meteredResolve()) return 1;
+                PTSS_HANDLE(ptss_trace_paths_opt(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, n, bounces, &pathOptions,
+                                                 NULL));
+                if (dPos) {   // planned rounds are not one sample per pixel: the scatter form, the moments by index pixel beside it
+                    PTSS_HANDLE(ptss_splat_paths(ctx, (const ptss_path_result*)dRes, (const ptss_film_position*)dPos, n, (ptss_splat_entry*)dLinear, width,
+                                                 height, &splatFilter, &linearParams, NULL));
+                    PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, (const uint32_t*)dIndex, 0, n, NULL,
+                                                                   (ptss_linear_moment*)dMoments, n, &linearParams, NULL));
+                } else {
+                    PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, (const uint32_t*)dIndex, 0, n,
+                                                                   (ptss_linear_entry*)dLinear, (ptss_linear_moment*)dMoments, n, &linearParams, NULL));
+                }
+                if (autoExposure && meterRound((ticks > 0 ? ticks : 1) + t)) return 1;
             }
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            ptss_plan_info info;
+            if (hipMemcpy(&info, dInfo, sizeof(info), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--adaptive-linear: read-back\n"); return 1; }
+            printf("adaptive-linear: rounds %d totalWeight %llu activePixels %u unsampledPixels %u cappedPixels %u uniform %u\n", adaptiveLinear,
+                   info.totalWeight, info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
         if (adaptive >= 0) {   // the planned rounds: ray slot i keeps stream i whatever pixel the plan gives it
             ptss_plan_params plan;

@@ -18,6 +18,7 @@ from ptss_types import (FILM_DTYPE, FILM_EQUIRECT, FILM_PINHOLE, FILM_THIN_LENS,
                         UChar4, UpsampleParams, Vec3, struct_to_dict)
 from ptss_types import POSITION_DTYPE, SPLAT_BOX, SPLAT_DTYPE, SPLAT_GAUSSIAN, SPLAT_TENT, FilmPosition, SplatEntry, SplatFilter
 from ptss_types import METER_BINS, METER_BLOCK, METER_GRID_CAP, METER_STATE_DTYPE, MeterParams, MeterState
+from ptss_types import MOMENT_DTYPE, LinearMoment, LinearPlanParams
 from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SPLAT, GLARE_MAX_LEVELS, GLARE_MIX, GLARE_TAIL_ENTRIES, GLARE_TILE, GlareLevel,
                         GlareParams)
 
@@ -194,6 +195,12 @@ def host_lib():
         L.ptss_probe_plan_target.restype = C.c_ulonglong
         L.ptss_probe_accumulate_linear.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LinearParams),
                                                    C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_accumulate_linear_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.POINTER(LinearParams), C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_plan_samples_linear.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(LinearParams), C.POINTER(LinearPlanParams), C.c_size_t,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(PlanInfo)]
+        L.ptss_probe_linear_plan_weight.argtypes = [C.POINTER(LinearMoment), C.POINTER(LinearParams), C.POINTER(LinearPlanParams)]
+        L.ptss_probe_linear_plan_weight.restype = C.c_uint32
         L.ptss_probe_resolve_linear.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_void_p, C.c_void_p, C.c_void_p]
         L.ptss_probe_film_positions.argtypes = [C.POINTER(FilmCamera), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_ulonglong)]
@@ -305,6 +312,10 @@ def device_lib():
         L.ptss_accumulate_paths_linear.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, C.POINTER(LinearParams), vp]
         L.ptss_resolve_linear.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), vp, vp, vp, vp]
         L.ptss_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_linear_plan_params.argtypes = [C.POINTER(LinearPlanParams)]
+        L.ptss_accumulate_paths_linear_stats.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(LinearParams), vp]
+        L.ptss_plan_samples_linear.argtypes = [vp, vp, C.c_size_t, C.POINTER(LinearParams), C.POINTER(LinearPlanParams), C.c_size_t, vp, vp, vp, vp]
+        L.ptss_linear_stats_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_default_splat_filter.argtypes = [C.POINTER(SplatFilter)]
         L.ptss_generate_rays_positions.argtypes = [vp, C.POINTER(FilmCamera), C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]
         L.ptss_splat_paths.argtypes = [vp, vp, vp, C.c_size_t, vp, C.c_int, C.c_int, C.POINTER(SplatFilter), C.POINTER(LinearParams), vp]
@@ -768,6 +779,63 @@ def _probe_resolve(name, film_dtype, film, first_pixel, count, params, linear, p
     if rc != 0:
         raise PtssError(f"{name}: {rc}")
     return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+
+# ---- adaptive sampling on the linear film (ptss_accumulate_paths_linear_stats / ptss_plan_samples_linear) ----
+def linear_plan_params(min_samples=8, max_samples=1 << 23, threshold=0.02, floor=1.0 / 64.0):
+    """A ptss_linear_plan_params; the defaults are ptss_default_linear_plan_params' (design choices, not measurements)."""
+    p = LinearPlanParams()
+    p.structSize = C.sizeof(LinearPlanParams)
+    p.minSamples, p.maxSamples, p.threshold, p.floor = int(min_samples), int(max_samples), float(threshold), float(floor)
+    return p
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def probe_accumulate_linear_stats(results, film, moments, first_pixel=0, index=None, params=None):
+    """ptss_accumulate_paths_linear_stats on the host (csrc/ptlinstats.h; the specification of the device's moments) -> (film afterwards
+    (P,) LINEAR_DTYPE or None, moments afterwards (P,) MOMENT_DTYPE, number of index entries dropped). film: (P,) LINEAR_DTYPE or (P, 4)
+    uint64, or None (moments only); moments: (P,) MOMENT_DTYPE or (P, 4) uint64. Neither is modified."""
+    r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+    n = len(r)
+    idx = _film_index(index, n)
+    m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments", copy=True)
+    f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True) if film is not None else None
+    if f is not None and len(f) != len(m):
+        raise ValueError("moments: one row per film pixel")
+    params = params if params is not None else linear_params()
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_accumulate_linear_stats(_ptr(r), _ptr(idx), int(first_pixel), n, _ptr(f), _ptr(m), len(m), C.byref(params),
+                                                       C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_accumulate_linear_stats: {rc}")
+    return (f.view(LINEAR_DTYPE).reshape(-1) if f is not None else None), m.view(MOMENT_DTYPE).reshape(-1), int(rejected.value)
+
+
+def probe_plan_samples_linear(moments, n, params=None, plan=None):
+    """ptss_plan_samples_linear on the host (csrc/ptlinstats.h; the specification of the device's plan) -> (cdf (P,) uint64, index (n,)
+    uint32, info: a dict). moments: (P,) MOMENT_DTYPE or (P, 4) uint64; params: the film's linear_params; plan: a linear_plan_params."""
+    m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments")
+    params = params if params is not None else linear_params()
+    plan = plan if plan is not None else linear_plan_params()
+    cdf, index, info = np.zeros(len(m), dtype=np.uint64), np.zeros(int(n), dtype=np.uint32), PlanInfo()
+    rc = host_lib().ptss_probe_plan_samples_linear(_ptr(m), len(m), C.byref(params), C.byref(plan), int(n), _ptr(cdf), _ptr(index), C.byref(info))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_plan_samples_linear: {rc}")
+    return cdf, index, plan_info_dict(info)
+
+
+def probe_linear_plan_weight(moment, params=None, plan=None):
+    """The weight ptss_plan_samples_linear gives one moment row (sumY, sqLo, sqHi, samples); PtssError for refused parameters."""
+    m = LinearMoment(*[int(v) for v in moment])
+    params = params if params is not None else linear_params()
+    plan = plan if plan is not None else linear_plan_params()
+    w = int(host_lib().ptss_probe_linear_plan_weight(C.byref(m), C.byref(params), C.byref(plan)))
+    if w == 0xffffffff:
+        raise PtssError("ptss_probe_linear_plan_weight: refused")
+    return w
 
 
 # ---- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat; DESIGN.md §3.30) ----
@@ -1887,6 +1955,82 @@ class Renderer:
         out = self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths_linear(self._ctx, res, idx, first, n, f, P, C.byref(params), st)),
                                LINEAR_DTYPE, np.uint64, results, film, first_pixel, index)
         return None if out is None else out[0]
+
+    # --- adaptive sampling on the linear film (ptss_accumulate_paths_linear_stats / ptss_plan_samples_linear) ------------------
+    def accumulate_paths_linear_stats(self, results, film, moments, first_pixel=0, index=None, params=None):
+        """ptss_accumulate_paths_linear_stats: accumulate_paths_linear, with the luminance moments kept as well; film may be None
+        (moments only). numpy: results (N,) PATH_RESULT_DTYPE or (N, 4) float32; film (P,) LINEAR_DTYPE or (P, 4) uint64 or None;
+        moments (P,) MOMENT_DTYPE or (P, 4) uint64 (neither modified) -> (film afterwards or None, moments afterwards (P,) MOMENT_DTYPE).
+        torch: results (N, 4) float32, film (P, 4) int64 or None, moments (P, 4) int64, both UPDATED IN PLACE, index (N,) int32 or None,
+        all on one device -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        if type(results).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            n, dev = results.shape[0], results.device
+            d_res = self._torch_ptr(results, "results", "float32", 4)
+            d_mom = self._torch_ptr(moments, "moments", "int64", 4, dev)
+            P = moments.shape[0]
+            d_film = self._torch_ptr(film, "film", "int64", 4, dev, P) if film is not None else None
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
+            _check(L.ptss_accumulate_paths_linear_stats(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, d_mom, P, C.byref(params),
+                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+        n = len(r)
+        idx = _film_index(index, n)
+        m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments", copy=True)
+        P = len(m)
+        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True) if film is not None else None
+        if f is not None and len(f) != P:
+            raise ValueError("moments: one row per film pixel")
+        if n == 0:
+            _check(L.ptss_accumulate_paths_linear_stats(self._ctx, None, None, int(first_pixel), 0, None, None, P, C.byref(params), None))
+        else:
+            self._round_trip([r, idx, f, m],
+                             lambda d: _check(L.ptss_accumulate_paths_linear_stats(self._ctx, d[0], d[1], int(first_pixel), n, d[2], d[3], P,
+                                                                                   C.byref(params), None)), read=(2, 3))
+        return (f.view(LINEAR_DTYPE).reshape(-1) if f is not None else None), m.view(MOMENT_DTYPE).reshape(-1)
+
+    def plan_samples_linear(self, moments, n, params=None, plan=None, cdf=None, index=None, info=None):
+        """ptss_plan_samples_linear: the next round's index from a linear film's moments.
+        numpy: moments (P,) MOMENT_DTYPE or (P, 4) uint64 -> (cdf (P,) uint64, index (n,) uint32, info: a dict). torch: moments (P, 4)
+        int64, cdf a (plan_cdf_entries(P),) int64 tensor, index an (n,) int32 tensor and info a (4,) int64 tensor or None, all contiguous
+        on one device, WRITTEN IN PLACE -> None, on the current stream. params: the film's linear_params; plan: a linear_plan_params."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        plan = plan if plan is not None else linear_plan_params()
+        n = int(n)
+        if type(moments).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, P = moments.device, moments.shape[0]
+            d_mom = self._torch_ptr(moments, "moments", "int64", 4)
+            d_cdf = self._torch_ptr(cdf, "cdf", "int64", 0, dev, plan_cdf_entries(P))
+            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n)
+            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(L.ptss_plan_samples_linear(self._ctx, d_mom, P, C.byref(params), C.byref(plan), n, d_cdf, d_idx, d_info, C.c_void_p(stream)))
+            return None
+        m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments")
+        P = len(m)
+        work = np.zeros(plan_cdf_entries(P), dtype=np.uint64)
+        out, found = np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
+        if n == 0:
+            _check(L.ptss_plan_samples_linear(self._ctx, None, P, C.byref(params), C.byref(plan), 0, None, None, None, None))
+        else:
+            self._round_trip([m, work, out, found],
+                             lambda d: _check(L.ptss_plan_samples_linear(self._ctx, d[0], P, C.byref(params), C.byref(plan), n, d[1], d[2], d[3],
+                                                                         None)), read=(1, 2, 3))
+        return work[:P], out, plan_info_dict(found)
+
+    def linear_stats_launches(self):
+        """ptss_linear_stats_launches: (accumulate_paths_linear_stats, plan_samples_linear calls that launched since the context was
+        created)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_linear_stats_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
 
     def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.

@@ -140,6 +140,18 @@ class LinearParams(C.Structure):   # ptss_linear_params: how a linear film count
     _fields_ = [("structSize", C.c_uint), ("scaleLog2", C.c_int), ("clampMax", C.c_float), ("exposure", C.c_float), ("reserved", C.c_uint)]
 
 
+class LinearMoment(C.Structure):   # ptss_linear_moment: the luminance moments of one linear-film pixel (y^2 kept as two sums) and their count
+    _fields_ = [("sumY", C.c_ulonglong), ("sqLo", C.c_ulonglong), ("sqHi", C.c_ulonglong), ("samples", C.c_ulonglong)]
+
+
+MOMENT_DTYPE = np.dtype([("sumY", np.uint64), ("sqLo", np.uint64), ("sqHi", np.uint64), ("samples", np.uint64)])
+
+
+class LinearPlanParams(C.Structure):   # ptss_linear_plan_params: how ptss_plan_samples_linear weighs a pixel
+    _fields_ = [("structSize", C.c_uint), ("minSamples", C.c_uint32), ("maxSamples", C.c_uint32), ("threshold", C.c_float), ("floor", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
 class FilmPosition(C.Structure):   # ptss_film_position: where a sample lies on the film, in pixels
     _fields_ = [("x", C.c_float), ("y", C.c_float)]
 

@@ -428,8 +428,8 @@ int ptss_adaptive_launches(const ptss_context* ctx, unsigned long long* out2); /
  * — 16 bytes for results, film, linear and history, 4 for index and pixels — (PTSS_EINVAL, also with n = 0 or count = 0 for the
  * parameters); the ranges ptss_accumulate_paths refuses, firstPixel + count >= 2^31 (PTSS_ERANGE). n = 0 and count = 0 return PTSS_OK.
  * ptss_linear_launches: the calls of each kind that launched since ptss_create. ptss_default_linear_params: scaleLog2 20, clampMax
- * 65536, exposure 1 — design choices, not measurements. A caller who also wants ptss_plan_samples keeps calling
- * ptss_accumulate_paths_stats on the same results: the plan is defined on display steps. */
+ * 65536, exposure 1 — design choices, not measurements. A caller who wants a sampling plan on this film keeps its moments
+ * with ptss_accumulate_paths_linear_stats and plans with ptss_plan_samples_linear (below). */
 int ptss_default_linear_params(ptss_linear_params* params);
 int ptss_accumulate_paths_linear(ptss_context* ctx, const ptss_path_result* dev_results, const uint32_t* dev_index /* may be NULL */,
                                  size_t firstPixel, size_t n, ptss_linear_entry* dev_film, size_t filmPixels, const ptss_linear_params* params,
@@ -438,6 +438,43 @@ int ptss_resolve_linear(ptss_context* ctx, const ptss_linear_entry* dev_film, si
                         ptss_history_entry* dev_linear /* may be NULL */, ptss_uchar4* dev_pixels /* may be NULL */,
                         ptss_history_entry* dev_history /* may be NULL */, void* hipStream);
 int ptss_linear_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] accumulates, [1] resolves */
+
+/* Adaptive sampling on the linear film: the film also keeps the first and second moment of its samples' luminance,
+ * exactly, and the plan spends the next round by the relative standard error of a pixel's mean luminance — a quantity that does not
+ * depend on the exposure chosen afterwards. csrc/ptlinstats.h has the arithmetic; its host build (ptss_probe_accumulate_linear_stats,
+ * ptss_probe_plan_samples_linear) is the specification and the device agrees with it byte for byte.
+ *
+ * ptss_accumulate_paths_linear_stats: ptss_accumulate_paths_linear's arguments, refusals and film bytes, and for every ray that reaches
+ * pixel p, with q_r, q_g, q_b that call's fixed-point channels: y = (54 q_r + 183 q_g + 19 q_b + 128) >> 8 (<= 2^40; the meter's
+ * luminance), dev_moments[p].sumY += y, .sqLo += y^2 & (2^40 - 1), .sqHi += y^2 >> 40, .samples += 1. All sums are unsigned 64-bit
+ * integers, below 2^64 while samples < 2^23 and wrapping beyond; they do not depend on the order of the samples, on the index or on the
+ * split of a batch into calls. dev_film may be NULL: moments only (a filtered film keeps them by home pixel beside ptss_splat_paths).
+ * Without an index: one kernel, a plain read-modify-write of the rows. With an index: runs of equal pixels inside a wave are summed on
+ * chip and the run's first lane issues four 64-bit atomics for the moment row and four for the film entry. The caller zero-fills new
+ * moments.
+ *
+ * ptss_plan_samples_linear: ptss_plan_samples over those moments. N = samples, Sy = sumY, Q = sqHi * 2^40 + sqLo: N < minSamples weighs
+ * 2^19, N >= maxSamples 0; otherwise D = max(N Q - Sy^2, 0) in 128-bit integers, r = sqrt(D) as f32 (through a 64-bit mantissa with a
+ * sticky bit when D >= 2^64), seY = r / (N sqrt N), meanY = Sy / N, rel = seY / (meanY + floor * 2^scaleLog2), every step correctly
+ * rounded f32, and the weight is rel > threshold ? min(rel * 2^18, 2^19 - 1) : 0. Running sum, targets, search, the uniform fallback,
+ * dev_cdf (ptss_plan_cdf_entries words), dev_index and dev_info are ptss_plan_samples'. Four launches, no host round trip.
+ *
+ * Both calls are asynchronous on hipStream (NULL: the context's stream), leave no trace in frame state, own no bit of
+ * ptss_launched_kernels and serve sharded contexts; ptss_linear_launches and ptss_adaptive_launches do not count them. Refused without
+ * touching the device and without counting: everything ptss_accumulate_paths_linear and ptss_plan_samples refuse about the arguments
+ * they share; null or misaligned moments (16 bytes), null plan params, a wrong structSize, minSamples 0, maxSamples outside
+ * [minSamples, 2^23], a threshold that is negative or not finite, a floor that is not finite, has floor * 2^scaleLog2 < 1 or exceeds
+ * clampMax, a non-zero reserved (PTSS_EINVAL). n = 0 returns PTSS_OK with nothing launched. ptss_default_linear_plan_params: minSamples
+ * 8, maxSamples 2^23, threshold 0.02, floor 1/64 — design choices, not measurements. ptss_linear_stats_launches: the calls of each kind
+ * that launched since ptss_create. */
+int ptss_default_linear_plan_params(ptss_linear_plan_params* params);
+int ptss_accumulate_paths_linear_stats(ptss_context* ctx, const ptss_path_result* dev_results, const uint32_t* dev_index /* may be NULL */,
+                                       size_t firstPixel, size_t n, ptss_linear_entry* dev_film /* may be NULL: moments only */,
+                                       ptss_linear_moment* dev_moments, size_t filmPixels, const ptss_linear_params* params, void* hipStream);
+int ptss_plan_samples_linear(ptss_context* ctx, const ptss_linear_moment* dev_moments, size_t filmPixels, const ptss_linear_params* params,
+                             const ptss_linear_plan_params* plan, size_t n, unsigned long long* dev_cdf, uint32_t* dev_index,
+                             ptss_plan_info* dev_info /* may be NULL */, void* hipStream);
+int ptss_linear_stats_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] accumulates, [1] plans */
 
 /* The filtered linear film: the linear film's fixed-point samples, spread over the pixels around the sample's position
  * by a box, a tent or a Gaussian pixel filter (ptss_splat_filter) whose weights are integers. Every contribution is an integer, so a

@@ -205,6 +205,18 @@ unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long lo
  * index entries >= filmPixels. PTSS_HOST_EINVAL: whatever ptss_accumulate_paths_linear refuses, alignment aside. */
 int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t* index /* may be NULL */, size_t firstPixel, size_t n,
                                  ptss_linear_entry* film, size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected);
+/* ptss_accumulate_paths_linear_stats on the host (csrc/ptlinstats.h — the very operations the kernels evaluate; this build is the
+ * specification): the same arguments over host memory, film may be NULL. PTSS_HOST_EINVAL: whatever the device call refuses, alignment
+ * aside. */
+int ptss_probe_accumulate_linear_stats(const ptss_path_result* results, const uint32_t* index /* may be NULL */, size_t firstPixel, size_t n,
+                                       ptss_linear_entry* film /* may be NULL */, ptss_linear_moment* moments, size_t filmPixels,
+                                       const ptss_linear_params* params, unsigned long long* rejected);
+/* ptss_plan_samples_linear on the host: cdf needs filmPixels entries here. ptss_probe_linear_plan_weight: the weight of one moment row,
+ * 0xffffffff for refused parameters. */
+int ptss_probe_plan_samples_linear(const ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
+                                   const ptss_linear_plan_params* plan, size_t n, unsigned long long* cdf, uint32_t* index,
+                                   ptss_plan_info* info /* may be NULL */);
+uint32_t ptss_probe_linear_plan_weight(const ptss_linear_moment* moment, const ptss_linear_params* params, const ptss_linear_plan_params* plan);
 /* ptss_resolve_linear on the host, with the LITERAL tone map (like ptss_probe_accumulate it needs no thresholds): pixels firstPixel ..
  * firstPixel + count of film into linear, pixels and history (each may be NULL). PTSS_HOST_EINVAL: whatever ptss_resolve_linear
  * refuses, alignment aside. */

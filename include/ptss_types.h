@@ -261,6 +261,27 @@ typedef struct ptss_linear_params {
     unsigned int reserved;   /* 0 */
 } ptss_linear_params;
 
+/* A pixel's luminance moments beside a linear film (ptss_accumulate_paths_linear_stats). y is the Rec. 709 luminance of a
+ * sample's fixed-point channels (at most 2^40); sumY: the sum of y; sqLo, sqHi: the sums of y^2 & (2^40 - 1) and of y^2 >> 40, kept
+ * apart because y^2 does not fit one word (the second moment is sqHi * 2^40 + sqLo); samples: how many. 32 B, 16-byte aligned access; a
+ * new film is all zero; samples < 2^23 keeps every word below 2^64. */
+typedef struct ptss_linear_moment {
+    unsigned long long sumY, sqLo, sqHi, samples;
+} ptss_linear_moment;
+
+/* How ptss_plan_samples_linear weighs a pixel (ptss.h). minSamples, maxSamples: as in ptss_plan_params; threshold >= 0,
+ * finite: the relative standard error of the pixel's mean luminance at or below which it counts as converged; floor: finite, in linear
+ * radiance, added to the mean luminance under the error so that dark pixels do not outrank everything, with floor * 2^scaleLog2 >= 1 and
+ * floor <= clampMax of the film's ptss_linear_params. */
+typedef struct ptss_linear_plan_params {
+    unsigned int structSize; /* sizeof(ptss_linear_plan_params) as the caller compiled it */
+    uint32_t minSamples;
+    uint32_t maxSamples;
+    float threshold;
+    float floor;
+    uint32_t reserved[3];    /* 0 */
+} ptss_linear_plan_params;
+
 /* Where on the film a sample lies, in pixels (ptss_generate_rays_positions): pixel (i, j) owns [i, i + 1) x [j, j + 1),
  * its centre is (i + 0.5, j + 0.5). 8 B, 8-byte aligned access. */
 typedef struct ptss_film_position {
@@ -416,6 +437,11 @@ static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g) 
 static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
                   offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
               "ptss_linear_params is five 32-bit words");
+static_assert(sizeof(ptss_linear_moment) == 32 && offsetof(ptss_linear_moment, sqLo) == 8 && offsetof(ptss_linear_moment, samples) == 24,
+              "ptss_linear_moment is two 16-byte rows");
+static_assert(sizeof(ptss_linear_plan_params) == 32 && offsetof(ptss_linear_plan_params, threshold) == 12 &&
+                  offsetof(ptss_linear_plan_params, floor) == 16 && offsetof(ptss_linear_plan_params, reserved) == 20,
+              "ptss_linear_plan_params is eight 32-bit words");
 static_assert(sizeof(ptss_film_position) == 8 && offsetof(ptss_film_position, y) == 4, "ptss_film_position is two floats");
 static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, kind) == 4 && offsetof(ptss_splat_filter, radius) == 8 &&
                   offsetof(ptss_splat_filter, alpha) == 12 && offsetof(ptss_splat_filter, reserved) == 16,
@@ -467,6 +493,11 @@ _Static_assert(sizeof(ptss_linear_entry) == 32 && offsetof(ptss_linear_entry, g)
 _Static_assert(sizeof(ptss_linear_params) == 20 && offsetof(ptss_linear_params, scaleLog2) == 4 && offsetof(ptss_linear_params, clampMax) == 8 &&
                    offsetof(ptss_linear_params, exposure) == 12 && offsetof(ptss_linear_params, reserved) == 16,
                "ptss_linear_params is five 32-bit words");
+_Static_assert(sizeof(ptss_linear_moment) == 32 && offsetof(ptss_linear_moment, sqLo) == 8 && offsetof(ptss_linear_moment, samples) == 24,
+               "ptss_linear_moment is two 16-byte rows");
+_Static_assert(sizeof(ptss_linear_plan_params) == 32 && offsetof(ptss_linear_plan_params, threshold) == 12 &&
+                   offsetof(ptss_linear_plan_params, floor) == 16 && offsetof(ptss_linear_plan_params, reserved) == 20,
+               "ptss_linear_plan_params is eight 32-bit words");
 _Static_assert(sizeof(ptss_film_position) == 8 && offsetof(ptss_film_position, y) == 4, "ptss_film_position is two floats");
 _Static_assert(sizeof(ptss_splat_filter) == 20 && offsetof(ptss_splat_filter, kind) == 4 && offsetof(ptss_splat_filter, radius) == 8 &&
                    offsetof(ptss_splat_filter, alpha) == 12 && offsetof(ptss_splat_filter, reserved) == 16,
