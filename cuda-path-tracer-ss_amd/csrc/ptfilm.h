@@ -1,5 +1,6 @@
-// ptfilm.h — what the film kernels of a path query share (ptss_film.hip, ptss_adaptive.hip, ptss_linear.hip; DESIGN.md §3.26, §3.28,
-// §3.29): the count of an index's dropped entries, the resolve of an 8-bit film entry, and the reduction that sums a wave's runs of equal
+// ptfilm.h — what the film kernels of a path query share (ptss_film.hip, ptss_adaptive.hip, ptss_linear.hip, ptss_splat.hip, ptss_meter.hip,
+// ptss_glare.hip, ptss_resolve.hip): the tail of a launch function, the count of an index's dropped
+// entries, the resolve of an 8-bit film entry, the read of a glare pyramid's entry, and the reduction that sums a wave's runs of equal
 // pixels into each run's head lane. Like the layer headers it is private to the one translation unit that includes it.
 #pragma once
 #include "ptwave.h"
@@ -9,6 +10,13 @@ namespace ptss {
 namespace {
 
 inline unsigned filmBlocksFor(uint32_t n, unsigned block) { return (n + block - 1) / block; }
+
+// the tail of a launch function: the error of the launch just enqueued, which is counted if it succeeded
+inline hipError_t counted(unsigned long long* launches) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) ++*launches;
+    return e;
+}
 
 // dropped entries of one wave, counted with one atomic: `dropped` is the lane's own verdict
 __device__ __forceinline__ void countDropped(bool dropped, unsigned long long* rejected) {
@@ -30,6 +38,12 @@ __device__ __forceinline__ void resolveEntry(uint4 e, uint32_t p, ptss_uchar4* _
         const vec3 c = ptdn::displayValue(e.x, e.y, e.z, inv);
         history[p] = float4{c.x, c.y, c.z, (float)e.w};
     }
+}
+
+// the three channels of entry e of a glare level (ptss_glare_entry: 32 B, read as two 16-byte rows)
+__device__ __forceinline__ void loadEntry(const ulonglong2* __restrict__ level, size_t e, unsigned long long* v) {
+    const ulonglong2 rg = level[2 * e], bz = level[2 * e + 1];
+    v[0] = rg.x, v[1] = rg.y, v[2] = bz.x;
 }
 
 // The segmented reduction of the scatter kernels: the lanes of a wave that hold one key side by side are summed towards the run's first

@@ -2,7 +2,7 @@
 // the luminance moments of a sample in fixed point, and the integer weight of a pixel from the relative standard error of its mean
 // luminance. PTM_HD over ptmath.h, ptlinear.h and ptmeter.h's luminance: the host build of this header (libptss_host.so,
 // ptss_probe_accumulate_linear_stats / ptss_probe_plan_samples_linear / ptss_probe_linear_plan_weight) is the specification, the kernels of
-// ptss_linstats.hip evaluate the same operations in the same order, and the two agree byte for byte. Targets, search, uniform fallback and
+// ptss_linear.hip evaluate the same operations in the same order, and the two agree byte for byte. Targets, search, uniform fallback and
 // the workspace are ptadaptive.h's, unchanged: a weight is at most 2^19 here as there.
 //
 // A sample: q = ptlin::toFixed per channel (<= 2^40), y = ptmeter::luminance(q) <= 2^40, and y^2 <= 2^80 kept carry-save as

@@ -337,9 +337,7 @@ hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint
             hipLaunchKernelGGL(statsResolveKernel, grid, block, 0, st, index, n, static_cast<const uint4*>(film), filmPixels, pixels,
                                static_cast<float4*>(history));
     }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
@@ -356,9 +354,7 @@ hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned lo
     hipLaunchKernelGGL(planDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(planIndexKernel, dim3(filmBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
-    e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchPlanSamplesLinear(hipStream_t st, const void* moments, uint32_t filmPixels, const ptss_linear_params& film,
@@ -375,9 +371,7 @@ hipError_t launchPlanSamplesLinear(hipStream_t st, const void* moments, uint32_t
     hipLaunchKernelGGL(linPlanDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(planIndexKernel, dim3(filmBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
-    e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 }  // namespace ptss

@@ -1481,28 +1481,9 @@ int ptss_accumulate_paths_linear(ptss_context* c, const ptss_path_result* dev_re
     FilmCall f;
     RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
     if (!f.go) return PTSS_OK;
-    HIP_TRY(ptss::launchLinearAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, f.filmPixels, *params,
+    HIP_TRY(ptss::launchLinearAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, nullptr, f.filmPixels, *params,
                                          c->dTotal + kFilmRejectedWord, &c->linearLaunches[0]));
     noteFilmIndex(c, dev_index, f.st);
-    return PTSS_OK;
-}
-
-int ptss_resolve_linear(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
-                        ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
-    if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
-    if (count == 0) return PTSS_OK;
-    if (!dev_film) return fail(PTSS_EINVAL, "null film with count > 0");
-    if ((((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_pixels & 3u))
-        return fail(PTSS_EINVAL, "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned");
-    if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count))
-        return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
-    const SceneImage& im = c->images[0];
-    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
-    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(ptss::launchLinearResolve(streamOf(c, hipStream), dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTableOf(im), dev_linear,
-                                      dev_pixels, dev_history, &c->linearLaunches[1]));
     return PTSS_OK;
 }
 
@@ -1513,7 +1494,7 @@ int ptss_linear_launches(const ptss_context* c, unsigned long long* out2) {
     return PTSS_OK;
 }
 
-// ---- adaptive sampling on the linear film (ptss_linstats.hip, ptss_adaptive.hip; csrc/ptlinstats.h). Like the film calls:
+// ---- adaptive sampling on the linear film (ptss_linear.hip, ptss_adaptive.hip; csrc/ptlinstats.h). Like the film calls:
 // no frame state, the caller's stream ----
 int ptss_default_linear_plan_params(ptss_linear_plan_params* p) {
     if (!p) return fail(PTSS_EINVAL, "params is null");
@@ -1538,8 +1519,8 @@ int ptss_accumulate_paths_linear_stats(ptss_context* c, const ptss_path_result* 
     FilmCall f;
     RC_TRY(filmCall(c, &f, filmPixels, "filmPixels must be below 2^31", n, bad, dev_index, firstPixel, true, hipStream));
     if (!f.go) return PTSS_OK;
-    HIP_TRY(ptss::launchLinStatsAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, dev_moments, f.filmPixels, *params,
-                                           c->dTotal + kFilmRejectedWord, &c->linStatsLaunches[0]));
+    HIP_TRY(ptss::launchLinearAccumulate(f.st, dev_results, dev_index, f.firstPixel, f.n, dev_film, dev_moments, f.filmPixels, *params,
+                                         c->dTotal + kFilmRejectedWord, &c->linStatsLaunches[0]));
     noteFilmIndex(c, dev_index, f.st);
     return PTSS_OK;
 }
@@ -1651,25 +1632,6 @@ int ptss_splat_paths_homed(ptss_context* c, const ptss_path_result* dev_results,
     return PTSS_OK;
 }
 
-int ptss_resolve_splat(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
-                       ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
-    if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
-    if (count == 0) return PTSS_OK;
-    if (!dev_film) return fail(PTSS_EINVAL, "null film with count > 0");
-    if ((((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_pixels & 3u))
-        return fail(PTSS_EINVAL, "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned");
-    if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count))
-        return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
-    const SceneImage& im = c->images[0];
-    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
-    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    HIP_TRY(ptss::launchSplatResolve(streamOf(c, hipStream), dev_film, (uint32_t)firstPixel, (uint32_t)count, *params, quantTableOf(im), dev_linear,
-                                     dev_pixels, dev_history, &c->splatLaunches[2]));
-    return PTSS_OK;
-}
-
 int ptss_splat_stats(ptss_context* c, unsigned long long* out5) {
     if (!c || !out5) return fail(PTSS_EINVAL, "null argument");
     for (int k = 0; k < 3; ++k) out5[k] = c->splatLaunches[k];
@@ -1697,13 +1659,16 @@ int ptss_default_meter_params(ptss_meter_params* p) {
 
 // What the calls over a range of a film share behind their own ctx and params checks, in ptss_resolve_linear's order: count == 0 (nothing
 // to do: PTSS_OK with go == false), the call's own verdict on its buffers (FilmCall's `badBuffers`), the range, the scene image where the
-// call reads it, device and stream. FilmCall's firstPixel and n are the range; filmPixels stays 0
-static int rangeCall(ptss_context* c, FilmCall* f, size_t firstPixel, size_t count, const char* badBuffers, bool readsImage, void* hipStream) {
+// call reads it, `writes` (a call none of whose outputs is there has nothing to do either, and does not touch the device), device and
+// stream. FilmCall's firstPixel and n are the range; filmPixels stays 0
+static int rangeCall(ptss_context* c, FilmCall* f, size_t firstPixel, size_t count, const char* badBuffers, bool readsImage, bool writes,
+                     void* hipStream) {
     if (count == 0) return PTSS_OK;
     if (badBuffers) return fail(PTSS_EINVAL, badBuffers);
     if (!fits31(firstPixel) || !fits31(count) || !fits31(firstPixel + count)) return fail(PTSS_ERANGE, "firstPixel + count must be below 2^31");
     const SceneImage& im = c->images[0];
     if (readsImage && !im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    if (!writes) return PTSS_OK;
     HIP_TRY(hipSetDevice(c->cfg.device));
     *f = FilmCall{true, streamOf(c, hipStream), (uint32_t)firstPixel, (uint32_t)count, 0u, readsImage ? quantTableOf(im) : nullptr};
     return PTSS_OK;
@@ -1715,7 +1680,7 @@ static int meterFilm(ptss_context* c, const void* dev_film, bool splat, size_t f
                       : ((uintptr_t)dev_film & 15u) || ((uintptr_t)dev_histogram & 3u) ? "film must be 16-byte aligned, dev_histogram 4-byte aligned"
                                                                                          : nullptr;
     FilmCall f;
-    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, false, hipStream));
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, false, true, hipStream));
     if (!f.go) return PTSS_OK;
     HIP_TRY(ptss::launchMeterHistogram(f.st, dev_film, splat, f.firstPixel, f.n, dev_histogram, &c->meterLaunches[0]));
     return PTSS_OK;
@@ -1739,37 +1704,6 @@ int ptss_meter_exposure(ptss_context* c, const uint32_t* dev_histogram, const pt
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(ptss::launchMeterExposure(streamOf(c, hipStream), dev_histogram, *params, *meter, dev_state, &c->meterLaunches[1]));
     return PTSS_OK;
-}
-
-static int resolveMetered(ptss_context* c, const void* dev_film, bool splat, size_t firstPixel, size_t count, const ptss_linear_params* params,
-                          const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history,
-                          void* hipStream) {
-    if (!c) return fail(PTSS_EINVAL, "ctx is null");
-    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
-    const char* bad = !dev_film || !dev_state ? "null film or state with count > 0"
-                      : (((uintptr_t)dev_film | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) || ((uintptr_t)dev_state & 7u) ||
-                              ((uintptr_t)dev_pixels & 3u)
-                          ? "film, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned"
-                          : nullptr;
-    FilmCall f;
-    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, hipStream));
-    if (!f.go) return PTSS_OK;
-    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
-    HIP_TRY(ptss::launchResolveMetered(f.st, dev_film, splat, f.firstPixel, f.n, *params, dev_state, f.quantTable, dev_linear, dev_pixels, dev_history,
-                                       &c->meterLaunches[2]));
-    return PTSS_OK;
-}
-
-int ptss_resolve_linear_metered(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
-                                const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
-                                ptss_history_entry* dev_history, void* hipStream) {
-    return resolveMetered(c, dev_film, false, firstPixel, count, params, dev_state, dev_linear, dev_pixels, dev_history, hipStream);
-}
-
-int ptss_resolve_splat_metered(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
-                               const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
-                               ptss_history_entry* dev_history, void* hipStream) {
-    return resolveMetered(c, dev_film, true, firstPixel, count, params, dev_state, dev_linear, dev_pixels, dev_history, hipStream);
 }
 
 int ptss_meter_launches(const ptss_context* c, unsigned long long* out3) {
@@ -1819,46 +1753,102 @@ int ptss_glare_build(ptss_context* c, const void* dev_film, int filmKind, int wi
     return PTSS_OK;
 }
 
-static int resolveGlare(ptss_context* c, const void* dev_film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params, int width,
-                        int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid, const ptss_meter_state* dev_state,
-                        ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
-    RC_TRY(glareArguments(c, params, glare, filmKind, width, height));
-    const char* bad = !dev_film || !dev_pyramid ? "null film or pyramid with count > 0"
+int ptss_glare_launches(const ptss_context* c, unsigned long long* out3) {
+    if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 3; ++k) out3[k] = c->glareLaunches[k];
+    return PTSS_OK;
+}
+
+// ---- the resolves of the two linear films (ptss_resolve.hip). Like the film calls: no frame state, the caller's stream ----
+// The one body behind the six, each of which has checked ctx. In this order: the film's parameters (with `glare`: glareArguments), then
+// rangeCall's checks — count == 0, the buffers, the range, the scene image, nothing to write. The buffers: `missing` is the caller's
+// verdict on the pointers it requires, `nullText` and `alignText` are its own wordings; the alignment asked of a pointer is the same in
+// every call, and a pointer a call does not have is null. With `glare` the range has to lie in the film as well, which is looked at
+// once the buffers have passed. dev_state: the metered resolves' (required there: `missing`), a glare resolve's or nullptr
+static int resolveLinearFilm(ptss_context* c, const void* dev_film, bool splat, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             const ptss_meter_state* dev_state, const ptss::GlareResolveArgs* glare, bool missing, const char* nullText,
+                             const char* alignText, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history,
+                             unsigned long long* launches, void* hipStream) {
+    if (glare) {
+        RC_TRY(glareArguments(c, params, glare->params, splat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, glare->width, glare->height));
+    } else if (const char* what = ptlin::paramsError(params)) {
+        return fail(PTSS_EINVAL, what);
+    }
+    const void* dev_pyramid = glare ? glare->pyramid : nullptr;
+    const char* bad = missing ? nullText
                       : (((uintptr_t)dev_film | (uintptr_t)dev_pyramid | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) ||
                               ((uintptr_t)dev_state & 7u) || ((uintptr_t)dev_pixels & 3u)
-                          ? "film, pyramid, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned"
+                          ? alignText
                           : nullptr;
-    const unsigned long long filmPixels = (unsigned long long)width * (unsigned long long)height;   // below 2^31
-    if (count != 0 && !bad && (firstPixel > filmPixels || count > filmPixels - firstPixel)) return fail(PTSS_ERANGE, "firstPixel + count leaves the film");
+    if (glare && count != 0 && !bad) {
+        const unsigned long long filmPixels = (unsigned long long)glare->width * (unsigned long long)glare->height;   // below 2^31
+        if (firstPixel > filmPixels || count > filmPixels - firstPixel) return fail(PTSS_ERANGE, "firstPixel + count leaves the film");
+    }
     FilmCall f;
-    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, hipStream));
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, dev_linear || dev_pixels || dev_history, hipStream));
     if (!f.go) return PTSS_OK;
-    if (!dev_linear && !dev_pixels && !dev_history) return PTSS_OK;   // nothing to write
-    HIP_TRY(ptss::launchResolveGlare(f.st, dev_film, filmKind == PTSS_GLARE_FILM_SPLAT, f.firstPixel, f.n, *params, width, height, *glare, dev_pyramid,
-                                     dev_state, f.quantTable, dev_linear, dev_pixels, dev_history, &c->glareLaunches[2]));
+    HIP_TRY(ptss::launchLinearFilmResolve(f.st, dev_film, splat, f.firstPixel, f.n, *params, dev_state, glare, f.quantTable, dev_linear, dev_pixels,
+                                          dev_history, launches));
     return PTSS_OK;
+}
+
+static const char* const kResolveAlign = "film, linear and history must be 16-byte aligned, dev_pixels 4-byte aligned";
+static const char* const kResolveMeteredAlign = "film, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned";
+static const char* const kResolveGlareAlign =
+    "film, pyramid, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned";
+
+int ptss_resolve_linear(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                        ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, false, firstPixel, count, params, nullptr, nullptr, !dev_film, "null film with count > 0", kResolveAlign,
+                             dev_linear, dev_pixels, dev_history, &c->linearLaunches[1], hipStream);
+}
+
+int ptss_resolve_splat(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                       ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, true, firstPixel, count, params, nullptr, nullptr, !dev_film, "null film with count > 0", kResolveAlign,
+                             dev_linear, dev_pixels, dev_history, &c->splatLaunches[2], hipStream);
+}
+
+int ptss_resolve_linear_metered(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                                const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                                ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, false, firstPixel, count, params, dev_state, nullptr, !dev_film || !dev_state,
+                             "null film or state with count > 0", kResolveMeteredAlign, dev_linear, dev_pixels, dev_history,
+                             &c->meterLaunches[2], hipStream);
+}
+
+int ptss_resolve_splat_metered(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                               const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
+                               ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, true, firstPixel, count, params, dev_state, nullptr, !dev_film || !dev_state,
+                             "null film or state with count > 0", kResolveMeteredAlign, dev_linear, dev_pixels, dev_history,
+                             &c->meterLaunches[2], hipStream);
 }
 
 int ptss_resolve_linear_glare(ptss_context* c, const ptss_linear_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
                               int width, int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid,
                               const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
                               ptss_history_entry* dev_history, void* hipStream) {
-    return resolveGlare(c, dev_film, PTSS_GLARE_FILM_LINEAR, firstPixel, count, params, width, height, glare, dev_pyramid, dev_state, dev_linear,
-                        dev_pixels, dev_history, hipStream);
+    const ptss::GlareResolveArgs g{width, height, glare, dev_pyramid};
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, false, firstPixel, count, params, dev_state, &g, !dev_film || !dev_pyramid,
+                             "null film or pyramid with count > 0", kResolveGlareAlign, dev_linear, dev_pixels, dev_history,
+                             &c->glareLaunches[2], hipStream);
 }
 
 int ptss_resolve_splat_glare(ptss_context* c, const ptss_splat_entry* dev_film, size_t firstPixel, size_t count, const ptss_linear_params* params,
                              int width, int height, const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid,
                              const ptss_meter_state* dev_state, ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels,
                              ptss_history_entry* dev_history, void* hipStream) {
-    return resolveGlare(c, dev_film, PTSS_GLARE_FILM_SPLAT, firstPixel, count, params, width, height, glare, dev_pyramid, dev_state, dev_linear,
-                        dev_pixels, dev_history, hipStream);
-}
-
-int ptss_glare_launches(const ptss_context* c, unsigned long long* out3) {
-    if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
-    for (int k = 0; k < 3; ++k) out3[k] = c->glareLaunches[k];
-    return PTSS_OK;
+    const ptss::GlareResolveArgs g{width, height, glare, dev_pyramid};
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    return resolveLinearFilm(c, dev_film, true, firstPixel, count, params, dev_state, &g, !dev_film || !dev_pyramid,
+                             "null film or pyramid with count > 0", kResolveGlareAlign, dev_linear, dev_pixels, dev_history,
+                             &c->glareLaunches[2], hipStream);
 }
 
 // ptss_render_features_scaled: ptss_render_features' launch for the frame of factor * width x factor * height — the tile map and the eye

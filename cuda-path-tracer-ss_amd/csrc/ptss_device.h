@@ -221,59 +221,57 @@ hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint
 hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
                              const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
                              unsigned long long* launches);
-// adaptive sampling on the linear film (ptss_linstats.hip, ptss_adaptive.hip; ptss_accumulate_paths_linear_stats / ptss_plan_samples_linear;
-// DESIGN.md §3.33). launchLinStatsAccumulate: launchLinearAccumulate's buffers and bytes, film or nullptr, plus moments = filmPixels x 32 B
-// (ptss_linear_moment). launchPlanSamplesLinear: launchPlanSamples' cdf, index and info over those moments; both params checked by the caller
-// (ptlin::paramsError, ptls::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
-hipError_t launchLinStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
-                                    void* moments, uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
-                                    unsigned long long* launches);
+// adaptive sampling on the linear film (ptss_adaptive.hip; ptss_plan_samples_linear; the moments are launchLinearAccumulate's).
+// launchPlanSamplesLinear: launchPlanSamples' cdf, index and info over moments = filmPixels x 32 B (ptss_linear_moment); both params checked
+// by the caller (ptlin::paramsError, ptls::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
 hipError_t launchPlanSamplesLinear(hipStream_t st, const void* moments, uint32_t filmPixels, const ptss_linear_params& film,
                                    const ptss_linear_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index,
                                    ptss_plan_info* info, unsigned long long* launches);
-// the linear film (ptss_linear.hip; ptss_accumulate_paths_linear / ptss_resolve_linear). launchLinearAccumulate:
-// launchFilmAccumulate's results, index and counter, film = filmPixels x 32 B (ptss_linear_entry). launchLinearResolve: pixels firstPixel ..
-// firstPixel + count of the film into linear / history (16 B per pixel) and pixels, each or nullptr (not all three). params: checked by the
-// caller (ptlin::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+// the linear film (ptss_linear.hip; ptss_accumulate_paths_linear / ptss_accumulate_paths_linear_stats).
+// launchLinearAccumulate: launchFilmAccumulate's results, index and counter, film = filmPixels x 32 B (ptss_linear_entry), moments =
+// filmPixels x 32 B (ptss_linear_moment); each of the two may be nullptr, not both. params: checked by the caller (ptlin::paramsError).
+// No bit of ptss_launched_kernels: *launches is incremented once per call that launched
 hipError_t launchLinearAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
-                                  uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
+                                  void* moments, uint32_t filmPixels, const ptss_linear_params& params, unsigned long long* rejected,
                                   unsigned long long* launches);
-hipError_t launchLinearResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                               const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
-// the filtered linear film (ptss_splat.hip; ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat). results = n x
-// 16 B, positions = n x 8 B, film = width x height x 32 B (ptss_splat_entry). launchSplatHomed: sample i is homed at pixel firstPixel + i,
-// n > 0 and firstPixel + n <= width * height. counters: two device words, samples dropped and samples clamped. filter and params: checked
-// by the caller (ptspl::filterError, ptlin::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
+// the resolves of the two linear films (ptss_resolve.hip; ptss_resolve_linear / ptss_resolve_splat, their _metered and _glare forms; DESIGN.md
+// §3.29 - §3.32): pixels firstPixel .. firstPixel + count of the film, 32 B per pixel and a ptss_splat_entry where `splat`, into linear /
+// history (16 B per pixel) and pixels, each or nullptr (not all three). state = 48 B, read, or nullptr: no exposure but params'. glare =
+// nullptr, or the film's sides, the glare's parameters and the pyramid launchGlareBuild made, read at level 1 only. params and glare:
+// checked by the caller (ptlin::paramsError, ptglare::paramsError, ptglare::sidesError). No bit of ptss_launched_kernels: *launches is
+// incremented once per call that launched
+struct GlareResolveArgs {
+    int width, height;
+    const ptss_glare_params* params;
+    const void* pyramid;
+};
+hipError_t launchLinearFilmResolve(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                                   const ptss_meter_state* state, const GlareResolveArgs* glare, const float* quantTable, void* linear,
+                                   ptss_uchar4* pixels, void* history, unsigned long long* launches);
+// the filtered linear film (ptss_splat.hip; ptss_splat_paths / ptss_splat_paths_homed). results = n x 16 B, positions = n x
+// 8 B, film = width x height x 32 B (ptss_splat_entry). launchSplatHomed: sample i is homed at pixel firstPixel + i, n > 0 and firstPixel +
+// n <= width * height. counters: two device words, samples dropped and samples clamped. filter and params: checked by the caller
+// (ptspl::filterError, ptlin::paramsError). No bit of ptss_launched_kernels: *launches is incremented once per call that launched
 hipError_t launchSplatScatter(hipStream_t st, const void* results, const void* positions, uint32_t n, void* film, int width, int height,
                               const ptss_splat_filter& filter, const ptss_linear_params& params, unsigned long long* counters,
                               unsigned long long* launches);
 hipError_t launchSplatHomed(hipStream_t st, const void* results, const void* positions, uint32_t firstPixel, uint32_t n, void* film, int width,
                             int height, const ptss_splat_filter& filter, const ptss_linear_params& params, unsigned long long* counters,
                             unsigned long long* launches);
-hipError_t launchSplatResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
-// the meter of the two linear films (ptss_meter.hip; ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure and the metered resolves;
-// DESIGN.md §3.31). film = 32 B per pixel, a ptss_splat_entry where `splat`; histogram = PTSS_METER_BINS x 4 B, added to; state = 48 B,
-// read and written by launchMeterExposure, read by launchResolveMetered, whose other arguments are launchLinearResolve's. params and
-// meter: checked by the caller (ptlin::paramsError, ptmeter::paramsError). No bit of ptss_launched_kernels: *launches is incremented once
-// per call that launched
+// the meter of the two linear films (ptss_meter.hip; ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure). film = 32 B
+// per pixel, a ptss_splat_entry where `splat`; histogram = PTSS_METER_BINS x 4 B, added to; state = 48 B, read and written by
+// launchMeterExposure. params and meter: checked by the caller (ptlin::paramsError, ptmeter::paramsError). No bit of
+// ptss_launched_kernels: *launches is incremented once per call that launched
 hipError_t launchMeterHistogram(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, uint32_t* histogram,
                                 unsigned long long* launches);
 hipError_t launchMeterExposure(hipStream_t st, const uint32_t* histogram, const ptss_linear_params& params, const ptss_meter_params& meter,
                                ptss_meter_state* state, unsigned long long* launches);
-hipError_t launchResolveMetered(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                                const ptss_meter_state* state, const float* quantTable, void* linear, ptss_uchar4* pixels, void* history,
-                                unsigned long long* launches);
-// glare for the two linear films (ptss_glare.hip; ptss_glare_build and the glare resolves). film = width x height x 32 B, a
-// ptss_splat_entry where `splat`; pyramid = the entries ptglare::layoutOf counts, 32 B each. launchGlareBuild: launches[0] is incremented
-// once when every kernel of the build launched, launches[1] by each kernel that did. launchResolveGlare: launchLinearResolve's arguments,
-// state = 48 B or nullptr, pyramid read at level 1 only; *launches is incremented. params and glare: checked by the caller
-// (ptlin::paramsError, ptglare::paramsError, ptglare::sidesError). No bit of ptss_launched_kernels
+// glare for the two linear films (ptss_glare.hip; ptss_glare_build). film = width x height x 32 B, a ptss_splat_entry where
+// `splat`; pyramid = the entries ptglare::layoutOf counts, 32 B each. launches[0] is incremented once when every kernel of the build
+// launched, launches[1] by each kernel that did. params and glare: checked by the caller (ptlin::paramsError, ptglare::paramsError,
+// ptglare::sidesError). No bit of ptss_launched_kernels
 hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int width, int height, const ptss_linear_params& params,
                             const ptss_glare_params& glare, void* pyramid, unsigned long long* launches);
-hipError_t launchResolveGlare(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                              int width, int height, const ptss_glare_params& glare, const void* pyramid, const ptss_meter_state* state,
-                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

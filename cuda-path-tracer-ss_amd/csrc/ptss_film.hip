@@ -165,9 +165,7 @@ hipError_t launchFilmRays(hipStream_t st, const ptcam::Film& film, uint32_t firs
     else
         hipLaunchKernelGGL(filmRayPositionsKernel, grid, block, 0, st, film, filmPixels, firstPixel, index, n, static_cast<uint32_t*>(rng),
                            static_cast<float4*>(rays), static_cast<float2*>(positions), rejected);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchFilmAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
@@ -186,9 +184,7 @@ hipError_t launchFilmAccumulate(hipStream_t st, const void* results, const uint3
             hipLaunchKernelGGL(filmResolveKernel, grid, block, 0, st, index, n, static_cast<const uint4*>(film), filmPixels, pixels,
                                static_cast<float4*>(history));
     }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchRayFeatures(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays,
@@ -199,9 +195,7 @@ hipError_t launchRayFeatures(hipStream_t st, const float4* sceneBlob, SceneLayou
     const auto kernel = sceneInLds ? rayFeatureKernel<true> : rayFeatureKernel<false>;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, st, sceneBlob, layout, static_cast<const float4*>(rays), defaultColor,
                        static_cast<float4*>(out), n);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 }  // namespace ptss

@@ -1,6 +1,6 @@
-// ptss_glare.hip — the kernels behind ptss_glare_build, ptss_resolve_linear_glare and ptss_resolve_splat_glare (include/ptss.h; DESIGN.md
-// §3.32): a pyramid of rounded integer averages of what a film's integer means hold above a threshold, and the resolve that adds it in
-// front of the tone map (csrc/ptglare.h has the arithmetic; its host build is the specification).
+// ptss_glare.hip — the kernels behind ptss_glare_build (include/ptss.h): a pyramid of rounded integer averages of what a
+// film's integer means hold above a threshold (csrc/ptglare.h has the arithmetic; its host build is the specification). The resolves that
+// add it in front of the tone map, ptss_resolve_linear_glare and ptss_resolve_splat_glare, are instantiations of ptss_resolve.hip's kernel.
 //
 //   glareReduceKernel      film -> d_1. One workgroup per kTile x kTile texels of level 1: the thresholded integer means of the (2 kTile + 2)^2
 //                          film pixels under them are staged in LDS, each divided once, and every thread sums its sixteen taps from there
@@ -8,7 +8,6 @@
 //   glareDownKernel        d_{k-1} -> d_k in global memory, one thread per texel; glareUpKernel: u_k = d_k + up(u_{k+1}) in place
 //   glareTailKernel        one workgroup: from the first level T whose successors and itself fit into LDS together, all remaining downs and
 //                          all their ups in one launch, barriers between the levels
-//   *ResolveGlareKernel    linearResolveKernel / splatResolveKernel plus four taps of u_1 (up(u_1) at the pixel), a state's exposure or none
 //
 // Everything is sums of integers: which kernel built a level does not show in the bytes. The one-launch-per-level form (no tail) and the
 // untiled reduce are compiled in measurement builds only (PTSS_TUNING_KNOBS); DESIGN.md §3.32 has their timings.
@@ -28,12 +27,6 @@ constexpr int kGlareTile = ptglare::kTile;
 constexpr int kGlareStage = ptglare::kStage;
 constexpr int kGlareBlock = kGlareTile * kGlareTile;   // the reduce, down and up kernels: one thread per texel of a 16 x 16 tile
 constexpr int kGlareTailBlock = ptglare::kTailBlock;
-constexpr int kGlareResolveBlock = 256;                // the glare resolves: their plain siblings' shape
-
-__device__ __forceinline__ void loadEntry(const ulonglong2* __restrict__ level, size_t e, u64* v) {
-    const ulonglong2 rg = level[2 * e], bz = level[2 * e + 1];
-    v[0] = rg.x, v[1] = rg.y, v[2] = bz.x;
-}
 
 __device__ __forceinline__ void storeEntry(ulonglong2* __restrict__ level, size_t e, const u64* v) {
     level[2 * e] = ulonglong2{v[0], v[1]};
@@ -166,50 +159,6 @@ __global__ __launch_bounds__(kGlareTailBlock) void glareTailKernel(ulonglong2* _
     }
 }
 
-// what the two glare resolves take besides their plain siblings' arguments
-struct GlareResolve {
-    int width;        // of the film
-    int cw, ch;       // level 1
-    ptglare::Rule rule;
-};
-
-template <bool Splat>
-__device__ __forceinline__ void resolveGlarePixel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count, ptlin::Scale sc,
-                                                  const GlareResolve& G, const ulonglong2* __restrict__ u1, const ptss_meter_state* __restrict__ state,
-                                                  const float* __restrict__ quantT, float4* __restrict__ linear, ptss_uchar4* __restrict__ pixels,
-                                                  float4* __restrict__ history) {
-    const uint32_t i = blockIdx.x * kGlareResolveBlock + threadIdx.x;
-    if (i >= count) return;
-    if (state) sc.exposure = state->exposure * sc.exposure;
-    const uint32_t p = firstPixel + i;
-    const int y = (int)(p / (uint32_t)G.width), x = (int)(p - (uint32_t)y * (uint32_t)G.width);
-    u64 up[3];
-    ptglare::upTexel(x, y, G.cw, G.ch, [&](int ci, int cj, u64* v) { loadEntry(u1, (size_t)cj * (size_t)G.cw + (size_t)ci, v); }, up);
-    const ulonglong2 rg = film[2 * (size_t)p], bw = film[2 * (size_t)p + 1];
-    float lin[4], hist[4];
-    uint32_t px;
-    ptglare::resolve(rg.x, rg.y, bw.x, Splat ? bw.y : (bw.y & 0xffffffffull), Splat, up, G.rule, sc, quantT, lin, &px, hist);
-    if (linear) linear[p] = float4{lin[0], lin[1], lin[2], lin[3]};
-    if (pixels) reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    if (history) history[p] = float4{hist[0], hist[1], hist[2], hist[3]};
-}
-
-__global__ __launch_bounds__(kGlareResolveBlock) void linearResolveGlareKernel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count,
-                                                                               ptlin::Scale sc, GlareResolve G, const ulonglong2* __restrict__ u1,
-                                                                               const ptss_meter_state* __restrict__ state,
-                                                                               const float* __restrict__ quantT, float4* __restrict__ linear,
-                                                                               ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    resolveGlarePixel<false>(film, firstPixel, count, sc, G, u1, state, quantT, linear, pixels, history);
-}
-
-__global__ __launch_bounds__(kGlareResolveBlock) void splatResolveGlareKernel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count,
-                                                                              ptlin::Scale sc, GlareResolve G, const ulonglong2* __restrict__ u1,
-                                                                              const ptss_meter_state* __restrict__ state,
-                                                                              const float* __restrict__ quantT, float4* __restrict__ linear,
-                                                                              ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    resolveGlarePixel<true>(film, firstPixel, count, sc, G, u1, state, quantT, linear, pixels, history);
-}
-
 static dim3 glareTiles(int w, int h) { return dim3((unsigned)((w + kGlareTile - 1) / kGlareTile), (unsigned)((h + kGlareTile - 1) / kGlareTile)); }
 
 hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int width, int height, const ptss_linear_params& params,
@@ -280,24 +229,6 @@ hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int wi
     }
     launches[1] += launched;
     if (ok) ++launches[0];
-    return e;
-}
-
-hipError_t launchResolveGlare(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                              int width, int height, const ptss_glare_params& glare, const void* pyramid, const ptss_meter_state* state,
-                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches) {
-    const GlareResolve G{width, ptglare::halfOf(width), ptglare::halfOf(height), ptglare::ruleOf(glare, params)};
-    const dim3 grid(filmBlocksFor(count, kGlareResolveBlock)), block(kGlareResolveBlock);
-    if (splat)
-        hipLaunchKernelGGL(splatResolveGlareKernel, grid, block, 0, st, static_cast<const ulonglong2*>(film), firstPixel, count, ptlin::scaleOf(params), G,
-                           static_cast<const ulonglong2*>(pyramid), state, quantTable, static_cast<float4*>(linear), pixels,
-                           static_cast<float4*>(history));
-    else
-        hipLaunchKernelGGL(linearResolveGlareKernel, grid, block, 0, st, static_cast<const ulonglong2*>(film), firstPixel, count, ptlin::scaleOf(params), G,
-                           static_cast<const ulonglong2*>(pyramid), state, quantTable, static_cast<float4*>(linear), pixels,
-                           static_cast<float4*>(history));
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
     return e;
 }
 

@@ -1,14 +1,13 @@
-// ptss_meter.hip — the kernels behind ptss_meter_linear, ptss_meter_splat, ptss_meter_exposure, ptss_resolve_linear_metered and
-// ptss_resolve_splat_metered (include/ptss.h): a luminance histogram of a linear or a filtered linear film, the exposure
-// it asks for, kept in device memory, and the two resolves reading their exposure from there (csrc/ptmeter.h has the arithmetic; its host
-// build is the specification).
+// ptss_meter.hip — the kernels behind ptss_meter_linear, ptss_meter_splat and ptss_meter_exposure (include/ptss.h): a
+// luminance histogram of a linear or a filtered linear film and the exposure it asks for, kept in device memory (csrc/ptmeter.h has the
+// arithmetic; its host build is the specification). The two resolves that read their exposure from there, ptss_resolve_linear_metered and
+// ptss_resolve_splat_metered, are instantiations of ptss_resolve.hip's kernel.
 //
 //   meterKernel            one streaming read of the film, 32 B per pixel as the two 16-byte rows the resolves read. The grid is capped
 //                          (ptmeter::kGridCap workgroups) and strides the range; a workgroup counts into 329 words of LDS and flushes its
 //                          non-zero bins with one 32-bit global atomic each — no global atomic per pixel. The counts are integers: every
 //                          form of the LDS step, every grid and every split of the range leaves the same bytes
 //   meterExposureKernel    one wave takes ptmeter::update's integer sums bin-parallel, lane 0 runs its float steps on the state in place
-//   *ResolveMeteredKernel  linearResolveKernel / splatResolveKernel with Scale.exposure = state->exposure * params.exposure
 //
 // How a wave's lanes reach the LDS bins has three forms (kFormAtomic, kFormRuns, kFormDistinct); DESIGN.md §3.31 has their timings and
 // why kMeterForm is the one the library ships. The other two are compiled in measurement builds only (PTSS_TUNING_KNOBS).
@@ -25,7 +24,6 @@ namespace ptss {
 using ptlin::u64;
 
 constexpr int kMeterBlock = ptmeter::kBlock;   // the histogram kernels: sixteen waves share one LDS histogram and one flush
-constexpr int kMeteredResolveBlock = 256;      // the metered resolves: their plain siblings' shape
 constexpr int kMeterBins = ptmeter::kBins;
 constexpr int kFormAtomic = 0;                        // a. every metered lane: one LDS atomic on its bin
 [[maybe_unused]] constexpr int kFormRuns = 1;       // b. neighbouring lanes with one bin summed first (sumRunsToHead), the run's head alone adds
@@ -121,40 +119,6 @@ __global__ __launch_bounds__(64) void meterExposureKernel(const uint32_t* __rest
     *state = s;
 }
 
-__global__ __launch_bounds__(kMeteredResolveBlock) void linearResolveMeteredKernel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count,
-                                                                          ptlin::Scale sc, const ptss_meter_state* __restrict__ state,
-                                                                          const float* __restrict__ quantT, float4* __restrict__ linear,
-                                                                          ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    const uint32_t i = blockIdx.x * kMeteredResolveBlock + threadIdx.x;
-    if (i >= count) return;
-    sc.exposure = state->exposure * sc.exposure;
-    const uint32_t p = firstPixel + i;
-    const ulonglong2 rg = film[2 * (size_t)p], bc = film[2 * (size_t)p + 1];
-    float lin[4], hist[4];
-    uint32_t px;
-    ptlin::resolve(rg.x, rg.y, bc.x, (uint32_t)bc.y, sc, quantT, lin, &px, hist);
-    if (linear) linear[p] = float4{lin[0], lin[1], lin[2], lin[3]};
-    if (pixels) reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    if (history) history[p] = float4{hist[0], hist[1], hist[2], hist[3]};
-}
-
-__global__ __launch_bounds__(kMeteredResolveBlock) void splatResolveMeteredKernel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count,
-                                                                         ptlin::Scale sc, const ptss_meter_state* __restrict__ state,
-                                                                         const float* __restrict__ quantT, float4* __restrict__ linear,
-                                                                         ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    const uint32_t i = blockIdx.x * kMeteredResolveBlock + threadIdx.x;
-    if (i >= count) return;
-    sc.exposure = state->exposure * sc.exposure;
-    const uint32_t p = firstPixel + i;
-    const ulonglong2 rg = film[2 * (size_t)p], bw = film[2 * (size_t)p + 1];
-    float lin[4], hist[4];
-    uint32_t px;
-    ptspl::resolve(rg.x, rg.y, bw.x, bw.y, sc, quantT, lin, &px, hist);
-    if (linear) linear[p] = float4{lin[0], lin[1], lin[2], lin[3]};
-    if (pixels) reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    if (history) history[p] = float4{hist[0], hist[1], hist[2], hist[3]};
-}
-
 template <int Form>
 static void launchMeterForm(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, uint32_t* histogram, unsigned cap) {
     const unsigned blocks = filmBlocksFor(count, kMeterBlock);
@@ -177,32 +141,13 @@ hipError_t launchMeterHistogram(hipStream_t st, const void* film, bool splat, ui
     else
 #endif
         launchMeterForm<kMeterForm>(st, film, splat, firstPixel, count, histogram, cap);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchMeterExposure(hipStream_t st, const uint32_t* histogram, const ptss_linear_params& params, const ptss_meter_params& meter,
                                ptss_meter_state* state, unsigned long long* launches) {
     hipLaunchKernelGGL(meterExposureKernel, dim3(1), dim3(64), 0, st, histogram, ptmeter::ruleOf(meter, params), state);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
-}
-
-hipError_t launchResolveMetered(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                                const ptss_meter_state* state, const float* quantTable, void* linear, ptss_uchar4* pixels, void* history,
-                                unsigned long long* launches) {
-    const dim3 grid(filmBlocksFor(count, kMeteredResolveBlock)), block(kMeteredResolveBlock);
-    if (splat)
-        hipLaunchKernelGGL(splatResolveMeteredKernel, grid, block, 0, st, static_cast<const ulonglong2*>(film), firstPixel, count, ptlin::scaleOf(params),
-                           state, quantTable, static_cast<float4*>(linear), pixels, static_cast<float4*>(history));
-    else
-        hipLaunchKernelGGL(linearResolveMeteredKernel, grid, block, 0, st, static_cast<const ulonglong2*>(film), firstPixel, count,
-                           ptlin::scaleOf(params), state, quantTable, static_cast<float4*>(linear), pixels, static_cast<float4*>(history));
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 }  // namespace ptss

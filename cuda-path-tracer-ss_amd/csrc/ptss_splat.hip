@@ -1,12 +1,11 @@
-// ptss_splat.hip — the kernels behind ptss_splat_paths, ptss_splat_paths_homed and ptss_resolve_splat (include/ptss.h): a
-// linear film whose samples are spread over the pixels around their position by a box, a tent or a Gaussian with integer weights
-// (csrc/ptsplat.h has the arithmetic; its host build is the specification). Every contribution is an integer, so the two forms below leave
-// the same bytes:
+// ptss_splat.hip — the kernels behind ptss_splat_paths and ptss_splat_paths_homed (include/ptss.h): a linear film whose
+// samples are spread over the pixels around their position by a box, a tent or a Gaussian with integer weights (csrc/ptsplat.h has the
+// arithmetic; its host build is the specification). ptss_resolve_splat is an instantiation of ptss_resolve.hip's kernel. Every
+// contribution is an integer, so the two forms below leave the same bytes:
 //
 //   splatScatterKernel   any positions in any order: one lane per sample walks its taps and issues four 64-bit integer atomics per tap
 //   splatHomedKernel     sample i sits in the pixel firstPixel + i: one thread per OUTPUT pixel gathers from the homes around it, staged in
 //                        LDS once per 16 x 16 tile, and does one plain read-modify-write of its entry. No atomics
-//   splatResolveKernel   a streaming pass like linearResolveKernel
 #include "ptss_device.h"
 #include "ptfilm.h"
 #include "ptsplat.h"
@@ -146,31 +145,13 @@ __global__ __launch_bounds__(kSplatBlock) void splatHomedKernel(const float4* __
     e[1] = bw;
 }
 
-// one streaming pass over pixels firstPixel .. firstPixel + count; each output may be null
-__global__ __launch_bounds__(kSplatBlock) void splatResolveKernel(const ulonglong2* __restrict__ film, uint32_t firstPixel, uint32_t count,
-                                                                   ptlin::Scale sc, const float* __restrict__ quantT, float4* __restrict__ linear,
-                                                                   ptss_uchar4* __restrict__ pixels, float4* __restrict__ history) {
-    const uint32_t i = blockIdx.x * kSplatBlock + threadIdx.x;
-    if (i >= count) return;
-    const uint32_t p = firstPixel + i;
-    const ulonglong2 rg = film[2 * (size_t)p], bw = film[2 * (size_t)p + 1];
-    float lin[4], hist[4];
-    uint32_t px;
-    ptspl::resolve(rg.x, rg.y, bw.x, bw.y, sc, quantT, lin, &px, hist);
-    if (linear) linear[p] = float4{lin[0], lin[1], lin[2], lin[3]};
-    if (pixels) reinterpret_cast<uint32_t*>(pixels)[p] = px;   // uchar4 {x, y, z, w = 255}
-    if (history) history[p] = float4{hist[0], hist[1], hist[2], hist[3]};
-}
-
 hipError_t launchSplatScatter(hipStream_t st, const void* results, const void* positions, uint32_t n, void* film, int width, int height,
                               const ptss_splat_filter& filter, const ptss_linear_params& params, unsigned long long* counters,
                               unsigned long long* launches) {
     hipLaunchKernelGGL(splatScatterKernel, dim3(filmBlocksFor(n, kSplatBlock)), dim3(kSplatBlock), 0, st, static_cast<const float4*>(results),
                        static_cast<const float2*>(positions), n, static_cast<u64*>(film), width, height, ptspl::filterOf(filter),
                        ptlin::scaleOf(params), counters);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 hipError_t launchSplatHomed(hipStream_t st, const void* results, const void* positions, uint32_t firstPixel, uint32_t n, void* film, int width,
@@ -182,18 +163,7 @@ hipError_t launchSplatHomed(hipStream_t st, const void* results, const void* pos
     const dim3 grid((unsigned)((width + kSplatTile - 1) / kSplatTile), (unsigned)((rowHi - rowLo + kSplatTile) / kSplatTile));
     hipLaunchKernelGGL(splatHomedKernel, grid, dim3(kSplatBlock), 0, st, static_cast<const float4*>(results), static_cast<const float2*>(positions),
                        firstPixel, n, static_cast<ulonglong2*>(film), width, height, rowLo, rowHi, F, ptlin::scaleOf(params), counters);
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
-}
-
-hipError_t launchSplatResolve(hipStream_t st, const void* film, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
-                              const float* quantTable, void* linear, ptss_uchar4* pixels, void* history, unsigned long long* launches) {
-    hipLaunchKernelGGL(splatResolveKernel, dim3(filmBlocksFor(count, kSplatBlock)), dim3(kSplatBlock), 0, st, static_cast<const ulonglong2*>(film),
-                       firstPixel, count, ptlin::scaleOf(params), quantTable, static_cast<float4*>(linear), pixels, static_cast<float4*>(history));
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) ++*launches;
-    return e;
+    return counted(launches);
 }
 
 }  // namespace ptss

@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""tools/isa_compare.py before.s after.s — compares the kernels of two gfx950 assembly dumps of one csrc/*.hip file (ptss_kernels.hip:
+"""tools/isa_compare.py before.s after.s [pairs.txt] — compares the kernels of two gfx950 assembly dumps of one csrc/*.hip file (ptss_kernels.hip:
 the kernels and launches, compiled as one translation unit over the layer headers ptwave.h .. ptshade.h; or one of the short kernel
 files), made by hipcc with the shipped flags and --cuda-device-only -S (tools/isa_dump.sh has the command line), instruction by
 instruction, after normalising symbol, label and comment text and dropping directives. Prints the summary kept as
-profiles/*/isa_compare.txt."""
+profiles/*/isa_compare.txt.
+
+Kernels are paired by mangled name. pairs.txt, for a change that renames kernels or moves them between files (feed it the concatenated
+dumps of the files concerned): lines of `old-name-substring new-name-substring`. A kernel missing after whose name holds the first is
+compared against the new kernel whose name holds the second; each side of a pair must name exactly one kernel."""
 import re
 import sys
 
@@ -47,6 +51,22 @@ def main():
           f"{len(differ)} differ, {len(missing)} missing; {len(after)} kernels after ({len(new)} new)")
     for k in differ:
         print(f"differs: {k} {len(before[k])} -> {len(after[k])} instructions")
+    if len(sys.argv) > 3:
+        pairs = [line.split() for line in open(sys.argv[3]) if line.strip() and not line.startswith("#")]
+        moved_same = 0
+        for old, successor in pairs:
+            olds, news = [k for k in missing if old in k], [k for k in new if successor in k]
+            if len(olds) != 1 or len(news) != 1:
+                print(f"pair {old} {successor}: {len(olds)} missing and {len(news)} new kernels match, one of each wanted")
+                continue
+            missing.remove(olds[0])
+            new.remove(news[0])
+            if before[olds[0]] == after[news[0]]:
+                moved_same += 1
+                print(f"moved, identical: {olds[0]} -> {news[0]}")
+            else:
+                print(f"moved, differs: {olds[0]} -> {news[0]} {len(before[olds[0]])} -> {len(after[news[0]])} instructions")
+        print(f"{len(pairs)} pairs: {moved_same} moved kernels identical; {len(missing)} kernels without a successor, {len(new)} without a predecessor")
     for k in missing:
         print(f"missing: {k}")
     for k in new:
