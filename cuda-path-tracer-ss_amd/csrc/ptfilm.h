@@ -1,7 +1,7 @@
 // ptfilm.h — what the film kernels of a path query share (ptss_film.hip, ptss_adaptive.hip, ptss_linear.hip, ptss_splat.hip, ptss_meter.hip,
 // ptss_glare.hip, ptss_resolve.hip): the tail of a launch function, the count of an index's dropped
-// entries, the resolve of an 8-bit film entry, the read of a glare pyramid's entry, and the reduction that sums a wave's runs of equal
-// pixels into each run's head lane. Like the layer headers it is private to the one translation unit that includes it.
+// entries, the resolve of an 8-bit film entry, the read of a glare pyramid's entry, the reduction that sums a wave's runs of equal
+// pixels into each run's head lane, and a wave's sum and inclusive scan. Like the layer headers it is private to the one translation unit that includes it.
 #pragma once
 #include "ptwave.h"
 #include "ptdenoise.h"
@@ -61,6 +61,24 @@ __device__ __forceinline__ bool sumRunsToHead(uint32_t key, Step step) {
 #pragma unroll
     for (uint32_t d = 1u; d < 64u; d <<= 1) step(d, lane + d < 64u && (above & ((1ull << d) - 1ull)) == 0ull);
     return head;
+}
+
+// the sum of v over the lanes of a wave, in every lane
+__device__ __forceinline__ uint32_t waveSum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+// inclusive sum over the lanes of a wave: lane `lane` gets the sum of lanes 0 .. lane (Word: unsigned, 32 or 64 bits)
+template <class Word>
+__device__ __forceinline__ Word waveScan(Word v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const Word o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
 }
 
 }  // namespace

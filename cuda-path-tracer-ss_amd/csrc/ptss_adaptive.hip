@@ -6,9 +6,10 @@
 // resolveEntry: csrc/ptfilm.h). With an index, the lanes of a wave that hold one pixel side by side — a plan's index is sorted, so all
 // of them do — are summed on chip first (ptfilm.h sumRunsToHead) and the run's head lane alone issues the atomics.
 //
-// The scan is reduce / scan of the tile sums / downsweep: three launches, no workgroup waits for another. The weight is computed inside
-// both loads; no weight array exists. ptss_plan_samples_linear runs the same scan over the linear film's moments: its
-// reduce and downsweep stand beside the others, the tile sums and the index kernel are shared.
+// The plan is one scan with two weight sources: reduce / scan of the tile sums / downsweep — three launches, no workgroup waits for
+// another — and the index. The weight is computed inside both loads; no weight array exists. PlanArgs takes it from the 8-bit film and
+// its moments (ptss_plan_samples), LinPlanArgs from the linear film's moments (ptss_plan_samples_linear; csrc/ptlinstats.h; DESIGN.md
+// §3.33): the reduce and the downsweep are templates on the two, the tile sums and the index kernel never see a weight.
 #include "ptss_device.h"
 #include "ptadaptive.h"
 #include "ptfilm.h"
@@ -97,40 +98,39 @@ __global__ __launch_bounds__(kStatsBlock) void statsResolveKernel(const uint32_t
 }
 
 // ---- the plan ------------------------------------------------------------------------------------------------------------------------------
+// What a plan reads, and the weight of pixel p < filmPixels from it (a weight is at most 2^19 in both; `kind`: ptad::kActive ..)
 struct PlanArgs {
     const uint4* film;
     const u64* moments;
     uint32_t filmPixels;
     uint32_t minSamples, maxSamples;
     float threshold;
+    __device__ __forceinline__ uint32_t weight(uint32_t p, uint32_t* kind) const {
+        const uint4 e = film[p];
+        return ptad::weight(e.x, e.y, e.z, e.w, moments[p], minSamples, maxSamples, threshold, kind);
+    }
+};
+
+struct LinPlanArgs {
+    const ulonglong2* moments;   // a row as the two 16-byte halves it is read in: {sumY, sqLo}, {sqHi, samples}
+    uint32_t filmPixels;
+    ptls::Rule rule;
+    __device__ __forceinline__ uint32_t weight(uint32_t p, uint32_t* kind) const {
+        const ulonglong2 ys = moments[2 * (size_t)p], hn = moments[2 * (size_t)p + 1];
+        return ptls::weight(ys.x, ys.y, hn.x, hn.y, rule, kind);
+    }
 };
 
 // the weight of pixel p (0 beyond the film), its kind added to the three counters
-__device__ __forceinline__ uint32_t loadWeight(const PlanArgs& a, uint32_t p, uint32_t& active, uint32_t& unsampled, uint32_t& capped) {
+template <class Args>
+__device__ __forceinline__ uint32_t loadWeight(const Args& a, uint32_t p, uint32_t& active, uint32_t& unsampled, uint32_t& capped) {
     if (p >= a.filmPixels) return 0u;
-    const uint4 e = a.film[p];
     uint32_t kind;
-    const uint32_t w = ptad::weight(e.x, e.y, e.z, e.w, a.moments[p], a.minSamples, a.maxSamples, a.threshold, &kind);
+    const uint32_t w = a.weight(p, &kind);
     active += kind & ptad::kActive ? 1u : 0u;
     unsampled += kind & ptad::kUnsampled ? 1u : 0u;
     capped += kind & ptad::kCapped ? 1u : 0u;
     return w;
-}
-
-__device__ __forceinline__ uint32_t waveSum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
-    return v;
-}
-
-// inclusive sum over the lanes of a wave
-__device__ __forceinline__ uint32_t waveScan(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (uint32_t d = 1u; d < 64u; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
 }
 
 // pixel k of lane `lane` of wave `wave` of tile `tile`: a wave owns 512 consecutive pixels, a round of it 64
@@ -139,7 +139,8 @@ __device__ __forceinline__ uint32_t scanPixel(uint32_t tile, uint32_t wave, uint
 }
 
 // step 1: the sum of a tile's weights (at most 2048 * 2^19 = 2^30) and its three counts -> work[3 tile .. 3 tile + 2]
-__global__ __launch_bounds__(kScanBlock) void planReduceKernel(PlanArgs a, u64* __restrict__ work) {
+template <class Args>
+__global__ __launch_bounds__(kScanBlock) void planReduceKernel(Args a, u64* __restrict__ work) {
     __shared__ uint32_t part[kScanWaves][4];
     const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
     uint32_t sum = 0u, active = 0u, unsampled = 0u, capped = 0u;
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(kSumsBlock) void planTileSumsKernel(u64* __restrict
             unsampled += w[1] >> 32;
             capped += w[2];
         }
-        u64 v = own;   // inclusive over the wave
+        u64 v = own;   // inclusive over the wave (written out: through ptfilm.h's waveScan the same instructions come out in another order)
 #pragma unroll
         for (uint32_t d = 1u; d < 64u; d <<= 1) {
             const u64 o = (u64)__shfl_up((long long)v, d, 64);
@@ -220,7 +221,8 @@ __global__ __launch_bounds__(kSumsBlock) void planTileSumsKernel(u64* __restrict
 }
 
 // step 3: the weights again, scanned inside the tile (32-bit: a tile's sum is at most 2^30) on top of the sum of the tiles in front
-__global__ __launch_bounds__(kScanBlock) void planDownsweepKernel(PlanArgs a, const u64* __restrict__ work, u64* __restrict__ cdf) {
+template <class Args>
+__global__ __launch_bounds__(kScanBlock) void planDownsweepKernel(Args a, const u64* __restrict__ work, u64* __restrict__ cdf) {
     __shared__ uint32_t waveTotal[kScanWaves];
     const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
     uint32_t incl[kScanPerLane];
@@ -251,76 +253,6 @@ __global__ __launch_bounds__(kStatsBlock) void planIndexKernel(const u64* __rest
                              : ptad::pixelOf(cdf, filmPixels, ptad::target((u64)i, (u64)n, total));
 }
 
-// ---- the plan on the linear film's moments (ptss_plan_samples_linear; csrc/ptlinstats.h) -----------------------------------
-// planReduceKernel and planDownsweepKernel with ptls::weight inside both loads: the same tile shape, the same workspace, the same sums (a
-// weight is at most 2^19 here too), so planTileSumsKernel and planIndexKernel serve both plans as they are.
-struct LinPlanArgs {
-    const ulonglong2* moments;   // a row as the two 16-byte halves it is read in: {sumY, sqLo}, {sqHi, samples}
-    uint32_t filmPixels;
-    ptls::Rule rule;
-};
-
-__device__ __forceinline__ uint32_t loadLinWeight(const LinPlanArgs& a, uint32_t p, uint32_t& active, uint32_t& unsampled, uint32_t& capped) {
-    if (p >= a.filmPixels) return 0u;
-    const ulonglong2 ys = a.moments[2 * (size_t)p], hn = a.moments[2 * (size_t)p + 1];
-    uint32_t kind;
-    const uint32_t w = ptls::weight(ys.x, ys.y, hn.x, hn.y, a.rule, &kind);
-    active += kind & ptad::kActive ? 1u : 0u;
-    unsampled += kind & ptad::kUnsampled ? 1u : 0u;
-    capped += kind & ptad::kCapped ? 1u : 0u;
-    return w;
-}
-
-__global__ __launch_bounds__(kScanBlock) void linPlanReduceKernel(LinPlanArgs a, u64* __restrict__ work) {
-    __shared__ uint32_t part[kScanWaves][4];
-    const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
-    uint32_t sum = 0u, active = 0u, unsampled = 0u, capped = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) sum += loadLinWeight(a, scanPixel(blockIdx.x, wave, k, lane), active, unsampled, capped);
-    sum = waveSum(sum);
-    active = waveSum(active);
-    unsampled = waveSum(unsampled);
-    capped = waveSum(capped);
-    if (lane == 0u) {
-        part[wave][0] = sum;
-        part[wave][1] = active;
-        part[wave][2] = unsampled;
-        part[wave][3] = capped;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint32_t t[4] = {0u, 0u, 0u, 0u};
-        for (int w = 0; w < kScanWaves; ++w)
-            for (int c = 0; c < 4; ++c) t[c] += part[w][c];
-        u64* out = work + (size_t)ptad::kWorkspacePerTile * blockIdx.x;
-        out[0] = (u64)t[0];
-        out[1] = (u64)t[1] | ((u64)t[2] << 32);
-        out[2] = (u64)t[3];
-    }
-}
-
-__global__ __launch_bounds__(kScanBlock) void linPlanDownsweepKernel(LinPlanArgs a, const u64* __restrict__ work, u64* __restrict__ cdf) {
-    __shared__ uint32_t waveTotal[kScanWaves];
-    const uint32_t lane = laneId(), wave = threadIdx.x / 64u;
-    uint32_t incl[kScanPerLane];
-    uint32_t running = 0u, unused0 = 0u, unused1 = 0u, unused2 = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) {
-        const uint32_t w = loadLinWeight(a, scanPixel(blockIdx.x, wave, k, lane), unused0, unused1, unused2);
-        incl[k] = running + waveScan(w, lane);
-        running = (uint32_t)__shfl((int)incl[k], 63, 64);   // the wave's sum so far
-    }
-    if (lane == 0u) waveTotal[wave] = running;
-    __syncthreads();
-    u64 front = work[(size_t)ptad::kWorkspacePerTile * blockIdx.x];
-    for (uint32_t k = 0u; k < wave; ++k) front += (u64)waveTotal[k];
-#pragma unroll
-    for (uint32_t k = 0; k < (uint32_t)kScanPerLane; ++k) {
-        const uint32_t p = scanPixel(blockIdx.x, wave, k, lane);
-        if (p < a.filmPixels) cdf[p] = front + (u64)incl[k];
-    }
-}
-
 hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint32_t* index, uint32_t firstPixel, uint32_t n, void* film,
                                  unsigned long long* moments, uint32_t filmPixels, ptss_uchar4* pixels, void* history, const float* quantTable,
                                  unsigned long long* rejected, unsigned long long* launches) {
@@ -340,38 +272,35 @@ hipError_t launchStatsAccumulate(hipStream_t st, const void* results, const uint
     return counted(launches);
 }
 
-hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
-                             const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
+// the four launches of a plan; `a` says where the weights come from
+template <class Args>
+static hipError_t launchPlan(hipStream_t st, const Args& a, uint32_t filmPixels, uint32_t n, u64* cdf, uint32_t* index, ptss_plan_info* info,
                              unsigned long long* launches) {
-    const PlanArgs a{static_cast<const uint4*>(film), moments, filmPixels, params.minSamples, params.maxSamples, params.threshold};
     const uint32_t tiles = (uint32_t)ptad::scanTiles(filmPixels);
     u64* work = cdf + filmPixels;   // the entries behind the film's own: kWorkspacePerTile words per tile
-    hipLaunchKernelGGL(planReduceKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, work);
+    hipLaunchKernelGGL(planReduceKernel<Args>, dim3(tiles), dim3(kScanBlock), 0, st, a, work);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(planTileSumsKernel, dim3(1), dim3(kSumsBlock), 0, st, work, tiles, info);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(planDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
+    hipLaunchKernelGGL(planDownsweepKernel<Args>, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(planIndexKernel, dim3(filmBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
     return counted(launches);
+}
+
+hipError_t launchPlanSamples(hipStream_t st, const void* film, const unsigned long long* moments, uint32_t filmPixels,
+                             const ptss_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info,
+                             unsigned long long* launches) {
+    const PlanArgs a{static_cast<const uint4*>(film), moments, filmPixels, params.minSamples, params.maxSamples, params.threshold};
+    return launchPlan(st, a, filmPixels, n, cdf, index, info, launches);
 }
 
 hipError_t launchPlanSamplesLinear(hipStream_t st, const void* moments, uint32_t filmPixels, const ptss_linear_params& film,
                                    const ptss_linear_plan_params& params, uint32_t n, unsigned long long* cdf, uint32_t* index,
                                    ptss_plan_info* info, unsigned long long* launches) {
     const LinPlanArgs a{static_cast<const ulonglong2*>(moments), filmPixels, ptls::ruleOf(params, film)};
-    const uint32_t tiles = (uint32_t)ptad::scanTiles(filmPixels);
-    u64* work = cdf + filmPixels;   // the entries behind the film's own: kWorkspacePerTile words per tile
-    hipLaunchKernelGGL(linPlanReduceKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, work);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(planTileSumsKernel, dim3(1), dim3(kSumsBlock), 0, st, work, tiles, info);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(linPlanDownsweepKernel, dim3(tiles), dim3(kScanBlock), 0, st, a, static_cast<const u64*>(work), cdf);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(planIndexKernel, dim3(filmBlocksFor(n, kStatsBlock)), dim3(kStatsBlock), 0, st, static_cast<const u64*>(cdf), filmPixels, n, index);
-    return counted(launches);
+    return launchPlan(st, a, filmPixels, n, cdf, index, info, launches);
 }
 
 }  // namespace ptss

@@ -1434,21 +1434,31 @@ int ptss_plan_cdf_entries(size_t filmPixels, size_t* entries) {
     return PTSS_OK;
 }
 
+// What the two plan calls share behind their own ctx and params checks, in this order: the film's size, n, n == 0 (nothing to do: PTSS_OK
+// with go == false), the call's own verdict on its buffers (FilmCall's `badBuffers`), device and stream. FilmCall's firstPixel stays 0
+static int planCall(ptss_context* c, FilmCall* f, size_t filmPixels, size_t n, const char* badBuffers, void* hipStream) {
+    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (badBuffers) return fail(PTSS_EINVAL, badBuffers);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    *f = FilmCall{true, streamOf(c, hipStream), 0u, (uint32_t)n, (uint32_t)filmPixels, nullptr};
+    return PTSS_OK;
+}
+
 int ptss_plan_samples(ptss_context* c, const ptss_film_entry* dev_film, const unsigned long long* dev_moments, size_t filmPixels,
                       const ptss_plan_params* params, size_t n, unsigned long long* dev_cdf, uint32_t* dev_index, ptss_plan_info* dev_info,
                       void* hipStream) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (const char* what = ptad::paramsError(params)) return fail(PTSS_EINVAL, what);
-    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
-    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
-    if (n == 0) return PTSS_OK;
-    if (!dev_film || !dev_moments || !dev_cdf || !dev_index) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if (((uintptr_t)dev_film & 15u) || (((uintptr_t)dev_moments | (uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u))
-        return fail(PTSS_EINVAL, "film must be 16-byte aligned, dev_moments, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = streamOf(c, hipStream);
-    HIP_TRY(ptss::launchPlanSamples(st, dev_film, dev_moments, (uint32_t)filmPixels, *params, (uint32_t)n, dev_cdf, dev_index, dev_info,
-                                    &c->adaptiveLaunches[1]));
+    const char* bad = !dev_film || !dev_moments || !dev_cdf || !dev_index ? kNullBuffer
+                      : ((uintptr_t)dev_film & 15u) || (((uintptr_t)dev_moments | (uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u)
+                          ? "film must be 16-byte aligned, dev_moments, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(planCall(c, &f, filmPixels, n, bad, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchPlanSamples(f.st, dev_film, dev_moments, f.filmPixels, *params, f.n, dev_cdf, dev_index, dev_info, &c->adaptiveLaunches[1]));
     return PTSS_OK;
 }
 
@@ -1531,16 +1541,14 @@ int ptss_plan_samples_linear(ptss_context* c, const ptss_linear_moment* dev_mome
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
     if (const char* what = ptls::paramsError(plan, params)) return fail(PTSS_EINVAL, what);
-    if (filmPixels == 0 || !fits31(filmPixels)) return fail(PTSS_ERANGE, "filmPixels must be in [1, 2^31)");
-    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
-    if (n == 0) return PTSS_OK;
-    if (!dev_moments || !dev_cdf || !dev_index) return fail(PTSS_EINVAL, "null buffer with n > 0");
-    if (((uintptr_t)dev_moments & 15u) || (((uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u))
-        return fail(PTSS_EINVAL, "moments must be 16-byte aligned, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned");
-    HIP_TRY(hipSetDevice(c->cfg.device));
-    hipStream_t st = streamOf(c, hipStream);
-    HIP_TRY(ptss::launchPlanSamplesLinear(st, dev_moments, (uint32_t)filmPixels, *params, *plan, (uint32_t)n, dev_cdf, dev_index, dev_info,
-                                          &c->linStatsLaunches[1]));
+    const char* bad = !dev_moments || !dev_cdf || !dev_index ? kNullBuffer
+                      : ((uintptr_t)dev_moments & 15u) || (((uintptr_t)dev_cdf | (uintptr_t)dev_info) & 7u) || ((uintptr_t)dev_index & 3u)
+                          ? "moments must be 16-byte aligned, dev_cdf and dev_info 8-byte, dev_index 4-byte aligned"
+                          : nullptr;
+    FilmCall f;
+    RC_TRY(planCall(c, &f, filmPixels, n, bad, hipStream));
+    if (!f.go) return PTSS_OK;
+    HIP_TRY(ptss::launchPlanSamplesLinear(f.st, dev_moments, f.filmPixels, *params, *plan, f.n, dev_cdf, dev_index, dev_info, &c->linStatsLaunches[1]));
     return PTSS_OK;
 }
 

@@ -97,12 +97,7 @@ __global__ __launch_bounds__(64) void meterExposureKernel(const uint32_t* __rest
         mine[k] = b < kMeterBins ? (u64)histogram[b] : 0ull;
         local += mine[k];
     }
-    u64 upTo = local;   // the counts of this lane's bins and of every lane below
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 below = (u64)__shfl_up((long long)upTo, d, 64);
-        if (lane >= d) upTo += below;
-    }
+    const u64 upTo = waveScan(local, (uint32_t)lane);   // the counts of this lane's bins and of every lane below
     const u64 T = (u64)__shfl((long long)upTo, 63, 64);
     const u64 lo = ptmeter::lowRank(T, rule), hi = ptmeter::highRank(T, rule);
     u64 before = upTo - local, sumLog = 0ull;

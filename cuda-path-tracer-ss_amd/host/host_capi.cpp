@@ -58,6 +58,27 @@ void triangleForm(const float* t, const float* o3, const float* d3, float limit,
     out[4] = b2;
     out[5] = h.det;
 }
+
+// The plan of ptss_plan_samples and ptss_plan_samples_linear behind their argument checks (csrc/ptadaptive.h): the running sums of
+// weight(p, &kind) over the film, the counts of the kinds, and the index under n evenly spaced targets
+template <class Weight>
+void planSamples(size_t filmPixels, size_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info, Weight weight) {
+    ptss_plan_info found{};
+    unsigned long long sum = 0;
+    for (size_t p = 0; p < filmPixels; ++p) {
+        uint32_t kind;
+        sum += weight(p, &kind);
+        cdf[p] = sum;
+        found.activePixels += (kind & ptad::kActive) ? 1u : 0u;
+        found.unsampledPixels += (kind & ptad::kUnsampled) ? 1u : 0u;
+        found.cappedPixels += (kind & ptad::kCapped) ? 1u : 0u;
+    }
+    found.totalWeight = sum;
+    found.uniform = sum == 0ull ? 1u : 0u;
+    for (size_t i = 0; i < n; ++i)
+        index[i] = sum == 0ull ? ptad::uniformPixel(i, n, filmPixels) : ptad::pixelOf(cdf, (uint32_t)filmPixels, ptad::target(i, n, sum));
+    if (info) *info = found;
+}
 }  // namespace
 
 extern "C" {
@@ -662,22 +683,9 @@ int ptss_probe_plan_samples(const ptss_film_entry* film, const unsigned long lon
     if (filmPixels == 0 || filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
     if (n == 0) return PTSS_HOST_OK;
     if (!film || !moments || !cdf || !index) return PTSS_HOST_EINVAL;
-    ptss_plan_info found{};
-    unsigned long long sum = 0;
-    for (size_t p = 0; p < filmPixels; ++p) {
-        uint32_t kind;
-        sum += ptad::weight(film[p].r, film[p].g, film[p].b, film[p].samples, moments[p], params->minSamples, params->maxSamples,
-                            params->threshold, &kind);
-        cdf[p] = sum;
-        found.activePixels += (kind & ptad::kActive) ? 1u : 0u;
-        found.unsampledPixels += (kind & ptad::kUnsampled) ? 1u : 0u;
-        found.cappedPixels += (kind & ptad::kCapped) ? 1u : 0u;
-    }
-    found.totalWeight = sum;
-    found.uniform = sum == 0ull ? 1u : 0u;
-    for (size_t i = 0; i < n; ++i)
-        index[i] = sum == 0ull ? ptad::uniformPixel(i, n, filmPixels) : ptad::pixelOf(cdf, (uint32_t)filmPixels, ptad::target(i, n, sum));
-    if (info) *info = found;
+    planSamples(filmPixels, n, cdf, index, info, [&](size_t p, uint32_t* kind) {
+        return ptad::weight(film[p].r, film[p].g, film[p].b, film[p].samples, moments[p], params->minSamples, params->maxSamples, params->threshold, kind);
+    });
     return PTSS_HOST_OK;
 }
 
@@ -690,11 +698,12 @@ unsigned long long ptss_probe_plan_target(unsigned long long i, unsigned long lo
     return n ? ptad::target(i, n, total) : 0ull;
 }
 
-int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
-                                 size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected) {
-    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
+// ptss_probe_accumulate_linear and ptss_probe_accumulate_linear_stats: the film, the moments or both take the samples (at least one is
+// there: the callers have checked), as the device's linearAccumulateKernel<kFilm, kMoments> does
+static int probeAccumulateLinear(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
+                                 ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected) {
     if (filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
-    if (n > 0 && (!results || !film)) return PTSS_HOST_EINVAL;
+    if (n > 0 && !results) return PTSS_HOST_EINVAL;
     if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
     const ptlin::Scale sc = ptlin::scaleOf(*params);
     unsigned long long dropped = 0;
@@ -706,38 +715,13 @@ int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t
         }
         ptlin::u64 q[3];
         const uint32_t flag = ptlin::sampleToFixed(results[i].radiance.x, results[i].radiance.y, results[i].radiance.z, sc, q);
-        film[p].r += q[0];
-        film[p].g += q[1];
-        film[p].b += q[2];
-        film[p].samples += 1u;
-        film[p].clamped += flag;
-    }
-    if (rejected) *rejected = dropped;
-    return PTSS_HOST_OK;
-}
-
-int ptss_probe_accumulate_linear_stats(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
-                                       ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
-                                       unsigned long long* rejected) {
-    if (ptlin::paramsError(params)) return PTSS_HOST_EINVAL;
-    if (filmPixels >= (size_t(1) << 31) || n >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
-    if (n > 0 && (!results || !moments)) return PTSS_HOST_EINVAL;
-    if (!index && (firstPixel > filmPixels || n > filmPixels - firstPixel)) return PTSS_HOST_EINVAL;
-    const ptlin::Scale sc = ptlin::scaleOf(*params);
-    unsigned long long dropped = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const size_t p = index ? index[i] : firstPixel + i;
-        if (p >= filmPixels) {
-            ++dropped;
-            continue;
+        if (moments) {
+            const ptls::Sample s = ptls::sampleOf(q[0], q[1], q[2]);
+            moments[p].sumY += s.y;
+            moments[p].sqLo += s.lo;
+            moments[p].sqHi += s.hi;
+            moments[p].samples += 1ull;
         }
-        ptlin::u64 q[3];
-        const uint32_t flag = ptlin::sampleToFixed(results[i].radiance.x, results[i].radiance.y, results[i].radiance.z, sc, q);
-        const ptls::Sample s = ptls::sampleOf(q[0], q[1], q[2]);
-        moments[p].sumY += s.y;
-        moments[p].sqLo += s.lo;
-        moments[p].sqHi += s.hi;
-        moments[p].samples += 1ull;
         if (film) {
             film[p].r += q[0];
             film[p].g += q[1];
@@ -750,6 +734,19 @@ int ptss_probe_accumulate_linear_stats(const ptss_path_result* results, const ui
     return PTSS_HOST_OK;
 }
 
+int ptss_probe_accumulate_linear(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
+                                 size_t filmPixels, const ptss_linear_params* params, unsigned long long* rejected) {
+    if (ptlin::paramsError(params) || (n > 0 && !film)) return PTSS_HOST_EINVAL;
+    return probeAccumulateLinear(results, index, firstPixel, n, film, nullptr, filmPixels, params, rejected);
+}
+
+int ptss_probe_accumulate_linear_stats(const ptss_path_result* results, const uint32_t* index, size_t firstPixel, size_t n, ptss_linear_entry* film,
+                                       ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
+                                       unsigned long long* rejected) {
+    if (ptlin::paramsError(params) || (n > 0 && !moments)) return PTSS_HOST_EINVAL;
+    return probeAccumulateLinear(results, index, firstPixel, n, film, moments, filmPixels, params, rejected);
+}
+
 int ptss_probe_plan_samples_linear(const ptss_linear_moment* moments, size_t filmPixels, const ptss_linear_params* params,
                                    const ptss_linear_plan_params* plan, size_t n, unsigned long long* cdf, uint32_t* index, ptss_plan_info* info) {
     if (ptlin::paramsError(params) || ptls::paramsError(plan, params)) return PTSS_HOST_EINVAL;
@@ -757,21 +754,9 @@ int ptss_probe_plan_samples_linear(const ptss_linear_moment* moments, size_t fil
     if (n == 0) return PTSS_HOST_OK;
     if (!moments || !cdf || !index) return PTSS_HOST_EINVAL;
     const ptls::Rule rule = ptls::ruleOf(*plan, *params);
-    ptss_plan_info found{};
-    unsigned long long sum = 0;
-    for (size_t p = 0; p < filmPixels; ++p) {
-        uint32_t kind;
-        sum += ptls::weight(moments[p].sumY, moments[p].sqLo, moments[p].sqHi, moments[p].samples, rule, &kind);
-        cdf[p] = sum;
-        found.activePixels += (kind & ptad::kActive) ? 1u : 0u;
-        found.unsampledPixels += (kind & ptad::kUnsampled) ? 1u : 0u;
-        found.cappedPixels += (kind & ptad::kCapped) ? 1u : 0u;
-    }
-    found.totalWeight = sum;
-    found.uniform = sum == 0ull ? 1u : 0u;
-    for (size_t i = 0; i < n; ++i)
-        index[i] = sum == 0ull ? ptad::uniformPixel(i, n, filmPixels) : ptad::pixelOf(cdf, (uint32_t)filmPixels, ptad::target(i, n, sum));
-    if (info) *info = found;
+    planSamples(filmPixels, n, cdf, index, info, [&](size_t p, uint32_t* kind) {
+        return ptls::weight(moments[p].sumY, moments[p].sqLo, moments[p].sqHi, moments[p].samples, rule, kind);
+    });
     return PTSS_HOST_OK;
 }
 

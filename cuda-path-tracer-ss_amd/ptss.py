@@ -712,11 +712,15 @@ def probe_plan_samples(film, moments, n, params=None):
     f = _rows(film, FILM_DTYPE, 4, np.uint32, "film")
     m = _moments(moments, len(f))
     params = params if params is not None else plan_params()
-    cdf, index, info = np.zeros(len(f), dtype=np.uint64), np.zeros(int(n), dtype=np.uint32), PlanInfo()
-    rc = host_lib().ptss_probe_plan_samples(f.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), len(f), C.byref(params), int(n),
-                                            cdf.ctypes.data_as(C.c_void_p), index.ctypes.data_as(C.c_void_p), C.byref(info))
+    return _probe_plan("ptss_probe_plan_samples", len(f), n, _ptr(f), _ptr(m), len(f), C.byref(params))
+
+
+def _probe_plan(name, P, n, *front):
+    """The body of probe_plan_samples and probe_plan_samples_linear: host call `name`, `front` its arguments in front of n."""
+    cdf, index, info = np.zeros(P, dtype=np.uint64), np.zeros(int(n), dtype=np.uint32), PlanInfo()
+    rc = getattr(host_lib(), name)(*front, int(n), _ptr(cdf), _ptr(index), C.byref(info))
     if rc != 0:
-        raise PtssError(f"ptss_probe_plan_samples: {rc}")
+        raise PtssError(f"{name}: {rc}")
     return cdf, index, plan_info_dict(info)
 
 
@@ -820,11 +824,7 @@ def probe_plan_samples_linear(moments, n, params=None, plan=None):
     m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments")
     params = params if params is not None else linear_params()
     plan = plan if plan is not None else linear_plan_params()
-    cdf, index, info = np.zeros(len(m), dtype=np.uint64), np.zeros(int(n), dtype=np.uint32), PlanInfo()
-    rc = host_lib().ptss_probe_plan_samples_linear(_ptr(m), len(m), C.byref(params), C.byref(plan), int(n), _ptr(cdf), _ptr(index), C.byref(info))
-    if rc != 0:
-        raise PtssError(f"ptss_probe_plan_samples_linear: {rc}")
-    return cdf, index, plan_info_dict(info)
+    return _probe_plan("ptss_probe_plan_samples_linear", len(m), n, _ptr(m), len(m), C.byref(params), C.byref(plan))
 
 
 def probe_linear_plan_weight(moment, params=None, plan=None):
@@ -1833,9 +1833,10 @@ class Renderer:
     _NO_MOMENTS = object()   # _accumulate's `moments` for a film that keeps none
 
     def _accumulate(self, call, film_dtype, word, results, film, first_pixel, index, moments=_NO_MOMENTS, pixels=None, history=None):
-        """The body of accumulate_paths, accumulate_paths_stats and accumulate_paths_linear. film_dtype, word: the film's record and the
-        type of its four words (a torch film holds them signed); call(results, index, first_pixel, n, film, P, moments, pixels, history,
-        stream): the C call, over device pointers or None. torch -> None; numpy -> (film, moments or None, pixels, history) afterwards."""
+        """The body of accumulate_paths, accumulate_paths_stats and accumulate_paths_linear (accumulate_paths_linear_stats, whose film may
+        be None and whose moments are records, has its own). film_dtype, word: the film's record and the type of its four words (a torch
+        film holds them signed); call(results, index, first_pixel, n, film, P, moments, pixels, history, stream): the C call, over device
+        pointers or None. torch -> None; numpy -> (film, moments or None, pixels, history) afterwards."""
         keeps_moments = moments is not self._NO_MOMENTS
         if type(results).__module__.split(".")[0] == "torch":
             import sys
@@ -1912,30 +1913,35 @@ class Renderer:
         (4,) int64 tensor or None, all contiguous on one device, WRITTEN IN PLACE -> None, on the current stream."""
         L = device_lib()
         params = params if params is not None else plan_params()
-        n = int(n)
-        if type(film).__module__.split(".")[0] == "torch":
+        return self._plan(lambda d, P, n, cdf, idx, inf, st: _check(L.ptss_plan_samples(self._ctx, d[0], d[1], P, C.byref(params), n, cdf, idx, inf, st)),
+                          [(film, "film", FILM_DTYPE, np.uint32), (moments, "moments", None, np.uint64)], n, cdf, index, info)
+
+    def _plan(self, call, inputs, n, cdf, index, info):
+        """The body of plan_samples and plan_samples_linear. inputs: what the plan reads, a row (value, name, record dtype, type of its
+        words) per array: P records of four words, or P plain words where the record is None; the first has records. call(the inputs'
+        pointers, P, n, cdf, index, info, stream): the C call, over device pointers or None. torch -> None; numpy -> (cdf, index, info)."""
+        n, head = int(n), inputs[0][0]
+        if type(head).__module__.split(".")[0] == "torch":
             import sys
             torch = sys.modules["torch"]
-            dev, P = film.device, film.shape[0]
-            d_film = self._torch_ptr(film, "film", "int32", 4)
-            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P)
+            dev, P = head.device, head.shape[0]
+            d_in = [self._torch_ptr(value, what, "int%d" % (8 * np.dtype(word).itemsize), 4 if record is not None else 0, *((dev, P) if k else ()))
+                    for k, (value, what, record, word) in enumerate(inputs)]
             d_cdf = self._torch_ptr(cdf, "cdf", "int64", 0, dev, plan_cdf_entries(P))
             d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n)
             d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_plan_samples(self._ctx, d_film, d_mom, P, C.byref(params), n, d_cdf, d_idx, d_info, C.c_void_p(stream)))
+            call(d_in, P, n, d_cdf, d_idx, d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
             return None
-        f = _rows(film, FILM_DTYPE, 4, np.uint32, "film")
-        P = len(f)
-        m = _moments(moments, P)
+        rows = []
+        for value, what, record, word in inputs:
+            rows.append(_rows(value, record, 4, word, what) if record is not None else _moments(value, len(rows[0])))
+        P, k = len(rows[0]), len(rows)
         work = np.zeros(plan_cdf_entries(P), dtype=np.uint64)
         out, found = np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
         if n == 0:
-            _check(L.ptss_plan_samples(self._ctx, None, None, P, C.byref(params), 0, None, None, None, None))
+            call([None] * k, P, 0, None, None, None, None)
         else:
-            self._round_trip([f, m, work, out, found],
-                             lambda d: _check(L.ptss_plan_samples(self._ctx, d[0], d[1], P, C.byref(params), n, d[2], d[3], d[4], None)),
-                             read=(2, 3, 4))
+            self._round_trip(rows + [work, out, found], lambda d: call(d[:k], P, n, d[k], d[k + 1], d[k + 2], None), read=(k, k + 1, k + 2))
         return work[:P], out, plan_info_dict(found)
 
     def adaptive_launches(self):
@@ -2001,29 +2007,8 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         plan = plan if plan is not None else linear_plan_params()
-        n = int(n)
-        if type(moments).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, P = moments.device, moments.shape[0]
-            d_mom = self._torch_ptr(moments, "moments", "int64", 4)
-            d_cdf = self._torch_ptr(cdf, "cdf", "int64", 0, dev, plan_cdf_entries(P))
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n)
-            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_plan_samples_linear(self._ctx, d_mom, P, C.byref(params), C.byref(plan), n, d_cdf, d_idx, d_info, C.c_void_p(stream)))
-            return None
-        m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments")
-        P = len(m)
-        work = np.zeros(plan_cdf_entries(P), dtype=np.uint64)
-        out, found = np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
-        if n == 0:
-            _check(L.ptss_plan_samples_linear(self._ctx, None, P, C.byref(params), C.byref(plan), 0, None, None, None, None))
-        else:
-            self._round_trip([m, work, out, found],
-                             lambda d: _check(L.ptss_plan_samples_linear(self._ctx, d[0], P, C.byref(params), C.byref(plan), n, d[1], d[2], d[3],
-                                                                         None)), read=(1, 2, 3))
-        return work[:P], out, plan_info_dict(found)
+        return self._plan(lambda d, P, n, cdf, idx, inf, st: _check(L.ptss_plan_samples_linear(self._ctx, d[0], P, C.byref(params), C.byref(plan), n, cdf, idx, inf, st)),
+                          [(moments, "moments", MOMENT_DTYPE, np.uint64)], n, cdf, index, info)
 
     def linear_stats_launches(self):
         """ptss_linear_stats_launches: (accumulate_paths_linear_stats, plan_samples_linear calls that launched since the context was
