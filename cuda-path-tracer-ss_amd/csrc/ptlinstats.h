@@ -84,6 +84,28 @@ PTM_HD float sqrt128(U128 D) {
     return ptm::sqrt((float)m) * ptlin::pow2(s / 2);
 }
 
+// the standard error of the mean luminance of a moment row (Sy, sqLo, sqHi, N), N >= 1, in fixed-point units: what weight() divides by the
+// mean, and what the linear denoiser (ptlindn.h) takes as a pixel's measured error
+PTM_HD float standardError(u64 Sy, u64 sqLo, u64 sqHi, u64 N) {
+    // Q = sqHi * 2^40 + sqLo
+    U128 Q{sqHi << 40, sqHi >> 24};
+    Q.lo += sqLo;
+    Q.hi += Q.lo < sqLo ? 1ull : 0ull;
+    // A = N * Q, B = Sy^2, both modulo 2^128
+    U128 A = mul64(N, Q.lo);
+    A.hi += N * Q.hi;
+    const U128 B = mul64(Sy, Sy);
+    const bool atLeast = A.hi > B.hi || (A.hi == B.hi && A.lo >= B.lo);
+    U128 D{0ull, 0ull};   // N^2 times the population variance of the luminance
+    if (atLeast) {
+        D.lo = A.lo - B.lo;
+        D.hi = A.hi - B.hi - (A.lo < B.lo ? 1ull : 0ull);
+    }
+    const float r = sqrt128(D);
+    const float fn = (float)N;
+    return ptm::div(r, fn * ptm::sqrt(fn));
+}
+
 // the weight of a pixel with moment row (Sy, sqLo, sqHi, N); *kind (may be null): ptad::kActive / kUnsampled / kCapped bits
 PTM_HD uint32_t weight(u64 Sy, u64 sqLo, u64 sqHi, u64 N, const Rule& R, uint32_t* kind) {
     uint32_t w = 0u, k = 0u;
@@ -93,23 +115,8 @@ PTM_HD uint32_t weight(u64 Sy, u64 sqLo, u64 sqHi, u64 N, const Rule& R, uint32_
     } else if (N >= (u64)R.maxSamples) {
         k = ptad::kCapped;
     } else {
-        // Q = sqHi * 2^40 + sqLo
-        U128 Q{sqHi << 40, sqHi >> 24};
-        Q.lo += sqLo;
-        Q.hi += Q.lo < sqLo ? 1ull : 0ull;
-        // A = N * Q, B = Sy^2, both modulo 2^128
-        U128 A = mul64(N, Q.lo);
-        A.hi += N * Q.hi;
-        const U128 B = mul64(Sy, Sy);
-        const bool atLeast = A.hi > B.hi || (A.hi == B.hi && A.lo >= B.lo);
-        U128 D{0ull, 0ull};   // N^2 times the population variance of the luminance
-        if (atLeast) {
-            D.lo = A.lo - B.lo;
-            D.hi = A.hi - B.hi - (A.lo < B.lo ? 1ull : 0ull);
-        }
-        const float r = sqrt128(D);
+        const float seY = standardError(Sy, sqLo, sqHi, N);
         const float fn = (float)N;
-        const float seY = ptm::div(r, fn * ptm::sqrt(fn));   // the standard error of the mean luminance, in fixed-point units
         const float meanY = ptm::div((float)Sy, fn);
         const float rel = ptm::div(seY, meanY + R.floorFixed);   // (the denominator is at least 1: no NaN, no division by zero)
         if (rel > R.threshold) w = (uint32_t)ptm::min(rel * kWeightScale, kWeightCap);

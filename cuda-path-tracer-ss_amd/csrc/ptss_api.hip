@@ -29,6 +29,7 @@
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
+#include "ptlindn.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -164,6 +165,8 @@ struct ptss_context {
     unsigned long long splatLaunches[3] = {0, 0, 0};          // ptss_splat_paths, ptss_splat_paths_homed, ptss_resolve_splat calls that launched
     unsigned long long meterLaunches[3] = {0, 0, 0};          // meter histograms, ptss_meter_exposure, metered resolves that launched
     unsigned long long glareLaunches[3] = {0, 0, 0};          // glare builds, the kernels they launched, glare resolves that launched
+    unsigned long long linDenoiseLaunches[2] = {0, 0};        // ptss_denoise_linear calls that launched, the kernels inside them
+    int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
     float4* dDenoise[2] = {nullptr, nullptr};   // ptss_denoise's ping-pong colour planes, allocated by its first call with levels >= 2
@@ -1764,6 +1767,63 @@ int ptss_glare_build(ptss_context* c, const void* dev_film, int filmKind, int wi
 int ptss_glare_launches(const ptss_context* c, unsigned long long* out3) {
     if (!c || !out3) return fail(PTSS_EINVAL, "null argument");
     for (int k = 0; k < 3; ++k) out3[k] = c->glareLaunches[k];
+    return PTSS_OK;
+}
+
+// ---- the denoiser of the two linear films (ptss_lindenoise.hip; csrc/ptlindn.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_denoise_linear_params(ptss_denoise_linear_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_denoise_linear_params);
+    p->levels = 5;
+    p->sigmaLuminance = 3.f;   // design choices, not measurements: three standard errors, and ptss_default_denoise_params' geometry
+    p->sigmaNormal = 0.1f;
+    p->sigmaDepth = 4.f;
+    p->reserved[0] = p->reserved[1] = p->reserved[2] = 0u;
+    return PTSS_OK;
+}
+
+int ptss_denoise_linear_workspace(int width, int height, size_t* bytes) {
+    if (!bytes) return fail(PTSS_EINVAL, "bytes is null");
+    if (const char* what = ptldn::sidesError(width, height)) return fail(PTSS_ERANGE, what);
+    size_t off[4];
+    *bytes = ptldn::workspaceLayout((size_t)width * (size_t)height, off);
+    return PTSS_OK;
+}
+
+int ptss_denoise_linear(ptss_context* c, const void* dev_film, int filmKind, int width, int height, const ptss_linear_moment* dev_moments,
+                        const ptss_pixel_feature* dev_features, const ptss_linear_params* params, const ptss_denoise_linear_params* denoise,
+                        void* dev_workspace, ptss_linear_entry* dev_out, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlin::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptldn::paramsError(denoise)) return fail(PTSS_EINVAL, what);
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return fail(PTSS_EINVAL, "unknown film kind");
+    if (const char* what = ptldn::sidesError(width, height)) return fail(PTSS_ERANGE, what);
+    if (!dev_film || !dev_moments || !dev_features || !dev_workspace || !dev_out) return fail(PTSS_EINVAL, "null film, moments, features, workspace or out");
+    if (((uintptr_t)dev_film | (uintptr_t)dev_moments | (uintptr_t)dev_features | (uintptr_t)dev_workspace | (uintptr_t)dev_out) & 15u)
+        return fail(PTSS_EINVAL, "film, moments, features, workspace and out must be 16-byte aligned");
+    if ((const void*)dev_out == dev_film) return fail(PTSS_EINVAL, "dev_out must not be dev_film");
+    size_t off[4];
+    const size_t bytes = ptldn::workspaceLayout((size_t)width * (size_t)height, off);
+    const uintptr_t ws = (uintptr_t)dev_workspace;
+    if (((uintptr_t)dev_out >= ws && (uintptr_t)dev_out - ws < bytes) || ((uintptr_t)dev_film >= ws && (uintptr_t)dev_film - ws < bytes))
+        return fail(PTSS_EINVAL, "film and out must not lie inside the workspace");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchLinearDenoise(streamOf(c, hipStream), dev_film, filmKind == PTSS_FILM_SPLAT, width, height, dev_moments, dev_features, *params,
+                                      *denoise, c->linDenoiseForm, dev_workspace, dev_out, c->linDenoiseLaunches));
+    return PTSS_OK;
+}
+
+int ptss_denoise_linear_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->linDenoiseLaunches[0];
+    out2[1] = c->linDenoiseLaunches[1];
+    return PTSS_OK;
+}
+
+int ptss_debug_denoise_linear_form(ptss_context* c, int form) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (form < 0 || form == 3 || form > 11) return fail(PTSS_EINVAL, "form must be 0, 1, 2 or 4 .. 11");
+    c->linDenoiseForm = form;
     return PTSS_OK;
 }
 

@@ -272,6 +272,15 @@ hipError_t launchMeterExposure(hipStream_t st, const uint32_t* histogram, const 
 // ptglare::sidesError). No bit of ptss_launched_kernels
 hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int width, int height, const ptss_linear_params& params,
                             const ptss_glare_params& glare, void* pyramid, unsigned long long* launches);
+// the denoiser of the two linear films (ptss_lindenoise.hip; ptss_denoise_linear). film = width x height x 32 B, a
+// ptss_splat_entry where `splat`; moments and features = 32 B per pixel; workspace = what ptldn::workspaceLayout counts; out = width x
+// height x 32 B. form: 0 the measured table of forms per spacing, 1 every pass unstaged, 2 staged wherever a staged kernel exists, 4 + mask staged at
+// pass k where bit k of the 3-bit mask is set.
+// launches[0] is incremented once when every kernel of the call launched, launches[1] by each kernel that did. params and denoise:
+// checked by the caller (ptlin::paramsError, ptldn::paramsError, ptldn::sidesError). No bit of ptss_launched_kernels
+hipError_t launchLinearDenoise(hipStream_t st, const void* film, bool splat, int width, int height, const void* moments, const void* features,
+                               const ptss_linear_params& params, const ptss_denoise_linear_params& denoise, int form, void* workspace, void* out,
+                               unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

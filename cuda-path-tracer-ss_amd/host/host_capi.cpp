@@ -18,6 +18,7 @@
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
+#include "ptlindn.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -981,6 +982,64 @@ int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, 
         if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
         if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
     }
+    return PTSS_HOST_OK;
+}
+
+// ---- the denoiser of the two linear films (csrc/ptlindn.h) ----
+int ptss_probe_denoise_linear(const void* film, int filmKind, int width, int height, const ptss_linear_moment* moments,
+                              const ptss_pixel_feature* features, const ptss_linear_params* params, const ptss_denoise_linear_params* denoise,
+                              ptss_linear_entry* out, float* out_plane) {
+    if (ptlin::paramsError(params) || ptldn::paramsError(denoise) || ptldn::sidesError(width, height)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if (!film || !moments || !features || !out || (const void*)out == film) return PTSS_HOST_EINVAL;
+    const bool splat = filmKind == PTSS_FILM_SPLAT;
+    const unsigned long long* words = static_cast<const unsigned long long*>(film);
+    unsigned long long* result = reinterpret_cast<unsigned long long*>(out);
+    const ptldn::Rule R = ptldn::ruleOf(*denoise, *params);
+    const size_t n = (size_t)width * (size_t)height;
+    const int L = denoise->levels;
+    std::vector<ptldn::Row> plane[2];
+    plane[0].resize(n);
+    if (L > 1) plane[1].resize(n);
+    for (size_t p = 0; p < n; ++p) {
+        const unsigned long long* e = words + 4 * p;
+        plane[0][p] = ptldn::prepare(e[0], e[1], e[2], e[3], splat, moments[p].sumY, moments[p].sqLo, moments[p].sqHi, moments[p].samples, R);
+        if (L == 0) ptldn::finishMeans(e[0], e[1], e[2], e[3], splat, result + 4 * p);
+    }
+    std::vector<ptldn::Row> final;
+    if (L > 0) final.resize(n);
+    auto featureAt = [&](int qx, int qy) {
+        const ptss_pixel_feature& f = features[(size_t)qy * (size_t)width + (size_t)qx];
+        return ptdn::Feature{f.normal, f.depth, f.materialIdx};
+    };
+    for (int i = 0; i < L; ++i) {
+        const std::vector<ptldn::Row>& src = plane[ptldn::sourcePlane(i)];
+        std::vector<ptldn::Row>& dst = i + 1 == L ? final : plane[1 - ptldn::sourcePlane(i)];
+        auto rowAt = [&](int qx, int qy) { return src[(size_t)qy * (size_t)width + (size_t)qx]; };
+        for (int y = 0; y < height; ++y)
+            for (int x = 0; x < width; ++x) dst[(size_t)y * (size_t)width + (size_t)x] = ptldn::filterPixel(x, y, width, height, 1 << i, R, rowAt, featureAt);
+    }
+    if (L > 0)
+        for (size_t p = 0; p < n; ++p) ptldn::finishRow(final[p], words[4 * p + 3], splat, R, result + 4 * p);
+    if (out_plane) {
+        const std::vector<ptldn::Row>& shown = L > 0 ? final : plane[0];
+        for (size_t p = 0; p < n; ++p) {
+            out_plane[4 * p] = shown[p].c.x, out_plane[4 * p + 1] = shown[p].c.y, out_plane[4 * p + 2] = shown[p].c.z;
+            out_plane[4 * p + 3] = shown[p].v;
+        }
+    }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_denoise_linear_finish(const float* rgb, unsigned long long word3, int filmKind, const ptss_linear_params* params,
+                                     unsigned long long* out4) {
+    if (!rgb || !out4 || ptlin::paramsError(params) || (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT)) return PTSS_HOST_EINVAL;
+    ptss_denoise_linear_params d{};
+    d.sigmaLuminance = d.sigmaNormal = d.sigmaDepth = 1.f;
+    const ptldn::Rule R = ptldn::ruleOf(d, *params);
+    const bool splat = filmKind == PTSS_FILM_SPLAT;
+    const ptldn::Row row{v3(rgb[0], rgb[1], rgb[2]), ptldn::weightOf(word3, splat) == 0ull ? ptldn::kEmpty : 0.f};
+    ptldn::finishRow(row, word3, splat, R, out4);
     return PTSS_HOST_OK;
 }
 

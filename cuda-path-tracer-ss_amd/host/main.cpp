@@ -53,6 +53,12 @@
 //                                    — after the last round ptss_glare_build over the film (default parameters; strength default
 //                                   0.1, threshold default 0, levels default 6) and ptss_resolve_linear_glare (ptss_resolve_splat_glare), with the
 //                                   meter's state where --auto-exposure keeps one. Without it every byte written is today's
+//             [--denoise-linear [levels[,sigmaLuminance]]]   with --linear, with or without --filter, --auto-exposure, --glare and --refill: the
+//                                   film is denoised in linear light — the rounds keep the luminance moments
+//                                   (ptss_accumulate_paths_linear_stats; with --filter by home pixel), the features are ptss_ray_features of the
+//                                   pixel-centre rays, and ptss_denoise_linear (default parameters; levels default 5, sigmaLuminance default 3)
+//                                   makes the linear film that --auto-exposure's meter (every round), --glare, the resolve and image.pfm then
+//                                   read. Levels 0 and the absent flag write the same bytes
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -89,6 +95,9 @@ int main(int argc, char* argv[]) {
     bool glare = false;                        // --glare: the final resolve of the linear film adds the glare pyramid
     float glareStrength = -1.f, glareThreshold = -1.f;   // ... its strength, threshold and levels when given
     int glareLevels = -1;
+    bool denoiseLinear = false;                       // --denoise-linear: the linear film is denoised in front of the meter, the glare and the resolve
+    int denoiseLinearLevels = -1;                     // ... its levels and sigmaLuminance when given
+    float denoiseLinearSigma = -1.f;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -157,6 +166,18 @@ int main(int argc, char* argv[]) {
                 }
             }
         }
+        else if (a == "--denoise-linear") {
+            denoiseLinear = true;
+            const char* v = i + 1 < argc ? argv[i + 1] : "";
+            if ((v[0] >= '0' && v[0] <= '9') || (v[0] == '-' && v[1] >= '0' && v[1] <= '9')) {
+                const int got = sscanf(next(), "%d,%f", &denoiseLinearLevels, &denoiseLinearSigma);
+                if (got < 1 || denoiseLinearLevels < 0 || denoiseLinearLevels > PTSS_DENOISE_MAX_LEVELS ||
+                    (got == 2 && !(denoiseLinearSigma > 0.f && denoiseLinearSigma < 1e30f))) {
+                    fprintf(stderr, "bad --denoise-linear (levels[,sigmaLuminance])\n");
+                    return 2;
+                }
+            }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -211,6 +232,7 @@ int main(int argc, char* argv[]) {
     if (adaptiveLinear >= 0 && linear < 0.f) { fprintf(stderr, "--adaptive-linear needs --film and --linear\n"); return 2; }
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
+    if (denoiseLinear && linear < 0.f) { fprintf(stderr, "--denoise-linear needs --film and --linear\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -394,6 +416,32 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
         }
+        void *dClean = nullptr, *dCleanFeat = nullptr, *dCleanWork = nullptr;   // --denoise-linear: the denoised film, the features, the workspace
+        ptss_denoise_linear_params cleanParams;
+        PTSS_HANDLE(ptss_default_denoise_linear_params(&cleanParams));
+        if (denoiseLinearLevels >= 0) cleanParams.levels = denoiseLinearLevels;
+        if (denoiseLinearSigma > 0.f) cleanParams.sigmaLuminance = denoiseLinearSigma;
+        if (denoiseLinear) {
+            size_t work = 0;
+            PTSS_HANDLE(ptss_denoise_linear_workspace(width, height, &work));
+            if (hipMalloc(&dClean, n * sizeof(ptss_linear_entry)) != hipSuccess || hipMalloc(&dCleanFeat, n * sizeof(ptss_pixel_feature)) != hipSuccess ||
+                hipMalloc(&dCleanWork, work) != hipSuccess ||
+                (!dMoments && (hipMalloc(&dMoments, n * sizeof(ptss_linear_moment)) != hipSuccess ||
+                               hipMemset(dMoments, 0, n * sizeof(ptss_linear_moment)) != hipSuccess))) {
+                fprintf(stderr, "--denoise-linear: device buffers\n");
+                return 1;
+            }
+        }
+        const bool keepMoments = adaptiveLinear >= 0 || denoiseLinear;   // the rounds accumulate with stats
+        // what the meter, the glare and the resolves read: the denoised film, a linear one whatever the rounds fill, or the rounds' own
+        const void* shown = denoiseLinear ? dClean : dLinear;
+        const bool shownSplat = !denoiseLinear && dPos;
+        auto denoiseFilm = [&]() -> int {
+            PTSS_HANDLE(ptss_denoise_linear(ctx, dLinear, dPos ? PTSS_FILM_SPLAT : PTSS_FILM_LINEAR, width, height, (const ptss_linear_moment*)dMoments,
+                                            (const ptss_pixel_feature*)dCleanFeat, &linearParams, &cleanParams, dCleanWork, (ptss_linear_entry*)dClean,
+                                            NULL));
+            return 0;
+        };
         void* dPyramid = nullptr;   // --glare
         ptss_glare_params glareParams;
         PTSS_HANDLE(ptss_default_glare_params(&glareParams));
@@ -407,26 +455,33 @@ int main(int argc, char* argv[]) {
             if (hipMalloc(&dPyramid, entries * sizeof(ptss_glare_entry)) != hipSuccess) { fprintf(stderr, "--glare: device buffers\n"); return 1; }
         }
         auto meteredResolve = [&]() -> int {   // the exposure is the state's, --linear's compensating
-            if (dPos) {
-                PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
+            if (shownSplat) {
+                PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
                                                        (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             } else {
-                PTSS_HANDLE(ptss_resolve_linear_metered(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
+                PTSS_HANDLE(ptss_resolve_linear_metered(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
                                                         (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             }
             return 0;
         };
         auto meterRound = [&](int round) -> int {   // meter, update, metered resolve: the round's exposure never leaves the device
             uint32_t* bins = (uint32_t*)dBins + (size_t)round * PTSS_METER_BINS;
-            if (dPos) {
-                PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, bins, NULL));
+            if (denoiseLinear && denoiseFilm()) return 1;   // the meter reads the denoised film of this round
+            if (shownSplat) {
+                PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)shown, 0, n, bins, NULL));
             } else {
-                PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, bins, NULL));
+                PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)shown, 0, n, bins, NULL));
             }
             PTSS_HANDLE(ptss_meter_exposure(ctx, bins, &linearParams, &meterParams, (ptss_meter_state*)dMeter, NULL));
             return meteredResolve();
         };
         PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, n, seed, 0, 0, NULL));
+        if (denoiseLinear) {   // the features of the pixel-centre rays (jitter 0 draws nothing: the streams stay what the rounds expect)
+            fc.jitter = 0;
+            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dRays, (ptss_pixel_feature*)dCleanFeat, n, NULL));
+            fc.jitter = 1;
+        }
         for (int t = 0; t < ticks; ++t) {
             if (dPos) {
                 PTSS_HANDLE(ptss_generate_rays_positions(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, (ptss_film_position*)dPos, NULL));
@@ -438,11 +493,11 @@ int main(int argc, char* argv[]) {
             if (dPos) {
                 PTSS_HANDLE(ptss_splat_paths_homed(ctx, (const ptss_path_result*)dRes, (const ptss_film_position*)dPos, 0, n, (ptss_splat_entry*)dLinear,
                                                    width, height, &splatFilter, &linearParams, NULL));
-                if (adaptiveLinear >= 0) {   // the moments by home pixel, beside the filtered film
+                if (keepMoments) {   // the moments by home pixel, beside the filtered film
                     PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, NULL, (ptss_linear_moment*)dMoments, n,
                                                                    &linearParams, NULL));
                 }
-            } else if (adaptiveLinear >= 0) {
+            } else if (keepMoments) {
                 PTSS_HANDLE(ptss_accumulate_paths_linear_stats(ctx, (const ptss_path_result*)dRes, NULL, 0, n, (ptss_linear_entry*)dLinear,
                                                                (ptss_linear_moment*)dMoments, n, &linearParams, NULL));
             } else if (linear >= 0.f) {
@@ -509,6 +564,7 @@ int main(int argc, char* argv[]) {
                    info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
         if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
+            if (denoiseLinear && (!autoExposure || ticks <= 0) && denoiseFilm()) return 1;   // (with a meter the last round's denoised film stands)
             if (autoExposure) {   // (the last round's metered resolve stands; without a round the new state's exposure, 0, shows black)
                 if (ticks <= 0 && meteredResolve()) return 1;
                 PTSS_HANDLE(ptss_synchronize(ctx));
@@ -519,22 +575,22 @@ int main(int argc, char* argv[]) {
             }
             if (glare) {   // the pyramid of the finished film, and the resolve that adds it: at the meter's exposure where there is one
                 const ptss_meter_state* state = autoExposure ? (const ptss_meter_state*)dMeter : NULL;
-                PTSS_HANDLE(ptss_glare_build(ctx, dLinear, dPos ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, width, height, &linearParams, &glareParams,
+                PTSS_HANDLE(ptss_glare_build(ctx, shown, shownSplat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, width, height, &linearParams, &glareParams,
                                              (ptss_glare_entry*)dPyramid, NULL));
-                if (dPos) {
-                    PTSS_HANDLE(ptss_resolve_splat_glare(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, width, height, &glareParams,
+                if (shownSplat) {
+                    PTSS_HANDLE(ptss_resolve_splat_glare(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, width, height, &glareParams,
                                                          (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
                                                          (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
                 } else {
-                    PTSS_HANDLE(ptss_resolve_linear_glare(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, width, height, &glareParams,
+                    PTSS_HANDLE(ptss_resolve_linear_glare(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, width, height, &glareParams,
                                                           (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
                                                           (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
                 }
-            } else if (!autoExposure && dPos) {
-                PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
+            } else if (!autoExposure && shownSplat) {
+                PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, (ptss_history_entry*)dMeans,
                                                (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             } else if (!autoExposure) {
-                PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dLinear, 0, n, &linearParams, (ptss_history_entry*)dMeans,
+                PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, (ptss_history_entry*)dMeans,
                                                 (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
             }
             PTSS_HANDLE(ptss_synchronize(ctx));
@@ -564,7 +620,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid, dClean, dCleanFeat, dCleanWork}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

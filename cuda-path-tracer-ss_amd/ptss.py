@@ -21,6 +21,7 @@ from ptss_types import METER_BINS, METER_BLOCK, METER_GRID_CAP, METER_STATE_DTYP
 from ptss_types import MOMENT_DTYPE, LinearMoment, LinearPlanParams
 from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SPLAT, GLARE_MAX_LEVELS, GLARE_MIX, GLARE_TAIL_ENTRIES, GLARE_TILE, GlareLevel,
                         GlareParams)
+from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DENOISE_MAX_LEVELS, FILM_LINEAR, FILM_SPLAT, DenoiseLinearParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -215,6 +216,9 @@ def host_lib():
         L.ptss_probe_glare_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LinearParams), C.POINTER(GlareParams), C.c_void_p]
         L.ptss_probe_resolve_glare.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_int, C.c_int,
                                                C.POINTER(GlareParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptss_probe_denoise_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LinearParams),
+                                                C.POINTER(DenoiseLinearParams), C.c_void_p, C.c_void_p]
+        L.ptss_probe_denoise_linear_finish.argtypes = [C.POINTER(C.c_float), C.c_ulonglong, C.c_int, C.POINTER(LinearParams), C.POINTER(C.c_ulonglong)]
         _host = L
     return _host
 
@@ -337,6 +341,11 @@ def device_lib():
                                                 vp, vp, vp, vp]
         L.ptss_resolve_splat_glare.argtypes = L.ptss_resolve_linear_glare.argtypes
         L.ptss_glare_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_denoise_linear_params.argtypes = [C.POINTER(DenoiseLinearParams)]
+        L.ptss_denoise_linear_workspace.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+        L.ptss_denoise_linear.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(LinearParams), C.POINTER(DenoiseLinearParams), vp, vp, vp]
+        L.ptss_denoise_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_denoise_linear_form.argtypes = [vp, C.c_int]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1056,6 +1065,63 @@ def probe_resolve_glare(film, width, height, pyramid, first_pixel=0, count=None,
     if rc != 0:
         raise PtssError(f"ptss_probe_resolve_glare: {rc}")
     return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+
+# ---- the denoiser of the two linear films (ptss_denoise_linear) ----
+def denoise_linear_params(levels=5, sigma_luminance=3.0, sigma_normal=0.1, sigma_depth=4.0):
+    """A ptss_denoise_linear_params; the defaults are ptss_default_denoise_linear_params' (design choices, not measurements)."""
+    p = DenoiseLinearParams()
+    p.structSize = C.sizeof(DenoiseLinearParams)
+    p.levels, p.sigmaLuminance, p.sigmaNormal, p.sigmaDepth = int(levels), float(sigma_luminance), float(sigma_normal), float(sigma_depth)
+    return p
+
+
+def denoise_linear_workspace(width, height):
+    """The bytes of workspace ptss_denoise_linear asks for over a width x height film (csrc/ptlindn.h workspaceLayout)."""
+    return (int(width) * int(height) * DENOISE_LINEAR_WORKSPACE_BYTES + 15) & ~15
+
+
+def _denoise_linear_inputs(film, film_kind, width, height, moments, features):
+    """The film, its kind, the moments and the features of a denoise_linear call as plain rows."""
+    f, kind = _glare_film(film, film_kind, width, height)
+    m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments")
+    ft = np.ascontiguousarray(np.asarray(features))
+    ft = ft.view(np.float32).reshape(-1, 8) if ft.dtype == FEATURE_DTYPE else np.ascontiguousarray(ft, dtype=np.float32)
+    if ft.ndim != 2 or ft.shape[1] != 8:
+        raise ValueError("features: (N,) FEATURE_DTYPE or (N, 8) float32")
+    if len(m) != len(f) or len(ft) != len(f):
+        raise ValueError("moments, features: one row per film pixel")
+    return f, kind, m, ft
+
+
+def probe_denoise_linear(film, width, height, moments, features, params=None, denoise=None, film_kind=None, plane=False):
+    """ptss_denoise_linear on the host (csrc/ptlindn.h; the specification of the device's film) -> the denoised film, (width * height,)
+    LINEAR_DTYPE; with plane=True -> (film, the last plane the call computed as (width * height, 4) float32 rows {r, g, b, variance}; an
+    empty pixel's variance is DENOISE_LINEAR_EMPTY). film: (P,) LINEAR_DTYPE or SPLAT_DTYPE, or (P, 4) uint64 with film_kind; moments: (P,)
+    MOMENT_DTYPE; features: (P,) FEATURE_DTYPE."""
+    f, kind, m, ft = _denoise_linear_inputs(film, film_kind, width, height, moments, features)
+    params = params if params is not None else linear_params()
+    denoise = denoise if denoise is not None else denoise_linear_params()
+    out = np.zeros((len(f), 4), dtype=np.uint64)
+    pl = np.zeros((len(f), 4), dtype=np.float32) if plane else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = host_lib().ptss_probe_denoise_linear(ptr(f), kind, int(width), int(height), ptr(m), ptr(ft), C.byref(params), C.byref(denoise), ptr(out),
+                                              ptr(pl))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_denoise_linear: {rc}")
+    out = out.view(LINEAR_DTYPE).reshape(-1)
+    return (out, pl) if plane else out
+
+
+def probe_denoise_linear_finish(rgb, word3, film_kind="linear", params=None):
+    """The finish of ptss_denoise_linear for one pixel on the host: the filtered colour rgb and the fourth word of the pixel's film entry ->
+    the output row as four Python integers (r, g, b sums and samples | clamped << 32)."""
+    params = params if params is not None else linear_params()
+    c, out = (C.c_float * 3)(*[float(v) for v in rgb]), (C.c_ulonglong * 4)()
+    rc = host_lib().ptss_probe_denoise_linear_finish(c, int(word3), int(_GLARE_FILMS.get(film_kind, film_kind)), C.byref(params), out)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_denoise_linear_finish: {rc}")
+    return tuple(int(v) for v in out)
 
 
 def default_denoise_params(**overrides):
@@ -2161,6 +2227,55 @@ class Renderer:
         out = (C.c_ulonglong * 3)()
         _check(device_lib().ptss_glare_launches(self._ctx, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    # --- the denoiser of the two linear films (ptss_denoise_linear) ------------------
+    def denoise_linear(self, film, width, height, moments, features, params=None, denoise=None, film_kind=None, out=None, workspace=None):
+        """ptss_denoise_linear: a whole linear or filtered linear film filtered in linear light, guided by its moments, into a linear film.
+        numpy: film (width * height,) LINEAR_DTYPE or SPLAT_DTYPE, or (P, 4) uint64 with film_kind "linear" / "splat"; moments (P,)
+        MOMENT_DTYPE; features (P,) FEATURE_DTYPE -> the denoised film, (P,) LINEAR_DTYPE; workspace=True -> (film, the workspace's bytes
+        afterwards as a uint8 array). torch: film and moments (P, 4) int64, features (P, 8) float32, out a (P, 4) int64 device tensor
+        WRITTEN IN PLACE, workspace a uint8 device tensor of denoise_linear_workspace(width, height) bytes (a new one where None) -> None,
+        on the current stream. params: the film's linear_params; denoise: a denoise_linear_params."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        denoise = denoise if denoise is not None else denoise_linear_params()
+        width, height = int(width), int(height)
+        nbytes = denoise_linear_workspace(width, height)
+        if type(film).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, P = film.device, width * height
+            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
+            d_film = self._torch_ptr(film, "film", "int64", 4, None, P)
+            d_mom = self._torch_ptr(moments, "moments", "int64", 4, dev, P)
+            d_feat = self._torch_ptr(features, "features", "float32", 8, dev, P)
+            d_out = self._torch_ptr(out, "out", "int64", 4, dev, P)
+            if workspace is None:
+                workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            d_ws = self._torch_ptr(workspace, "workspace", "uint8", 0, dev)
+            if workspace.shape[0] < nbytes:
+                raise ValueError("workspace: denoise_linear_workspace(width, height) bytes")
+            _check(L.ptss_denoise_linear(self._ctx, d_film, kind, width, height, d_mom, d_feat, C.byref(params), C.byref(denoise), d_ws, d_out,
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        f, kind, m, ft = _denoise_linear_inputs(film, film_kind, width, height, moments, features)
+        res = np.zeros((len(f), 4), dtype=np.uint64)
+        ws = np.zeros((nbytes,), dtype=np.uint8)
+        self._round_trip([f, m, ft, ws, res], lambda d: _check(L.ptss_denoise_linear(self._ctx, d[0], kind, width, height, d[1], d[2], C.byref(params),
+                                                                                     C.byref(denoise), d[3], d[4], None)), read=(3, 4))
+        res = res.view(LINEAR_DTYPE).reshape(-1)
+        return (res, ws) if workspace else res
+
+    def denoise_linear_launches(self):
+        """ptss_denoise_linear_launches: (denoise_linear calls that launched, the kernels inside them since the context was created)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_denoise_linear_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
+
+    def debug_denoise_linear_form(self, form):
+        """ptss_debug_denoise_linear_form (tests and measurements): 0 the measured form per spacing, 1 taps from global memory, 2 staged in
+        LDS wherever that kernel exists, 4 + mask staged at pass k where bit k of the mask (0 .. 7) is set. The bytes are the same."""
+        _check(device_lib().ptss_debug_denoise_linear_form(self._ctx, int(form)))
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

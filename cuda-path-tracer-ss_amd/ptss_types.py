@@ -205,6 +205,17 @@ class GlareLevel(C.Structure):   # ptss_glare_level: one level of a pyramid
 GLARE_DTYPE = np.dtype([("r", np.uint64), ("g", np.uint64), ("b", np.uint64), ("zero", np.uint64)])   # ptss_glare_entry
 
 
+# the denoiser of the two linear films (include/ptss_types.h PTSS_FILM_*; csrc/ptlindn.h: an empty pixel's variance, workspace bytes per pixel)
+FILM_LINEAR, FILM_SPLAT = GLARE_FILM_LINEAR, GLARE_FILM_SPLAT
+DENOISE_MAX_LEVELS = 6
+DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES = -1.0, 52
+
+
+class DenoiseLinearParams(C.Structure):   # ptss_denoise_linear_params: the passes and the three tolerances of ptss_denoise_linear
+    _fields_ = [("structSize", C.c_uint), ("levels", C.c_int), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

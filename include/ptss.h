@@ -616,6 +616,40 @@ int ptss_resolve_splat_glare(ptss_context* ctx, const ptss_splat_entry* dev_film
                              ptss_history_entry* dev_linear, ptss_uchar4* dev_pixels, ptss_history_entry* dev_history, void* hipStream);
 int ptss_glare_launches(const ptss_context* ctx, unsigned long long* out3); /* [0] builds, [1] kernels launched inside them, [2] glare resolves */
 
+/* Denoising the two linear films in linear light: an edge-avoiding A-trous filter between the accumulation and the
+ * meter, the glare and the resolve, whose luminance tolerance is each pixel's own measured error — the standard error of its mean
+ * luminance, from the exact moments ptss_accumulate_paths_linear_stats keeps — and whose result is a linear film again, so
+ * ptss_meter_linear, ptss_glare_build (PTSS_GLARE_FILM_LINEAR) and every ptss_resolve_linear* take it as they are. csrc/ptlindn.h has
+ * the arithmetic; its host build (ptss_probe_denoise_linear) is the specification and the device equals it byte for byte.
+ *
+ * ptss_denoise_linear: the whole film. dev_film: width * height entries, ptss_linear_entry or (PTSS_FILM_SPLAT) ptss_splat_entry;
+ * dev_moments: the film's moment rows (on a filtered film they are kept by home pixel and each row's own count applies); dev_features:
+ * what ptss_render_features, ptss_render_features_specular or ptss_ray_features wrote for the film's pixels; dev_workspace:
+ * ptss_denoise_linear_workspace bytes (52 per pixel), the caller's, free again when the call's work on the stream is done; dev_out:
+ * width * height ptss_linear_entry, not the film itself. A pixel without samples (or weight) has no colour: no pass reads it and its
+ * output row is zero. Every other pixel's output row is {m' K, m' K, m' K, samples = K, clamped}, m' the filtered mean rounded to the
+ * film's fixed point and K the entry's samples (a filtered film: its weight rounded to samples, at least 1, clamped = 0): the integer
+ * mean every consumer takes of it is m' exactly. levels = 0 copies the means (the output's resolve, meter and glare bytes are the
+ * input's). The moments are not changed and keep describing the unfiltered samples (ptss_plan_samples_linear goes on reading them).
+ * Asynchronous on hipStream (NULL: the context's); no frame state, serves sharded contexts; two calls sharing a workspace are ordered
+ * by the caller.
+ *
+ * Refused before the device is touched, nothing counted. PTSS_EINVAL: a null ctx or required pointer, a wrong structSize, an unknown
+ * film kind, levels outside [0, 6], a sigma that is not finite and positive, a non-zero reserved, whatever ptss_resolve_linear refuses
+ * about params, a pointer that is not 16-byte aligned, dev_out equal to dev_film, dev_out or dev_film inside the workspace.
+ * PTSS_ERANGE: width or height outside [1, 2^22], width * height >= 2^31.
+ * ptss_default_denoise_linear_params: levels 5, sigmaLuminance 3, sigmaNormal 0.1, sigmaDepth 4 (design choices, not measurements).
+ * ptss_debug_denoise_linear_form: tests and measurements only. 0 (the default): every pass runs the kernel form measured faster at its
+ * spacing; 1: taps from global memory at every spacing; 2: tile and halo staged in LDS wherever that kernel exists; 4 + mask (4 .. 11):
+ * staged at pass k (spacing 2^k, k = 0 .. 2) where bit k of the mask is set. Same bytes whatever the form. */
+int ptss_default_denoise_linear_params(ptss_denoise_linear_params* params);
+int ptss_denoise_linear_workspace(int width, int height, size_t* bytes);
+int ptss_denoise_linear(ptss_context* ctx, const void* dev_film, int filmKind /* PTSS_FILM_LINEAR | PTSS_FILM_SPLAT */, int width, int height,
+                        const ptss_linear_moment* dev_moments, const ptss_pixel_feature* dev_features, const ptss_linear_params* params,
+                        const ptss_denoise_linear_params* denoise, void* dev_workspace, ptss_linear_entry* dev_out, void* hipStream);
+int ptss_denoise_linear_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] calls that launched, [1] kernels inside them */
+int ptss_debug_denoise_linear_form(ptss_context* ctx, int form);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

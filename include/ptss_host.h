@@ -267,6 +267,20 @@ int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, 
                              int height, const ptss_glare_params* glare, const ptss_glare_entry* pyramid, const ptss_meter_state* state,
                              ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
 
+/* The denoiser of the two linear films on the host (csrc/ptlindn.h — the very operations the kernels evaluate; this build is the
+ * specification). ptss_probe_denoise_linear: ptss_denoise_linear as straight loops over host memory, without a workspace. out: width *
+ * height entries, all written. out_plane (may be NULL): width * height rows {c.r, c.g, c.b, v} of the last plane the call computed —
+ * what the last pass made before its finish, or with levels = 0 what prepare made; an empty pixel's row is {0, 0, 0, -1}. On the
+ * device, the plane in front of the last pass is therefore this call's out_plane with one level less. PTSS_HOST_EINVAL: whatever
+ * ptss_denoise_linear refuses, alignment aside (out == film included).
+ * ptss_probe_denoise_linear_finish: the finish of one pixel by itself — the output row (four 64-bit words of a ptss_linear_entry) of
+ * a pixel whose filtered colour is rgb[0..2] and whose film entry has word3 as its fourth word. */
+int ptss_probe_denoise_linear(const void* film, int filmKind, int width, int height, const ptss_linear_moment* moments,
+                              const ptss_pixel_feature* features, const ptss_linear_params* params, const ptss_denoise_linear_params* denoise,
+                              ptss_linear_entry* out, float* out_plane /* may be NULL */);
+int ptss_probe_denoise_linear_finish(const float* rgb, unsigned long long word3, int filmKind, const ptss_linear_params* params,
+                                     unsigned long long* out4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -373,6 +373,21 @@ typedef struct ptss_glare_level {
     unsigned long long first;
 } ptss_glare_level;
 
+/* Denoising a linear or a filtered linear film in linear light (ptss_denoise_linear). The film's kind is one of
+ * PTSS_GLARE_FILM_*; the two names below say the same without the glare. levels in [0, PTSS_DENOISE_MAX_LEVELS]: A-trous passes, tap
+ * spacing 2^i in pass i (0: the film's means, unfiltered); sigmaLuminance: the luminance tolerance in units of the pixel's measured
+ * standard error (it does not halve per pass); sigmaNormal, sigmaDepth: as in ptss_denoise_params. All three finite and positive. */
+#define PTSS_FILM_LINEAR PTSS_GLARE_FILM_LINEAR
+#define PTSS_FILM_SPLAT PTSS_GLARE_FILM_SPLAT
+typedef struct ptss_denoise_linear_params {
+    unsigned int structSize; /* sizeof(ptss_denoise_linear_params) as the caller compiled it */
+    int levels;
+    float sigmaLuminance;
+    float sigmaNormal;
+    float sigmaDepth;
+    uint32_t reserved[3];    /* 0 */
+} ptss_denoise_linear_params;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -461,6 +476,10 @@ static_assert(sizeof(ptss_glare_entry) == 32 && offsetof(ptss_glare_entry, g) ==
               "ptss_glare_entry is two 16-byte rows");
 static_assert(sizeof(ptss_glare_level) == 16 && offsetof(ptss_glare_level, height) == 4 && offsetof(ptss_glare_level, first) == 8,
               "ptss_glare_level is two 32-bit words and one 64-bit word");
+static_assert(sizeof(ptss_denoise_linear_params) == 32 && offsetof(ptss_denoise_linear_params, levels) == 4 &&
+                  offsetof(ptss_denoise_linear_params, sigmaLuminance) == 8 && offsetof(ptss_denoise_linear_params, sigmaDepth) == 16 &&
+                  offsetof(ptss_denoise_linear_params, reserved) == 20,
+              "ptss_denoise_linear_params is eight 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -517,6 +536,10 @@ _Static_assert(sizeof(ptss_glare_entry) == 32 && offsetof(ptss_glare_entry, g) =
                "ptss_glare_entry is two 16-byte rows");
 _Static_assert(sizeof(ptss_glare_level) == 16 && offsetof(ptss_glare_level, height) == 4 && offsetof(ptss_glare_level, first) == 8,
                "ptss_glare_level is two 32-bit words and one 64-bit word");
+_Static_assert(sizeof(ptss_denoise_linear_params) == 32 && offsetof(ptss_denoise_linear_params, levels) == 4 &&
+                   offsetof(ptss_denoise_linear_params, sigmaLuminance) == 8 && offsetof(ptss_denoise_linear_params, sigmaDepth) == 16 &&
+                   offsetof(ptss_denoise_linear_params, reserved) == 20,
+               "ptss_denoise_linear_params is eight 32-bit words");
 #endif
 
 #ifdef __cplusplus
