@@ -5,6 +5,8 @@
   ptss_main         g++ (host only) + libptss      host/main.cpp     headless drop-in of the reference's main(); --gpus N: one
                     + librccl                                       context per GPU, one ncclGather (host/MultiGpu.cpp)
   ptss_mathcheck, ptss_guardcheck   hipcc           tests/csrc/*.hip  device-side checks of the math fast paths (GPU tests run them)
+  ptss_identitycheck hipcc + libptss_host          tests/csrc/math_identity.hip   csrc/ptmath.h on the device against the g++ build of the
+                                                                    same functions (the host probes), bit for bit (tests/test_gpu_math_identity.py)
 (The CPU oracle — test infrastructure — has its own recipe, oracle/build.py; nothing here refers to it.)
 
 Both sides of the parity contract are compiled with -ffp-contract=off and without fast-math
@@ -105,15 +107,29 @@ def build_guardcheck(force=False):
     return out
 
 
+def build_identitycheck(force=False):
+    """ptss_identitycheck: every ptm:: transcendental, the literal tone map and the vector layer on the device against the host probes
+    of libptss_host.so (g++), by exhaustion over the float32 patterns (tests/test_gpu_math_identity.py)."""
+    out = os.path.join(LIBDIR, "ptss_identitycheck")
+    src = os.path.join(ROOT, "tests", "csrc", "math_identity.hip")
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    host = build_host()   # the specification it is linked against
+    if force or _newer(out, [src, host] + _headers()):
+        _run([hipcc] + [f for f in HIP_FLAGS if f != "-fPIC"] + ["-pthread", "-I", INC, "-I", CSRC, src, "-L", LIBDIR, "-lptss_host",
+                                                                 "-Wl,-rpath,$ORIGIN", "-o", out])
+    return out
+
+
 def build_all(force=False):
-    return [build_host(force), build_device(force), build_main(force), build_mathcheck(force), build_guardcheck(force)]
+    return [build_host(force), build_device(force), build_main(force), build_mathcheck(force), build_guardcheck(force),
+            build_identitycheck(force)]
 
 
 if __name__ == "__main__":
     force = "--force" in sys.argv
     what = [a for a in sys.argv[1:] if not a.startswith("-")]
     table = {"host": build_host, "device": build_device, "main": build_main,
-             "mathcheck": build_mathcheck, "guardcheck": build_guardcheck}
+             "mathcheck": build_mathcheck, "guardcheck": build_guardcheck, "identitycheck": build_identitycheck}
     if not what:
         build_all(force)
     for w in what:

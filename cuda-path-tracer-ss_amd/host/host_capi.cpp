@@ -28,6 +28,7 @@
 #include "ptpack.h"
 #include "ptstrip.h"
 #include "pttri.h"
+#include "ptvecops.h"
 #include "xorwow.h"
 
 struct ptss_scene {
@@ -197,6 +198,12 @@ int ptss_probe_math(int op, const float* x, const float* y, float* out, size_t n
             default: return PTSS_HOST_EINVAL;
         }
     }
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_vector(int op, const float* in, float* out, size_t n) {
+    if (!in || !out || op < 0 || op >= ptvecops::kOps) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) ptvecops::apply(op, in + ptvecops::kIn * i, out + ptvecops::kOut * i);
     return PTSS_HOST_OK;
 }
 

@@ -150,6 +150,7 @@ def host_lib():
         L.ptss_write_tga.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
         L.ptss_tile_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
         L.ptss_probe_math.argtypes = [C.c_int, _f32p, _f32p, _f32p, C.c_size_t]
+        L.ptss_probe_vector.argtypes = [C.c_int, _f32p, _f32p, C.c_size_t]
         L.ptss_probe_quantize.argtypes = [_f32p, C.POINTER(C.c_uint), C.c_size_t]
         L.ptss_probe_guard.argtypes = [C.c_int, _f32p, C.POINTER(C.c_uint), C.c_size_t]
         L.ptss_probe_guard_constants.argtypes = [_f32p]

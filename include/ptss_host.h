@@ -54,6 +54,13 @@ int ptss_tile_rows(int height, int band_rows, int rank, int world, int* rows, in
 
 /* Probes (tests only). op: 0 sin, 1 cos, 2 tan, 3 atan, 4 log, 5 exp, 6 pow(x,y), 7 sqrt */
 int ptss_probe_math(int op, const float* x, const float* y, float* out, size_t n);
+/* The vector layer of csrc/ptmath.h (its pinned fma chains), n cases of 12 floats in and 4 floats out each. op (operands -> results;
+ * quaternions as x, y, z, w; results an operation does not have are +0; csrc/ptvecops.h is the one statement of this table, compiled
+ * here and into the device side of tests/csrc/math_identity.hip): 0 dot(in[0..2], in[3..5]) -> out[0]; 1 cross(in[0..2], in[3..5]) ->
+ * out[0..2]; 2 in[0..2] / in[3]; 3 madd(v = in[0..2], s = in[3], o = in[4..6]); 4 madd(a = in[0..2], b = in[3..5], o = in[6..8]);
+ * 5 rotate(q = in[0..3], v = in[4..6]); 6 mul(p = in[0..3], q = in[4..7]) -> out[0..3]; 7 normalize(in[0..2]); 8 normalize(q =
+ * in[0..3]) -> out[0..3]; 9 length(in[0..2]) -> out[0]. PTSS_HOST_EINVAL: a null pointer or an op outside 0..9. */
+int ptss_probe_vector(int op, const float* in, float* out, size_t n);
 /* The range facts behind the guard-free fast paths of the shading code (csrc/ptmath.h; tests/test_guard_ranges.py).
  * ptss_probe_guard: out[i] = 1 or 0 for x[i] under op 0 fast_numerator, 1 fast_divisor, 2 fast_rcp_operand, 3 in_light_window (the
  * one-compare integer form of kLightD2Lo <= x < kLightD2Hi). ptss_probe_guard_constants: out9 = kSqrtLo, kSqrtHi, kRcpLo, kRcpHi,

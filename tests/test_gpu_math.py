@@ -2,7 +2,9 @@
 legitimate because they equal the IEEE results bit for bit. That is proven here by exhaustion on the GPU under test:
 every one of the 2^32 float32 patterns for rcp and sqrt; every one of the 2^46 mantissa pairs for div (~45 s), plus
 the guarded function across an exponent grid and the special values. Likewise the table form of the 8-bit tone map
-(csrc/ptquant.h) against the literal clamp / pow / scale sequence, for every float32 pattern."""
+(csrc/ptquant.h) against the literal clamp / pow / scale sequence, for every float32 pattern.
+Everything here holds device forms against device forms. That the device's literal tone map, its transcendentals and its
+vector layer equal the HOST's — the g++ build the oracle and the probes are — is tests/test_gpu_math_identity.py."""
 import os
 import re
 import subprocess
