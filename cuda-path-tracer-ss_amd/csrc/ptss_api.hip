@@ -30,6 +30,7 @@
 #include "ptmeter.h"
 #include "ptglare.h"
 #include "ptlindn.h"
+#include "ptlinrp.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -166,6 +167,7 @@ struct ptss_context {
     unsigned long long meterLaunches[3] = {0, 0, 0};          // meter histograms, ptss_meter_exposure, metered resolves that launched
     unsigned long long glareLaunches[3] = {0, 0, 0};          // glare builds, the kernels they launched, glare resolves that launched
     unsigned long long linDenoiseLaunches[2] = {0, 0};        // ptss_denoise_linear calls that launched, the kernels inside them
+    unsigned long long linReprojectLaunches = 0;              // ptss_reproject_linear calls that launched
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
@@ -1824,6 +1826,54 @@ int ptss_debug_denoise_linear_form(ptss_context* c, int form) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (form < 0 || form == 3 || form > 11) return fail(PTSS_EINVAL, "form must be 0, 1, 2 or 4 .. 11");
     c->linDenoiseForm = form;
+    return PTSS_OK;
+}
+
+// ---- carrying the two linear films across a camera move (ptss_linreproject.hip; csrc/ptlinrp.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_reproject_linear_params(ptss_reproject_linear_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_reproject_linear_params);
+    p->cosNormal = 0.9f;   // ptss_default_reproject_params' tests; a cap of 64 samples of history (design choices, not measurements)
+    p->depthTolerance = 0.02f;
+    p->minCoverage = 0.25f;
+    p->maxHistory = 64u;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+int ptss_reproject_linear(ptss_context* c, const ptss_film_camera* now, const ptss_pixel_feature* dev_features_now,
+                          const ptss_pixel_motion* dev_motion_now, const ptss_film_camera* prev, const ptss_pixel_feature* dev_features_prev,
+                          const void* dev_film_prev, int filmKind, const ptss_linear_moment* dev_moments_prev, const ptss_linear_params* film,
+                          const ptss_reproject_linear_params* params, void* dev_film_out, ptss_linear_moment* dev_moments_out,
+                          ptss_reproject_linear_info* dev_info, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    // in the order of the header's list: null pointers, structSize and parameter ranges, the cameras, the film's parameters, the kind,
+    // moments on one side only, alignment, overlap
+    if (!now || !prev || !film || !params || !dev_features_now || !dev_features_prev || !dev_film_prev || !dev_film_out)
+        return fail(PTSS_EINVAL, "null camera, parameters, features, previous film or output film");
+    if (const char* what = ptlrp::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlrp::cameraError(now)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlrp::cameraError(prev)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlin::paramsError(film)) return fail(PTSS_EINVAL, what);
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return fail(PTSS_EINVAL, "unknown film kind");
+    if ((dev_moments_prev == nullptr) != (dev_moments_out == nullptr))
+        return fail(PTSS_EINVAL, "dev_moments_prev and dev_moments_out must be given together or not at all");
+    if (((uintptr_t)dev_features_now | (uintptr_t)dev_motion_now | (uintptr_t)dev_features_prev | (uintptr_t)dev_film_prev | (uintptr_t)dev_moments_prev |
+         (uintptr_t)dev_film_out | (uintptr_t)dev_moments_out) & 15u)
+        return fail(PTSS_EINVAL, "features, motion, films and moments must be 16-byte aligned");
+    if ((uintptr_t)dev_info & 7u) return fail(PTSS_EINVAL, "dev_info must be 8-byte aligned");
+    if (const char* what = ptlrp::buffersError(now, dev_features_now, prev, dev_features_prev, dev_film_prev, dev_moments_prev, dev_film_out, dev_moments_out))
+        return fail(PTSS_EINVAL, what);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchLinearReproject(streamOf(c, hipStream), *now, dev_features_now, dev_motion_now, *prev, dev_features_prev, dev_film_prev,
+                                        filmKind == PTSS_FILM_SPLAT, dev_moments_prev, *film, *params, dev_film_out, dev_moments_out, dev_info,
+                                        &c->linReprojectLaunches));
+    return PTSS_OK;
+}
+
+int ptss_reproject_linear_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->linReprojectLaunches;
     return PTSS_OK;
 }
 

@@ -281,6 +281,14 @@ hipError_t launchGlareBuild(hipStream_t st, const void* film, bool splat, int wi
 hipError_t launchLinearDenoise(hipStream_t st, const void* film, bool splat, int width, int height, const void* moments, const void* features,
                                const ptss_linear_params& params, const ptss_denoise_linear_params& denoise, int form, void* workspace, void* out,
                                unsigned long long* launches);
+// seeding a linear film from the previous pose's (ptss_linreproject.hip; ptss_reproject_linear). Every film, moment and
+// feature buffer holds 32 B per pixel of its camera; motionNow, momentsPrev / momentsOut (together) and info may be null. *launches is
+// incremented when the kernel launched. Everything checked by the caller (ptlrp::cameraError, ptlrp::paramsError, ptlin::paramsError).
+// No bit of ptss_launched_kernels
+hipError_t launchLinearReproject(hipStream_t st, const ptss_film_camera& now, const void* featuresNow, const void* motionNow,
+                                 const ptss_film_camera& prev, const void* featuresPrev, const void* filmPrev, bool splat, const void* momentsPrev,
+                                 const ptss_linear_params& film, const ptss_reproject_linear_params& params, void* filmOut, void* momentsOut,
+                                 void* info, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

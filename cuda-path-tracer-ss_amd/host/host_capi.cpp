@@ -19,6 +19,7 @@
 #include "ptmeter.h"
 #include "ptglare.h"
 #include "ptlindn.h"
+#include "ptlinrp.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -1047,6 +1048,77 @@ int ptss_probe_denoise_linear_finish(const float* rgb, unsigned long long word3,
     const bool splat = filmKind == PTSS_FILM_SPLAT;
     const ptldn::Row row{v3(rgb[0], rgb[1], rgb[2]), ptldn::weightOf(word3, splat) == 0ull ? ptldn::kEmpty : 0.f};
     ptldn::finishRow(row, word3, splat, R, out4);
+    return PTSS_HOST_OK;
+}
+
+// ---- carrying the two linear films across a camera move (csrc/ptlinrp.h) ----
+extern "C++" {
+template <bool Moments>
+static void probeReprojectLinear(const ptcam::Film& now, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                                 const ptlrp::Prev& prev, const ptss_pixel_feature* features_prev, const unsigned long long* film_prev, bool splat,
+                                 const ptss_linear_moment* moments_prev, const ptlrp::Rule& R, unsigned long long* film_out,
+                                 ptss_linear_moment* moments_out, ptss_reproject_linear_info* info) {
+    auto materialAt = [&](size_t q) { return features_prev[q].materialIdx; };
+    auto geometryAt = [&](size_t q) { return ptrp::Geometry{features_prev[q].normal, features_prev[q].depth}; };
+    auto entryAt = [&](size_t q, unsigned long long* e) {
+        for (int k = 0; k < 4; ++k) e[k] = film_prev[4 * q + k];
+    };
+    auto momentAt = [&](size_t q, unsigned long long* m) {
+        m[0] = moments_prev[q].sumY, m[1] = moments_prev[q].sqLo, m[2] = moments_prev[q].sqHi, m[3] = moments_prev[q].samples;
+    };
+    for (int y = 0; y < now.height; ++y)
+        for (int x = 0; x < now.width; ++x) {
+            const size_t p = (size_t)y * (size_t)now.width + (size_t)x;
+            const ptdn::Feature fp{features_now[p].normal, features_now[p].depth, features_now[p].materialIdx};
+            auto pointOf = [&](vec3 o, vec3 d) -> vec3 { return motion_now ? vec3(motion_now[p].prevPoint) : madd(d, fp.depth, o); };
+            ptlrp::Seed s;
+            ptlrp::seedPixel<Moments>(x, y, fp, now, prev, R, splat, pointOf, materialAt, geometryAt, entryAt, momentAt, s);
+            for (int k = 0; k < 4; ++k) film_out[4 * p + k] = s.film[k];
+            if (Moments) moments_out[p] = ptss_linear_moment{s.moment[0], s.moment[1], s.moment[2], s.moment[3]};
+            if (info) {
+                info->seeded += s.status == ptlrp::kSeeded;
+                info->offFilm += s.status == ptlrp::kOffFilm;
+                info->noTap += s.status == ptlrp::kNoTap;
+                info->noVariance += s.noVariance;
+            }
+        }
+}
+}   // extern "C++"
+
+int ptss_probe_reproject_linear(const ptss_film_camera* now, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                                const ptss_film_camera* prev, const ptss_pixel_feature* features_prev, const void* film_prev, int filmKind,
+                                const ptss_linear_moment* moments_prev, const ptss_linear_params* film,
+                                const ptss_reproject_linear_params* params, void* film_out, ptss_linear_moment* moments_out,
+                                ptss_reproject_linear_info* info) {
+    if (!now || !prev || !film || !params) return PTSS_HOST_EINVAL;
+    if (ptlrp::paramsError(params) || ptlrp::cameraError(now) || ptlrp::cameraError(prev) || ptlin::paramsError(film)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if (ptlrp::buffersError(now, features_now, prev, features_prev, film_prev, moments_prev, film_out, moments_out)) return PTSS_HOST_EINVAL;
+    const ptcam::Film F = ptlrp::nowOf(*now);
+    const ptlrp::Prev P = ptlrp::prevOf(*prev);
+    const ptlrp::Rule R = ptlrp::ruleOf(*params, *film);
+    const bool splat = filmKind == PTSS_FILM_SPLAT;
+    if (moments_prev)
+        probeReprojectLinear<true>(F, features_now, motion_now, P, features_prev, static_cast<const unsigned long long*>(film_prev), splat, moments_prev,
+                                   R, static_cast<unsigned long long*>(film_out), moments_out, info);
+    else
+        probeReprojectLinear<false>(F, features_now, motion_now, P, features_prev, static_cast<const unsigned long long*>(film_prev), splat, nullptr, R,
+                                    static_cast<unsigned long long*>(film_out), nullptr, info);
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_reproject_linear_finish(const float* h, float w, int hasVariance, float s2, int filmKind, const ptss_linear_params* film,
+                                       const ptss_reproject_linear_params* params, unsigned long long* film4, unsigned long long* moment4) {
+    if (!h || !film4 || !moment4 || ptlin::paramsError(film) || ptlrp::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if (hasVariance && !(s2 >= 0.f && s2 <= ptlrp::kMaxVariance)) return PTSS_HOST_EINVAL;
+    const ptlrp::Rule R = ptlrp::ruleOf(*params, *film);
+    const float kf = ptlrp::historyCount(w, R.maxHistory);
+    for (int k = 0; k < 4; ++k) film4[k] = moment4[k] = 0ull;
+    if (!(kf >= 1.0f)) return PTSS_HOST_OK;
+    unsigned long long m[3];
+    ptlrp::filmRow(v3(h[0], h[1], h[2]), (unsigned long long)kf, filmKind == PTSS_FILM_SPLAT, R, m, film4);
+    ptlrp::momentRow(m, (unsigned long long)kf, hasVariance != 0, s2, moment4);
     return PTSS_HOST_OK;
 }
 

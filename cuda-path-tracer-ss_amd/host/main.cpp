@@ -59,6 +59,13 @@
 //                                   pixel-centre rays, and ptss_denoise_linear (default parameters; levels default 5, sigmaLuminance default 3)
 //                                   makes the linear film that --auto-exposure's meter (every round), --glare, the resolve and image.pfm then
 //                                   read. Levels 0 and the absent flag write the same bytes
+//             [--carry KEYS[,maxHistory]]   with --film and --linear, with or without --filter, --refill, --auto-exposure, --glare and
+//                                   --denoise-linear: the film is carried across a camera move — after --keys, --ticks rounds
+//                                   with the luminance moments at that pose; the features of the pixel-centre rays; KEYS move the camera; the
+//                                   features again; ptss_reproject_linear (default parameters; maxHistory default 64) seeds a new film and new
+//                                   moments; --ticks more rounds accumulate into them, and the usual tail runs. Prints the four counters of
+//                                   ptss_reproject_linear_info. Not with --adaptive or --adaptive-linear: the combination is left out to keep
+//                                   this program's matrix small. Without the flag every byte written is today's
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -98,6 +105,9 @@ int main(int argc, char* argv[]) {
     bool denoiseLinear = false;                       // --denoise-linear: the linear film is denoised in front of the meter, the glare and the resolve
     int denoiseLinearLevels = -1;                     // ... its levels and sigmaLuminance when given
     float denoiseLinearSigma = -1.f;
+    bool carry = false;                               // --carry: the linear film is carried across a second camera move
+    std::string carryKeys;                            // ... the keys of that move, and the cap of the history count when given
+    long carryHistory = -1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -178,6 +188,21 @@ int main(int argc, char* argv[]) {
                 }
             }
         }
+        else if (a == "--carry") {
+            carry = true;
+            carryKeys = next();
+            const size_t comma = carryKeys.find(',');
+            if (comma != std::string::npos) {
+                char* end = NULL;
+                carryHistory = strtol(carryKeys.c_str() + comma + 1, &end, 10);
+                if (end == carryKeys.c_str() + comma + 1 || *end != 0 || carryHistory < 1 || carryHistory > (1l << 23) - 1) carryHistory = 0;
+                carryKeys.erase(comma);
+            }
+            if (carryKeys.empty() || carryKeys.find_first_not_of("wasdqefhgt") != std::string::npos || carryHistory == 0) {
+                fprintf(stderr, "bad --carry (KEYS[,maxHistory]: keys of wasdqe fhgt, maxHistory 1 .. 8388607)\n");
+                return 2;
+            }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -233,6 +258,7 @@ int main(int argc, char* argv[]) {
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
     if (denoiseLinear && linear < 0.f) { fprintf(stderr, "--denoise-linear needs --film and --linear\n"); return 2; }
+    if (carry && (linear < 0.f || adaptiveLinear >= 0 || ticks < 1)) { fprintf(stderr, "--carry needs --film, --linear, at least one tick and no --adaptive-linear\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -408,7 +434,7 @@ int main(int argc, char* argv[]) {
             if (!splat.empty() && hipMalloc(&dPos, n * sizeof(ptss_film_position)) != hipSuccess) { fprintf(stderr, "--filter: device buffers\n"); return 1; }
         }
         if (autoExposure) {   // every round meters into a histogram of its own, zeroed here: nothing is cleared between the rounds' launches
-            const size_t rounds = (ticks > 0 ? (size_t)ticks : 1) + (adaptiveLinear > 0 ? (size_t)adaptiveLinear : 0);
+            const size_t rounds = (ticks > 0 ? (size_t)ticks : 1) * (carry ? 2 : 1) + (adaptiveLinear > 0 ? (size_t)adaptiveLinear : 0);
             if (hipMalloc(&dBins, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMalloc(&dMeter, sizeof(ptss_meter_state)) != hipSuccess ||
                 hipMemset(dBins, 0, rounds * PTSS_METER_BINS * sizeof(uint32_t)) != hipSuccess || hipMemset(dMeter, 0, sizeof(ptss_meter_state)) != hipSuccess ||
                 hipDeviceSynchronize() != hipSuccess) {
@@ -432,7 +458,24 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
         }
-        const bool keepMoments = adaptiveLinear >= 0 || denoiseLinear;   // the rounds accumulate with stats
+        // --carry: the features of both poses, the seeded film and moments (swapped with the rounds' own after the call), the counters
+        void *dCarryPrev = nullptr, *dCarryNow = nullptr, *dCarryFilm = nullptr, *dCarryMoments = nullptr, *dCarryInfo = nullptr;
+        ptss_reproject_linear_params carryParams;
+        PTSS_HANDLE(ptss_default_reproject_linear_params(&carryParams));
+        if (carryHistory > 0) carryParams.maxHistory = (uint32_t)carryHistory;
+        if (carry) {
+            if (hipMalloc(&dCarryPrev, n * sizeof(ptss_pixel_feature)) != hipSuccess || hipMalloc(&dCarryNow, n * sizeof(ptss_pixel_feature)) != hipSuccess ||
+                hipMalloc(&dCarryFilm, n * sizeof(ptss_linear_entry)) != hipSuccess || hipMalloc(&dCarryMoments, n * sizeof(ptss_linear_moment)) != hipSuccess ||
+                hipMalloc(&dCarryInfo, sizeof(ptss_reproject_linear_info)) != hipSuccess ||
+                hipMemset(dCarryInfo, 0, sizeof(ptss_reproject_linear_info)) != hipSuccess ||
+                (!dMoments && (hipMalloc(&dMoments, n * sizeof(ptss_linear_moment)) != hipSuccess ||
+                               hipMemset(dMoments, 0, n * sizeof(ptss_linear_moment)) != hipSuccess)) ||
+                hipDeviceSynchronize() != hipSuccess) {
+                fprintf(stderr, "--carry: device buffers\n");
+                return 1;
+            }
+        }
+        const bool keepMoments = adaptiveLinear >= 0 || denoiseLinear || carry;   // the rounds accumulate with stats
         // what the meter, the glare and the resolves read: the denoised film, a linear one whatever the rounds fill, or the rounds' own
         const void* shown = denoiseLinear ? dClean : dLinear;
         const bool shownSplat = !denoiseLinear && dPos;
@@ -482,7 +525,31 @@ int main(int argc, char* argv[]) {
             PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dRays, (ptss_pixel_feature*)dCleanFeat, n, NULL));
             fc.jitter = 1;
         }
-        for (int t = 0; t < ticks; ++t) {
+        auto centreFeatures = [&](void* features) -> int {   // (jitter 0 draws nothing: the streams stay what the rounds expect)
+            fc.jitter = 0;
+            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, NULL));
+            PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dRays, (ptss_pixel_feature*)features, n, NULL));
+            fc.jitter = 1;
+            return 0;
+        };
+        auto carryFilm = [&]() -> int {   // the move of --carry: the film of the pose so far seeds the film of the next
+            if (centreFeatures(dCarryPrev)) return 1;
+            ptss_film_camera before = fc;
+            for (char k : carryKeys) moveCamera(data->camera, (unsigned char)k);
+            PTSS_HANDLE(ptss_set_camera(ctx, &data->camera));
+            fc.camera = data->camera;
+            if (centreFeatures(dCarryNow)) return 1;
+            if (denoiseLinear && centreFeatures(dCleanFeat)) return 1;   // the denoiser is guided by the new pose's features from here on
+            PTSS_HANDLE(ptss_reproject_linear(ctx, &fc, (const ptss_pixel_feature*)dCarryNow, NULL, &before, (const ptss_pixel_feature*)dCarryPrev, dLinear,
+                                              dPos ? PTSS_FILM_SPLAT : PTSS_FILM_LINEAR, (const ptss_linear_moment*)dMoments, &linearParams, &carryParams,
+                                              dCarryFilm, (ptss_linear_moment*)dCarryMoments, (ptss_reproject_linear_info*)dCarryInfo, NULL));
+            std::swap(dLinear, dCarryFilm);
+            std::swap(dMoments, dCarryMoments);
+            if (!denoiseLinear) shown = dLinear;
+            return 0;
+        };
+        for (int t = 0; t < (carry ? 2 * ticks : ticks); ++t) {
+            if (carry && t == ticks && carryFilm()) return 1;
             if (dPos) {
                 PTSS_HANDLE(ptss_generate_rays_positions(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays, (ptss_film_position*)dPos, NULL));
             } else {
@@ -563,6 +630,12 @@ int main(int argc, char* argv[]) {
             printf("adaptive: rounds %d totalWeight %llu activePixels %u unsampledPixels %u cappedPixels %u uniform %u\n", adaptive, info.totalWeight,
                    info.activePixels, info.unsampledPixels, info.cappedPixels, info.uniform);
         }
+        if (carry) {
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            ptss_reproject_linear_info info;
+            if (hipMemcpy(&info, dCarryInfo, sizeof(info), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--carry: read-back\n"); return 1; }
+            printf("carry: seeded %llu offFilm %llu noTap %llu noVariance %llu\n", info.seeded, info.offFilm, info.noTap, info.noVariance);
+        }
         if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
             if (denoiseLinear && (!autoExposure || ticks <= 0) && denoiseFilm()) return 1;   // (with a meter the last round's denoised film stands)
             if (autoExposure) {   // (the last round's metered resolve stands; without a round the new state's exposure, 0, shows black)
@@ -620,7 +693,7 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid, dClean, dCleanFeat, dCleanWork}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid, dClean, dCleanFeat, dCleanWork, dCarryPrev, dCarryNow, dCarryFilm, dCarryMoments, dCarryInfo}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);

@@ -22,6 +22,7 @@ from ptss_types import MOMENT_DTYPE, LinearMoment, LinearPlanParams
 from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SPLAT, GLARE_MAX_LEVELS, GLARE_MIX, GLARE_TAIL_ENTRIES, GLARE_TILE, GlareLevel,
                         GlareParams)
 from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DENOISE_MAX_LEVELS, FILM_LINEAR, FILM_SPLAT, DenoiseLinearParams
+from ptss_types import REPROJECT_LINEAR_INFO_DTYPE, REPROJECT_LINEAR_MAX_HISTORY, ReprojectLinearParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -220,6 +221,11 @@ def host_lib():
         L.ptss_probe_denoise_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LinearParams),
                                                 C.POINTER(DenoiseLinearParams), C.c_void_p, C.c_void_p]
         L.ptss_probe_denoise_linear_finish.argtypes = [C.POINTER(C.c_float), C.c_ulonglong, C.c_int, C.POINTER(LinearParams), C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_reproject_linear.argtypes = [C.POINTER(FilmCamera), C.c_void_p, C.c_void_p, C.POINTER(FilmCamera), C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_void_p, C.POINTER(LinearParams), C.POINTER(ReprojectLinearParams), C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        L.ptss_probe_reproject_linear_finish.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(LinearParams),
+                                                         C.POINTER(ReprojectLinearParams), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         _host = L
     return _host
 
@@ -347,6 +353,10 @@ def device_lib():
         L.ptss_denoise_linear.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(LinearParams), C.POINTER(DenoiseLinearParams), vp, vp, vp]
         L.ptss_denoise_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_denoise_linear_form.argtypes = [vp, C.c_int]
+        L.ptss_default_reproject_linear_params.argtypes = [C.POINTER(ReprojectLinearParams)]
+        L.ptss_reproject_linear.argtypes = [vp, C.POINTER(FilmCamera), vp, vp, C.POINTER(FilmCamera), vp, vp, C.c_int, vp, C.POINTER(LinearParams),
+                                            C.POINTER(ReprojectLinearParams), vp, vp, vp, vp]
+        L.ptss_reproject_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1123,6 +1133,80 @@ def probe_denoise_linear_finish(rgb, word3, film_kind="linear", params=None):
     if rc != 0:
         raise PtssError(f"ptss_probe_denoise_linear_finish: {rc}")
     return tuple(int(v) for v in out)
+
+
+# ---- carrying the two linear films across a camera move (ptss_reproject_linear) ----
+def reproject_linear_params(cos_normal=0.9, depth_tolerance=0.02, min_coverage=0.25, max_history=64):
+    """A ptss_reproject_linear_params; the defaults are ptss_default_reproject_linear_params' (design choices, not measurements)."""
+    p = ReprojectLinearParams()
+    p.structSize = C.sizeof(ReprojectLinearParams)
+    p.cosNormal, p.depthTolerance, p.minCoverage, p.maxHistory, p.reserved = float(cos_normal), float(depth_tolerance), float(min_coverage), int(max_history), 0
+    return p
+
+
+def _feature_rows(features, pixels, what):
+    ft = np.ascontiguousarray(np.asarray(features))
+    ft = ft.view(np.float32).reshape(-1, 8) if ft.dtype == FEATURE_DTYPE else np.ascontiguousarray(ft, dtype=np.float32)
+    if ft.ndim != 2 or ft.shape[1] != 8 or len(ft) != pixels:
+        raise ValueError(f"{what}: one FEATURE_DTYPE row (or 8 float32) per pixel of its film")
+    return ft
+
+
+def _reproject_linear_inputs(now, features_now, motion_now, prev, features_prev, film_prev, film_kind, moments_prev):
+    """The buffers of a reproject_linear call as plain rows: (features_now, motion_now or None, features_prev, film_prev, kind, moments_prev
+    or None)."""
+    Pn, Pp = int(now.width) * int(now.height), int(prev.width) * int(prev.height)
+    if Pn <= 0 or Pp <= 0:
+        raise ValueError("the films' width and height must be positive")
+    f, kind = _glare_film(film_prev, film_kind, prev.width, prev.height)
+    fn, fp = _feature_rows(features_now, Pn, "features_now"), _feature_rows(features_prev, Pp, "features_prev")
+    mo = None
+    if motion_now is not None:
+        mo = np.ascontiguousarray(motion_now, dtype=MOTION_DTYPE).reshape(-1)
+        if len(mo) != Pn:
+            raise ValueError("motion_now: one row per pixel of the new film")
+    m = None
+    if moments_prev is not None:
+        m = _rows(moments_prev, MOMENT_DTYPE, 4, np.uint64, "moments_prev")
+        if len(m) != Pp:
+            raise ValueError("moments_prev: one row per pixel of the previous film")
+    return fn, mo, fp, f, kind, m
+
+
+def probe_reproject_linear(now, features_now, prev, features_prev, film_prev, moments_prev=None, params=None, reproject=None, film_kind=None,
+                           motion_now=None):
+    """ptss_reproject_linear on the host (csrc/ptlinrp.h; the specification of the device's rows) -> (the seeded film: (now.width *
+    now.height,) LINEAR_DTYPE or SPLAT_DTYPE, the kind of film_prev; its moments, (P,) MOMENT_DTYPE, or None without moments_prev; the
+    info, a REPROJECT_LINEAR_INFO_DTYPE record). now, prev: film_camera()s; features_*: FEATURE_DTYPE rows of each film's centre rays;
+    film_prev: (P',) LINEAR_DTYPE or SPLAT_DTYPE, or (P', 4) uint64 with film_kind; params: the film's linear_params; reproject: a
+    reproject_linear_params."""
+    fn, mo, fp, f, kind, m = _reproject_linear_inputs(now, features_now, motion_now, prev, features_prev, film_prev, film_kind, moments_prev)
+    params = params if params is not None else linear_params()
+    reproject = reproject if reproject is not None else reproject_linear_params()
+    out = np.zeros((len(fn), 4), dtype=np.uint64)
+    mout = np.zeros((len(fn), 4), dtype=np.uint64) if m is not None else None
+    info = np.zeros(1, dtype=REPROJECT_LINEAR_INFO_DTYPE)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = host_lib().ptss_probe_reproject_linear(C.byref(now), ptr(fn), ptr(mo), C.byref(prev), ptr(fp), ptr(f), kind, ptr(m), C.byref(params),
+                                                C.byref(reproject), ptr(out), ptr(mout), ptr(info))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_reproject_linear: {rc}")
+    out = out.view(SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE).reshape(-1)
+    return out, (mout.view(MOMENT_DTYPE).reshape(-1) if mout is not None else None), info[0]
+
+
+def probe_reproject_linear_finish(h, w, s2=None, film_kind="linear", params=None, reproject=None):
+    """Steps 4's rounding to 6 of ptss_reproject_linear for one pixel on the host: the reprojected mean h (three floats), the
+    interpolated count w and the interpolated per-sample variance s2 (None: no tap carried one) -> (the film row, the moment row), four
+    Python integers each."""
+    params = params if params is not None else linear_params()
+    reproject = reproject if reproject is not None else reproject_linear_params()
+    c, f4, m4 = (C.c_float * 3)(*[float(v) for v in h]), (C.c_ulonglong * 4)(), (C.c_ulonglong * 4)()
+    rc = host_lib().ptss_probe_reproject_linear_finish(c, float(w), 0 if s2 is None else 1, 0.0 if s2 is None else float(s2),
+                                                       int(_GLARE_FILMS.get(film_kind, film_kind)), C.byref(params), C.byref(reproject), f4, m4)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_reproject_linear_finish: {rc}")
+    return tuple(int(v) for v in f4), tuple(int(v) for v in m4)
 
 
 def default_denoise_params(**overrides):
@@ -2277,6 +2361,53 @@ class Renderer:
         """ptss_debug_denoise_linear_form (tests and measurements): 0 the measured form per spacing, 1 taps from global memory, 2 staged in
         LDS wherever that kernel exists, 4 + mask staged at pass k where bit k of the mask (0 .. 7) is set. The bytes are the same."""
         _check(device_lib().ptss_debug_denoise_linear_form(self._ctx, int(form)))
+
+    # --- carrying the two linear films across a camera move (ptss_reproject_linear) ------------------
+    def reproject_linear(self, now, features_now, prev, features_prev, film_prev, moments_prev=None, params=None, reproject=None, film_kind=None,
+                         motion_now=None, out=None, moments_out=None, info=None):
+        """ptss_reproject_linear: the previous pose's film seeds the new pose's. now, prev: film_camera()s; params: the film's
+        linear_params; reproject: a reproject_linear_params.
+        numpy: features_* FEATURE_DTYPE rows of each film's centre rays, film_prev (P',) LINEAR_DTYPE or SPLAT_DTYPE (or (P', 4) uint64
+        with film_kind), moments_prev (P',) MOMENT_DTYPE or None, motion_now (P,) MOTION_DTYPE or None -> (the seeded film, its kind
+        film_prev's; its moments or None; the info as a REPROJECT_LINEAR_INFO_DTYPE record). info: the counters' content beforehand.
+        torch: features (P, 8) float32, film_prev and moments_prev (P', 4) int64, motion_now (P, 4) float32 or None; out and moments_out
+        (P, 4) int64 device tensors WRITTEN IN PLACE, info a (4,) int64 device tensor ADDED TO or None -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        reproject = reproject if reproject is not None else reproject_linear_params()
+        if type(film_prev).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, Pn, Pp = film_prev.device, int(now.width) * int(now.height), int(prev.width) * int(prev.height)
+            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
+            d_fn = self._torch_ptr(features_now, "features_now", "float32", 8, dev, Pn)
+            d_fp = self._torch_ptr(features_prev, "features_prev", "float32", 8, dev, Pp)
+            d_film = self._torch_ptr(film_prev, "film_prev", "int64", 4, None, Pp)
+            d_mom = self._torch_ptr(moments_prev, "moments_prev", "int64", 4, dev, Pp) if moments_prev is not None else None
+            d_mot = self._torch_ptr(motion_now, "motion_now", "float32", 4, dev, Pn) if motion_now is not None else None
+            d_out = self._torch_ptr(out, "out", "int64", 4, dev, Pn)
+            d_mout = self._torch_ptr(moments_out, "moments_out", "int64", 4, dev, Pn) if moments_out is not None else None
+            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
+            _check(L.ptss_reproject_linear(self._ctx, C.byref(now), d_fn, d_mot, C.byref(prev), d_fp, d_film, kind, d_mom, C.byref(params),
+                                           C.byref(reproject), d_out, d_mout, d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        fn, mo, fp, f, kind, m = _reproject_linear_inputs(now, features_now, motion_now, prev, features_prev, film_prev, film_kind, moments_prev)
+        res = np.zeros((len(fn), 4), dtype=np.uint64)
+        mres = np.zeros((len(fn), 4), dtype=np.uint64) if m is not None else None
+        inf = np.zeros(1, dtype=REPROJECT_LINEAR_INFO_DTYPE)
+        if info is not None:
+            inf[0] = info
+        self._round_trip([fn, mo, fp, f, m, res, mres, inf],
+                         lambda d: _check(L.ptss_reproject_linear(self._ctx, C.byref(now), d[0], d[1], C.byref(prev), d[2], d[3], kind, d[4],
+                                                                  C.byref(params), C.byref(reproject), d[5], d[6], d[7], None)), read=(5, 6, 7))
+        res = res.view(SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE).reshape(-1)
+        return res, (mres.view(MOMENT_DTYPE).reshape(-1) if mres is not None else None), inf[0]
+
+    def reproject_linear_launches(self):
+        """ptss_reproject_linear_launches: the reproject_linear calls that launched since the context was created."""
+        out = C.c_ulonglong(0)
+        _check(device_lib().ptss_reproject_linear_launches(self._ctx, C.byref(out)))
+        return int(out.value)
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

@@ -216,6 +216,19 @@ class DenoiseLinearParams(C.Structure):   # ptss_denoise_linear_params: the pass
                 ("reserved", C.c_uint32 * 3)]
 
 
+# carrying the two linear films across a camera move (ptss_reproject_linear)
+REPROJECT_LINEAR_MAX_HISTORY = (1 << 23) - 1
+
+
+class ReprojectLinearParams(C.Structure):   # ptss_reproject_linear_params: the tap tests and the cap of the history count
+    _fields_ = [("structSize", C.c_uint), ("cosNormal", C.c_float), ("depthTolerance", C.c_float), ("minCoverage", C.c_float),
+                ("maxHistory", C.c_uint32), ("reserved", C.c_uint)]
+
+
+# ptss_reproject_linear_info: what a call adds to the caller's four counters
+REPROJECT_LINEAR_INFO_DTYPE = np.dtype([("seeded", np.uint64), ("offFilm", np.uint64), ("noTap", np.uint64), ("noVariance", np.uint64)])
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

@@ -650,6 +650,40 @@ int ptss_denoise_linear(ptss_context* ctx, const void* dev_film, int filmKind /*
 int ptss_denoise_linear_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] calls that launched, [1] kernels inside them */
 int ptss_debug_denoise_linear_form(ptss_context* ctx, int form);
 
+/* Carrying the two linear films across a camera move: the previous pose's film SEEDS the new pose's film once. For
+ * each pixel of the `now` film the call looks the previous film up through the first-hit features (four bilinear taps, a tap counting
+ * only where material, normal and depth agree and the previous entry is not empty) and writes {m' K, m' K, m' K, K}: the reprojected
+ * mean m' at the film's fixed point times an integer history count K <= maxHistory, with a moment row whose standard error is the
+ * reprojected per-sample variance over K. From there the film is an ordinary film: ptss_accumulate_paths_linear*, ptss_splat_paths*
+ * add to it, ptss_plan_samples_linear, ptss_denoise_linear, the meters, ptss_glare_build and every linear resolve take it as it is, and
+ * the history fades by itself as samples arrive. A pixel without history (disoccluded, off the previous film) is an all-zero row: the
+ * plan ranks it "unsampled". csrc/ptlinrp.h has the arithmetic; its host build (ptss_probe_reproject_linear) is the specification
+ * and the device equals it byte for byte.
+ *
+ * now, prev: the two poses' film cameras; they may differ in kind and size, prev->width x prev->height being the size of
+ * dev_features_prev, dev_film_prev and dev_moments_prev. `jitter` of both is not read: the centre ray is always used, and
+ * dev_features_now / dev_features_prev are ptss_ray_features of exactly those rays (ptss_generate_rays with jitter = 0).
+ * dev_motion_now (may be NULL): where each hit point was in the previous pose; valid only when the `now` film is the context's own
+ * pinhole camera at the context's size, because that is where ptss_render_features_motion writes rows — the call cannot check more
+ * than the pointer. dev_film_prev / dev_film_out: ptss_linear_entry or (PTSS_FILM_SPLAT) ptss_splat_entry, both the same kind;
+ * dev_film_out has now->width * now->height entries, all written. dev_moments_prev (may be NULL) and dev_moments_out are given
+ * together or not at all. dev_info (may be NULL): four counters the call ADDS to; the caller zero-fills.
+ * Asynchronous on hipStream (NULL: the context's); no frame state, no bit of ptss_launched_kernels, serves sharded contexts.
+ *
+ * Refused with PTSS_EINVAL before the device is touched, nothing written or counted: a null ctx or required pointer, a wrong
+ * structSize, a parameter outside its range, a camera ptss_generate_rays refuses, a side above 2^22 or width * height >= 2^31, whatever
+ * ptss_resolve_linear refuses about `film`, an unknown film kind, moments given on one side only, a film, moment or feature pointer
+ * that is not 16-byte aligned (dev_info: 8), an output range that overlaps the previous film or moments or the other output. */
+int ptss_default_reproject_linear_params(ptss_reproject_linear_params* params);
+int ptss_reproject_linear(ptss_context* ctx, const ptss_film_camera* now, const ptss_pixel_feature* dev_features_now,
+                          const ptss_pixel_motion* dev_motion_now /* may be NULL */, const ptss_film_camera* prev,
+                          const ptss_pixel_feature* dev_features_prev, const void* dev_film_prev,
+                          int filmKind /* PTSS_FILM_LINEAR | PTSS_FILM_SPLAT */, const ptss_linear_moment* dev_moments_prev /* may be NULL */,
+                          const ptss_linear_params* film, const ptss_reproject_linear_params* params, void* dev_film_out,
+                          ptss_linear_moment* dev_moments_out /* NULL exactly when dev_moments_prev is */,
+                          ptss_reproject_linear_info* dev_info /* may be NULL */, void* hipStream);
+int ptss_reproject_linear_launches(const ptss_context* ctx, unsigned long long* out); /* calls that launched */
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

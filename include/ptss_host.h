@@ -288,6 +288,21 @@ int ptss_probe_denoise_linear(const void* film, int filmKind, int width, int hei
 int ptss_probe_denoise_linear_finish(const float* rgb, unsigned long long word3, int filmKind, const ptss_linear_params* params,
                                      unsigned long long* out4);
 
+/* Carrying the two linear films across a camera move on the host (csrc/ptlinrp.h — the very operations the kernel evaluates; this
+ * build is the specification). ptss_probe_reproject_linear: ptss_reproject_linear as a straight loop over host memory; info (may be
+ * NULL) is added to, as on the device. PTSS_HOST_EINVAL: whatever ptss_reproject_linear refuses, alignment aside.
+ * ptss_probe_reproject_linear_finish: steps 4's rounding to 6 for one pixel by themselves — the reprojected mean h[0..2], the
+ * interpolated count w and (hasVariance != 0) the interpolated per-sample variance s2 -> the film row and the moment row, four 64-bit
+ * words each; a K of 0 gives two all-zero rows. Returns PTSS_HOST_EINVAL for a null pointer, refused params, or an s2 that is
+ * negative, NaN or above 2^80 (the lookup clamps it). */
+int ptss_probe_reproject_linear(const ptss_film_camera* now, const ptss_pixel_feature* features_now, const ptss_pixel_motion* motion_now,
+                                const ptss_film_camera* prev, const ptss_pixel_feature* features_prev, const void* film_prev, int filmKind,
+                                const ptss_linear_moment* moments_prev, const ptss_linear_params* film,
+                                const ptss_reproject_linear_params* params, void* film_out, ptss_linear_moment* moments_out,
+                                ptss_reproject_linear_info* info);
+int ptss_probe_reproject_linear_finish(const float* h, float w, int hasVariance, float s2, int filmKind, const ptss_linear_params* film,
+                                       const ptss_reproject_linear_params* params, unsigned long long* film4, unsigned long long* moment4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -388,6 +388,26 @@ typedef struct ptss_denoise_linear_params {
     uint32_t reserved[3];    /* 0 */
 } ptss_denoise_linear_params;
 
+/* Carrying a linear or a filtered linear film across a camera move (ptss_reproject_linear). cosNormal, depthTolerance,
+ * minCoverage: as in ptss_reproject_params; maxHistory: the cap of the history count K a seeded pixel starts with. */
+typedef struct ptss_reproject_linear_params {
+    unsigned int structSize; /* sizeof(ptss_reproject_linear_params) as the caller compiled it */
+    float cosNormal;         /* [-1, 1]                       default 0.9  */
+    float depthTolerance;    /* finite, >= 0                  default 0.02 */
+    float minCoverage;       /* [0, 1]                        default 0.25 */
+    uint32_t maxHistory;     /* 1 .. 2^23 - 1: cap of K       default 64   */
+    unsigned int reserved;   /* 0 */
+} ptss_reproject_linear_params;
+
+/* What ptss_reproject_linear counts, written with integer adds: the caller zero-fills. 32 B, 8-byte aligned. seeded + offFilm + noTap
+ * is the number of pixels of the new film. */
+typedef struct ptss_reproject_linear_info {
+    unsigned long long seeded;     /* pixels that got K >= 1 */
+    unsigned long long offFilm;    /* projection rejected: behind the previous camera, outside its film, not finite */
+    unsigned long long noTap;      /* on the film, but no tap counted or coverage below minCoverage: disoccluded, other material, empty history */
+    unsigned long long noVariance; /* seeded, moments asked for, but no counting tap had a moment row of N >= 2 */
+} ptss_reproject_linear_info;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -480,6 +500,13 @@ static_assert(sizeof(ptss_denoise_linear_params) == 32 && offsetof(ptss_denoise_
                   offsetof(ptss_denoise_linear_params, sigmaLuminance) == 8 && offsetof(ptss_denoise_linear_params, sigmaDepth) == 16 &&
                   offsetof(ptss_denoise_linear_params, reserved) == 20,
               "ptss_denoise_linear_params is eight 32-bit words");
+static_assert(sizeof(ptss_reproject_linear_params) == 24 && offsetof(ptss_reproject_linear_params, cosNormal) == 4 &&
+                  offsetof(ptss_reproject_linear_params, minCoverage) == 12 && offsetof(ptss_reproject_linear_params, maxHistory) == 16 &&
+                  offsetof(ptss_reproject_linear_params, reserved) == 20,
+              "ptss_reproject_linear_params is six 32-bit words");
+static_assert(sizeof(ptss_reproject_linear_info) == 32 && offsetof(ptss_reproject_linear_info, offFilm) == 8 &&
+                  offsetof(ptss_reproject_linear_info, noVariance) == 24,
+              "ptss_reproject_linear_info is four 64-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -540,6 +567,13 @@ _Static_assert(sizeof(ptss_denoise_linear_params) == 32 && offsetof(ptss_denoise
                    offsetof(ptss_denoise_linear_params, sigmaLuminance) == 8 && offsetof(ptss_denoise_linear_params, sigmaDepth) == 16 &&
                    offsetof(ptss_denoise_linear_params, reserved) == 20,
                "ptss_denoise_linear_params is eight 32-bit words");
+_Static_assert(sizeof(ptss_reproject_linear_params) == 24 && offsetof(ptss_reproject_linear_params, cosNormal) == 4 &&
+                   offsetof(ptss_reproject_linear_params, minCoverage) == 12 && offsetof(ptss_reproject_linear_params, maxHistory) == 16 &&
+                   offsetof(ptss_reproject_linear_params, reserved) == 20,
+               "ptss_reproject_linear_params is six 32-bit words");
+_Static_assert(sizeof(ptss_reproject_linear_info) == 32 && offsetof(ptss_reproject_linear_info, offFilm) == 8 &&
+                   offsetof(ptss_reproject_linear_info, noVariance) == 24,
+               "ptss_reproject_linear_info is four 64-bit words");
 #endif
 
 #ifdef __cplusplus
