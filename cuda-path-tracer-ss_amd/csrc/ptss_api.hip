@@ -31,6 +31,7 @@
 #include "ptglare.h"
 #include "ptlindn.h"
 #include "ptlinrp.h"
+#include "ptlinup.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -168,6 +169,8 @@ struct ptss_context {
     unsigned long long glareLaunches[3] = {0, 0, 0};          // glare builds, the kernels they launched, glare resolves that launched
     unsigned long long linDenoiseLaunches[2] = {0, 0};        // ptss_denoise_linear calls that launched, the kernels inside them
     unsigned long long linReprojectLaunches = 0;              // ptss_reproject_linear calls that launched
+    unsigned long long linUpsampleLaunches = 0;               // ptss_upsample_linear calls that launched
+    int linUpsampleForm = 0;                                  // ptss_debug_upsample_linear_form: 0 the measured table, 1 global memory, 2 staged
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
@@ -1874,6 +1877,53 @@ int ptss_reproject_linear(ptss_context* c, const ptss_film_camera* now, const pt
 int ptss_reproject_linear_launches(const ptss_context* c, unsigned long long* out) {
     if (!c || !out) return fail(PTSS_EINVAL, "null argument");
     *out = c->linReprojectLaunches;
+    return PTSS_OK;
+}
+
+// ---- upsampling the two linear films (ptss_linupsample.hip; csrc/ptlinup.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_upsample_linear_params(ptss_upsample_linear_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_upsample_linear_params);
+    p->factor = 2;   // ptss_default_upsample_params' values (design choices, not measurements)
+    p->sigmaNormal = 0.1f;
+    p->sigmaDepth = 4.0f;
+    p->flags = 0u;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+int ptss_upsample_linear(ptss_context* c, const void* dev_film_lo, int filmKind, int width, int height, const ptss_pixel_feature* dev_features_lo,
+                         const ptss_pixel_feature* dev_features_hi, const ptss_linear_params* film, const ptss_upsample_linear_params* params,
+                         ptss_linear_entry* dev_film_hi, ptss_upsample_linear_info* dev_info, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    // in the order of the header's list: null pointers, the parameters, the kind, the film's parameters, the sides, alignment, overlap
+    if (!film || !params || !dev_film_lo || !dev_features_lo || !dev_features_hi || !dev_film_hi)
+        return fail(PTSS_EINVAL, "null parameters, film, features or output film");
+    if (const char* what = ptlup::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return fail(PTSS_EINVAL, "unknown film kind");
+    if (const char* what = ptlin::paramsError(film)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlup::sidesError(width, height, params->factor)) return fail(PTSS_ERANGE, what);
+    if (((uintptr_t)dev_film_lo | (uintptr_t)dev_features_lo | (uintptr_t)dev_features_hi | (uintptr_t)dev_film_hi) & 15u)
+        return fail(PTSS_EINVAL, "films and features must be 16-byte aligned");
+    if ((uintptr_t)dev_info & 7u) return fail(PTSS_EINVAL, "dev_info must be 8-byte aligned");
+    const size_t loBytes = 32 * (size_t)width * (size_t)height, hiBytes = loBytes * (size_t)params->factor * (size_t)params->factor;
+    if (ptlup::rangesOverlap(dev_film_hi, hiBytes, dev_film_lo, loBytes)) return fail(PTSS_EINVAL, "dev_film_hi overlaps dev_film_lo");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchLinearUpsample(streamOf(c, hipStream), dev_film_lo, filmKind == PTSS_FILM_SPLAT, width, height, dev_features_lo, dev_features_hi,
+                                       *film, *params, c->linUpsampleForm, dev_film_hi, dev_info, &c->linUpsampleLaunches));
+    return PTSS_OK;
+}
+
+int ptss_upsample_linear_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->linUpsampleLaunches;
+    return PTSS_OK;
+}
+
+int ptss_debug_upsample_linear_form(ptss_context* c, int form) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
+    c->linUpsampleForm = form;
     return PTSS_OK;
 }
 

@@ -289,6 +289,13 @@ hipError_t launchLinearReproject(hipStream_t st, const ptss_film_camera& now, co
                                  const ptss_film_camera& prev, const void* featuresPrev, const void* filmPrev, bool splat, const void* momentsPrev,
                                  const ptss_linear_params& film, const ptss_reproject_linear_params& params, void* filmOut, void* momentsOut,
                                  void* info, unsigned long long* launches);
+// a linear film of factor times the size from a small one (ptss_linupsample.hip; ptss_upsample_linear). filmLo and
+// featuresLo hold 32 B per pixel of width x height, featuresHi and filmHi of factor * width x factor * height; info may be null. form: 0
+// the measured table, 1 taps from global memory, 2 staged in LDS. *launches is incremented when the kernel launched. Everything checked
+// by the caller (ptlup::paramsError, ptlup::sidesError, ptlin::paramsError). No bit of ptss_launched_kernels
+hipError_t launchLinearUpsample(hipStream_t st, const void* filmLo, bool splat, int width, int height, const void* featuresLo,
+                                const void* featuresHi, const ptss_linear_params& film, const ptss_upsample_linear_params& params, int form,
+                                void* filmHi, void* info, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

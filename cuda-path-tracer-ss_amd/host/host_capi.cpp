@@ -20,6 +20,7 @@
 #include "ptglare.h"
 #include "ptlindn.h"
 #include "ptlinrp.h"
+#include "ptlinup.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptquant.h"
@@ -1119,6 +1120,43 @@ int ptss_probe_reproject_linear_finish(const float* h, float w, int hasVariance,
     unsigned long long m[3];
     ptlrp::filmRow(v3(h[0], h[1], h[2]), (unsigned long long)kf, filmKind == PTSS_FILM_SPLAT, R, m, film4);
     ptlrp::momentRow(m, (unsigned long long)kf, hasVariance != 0, s2, moment4);
+    return PTSS_HOST_OK;
+}
+
+// ---- upsampling the two linear films (csrc/ptlinup.h) ----
+int ptss_probe_upsample_linear(const void* film_lo, int filmKind, int width, int height, const ptss_pixel_feature* features_lo,
+                               const ptss_pixel_feature* features_hi, const ptss_linear_params* film, const ptss_upsample_linear_params* params,
+                               ptss_linear_entry* film_hi, ptss_upsample_linear_info* info) {
+    if (!film_lo || !features_lo || !features_hi || !film || !params || !film_hi) return PTSS_HOST_EINVAL;
+    if (ptlup::paramsError(params) || ptlin::paramsError(film)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if (ptlup::sidesError(width, height, params->factor)) return PTSS_HOST_ERANGE;
+    const int f = params->factor, hiW = width * f, hiH = height * f;
+    if (ptlup::rangesOverlap(film_hi, 32 * (size_t)hiW * (size_t)hiH, film_lo, 32 * (size_t)width * (size_t)height)) return PTSS_HOST_EINVAL;
+    const ptlup::Rule R = ptlup::ruleOf(*params, *film);
+    const bool splat = filmKind == PTSS_FILM_SPLAT;
+    const unsigned long long* lo = static_cast<const unsigned long long*>(film_lo);
+    unsigned long long* hi = reinterpret_cast<unsigned long long*>(film_hi);
+    auto tapAt = [&](int, int, int cx, int cy, unsigned long long* e) {
+        const size_t q = (size_t)cy * (size_t)width + (size_t)cx;
+        for (int k = 0; k < 4; ++k) e[k] = lo[4 * q + k];
+    };
+    auto featureAt = [&](int, int, int cx, int cy) {
+        const ptss_pixel_feature& g = features_lo[(size_t)cy * (size_t)width + (size_t)cx];
+        return ptdn::Feature{g.normal, g.depth, g.materialIdx};
+    };
+    auto depthAt = [&](int x, int y) { return features_hi[(size_t)y * (size_t)hiW + (size_t)x].depth; };
+    for (int Y = 0; Y < hiH; ++Y)
+        for (int X = 0; X < hiW; ++X) {
+            const size_t p = (size_t)Y * (size_t)hiW + (size_t)X;
+            const ptdn::Feature fp{features_hi[p].normal, features_hi[p].depth, features_hi[p].materialIdx};
+            const int status = ptlup::upsamplePixel<false>(X, Y, width, height, R, splat, fp, tapAt, featureAt, depthAt, hi + 4 * p);
+            if (info) {
+                info->filtered += status == ptlup::kFiltered;
+                info->fallback += status == ptlup::kFallback;
+                info->empty += status == ptlup::kEmpty;
+            }
+        }
     return PTSS_HOST_OK;
 }
 

@@ -66,6 +66,13 @@
 //                                   moments; --ticks more rounds accumulate into them, and the usual tail runs. Prints the four counters of
 //                                   ptss_reproject_linear_info. Not with --adaptive or --adaptive-linear: the combination is left out to keep
 //                                   this program's matrix small. Without the flag every byte written is today's
+//             [--upscale-linear F]  with --film and --linear, with or without --filter, --refill, --denoise-linear, --auto-exposure and --glare:
+//                                   the film is traced (and denoised) at the given size and upsampled in linear light to F (1..4) times the
+//                                   size — the features are ptss_ray_features of the centre rays of the same film camera at
+//                                   both sizes, ptss_upsample_linear (default parameters; the wrap flag for --film equirect) makes the large
+//                                   linear film, and --auto-exposure's meter (every round), --glare, the resolve, image.tga and image.pfm work
+//                                   on it: both files are F times the size. Prints the three counters of ptss_upsample_linear_info. Not with
+//                                   --carry, --adaptive-linear or --denoise (the 8-bit filter): left out to keep this program's matrix small
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -88,6 +95,7 @@ int main(int argc, char* argv[]) {
     int specularSteps = -1;   // --specular-features: -1 absent (first-hit features), else maxSteps
     bool temporal = false;
     int upscale = 0;   // --upscale: 0 absent, else the factor
+    int upscaleLinear = 0;   // --upscale-linear: 0 absent, else the factor
     std::string film;  // --film: the camera model, empty = the frame loop
     float lensRadius = 0.05f, focusDistance = 5.0f;   // --lens
     bool refill = false;   // --refill: the film's trace with the refill schedule
@@ -135,6 +143,10 @@ int main(int argc, char* argv[]) {
         else if (a == "--specular-features") specularSteps = atoi(next());
         else if (a == "--temporal") temporal = true;
         else if (a == "--upscale") upscale = atoi(next());
+        else if (a == "--upscale-linear") {
+            upscaleLinear = atoi(next());
+            if (upscaleLinear < 1 || upscaleLinear > 4) { fprintf(stderr, "bad --upscale-linear (a factor 1..4)\n"); return 2; }
+        }
         else if (a == "--film") film = next();
         else if (a == "--refill") refill = true;
         else if (a == "--adaptive") {
@@ -258,6 +270,10 @@ int main(int argc, char* argv[]) {
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
     if (denoiseLinear && linear < 0.f) { fprintf(stderr, "--denoise-linear needs --film and --linear\n"); return 2; }
+    if (upscaleLinear != 0 && (linear < 0.f || carry || adaptiveLinear >= 0 || denoise != -2)) {
+        fprintf(stderr, "--upscale-linear needs --film and --linear, and none of --carry, --adaptive-linear, --denoise\n");
+        return 2;
+    }
     if (carry && (linear < 0.f || adaptiveLinear >= 0 || ticks < 1)) { fprintf(stderr, "--carry needs --film, --linear, at least one tick and no --adaptive-linear\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
@@ -478,7 +494,52 @@ int main(int argc, char* argv[]) {
         const bool keepMoments = adaptiveLinear >= 0 || denoiseLinear || carry;   // the rounds accumulate with stats
         // what the meter, the glare and the resolves read: the denoised film, a linear one whatever the rounds fill, or the rounds' own
         const void* shown = denoiseLinear ? dClean : dLinear;
-        const bool shownSplat = !denoiseLinear && dPos;
+        bool shownSplat = !denoiseLinear && dPos;
+        // --upscale-linear: what is shown is the large film, made from the one above; its size, means and pixels
+        size_t shownN = n;
+        int shownW = width, shownH = height;
+        void *dShownMeans = dMeans, *dShownPixels = bitmap.devPixels, *dShownHist = dHist;
+        void *dBigFilm = nullptr, *dBigMeans = nullptr, *dBigPixels = nullptr, *dBigFeat = nullptr, *dSmallFeat = nullptr, *dBigInfo = nullptr;
+        ptss_upsample_linear_params bigParams;
+        PTSS_HANDLE(ptss_default_upsample_linear_params(&bigParams));
+        const void* smallFilm = shown;
+        const bool smallSplat = shownSplat;
+        if (upscaleLinear != 0) {
+            bigParams.factor = upscaleLinear;
+            if (filmKind == PTSS_FILM_EQUIRECT) bigParams.flags |= PTSS_UPSAMPLE_LINEAR_WRAP_X;
+            shownW = width * upscaleLinear, shownH = height * upscaleLinear;
+            shownN = (size_t)shownW * (size_t)shownH;
+            // the centre rays of the same film camera at both sizes (jitter 0 draws nothing; streams of their own all the same)
+            void *dBigRng = nullptr, *dBigRays = nullptr;
+            if (hipMalloc(&dBigFilm, shownN * sizeof(ptss_linear_entry)) != hipSuccess || hipMalloc(&dBigMeans, shownN * sizeof(ptss_history_entry)) != hipSuccess ||
+                hipMalloc(&dBigPixels, shownN * sizeof(ptss_uchar4)) != hipSuccess || hipMalloc(&dBigFeat, shownN * sizeof(ptss_pixel_feature)) != hipSuccess ||
+                hipMalloc(&dSmallFeat, n * sizeof(ptss_pixel_feature)) != hipSuccess || hipMalloc(&dBigInfo, sizeof(ptss_upsample_linear_info)) != hipSuccess ||
+                hipMemset(dBigInfo, 0, sizeof(ptss_upsample_linear_info)) != hipSuccess || hipMalloc(&dBigRng, shownN * sizeof(ptss_path_rng)) != hipSuccess ||
+                hipMalloc(&dBigRays, shownN * sizeof(ptss_ray_query)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+                fprintf(stderr, "--upscale-linear: device buffers\n");
+                return 1;
+            }
+            PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dBigRng, shownN, seed, 0, 0, NULL));
+            ptss_film_camera centre = fc;
+            centre.jitter = 0;
+            PTSS_HANDLE(ptss_generate_rays(ctx, &centre, 0, NULL, n, (ptss_path_rng*)dBigRng, (ptss_ray_query*)dBigRays, NULL));
+            PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dBigRays, (ptss_pixel_feature*)dSmallFeat, n, NULL));
+            centre.width = shownW, centre.height = shownH;
+            PTSS_HANDLE(ptss_generate_rays(ctx, &centre, 0, NULL, shownN, (ptss_path_rng*)dBigRng, (ptss_ray_query*)dBigRays, NULL));
+            PTSS_HANDLE(ptss_ray_features(ctx, (const ptss_ray_query*)dBigRays, (ptss_pixel_feature*)dBigFeat, shownN, NULL));
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            (void)hipFree(dBigRng);
+            (void)hipFree(dBigRays);
+            shown = dBigFilm;
+            shownSplat = false;
+            dShownMeans = dBigMeans, dShownPixels = dBigPixels, dShownHist = nullptr;
+        }
+        auto upsampleFilm = [&]() -> int {
+            PTSS_HANDLE(ptss_upsample_linear(ctx, smallFilm, smallSplat ? PTSS_FILM_SPLAT : PTSS_FILM_LINEAR, width, height,
+                                             (const ptss_pixel_feature*)dSmallFeat, (const ptss_pixel_feature*)dBigFeat, &linearParams, &bigParams,
+                                             (ptss_linear_entry*)dBigFilm, (ptss_upsample_linear_info*)dBigInfo, NULL));
+            return 0;
+        };
         auto denoiseFilm = [&]() -> int {
             PTSS_HANDLE(ptss_denoise_linear(ctx, dLinear, dPos ? PTSS_FILM_SPLAT : PTSS_FILM_LINEAR, width, height, (const ptss_linear_moment*)dMoments,
                                             (const ptss_pixel_feature*)dCleanFeat, &linearParams, &cleanParams, dCleanWork, (ptss_linear_entry*)dClean,
@@ -494,26 +555,27 @@ int main(int argc, char* argv[]) {
         if (glare) {
             ptss_glare_level levels[PTSS_GLARE_MAX_LEVELS];
             size_t entries = 0;
-            PTSS_HANDLE(ptss_glare_layout(width, height, glareParams.levels, levels, &entries));
+            PTSS_HANDLE(ptss_glare_layout(shownW, shownH, glareParams.levels, levels, &entries));
             if (hipMalloc(&dPyramid, entries * sizeof(ptss_glare_entry)) != hipSuccess) { fprintf(stderr, "--glare: device buffers\n"); return 1; }
         }
         auto meteredResolve = [&]() -> int {   // the exposure is the state's, --linear's compensating
             if (shownSplat) {
-                PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
-                                                       (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                PTSS_HANDLE(ptss_resolve_splat_metered(ctx, (const ptss_splat_entry*)shown, 0, shownN, &linearParams, (const ptss_meter_state*)dMeter,
+                                                       (ptss_history_entry*)dShownMeans, (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
             } else {
-                PTSS_HANDLE(ptss_resolve_linear_metered(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, (const ptss_meter_state*)dMeter,
-                                                        (ptss_history_entry*)dMeans, (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                PTSS_HANDLE(ptss_resolve_linear_metered(ctx, (const ptss_linear_entry*)shown, 0, shownN, &linearParams, (const ptss_meter_state*)dMeter,
+                                                        (ptss_history_entry*)dShownMeans, (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
             }
             return 0;
         };
         auto meterRound = [&](int round) -> int {   // meter, update, metered resolve: the round's exposure never leaves the device
             uint32_t* bins = (uint32_t*)dBins + (size_t)round * PTSS_METER_BINS;
             if (denoiseLinear && denoiseFilm()) return 1;   // the meter reads the denoised film of this round
+            if (upscaleLinear != 0 && upsampleFilm()) return 1;   // ... at the large size
             if (shownSplat) {
-                PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)shown, 0, n, bins, NULL));
+                PTSS_HANDLE(ptss_meter_splat(ctx, (const ptss_splat_entry*)shown, 0, shownN, bins, NULL));
             } else {
-                PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)shown, 0, n, bins, NULL));
+                PTSS_HANDLE(ptss_meter_linear(ctx, (const ptss_linear_entry*)shown, 0, shownN, bins, NULL));
             }
             PTSS_HANDLE(ptss_meter_exposure(ctx, bins, &linearParams, &meterParams, (ptss_meter_state*)dMeter, NULL));
             return meteredResolve();
@@ -638,6 +700,7 @@ int main(int argc, char* argv[]) {
         }
         if (linear >= 0.f) {   // the film resolved once: the screenshot's bytes, the filter's history, and the linear means as a PFM
             if (denoiseLinear && (!autoExposure || ticks <= 0) && denoiseFilm()) return 1;   // (with a meter the last round's denoised film stands)
+            if (upscaleLinear != 0 && (!autoExposure || ticks <= 0) && upsampleFilm()) return 1;   // (... and its large film)
             if (autoExposure) {   // (the last round's metered resolve stands; without a round the new state's exposure, 0, shows black)
                 if (ticks <= 0 && meteredResolve()) return 1;
                 PTSS_HANDLE(ptss_synchronize(ctx));
@@ -648,32 +711,43 @@ int main(int argc, char* argv[]) {
             }
             if (glare) {   // the pyramid of the finished film, and the resolve that adds it: at the meter's exposure where there is one
                 const ptss_meter_state* state = autoExposure ? (const ptss_meter_state*)dMeter : NULL;
-                PTSS_HANDLE(ptss_glare_build(ctx, shown, shownSplat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, width, height, &linearParams, &glareParams,
+                PTSS_HANDLE(ptss_glare_build(ctx, shown, shownSplat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, shownW, shownH, &linearParams, &glareParams,
                                              (ptss_glare_entry*)dPyramid, NULL));
                 if (shownSplat) {
-                    PTSS_HANDLE(ptss_resolve_splat_glare(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, width, height, &glareParams,
-                                                         (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
-                                                         (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                    PTSS_HANDLE(ptss_resolve_splat_glare(ctx, (const ptss_splat_entry*)shown, 0, shownN, &linearParams, shownW, shownH, &glareParams,
+                                                         (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dShownMeans,
+                                                         (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
                 } else {
-                    PTSS_HANDLE(ptss_resolve_linear_glare(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, width, height, &glareParams,
-                                                          (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dMeans,
-                                                          (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                    PTSS_HANDLE(ptss_resolve_linear_glare(ctx, (const ptss_linear_entry*)shown, 0, shownN, &linearParams, shownW, shownH, &glareParams,
+                                                          (const ptss_glare_entry*)dPyramid, state, (ptss_history_entry*)dShownMeans,
+                                                          (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
                 }
             } else if (!autoExposure && shownSplat) {
-                PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)shown, 0, n, &linearParams, (ptss_history_entry*)dMeans,
-                                               (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                PTSS_HANDLE(ptss_resolve_splat(ctx, (const ptss_splat_entry*)shown, 0, shownN, &linearParams, (ptss_history_entry*)dShownMeans,
+                                               (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
             } else if (!autoExposure) {
-                PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)shown, 0, n, &linearParams, (ptss_history_entry*)dMeans,
-                                                (ptss_uchar4*)bitmap.devPixels, (ptss_history_entry*)dHist, NULL));
+                PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)shown, 0, shownN, &linearParams, (ptss_history_entry*)dShownMeans,
+                                                (ptss_uchar4*)dShownPixels, (ptss_history_entry*)dShownHist, NULL));
             }
             PTSS_HANDLE(ptss_synchronize(ctx));
-            std::vector<ptss_history_entry> means(n);
-            if (hipMemcpy(means.data(), dMeans, n * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--linear: read-back\n"); return 1; }
+            std::vector<ptss_history_entry> means(shownN);
+            if (hipMemcpy(means.data(), dShownMeans, shownN * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--linear: read-back\n"); return 1; }
+            if (upscaleLinear != 0) {   // the large image is this option's to write: the screenshot below is of the display buffer, at the small size
+                ptss_upsample_linear_info info;
+                std::vector<ptss_uchar4> host(shownN);
+                if (hipMemcpy(&info, dBigInfo, sizeof(info), hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(host.data(), dBigPixels, shownN * sizeof(ptss_uchar4), hipMemcpyDeviceToHost) != hipSuccess) {
+                    fprintf(stderr, "--upscale-linear: read-back\n");
+                    return 1;
+                }
+                printf("upscale-linear: factor %d filtered %llu fallback %llu empty %llu\n", upscaleLinear, info.filtered, info.fallback, info.empty);
+                if (!writeTga(out.c_str(), host.data(), shownW, shownH)) fprintf(stderr, "--upscale-linear: cannot write %s\n", out.c_str());
+            }
             std::string name = out;
             const size_t dot = name.rfind(".tga");
             if (dot != std::string::npos && dot + 4 == name.size()) name.erase(dot);
             name += ".pfm";
-            if (!writePfm(name.c_str(), means.data(), width, height)) fprintf(stderr, "--linear: cannot write %s\n", name.c_str());
+            if (!writePfm(name.c_str(), means.data(), shownW, shownH)) fprintf(stderr, "--linear: cannot write %s\n", name.c_str());
         }
         if (filter && ticks > 0) {   // the features of the film's pixel centres, then the filter over the film's display values
             ptss_denoise_params params;
@@ -693,14 +767,14 @@ int main(int argc, char* argv[]) {
             if (!writeTga(name.c_str(), host.data(), width, height)) fprintf(stderr, "--film --denoise: cannot write %s\n", name.c_str());
         }
         PTSS_HANDLE(ptss_synchronize(ctx));
-        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid, dClean, dCleanFeat, dCleanWork, dCarryPrev, dCarryNow, dCarryFilm, dCarryMoments, dCarryInfo}) (void)hipFree(p);
+        for (void* p : {dRng, dRays, dRes, dFilm, dHist, dFeat, dOut, dMoments, dCdf, dIndex, dInfo, dLinear, dMeans, dPos, dBins, dMeter, dPyramid, dClean, dCleanFeat, dCleanWork, dCarryPrev, dCarryNow, dCarryFilm, dCarryMoments, dCarryInfo, dBigFilm, dBigMeans, dBigPixels, dBigFeat, dSmallFeat, dBigInfo}) (void)hipFree(p);
     } else {
         for (char k : keys) bitmap.push_key((unsigned char)k);
         bitmap.anim_and_exit((void (*)(uchar4*, void*, int))generateFrame, NULL, (void (*)(unsigned char, int, int))Key);
     }
 
     if (!quiet) printf("\n");
-    if (!out.empty() && !temporal) {
+    if (!out.empty() && !temporal && upscaleLinear == 0) {
         char name[160];
         strncpy(name, out.c_str(), sizeof(name) - 1);
         name[sizeof(name) - 1] = 0;

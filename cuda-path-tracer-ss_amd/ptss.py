@@ -23,6 +23,7 @@ from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SP
                         GlareParams)
 from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DENOISE_MAX_LEVELS, FILM_LINEAR, FILM_SPLAT, DenoiseLinearParams
 from ptss_types import REPROJECT_LINEAR_INFO_DTYPE, REPROJECT_LINEAR_MAX_HISTORY, ReprojectLinearParams
+from ptss_types import UPSAMPLE_LINEAR_INFO_DTYPE, UPSAMPLE_LINEAR_WRAP_X, UpsampleLinearParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -226,6 +227,8 @@ def host_lib():
                                                   C.c_void_p]
         L.ptss_probe_reproject_linear_finish.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(LinearParams),
                                                          C.POINTER(ReprojectLinearParams), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_upsample_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LinearParams),
+                                                 C.POINTER(UpsampleLinearParams), C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -357,6 +360,10 @@ def device_lib():
         L.ptss_reproject_linear.argtypes = [vp, C.POINTER(FilmCamera), vp, vp, C.POINTER(FilmCamera), vp, vp, C.c_int, vp, C.POINTER(LinearParams),
                                             C.POINTER(ReprojectLinearParams), vp, vp, vp, vp]
         L.ptss_reproject_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_upsample_linear_params.argtypes = [C.POINTER(UpsampleLinearParams)]
+        L.ptss_upsample_linear.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(LinearParams), C.POINTER(UpsampleLinearParams), vp, vp, vp]
+        L.ptss_upsample_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_upsample_linear_form.argtypes = [vp, C.c_int]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1207,6 +1214,46 @@ def probe_reproject_linear_finish(h, w, s2=None, film_kind="linear", params=None
     if rc != 0:
         raise PtssError(f"ptss_probe_reproject_linear_finish: {rc}")
     return tuple(int(v) for v in f4), tuple(int(v) for v in m4)
+
+
+# ---- upsampling the two linear films (ptss_upsample_linear) ----
+def upsample_linear_params(factor=2, sigma_normal=0.1, sigma_depth=4.0, wrap_x=False):
+    """A ptss_upsample_linear_params; the defaults are ptss_default_upsample_linear_params'. wrap_x: the film is an equirect one."""
+    p = UpsampleLinearParams()
+    p.structSize = C.sizeof(UpsampleLinearParams)
+    p.factor, p.sigmaNormal, p.sigmaDepth = int(factor), float(sigma_normal), float(sigma_depth)
+    p.flags, p.reserved = (UPSAMPLE_LINEAR_WRAP_X if wrap_x else 0), 0
+    return p
+
+
+def _upsample_linear_inputs(film_lo, film_kind, width, height, features_lo, features_hi, upsample):
+    """The buffers of an upsample_linear call as plain rows: (film, kind, features_lo, features_hi, the large film's pixels)."""
+    if int(width) <= 0 or int(height) <= 0:
+        raise ValueError("width and height must be positive")
+    f, kind = _glare_film(film_lo, film_kind, width, height)
+    fac = max(1, int(upsample.factor))
+    P = int(width) * int(height) * fac * fac
+    return f, kind, _feature_rows(features_lo, int(width) * int(height), "features_lo"), _feature_rows(features_hi, P, "features_hi"), P
+
+
+def probe_upsample_linear(film_lo, width, height, features_lo, features_hi, params=None, upsample=None, film_kind=None, info=None):
+    """ptss_upsample_linear on the host (csrc/ptlinup.h; the specification of the device's rows) -> (the large film, (factor^2 * width *
+    height,) LINEAR_DTYPE; the info, an UPSAMPLE_LINEAR_INFO_DTYPE record). film_lo: (width * height,) LINEAR_DTYPE or SPLAT_DTYPE, or
+    (P, 4) uint64 with film_kind; features_lo / features_hi: FEATURE_DTYPE rows of both sizes; params: the film's linear_params;
+    upsample: an upsample_linear_params; info: the counters' content beforehand."""
+    params = params if params is not None else linear_params()
+    upsample = upsample if upsample is not None else upsample_linear_params()
+    f, kind, flo, fhi, P = _upsample_linear_inputs(film_lo, film_kind, width, height, features_lo, features_hi, upsample)
+    out = np.zeros((P, 4), dtype=np.uint64)
+    inf = np.zeros(1, dtype=UPSAMPLE_LINEAR_INFO_DTYPE)
+    if info is not None:
+        inf[0] = info
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = host_lib().ptss_probe_upsample_linear(ptr(f), kind, int(width), int(height), ptr(flo), ptr(fhi), C.byref(params), C.byref(upsample), ptr(out),
+                                               ptr(inf))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_upsample_linear: {rc}")
+    return out.view(LINEAR_DTYPE).reshape(-1), inf[0]
 
 
 def default_denoise_params(**overrides):
@@ -2408,6 +2455,55 @@ class Renderer:
         out = C.c_ulonglong(0)
         _check(device_lib().ptss_reproject_linear_launches(self._ctx, C.byref(out)))
         return int(out.value)
+
+    # --- upsampling the two linear films (ptss_upsample_linear) ------------------
+    def upsample_linear(self, film_lo, width, height, features_lo, features_hi, params=None, upsample=None, film_kind=None, out=None, info=None):
+        """ptss_upsample_linear: a linear or a filtered linear film of width x height -> a linear film of factor times the size. params: the
+        film's linear_params; upsample: an upsample_linear_params.
+        numpy: film_lo (P,) LINEAR_DTYPE or SPLAT_DTYPE (or (P, 4) uint64 with film_kind), features_lo / features_hi FEATURE_DTYPE rows of
+        both sizes -> (the large film, (factor^2 P,) LINEAR_DTYPE; the info as an UPSAMPLE_LINEAR_INFO_DTYPE record, or None with
+        info=False: dev_info NULL). info: the counters' content beforehand.
+        torch: film_lo (P, 4) int64, features (., 8) float32; out a (factor^2 P, 4) int64 device tensor WRITTEN IN PLACE, info a (3,) int64
+        device tensor ADDED TO or None -> None, on the current stream."""
+        L = device_lib()
+        params = params if params is not None else linear_params()
+        upsample = upsample if upsample is not None else upsample_linear_params()
+        if type(film_lo).__module__.split(".")[0] == "torch":
+            import sys
+            torch = sys.modules["torch"]
+            dev, Pl = film_lo.device, int(width) * int(height)
+            Ph = Pl * int(upsample.factor) ** 2
+            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
+            d_film = self._torch_ptr(film_lo, "film_lo", "int64", 4, None, Pl)
+            d_flo = self._torch_ptr(features_lo, "features_lo", "float32", 8, dev, Pl)
+            d_fhi = self._torch_ptr(features_hi, "features_hi", "float32", 8, dev, Ph)
+            d_out = self._torch_ptr(out, "out", "int64", 4, dev, Ph)
+            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 3) if info is not None else None
+            _check(L.ptss_upsample_linear(self._ctx, d_film, kind, int(width), int(height), d_flo, d_fhi, C.byref(params), C.byref(upsample), d_out,
+                                          d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            return None
+        f, kind, flo, fhi, P = _upsample_linear_inputs(film_lo, film_kind, width, height, features_lo, features_hi, upsample)
+        res = np.zeros((P, 4), dtype=np.uint64)
+        inf = None
+        if info is not False:
+            inf = np.zeros(1, dtype=UPSAMPLE_LINEAR_INFO_DTYPE)
+            if info is not None:
+                inf[0] = info
+        self._round_trip([f, flo, fhi, res, inf],
+                         lambda d: _check(L.ptss_upsample_linear(self._ctx, d[0], kind, int(width), int(height), d[1], d[2], C.byref(params),
+                                                                 C.byref(upsample), d[3], d[4], None)), read=(3, 4))
+        return res.view(LINEAR_DTYPE).reshape(-1), (inf[0] if inf is not None else None)
+
+    def upsample_linear_launches(self):
+        """ptss_upsample_linear_launches: the upsample_linear calls that launched since the context was created."""
+        out = C.c_ulonglong(0)
+        _check(device_lib().ptss_upsample_linear_launches(self._ctx, C.byref(out)))
+        return int(out.value)
+
+    def debug_upsample_linear_form(self, form):
+        """ptss_debug_upsample_linear_form (tests and measurements): 0 the form measured faster at each factor, 1 every tap from global
+        memory, 2 the lo pixels of a tile divided once and staged in LDS. The bytes are the same."""
+        _check(device_lib().ptss_debug_upsample_linear_form(self._ctx, int(form)))
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

@@ -229,6 +229,19 @@ class ReprojectLinearParams(C.Structure):   # ptss_reproject_linear_params: the 
 REPROJECT_LINEAR_INFO_DTYPE = np.dtype([("seeded", np.uint64), ("offFilm", np.uint64), ("noTap", np.uint64), ("noVariance", np.uint64)])
 
 
+# upsampling the two linear films (ptss_upsample_linear)
+UPSAMPLE_LINEAR_WRAP_X = 1
+
+
+class UpsampleLinearParams(C.Structure):   # ptss_upsample_linear_params
+    _fields_ = [("structSize", C.c_uint), ("factor", C.c_int), ("sigmaNormal", C.c_float), ("sigmaDepth", C.c_float), ("flags", C.c_uint),
+                ("reserved", C.c_uint)]
+
+
+# ptss_upsample_linear_info: what a call adds to the caller's three counters
+UPSAMPLE_LINEAR_INFO_DTYPE = np.dtype([("filtered", np.uint64), ("fallback", np.uint64), ("empty", np.uint64)])
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

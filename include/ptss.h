@@ -684,6 +684,41 @@ int ptss_reproject_linear(ptss_context* ctx, const ptss_film_camera* now, const 
                           ptss_reproject_linear_info* dev_info /* may be NULL */, void* hipStream);
 int ptss_reproject_linear_launches(const ptss_context* ctx, unsigned long long* out); /* calls that launched */
 
+/* Upsampling the two linear films in linear light: a linear or a filtered linear film of width x height becomes a
+ * LINEAR film of factor * width x factor * height, between ptss_denoise_linear and the meter, the glare build and the resolves, which
+ * take the result exactly as it is — the glare pyramid is built at the large size, the exposure can change afterwards, and edges are
+ * interpolated in linear light, in front of the tone map. Per hi pixel the four lo pixels around its centre (ptss_upsample's taps and
+ * bilinear weights) count where they are inside the film, hold samples and have the hi pixel's material, weighted by the normal and
+ * depth terms of ptss_upsample; the weighted mean of their means, written around the nearest counted one and clamped to their hull,
+ * is rounded to the film's fixed point as m' and the row is {m' K, m' K, m' K, samples = K, clamped = 0}, K the nearest counted tap's
+ * count: every consumer's integer mean of it is m' exactly. A channel in which all counted taps agree keeps their integer mean itself.
+ * No tap counted: the nearest lo pixel's own means and count, or an all-zero row where that pixel is empty. csrc/ptlinup.h has the
+ * arithmetic; its host build (ptss_probe_upsample_linear) is the specification and the device equals it byte for byte.
+ *
+ * dev_film_lo: ptss_linear_entry or (PTSS_FILM_SPLAT) ptss_splat_entry, width * height of them; dev_film_hi: factor^2 * width * height
+ * ptss_linear_entry, all written. dev_features_lo / dev_features_hi: ptss_render_features / ptss_render_features_scaled of the same
+ * camera, or ptss_ray_features of the centre rays (jitter = 0) of the same film camera at width x height and at factor * width x
+ * factor * height (thin-lens and equirect films). params->flags & PTSS_UPSAMPLE_LINEAR_WRAP_X: an equirect film — tap columns and
+ * the depth slope's left and right neighbours wrap at the seam. dev_info (may be NULL): three counters the call ADDS to; the caller
+ * zero-fills; they sum to the large film's pixels. Asynchronous on hipStream (NULL: the context's); no frame state, no bit of
+ * ptss_launched_kernels; the sizes are the caller's, so it serves sharded contexts. No moments are written for the large film: the
+ * plan and the denoiser work at the small size.
+ *
+ * Refused before the device is touched, nothing written or counted. PTSS_EINVAL: a null ctx or required pointer, a wrong structSize,
+ * a factor outside 1..4, a sigma that is not finite and positive, an unknown flag, a non-zero reserved, an unknown film kind, whatever
+ * ptss_resolve_linear refuses about `film`, a film or feature pointer that is not 16-byte aligned (dev_info: 8), an output range that
+ * overlaps the input film. PTSS_ERANGE: width or height outside [1, 2^22], factor * width or factor * height above 2^22,
+ * factor^2 * width * height >= 2^31.
+ * ptss_debug_upsample_linear_form (tests and measurements): 0 the form measured faster at each factor, 1 every tap from global
+ * memory, 2 the lo pixels of a tile divided once and staged in LDS. The bytes are the same whatever the form. */
+int ptss_default_upsample_linear_params(ptss_upsample_linear_params* params); /* factor 2, sigmaNormal 0.1, sigmaDepth 4, flags 0 */
+int ptss_upsample_linear(ptss_context* ctx, const void* dev_film_lo, int filmKind /* PTSS_FILM_LINEAR | PTSS_FILM_SPLAT */, int width, int height,
+                         const ptss_pixel_feature* dev_features_lo, const ptss_pixel_feature* dev_features_hi, const ptss_linear_params* film,
+                         const ptss_upsample_linear_params* params, ptss_linear_entry* dev_film_hi,
+                         ptss_upsample_linear_info* dev_info /* may be NULL */, void* hipStream);
+int ptss_upsample_linear_launches(const ptss_context* ctx, unsigned long long* out); /* calls that launched */
+int ptss_debug_upsample_linear_form(ptss_context* ctx, int form);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

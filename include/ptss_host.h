@@ -18,6 +18,7 @@ extern "C" {
 #define PTSS_HOST_OK 0
 #define PTSS_HOST_EINVAL (-1)
 #define PTSS_HOST_EIO (-2)
+#define PTSS_HOST_ERANGE (-3) /* a size outside what the call serves (ptss_probe_upsample_linear) */
 
 typedef struct ptss_scene ptss_scene; /* owns a C++ Scene */
 
@@ -302,6 +303,13 @@ int ptss_probe_reproject_linear(const ptss_film_camera* now, const ptss_pixel_fe
                                 ptss_reproject_linear_info* info);
 int ptss_probe_reproject_linear_finish(const float* h, float w, int hasVariance, float s2, int filmKind, const ptss_linear_params* film,
                                        const ptss_reproject_linear_params* params, unsigned long long* film4, unsigned long long* moment4);
+
+/* Upsampling the two linear films on the host (csrc/ptlinup.h — the very operations the kernels evaluate; this build is the
+ * specification): ptss_upsample_linear as a straight loop over host memory; info (may be NULL) is added to, as on the device.
+ * PTSS_HOST_EINVAL / PTSS_HOST_ERANGE: whatever ptss_upsample_linear refuses with PTSS_EINVAL / PTSS_ERANGE, alignment aside. */
+int ptss_probe_upsample_linear(const void* film_lo, int filmKind, int width, int height, const ptss_pixel_feature* features_lo,
+                               const ptss_pixel_feature* features_hi, const ptss_linear_params* film, const ptss_upsample_linear_params* params,
+                               ptss_linear_entry* film_hi, ptss_upsample_linear_info* info);
 
 #ifdef __cplusplus
 }

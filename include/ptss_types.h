@@ -408,6 +408,26 @@ typedef struct ptss_reproject_linear_info {
     unsigned long long noVariance; /* seeded, moments asked for, but no counting tap had a moment row of N >= 2 */
 } ptss_reproject_linear_info;
 
+/* Upsampling a linear or a filtered linear film in linear light (ptss_upsample_linear). factor, sigmaNormal,
+ * sigmaDepth: as in ptss_upsample_params. PTSS_UPSAMPLE_LINEAR_WRAP_X: the film is an equirect one, its columns wrap at the seam. */
+#define PTSS_UPSAMPLE_LINEAR_WRAP_X 1u
+typedef struct ptss_upsample_linear_params {
+    unsigned int structSize; /* sizeof(ptss_upsample_linear_params) as the caller compiled it */
+    int factor;              /* hi pixels per lo pixel and axis: 1 .. 4   default 2   */
+    float sigmaNormal;       /* finite, > 0                               default 0.1 */
+    float sigmaDepth;        /* finite, > 0                               default 4   */
+    unsigned int flags;      /* PTSS_UPSAMPLE_LINEAR_*                    default 0   */
+    unsigned int reserved;   /* 0 */
+} ptss_upsample_linear_params;
+
+/* What ptss_upsample_linear counts, written with integer adds: the caller zero-fills. 24 B, 8-byte aligned. The three sum to the
+ * number of pixels of the large film. */
+typedef struct ptss_upsample_linear_info {
+    unsigned long long filtered; /* hi pixels with at least one counted tap */
+    unsigned long long fallback; /* no tap counted: the row of the nearest lo pixel's means */
+    unsigned long long empty;    /* no tap counted and the nearest lo pixel is empty: an all-zero row */
+} ptss_upsample_linear_info;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -507,6 +527,13 @@ static_assert(sizeof(ptss_reproject_linear_params) == 24 && offsetof(ptss_reproj
 static_assert(sizeof(ptss_reproject_linear_info) == 32 && offsetof(ptss_reproject_linear_info, offFilm) == 8 &&
                   offsetof(ptss_reproject_linear_info, noVariance) == 24,
               "ptss_reproject_linear_info is four 64-bit words");
+static_assert(sizeof(ptss_upsample_linear_params) == 24 && offsetof(ptss_upsample_linear_params, factor) == 4 &&
+                  offsetof(ptss_upsample_linear_params, sigmaDepth) == 12 && offsetof(ptss_upsample_linear_params, flags) == 16 &&
+                  offsetof(ptss_upsample_linear_params, reserved) == 20,
+              "ptss_upsample_linear_params is six 32-bit words");
+static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample_linear_info, fallback) == 8 &&
+                  offsetof(ptss_upsample_linear_info, empty) == 16,
+              "ptss_upsample_linear_info is three 64-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -574,6 +601,13 @@ _Static_assert(sizeof(ptss_reproject_linear_params) == 24 && offsetof(ptss_repro
 _Static_assert(sizeof(ptss_reproject_linear_info) == 32 && offsetof(ptss_reproject_linear_info, offFilm) == 8 &&
                    offsetof(ptss_reproject_linear_info, noVariance) == 24,
                "ptss_reproject_linear_info is four 64-bit words");
+_Static_assert(sizeof(ptss_upsample_linear_params) == 24 && offsetof(ptss_upsample_linear_params, factor) == 4 &&
+                   offsetof(ptss_upsample_linear_params, sigmaDepth) == 12 && offsetof(ptss_upsample_linear_params, flags) == 16 &&
+                   offsetof(ptss_upsample_linear_params, reserved) == 20,
+               "ptss_upsample_linear_params is six 32-bit words");
+_Static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample_linear_info, fallback) == 8 &&
+                   offsetof(ptss_upsample_linear_info, empty) == 16,
+               "ptss_upsample_linear_info is three 64-bit words");
 #endif
 
 #ifdef __cplusplus
