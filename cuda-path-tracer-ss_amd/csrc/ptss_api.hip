@@ -29,6 +29,7 @@
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
+#include "pttone.h"
 #include "ptlindn.h"
 #include "ptlinrp.h"
 #include "ptlinup.h"
@@ -171,6 +172,8 @@ struct ptss_context {
     unsigned long long linReprojectLaunches = 0;              // ptss_reproject_linear calls that launched
     unsigned long long linUpsampleLaunches = 0;               // ptss_upsample_linear calls that launched
     int linUpsampleForm = 0;                                  // ptss_debug_upsample_linear_form: 0 the measured table, 1 global memory, 2 staged
+    unsigned long long toneLaunches[2] = {0, 0};              // ptss_tone_build, ptss_resolve_toned calls that launched
+    int toneForm = 0;                                         // ptss_debug_tone_form: 0 the shipped lookup, 1 staged in LDS, 2 guess and settle
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
     bool splatCounted = false;
@@ -2017,6 +2020,76 @@ int ptss_resolve_splat_glare(ptss_context* c, const ptss_splat_entry* dev_film, 
     return resolveLinearFilm(c, dev_film, true, firstPixel, count, params, dev_state, &g, !dev_film || !dev_pyramid,
                              "null film or pyramid with count > 0", kResolveGlareAlign, dev_linear, dev_pixels, dev_history,
                              &c->glareLaunches[2], hipStream);
+}
+
+// ---- tone curves for the two linear films (ptss_tone.hip; csrc/pttone.h). Like the film calls: no frame state, the caller's stream ----
+int ptss_default_tone_params(ptss_tone_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    p->structSize = (unsigned int)sizeof(ptss_tone_params);
+    p->curve = PTSS_TONE_FILMIC;   // design choices, not measurements: a common filmic fit, the display's own transfer, the TGA's depth
+    p->transfer = PTSS_TRANSFER_SRGB;
+    p->bits = 8;
+    p->flags = 0u;
+    p->white = 4.0f;
+    p->filmic[0] = 2.51f, p->filmic[1] = 0.03f, p->filmic[2] = 2.43f, p->filmic[3] = 0.59f, p->filmic[4] = 0.14f;
+    p->reserved = 0u;
+    return PTSS_OK;
+}
+
+size_t ptss_tone_table_floats(int bits) { return (bits == 8 || bits == 10) ? (size_t)pttone::tableFloats(bits) : 0; }
+
+int ptss_tone_build(ptss_context* c, const ptss_tone_params* tone, float* dev_table, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = pttone::paramsError(tone)) return fail(PTSS_EINVAL, what);
+    if (!dev_table) return fail(PTSS_EINVAL, "dev_table is null");
+    if ((uintptr_t)dev_table & 15u) return fail(PTSS_EINVAL, "dev_table must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchToneBuild(streamOf(c, hipStream), *tone, dev_table, &c->toneLaunches[0]));
+    return PTSS_OK;
+}
+
+int ptss_resolve_toned(ptss_context* c, const void* dev_film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                       const ptss_tone_params* tone, const float* dev_table, const ptss_meter_state* dev_state, int width, int height,
+                       const ptss_glare_params* glare, const ptss_glare_entry* dev_pyramid, ptss_history_entry* dev_linear, uint32_t* dev_pixels,
+                       ptss_history_entry* dev_history, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return fail(PTSS_EINVAL, "unknown film kind");
+    if (glare)
+        RC_TRY(glareArguments(c, params, glare, filmKind, width, height));
+    else if (const char* what = ptlin::paramsError(params))
+        return fail(PTSS_EINVAL, what);
+    if (const char* what = pttone::paramsError(tone)) return fail(PTSS_EINVAL, what);
+    if (!glare && dev_pyramid) return fail(PTSS_EINVAL, "a pyramid needs its glare parameters");
+    const bool missing = !dev_film || !dev_table || (glare && !dev_pyramid);
+    const char* bad = missing ? "null film, table or pyramid with count > 0"
+                      : (((uintptr_t)dev_film | (uintptr_t)dev_table | (uintptr_t)dev_pyramid | (uintptr_t)dev_linear | (uintptr_t)dev_history) & 15u) ||
+                              ((uintptr_t)dev_state & 7u) || ((uintptr_t)dev_pixels & 3u)
+                          ? "film, table, pyramid, linear and history must be 16-byte aligned, dev_state 8-byte, dev_pixels 4-byte aligned"
+                          : nullptr;
+    if (glare && count != 0 && !bad) {
+        const unsigned long long filmPixels = (unsigned long long)width * (unsigned long long)height;   // below 2^31
+        if (firstPixel > filmPixels || count > filmPixels - firstPixel) return fail(PTSS_ERANGE, "firstPixel + count leaves the film");
+    }
+    FilmCall f;
+    RC_TRY(rangeCall(c, &f, firstPixel, count, bad, true, dev_linear || dev_pixels || dev_history, hipStream));
+    if (!f.go) return PTSS_OK;
+    const ptss::GlareResolveArgs g{width, height, glare, dev_pyramid};
+    HIP_TRY(ptss::launchTonedResolve(f.st, dev_film, filmKind == PTSS_FILM_SPLAT, f.firstPixel, f.n, *params, *tone, dev_table, dev_state,
+                                     glare ? &g : nullptr, c->toneForm, dev_linear, dev_pixels, dev_history, &c->toneLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_tone_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->toneLaunches[0], out2[1] = c->toneLaunches[1];
+    return PTSS_OK;
+}
+
+int ptss_debug_tone_form(ptss_context* c, int form) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
+    c->toneForm = form;
+    return PTSS_OK;
 }
 
 // ptss_render_features_scaled: ptss_render_features' launch for the frame of factor * width x factor * height — the tile map and the eye

@@ -248,6 +248,15 @@ struct GlareResolveArgs {
 hipError_t launchLinearFilmResolve(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
                                    const ptss_meter_state* state, const GlareResolveArgs* glare, const float* quantTable, void* linear,
                                    ptss_uchar4* pixels, void* history, unsigned long long* launches);
+// tone curves for the two linear films (ptss_tone.hip; ptss_tone_build, ptss_resolve_toned). table =
+// pttone::tableFloats(tone.bits) floats, 16-byte aligned. launchTonedResolve: launchLinearFilmResolve's arguments with the tone's
+// parameters and its table; pixels = one 32-bit word per pixel; form: 0 the shipped lookup, 1 the table staged in LDS, 2 the guess settled
+// against global memory. tone: checked by the caller (pttone::paramsError). No bit of ptss_launched_kernels: *launches is incremented once
+// per call that launched
+hipError_t launchToneBuild(hipStream_t st, const ptss_tone_params& tone, float* table, unsigned long long* launches);
+hipError_t launchTonedResolve(hipStream_t st, const void* film, bool splat, uint32_t firstPixel, uint32_t count, const ptss_linear_params& params,
+                              const ptss_tone_params& tone, const float* table, const ptss_meter_state* state, const GlareResolveArgs* glare, int form,
+                              void* linear, uint32_t* pixels, void* history, unsigned long long* launches);
 // the filtered linear film (ptss_splat.hip; ptss_splat_paths / ptss_splat_paths_homed). results = n x 16 B, positions = n x
 // 8 B, film = width x height x 32 B (ptss_splat_entry). launchSplatHomed: sample i is homed at pixel firstPixel + i, n > 0 and firstPixel +
 // n <= width * height. counters: two device words, samples dropped and samples clamped. filter and params: checked by the caller

@@ -18,6 +18,7 @@
 #include "ptsplat.h"
 #include "ptmeter.h"
 #include "ptglare.h"
+#include "pttone.h"
 #include "ptlindn.h"
 #include "ptlinrp.h"
 #include "ptlinup.h"
@@ -989,6 +990,71 @@ int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, 
         ptglare::resolve(e[0], e[1], e[2], glareWeightOf(e, splat), splat, up, R, sc, nullptr, lin, &px, hist);
         if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
         if (pixels) pixels[p] = ptss_uchar4{(unsigned char)px, (unsigned char)(px >> 8), (unsigned char)(px >> 16), (unsigned char)(px >> 24)};
+        if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
+    }
+    return PTSS_HOST_OK;
+}
+
+// ---- tone curves for the two linear films (csrc/pttone.h) ----
+int ptss_probe_tone_build(const ptss_tone_params* params, float* table) {
+    if (pttone::paramsError(params) || !table) return PTSS_HOST_EINVAL;
+    return pttone::buildTable(*params, table) ? PTSS_HOST_OK : PTSS_HOST_ERANGE;   // unsorted: the table is written all the same, its flag set
+}
+
+int ptss_probe_tone_value(const ptss_tone_params* params, const float* x, float* v, size_t n) {
+    if (pttone::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!x || !v) return PTSS_HOST_EINVAL;
+    const pttone::Stage S = pttone::stageOf(*params, params->curve);
+    for (size_t i = 0; i < n; ++i) v[i] = pttone::valueOf(S, x[i]);
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_tone_level(const float* table, int bits, const float* x, uint32_t* level, size_t n) {
+    if (bits != 8 && bits != 10) return PTSS_HOST_EINVAL;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!table || !x || !level) return PTSS_HOST_EINVAL;
+    for (size_t i = 0; i < n; ++i) level[i] = pttone::levelCount(table, pttone::topOf(bits), x[i]);
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_resolve_toned(const void* film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             const ptss_tone_params* tone, const float* table, const ptss_meter_state* state, int width, int height,
+                             const ptss_glare_params* glare, const ptss_glare_entry* pyramid, ptss_history_entry* linear, uint32_t* pixels,
+                             ptss_history_entry* history) {
+    if (ptlin::paramsError(params) || pttone::paramsError(tone)) return PTSS_HOST_EINVAL;
+    if (filmKind != PTSS_FILM_LINEAR && filmKind != PTSS_FILM_SPLAT) return PTSS_HOST_EINVAL;
+    if ((glare == nullptr) != (pyramid == nullptr)) return PTSS_HOST_EINVAL;
+    if (glare && (ptglare::paramsError(glare, *params) || ptglare::sidesError(width, height))) return PTSS_HOST_EINVAL;
+    if (count == 0) return PTSS_HOST_OK;
+    if (!film || !table || firstPixel >= (size_t(1) << 31) || count >= (size_t(1) << 31) || firstPixel + count >= (size_t(1) << 31)) return PTSS_HOST_EINVAL;
+    if (glare) {
+        const size_t filmPixels = (size_t)width * (size_t)height;
+        if (firstPixel > filmPixels || count > filmPixels - firstPixel) return PTSS_HOST_EINVAL;
+    }
+    const bool splat = filmKind == PTSS_FILM_SPLAT;
+    const unsigned long long* words = static_cast<const unsigned long long*>(film);
+    const pttone::Rule R = pttone::ruleOf(*tone);
+    ptglare::Rule G{};
+    if (glare) G = ptglare::ruleOf(*glare, *params);
+    ptlin::Scale sc = ptlin::scaleOf(*params);
+    if (state) sc.exposure = state->exposure * sc.exposure;
+    const int cw = ptglare::halfOf(width), ch = ptglare::halfOf(height);
+    const uint32_t K = R.shown.K;
+    for (size_t p = firstPixel; p < firstPixel + count; ++p) {
+        ptlin::u64 up[3] = {0ull, 0ull, 0ull};
+        if (glare)
+            ptglare::upTexel((int)(p % (size_t)width), (int)(p / (size_t)width), cw, ch, [&](int i, int j, ptlin::u64* v) {
+                const ptss_glare_entry& e = pyramid[(size_t)j * (size_t)cw + (size_t)i];
+                v[0] = e.r, v[1] = e.g, v[2] = e.b;
+            }, up);
+        const unsigned long long* e = words + 4 * p;
+        float lin[4], hist[4];
+        uint32_t px;
+        pttone::resolve(e[0], e[1], e[2], glareWeightOf(e, splat), splat, glare ? up : nullptr, &G, sc, R,
+                        [&](float x) { return pttone::levelCount(table, K, x); }, lin, &px, hist);
+        if (linear) linear[p] = ptss_history_entry{lin[0], lin[1], lin[2], lin[3]};
+        if (pixels) pixels[p] = px;
         if (history) history[p] = ptss_history_entry{hist[0], hist[1], hist[2], hist[3]};
     }
     return PTSS_HOST_OK;

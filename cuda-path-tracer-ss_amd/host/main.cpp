@@ -53,6 +53,12 @@
 //                                    — after the last round ptss_glare_build over the film (default parameters; strength default
 //                                   0.1, threshold default 0, levels default 6) and ptss_resolve_linear_glare (ptss_resolve_splat_glare), with the
 //                                   meter's state where --auto-exposure keeps one. Without it every byte written is today's
+//             [--tone clamp|reinhard[,white]|filmic [--srgb] [--tone-luminance]]   with --film and --linear, with or without --filter,
+//                                   --auto-exposure, --glare, --denoise-linear, --upscale-linear and --refill: the film is shown through a tone curve
+//                                    — ptss_tone_build (8 bits: the TGA's depth; white default 4, the default filmic
+//                                   coefficients; the 2.2 power unless --srgb) and, after the last round, ptss_resolve_toned with the meter's state
+//                                   and the glare pyramid where those options keep them. --tone clamp writes the bytes of the run without it;
+//                                   without the flag every byte written is today's
 //             [--denoise-linear [levels[,sigmaLuminance]]]   with --linear, with or without --filter, --auto-exposure, --glare and --refill: the
 //                                   film is denoised in linear light — the rounds keep the luminance moments
 //                                   (ptss_accumulate_paths_linear_stats; with --filter by home pixel), the features are ptss_ray_features of the
@@ -110,6 +116,9 @@ int main(int argc, char* argv[]) {
     bool glare = false;                        // --glare: the final resolve of the linear film adds the glare pyramid
     float glareStrength = -1.f, glareThreshold = -1.f;   // ... its strength, threshold and levels when given
     int glareLevels = -1;
+    int toneCurve = -1;                        // --tone: the final resolve of the linear film goes through a tone curve (PTSS_TONE_*)
+    float toneWhite = -1.f;                    // ... Reinhard's white point when given
+    bool toneSrgb = false, toneLuminance = false;   // --srgb, --tone-luminance
     bool denoiseLinear = false;                       // --denoise-linear: the linear film is denoised in front of the meter, the glare and the resolve
     int denoiseLinearLevels = -1;                     // ... its levels and sigmaLuminance when given
     float denoiseLinearSigma = -1.f;
@@ -188,6 +197,21 @@ int main(int argc, char* argv[]) {
                 }
             }
         }
+        else if (a == "--tone") {
+            const std::string v = i + 1 < argc ? next() : "";
+            char tail = 0;
+            if (v == "clamp") toneCurve = PTSS_TONE_CLAMP;
+            else if (v == "filmic") toneCurve = PTSS_TONE_FILMIC;
+            else if (v == "reinhard") toneCurve = PTSS_TONE_REINHARD;
+            else if (sscanf(v.c_str(), "reinhard,%f%c", &toneWhite, &tail) == 1 && toneWhite > 0.f && toneWhite <= 65536.f && 1.f / (toneWhite * toneWhite) < 3e38f)
+                toneCurve = PTSS_TONE_REINHARD;
+            else {
+                fprintf(stderr, "bad --tone (clamp | reinhard[,white] | filmic)\n");
+                return 2;
+            }
+        }
+        else if (a == "--srgb") toneSrgb = true;
+        else if (a == "--tone-luminance") toneLuminance = true;
         else if (a == "--denoise-linear") {
             denoiseLinear = true;
             const char* v = i + 1 < argc ? argv[i + 1] : "";
@@ -269,6 +293,8 @@ int main(int argc, char* argv[]) {
     if (adaptiveLinear >= 0 && linear < 0.f) { fprintf(stderr, "--adaptive-linear needs --film and --linear\n"); return 2; }
     if (autoExposure && linear < 0.f) { fprintf(stderr, "--auto-exposure needs --linear\n"); return 2; }
     if (glare && linear < 0.f) { fprintf(stderr, "--glare needs --linear\n"); return 2; }
+    if (toneCurve >= 0 && linear < 0.f) { fprintf(stderr, "--tone needs --film and --linear\n"); return 2; }
+    if ((toneSrgb || toneLuminance) && toneCurve < 0) { fprintf(stderr, "--srgb and --tone-luminance need --tone\n"); return 2; }
     if (denoiseLinear && linear < 0.f) { fprintf(stderr, "--denoise-linear needs --film and --linear\n"); return 2; }
     if (upscaleLinear != 0 && (linear < 0.f || carry || adaptiveLinear >= 0 || denoise != -2)) {
         fprintf(stderr, "--upscale-linear needs --film and --linear, and none of --carry, --adaptive-linear, --denoise\n");
@@ -709,7 +735,32 @@ int main(int argc, char* argv[]) {
                 printf("auto-exposure: exposure %.9g target %.9g meanLog2 %.9g updates %u metered %llu black %llu counted %llu sumLog %llu\n", state.exposure,
                        state.target, state.meanLog2, state.updates, state.metered, state.black, state.counted, state.sumLog);
             }
-            if (glare) {   // the pyramid of the finished film, and the resolve that adds it: at the meter's exposure where there is one
+            if (toneCurve >= 0) {   // the finished film through the tone curve, with the meter's state and the glare pyramid where there are any
+                const ptss_meter_state* state = autoExposure ? (const ptss_meter_state*)dMeter : NULL;
+                ptss_tone_params tone;
+                PTSS_HANDLE(ptss_default_tone_params(&tone));
+                tone.curve = toneCurve;
+                tone.transfer = toneSrgb ? PTSS_TRANSFER_SRGB : PTSS_TRANSFER_GAMMA22;
+                tone.flags = toneLuminance ? PTSS_TONE_LUMINANCE : 0u;
+                if (toneWhite > 0.f) tone.white = toneWhite;
+                void* dToneTable = nullptr;
+                if (hipMalloc(&dToneTable, ptss_tone_table_floats(tone.bits) * sizeof(float)) != hipSuccess) { fprintf(stderr, "--tone: device buffers\n"); return 1; }
+                PTSS_HANDLE(ptss_tone_build(ctx, &tone, (float*)dToneTable, NULL));
+                if (glare)
+                    PTSS_HANDLE(ptss_glare_build(ctx, shown, shownSplat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, shownW, shownH, &linearParams,
+                                                 &glareParams, (ptss_glare_entry*)dPyramid, NULL));
+                PTSS_HANDLE(ptss_resolve_toned(ctx, shown, shownSplat ? PTSS_FILM_SPLAT : PTSS_FILM_LINEAR, 0, shownN, &linearParams, &tone,
+                                               (const float*)dToneTable, state, shownW, shownH, glare ? &glareParams : NULL,
+                                               glare ? (const ptss_glare_entry*)dPyramid : NULL, (ptss_history_entry*)dShownMeans, (uint32_t*)dShownPixels,
+                                               (ptss_history_entry*)dShownHist, NULL));
+                PTSS_HANDLE(ptss_synchronize(ctx));
+                float flag = 1.f;   // T[K + 2]: 0 where the thresholds are in order
+                if (hipMemcpy(&flag, (const float*)dToneTable + (1 << tone.bits) + 1, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess || flag != 0.f) {
+                    fprintf(stderr, "--tone: the table's thresholds are not in order\n");
+                    return 1;
+                }
+                (void)hipFree(dToneTable);
+            } else if (glare) {   // the pyramid of the finished film, and the resolve that adds it: at the meter's exposure where there is one
                 const ptss_meter_state* state = autoExposure ? (const ptss_meter_state*)dMeter : NULL;
                 PTSS_HANDLE(ptss_glare_build(ctx, shown, shownSplat ? PTSS_GLARE_FILM_SPLAT : PTSS_GLARE_FILM_LINEAR, shownW, shownH, &linearParams, &glareParams,
                                              (ptss_glare_entry*)dPyramid, NULL));

@@ -24,6 +24,7 @@ from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SP
 from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DENOISE_MAX_LEVELS, FILM_LINEAR, FILM_SPLAT, DenoiseLinearParams
 from ptss_types import REPROJECT_LINEAR_INFO_DTYPE, REPROJECT_LINEAR_MAX_HISTORY, ReprojectLinearParams
 from ptss_types import UPSAMPLE_LINEAR_INFO_DTYPE, UPSAMPLE_LINEAR_WRAP_X, UpsampleLinearParams
+from ptss_types import TONE_CLAMP, TONE_FILMIC, TONE_LUMINANCE, TONE_REINHARD, TRANSFER_GAMMA22, TRANSFER_SRGB, ToneParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.path.join(_HERE, "lib")
@@ -219,6 +220,11 @@ def host_lib():
         L.ptss_probe_glare_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LinearParams), C.POINTER(GlareParams), C.c_void_p]
         L.ptss_probe_resolve_glare.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.c_int, C.c_int,
                                                C.POINTER(GlareParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ptss_probe_tone_build.argtypes = [C.POINTER(ToneParams), C.c_void_p]
+        L.ptss_probe_tone_value.argtypes = [C.POINTER(ToneParams), C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ptss_probe_tone_level.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.ptss_probe_resolve_toned.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.POINTER(ToneParams), C.c_void_p,
+                                               C.c_void_p, C.c_int, C.c_int, C.POINTER(GlareParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ptss_probe_denoise_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LinearParams),
                                                 C.POINTER(DenoiseLinearParams), C.c_void_p, C.c_void_p]
         L.ptss_probe_denoise_linear_finish.argtypes = [C.POINTER(C.c_float), C.c_ulonglong, C.c_int, C.POINTER(LinearParams), C.POINTER(C.c_ulonglong)]
@@ -351,6 +357,14 @@ def device_lib():
                                                 vp, vp, vp, vp]
         L.ptss_resolve_splat_glare.argtypes = L.ptss_resolve_linear_glare.argtypes
         L.ptss_glare_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_default_tone_params.argtypes = [C.POINTER(ToneParams)]
+        L.ptss_tone_table_floats.argtypes = [C.c_int]
+        L.ptss_tone_table_floats.restype = C.c_size_t
+        L.ptss_tone_build.argtypes = [vp, C.POINTER(ToneParams), vp, vp]
+        L.ptss_resolve_toned.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_size_t, C.POINTER(LinearParams), C.POINTER(ToneParams), vp, vp, C.c_int, C.c_int,
+                                         C.POINTER(GlareParams), vp, vp, vp, vp, vp]
+        L.ptss_tone_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_tone_form.argtypes = [vp, C.c_int]
         L.ptss_default_denoise_linear_params.argtypes = [C.POINTER(DenoiseLinearParams)]
         L.ptss_denoise_linear_workspace.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_size_t)]
         L.ptss_denoise_linear.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(LinearParams), C.POINTER(DenoiseLinearParams), vp, vp, vp]
@@ -1082,6 +1096,121 @@ def probe_resolve_glare(film, width, height, pyramid, first_pixel=0, count=None,
                                              ptr(st), ptr(ln), ptr(px), ptr(hs))
     if rc != 0:
         raise PtssError(f"ptss_probe_resolve_glare: {rc}")
+    return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+
+# ---- tone curves for the two linear films (ptss_tone_build, ptss_resolve_toned) ----
+_TONE_CURVES = {"clamp": TONE_CLAMP, "reinhard": TONE_REINHARD, "filmic": TONE_FILMIC}
+_TONE_TRANSFERS = {"gamma22": TRANSFER_GAMMA22, "srgb": TRANSFER_SRGB}
+TONE_DEFAULT_FILMIC = (2.51, 0.03, 2.43, 0.59, 0.14)
+
+
+def tone_params(curve="filmic", transfer="srgb", bits=8, luminance=False, white=4.0, filmic=TONE_DEFAULT_FILMIC):
+    """A ptss_tone_params; curve: "clamp", "reinhard", "filmic" or a PTSS_TONE_* value; transfer: "gamma22", "srgb" or a PTSS_TRANSFER_*
+    value; the defaults are ptss_default_tone_params' (design choices, not measurements)."""
+    p = ToneParams()
+    p.structSize = C.sizeof(ToneParams)
+    p.curve, p.transfer, p.bits = int(_TONE_CURVES.get(curve, curve)), int(_TONE_TRANSFERS.get(transfer, transfer)), int(bits)
+    p.flags, p.white, p.reserved = (TONE_LUMINANCE if luminance else 0), float(white), 0
+    p.filmic[:] = [float(v) for v in filmic]
+    return p
+
+
+def tone_table_floats(bits):
+    """ptss_tone_table_floats: the floats of a table, 2^bits + 4."""
+    if bits not in (8, 10):
+        raise ValueError("bits: 8 or 10")
+    return (1 << bits) + 4
+
+
+def tone_table_sorted(table):
+    """Whether a table's builder found its thresholds in order: its flag T[K + 2] is 0."""
+    t = np.asarray(table, dtype=np.float32).reshape(-1)
+    return float(t[len(t) - 3]) == 0.0
+
+
+def _tone_table(table, bits):
+    t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+    if len(t) != tone_table_floats(bits):
+        raise ValueError("table: tone_table_floats(bits) float32")
+    return t
+
+
+def probe_tone_build(tone=None):
+    """ptss_tone_build on the host (csrc/pttone.h; the specification of the device's table) -> (tone_table_floats(bits),) float32: T[0] =
+    -inf, T[1 .. K], NaN, the flag (0: in order), NaN, NaN. Raises where the thresholds came out of order."""
+    tone = tone if tone is not None else tone_params()
+    if tone.bits not in (8, 10):
+        raise PtssError("ptss_probe_tone_build: -1")
+    out = np.zeros(tone_table_floats(tone.bits), dtype=np.float32)
+    rc = host_lib().ptss_probe_tone_build(C.byref(tone), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_tone_build: {rc}")
+    return out
+
+
+def probe_tone_value(tone, x):
+    """The literal display value transfer(curve(x)) of `tone`, float32 in and out."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    v = np.zeros(x.shape, dtype=np.float32)
+    rc = host_lib().ptss_probe_tone_value(C.byref(tone), x.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), x.size)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_tone_value: {rc}")
+    return v
+
+
+def probe_tone_level(table, bits, x):
+    """The level of x by the table: the number of k in 1 .. K with x >= table[k] -> uint32, x's shape."""
+    t = _tone_table(table, bits)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.zeros(x.shape, dtype=np.uint32)
+    rc = host_lib().ptss_probe_tone_level(t.ctypes.data_as(C.c_void_p), int(bits), x.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), x.size)
+    if rc != 0:
+        raise PtssError(f"ptss_probe_tone_level: {rc}")
+    return out
+
+
+def unpack_pixels10(pixels):
+    """The words of a 10-bit toned resolve, (P, 4) uint8 or (P,) uint32 -> (P, 4) uint16: r, g, b in 0 .. 1023 and the two alpha bits."""
+    w = np.ascontiguousarray(pixels)
+    w = w.view(np.uint32).reshape(-1) if w.dtype == np.uint8 else w.astype(np.uint32).reshape(-1)
+    return np.stack([w & 1023, (w >> 10) & 1023, (w >> 20) & 1023, w >> 30], axis=1).astype(np.uint16)
+
+
+def pack_pixels10(rgba):
+    """unpack_pixels10's inverse -> (P, 4) uint8, the words' bytes."""
+    a = np.asarray(rgba, dtype=np.uint32).reshape(-1, 4)
+    w = (a[:, 0] & 1023) | ((a[:, 1] & 1023) << 10) | ((a[:, 2] & 1023) << 20) | ((a[:, 3] & 3) << 30)
+    return np.ascontiguousarray(w.astype(np.uint32)).view(np.uint8).reshape(-1, 4)
+
+
+def probe_resolve_toned(film, tone, table, first_pixel=0, count=None, params=None, state=None, glare=None, linear=True, pixels=True, history=True,
+                        film_kind=None):
+    """ptss_resolve_toned on the host -> probe_resolve_linear's results, pixels as the (P, 4) bytes of the words (unpack_pixels10 for 10
+    bits). film: (P,) LINEAR_DTYPE or SPLAT_DTYPE, or (P, 4) uint64 with film_kind; table: what probe_tone_build or Renderer.tone_build gave
+    for `tone`; state: a meter's state or None; glare: None or (width, height, a glare_params, the film's pyramid)."""
+    if film_kind is None:
+        film_kind = FILM_SPLAT if np.asarray(film).dtype == SPLAT_DTYPE else FILM_LINEAR
+    kind = int(_GLARE_FILMS.get(film_kind, film_kind))
+    f = _rows(film, SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE, 4, np.uint64, "film")
+    P = len(f)
+    first_pixel, count = _linear_range(P, first_pixel, count)
+    params = params if params is not None else linear_params()
+    t = _tone_table(table, tone.bits)
+    width = height = 0
+    g_params = pyr = None
+    if glare is not None:
+        width, height, g_params, g_pyramid = glare
+        if P != int(width) * int(height):
+            raise ValueError("film: width * height entries")
+        pyr = _glare_pyramid(g_pyramid, glare_layout(width, height, g_params.levels)[1])
+    ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
+    st = _meter_state(state) if state is not None else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    rc = host_lib().ptss_probe_resolve_toned(ptr(f), kind, first_pixel, count, C.byref(params), C.byref(tone), ptr(t), ptr(st), int(width), int(height),
+                                             C.byref(g_params) if g_params is not None else None, ptr(pyr), ptr(ln), ptr(px), ptr(hs))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_resolve_toned: {rc}")
     return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
 
@@ -2215,7 +2344,7 @@ class Renderer:
         _check(device_lib().ptss_linear_stats_launches(self._ctx, out))
         return int(out[0]), int(out[1])
 
-    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None):
+    def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None, tone=None):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
         numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64; linear / pixels / history: None (NULL), True (zeros beforehand) or the buffer's
         content beforehand -> (linear (P,) HISTORY_DTYPE: the unexposed means and the sample count, pixels (P, 4) uint8, history (P,)
@@ -2224,19 +2353,29 @@ class Renderer:
         metered: a meter's state (numpy: a METER_STATE_DTYPE record; torch: a (6,) int64 device tensor) -> ptss_resolve_linear_metered:
         the exposure is the state's times params.exposure. Without it ptss_resolve_linear is called.
         glare: (width, height, a glare_params, the pyramid glare_build gave for this film and those parameters; torch: an (entries, 4)
-        int64 device tensor) -> ptss_resolve_linear_glare, with `metered` as its state or NULL."""
+        int64 device tensor) -> ptss_resolve_linear_glare, with `metered` as its state or NULL.
+        tone: (a tone_params, the table tone_build gave for it; torch: a (tone_table_floats(bits),) float32 device tensor) ->
+        ptss_resolve_toned, with `metered` and `glare` as its state and its pyramid; pixels are the words' bytes (unpack_pixels10)."""
         L = device_lib()
         return self._resolve(L.ptss_resolve_linear, L.ptss_resolve_linear_metered, LINEAR_DTYPE, film, first_pixel, count, params, linear, pixels,
-                             history, metered, L.ptss_resolve_linear_glare, glare)
+                             history, metered, L.ptss_resolve_linear_glare, glare, tone, FILM_LINEAR)
 
-    def _resolve(self, plain, with_state, film_dtype, film, first_pixel, count, params, linear, pixels, history, metered, with_glare=None, glare=None):
-        """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, `with_state` where `metered` is a state, or
-        `with_glare` where `glare` is (width, height, glare_params, pyramid)."""
+    def _resolve(self, plain, with_state, film_dtype, film, first_pixel, count, params, linear, pixels, history, metered, with_glare=None, glare=None,
+                 tone=None, film_kind=FILM_LINEAR):
+        """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, `with_state` where `metered` is a state,
+        `with_glare` where `glare` is (width, height, glare_params, pyramid), or ptss_resolve_toned where `tone` is (tone_params, table)."""
         params = params if params is not None else linear_params()
-        d_pyr = pyr = None
+        d_pyr = pyr = d_table = table = None
         if glare is not None:
             g_width, g_height, g_params, g_pyramid = glare
             g_entries = glare_layout(g_width, g_height, g_params.levels)[1]
+        if tone is not None:
+            t_params, t_table = tone
+            toned = device_lib().ptss_resolve_toned
+            call = lambda ctx, f, first, n, par, ln, px, hs, st: toned(
+                ctx, f, int(film_kind), first, n, par, C.byref(t_params), d_table, d_state, int(g_width) if glare is not None else 0,
+                int(g_height) if glare is not None else 0, C.byref(g_params) if glare is not None else None, d_pyr, ln, px, hs, st)
+        elif glare is not None:
             call = lambda ctx, f, first, n, par, ln, px, hs, st: with_glare(ctx, f, first, n, par, int(g_width), int(g_height), C.byref(g_params),
                                                                            d_pyr, d_state, ln, px, hs, st)
         elif metered is None:
@@ -2254,6 +2393,8 @@ class Renderer:
                 if P != int(g_width) * int(g_height):
                     raise ValueError("film: width * height entries")
                 d_pyr = self._torch_ptr(g_pyramid, "pyramid", "int64", 4, dev, g_entries)
+            if tone is not None:
+                d_table = self._torch_ptr(t_table, "table", "float32", 0, dev, tone_table_floats(t_params.bits))
             d_ln = self._torch_ptr(linear, "linear", "float32", 4, dev, P) if linear is not None else None
             d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
             d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
@@ -2270,14 +2411,16 @@ class Renderer:
             if P != int(g_width) * int(g_height):
                 raise ValueError("film: width * height entries")
             pyr = _glare_pyramid(g_pyramid, g_entries)
+        if tone is not None:
+            table = _tone_table(t_table, t_params.bits)
         if count == 0:
             _check(call(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
         else:
             def run(d):
-                nonlocal d_state, d_pyr
-                d_state, d_pyr = d[4], d[5]
+                nonlocal d_state, d_pyr, d_table
+                d_state, d_pyr, d_table = d[4], d[5], d[6]
                 _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None))
-            self._round_trip([f, ln, px, hs, state, pyr], run, read=(1, 2, 3))
+            self._round_trip([f, ln, px, hs, state, pyr, table], run, read=(1, 2, 3))
         return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
 
     # --- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat) ------------------
@@ -2319,13 +2462,42 @@ class Renderer:
             self._round_trip([r, pos, f], lambda d: call(d[0], d[1], n, d[2], None), read=(2,))
         return f.view(SPLAT_DTYPE).reshape(-1)
 
-    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None):
+    def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None, tone=None):
         """ptss_resolve_splat: resolve_linear's arguments and results over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64); the
         weight of linear and history is the summed filter weight. metered: as in resolve_linear (ptss_resolve_splat_metered); glare: as in
-        resolve_linear (ptss_resolve_splat_glare)."""
+        resolve_linear (ptss_resolve_splat_glare); tone: as in resolve_linear (ptss_resolve_toned with PTSS_FILM_SPLAT)."""
         L = device_lib()
         return self._resolve(L.ptss_resolve_splat, L.ptss_resolve_splat_metered, SPLAT_DTYPE, film, first_pixel, count, params, linear, pixels,
-                             history, metered, L.ptss_resolve_splat_glare, glare)
+                             history, metered, L.ptss_resolve_splat_glare, glare, tone, FILM_SPLAT)
+
+    # --- tone curves for the two linear films (ptss_tone_build; the resolves take tone=) ------------------
+    def tone_build(self, tone=None, table=None):
+        """ptss_tone_build: the table of a tone_params on the device. numpy (table None) -> (tone_table_floats(bits),) float32, the bytes of
+        probe_tone_build; raises where the thresholds came out of order. torch: table a (tone_table_floats(bits),) float32 device tensor
+        WRITTEN IN PLACE -> None, on the current stream (tone_table_sorted reads its flag)."""
+        L = device_lib()
+        tone = tone if tone is not None else tone_params()
+        if table is not None:
+            import sys
+            torch = sys.modules["torch"]
+            d_table = self._torch_ptr(table, "table", "float32", 0, None, tone_table_floats(tone.bits) if tone.bits in (8, 10) else None)
+            _check(L.ptss_tone_build(self._ctx, C.byref(tone), d_table, C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
+            return None
+        out = np.zeros(tone_table_floats(tone.bits) if tone.bits in (8, 10) else 4, dtype=np.float32)
+        self._round_trip([out], lambda d: _check(L.ptss_tone_build(self._ctx, C.byref(tone), d[0], None)), read=(0,))
+        if not tone_table_sorted(out):
+            raise PtssError("ptss_tone_build: the thresholds are not in order")
+        return out
+
+    def tone_launches(self):
+        """ptss_tone_launches: (tone_build calls, toned resolves that launched since the context was created)."""
+        out = (C.c_ulonglong * 2)()
+        _check(device_lib().ptss_tone_launches(self._ctx, out))
+        return int(out[0]), int(out[1])
+
+    def debug_tone_form(self, form):
+        """ptss_debug_tone_form: 0 the shipped lookup, 1 the table staged in LDS, 2 the guess settled against global memory."""
+        _check(device_lib().ptss_debug_tone_form(self._ctx, int(form)))
 
     # --- glare for the two linear films (ptss_glare_build; the resolves take glare=) ------------------
     def glare_build(self, film, width, height, params=None, glare=None, film_kind=None, pyramid=None):

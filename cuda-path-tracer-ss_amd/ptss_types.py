@@ -242,6 +242,17 @@ class UpsampleLinearParams(C.Structure):   # ptss_upsample_linear_params
 UPSAMPLE_LINEAR_INFO_DTYPE = np.dtype([("filtered", np.uint64), ("fallback", np.uint64), ("empty", np.uint64)])
 
 
+# tone curves for the two linear films (include/ptss_types.h PTSS_TONE_*, PTSS_TRANSFER_*)
+TONE_CLAMP, TONE_REINHARD, TONE_FILMIC = 0, 1, 2
+TRANSFER_GAMMA22, TRANSFER_SRGB = 0, 1
+TONE_LUMINANCE = 1
+
+
+class ToneParams(C.Structure):   # ptss_tone_params: the curve, the transfer function, the bit depth
+    _fields_ = [("structSize", C.c_uint), ("curve", C.c_int), ("transfer", C.c_int), ("bits", C.c_int), ("flags", C.c_uint), ("white", C.c_float),
+                ("filmic", C.c_float * 5), ("reserved", C.c_uint)]
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {
@@ -294,6 +305,7 @@ assert C.sizeof(SplatEntry) == 32 == SPLAT_DTYPE.itemsize and SplatEntry.weight.
 assert C.sizeof(MeterParams) == 32 and MeterParams.reserved.offset == 28 and C.sizeof(MeterState) == 48 == METER_STATE_DTYPE.itemsize
 assert MeterState.metered.offset == 16 == METER_STATE_DTYPE.fields["metered"][1] and MeterState.sumLog.offset == 40 == METER_STATE_DTYPE.fields["sumLog"][1]
 assert C.sizeof(GlareParams) == 24 and GlareParams.reserved.offset == 20 and C.sizeof(GlareLevel) == 16 and GLARE_DTYPE.itemsize == 32
+assert C.sizeof(ToneParams) == 48 and ToneParams.white.offset == 20 and ToneParams.filmic.offset == 24 and ToneParams.reserved.offset == 44
 
 
 def struct_to_dict(s):

@@ -719,6 +719,47 @@ int ptss_upsample_linear(ptss_context* ctx, const void* dev_film_lo, int filmKin
 int ptss_upsample_linear_launches(const ptss_context* ctx, unsigned long long* out); /* calls that launched */
 int ptss_debug_upsample_linear_form(ptss_context* ctx, int form);
 
+/* Tone curves for the two linear films: a shoulder instead of the hard clip at display white, the sRGB transfer
+ * function, 10 bits. The last step of generate -> trace -> accumulate -> denoise -> reproject -> upsample -> meter -> glare -> resolve.
+ * csrc/pttone.h has the arithmetic; its host build (ptss_probe_tone_*) is the specification and the device equals it byte for byte. A
+ * quantised curve is a step function of its input, so it is fully described by its thresholds: whatever the curve costs in float
+ * operations, the pixel is a search in a table, and THE TABLE IS THE SPECIFICATION OF THE PIXEL: the level of x is the number of k in
+ * 1 .. K (K = 2^bits - 1) with x >= T[k]; NaN and negatives give 0.
+ *
+ * ptss_default_tone_params: PTSS_TONE_FILMIC, PTSS_TRANSFER_SRGB, 8 bits, no flags, white 4, filmic 2.51, 0.03, 2.43, 0.59, 0.14 (design
+ * choices, not measurements). ptss_tone_table_floats: the floats of a table, 2^bits + 4 (0 for other bits).
+ *
+ * ptss_tone_build: the table of `tone` on the device, by one kernel of one thread per threshold and 31 bisection steps of the literal
+ * level; nothing returns to the host. T[0] = -inf, T[1 .. K], T[K + 1] = NaN, T[K + 2] = 0 — or 1 where the thresholds came out of order,
+ * which the bisections' shared midpoints rule out (csrc/pttone.h) and which a caller can read back —, T[K + 3] = T[K + 4] = NaN. dev_table: 16-byte aligned. The bytes
+ * are ptss_probe_tone_build's.
+ *
+ * ptss_resolve_toned: the six linear resolves behind one entry point, shown through the table. filmKind: the film is ptss_linear_entry
+ * or ptss_splat_entry. dev_state: NULL or a meter's state (the exposure is state->exposure * params->exposure). glare with dev_pyramid:
+ * both NULL, or the parameters and the pyramid of ptss_glare_build for this film (width and height are read only then): the glare
+ * resolves' m'. Channel input x_c = mean_c * exposure, or with PTSS_TONE_LUMINANCE x_c scaled by curve(Y) / Y of the exposed luminance Y,
+ * the table being that of the clamp. dev_linear: the unexposed means and the weight, as every linear resolve writes them; dev_pixels: one
+ * 32-bit word per pixel, r | g << 8 | b << 16 | 255 << 24 at 8 bits, r | g << 10 | b << 20 | 3 << 30 at 10; dev_history: 255 * the literal
+ * display value of x_c and the weight, on the denoiser's 0 .. 255 scale at either depth. A pixel without samples or weight gives the
+ * empty row (zeros, the alpha bits set). Each output may be NULL. tone must be what dev_table was built from. PTSS_TONE_CLAMP with
+ * PTSS_TRANSFER_GAMMA22 at 8 bits without flags writes the bytes of the plain, metered and glare resolves.
+ * Asynchronous on hipStream (NULL: the context's), no frame state, any shard. Nothing to write (count == 0 or all three outputs NULL) is
+ * PTSS_OK without a launch. Refused before the device is touched, nothing counted: whatever the sibling resolves refuse, and PTSS_EINVAL
+ * for an unknown film kind, a null or misaligned table, a tone structSize, curve, transfer, flag, bits, white, filmic[] or reserved
+ * outside what ptss_types.h states, a pyramid without glare parameters.
+ * ptss_debug_tone_form (tests and measurements): 0 the shipped lookup, 1 the table staged in LDS and a branch-free binary search, 2 a
+ * first guess from the hardware log2 / exp2 settled by exact comparisons against the table in global memory. The bytes are the same. */
+int ptss_default_tone_params(ptss_tone_params* params);
+size_t ptss_tone_table_floats(int bits);
+int ptss_tone_build(ptss_context* ctx, const ptss_tone_params* tone, float* dev_table, void* hipStream);
+int ptss_resolve_toned(ptss_context* ctx, const void* dev_film, int filmKind /* PTSS_FILM_LINEAR | PTSS_FILM_SPLAT */, size_t firstPixel, size_t count,
+                       const ptss_linear_params* params, const ptss_tone_params* tone, const float* dev_table,
+                       const ptss_meter_state* dev_state /* may be NULL */, int width, int height, const ptss_glare_params* glare /* may be NULL */,
+                       const ptss_glare_entry* dev_pyramid /* NULL with glare NULL */, ptss_history_entry* dev_linear, uint32_t* dev_pixels,
+                       ptss_history_entry* dev_history, void* hipStream);
+int ptss_tone_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] table builds, [1] toned resolves */
+int ptss_debug_tone_form(ptss_context* ctx, int form);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

@@ -275,6 +275,23 @@ int ptss_probe_resolve_glare(const void* film, int filmKind, size_t firstPixel, 
                              int height, const ptss_glare_params* glare, const ptss_glare_entry* pyramid, const ptss_meter_state* state,
                              ptss_history_entry* linear, ptss_uchar4* pixels, ptss_history_entry* history);
 
+/* Tone curves on the host (csrc/pttone.h — the very operations the kernels evaluate; this build is the specification).
+ * ptss_probe_tone_build: ptss_tone_build on the host. table: ptss_tone_table_floats(params->bits) = 2^bits + 4 floats, all written: T[0] =
+ * -inf, the thresholds T[1 .. K] (K = 2^bits - 1), T[K + 1] = NaN, T[K + 2] = 0 (1 where the thresholds are not in order: the call then
+ * returns PTSS_HOST_ERANGE), T[K + 3] = T[K + 4] = NaN.
+ * ptss_probe_tone_value: the literal display value transfer(curve(x)) of the parameters' own curve, whatever their flags.
+ * ptss_probe_tone_level: the level of x by the table: the number of k in 1 .. K with x >= table[k].
+ * ptss_probe_resolve_toned: ptss_resolve_toned on the host, over either film kind: pixels firstPixel .. firstPixel + count, one 32-bit word
+ * per pixel in `pixels`. state may be NULL; glare and pyramid are both NULL or both given, width and height are read only then; linear /
+ * pixels / history each may be NULL. PTSS_HOST_EINVAL: whatever the device calls refuse, alignment aside. */
+int ptss_probe_tone_build(const ptss_tone_params* params, float* table);
+int ptss_probe_tone_value(const ptss_tone_params* params, const float* x, float* v, size_t n);
+int ptss_probe_tone_level(const float* table, int bits, const float* x, uint32_t* level, size_t n);
+int ptss_probe_resolve_toned(const void* film, int filmKind, size_t firstPixel, size_t count, const ptss_linear_params* params,
+                             const ptss_tone_params* tone, const float* table, const ptss_meter_state* state, int width, int height,
+                             const ptss_glare_params* glare, const ptss_glare_entry* pyramid, ptss_history_entry* linear, uint32_t* pixels,
+                             ptss_history_entry* history);
+
 /* The denoiser of the two linear films on the host (csrc/ptlindn.h — the very operations the kernels evaluate; this build is the
  * specification). ptss_probe_denoise_linear: ptss_denoise_linear as straight loops over host memory, without a workspace. out: width *
  * height entries, all written. out_plane (may be NULL): width * height rows {c.r, c.g, c.b, v} of the last plane the call computed —

@@ -428,6 +428,28 @@ typedef struct ptss_upsample_linear_info {
     unsigned long long empty;    /* no tap counted and the nearest lo pixel is empty: an all-zero row */
 } ptss_upsample_linear_info;
 
+/* Tone curves for the two linear films (ptss_tone_build, ptss_resolve_toned; csrc/pttone.h): a curve, a transfer
+ * function and a bit depth, evaluated once into a table of thresholds that the resolve searches. white: PTSS_TONE_REINHARD only, the input
+ * that reaches display white, finite, in (0, 65536] with 1 / white^2 finite in float32. filmic[5] = a, b, c, d, e of
+ * x (a x + b) / (x (c x + d) + e), PTSS_TONE_FILMIC only: finite, >= 0, e > 0, and such that the curve is a number at the saturation
+ * bound 2^40 (csrc/pttone.h). PTSS_TONE_LUMINANCE: the curve moves the luminance and the channels follow it, keeping their ratios. */
+#define PTSS_TONE_CLAMP 0
+#define PTSS_TONE_REINHARD 1
+#define PTSS_TONE_FILMIC 2
+#define PTSS_TRANSFER_GAMMA22 0
+#define PTSS_TRANSFER_SRGB 1
+#define PTSS_TONE_LUMINANCE 1u
+typedef struct ptss_tone_params {
+    unsigned int structSize; /* sizeof(ptss_tone_params) as the caller compiled it */
+    int curve;               /* PTSS_TONE_*                  default PTSS_TONE_FILMIC   */
+    int transfer;            /* PTSS_TRANSFER_*              default PTSS_TRANSFER_SRGB */
+    int bits;                /* 8 or 10                      default 8                  */
+    unsigned int flags;      /* PTSS_TONE_LUMINANCE          default 0                  */
+    float white;             /*                              default 4                  */
+    float filmic[5];         /*                              default 2.51, 0.03, 2.43, 0.59, 0.14 */
+    unsigned int reserved;   /* 0 */
+} ptss_tone_params;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -534,6 +556,9 @@ static_assert(sizeof(ptss_upsample_linear_params) == 24 && offsetof(ptss_upsampl
 static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample_linear_info, fallback) == 8 &&
                   offsetof(ptss_upsample_linear_info, empty) == 16,
               "ptss_upsample_linear_info is three 64-bit words");
+static_assert(sizeof(ptss_tone_params) == 48 && offsetof(ptss_tone_params, curve) == 4 && offsetof(ptss_tone_params, bits) == 12 &&
+                  offsetof(ptss_tone_params, white) == 20 && offsetof(ptss_tone_params, filmic) == 24 && offsetof(ptss_tone_params, reserved) == 44,
+              "ptss_tone_params is twelve 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -608,6 +633,9 @@ _Static_assert(sizeof(ptss_upsample_linear_params) == 24 && offsetof(ptss_upsamp
 _Static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample_linear_info, fallback) == 8 &&
                    offsetof(ptss_upsample_linear_info, empty) == 16,
                "ptss_upsample_linear_info is three 64-bit words");
+_Static_assert(sizeof(ptss_tone_params) == 48 && offsetof(ptss_tone_params, curve) == 4 && offsetof(ptss_tone_params, bits) == 12 &&
+                   offsetof(ptss_tone_params, white) == 20 && offsetof(ptss_tone_params, filmic) == 24 && offsetof(ptss_tone_params, reserved) == 44,
+               "ptss_tone_params is twelve 32-bit words");
 #endif
 
 #ifdef __cplusplus
