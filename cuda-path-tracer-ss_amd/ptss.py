@@ -9,6 +9,7 @@ imports torch.
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -239,12 +240,26 @@ def host_lib():
     return _host
 
 
+def _torch():
+    """torch where the caller has imported it, None otherwise: the one place that looks for it (nothing here imports it)."""
+    return sys.modules.get("torch")
+
+
+def _is_torch(value):
+    """Whether `value` is a torch object: what sends a Renderer call down its tensor path."""
+    return type(value).__module__.split(".")[0] == "torch"
+
+
+def _stream_of(torch, device):
+    """The raw handle of torch's current stream on `device`."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
 def _torch_first():
     """PyTorch bundles its own HIP runtime and libptss.so links ROCm's; both may share a process, but torch's must initialise
     first or a later torch.cuda call can fail with "No HIP GPUs are available" (INTEGRATION.md §5). If torch is already
     imported, initialise it now — before libptss.so's runtime touches the device."""
-    import sys
-    torch = sys.modules.get("torch")
+    torch = _torch()
     if torch is None:
         return
     try:
@@ -585,6 +600,26 @@ HISTORY_DTYPE = np.dtype([("r", np.float32), ("g", np.float32), ("b", np.float32
 assert HISTORY_DTYPE.itemsize == C.sizeof(HistoryEntry)
 MOTION_DTYPE = np.dtype([("prevPoint", np.float32, 3), ("surface", np.int32)])
 assert MOTION_DTYPE.itemsize == C.sizeof(PixelMotion)
+
+
+def _query_rays(rays):
+    """The rays of a ray or a path query as (N, 8) float32 rows."""
+    a = np.asarray(rays)
+    if a.dtype == RAY_DTYPE:
+        a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 8:
+        raise ValueError("rays: (N, 8) float32 or (N,) RAY_DTYPE")
+    return a
+
+
+# what the queries say of a tensor they refuse
+_QUERY_TEXTS = {"rays": "rays: a contiguous (N, 8) float32 device tensor", "rng": "rng: a contiguous (N, 6) int32 tensor on the rays' device"}
+
+
+def _records(rows, dtype):
+    """Plain rows as (N,) records of `dtype`; None stays None."""
+    return rows.view(dtype).reshape(-1) if rows is not None else None
 
 
 # ---- the schedule of a path query (ptss_trace_paths_opt; DESIGN.md §3.27) ----
@@ -1025,7 +1060,13 @@ def probe_meter_exposure(histogram, state=None, params=None, meter=None):
 
 # ---- glare for the two linear films (ptss_glare_build and the glare resolves) ----
 _GLARE_MODES = {"add": GLARE_ADD, "mix": GLARE_MIX}
-_GLARE_FILMS = {"linear": GLARE_FILM_LINEAR, "splat": GLARE_FILM_SPLAT}
+_FILM_KINDS = {"linear": FILM_LINEAR, "splat": FILM_SPLAT}   # the names of the PTSS_FILM_* values (the glare calls' PTSS_GLARE_FILM_* are the same)
+
+
+def _film_kind(film_kind, default=None):
+    """A film_kind argument as its PTSS_FILM_* value: "linear", "splat" or a value; None: `default`."""
+    film_kind = default if film_kind is None else film_kind
+    return int(_FILM_KINDS.get(film_kind, film_kind))
 
 
 def glare_params(levels=6, mode="mix", threshold=0.0, strength=0.1):
@@ -1046,12 +1087,12 @@ def glare_layout(width, height, levels):
 
 
 def _glare_film(film, film_kind, width, height):
-    """A film for a glare call as (width * height, 4) uint64 rows, and its PTSS_GLARE_FILM_* value. film_kind: "linear", "splat", a value,
+    """A whole film as (width * height, 4) uint64 rows, and its PTSS_FILM_* value. film_kind: "linear", "splat", a value,
     or None: what the film's dtype says (plain rows count as linear)."""
     if film_kind is None:
-        film_kind = GLARE_FILM_SPLAT if np.asarray(film).dtype == SPLAT_DTYPE else GLARE_FILM_LINEAR
-    kind = int(_GLARE_FILMS.get(film_kind, film_kind))
-    f = _rows(film, SPLAT_DTYPE if kind == GLARE_FILM_SPLAT else LINEAR_DTYPE, 4, np.uint64, "film")
+        film_kind = FILM_SPLAT if np.asarray(film).dtype == SPLAT_DTYPE else FILM_LINEAR
+    kind = _film_kind(film_kind)
+    f = _rows(film, SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE, 4, np.uint64, "film")
     if len(f) != int(width) * int(height):
         raise ValueError("film: width * height entries")
     return f, kind
@@ -1191,7 +1232,7 @@ def probe_resolve_toned(film, tone, table, first_pixel=0, count=None, params=Non
     for `tone`; state: a meter's state or None; glare: None or (width, height, a glare_params, the film's pyramid)."""
     if film_kind is None:
         film_kind = FILM_SPLAT if np.asarray(film).dtype == SPLAT_DTYPE else FILM_LINEAR
-    kind = int(_GLARE_FILMS.get(film_kind, film_kind))
+    kind = _film_kind(film_kind)
     f = _rows(film, SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE, 4, np.uint64, "film")
     P = len(f)
     first_pixel, count = _linear_range(P, first_pixel, count)
@@ -1265,7 +1306,7 @@ def probe_denoise_linear_finish(rgb, word3, film_kind="linear", params=None):
     the output row as four Python integers (r, g, b sums and samples | clamped << 32)."""
     params = params if params is not None else linear_params()
     c, out = (C.c_float * 3)(*[float(v) for v in rgb]), (C.c_ulonglong * 4)()
-    rc = host_lib().ptss_probe_denoise_linear_finish(c, int(word3), int(_GLARE_FILMS.get(film_kind, film_kind)), C.byref(params), out)
+    rc = host_lib().ptss_probe_denoise_linear_finish(c, int(word3), _film_kind(film_kind), C.byref(params), out)
     if rc != 0:
         raise PtssError(f"ptss_probe_denoise_linear_finish: {rc}")
     return tuple(int(v) for v in out)
@@ -1339,7 +1380,7 @@ def probe_reproject_linear_finish(h, w, s2=None, film_kind="linear", params=None
     reproject = reproject if reproject is not None else reproject_linear_params()
     c, f4, m4 = (C.c_float * 3)(*[float(v) for v in h]), (C.c_ulonglong * 4)(), (C.c_ulonglong * 4)()
     rc = host_lib().ptss_probe_reproject_linear_finish(c, float(w), 0 if s2 is None else 1, 0.0 if s2 is None else float(s2),
-                                                       int(_GLARE_FILMS.get(film_kind, film_kind)), C.byref(params), C.byref(reproject), f4, m4)
+                                                       _film_kind(film_kind), C.byref(params), C.byref(reproject), f4, m4)
     if rc != 0:
         raise PtssError(f"ptss_probe_reproject_linear_finish: {rc}")
     return tuple(int(v) for v in f4), tuple(int(v) for v in m4)
@@ -1860,13 +1901,11 @@ class Renderer:
         device tensor of n x 19 words in that layout, whose pointer is passed — asynchronous on `stream` (a raw stream handle;
         default: the tensor's current torch stream)."""
         L = device_lib()
-        if type(triangles).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            if triangles.dtype != torch.float32 or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() % 19:
+        if _is_torch(triangles):
+            if triangles.dtype != _torch().float32 or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() % 19:
                 raise ValueError("triangles: a contiguous float32 device tensor of n x 19 words")
             if stream is None:
-                stream = torch.cuda.current_stream(triangles.device).cuda_stream
+                stream = _stream_of(_torch(), triangles.device)
             _check(L.ptss_update_triangles(self._ctx, C.c_void_p(triangles.data_ptr()), first, triangles.numel() // 19, C.c_void_p(stream)))
         else:
             a = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
@@ -1889,9 +1928,7 @@ class Renderer:
 
     def resort_launches(self):
         """ptss_resort_launches: resort_triangles calls that launched, since the context was created."""
-        v = C.c_ulonglong()
-        _check(device_lib().ptss_resort_launches(self._ctx, C.byref(v)))
-        return v.value
+        return self._counters("ptss_resort_launches", 1)
 
     def strip_words(self):
         """ptss_read_strip_words: (words, enabled) — the uint64 strip words bounce 0 of the latest frame read (csrc/ptstrip.h), and whether it did."""
@@ -1907,9 +1944,7 @@ class Renderer:
 
     def update_rejected(self):
         """Records update_triangles has refused (a vertex not finite or beyond 2^40) since the context was created."""
-        v = C.c_ulonglong()
-        _check(device_lib().ptss_update_rejected(self._ctx, C.byref(v)))
-        return v.value
+        return self._counters("ptss_update_rejected", 1)
 
     def triangle_bounds(self):
         """ptss_read_triangle_bounds: (leaves + groups, 12) float32, the leaves' bounds first (mesh images only)."""
@@ -1924,6 +1959,12 @@ class Renderer:
         _check(device_lib().ptss_read_triangle_positions(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int)), out.size))
         return out
 
+    def _counters(self, name, k):
+        """The k 64-bit counters the library's `name` reads: one as an int, several as a tuple."""
+        out = (C.c_ulonglong * k)()
+        _check(getattr(device_lib(), name)(self._ctx, out))
+        return int(out[0]) if k == 1 else tuple(int(v) for v in out)
+
     # --- batched ray queries (ptss_intersect / ptss_occluded) ------------------------------------------
     def intersect(self, rays):
         """Closest hits. rays: (N, 8) float32 or an (N,) RAY_DTYPE array -> (N,) HIT_DTYPE array; or a contiguous (N, 8) float32
@@ -1937,42 +1978,15 @@ class Renderer:
     def _query(self, rays, any_hit):
         L = device_lib()
         fn = L.ptss_occluded if any_hit else L.ptss_intersect
-        if type(rays).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-                raise ValueError("rays: a contiguous (N, 8) float32 device tensor")
-            n = rays.shape[0]
-            out = (torch.empty(n, dtype=torch.int32, device=rays.device) if any_hit
-                   else torch.empty((n, 12), dtype=torch.float32, device=rays.device))
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(fn(self._ctx, C.c_void_p(rays.data_ptr()), C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
-            return out
-        a = np.asarray(rays)
-        if a.dtype == RAY_DTYPE:
-            a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != 8:
-            raise ValueError("rays: (N, 8) float32 or (N,) RAY_DTYPE")
-        n = a.shape[0]
-        out = np.empty(n, dtype=np.uint32) if any_hit else np.empty(n, dtype=HIT_DTYPE)
-        if n == 0:
-            return out
-        H = _hip_lib()
-        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
-        d_rays, d_out = C.c_void_p(), C.c_void_p()
-        _hip_check(H.hipMalloc(C.byref(d_rays), a.nbytes), "hipMalloc")
-        try:
-            _hip_check(H.hipMalloc(C.byref(d_out), out.nbytes), "hipMalloc")
-            _hip_check(H.hipMemcpy(d_rays, a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
-            _check(fn(self._ctx, d_rays, d_out, n, None))
-            self.synchronize()
-            _hip_check(H.hipMemcpy(out.ctypes.data, d_out, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
-        finally:
-            H.hipFree(d_rays)
-            if d_out:
-                H.hipFree(d_out)
-        return out
+
+        def arrays():
+            a = _query_rays(rays)
+            return [a, np.empty(len(a), dtype=np.uint32 if any_hit else HIT_DTYPE)]
+
+        # without rays the array path calls nothing: that is where `d` holds None
+        return self._device_call([("rays", rays, "float32", 8, None, None), ("out", None, *(("int32", 0) if any_hit else ("float32", 12)), "rays", "empty")],
+                                 lambda d, n, stream: fn(self._ctx, d[0], d[1], n["rays"], stream) if d[0] is not None else 0,
+                                 arrays, read=(1,), null=lambda n: n["rays"] == 0, result=lambda a: a[1], returns="out", texts=_QUERY_TEXTS)
 
     # --- batched path queries (ptss_seed_path_rng / ptss_trace_paths) ------------------------------------
     def seed_path_rng(self, n, seed, first_sequence=0, skip=0, device=None):
@@ -1981,30 +1995,20 @@ class Renderer:
         the current torch stream and left there for trace_paths."""
         L = device_lib()
         n = int(n)
-        if device is not None:
-            import sys
-            torch = sys.modules.get("torch")
+        seed_into = lambda d, stream: _check(L.ptss_seed_path_rng(self._ctx, d, n, seed, first_sequence, skip, stream))
+        if device is not None:   # no tensor comes in to take a device from: this path is the wrapper's own
+            torch = _torch()
             if torch is None:
                 raise ValueError("device=...: import torch first")
             dev = torch.device("cuda", self.cfg.device) if device is True else torch.device(device)
             out = torch.empty((n, 6), dtype=torch.int32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(L.ptss_seed_path_rng(self._ctx, C.c_void_p(out.data_ptr()) if n else None, n, seed, first_sequence, skip, C.c_void_p(stream)))
+            seed_into(C.c_void_p(out.data_ptr()) if n else None, C.c_void_p(_stream_of(torch, dev)))
             return out
         out = np.empty(n, dtype=PATH_RNG_DTYPE)
         if n == 0:
-            _check(L.ptss_seed_path_rng(self._ctx, None, 0, seed, first_sequence, skip, None))
-            return out
-        H = _hip_lib()
-        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
-        d = C.c_void_p()
-        _hip_check(H.hipMalloc(C.byref(d), out.nbytes), "hipMalloc")
-        try:
-            _check(L.ptss_seed_path_rng(self._ctx, d, n, seed, first_sequence, skip, None))
-            self.synchronize()
-            _hip_check(H.hipMemcpy(out.ctypes.data, d, out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
-        finally:
-            H.hipFree(d)
+            seed_into(None, None)
+        else:
+            self._round_trip([out], lambda d: seed_into(d[0], None), read=(0,))
         return out
 
     def trace_paths(self, rays, rng, max_iterations, schedule=None, max_workgroups=0):
@@ -2017,71 +2021,33 @@ class Renderer:
         `bounces`), on the current stream."""
         L = device_lib()
         if schedule is None:
-            trace = lambda a, b, c, count, stream: L.ptss_trace_paths(self._ctx, a, b, c, count, int(max_iterations), stream)
+            call = lambda d, n, stream: L.ptss_trace_paths(self._ctx, d[0], d[1], d[2], n["rays"], int(max_iterations), stream)
         else:
             options = path_options(schedule, max_workgroups)
-            trace = lambda a, b, c, count, stream: L.ptss_trace_paths_opt(self._ctx, a, b, c, count, int(max_iterations), C.byref(options), stream)
-        if type(rays).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-                raise ValueError("rays: a contiguous (N, 8) float32 device tensor")
-            n = rays.shape[0]
-            if (type(rng).__module__.split(".")[0] != "torch" or rng.dtype != torch.int32 or tuple(rng.shape) != (n, 6) or not rng.is_contiguous() or
-                    rng.device != rays.device):
-                raise ValueError("rng: a contiguous (N, 6) int32 tensor on the rays' device")
-            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(trace(C.c_void_p(rays.data_ptr()), C.c_void_p(rng.data_ptr()), C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
-            return out
-        a = np.asarray(rays)
-        if a.dtype == RAY_DTYPE:
-            a = np.ascontiguousarray(a).view(np.float32).reshape(-1, 8)
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.ndim != 2 or a.shape[1] != 8:
-            raise ValueError("rays: (N, 8) float32 or (N,) RAY_DTYPE")
-        n = a.shape[0]
-        s = np.asarray(rng)
-        if s.dtype == PATH_RNG_DTYPE:
-            s = np.ascontiguousarray(s).view(np.uint32).reshape(-1, 6)
-        s = np.ascontiguousarray(s, dtype=np.uint32)
-        if s.shape != (n, 6):
-            raise ValueError("rng: (N,) PATH_RNG_DTYPE or (N, 6) uint32, one state per ray")
-        out = np.empty(n, dtype=PATH_RESULT_DTYPE)
-        after = np.empty(n, dtype=PATH_RNG_DTYPE)
-        if n == 0:
-            _check(trace(None, None, None, 0, None))
-            return out, after
-        H = _hip_lib()
-        _hip_check(H.hipSetDevice(self.cfg.device), "hipSetDevice")
-        bufs = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
-        try:
-            for b, nbytes in zip(bufs, (a.nbytes, s.nbytes, out.nbytes)):
-                _hip_check(H.hipMalloc(C.byref(b), nbytes), "hipMalloc")
-            _hip_check(H.hipMemcpy(bufs[0], a.ctypes.data, a.nbytes, 1), "hipMemcpy")   # hipMemcpyHostToDevice
-            _hip_check(H.hipMemcpy(bufs[1], s.ctypes.data, s.nbytes, 1), "hipMemcpy")
-            _check(trace(bufs[0], bufs[1], bufs[2], n, None))
-            self.synchronize()
-            _hip_check(H.hipMemcpy(out.ctypes.data, bufs[2], out.nbytes, 2), "hipMemcpy")   # hipMemcpyDeviceToHost
-            _hip_check(H.hipMemcpy(after.ctypes.data, bufs[1], after.nbytes, 2), "hipMemcpy")
-        finally:
-            for b in bufs:
-                if b:
-                    H.hipFree(b)
-        return out, after
+            call = lambda d, n, stream: L.ptss_trace_paths_opt(self._ctx, d[0], d[1], d[2], n["rays"], int(max_iterations), C.byref(options), stream)
+
+        def arrays():
+            a = _query_rays(rays)
+            s = np.asarray(rng)
+            if s.dtype == PATH_RNG_DTYPE:
+                s = np.ascontiguousarray(s).view(np.uint32).reshape(-1, 6)
+            s = np.array(s, dtype=np.uint32, order="C")   # a copy: the streams afterwards are read back into it
+            if s.shape != (len(a), 6):
+                raise ValueError("rng: (N,) PATH_RNG_DTYPE or (N, 6) uint32, one state per ray")
+            return [a, s, np.empty(len(a), dtype=PATH_RESULT_DTYPE)]
+
+        return self._device_call([("rays", rays, "float32", 8, None, None), ("rng", rng, "int32", 6, "rays", None), ("out", None, "float32", 4, "rays", "empty")],
+                                 call, arrays, read=(1, 2), null=lambda n: n["rays"] == 0, result=lambda a: (a[2], _records(a[1], PATH_RNG_DTYPE)),
+                                 returns="out", texts=_QUERY_TEXTS)
 
     def path_launches(self):
         """ptss_path_launches: (ptss_trace_paths launches with the scene image read in place, with it staged in LDS)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_path_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_path_launches", 2)
 
     def path_refill_stats(self):
         """ptss_path_refill_stats: (refill launches with the scene image read in place, staged in LDS, wave iterations, lane iterations,
         dequeues) since the context was created; synchronises with the stream of the latest refill call."""
-        out = (C.c_ulonglong * 5)()
-        _check(device_lib().ptss_path_refill_stats(self._ctx, out))
-        return tuple(int(v) for v in out)
+        return self._counters("ptss_path_refill_stats", 5)
 
     # --- the film of a path query (ptss_generate_rays / ptss_accumulate_paths / ptss_ray_features) ------------------
     def _round_trip(self, arrays, call, read):
@@ -2105,14 +2071,54 @@ class Renderer:
                 if b:
                     H.hipFree(b)
 
-    @staticmethod
-    def _torch_ptr(t, what, dtype, columns, device=None, n=None):
-        """The device pointer of torch tensor `t`, checked: contiguous, on `device`, dtype `dtype` (a name), shape (n, columns)."""
-        if (type(t).__module__.split(".")[0] != "torch" or str(t.dtype) != "torch." + dtype or not t.is_contiguous() or not t.is_cuda or
-                (device is not None and t.device != device) or t.dim() != (2 if columns else 1) or (columns and t.shape[1] != columns) or
-                (n is not None and t.shape[0] != n)):
-            raise ValueError(f"{what}: a contiguous {dtype} device tensor of shape ({'N' if n is None else n}{', %d' % columns if columns else ''})")
-        return C.c_void_p(t.data_ptr())
+    def _device_call(self, bufs, call, arrays, read=(), null=None, result=None, primary=0, returns=None, tensors=None, texts=None):
+        """One library call over buffers that come as device tensors or as arrays: both paths of a wrapper.
+        bufs: a row (name, value, torch dtype name, columns (0: one-dimensional), rows, absent) per buffer argument, in the order in which
+        they are checked. rows: the row count expected: a number, the name of an earlier buffer (as many as it has), a function of the
+        counts so far, or None (any). absent: what a value of None is: None (refused like any other wrong value), "null" (a NULL pointer),
+        "empty" / "zeros" (a new tensor). call(d, n, stream) -> the library's status: d the device pointers in bufs' order, n each buffer's
+        row count by name.
+        Tensors, where the value of bufs[primary] is one (`tensors`: a verdict of the wrapper's instead): every tensor is held against its
+        row (ValueError: texts[name] where given) and the primary's device, the call goes to that device's current stream and is not
+        waited for -> the tensor of the buffer named `returns`, or None.
+        Arrays otherwise: arrays() -> the buffers in bufs' order as the helpers above normalise them (None: NULL); _round_trip uploads
+        them, calls on the context's stream, waits and downloads those at `read` — or, where null(n) finds a call of size zero, the library
+        is called with NULL for every buffer — -> result(the arrays)."""
+        head = bufs[primary][1]
+        if _is_torch(head) if tensors is None else tensors:
+            torch, dev = sys.modules["torch"], getattr(head, "device", None)
+            Tensor, on_gpu = torch.Tensor, getattr(head, "is_cuda", False)   # a tensor on the primary's device is on a GPU if the primary is
+            d, n, kept = [], {}, None   # (the pointers go as plain integers: the library's argument types convert them)
+            for what, t, dtype, columns, rows, absent in bufs:
+                if t is None and absent == "null":
+                    d.append(None)
+                    continue
+                if type(rows) is str:
+                    rows = n[rows]
+                elif rows is not None and type(rows) is not int:
+                    rows = rows(n)
+                if t is None and absent is not None:
+                    t = getattr(torch, absent)((rows, columns) if columns else (rows,), dtype=getattr(torch, dtype), device=dev)
+                    shape = t.shape
+                else:
+                    shape = t.shape if isinstance(t, Tensor) else None
+                    if (shape is None or t.dtype is not getattr(torch, dtype) or not t.is_contiguous() or not on_gpu or t.device != dev or
+                            len(shape) != (2 if columns else 1) or (columns and shape[1] != columns) or (rows is not None and shape[0] != rows)):
+                        raise ValueError(texts[what] if texts else f"{what}: a contiguous {dtype} device tensor of shape "
+                                         f"({'N' if rows is None else rows}{', %d' % columns if columns else ''})")
+                if what == returns:
+                    kept = t
+                n[what] = shape[0]
+                d.append(t.data_ptr())
+            _check(call(d, n, _stream_of(torch, dev)))
+            return kept
+        a = arrays()
+        n = {row[0]: len(x) if x is not None else 0 for row, x in zip(bufs, a)}
+        if null is not None and null(n):
+            _check(call([None] * len(a), n, None))
+        else:
+            self._round_trip(a, lambda d: _check(call(d, n, None)), read)
+        return result(a)
 
     def generate_rays(self, film, rng, first_pixel=0, index=None, rays=None, positions=None):
         """ptss_generate_rays: the eye rays of film pixels index[i] (first_pixel + i without an index) from streams rng[i].
@@ -2123,73 +2129,57 @@ class Renderer:
         int32 device tensor, UPDATED IN PLACE, index an (N,) int32 tensor or None, rays an (N, 8) float32 tensor to write (a new one
         otherwise) -> rays, on the current stream."""
         L = device_lib()
-        if type(rng).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n = rng.shape[0]
-            d_rng = self._torch_ptr(rng, "rng", "int32", 6)
-            if rays is None:
-                rays = torch.zeros((n, 8), dtype=torch.float32, device=rng.device)
-            d_rays = self._torch_ptr(rays, "rays", "float32", 8, rng.device, n)
-            d_idx = self._torch_ptr(index, "index", "int32", 0, rng.device, n) if index is not None else None
-            stream = torch.cuda.current_stream(rng.device).cuda_stream
-            if positions is not None:
-                d_pos = self._torch_ptr(positions, "positions", "float32", 2, rng.device, n)
-                _check(L.ptss_generate_rays_positions(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, d_pos, C.c_void_p(stream)))
-            else:
-                _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d_idx, n, d_rng, d_rays, C.c_void_p(stream)))
-            return rays
-        s = _rng_words(rng)
-        n = len(s)
-        idx = _film_index(index, n)
-        out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
-        if len(out) != n:
-            raise ValueError("rays: one row per stream")
-        if positions is not None:
-            pos = np.zeros((n, 2), dtype=np.float32)
-            self._round_trip([idx, s, out, pos], lambda d: _check(L.ptss_generate_rays_positions(self._ctx, C.byref(film), int(first_pixel), d[0], n,
-                                                                                                   d[1], d[2], d[3], None)), read=(1, 2, 3))
-            return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1), pos.view(POSITION_DTYPE).reshape(-1)
-        if n == 0:
-            _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), None, 0, None, None, None))
-        else:
-            self._round_trip([idx, s, out], lambda d: _check(L.ptss_generate_rays(self._ctx, C.byref(film), int(first_pixel), d[0], n, d[1], d[2], None)),
-                             read=(1, 2))
-        return out.view(RAY_DTYPE).reshape(-1), s.view(PATH_RNG_DTYPE).reshape(-1)
+        first_pixel, placed = int(first_pixel), positions is not None
+        bufs = [("rng", rng, "int32", 6, None, None), ("rays", rays, "float32", 8, "rng", "zeros"), ("index", index, "int32", 0, "rng", "null")]
+        if placed:
+            bufs.append(("positions", positions, "float32", 2, "rng", None))
+
+        def arrays():
+            s = _rng_words(rng)
+            n = len(s)
+            idx = _film_index(index, n)
+            out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
+            if len(out) != n:
+                raise ValueError("rays: one row per stream")
+            return [s, out, idx] + ([np.zeros((n, 2), dtype=np.float32)] if placed else [])
+
+        def call(d, n, stream):
+            if placed:
+                return L.ptss_generate_rays_positions(self._ctx, C.byref(film), first_pixel, d[2], n["rng"], d[0], d[1], d[3], stream)
+            return L.ptss_generate_rays(self._ctx, C.byref(film), first_pixel, d[2], n["rng"], d[0], d[1], stream)
+
+        def result(a):
+            out = (_records(a[1], RAY_DTYPE), _records(a[0], PATH_RNG_DTYPE))
+            return out + (_records(a[3], POSITION_DTYPE),) if placed else out
+
+        # without streams ptss_generate_rays is called with NULL; ptss_generate_rays_positions always with buffers
+        return self._device_call(bufs, call, arrays, read=(0, 1, 3) if placed else (0, 1), null=None if placed else lambda n: n["rng"] == 0,
+                                 result=result, returns="rays")
 
     _NO_MOMENTS = object()   # _accumulate's `moments` for a film that keeps none
 
-    def _accumulate(self, call, film_dtype, word, results, film, first_pixel, index, moments=_NO_MOMENTS, pixels=None, history=None):
+    def _accumulate(self, call, film_dtype, word, results, film, index, moments=_NO_MOMENTS, pixels=None, history=None):
         """The body of accumulate_paths, accumulate_paths_stats and accumulate_paths_linear (accumulate_paths_linear_stats, whose film may
         be None and whose moments are records, has its own). film_dtype, word: the film's record and the type of its four words (a torch
-        film holds them signed); call(results, index, first_pixel, n, film, P, moments, pixels, history, stream): the C call, over device
-        pointers or None. torch -> None; numpy -> (film, moments or None, pixels, history) afterwards."""
+        film holds them signed); call(d, n, stream): the C call as _device_call makes it, d the pointers of (results, film, moments, index,
+        pixels, history). torch -> None; numpy -> (film, moments or None, pixels, history) afterwards."""
         keeps_moments = moments is not self._NO_MOMENTS
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_film = self._torch_ptr(film, "film", "int%d" % (8 * np.dtype(word).itemsize), 4, dev)
-            P = film.shape[0]
-            d_mom = self._torch_ptr(moments, "moments", "int64", 0, dev, P) if keeps_moments else None
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
-            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
-            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
-            call(d_res, d_idx, int(first_pixel), n, d_film, P, d_mom, d_px, d_hs, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        idx = _film_index(index, n)
-        f = _rows(film, film_dtype, 4, word, "film", copy=True)
-        P = len(f)
-        m = _moments(moments, P) if keeps_moments else None
-        px, hs = _film_outputs(P, pixels=pixels, history=history)
-        if n == 0:
-            call(None, None, int(first_pixel), 0, None, P, None, None, None, None)
-        else:
-            self._round_trip([r, idx, f, m, px, hs], lambda d: call(d[0], d[1], int(first_pixel), n, d[2], P, d[3], d[4], d[5], None), read=(2, 3, 4, 5))
-        return f.view(film_dtype).reshape(-1), m, px, (hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+
+        def arrays():
+            r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+            idx = _film_index(index, len(r))
+            f = _rows(film, film_dtype, 4, word, "film", copy=True)
+            m = _moments(moments, len(f)) if keeps_moments else None
+            px, hs = _film_outputs(len(f), pixels=pixels, history=history)
+            return [r, f, m, idx, px, hs]
+
+        return self._device_call(
+            [("results", results, "float32", 4, None, None), ("film", film, "int32" if word is np.uint32 else "int64", 4, None, None),
+             ("moments", moments, "int64", 0, "film", None) if keeps_moments else ("moments", None, "int64", 0, "film", "null"),
+             ("index", index, "int32", 0, "results", "null"), ("pixels", pixels, "uint8", 4, "film", "null"),
+             ("history", history, "float32", 4, "film", "null")],
+            call, arrays, read=(1, 2, 4, 5), null=lambda n: n["results"] == 0,
+            result=lambda a: (_records(a[1], film_dtype), a[2], a[4], _records(a[5], HISTORY_DTYPE)))
 
     def accumulate_paths(self, results, film, first_pixel=0, index=None, pixels=None, history=None):
         """ptss_accumulate_paths: the samples of `results` added to the film, the touched pixels resolved.
@@ -2198,8 +2188,8 @@ class Renderer:
         or None, history (P,) HISTORY_DTYPE or None). torch: results (N, 4) float32, film (P, 4) int32 UPDATED IN PLACE, index (N,) int32
         or None, pixels (P, 4) uint8 or None, history (P, 4) float32 or None, all on one device -> None, on the current stream."""
         L = device_lib()
-        out = self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths(self._ctx, res, idx, first, n, f, P, px, hs, st)),
-                               FILM_DTYPE, np.uint32, results, film, first_pixel, index, pixels=pixels, history=history)
+        out = self._accumulate(lambda d, n, st: L.ptss_accumulate_paths(self._ctx, d[0], d[3], int(first_pixel), n["results"], d[1], n["film"], d[4], d[5], st),
+                               FILM_DTYPE, np.uint32, results, film, index, pixels=pixels, history=history)
         return None if out is None else (out[0], out[2], out[3])
 
     def ray_features(self, rays):
@@ -2207,31 +2197,23 @@ class Renderer:
         a contiguous (N, 8) float32 device tensor -> an (N, 8) float32 tensor (word 7 holds the bits of materialIdx), on the current
         stream."""
         L = device_lib()
-        if type(rays).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            d_rays = self._torch_ptr(rays, "rays", "float32", 8)
-            n = rays.shape[0]
-            out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
-            stream = torch.cuda.current_stream(rays.device).cuda_stream
-            _check(L.ptss_ray_features(self._ctx, d_rays, C.c_void_p(out.data_ptr()), n, C.c_void_p(stream)))
-            return out
-        a = _rows(rays, RAY_DTYPE, 8, np.float32, "rays")
-        n = len(a)
-        out = np.zeros(n, dtype=FEATURE_DTYPE)
-        if n == 0:
-            _check(L.ptss_ray_features(self._ctx, None, None, 0, None))
-        else:
-            self._round_trip([a, out], lambda d: _check(L.ptss_ray_features(self._ctx, d[0], d[1], n, None)), read=(1,))
-        return out
+
+        def arrays():
+            a = _rows(rays, RAY_DTYPE, 8, np.float32, "rays")
+            return [a, np.zeros(len(a), dtype=FEATURE_DTYPE)]
+
+        return self._device_call([("rays", rays, "float32", 8, None, None), ("out", None, "float32", 8, "rays", "empty")],
+                                 lambda d, n, stream: L.ptss_ray_features(self._ctx, d[0], d[1], n["rays"], stream),
+                                 arrays, read=(1,), null=lambda n: n["rays"] == 0, result=lambda a: a[1], returns="out")
 
     def accumulate_paths_stats(self, results, film, moments, first_pixel=0, index=None, pixels=None, history=None):
         """ptss_accumulate_paths_stats: accumulate_paths, with the second moments kept as well.
         numpy: accumulate_paths' arguments and moments (P,) uint64 (not modified) -> (film, moments afterwards, pixels, history).
         torch: moments a contiguous (P,) int64 device tensor UPDATED IN PLACE like the film -> None, on the current stream."""
         L = device_lib()
-        return self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths_stats(self._ctx, res, idx, first, n, f, m, P, px, hs, st)),
-                                FILM_DTYPE, np.uint32, results, film, first_pixel, index, moments, pixels, history)
+        return self._accumulate(lambda d, n, st: L.ptss_accumulate_paths_stats(self._ctx, d[0], d[3], int(first_pixel), n["results"], d[1], d[2], n["film"],
+                                                                                d[4], d[5], st),
+                                FILM_DTYPE, np.uint32, results, film, index, moments, pixels, history)
 
     def plan_samples(self, film, moments, n, params=None, cdf=None, index=None, info=None):
         """ptss_plan_samples: the next round's index from film and moments.
@@ -2240,42 +2222,32 @@ class Renderer:
         (4,) int64 tensor or None, all contiguous on one device, WRITTEN IN PLACE -> None, on the current stream."""
         L = device_lib()
         params = params if params is not None else plan_params()
-        return self._plan(lambda d, P, n, cdf, idx, inf, st: _check(L.ptss_plan_samples(self._ctx, d[0], d[1], P, C.byref(params), n, cdf, idx, inf, st)),
+        return self._plan(lambda d, rows, st: L.ptss_plan_samples(self._ctx, d[0], d[1], rows["film"], C.byref(params), int(n), d[2], d[3], d[4], st),
                           [(film, "film", FILM_DTYPE, np.uint32), (moments, "moments", None, np.uint64)], n, cdf, index, info)
 
     def _plan(self, call, inputs, n, cdf, index, info):
         """The body of plan_samples and plan_samples_linear. inputs: what the plan reads, a row (value, name, record dtype, type of its
-        words) per array: P records of four words, or P plain words where the record is None; the first has records. call(the inputs'
-        pointers, P, n, cdf, index, info, stream): the C call, over device pointers or None. torch -> None; numpy -> (cdf, index, info)."""
-        n, head = int(n), inputs[0][0]
-        if type(head).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, P = head.device, head.shape[0]
-            d_in = [self._torch_ptr(value, what, "int%d" % (8 * np.dtype(word).itemsize), 4 if record is not None else 0, *((dev, P) if k else ()))
-                    for k, (value, what, record, word) in enumerate(inputs)]
-            d_cdf = self._torch_ptr(cdf, "cdf", "int64", 0, dev, plan_cdf_entries(P))
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n)
-            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
-            call(d_in, P, n, d_cdf, d_idx, d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            return None
-        rows = []
-        for value, what, record, word in inputs:
-            rows.append(_rows(value, record, 4, word, what) if record is not None else _moments(value, len(rows[0])))
-        P, k = len(rows[0]), len(rows)
-        work = np.zeros(plan_cdf_entries(P), dtype=np.uint64)
-        out, found = np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)
-        if n == 0:
-            call([None] * k, P, 0, None, None, None, None)
-        else:
-            self._round_trip(rows + [work, out, found], lambda d: call(d[:k], P, n, d[k], d[k + 1], d[k + 2], None), read=(k, k + 1, k + 2))
-        return work[:P], out, plan_info_dict(found)
+        words) per array: P records of four words, or P plain words where the record is None; the first has records. call(d, rows,
+        stream): the C call as _device_call makes it, d the pointers of (the inputs, cdf, index, info). torch -> None; numpy -> (cdf, index,
+        info)."""
+        n, k, first = int(n), len(inputs), inputs[0][1]
+        bufs = [(what, value, "int32" if word is np.uint32 else "int64", 4 if record is not None else 0, first if j else None, None)
+                for j, (value, what, record, word) in enumerate(inputs)]
+        bufs += [("cdf", cdf, "int64", 0, lambda rows: plan_cdf_entries(rows[first]), None), ("index", index, "int32", 0, n, None),
+                 ("info", info, "int64", 0, 4, "null")]
+
+        def arrays():
+            rows = []
+            for value, what, record, word in inputs:
+                rows.append(_rows(value, record, 4, word, what) if record is not None else _moments(value, len(rows[0])))
+            return rows + [np.zeros(plan_cdf_entries(len(rows[0])), dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(4, dtype=np.uint64)]
+
+        return self._device_call(bufs, call, arrays, read=(k, k + 1, k + 2), null=lambda rows: n == 0,
+                                 result=lambda a: (a[k][:len(a[0])], a[k + 1], plan_info_dict(a[k + 2])))
 
     def adaptive_launches(self):
         """ptss_adaptive_launches: (accumulate_paths_stats, plan_samples calls that launched since the context was created)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_adaptive_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_adaptive_launches", 2)
 
     # --- the linear film (ptss_accumulate_paths_linear / ptss_resolve_linear) ------------------
     def accumulate_paths_linear(self, results, film, first_pixel=0, index=None, params=None):
@@ -2285,8 +2257,9 @@ class Renderer:
         on one device -> None, on the current stream."""
         L = device_lib()
         params = params if params is not None else linear_params()
-        out = self._accumulate(lambda res, idx, first, n, f, P, m, px, hs, st: _check(L.ptss_accumulate_paths_linear(self._ctx, res, idx, first, n, f, P, C.byref(params), st)),
-                               LINEAR_DTYPE, np.uint64, results, film, first_pixel, index)
+        out = self._accumulate(lambda d, n, st: L.ptss_accumulate_paths_linear(self._ctx, d[0], d[3], int(first_pixel), n["results"], d[1], n["film"],
+                                                                               C.byref(params), st),
+                               LINEAR_DTYPE, np.uint64, results, film, index)
         return None if out is None else out[0]
 
     # --- adaptive sampling on the linear film (ptss_accumulate_paths_linear_stats / ptss_plan_samples_linear) ------------------
@@ -2298,33 +2271,22 @@ class Renderer:
         all on one device -> None, on the current stream."""
         L = device_lib()
         params = params if params is not None else linear_params()
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_mom = self._torch_ptr(moments, "moments", "int64", 4, dev)
-            P = moments.shape[0]
-            d_film = self._torch_ptr(film, "film", "int64", 4, dev, P) if film is not None else None
-            d_idx = self._torch_ptr(index, "index", "int32", 0, dev, n) if index is not None else None
-            _check(L.ptss_accumulate_paths_linear_stats(self._ctx, d_res, d_idx, int(first_pixel), n, d_film, d_mom, P, C.byref(params),
-                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        idx = _film_index(index, n)
-        m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments", copy=True)
-        P = len(m)
-        f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True) if film is not None else None
-        if f is not None and len(f) != P:
-            raise ValueError("moments: one row per film pixel")
-        if n == 0:
-            _check(L.ptss_accumulate_paths_linear_stats(self._ctx, None, None, int(first_pixel), 0, None, None, P, C.byref(params), None))
-        else:
-            self._round_trip([r, idx, f, m],
-                             lambda d: _check(L.ptss_accumulate_paths_linear_stats(self._ctx, d[0], d[1], int(first_pixel), n, d[2], d[3], P,
-                                                                                   C.byref(params), None)), read=(2, 3))
-        return (f.view(LINEAR_DTYPE).reshape(-1) if f is not None else None), m.view(MOMENT_DTYPE).reshape(-1)
+
+        def arrays():
+            r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+            idx = _film_index(index, len(r))
+            m = _rows(moments, MOMENT_DTYPE, 4, np.uint64, "moments", copy=True)
+            f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film", copy=True) if film is not None else None
+            if f is not None and len(f) != len(m):
+                raise ValueError("moments: one row per film pixel")
+            return [r, m, f, idx]
+
+        return self._device_call(
+            [("results", results, "float32", 4, None, None), ("moments", moments, "int64", 4, None, None), ("film", film, "int64", 4, "moments", "null"),
+             ("index", index, "int32", 0, "results", "null")],
+            lambda d, n, stream: L.ptss_accumulate_paths_linear_stats(self._ctx, d[0], d[3], int(first_pixel), n["results"], d[2], d[1], n["moments"],
+                                                                      C.byref(params), stream),
+            arrays, read=(1, 2), null=lambda n: n["results"] == 0, result=lambda a: (_records(a[2], LINEAR_DTYPE), _records(a[1], MOMENT_DTYPE)))
 
     def plan_samples_linear(self, moments, n, params=None, plan=None, cdf=None, index=None, info=None):
         """ptss_plan_samples_linear: the next round's index from a linear film's moments.
@@ -2334,15 +2296,14 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         plan = plan if plan is not None else linear_plan_params()
-        return self._plan(lambda d, P, n, cdf, idx, inf, st: _check(L.ptss_plan_samples_linear(self._ctx, d[0], P, C.byref(params), C.byref(plan), n, cdf, idx, inf, st)),
+        return self._plan(lambda d, rows, st: L.ptss_plan_samples_linear(self._ctx, d[0], rows["moments"], C.byref(params), C.byref(plan), int(n), d[1],
+                                                                         d[2], d[3], st),
                           [(moments, "moments", MOMENT_DTYPE, np.uint64)], n, cdf, index, info)
 
     def linear_stats_launches(self):
         """ptss_linear_stats_launches: (accumulate_paths_linear_stats, plan_samples_linear calls that launched since the context was
         created)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_linear_stats_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_linear_stats_launches", 2)
 
     def resolve_linear(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None, tone=None):
         """ptss_resolve_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film resolved.
@@ -2364,64 +2325,47 @@ class Renderer:
                  tone=None, film_kind=FILM_LINEAR):
         """The body of resolve_linear and resolve_splat over a film of 32-byte entries: `plain`, `with_state` where `metered` is a state,
         `with_glare` where `glare` is (width, height, glare_params, pyramid), or ptss_resolve_toned where `tone` is (tone_params, table)."""
+        L = device_lib()
         params = params if params is not None else linear_params()
-        d_pyr = pyr = d_table = table = None
-        if glare is not None:
-            g_width, g_height, g_params, g_pyramid = glare
-            g_entries = glare_layout(g_width, g_height, g_params.levels)[1]
-        if tone is not None:
-            t_params, t_table = tone
-            toned = device_lib().ptss_resolve_toned
-            call = lambda ctx, f, first, n, par, ln, px, hs, st: toned(
-                ctx, f, int(film_kind), first, n, par, C.byref(t_params), d_table, d_state, int(g_width) if glare is not None else 0,
-                int(g_height) if glare is not None else 0, C.byref(g_params) if glare is not None else None, d_pyr, ln, px, hs, st)
-        elif glare is not None:
-            call = lambda ctx, f, first, n, par, ln, px, hs, st: with_glare(ctx, f, first, n, par, int(g_width), int(g_height), C.byref(g_params),
-                                                                           d_pyr, d_state, ln, px, hs, st)
-        elif metered is None:
-            call = plain
-        else:
-            call = lambda ctx, f, first, n, par, ln, px, hs, st: with_state(ctx, f, first, n, par, d_state, ln, px, hs, st)
-        if type(film).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, P = film.device, film.shape[0]
-            first_pixel, count = _linear_range(P, first_pixel, count)
-            d_film = self._torch_ptr(film, "film", "int64", 4)
-            d_state = self._torch_ptr(metered, "metered", "int64", 0, dev, 6) if metered is not None else None
-            if glare is not None:
-                if P != int(g_width) * int(g_height):
-                    raise ValueError("film: width * height entries")
-                d_pyr = self._torch_ptr(g_pyramid, "pyramid", "int64", 4, dev, g_entries)
-            if tone is not None:
-                d_table = self._torch_ptr(t_table, "table", "float32", 0, dev, tone_table_floats(t_params.bits))
-            d_ln = self._torch_ptr(linear, "linear", "float32", 4, dev, P) if linear is not None else None
-            d_px = self._torch_ptr(pixels, "pixels", "uint8", 4, dev, P) if pixels is not None else None
-            d_hs = self._torch_ptr(history, "history", "float32", 4, dev, P) if history is not None else None
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(call(self._ctx, d_film, first_pixel, count, C.byref(params), d_ln, d_px, d_hs, C.c_void_p(stream)))
-            return None
-        f = _rows(film, film_dtype, 4, np.uint64, "film")
-        P = len(f)
-        first_pixel, count = _linear_range(P, first_pixel, count)
-        ln, px, hs = _film_outputs(P, linear=linear, pixels=pixels, history=history)
-        state = _meter_state(metered) if metered is not None else None
-        d_state = None
-        if glare is not None:
-            if P != int(g_width) * int(g_height):
+        g_width, g_height, g_params, g_pyramid = glare if glare is not None else (0, 0, None, None)
+        g_width, g_height, g_entries = int(g_width), int(g_height), glare_layout(g_width, g_height, g_params.levels)[1] if glare is not None else None
+        t_params, t_table = tone if tone is not None else (None, None)
+
+        span = lambda n: _linear_range(n["film"], first_pixel, count)
+
+        def entries(n):   # of the pyramid, which is looked at once the film is seen to be the glare's
+            if n["film"] != g_width * g_height:
                 raise ValueError("film: width * height entries")
-            pyr = _glare_pyramid(g_pyramid, g_entries)
-        if tone is not None:
-            table = _tone_table(t_table, t_params.bits)
-        if count == 0:
-            _check(call(self._ctx, None, first_pixel, 0, C.byref(params), None, None, None, None))
-        else:
-            def run(d):
-                nonlocal d_state, d_pyr, d_table
-                d_state, d_pyr, d_table = d[4], d[5], d[6]
-                _check(call(self._ctx, d[0], first_pixel, count, C.byref(params), d[1], d[2], d[3], None))
-            self._round_trip([f, ln, px, hs, state, pyr, table], run, read=(1, 2, 3))
-        return (ln.view(HISTORY_DTYPE).reshape(-1) if ln is not None else None, px, hs.view(HISTORY_DTYPE).reshape(-1) if hs is not None else None)
+            return g_entries
+
+        def call(d, n, stream):
+            first, many = span(n)
+            f, state, pyr, table, *out = d
+            if tone is not None:
+                return L.ptss_resolve_toned(self._ctx, f, int(film_kind), first, many, C.byref(params), C.byref(t_params), table, state, g_width,
+                                            g_height, C.byref(g_params) if glare is not None else None, pyr, *out, stream)
+            if glare is not None:
+                return with_glare(self._ctx, f, first, many, C.byref(params), g_width, g_height, C.byref(g_params), pyr, state, *out, stream)
+            if metered is not None:
+                return with_state(self._ctx, f, first, many, C.byref(params), state, *out, stream)
+            return plain(self._ctx, f, first, many, C.byref(params), *out, stream)
+
+        def arrays():
+            f = _rows(film, film_dtype, 4, np.uint64, "film")
+            span({"film": len(f)})
+            ln, px, hs = _film_outputs(len(f), linear=linear, pixels=pixels, history=history)
+            state = _meter_state(metered) if metered is not None else None
+            pyr = _glare_pyramid(g_pyramid, entries({"film": len(f)})) if glare is not None else None
+            return [f, state, pyr, _tone_table(t_table, t_params.bits) if tone is not None else None, ln, px, hs]
+
+        return self._device_call(
+            [("film", film, "int64", 4, None, None), ("metered", metered, "int64", 0, 6, "null"),
+             ("pyramid", g_pyramid, "int64", 4, entries if glare is not None else None, None if glare is not None else "null"),
+             ("table", t_table, "float32", 0, tone_table_floats(t_params.bits) if tone is not None else None, None if tone is not None else "null"),
+             ("linear", linear, "float32", 4, "film", "null"), ("pixels", pixels, "uint8", 4, "film", "null"),
+             ("history", history, "float32", 4, "film", "null")],
+            call, arrays, read=(4, 5, 6), null=lambda n: span(n)[1] == 0,
+            result=lambda a: (_records(a[4], HISTORY_DTYPE), a[5], _records(a[6], HISTORY_DTYPE)))
 
     # --- the filtered linear film (ptss_splat_paths / ptss_splat_paths_homed / ptss_resolve_splat) ------------------
     def splat_paths(self, results, positions, film, width, height, filter=None, params=None, homed_first_pixel=None):
@@ -2435,32 +2379,23 @@ class Renderer:
         params = params if params is not None else linear_params()
         width, height = int(width), int(height)
 
-        def call(res, pos, n, f, st):
+        def call(d, n, stream):
             if homed_first_pixel is None:
-                _check(L.ptss_splat_paths(self._ctx, res, pos, n, f, width, height, C.byref(filter), C.byref(params), st))
-            else:
-                _check(L.ptss_splat_paths_homed(self._ctx, res, pos, int(homed_first_pixel), n, f, width, height, C.byref(filter), C.byref(params), st))
+                return L.ptss_splat_paths(self._ctx, d[0], d[1], n["results"], d[2], width, height, C.byref(filter), C.byref(params), stream)
+            return L.ptss_splat_paths_homed(self._ctx, d[0], d[1], int(homed_first_pixel), n["results"], d[2], width, height, C.byref(filter),
+                                            C.byref(params), stream)
 
-        if type(results).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            n, dev = results.shape[0], results.device
-            d_res = self._torch_ptr(results, "results", "float32", 4)
-            d_pos = self._torch_ptr(positions, "positions", "float32", 2, dev, n)
-            d_film = self._torch_ptr(film, "film", "int64", 4, dev, width * height)
-            call(d_res, d_pos, n, d_film, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            return None
-        r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
-        n = len(r)
-        pos = _positions(positions, n)
-        f = _rows(film, SPLAT_DTYPE, 4, np.uint64, "film", copy=True)
-        if len(f) != width * height:
-            raise ValueError("film: width * height entries")
-        if n == 0:
-            call(None, None, 0, None, None)
-        else:
-            self._round_trip([r, pos, f], lambda d: call(d[0], d[1], n, d[2], None), read=(2,))
-        return f.view(SPLAT_DTYPE).reshape(-1)
+        def arrays():
+            r = _rows(results, PATH_RESULT_DTYPE, 4, np.float32, "results")
+            pos = _positions(positions, len(r))
+            f = _rows(film, SPLAT_DTYPE, 4, np.uint64, "film", copy=True)
+            if len(f) != width * height:
+                raise ValueError("film: width * height entries")
+            return [r, pos, f]
+
+        return self._device_call([("results", results, "float32", 4, None, None), ("positions", positions, "float32", 2, "results", None),
+                                  ("film", film, "int64", 4, width * height, None)],
+                                 call, arrays, read=(2,), null=lambda n: n["results"] == 0, result=lambda a: _records(a[2], SPLAT_DTYPE))
 
     def resolve_splat(self, film, first_pixel=0, count=None, params=None, linear=True, pixels=True, history=True, metered=None, glare=None, tone=None):
         """ptss_resolve_splat: resolve_linear's arguments and results over a filtered film, (P,) SPLAT_DTYPE (torch: (P, 4) int64); the
@@ -2477,23 +2412,20 @@ class Renderer:
         WRITTEN IN PLACE -> None, on the current stream (tone_table_sorted reads its flag)."""
         L = device_lib()
         tone = tone if tone is not None else tone_params()
-        if table is not None:
-            import sys
-            torch = sys.modules["torch"]
-            d_table = self._torch_ptr(table, "table", "float32", 0, None, tone_table_floats(tone.bits) if tone.bits in (8, 10) else None)
-            _check(L.ptss_tone_build(self._ctx, C.byref(tone), d_table, C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)))
-            return None
-        out = np.zeros(tone_table_floats(tone.bits) if tone.bits in (8, 10) else 4, dtype=np.float32)
-        self._round_trip([out], lambda d: _check(L.ptss_tone_build(self._ctx, C.byref(tone), d[0], None)), read=(0,))
-        if not tone_table_sorted(out):
-            raise PtssError("ptss_tone_build: the thresholds are not in order")
-        return out
+        floats = tone_table_floats(tone.bits) if tone.bits in (8, 10) else None   # other bits are the library's to refuse
+
+        def result(a):
+            if not tone_table_sorted(a[0]):
+                raise PtssError("ptss_tone_build: the thresholds are not in order")
+            return a[0]
+
+        return self._device_call([("table", table, "float32", 0, floats, None)],
+                                 lambda d, n, stream: L.ptss_tone_build(self._ctx, C.byref(tone), d[0], stream),
+                                 lambda: [np.zeros(floats or 4, dtype=np.float32)], read=(0,), result=result, tensors=table is not None)
 
     def tone_launches(self):
         """ptss_tone_launches: (tone_build calls, toned resolves that launched since the context was created)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_tone_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_tone_launches", 2)
 
     def debug_tone_form(self, form):
         """ptss_debug_tone_form: 0 the shipped lookup, 1 the table staged in LDS, 2 the guess settled against global memory."""
@@ -2508,29 +2440,22 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         glare = glare if glare is not None else glare_params()
-        width, height = int(width), int(height)
-        if type(film).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev = film.device
-            kind = int(_GLARE_FILMS.get(film_kind, GLARE_FILM_LINEAR if film_kind is None else film_kind))
-            d_film = self._torch_ptr(film, "film", "int64", 4, None, width * height)
-            d_pyr = self._torch_ptr(pyramid, "pyramid", "int64", 4, dev, glare_layout(width, height, glare.levels)[1])
-            _check(L.ptss_glare_build(self._ctx, d_film, kind, width, height, C.byref(params), C.byref(glare), d_pyr,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        f, kind = _glare_film(film, film_kind, width, height)
-        out = np.zeros((glare_layout(width, height, glare.levels)[1], 4), dtype=np.uint64)
-        self._round_trip([f, out], lambda d: _check(L.ptss_glare_build(self._ctx, d[0], kind, width, height, C.byref(params), C.byref(glare), d[1], None)),
-                         read=(1,))
-        return out.view(GLARE_DTYPE).reshape(-1)
+        width, height, kind = int(width), int(height), _film_kind(film_kind, FILM_LINEAR)
+        entries = lambda n=None: glare_layout(width, height, glare.levels)[1]
+
+        def arrays():
+            nonlocal kind   # of an array it is what the film's dtype says
+            f, kind = _glare_film(film, film_kind, width, height)
+            return [f, np.zeros((entries(), 4), dtype=np.uint64)]
+
+        return self._device_call([("film", film, "int64", 4, width * height, None), ("pyramid", pyramid, "int64", 4, entries, None)],
+                                 lambda d, n, stream: L.ptss_glare_build(self._ctx, d[0], kind, width, height, C.byref(params), C.byref(glare), d[1], stream),
+                                 arrays, read=(1,), result=lambda a: _records(a[1], GLARE_DTYPE))
 
     def glare_launches(self):
         """ptss_glare_launches: (glare_build calls, the kernels they launched, glare resolves that launched since the context was
         created)."""
-        out = (C.c_ulonglong * 3)()
-        _check(device_lib().ptss_glare_launches(self._ctx, out))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._counters("ptss_glare_launches", 3)
 
     # --- the denoiser of the two linear films (ptss_denoise_linear) ------------------
     def denoise_linear(self, film, width, height, moments, features, params=None, denoise=None, film_kind=None, out=None, workspace=None):
@@ -2543,38 +2468,27 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         denoise = denoise if denoise is not None else denoise_linear_params()
-        width, height = int(width), int(height)
-        nbytes = denoise_linear_workspace(width, height)
-        if type(film).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, P = film.device, width * height
-            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
-            d_film = self._torch_ptr(film, "film", "int64", 4, None, P)
-            d_mom = self._torch_ptr(moments, "moments", "int64", 4, dev, P)
-            d_feat = self._torch_ptr(features, "features", "float32", 8, dev, P)
-            d_out = self._torch_ptr(out, "out", "int64", 4, dev, P)
-            if workspace is None:
-                workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            d_ws = self._torch_ptr(workspace, "workspace", "uint8", 0, dev)
-            if workspace.shape[0] < nbytes:
+        width, height, kind = int(width), int(height), _film_kind(film_kind, FILM_LINEAR)
+        P, nbytes = width * height, denoise_linear_workspace(width, height)
+
+        def call(d, n, stream):
+            if n["workspace"] < nbytes:
                 raise ValueError("workspace: denoise_linear_workspace(width, height) bytes")
-            _check(L.ptss_denoise_linear(self._ctx, d_film, kind, width, height, d_mom, d_feat, C.byref(params), C.byref(denoise), d_ws, d_out,
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        f, kind, m, ft = _denoise_linear_inputs(film, film_kind, width, height, moments, features)
-        res = np.zeros((len(f), 4), dtype=np.uint64)
-        ws = np.zeros((nbytes,), dtype=np.uint8)
-        self._round_trip([f, m, ft, ws, res], lambda d: _check(L.ptss_denoise_linear(self._ctx, d[0], kind, width, height, d[1], d[2], C.byref(params),
-                                                                                     C.byref(denoise), d[3], d[4], None)), read=(3, 4))
-        res = res.view(LINEAR_DTYPE).reshape(-1)
-        return (res, ws) if workspace else res
+            return L.ptss_denoise_linear(self._ctx, d[0], kind, width, height, d[1], d[2], C.byref(params), C.byref(denoise), d[4], d[3], stream)
+
+        def arrays():
+            nonlocal kind   # of an array it is what the film's dtype says
+            f, kind, m, ft = _denoise_linear_inputs(film, film_kind, width, height, moments, features)
+            return [f, m, ft, np.zeros((len(f), 4), dtype=np.uint64), np.zeros((nbytes,), dtype=np.uint8)]
+
+        return self._device_call([("film", film, "int64", 4, P, None), ("moments", moments, "int64", 4, P, None), ("features", features, "float32", 8, P, None),
+                                  ("out", out, "int64", 4, P, None), ("workspace", workspace, "uint8", 0, nbytes if workspace is None else None, "empty")],
+                                 call, arrays, read=(3, 4),
+                                 result=lambda a: (_records(a[3], LINEAR_DTYPE), a[4]) if workspace else _records(a[3], LINEAR_DTYPE))
 
     def denoise_linear_launches(self):
         """ptss_denoise_linear_launches: (denoise_linear calls that launched, the kernels inside them since the context was created)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_denoise_linear_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_denoise_linear_launches", 2)
 
     def debug_denoise_linear_form(self, form):
         """ptss_debug_denoise_linear_form (tests and measurements): 0 the measured form per spacing, 1 taps from global memory, 2 staged in
@@ -2594,39 +2508,29 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         reproject = reproject if reproject is not None else reproject_linear_params()
-        if type(film_prev).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, Pn, Pp = film_prev.device, int(now.width) * int(now.height), int(prev.width) * int(prev.height)
-            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
-            d_fn = self._torch_ptr(features_now, "features_now", "float32", 8, dev, Pn)
-            d_fp = self._torch_ptr(features_prev, "features_prev", "float32", 8, dev, Pp)
-            d_film = self._torch_ptr(film_prev, "film_prev", "int64", 4, None, Pp)
-            d_mom = self._torch_ptr(moments_prev, "moments_prev", "int64", 4, dev, Pp) if moments_prev is not None else None
-            d_mot = self._torch_ptr(motion_now, "motion_now", "float32", 4, dev, Pn) if motion_now is not None else None
-            d_out = self._torch_ptr(out, "out", "int64", 4, dev, Pn)
-            d_mout = self._torch_ptr(moments_out, "moments_out", "int64", 4, dev, Pn) if moments_out is not None else None
-            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 4) if info is not None else None
-            _check(L.ptss_reproject_linear(self._ctx, C.byref(now), d_fn, d_mot, C.byref(prev), d_fp, d_film, kind, d_mom, C.byref(params),
-                                           C.byref(reproject), d_out, d_mout, d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        fn, mo, fp, f, kind, m = _reproject_linear_inputs(now, features_now, motion_now, prev, features_prev, film_prev, film_kind, moments_prev)
-        res = np.zeros((len(fn), 4), dtype=np.uint64)
-        mres = np.zeros((len(fn), 4), dtype=np.uint64) if m is not None else None
-        inf = np.zeros(1, dtype=REPROJECT_LINEAR_INFO_DTYPE)
-        if info is not None:
-            inf[0] = info
-        self._round_trip([fn, mo, fp, f, m, res, mres, inf],
-                         lambda d: _check(L.ptss_reproject_linear(self._ctx, C.byref(now), d[0], d[1], C.byref(prev), d[2], d[3], kind, d[4],
-                                                                  C.byref(params), C.byref(reproject), d[5], d[6], d[7], None)), read=(5, 6, 7))
-        res = res.view(SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE).reshape(-1)
-        return res, (mres.view(MOMENT_DTYPE).reshape(-1) if mres is not None else None), inf[0]
+        Pn, Pp, kind = int(now.width) * int(now.height), int(prev.width) * int(prev.height), _film_kind(film_kind, FILM_LINEAR)
+
+        def arrays():
+            nonlocal kind   # of an array it is what the film's dtype says
+            fn, mo, fp, f, kind, m = _reproject_linear_inputs(now, features_now, motion_now, prev, features_prev, film_prev, film_kind, moments_prev)
+            inf = np.zeros(1, dtype=REPROJECT_LINEAR_INFO_DTYPE)
+            if info is not None:
+                inf[0] = info
+            return [fn, fp, f, m, mo, np.zeros((len(fn), 4), dtype=np.uint64), np.zeros((len(fn), 4), dtype=np.uint64) if m is not None else None, inf]
+
+        return self._device_call(
+            [("features_now", features_now, "float32", 8, Pn, None), ("features_prev", features_prev, "float32", 8, Pp, None),
+             ("film_prev", film_prev, "int64", 4, Pp, None), ("moments_prev", moments_prev, "int64", 4, Pp, "null"),
+             ("motion_now", motion_now, "float32", 4, Pn, "null"), ("out", out, "int64", 4, Pn, None), ("moments_out", moments_out, "int64", 4, Pn, "null"),
+             ("info", info, "int64", 0, 4, "null")],
+            lambda d, n, stream: L.ptss_reproject_linear(self._ctx, C.byref(now), d[0], d[4], C.byref(prev), d[1], d[2], kind, d[3], C.byref(params),
+                                                         C.byref(reproject), d[5], d[6], d[7], stream),
+            arrays, read=(5, 6, 7), primary=2,   # the device is film_prev's
+            result=lambda a: (_records(a[5], SPLAT_DTYPE if kind == FILM_SPLAT else LINEAR_DTYPE), _records(a[6], MOMENT_DTYPE), a[7][0]))
 
     def reproject_linear_launches(self):
         """ptss_reproject_linear_launches: the reproject_linear calls that launched since the context was created."""
-        out = C.c_ulonglong(0)
-        _check(device_lib().ptss_reproject_linear_launches(self._ctx, C.byref(out)))
-        return int(out.value)
+        return self._counters("ptss_reproject_linear_launches", 1)
 
     # --- upsampling the two linear films (ptss_upsample_linear) ------------------
     def upsample_linear(self, film_lo, width, height, features_lo, features_hi, params=None, upsample=None, film_kind=None, out=None, info=None):
@@ -2640,37 +2544,27 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         upsample = upsample if upsample is not None else upsample_linear_params()
-        if type(film_lo).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, Pl = film_lo.device, int(width) * int(height)
-            Ph = Pl * int(upsample.factor) ** 2
-            kind = int(_GLARE_FILMS.get(film_kind, FILM_LINEAR if film_kind is None else film_kind))
-            d_film = self._torch_ptr(film_lo, "film_lo", "int64", 4, None, Pl)
-            d_flo = self._torch_ptr(features_lo, "features_lo", "float32", 8, dev, Pl)
-            d_fhi = self._torch_ptr(features_hi, "features_hi", "float32", 8, dev, Ph)
-            d_out = self._torch_ptr(out, "out", "int64", 4, dev, Ph)
-            d_info = self._torch_ptr(info, "info", "int64", 0, dev, 3) if info is not None else None
-            _check(L.ptss_upsample_linear(self._ctx, d_film, kind, int(width), int(height), d_flo, d_fhi, C.byref(params), C.byref(upsample), d_out,
-                                          d_info, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        f, kind, flo, fhi, P = _upsample_linear_inputs(film_lo, film_kind, width, height, features_lo, features_hi, upsample)
-        res = np.zeros((P, 4), dtype=np.uint64)
-        inf = None
-        if info is not False:
-            inf = np.zeros(1, dtype=UPSAMPLE_LINEAR_INFO_DTYPE)
-            if info is not None:
+        Pl, kind = int(width) * int(height), _film_kind(film_kind, FILM_LINEAR)
+        Ph = Pl * int(upsample.factor) ** 2
+
+        def arrays():
+            nonlocal kind   # of an array it is what the film's dtype says
+            f, kind, flo, fhi, P = _upsample_linear_inputs(film_lo, film_kind, width, height, features_lo, features_hi, upsample)
+            inf = np.zeros(1, dtype=UPSAMPLE_LINEAR_INFO_DTYPE) if info is not False else None
+            if info is not None and info is not False:
                 inf[0] = info
-        self._round_trip([f, flo, fhi, res, inf],
-                         lambda d: _check(L.ptss_upsample_linear(self._ctx, d[0], kind, int(width), int(height), d[1], d[2], C.byref(params),
-                                                                 C.byref(upsample), d[3], d[4], None)), read=(3, 4))
-        return res.view(LINEAR_DTYPE).reshape(-1), (inf[0] if inf is not None else None)
+            return [f, flo, fhi, np.zeros((P, 4), dtype=np.uint64), inf]
+
+        return self._device_call(
+            [("film_lo", film_lo, "int64", 4, Pl, None), ("features_lo", features_lo, "float32", 8, Pl, None),
+             ("features_hi", features_hi, "float32", 8, Ph, None), ("out", out, "int64", 4, Ph, None), ("info", info, "int64", 0, 3, "null")],
+            lambda d, n, stream: L.ptss_upsample_linear(self._ctx, d[0], kind, int(width), int(height), d[1], d[2], C.byref(params), C.byref(upsample),
+                                                        d[3], d[4], stream),
+            arrays, read=(3, 4), result=lambda a: (_records(a[3], LINEAR_DTYPE), a[4][0] if a[4] is not None else None))
 
     def upsample_linear_launches(self):
         """ptss_upsample_linear_launches: the upsample_linear calls that launched since the context was created."""
-        out = C.c_ulonglong(0)
-        _check(device_lib().ptss_upsample_linear_launches(self._ctx, C.byref(out)))
-        return int(out.value)
+        return self._counters("ptss_upsample_linear_launches", 1)
 
     def debug_upsample_linear_form(self, form):
         """ptss_debug_upsample_linear_form (tests and measurements): 0 the form measured faster at each factor, 1 every tap from global
@@ -2680,23 +2574,11 @@ class Renderer:
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):
         """The body of meter_linear and meter_splat."""
-        if type(film).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev, P = film.device, film.shape[0]
-            first_pixel, count = _linear_range(P, first_pixel, count)
-            d_film = self._torch_ptr(film, "film", "int64", 4)
-            d_hist = self._torch_ptr(histogram, "histogram", "int32", 0, dev, METER_BINS)
-            _check(call(self._ctx, d_film, first_pixel, count, d_hist, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        f = _rows(film, film_dtype, 4, np.uint64, "film")
-        first_pixel, count = _linear_range(len(f), first_pixel, count)
-        h = _histogram(histogram)
-        if count == 0:
-            _check(call(self._ctx, None, first_pixel, 0, None, None))
-        else:
-            self._round_trip([f, h], lambda d: _check(call(self._ctx, d[0], first_pixel, count, d[1], None)), read=(1,))
-        return h
+        span = lambda n: _linear_range(n["film"], first_pixel, count)
+        return self._device_call([("film", film, "int64", 4, None, None), ("histogram", histogram, "int32", 0, METER_BINS, None)],
+                                 lambda d, n, stream: call(self._ctx, d[0], *span(n), d[1], stream),
+                                 lambda: [_rows(film, film_dtype, 4, np.uint64, "film"), _histogram(histogram)],
+                                 read=(1,), null=lambda n: span(n)[1] == 0, result=lambda a: a[1])
 
     def meter_linear(self, film, first_pixel=0, count=None, histogram=None):
         """ptss_meter_linear: pixels first_pixel .. first_pixel + count (None: to the film's end) of a linear film counted into a
@@ -2717,49 +2599,31 @@ class Renderer:
         L = device_lib()
         params = params if params is not None else linear_params()
         meter = meter if meter is not None else meter_params()
-        if type(histogram).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
-            dev = histogram.device
-            d_hist = self._torch_ptr(histogram, "histogram", "int32", 0, None, METER_BINS)
-            d_state = self._torch_ptr(state, "state", "int64", 0, dev, 6)
-            _check(L.ptss_meter_exposure(self._ctx, d_hist, C.byref(params), C.byref(meter), d_state, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-            return None
-        h, s = _histogram(histogram), _meter_state(state)
-        self._round_trip([h, s], lambda d: _check(L.ptss_meter_exposure(self._ctx, d[0], C.byref(params), C.byref(meter), d[1], None)), read=(1,))
-        return s
+        return self._device_call([("histogram", histogram, "int32", 0, METER_BINS, None), ("state", state, "int64", 0, 6, None)],
+                                 lambda d, n, stream: L.ptss_meter_exposure(self._ctx, d[0], C.byref(params), C.byref(meter), d[1], stream),
+                                 lambda: [_histogram(histogram), _meter_state(state)], read=(1,), result=lambda a: a[1])
 
     def meter_launches(self):
         """ptss_meter_launches: (meter_linear / meter_splat, meter_exposure, metered resolve calls that launched since the context was
         created)."""
-        out = (C.c_ulonglong * 3)()
-        _check(device_lib().ptss_meter_launches(self._ctx, out))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._counters("ptss_meter_launches", 3)
 
     def splat_stats(self):
         """ptss_splat_stats: (scatter launches, homed launches, resolves, samples dropped, samples clamped) since the context was
         created; synchronises with the stream of the latest splat."""
-        out = (C.c_ulonglong * 5)()
-        _check(device_lib().ptss_splat_stats(self._ctx, out))
-        return tuple(int(v) for v in out)
+        return self._counters("ptss_splat_stats", 5)
 
     def linear_launches(self):
         """ptss_linear_launches: (accumulate_paths_linear, resolve_linear calls that launched since the context was created)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_linear_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_linear_launches", 2)
 
     def film_launches(self):
         """ptss_film_launches: (generate_rays, accumulate_paths, ray_features calls that launched since the context was created)."""
-        out = (C.c_ulonglong * 3)()
-        _check(device_lib().ptss_film_launches(self._ctx, out))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._counters("ptss_film_launches", 3)
 
     def film_rejected(self):
         """ptss_film_rejected: the index entries the film calls dropped since the context was created (synchronises)."""
-        out = C.c_ulonglong(0)
-        _check(device_lib().ptss_film_rejected(self._ctx, C.byref(out)))
-        return int(out.value)
+        return self._counters("ptss_film_rejected", 1)
 
     # --- first-hit features and the denoiser (ptss_render_features / ptss_denoise) ---------------------
     def _device_buffer(self, name, nbytes):
@@ -2811,14 +2675,12 @@ class Renderer:
         use them."""
         L = device_lib()
         d_feat, d_mot = self.features_devptr(), self.motion_devptr()
-        if type(prev_triangles).__module__.split(".")[0] == "torch":
-            import sys
-            torch = sys.modules["torch"]
+        if _is_torch(prev_triangles):
             t = prev_triangles
-            if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() % 19:
+            if t.dtype != _torch().float32 or not t.is_contiguous() or not t.is_cuda or t.numel() % 19:
                 raise ValueError("prev_triangles: a contiguous float32 device tensor of n x 19 words")
             if stream is None:
-                stream = torch.cuda.current_stream(t.device).cuda_stream
+                stream = _stream_of(_torch(), t.device)
             d_prev, count = C.c_void_p(t.data_ptr()) if t.numel() else None, t.numel() // 19
         elif prev_triangles is None:
             d_prev, count = None, 0
@@ -2865,9 +2727,7 @@ class Renderer:
 
     def specular_feature_launches(self):
         """ptss_specular_feature_launches: (launches with the scene image read in place, launches with it staged in LDS)."""
-        out = (C.c_ulonglong * 2)()
-        _check(device_lib().ptss_specular_feature_launches(self._ctx, out))
-        return int(out[0]), int(out[1])
+        return self._counters("ptss_specular_feature_launches", 2)
 
     # --- rendering below display size (ptss_render_features_scaled / ptss_upsample) ---------------------------
     def features_scaled_devptr(self, factor):
@@ -2946,9 +2806,7 @@ class Renderer:
 
     def upsample_launches(self):
         """ptss_upsample_launches: accepted ptss_upsample calls that launched, since the context was created."""
-        v = C.c_ulonglong()
-        _check(device_lib().ptss_upsample_launches(self._ctx, C.byref(v)))
-        return v.value
+        return self._counters("ptss_upsample_launches", 1)
 
     def denoise(self, features=None, levels=None, sigma_color=None, sigma_normal=None, sigma_depth=None, dev_out=None, stream=None):
         """ptss_denoise of the accumulated image -> (local_pixels, 4) uint8 RGBA. features: None (the buffer of the last
