@@ -33,6 +33,7 @@
 #include "ptlindn.h"
 #include "ptlinrp.h"
 #include "ptlinup.h"
+#include "ptsurface.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -116,7 +117,8 @@ struct ptss_context {
     unsigned long long* dTotal = nullptr;   // [0 .. kMaxLanes) ray-bounce totals per lane, [kMaxLanes]: records ptss_update_triangles
                                             // rejected (kRejectedWord), [kMaxLanes + 1]: index entries the film calls dropped (kFilmRejectedWord),
                                             // [kMaxLanes + 2], [+ 3]: samples the splat calls dropped and clamped (kSplatCountersWord),
-                                            // [kMaxLanes + 4 .. +8) unused, then one word: guard timeouts (must stay 0)
+                                            // [kMaxLanes + 4]: entries ptss_generate_rays_surface dropped (kSurfaceRejectedWord),
+                                            // [kMaxLanes + 5 .. +8) unused, then one word: guard timeouts (must stay 0)
     uint32_t* dAccumOwned = nullptr;
     uint32_t* dAccum = nullptr;  // owned or bound
     float* dFsum = nullptr;
@@ -173,6 +175,10 @@ struct ptss_context {
     unsigned long long linUpsampleLaunches = 0;               // ptss_upsample_linear calls that launched
     int linUpsampleForm = 0;                                  // ptss_debug_upsample_linear_form: 0 the measured table, 1 global memory, 2 staged
     unsigned long long toneLaunches[2] = {0, 0};              // ptss_tone_build, ptss_resolve_toned calls that launched
+    unsigned long long surfaceLaunches[2] = {0, 0};           // ptss_generate_rays_surface, ptss_dilate_linear calls that launched
+    hipStream_t surfaceStream = nullptr;                      // the stream of the latest ptss_generate_rays_surface (ptss_surface_rejected synchronises on it)
+    bool surfaceCounted = false;
+    int dilateForm = 0;                                       // ptss_debug_dilate_linear_form: 0 the shipped form, 1 global memory, 2 staged
     int toneForm = 0;                                         // ptss_debug_tone_form: 0 the shipped lookup, 1 staged in LDS, 2 guess and settle
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
@@ -190,6 +196,7 @@ struct ptss_context {
 constexpr int kTotalWords = ptss::kMaxLanes + 8 + 1;
 constexpr int kRejectedWord = ptss::kMaxLanes;
 constexpr int kFilmRejectedWord = ptss::kMaxLanes + 1;
+constexpr int kSurfaceRejectedWord = ptss::kMaxLanes + 4;   // entries ptss_generate_rays_surface dropped
 constexpr int kSplatCountersWord = ptss::kMaxLanes + 2;   // two words: samples the splat calls dropped, samples they clamped
 
 namespace {
@@ -1927,6 +1934,62 @@ int ptss_debug_upsample_linear_form(ptss_context* c, int form) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
     c->linUpsampleForm = form;
+    return PTSS_OK;
+}
+
+// ---- rays from surface points and the gutter fill (ptss_surface.hip; csrc/ptsurface.h). Like the film calls: images[0] at most, no frame state, the caller's stream ----
+int ptss_generate_rays_surface(ptss_context* c, const ptss_surface_params* params, const ptss_surface_point* dev_points, size_t numPoints,
+                               size_t firstPoint, const uint32_t* dev_index, size_t n, ptss_path_rng* dev_rng, ptss_ray_query* dev_rays,
+                               ptss_ray_hit* dev_surfels, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptsurf::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (!fits31(numPoints)) return fail(PTSS_ERANGE, "numPoints must be below 2^31");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_points || !dev_rng || !dev_rays) return fail(PTSS_EINVAL, kNullBuffer);
+    if ((((uintptr_t)dev_points | (uintptr_t)dev_rays | (uintptr_t)dev_surfels) & 15u) || (((uintptr_t)dev_rng | (uintptr_t)dev_index) & 3u))
+        return fail(PTSS_EINVAL, "points, rays and surfels must be 16-byte aligned, dev_rng and dev_index 4-byte aligned");
+    if (!dev_index && (firstPoint > numPoints || n > numPoints - firstPoint)) return fail(PTSS_ERANGE, "firstPoint + n leaves the points");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = streamOf(c, hipStream);
+    HIP_TRY(ptss::launchSurfaceRays(st, im.dBlob, im.layout, *params, dev_points, (uint32_t)numPoints, dev_index ? 0u : (uint32_t)firstPoint, dev_index,
+                                    (uint32_t)n, dev_rng, dev_rays, dev_surfels, c->dTotal + kSurfaceRejectedWord, &c->surfaceLaunches[0]));
+    c->surfaceStream = st;
+    c->surfaceCounted = true;
+    return PTSS_OK;
+}
+
+int ptss_dilate_linear(ptss_context* c, const ptss_linear_entry* dev_film, int width, int height, ptss_linear_entry* dev_out, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (!dev_film || !dev_out) return fail(PTSS_EINVAL, "null film");
+    if (dev_film == dev_out) return fail(PTSS_EINVAL, "dev_out must not be dev_film");
+    if (((uintptr_t)dev_film | (uintptr_t)dev_out) & 15u) return fail(PTSS_EINVAL, "films must be 16-byte aligned");
+    if (const char* what = ptsurf::dilateSidesError(width, height)) return fail(PTSS_ERANGE, what);
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchDilateLinear(streamOf(c, hipStream), dev_film, width, height, c->dilateForm, dev_out, &c->surfaceLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_surface_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    for (int k = 0; k < 2; ++k) out2[k] = c->surfaceLaunches[k];
+    return PTSS_OK;
+}
+
+int ptss_surface_rejected(ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    if (c->surfaceCounted) HIP_TRY(hipStreamSynchronize(c->surfaceStream));
+    HIP_TRY(hipMemcpy(out, c->dTotal + kSurfaceRejectedWord, sizeof(*out), hipMemcpyDeviceToHost));
+    return PTSS_OK;
+}
+
+int ptss_debug_dilate_linear_form(ptss_context* c, int form) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
+    c->dilateForm = form;
     return PTSS_OK;
 }
 

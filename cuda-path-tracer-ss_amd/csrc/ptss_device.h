@@ -305,6 +305,16 @@ hipError_t launchLinearReproject(hipStream_t st, const ptss_film_camera& now, co
 hipError_t launchLinearUpsample(hipStream_t st, const void* filmLo, bool splat, int width, int height, const void* featuresLo,
                                 const void* featuresHi, const ptss_linear_params& film, const ptss_upsample_linear_params& params, int form,
                                 void* filmHi, void* info, unsigned long long* launches);
+// rays from surface points (ptss_surface.hip; ptss_generate_rays_surface). points: numPoints rows of 16 B; rng: n streams of
+// 24 B; rays: n rows of 32 B; surfels (may be null): n rows of 48 B; index may be null. The image's counts bound every gather inside
+// the kernel; *rejected counts the dropped entries. Everything else checked by the caller (ptsurf::paramsError). *launches is
+// incremented when the kernel launched. No bit of ptss_launched_kernels
+hipError_t launchSurfaceRays(hipStream_t st, const float4* sceneBlob, const SceneLayout& layout, const ptss_surface_params& params,
+                             const void* points, uint32_t numPoints, uint32_t firstPoint, const uint32_t* index, uint32_t n, void* rng, void* rays,
+                             void* surfels, unsigned long long* rejected, unsigned long long* launches);
+// one gutter-fill pass over a linear film (ptss_surface.hip; ptss_dilate_linear). film and out: width x height entries of 32 B, not the
+// same buffer. form: 0 the shipped one, 1 from global memory, 2 staged in LDS. Sides checked by the caller (ptsurf::dilateSidesError)
+hipError_t launchDilateLinear(hipStream_t st, const void* film, int width, int height, int form, void* out, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

@@ -24,6 +24,7 @@
 #include "ptlinup.h"
 #include "ptmotion.h"
 #include "ptspecular.h"
+#include "ptsurface.h"
 #include "ptquant.h"
 #include "ptlocate.h"
 #include "ptmesh.h"
@@ -1224,6 +1225,82 @@ int ptss_probe_upsample_linear(const void* film_lo, int filmKind, int width, int
             }
         }
     return PTSS_HOST_OK;
+}
+
+// ---- rays from surface points, the gutter fill, the atlas (csrc/ptsurface.h) ----
+int ptss_probe_surface_rays(const ptss_triangle* triangles, size_t numTriangles, const ptss_sphere* spheres, size_t numSpheres,
+                            const ptss_surface_params* params, const ptss_surface_point* points, size_t numPoints, size_t firstPoint,
+                            const uint32_t* index, size_t n, ptss_path_rng* rng, ptss_ray_query* rays, ptss_ray_hit* surfels,
+                            unsigned long long* rejected) {
+    if (ptsurf::paramsError(params)) return PTSS_HOST_EINVAL;
+    if (n >= (size_t(1) << 31) || numPoints >= (size_t(1) << 31)) return PTSS_HOST_ERANGE;
+    if (rejected) *rejected = 0;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!points || !rng || !rays || (numTriangles > 0 && !triangles) || (numSpheres > 0 && !spheres)) return PTSS_HOST_EINVAL;
+    if (!index && (firstPoint > numPoints || n > numPoints - firstPoint)) return PTSS_HOST_ERANGE;
+    unsigned long long dropped = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned long long p = index ? index[i] : firstPoint + i;
+        if (p >= numPoints) {
+            ++dropped;
+            continue;
+        }
+        const ptss_surface_point pt = points[p];
+        const uint32_t prim = (uint32_t)pt.surface & ~ptsurf::kTriangleBit;
+        const bool triangle = ((uint32_t)pt.surface & ptsurf::kTriangleBit) != 0u;
+        bool ok = pt.surface >= 0 && ptsurf::flagsAccepted(pt.flags);
+        ok = ok && (triangle ? prim < numTriangles && ptsurf::triangleAccepted(pt.a, pt.b) : prim < numSpheres && ptsurf::sphereAccepted(pt.a, pt.b));
+        if (!ok) {
+            ++dropped;
+            continue;
+        }
+        ptsurf::Surfel s;
+        int materialIdx;
+        if (triangle) {
+            const ptss_triangle& t = triangles[prim];
+            s = ptsurf::triangleSurfel(t.vertex0, t.vertex1 - t.vertex0, t.vertex2 - t.vertex0, t.normal0, t.normal1, t.normal2, pt.a, pt.b, pt.flags);
+            materialIdx = t.materialIdx;
+        } else {
+            const ptss_sphere& sp = spheres[prim];
+            s = ptsurf::sphereSurfel(sp.position, sp.radius * sp.radius, pt.a, pt.b, pt.flags);
+            materialIdx = sp.materialIdx;
+        }
+        float u1 = 0.0f, u2 = 0.0f;
+        if (ptsurf::draws(params->mode)) {
+            ptrng::State st;
+            for (int w = 0; w < 5; ++w) st.v[w] = rng[i].v[w];
+            st.d = rng[i].d;
+            u1 = ptrng::uniform(st);
+            u2 = ptrng::uniform(st);
+            for (int w = 0; w < 5; ++w) rng[i].v[w] = st.v[w];
+            rng[i].d = st.d;
+        }
+        rays[i] = ptsurf::surfaceRay(s, params->mode, params->maxDistance, u1, u2);
+        if (surfels) surfels[i] = ptsurf::surfelHit(s, materialIdx, triangle ? PTSS_HIT_TRIANGLE : PTSS_HIT_SPHERE, (int)prim, pt.a, pt.b);
+    }
+    if (rejected) *rejected = dropped;
+    return PTSS_HOST_OK;
+}
+
+int ptss_probe_dilate_linear(const ptss_linear_entry* film, int width, int height, ptss_linear_entry* out) {
+    if (!film || !out || film == out) return PTSS_HOST_EINVAL;
+    if (ptsurf::dilateSidesError(width, height)) return PTSS_HOST_ERANGE;
+    auto at = [&](int x, int y) {
+        const ptss_linear_entry& e = film[(size_t)y * (size_t)width + (size_t)x];
+        return ptsurf::Texel{e.r, e.g, e.b, e.samples, e.clamped};
+    };
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const ptsurf::Texel t = ptsurf::dilateTexel(x, y, width, height, at);
+            out[(size_t)y * (size_t)width + (size_t)x] = ptss_linear_entry{t.r, t.g, t.b, t.samples, t.clamped};
+        }
+    return PTSS_HOST_OK;
+}
+
+int ptss_surface_atlas(const ptss_triangle* triangles, size_t first, size_t count, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
+                       ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints) {
+    static_assert(PTSS_HOST_EINVAL == -1 && PTSS_HOST_ERANGE == -3, "ptsurf::atlas returns these");
+    return ptsurf::atlas(triangles, first, count, texelsPerUnit, minSide, maxSide, atlasWidth, points, texels, capacity, atlasHeight, numPoints);
 }
 
 }  // extern "C"

@@ -72,6 +72,12 @@
 //                                   moments; --ticks more rounds accumulate into them, and the usual tail runs. Prints the four counters of
 //                                   ptss_reproject_linear_info. Not with --adaptive or --adaptive-linear: the combination is left out to keep
 //                                   this program's matrix small. Without the flag every byte written is today's
+//             [--bake [texelsPerUnit[,samples[,passes]]]]   a light map of the scene's triangles (--obj models included) instead of an image
+//                                   (DESIGN.md §3.38): ptss_surface_atlas at --size's width (sides 1 .. 64, texelsPerUnit default 4), streams from
+//                                   ptss_seed_path_rng(--seed), then `samples` (default 16) rounds of ptss_generate_rays_surface (cosine) ->
+//                                   ptss_trace_paths -> ptss_accumulate_paths_linear indexed by texel, `passes` (default 1) of ptss_dilate_linear,
+//                                   ptss_resolve_linear; writes the linear means to --out (default lightmap.pfm) and prints the atlas size
+//                                   and the rejected count. Not with --film, --temporal, --denoise, --upscale, --pick, --gpus
 //             [--upscale-linear F]  with --film and --linear, with or without --filter, --refill, --denoise-linear, --auto-exposure and --glare:
 //                                   the film is traced (and denoised) at the given size and upsampled in linear light to F (1..4) times the
 //                                   size — the features are ptss_ray_features of the centre rays of the same film camera at
@@ -83,10 +89,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
+#include <vector>
 
 #include "CudaTracer.h"
 #include "HostOps.h"
+#include "ptsurface.h"
 
 int main(int argc, char* argv[]) {
     std::string preset = "default", out, keys;
@@ -125,6 +134,9 @@ int main(int argc, char* argv[]) {
     bool carry = false;                               // --carry: the linear film is carried across a second camera move
     std::string carryKeys;                            // ... the keys of that move, and the cap of the history count when given
     long carryHistory = -1;
+    bool bake = false;                                // --bake: a light map of the scene's triangles instead of an image
+    float bakeTexels = 4.f;                           // ... texels per unit of length, samples per texel, gutter-fill passes
+    int bakeSamples = 16, bakePasses = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -239,6 +251,16 @@ int main(int argc, char* argv[]) {
                 return 2;
             }
         }
+        else if (a == "--bake") {
+            bake = true;
+            if (i + 1 < argc && ((argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') || argv[i + 1][0] == '.')) {
+                const int got = sscanf(next(), "%f,%d,%d", &bakeTexels, &bakeSamples, &bakePasses);
+                if (got < 1 || !(bakeTexels > 0.f && bakeTexels < 1e30f) || bakeSamples < 1 || bakeSamples > (1 << 22) || bakePasses < 0 || bakePasses > 64) {
+                    fprintf(stderr, "bad --bake (texelsPerUnit[,samples[,passes]]: samples 1 .. 4194304, passes 0 .. 64)\n");
+                    return 2;
+                }
+            }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -301,6 +323,12 @@ int main(int argc, char* argv[]) {
         return 2;
     }
     if (carry && (linear < 0.f || adaptiveLinear >= 0 || ticks < 1)) { fprintf(stderr, "--carry needs --film, --linear, at least one tick and no --adaptive-linear\n"); return 2; }
+    if (bake && (gpus > 0 || !film.empty() || temporal || denoise != -2 || upscale != 0 || !picks.empty() || samples != 1 || bounces < 1 || bounces > 64 ||
+                 width < 1)) {
+        fprintf(stderr, "--bake needs one context (no --gpus), 1..64 bounces, one sample per pass and none of --film, --temporal, --denoise, --upscale, "
+                        "--pick\n");
+        return 2;
+    }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -368,6 +396,65 @@ int main(int argc, char* argv[]) {
     };
 
     bitmap.set_max_ticks(ticks);
+    if (bake) {   // the loop of INTEGRATION.md §2g "Baking": atlas, seed, then per sample generate, trace, accumulate by texel; gutter fills; resolve
+        const int maxSide = width < 64 ? width : 64;
+        size_t K = 0;
+        int atlasH = 0;
+        const ptss_triangle* tris = scene.trianglesVec.empty() ? nullptr : scene.trianglesVec.data();
+        const size_t T = scene.trianglesVec.size();
+        if (T == 0 || ptsurf::atlas(tris, 0, T, bakeTexels, 1, maxSide, width, nullptr, nullptr, 0, &atlasH, &K) != 0 || K == 0) {
+            fprintf(stderr, "--bake: the scene has no triangles, or the atlas of %d columns does not fit 2^31 texels\n", width);
+            return 2;
+        }
+        std::vector<ptss_surface_point> points(K);
+        std::vector<uint32_t> texels(K);
+        ptsurf::atlas(tris, 0, T, bakeTexels, 1, maxSide, width, points.data(), texels.data(), K, &atlasH, &K);
+        const size_t P = (size_t)width * (size_t)atlasH;
+        void *dPoints = nullptr, *dTexels = nullptr, *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dMap[2] = {nullptr, nullptr}, *dMeans = nullptr;
+        if (hipMalloc(&dPoints, K * sizeof(ptss_surface_point)) != hipSuccess || hipMalloc(&dTexels, K * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc(&dRng, K * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dRays, K * sizeof(ptss_ray_query)) != hipSuccess ||
+            hipMalloc(&dRes, K * sizeof(ptss_path_result)) != hipSuccess || hipMalloc(&dMap[0], P * sizeof(ptss_linear_entry)) != hipSuccess ||
+            hipMalloc(&dMap[1], P * sizeof(ptss_linear_entry)) != hipSuccess || hipMalloc(&dMeans, P * sizeof(ptss_history_entry)) != hipSuccess ||
+            hipMemcpy(dPoints, points.data(), K * sizeof(ptss_surface_point), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dTexels, texels.data(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemset(dMap[0], 0, P * sizeof(ptss_linear_entry)) != hipSuccess) {
+            fprintf(stderr, "--bake: device buffers\n");
+            return 1;
+        }
+        ptss_surface_params sp;
+        sp.structSize = (unsigned int)sizeof(sp);
+        sp.mode = PTSS_SURFACE_COSINE;
+        sp.maxDistance = ptm::inf();
+        sp.reserved = 0u;
+        ptss_linear_params linearParams;
+        PTSS_HANDLE(ptss_default_linear_params(&linearParams));
+        PTSS_HANDLE(ptss_seed_path_rng(ctx, (ptss_path_rng*)dRng, K, seed, 0, 0, NULL));
+        for (int s = 0; s < bakeSamples; ++s) {
+            PTSS_HANDLE(ptss_generate_rays_surface(ctx, &sp, (const ptss_surface_point*)dPoints, K, 0, NULL, K, (ptss_path_rng*)dRng, (ptss_ray_query*)dRays,
+                                                   NULL, NULL));
+            PTSS_HANDLE(ptss_trace_paths(ctx, (const ptss_ray_query*)dRays, (ptss_path_rng*)dRng, (ptss_path_result*)dRes, K, bounces, NULL));
+            PTSS_HANDLE(ptss_accumulate_paths_linear(ctx, (const ptss_path_result*)dRes, (const uint32_t*)dTexels, 0, K, (ptss_linear_entry*)dMap[0], P,
+                                                     &linearParams, NULL));
+        }
+        int cur = 0;
+        for (int pass = 0; pass < bakePasses; ++pass, cur = 1 - cur)
+            PTSS_HANDLE(ptss_dilate_linear(ctx, (const ptss_linear_entry*)dMap[cur], width, atlasH, (ptss_linear_entry*)dMap[1 - cur], NULL));
+        PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dMap[cur], 0, P, &linearParams, (ptss_history_entry*)dMeans, NULL, NULL, NULL));
+        PTSS_HANDLE(ptss_synchronize(ctx));
+        unsigned long long rejected = 0;
+        PTSS_HANDLE(ptss_surface_rejected(ctx, &rejected));
+        std::vector<ptss_history_entry> means(P);
+        if (hipMemcpy(means.data(), dMeans, P * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--bake: read-back\n"); return 1; }
+        const std::string name = out.empty() ? "lightmap.pfm" : out;
+        if (!writePfm(name.c_str(), means.data(), width, atlasH)) { fprintf(stderr, "--bake: cannot write %s\n", name.c_str()); return 1; }
+        printf("bake: atlas %d x %d, %zu texels of %zu triangles, %d samples, %d passes, rejected %llu\n", width, atlasH, K, T, bakeSamples, bakePasses,
+               rejected);
+        for (void* d : {dPoints, dTexels, dRng, dRays, dRes, dMap[0], dMap[1], dMeans}) (void)hipFree(d);
+        PTSS_HANDLE(ptss_destroy(ctx));
+        bitmap.free_resources();
+        delete data;
+        return 0;
+    }
     if (temporal) {   // the loop of INTEGRATION.md: frames, features, reproject from the history kept at the previous pose, keep, move
         const size_t n = (size_t)width * (size_t)height;
         void *df[2] = {nullptr, nullptr}, *dh[2] = {nullptr, nullptr}, *dp = nullptr;

@@ -25,6 +25,7 @@ from ptss_types import (GLARE_ADD, GLARE_DTYPE, GLARE_FILM_LINEAR, GLARE_FILM_SP
 from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DENOISE_MAX_LEVELS, FILM_LINEAR, FILM_SPLAT, DenoiseLinearParams
 from ptss_types import REPROJECT_LINEAR_INFO_DTYPE, REPROJECT_LINEAR_MAX_HISTORY, ReprojectLinearParams
 from ptss_types import UPSAMPLE_LINEAR_INFO_DTYPE, UPSAMPLE_LINEAR_WRAP_X, UpsampleLinearParams
+from ptss_types import SPHERE_DTYPE, SURFACE_BACK, SURFACE_COSINE, SURFACE_NORMAL, SURFACE_POINT_DTYPE, SURFACE_TRIANGLE, SurfaceParams
 from ptss_types import TONE_CLAMP, TONE_FILMIC, TONE_LUMINANCE, TONE_REINHARD, TRANSFER_GAMMA22, TRANSFER_SRGB, ToneParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -236,6 +237,11 @@ def host_lib():
                                                          C.POINTER(ReprojectLinearParams), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
         L.ptss_probe_upsample_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LinearParams),
                                                  C.POINTER(UpsampleLinearParams), C.c_void_p, C.c_void_p]
+        L.ptss_probe_surface_rays.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(SurfaceParams), C.c_void_p, C.c_size_t,
+                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        L.ptss_probe_dilate_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.ptss_surface_atlas.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
         _host = L
     return _host
 
@@ -393,6 +399,11 @@ def device_lib():
         L.ptss_upsample_linear.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(LinearParams), C.POINTER(UpsampleLinearParams), vp, vp, vp]
         L.ptss_upsample_linear_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_upsample_linear_form.argtypes = [vp, C.c_int]
+        L.ptss_generate_rays_surface.argtypes = [vp, C.POINTER(SurfaceParams), vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp]
+        L.ptss_dilate_linear.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        L.ptss_surface_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_surface_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_dilate_linear_form.argtypes = [vp, C.c_int]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1424,6 +1435,119 @@ def probe_upsample_linear(film_lo, width, height, features_lo, features_hi, para
     if rc != 0:
         raise PtssError(f"ptss_probe_upsample_linear: {rc}")
     return out.view(LINEAR_DTYPE).reshape(-1), inf[0]
+
+
+# ---- rays from surface points, the atlas, the gutter fill (ptss_generate_rays_surface / ptss_dilate_linear) ----
+_SURFACE_MODES = {"normal": SURFACE_NORMAL, "cosine": SURFACE_COSINE}
+
+
+def surface_params(mode="cosine", max_distance=float("inf")):
+    """A ptss_surface_params. mode: "normal" (no draw) or "cosine" (two draws), or a PTSS_SURFACE_* value; max_distance: every ray's tmax."""
+    p = SurfaceParams()
+    p.structSize = C.sizeof(SurfaceParams)
+    p.mode, p.maxDistance, p.reserved = _SURFACE_MODES.get(mode, mode), float(max_distance), 0
+    return p
+
+
+def surface_draws(params):
+    """The uniforms a ray of ptss_generate_rays_surface takes from its stream: 0 or 2."""
+    return 2 if params.mode == SURFACE_COSINE else 0
+
+
+def scene_records(scene):
+    """The triangles and spheres of a ptss.Scene as ((T,) TRIANGLE_DTYPE, (S,) SPHERE_DTYPE) copies."""
+    d = scene.desc
+    tri = np.zeros(d.numTriangles, dtype=TRIANGLE_DTYPE)
+    sph = np.zeros(d.numSpheres, dtype=SPHERE_DTYPE)
+    if d.numTriangles:
+        C.memmove(tri.ctypes.data, d.triangles, tri.nbytes)
+    if d.numSpheres:
+        C.memmove(sph.ctypes.data, d.spheres, sph.nbytes)
+    return tri, sph
+
+
+def _surface_points(points):
+    a = np.asarray(points)
+    if a.dtype != SURFACE_POINT_DTYPE:
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("points: (P,) SURFACE_POINT_DTYPE or (P, 4) uint32")
+        return a
+    return np.ascontiguousarray(a).view(np.uint32).reshape(-1, 4)
+
+
+def _surface_buffers(points, rng, index, rays, surfels):
+    """The buffers of a generate_rays_surface call as plain rows: [points, streams (a copy), rays, index or None, surfels or None]."""
+    pts, s = _surface_points(points), _rng_words(rng)
+    n = len(s)
+    idx = _film_index(index, n)
+    out = np.zeros((n, 8), dtype=np.float32) if rays is None else _rows(rays, RAY_DTYPE, 8, np.float32, "rays", copy=True)
+    sur = None
+    if surfels is True:
+        sur = np.zeros((n, 12), dtype=np.float32)
+    elif surfels is not None and surfels is not False:
+        sur = _rows(surfels, HIT_DTYPE, 12, np.float32, "surfels", copy=True)
+    if len(out) != n or (sur is not None and len(sur) != n):
+        raise ValueError("rays and surfels: one row per stream")
+    return [pts, s, out, idx, sur]
+
+
+def probe_surface_rays(triangles, spheres, points, rng, params=None, first_point=0, index=None, rays=None, surfels=None):
+    """ptss_generate_rays_surface on the host (csrc/ptsurface.h; the specification of the device's rays) over the caller's own records.
+    triangles: (T,) TRIANGLE_DTYPE or None; spheres: (S,) SPHERE_DTYPE or None; points: (P,) SURFACE_POINT_DTYPE; rng: (N,) PATH_RNG_DTYPE
+    or (N, 6) uint32 -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE: the streams afterwards, (N,) HIT_DTYPE or None, entries rejected).
+    rays / surfels: the buffers' content beforehand (surfels=True: zeros; None: no surfels): a rejected entry keeps it."""
+    params = params if params is not None else surface_params()
+    tri = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1) if triangles is not None else np.zeros(0, dtype=TRIANGLE_DTYPE)
+    sph = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1) if spheres is not None else np.zeros(0, dtype=SPHERE_DTYPE)
+    pts, s, out, idx, sur = _surface_buffers(points, rng, index, rays, surfels)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    rejected = C.c_ulonglong(0)
+    rc = host_lib().ptss_probe_surface_rays(ptr(tri), len(tri), ptr(sph), len(sph), C.byref(params), ptr(pts), len(pts), int(first_point), ptr(idx),
+                                            len(s), ptr(s), ptr(out), ptr(sur), C.byref(rejected))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_surface_rays: {rc}")
+    return _records(out, RAY_DTYPE), _records(s, PATH_RNG_DTYPE), _records(sur, HIT_DTYPE), int(rejected.value)
+
+
+def surface_atlas(triangles, texels_per_unit, width, min_side=1, max_side=64, first=0, count=None, fill=True):
+    """ptss_surface_atlas (host only): the texels of a light map over triangles[first : first + count] -> ((K,) SURFACE_POINT_DTYPE, (K,)
+    uint32 texel numbers y * width + x, the atlas height); with fill=False only (K, height): the count-only call."""
+    tri = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1)
+    count = len(tri) - int(first) if count is None else int(count)
+    if int(first) < 0 or count < 0 or int(first) + count > len(tri):
+        raise ValueError("first + count leaves the triangles")
+    height, made = C.c_int(0), C.c_size_t(0)
+    args = (tri.ctypes.data_as(C.c_void_p) if len(tri) else None, int(first), count, float(texels_per_unit), int(min_side), int(max_side), int(width))
+    rc = host_lib().ptss_surface_atlas(*args, None, None, 0, C.byref(height), C.byref(made))
+    if rc != 0:
+        raise PtssError(f"ptss_surface_atlas: {rc}")
+    if not fill:
+        return int(made.value), int(height.value)
+    points, texels = np.zeros(made.value, dtype=SURFACE_POINT_DTYPE), np.zeros(made.value, dtype=np.uint32)
+    if made.value:
+        rc = host_lib().ptss_surface_atlas(*args, points.ctypes.data_as(C.c_void_p), texels.ctypes.data_as(C.c_void_p), len(points), C.byref(height),
+                                           C.byref(made))
+        if rc != 0 or made.value != len(points):
+            raise PtssError(f"ptss_surface_atlas: {rc}")
+    return points, texels, int(height.value)
+
+
+def _dilate_film(film, width, height):
+    f = _rows(film, LINEAR_DTYPE, 4, np.uint64, "film")
+    if int(width) <= 0 or int(height) <= 0 or len(f) != int(width) * int(height):
+        raise ValueError("film: width * height entries, both sides positive")
+    return f
+
+
+def probe_dilate_linear(film, width, height):
+    """ptss_dilate_linear on the host: one gutter-fill pass over a (width * height,) LINEAR_DTYPE film -> the second film."""
+    f = _dilate_film(film, width, height)
+    out = np.zeros_like(f)
+    rc = host_lib().ptss_probe_dilate_linear(f.ctypes.data_as(C.c_void_p), int(width), int(height), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_dilate_linear: {rc}")
+    return out.view(LINEAR_DTYPE).reshape(-1)
 
 
 def default_denoise_params(**overrides):
@@ -2570,6 +2694,51 @@ class Renderer:
         """ptss_debug_upsample_linear_form (tests and measurements): 0 the form measured faster at each factor, 1 every tap from global
         memory, 2 the lo pixels of a tile divided once and staged in LDS. The bytes are the same."""
         _check(device_lib().ptss_debug_upsample_linear_form(self._ctx, int(form)))
+
+    # --- rays from surface points and the gutter fill (ptss_generate_rays_surface / ptss_dilate_linear; DESIGN.md §3.38) ------------------
+    def generate_rays_surface(self, points, rng, params=None, first_point=0, index=None, rays=None, surfels=None):
+        """ptss_generate_rays_surface: ray i leaves from points[index[i]] (points[first_point + i] without an index) with stream rng[i].
+        numpy: points (P,) SURFACE_POINT_DTYPE, rng (N,) PATH_RNG_DTYPE or (N, 6) uint32 -> ((N,) RAY_DTYPE, (N,) PATH_RNG_DTYPE: the
+        streams afterwards, (N,) HIT_DTYPE surfels or None). rays / surfels: the buffers' content beforehand (zeros otherwise; surfels
+        None: dev_surfels NULL, True: zeros): a rejected entry keeps it.
+        torch: points a contiguous (P, 4) int32 device tensor, rng (N, 6) int32 UPDATED IN PLACE, index (N,) int32 or None, rays an
+        (N, 8) float32 tensor to write (a new one otherwise), surfels an (N, 12) float32 tensor to write or None -> rays, on the
+        current stream."""
+        L = device_lib()
+        params = params if params is not None else surface_params()
+        first_point = int(first_point)
+        bufs = [("points", points, "int32", 4, None, None), ("rng", rng, "int32", 6, None, None), ("rays", rays, "float32", 8, "rng", "zeros"),
+                ("index", index, "int32", 0, "rng", "null"), ("surfels", surfels, "float32", 12, "rng", "null")]
+        return self._device_call(
+            bufs, lambda d, n, stream: L.ptss_generate_rays_surface(self._ctx, C.byref(params), d[0], n["points"], first_point, d[3], n["rng"], d[1],
+                                                                    d[2], d[4], stream),
+            lambda: _surface_buffers(points, rng, index, rays, surfels), read=(1, 2, 4), null=lambda n: n["rng"] == 0,
+            result=lambda a: (_records(a[2], RAY_DTYPE), _records(a[1], PATH_RNG_DTYPE), _records(a[4], HIT_DTYPE)), primary=1, returns="rays")
+
+    def dilate_linear(self, film, width, height, out=None):
+        """ptss_dilate_linear: one gutter-fill pass over a width x height linear film. numpy: film (P,) LINEAR_DTYPE or (P, 4) uint64 ->
+        the second film, (P,) LINEAR_DTYPE. torch: film (P, 4) int64, out a (P, 4) int64 device tensor to write (a new one otherwise)
+        -> out, on the current stream."""
+        L = device_lib()
+        P = int(width) * int(height)
+        return self._device_call(
+            [("film", film, "int64", 4, P, None), ("out", out, "int64", 4, P, "empty")],
+            lambda d, n, stream: L.ptss_dilate_linear(self._ctx, d[0], int(width), int(height), d[1], stream),
+            lambda: [_dilate_film(film, width, height), np.zeros((P, 4), dtype=np.uint64)], read=(1,),
+            result=lambda a: _records(a[1], LINEAR_DTYPE), returns="out")
+
+    def surface_launches(self):
+        """ptss_surface_launches: (generate_rays_surface, dilate_linear calls that launched since the context was created)."""
+        return self._counters("ptss_surface_launches", 2)
+
+    def surface_rejected(self):
+        """ptss_surface_rejected: the entries generate_rays_surface dropped since the context was created (synchronises)."""
+        return self._counters("ptss_surface_rejected", 1)
+
+    def debug_dilate_linear_form(self, form):
+        """ptss_debug_dilate_linear_form (tests and measurements): 0 the shipped form, 1 the nine rows from global memory, 2 a tile with
+        its ring staged in LDS. The bytes are the same."""
+        _check(device_lib().ptss_debug_dilate_linear_form(self._ctx, int(form)))
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

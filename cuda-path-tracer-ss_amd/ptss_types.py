@@ -253,6 +253,20 @@ class ToneParams(C.Structure):   # ptss_tone_params: the curve, the transfer fun
                 ("filmic", C.c_float * 5), ("reserved", C.c_uint)]
 
 
+# rays from surface points (ptss_generate_rays_surface)
+SURFACE_NORMAL, SURFACE_COSINE = 0, 1   # PTSS_SURFACE_NORMAL, PTSS_SURFACE_COSINE
+SURFACE_BACK = 1                        # PTSS_SURFACE_BACK
+SURFACE_TRIANGLE = 0x40000000           # PTSS_SURFACE_TRIANGLE
+
+
+class SurfaceParams(C.Structure):   # ptss_surface_params
+    _fields_ = [("structSize", C.c_uint), ("mode", C.c_int), ("maxDistance", C.c_float), ("reserved", C.c_uint)]
+
+
+SURFACE_POINT_DTYPE = np.dtype([("surface", np.int32), ("a", np.float32), ("b", np.float32), ("flags", np.uint32)])   # ptss_surface_point
+SPHERE_DTYPE = np.dtype([("position", np.float32, 3), ("radius", np.float32), ("materialIdx", np.int32)])             # ptss_sphere
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

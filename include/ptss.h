@@ -760,6 +760,42 @@ int ptss_resolve_toned(ptss_context* ctx, const void* dev_film, int filmKind /* 
 int ptss_tone_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] table builds, [1] toned resolves */
 int ptss_debug_tone_form(ptss_context* ctx, int form);
 
+/* Light maps and probes on the scene's own surfaces: rays that leave from surface points, made on the device from
+ * the scene image, and the gutter fill of a baked film. With them the chain generate -> trace -> accumulate -> plan -> meter -> resolve
+ * is a baker: the film is indexed by texel number, the index of a round is the texels of its rays. csrc/ptsurface.h has the arithmetic;
+ * its host build (ptss_probe_surface_rays, ptss_probe_dilate_linear) is the specification and the device equals it byte for byte.
+ *
+ * ptss_generate_rays_surface: ray i leaves from point p = dev_index ? dev_index[i] : firstPoint + i of dev_points[0 .. numPoints), with
+ * stream dev_rng[i], which is stored back advanced by the mode's draws (PTSS_SURFACE_NORMAL: none — the stream is neither read nor
+ * written; PTSS_SURFACE_COSINE: two). Several rays may share a point. direction: unit length; origin: the point bumped along its
+ * normal as scatter() bumps a Lambert ray; tmax = params->maxDistance; pad = 0. dev_surfels[i], when given, is the ptss_ray_hit a ray
+ * arriving at the point would report: point, distance 0, the unit normal on the side the flags name, materialIdx, kind, primitive,
+ * w1 = a and w2 = b (0 for spheres). The geometry is read from the scene image in use (ptss_update_triangles, ptss_resort_triangles and
+ * ptss_set_scene are seen; the caller orders the calls on their streams as those calls ask).
+ * An entry is REJECTED — no row written, the stream left as it is, counted (ptss_surface_rejected, which synchronises with the stream
+ * of the latest call) — when its index is at or above numPoints, its surface is negative or names a primitive the scene does not hold,
+ * a and b are outside the primitive (ptss_types.h), or a reserved flag bit is set.
+ *
+ * ptss_dilate_linear: one gutter-fill pass over a width x height linear film into dev_out, which must not be dev_film: a texel with
+ * samples is copied; an empty one receives the field-by-field integer sum of its up to eight neighbours that hold samples — their
+ * sample-weighted mean, an ordinary film row — or stays all zero. Repeat the pass for wider gutters.
+ *
+ * Both are asynchronous on hipStream (NULL: the context's), read the scene image at most, leave no frame state, serve any shard and own
+ * no bit of ptss_launched_kernels. n = 0 returns PTSS_OK. Refused before the device is touched, nothing counted: PTSS_EINVAL a null
+ * context, a null required pointer, a wrong structSize, an unknown mode, a non-zero reserved, a maxDistance that is not positive, a
+ * pointer that is not aligned (16 bytes for points, rays, surfels and films, 4 for streams and indices), dev_out == dev_film;
+ * PTSS_ERANGE n >= 2^31, numPoints >= 2^31, width or height below 1 or width * height >= 2^31, firstPoint + n beyond numPoints without
+ * an index.
+ * ptss_debug_dilate_linear_form (tests and measurements): 0 the shipped form, 1 the nine rows from global memory, 2 a 32 x 8 tile with
+ * a ring of one staged in LDS. The bytes are the same. */
+int ptss_generate_rays_surface(ptss_context* ctx, const ptss_surface_params* params, const ptss_surface_point* dev_points, size_t numPoints,
+                               size_t firstPoint, const uint32_t* dev_index /* may be NULL */, size_t n, ptss_path_rng* dev_rng /* in/out */,
+                               ptss_ray_query* dev_rays, ptss_ray_hit* dev_surfels /* may be NULL */, void* hipStream);
+int ptss_dilate_linear(ptss_context* ctx, const ptss_linear_entry* dev_film, int width, int height, ptss_linear_entry* dev_out, void* hipStream);
+int ptss_surface_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] generate, [1] dilate calls that launched */
+int ptss_surface_rejected(ptss_context* ctx, unsigned long long* out);
+int ptss_debug_dilate_linear_form(ptss_context* ctx, int form);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

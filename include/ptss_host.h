@@ -328,6 +328,30 @@ int ptss_probe_upsample_linear(const void* film_lo, int filmKind, int width, int
                                const ptss_pixel_feature* features_hi, const ptss_linear_params* film, const ptss_upsample_linear_params* params,
                                ptss_linear_entry* film_hi, ptss_upsample_linear_info* info);
 
+/* Rays from surface points and the gutter fill on the host (csrc/ptsurface.h — the very operations the kernels evaluate; this build is
+ * the specification). ptss_probe_surface_rays: ptss_generate_rays_surface over the caller's own records — e1 = v1 - v0
+ * and e2 = v2 - v0 and radius * radius formed as the packer forms them — with the same remaining arguments and outputs; *rejected (may
+ * be NULL) is SET to the entries dropped. ptss_probe_dilate_linear: ptss_dilate_linear as a straight loop. PTSS_HOST_EINVAL /
+ * PTSS_HOST_ERANGE: whatever the device calls refuse with PTSS_EINVAL / PTSS_ERANGE, alignment aside.
+ *
+ * ptss_surface_atlas (host only; a convenience, not a kernel): the texels of a light map over triangles[first .. first + count).
+ * Triangle t gets a square block of side s = clamp(ceil(longestEdge * texelsPerUnit), minSide, maxSide) (a longest edge that is not a
+ * number gives minSide); the blocks are shelf-packed left to right in the caller's order into atlasWidth columns with one empty texel
+ * between blocks and between shelves; the texels (i, j) of a block with i + j <= s - 1 each get one surface point strictly inside
+ * the triangle, a = (3 i + 1) / (3 s), b = (3 j + 1) / (3 s) — the centroid of the texel's lower-left half, so a + b <= 1 - 1 / (3 s).
+ * points[k] / texels[k] (each may be NULL: count only; capacity entries at most are written): the point and the number
+ * y * atlasWidth + x of its texel, in the caller's triangle order, rows of a block bottom up. *atlasHeight (may be NULL): the rows
+ * used; *numPoints: the points there are, whatever the capacity. PTSS_HOST_EINVAL: null triangles with count > 0, a null numPoints,
+ * texelsPerUnit not a positive finite number, minSide < 1, maxSide < minSide, maxSide > 4096 or maxSide > atlasWidth; PTSS_HOST_ERANGE:
+ * first + count at or above 2^30 (the surface encoding), an atlas of 2^31 texels or more. */
+int ptss_probe_surface_rays(const ptss_triangle* triangles, size_t numTriangles, const ptss_sphere* spheres, size_t numSpheres,
+                            const ptss_surface_params* params, const ptss_surface_point* points, size_t numPoints, size_t firstPoint,
+                            const uint32_t* index /* may be NULL */, size_t n, ptss_path_rng* rng, ptss_ray_query* rays,
+                            ptss_ray_hit* surfels /* may be NULL */, unsigned long long* rejected);
+int ptss_probe_dilate_linear(const ptss_linear_entry* film, int width, int height, ptss_linear_entry* out);
+int ptss_surface_atlas(const ptss_triangle* triangles, size_t first, size_t count, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
+                       ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints);
+
 #ifdef __cplusplus
 }
 #endif

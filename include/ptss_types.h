@@ -450,6 +450,30 @@ typedef struct ptss_tone_params {
     unsigned int reserved;   /* 0 */
 } ptss_tone_params;
 
+/* Rays from points on the scene's own surfaces (ptss_generate_rays_surface; csrc/ptsurface.h): a light-map texel, a
+ * probe on a wall. surface: ptss_pixel_motion::surface's encoding — sphere k is k, triangle t is PTSS_SURFACE_TRIANGLE | t, both the
+ * caller's indices. a, b: on a triangle the weights w1, w2 of a ptss_ray_hit (a >= 0, b >= 0, a + b <= 1 as float32 rounds the sum); on
+ * a sphere unit fractions of longitude and latitude as on an equirect film (both in [0, 1]). flags: PTSS_SURFACE_BACK — the ray leaves
+ * from the other side (the normal negated); every other bit 0. 16 B, 16-byte aligned access. */
+#define PTSS_SURFACE_BACK 1u
+typedef struct ptss_surface_point {
+    int surface;
+    float a, b;
+    uint32_t flags;
+} ptss_surface_point;
+
+/* How ptss_generate_rays_surface makes the ray of a point. PTSS_SURFACE_NORMAL: along the normal, no draw; PTSS_SURFACE_COSINE: two
+ * draws from the ray's stream, cosine-weighted about the normal (the reference's Lambert sampler). maxDistance > 0, +inf allowed: every
+ * ray's tmax (ptss_trace_paths ignores it; with ptss_occluded a finite one makes ambient-occlusion rays). */
+#define PTSS_SURFACE_NORMAL 0
+#define PTSS_SURFACE_COSINE 1
+typedef struct ptss_surface_params {
+    unsigned int structSize; /* sizeof(ptss_surface_params) as the caller compiled it */
+    int mode;                /* PTSS_SURFACE_NORMAL or PTSS_SURFACE_COSINE */
+    float maxDistance;       /* > 0 */
+    unsigned int reserved;   /* 0 */
+} ptss_surface_params;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -559,6 +583,12 @@ static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample_
 static_assert(sizeof(ptss_tone_params) == 48 && offsetof(ptss_tone_params, curve) == 4 && offsetof(ptss_tone_params, bits) == 12 &&
                   offsetof(ptss_tone_params, white) == 20 && offsetof(ptss_tone_params, filmic) == 24 && offsetof(ptss_tone_params, reserved) == 44,
               "ptss_tone_params is twelve 32-bit words");
+static_assert(sizeof(ptss_surface_point) == 16 && offsetof(ptss_surface_point, a) == 4 && offsetof(ptss_surface_point, b) == 8 &&
+                  offsetof(ptss_surface_point, flags) == 12,
+              "ptss_surface_point is one 16-byte row");
+static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params, mode) == 4 && offsetof(ptss_surface_params, maxDistance) == 8 &&
+                  offsetof(ptss_surface_params, reserved) == 12,
+              "ptss_surface_params is four 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -636,6 +666,12 @@ _Static_assert(sizeof(ptss_upsample_linear_info) == 24 && offsetof(ptss_upsample
 _Static_assert(sizeof(ptss_tone_params) == 48 && offsetof(ptss_tone_params, curve) == 4 && offsetof(ptss_tone_params, bits) == 12 &&
                    offsetof(ptss_tone_params, white) == 20 && offsetof(ptss_tone_params, filmic) == 24 && offsetof(ptss_tone_params, reserved) == 44,
                "ptss_tone_params is twelve 32-bit words");
+_Static_assert(sizeof(ptss_surface_point) == 16 && offsetof(ptss_surface_point, a) == 4 && offsetof(ptss_surface_point, b) == 8 &&
+                   offsetof(ptss_surface_point, flags) == 12,
+               "ptss_surface_point is one 16-byte row");
+_Static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params, mode) == 4 && offsetof(ptss_surface_params, maxDistance) == 8 &&
+                   offsetof(ptss_surface_params, reserved) == 12,
+               "ptss_surface_params is four 32-bit words");
 #endif
 
 #ifdef __cplusplus
