@@ -34,6 +34,7 @@
 #include "ptlinrp.h"
 #include "ptlinup.h"
 #include "ptsurface.h"
+#include "ptlightmap.h"
 
 using namespace ptv;
 using ptpack::cameraInRange;
@@ -179,6 +180,8 @@ struct ptss_context {
     hipStream_t surfaceStream = nullptr;                      // the stream of the latest ptss_generate_rays_surface (ptss_surface_rejected synchronises on it)
     bool surfaceCounted = false;
     int dilateForm = 0;                                       // ptss_debug_dilate_linear_form: 0 the shipped form, 1 global memory, 2 staged
+    unsigned long long lightmapLaunches = 0;                  // ptss_lookup_lightmap calls that launched
+    int lightmapForm = 0;                                     // ptss_debug_lightmap_form: 0 the shipped form, 1 one lane per hit, 2 four lanes per hit
     int toneForm = 0;                                         // ptss_debug_tone_form: 0 the shipped lookup, 1 staged in LDS, 2 guess and settle
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
     hipStream_t splatStream = nullptr;                        // the stream of the latest splat (ptss_splat_stats synchronises on it)
@@ -1990,6 +1993,53 @@ int ptss_debug_dilate_linear_form(ptss_context* c, int form) {
     if (!c) return fail(PTSS_EINVAL, "ctx is null");
     if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
     c->dilateForm = form;
+    return PTSS_OK;
+}
+
+// ---- reading a baked light map back (ptss_lightmap.hip; csrc/ptlightmap.h). images[0]'s materials at most, no frame state, the caller's stream ----
+int ptss_default_lightmap_params(ptss_lightmap_params* p) {
+    if (!p) return fail(PTSS_EINVAL, "params is null");
+    *p = ptss_lightmap_params{};
+    p->structSize = (unsigned int)sizeof(*p);
+    p->atlasWidth = p->atlasHeight = 1;
+    p->filter = PTSS_LIGHTMAP_BILINEAR;
+    return PTSS_OK;
+}
+
+int ptss_lookup_lightmap(ptss_context* c, const ptss_lightmap_params* params, const ptss_linear_params* film, const ptss_surface_block* dev_blocksTri,
+                         const ptss_surface_block* dev_blocksSph, const ptss_linear_entry* dev_map, const ptss_ray_hit* dev_hits, size_t n,
+                         ptss_linear_entry* dev_out, uint32_t* dev_info, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlm::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlin::paramsError(film)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlm::rangeError(params)) return fail(PTSS_ERANGE, what);
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_map || !dev_hits || !dev_out || (params->numTriangleBlocks > 0 && !dev_blocksTri) || (params->numSphereBlocks > 0 && !dev_blocksSph))
+        return fail(PTSS_EINVAL, kNullBuffer);
+    if ((((uintptr_t)dev_blocksTri | (uintptr_t)dev_blocksSph | (uintptr_t)dev_map | (uintptr_t)dev_hits | (uintptr_t)dev_out) & 15u) ||
+        ((uintptr_t)dev_info & 3u))
+        return fail(PTSS_EINVAL, "blocks, map, hits and out must be 16-byte aligned, dev_info 4-byte aligned");
+    if (ptlrp::rangesOverlap(dev_out, 32 * n, dev_map, 32 * (size_t)params->atlasWidth * (size_t)params->atlasHeight))
+        return fail(PTSS_EINVAL, "dev_out overlaps dev_map");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchLookupLightmap(streamOf(c, hipStream), im.dBlob, im.layout, *params, *film, dev_blocksTri, dev_blocksSph, dev_map, dev_hits,
+                                       (uint32_t)n, c->lightmapForm, dev_out, dev_info, &c->lightmapLaunches));
+    return PTSS_OK;
+}
+
+int ptss_lightmap_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->lightmapLaunches;
+    return PTSS_OK;
+}
+
+int ptss_debug_lightmap_form(ptss_context* c, int form) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (form < 0 || form > 2) return fail(PTSS_EINVAL, "form must be 0, 1 or 2");
+    c->lightmapForm = form;
     return PTSS_OK;
 }
 

@@ -315,6 +315,13 @@ hipError_t launchSurfaceRays(hipStream_t st, const float4* sceneBlob, const Scen
 // one gutter-fill pass over a linear film (ptss_surface.hip; ptss_dilate_linear). film and out: width x height entries of 32 B, not the
 // same buffer. form: 0 the shipped one, 1 from global memory, 2 staged in LDS. Sides checked by the caller (ptsurf::dilateSidesError)
 hipError_t launchDilateLinear(hipStream_t st, const void* film, int width, int height, int form, void* out, unsigned long long* launches);
+// hits -> film rows through a baked light map (ptss_lightmap.hip; ptss_lookup_lightmap). blocksTri / blocksSph: rows of 16 B
+// (null with a count of 0 in params); map: atlasWidth x atlasHeight entries of 32 B; hits: n rows of 48 B; out: n entries of 32 B; info
+// (may be null): four uint32 counts, added to. form: 0 the shipped one, 1 one lane per hit, 2 four lanes per hit. Everything checked by
+// the caller (ptlm::paramsError, rangeError); the kernel holds every table row and index against params and the image's counts
+hipError_t launchLookupLightmap(hipStream_t st, const float4* sceneBlob, const SceneLayout& layout, const ptss_lightmap_params& params,
+                                const ptss_linear_params& film, const void* blocksTri, const void* blocksSph, const void* map, const void* hits,
+                                uint32_t n, int form, void* out, void* info, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

@@ -169,34 +169,65 @@ PTM_HD Texel dilateTexel(int x, int y, int width, int height, At at) {
     return o;
 }
 
-// ---- the atlas (host only: ptss_surface_atlas, ptss_main --bake) ----
+// ---- the atlas (host only: ptss_surface_atlas, ptss_surface_atlas_blocks, ptss_main --bake) ----
 // The texels of a light map over triangles[first .. first + count): triangle t gets a square block of side s = clamp(ceil(longestEdge
 // * texelsPerUnit), minSide, maxSide) (a product that is not a number: minSide); blocks are shelf-packed left to right in the caller's
 // order into atlasWidth columns, one empty texel between blocks and between shelves; the texels (i, j) of a block with i + j <= s - 1
 // each get the point a = (3 i + 1) / (3 s), b = (3 j + 1) / (3 s): one float division each, a + b <= 1 - 1 / (3 s) before rounding and
 // s <= 4096, so the rounded sum stays below 1. Returns 0, -1 for refused arguments, -3 for a range (PTSS_HOST_EINVAL, PTSS_HOST_ERANGE).
+//
+// atlasBlocks (ptss_surface_atlas_blocks) is the same walk continued over spheres[firstSphere .. firstSphere +
+// numSpheres) on the same shelves: sphere k gets h = clamp(ceil(kPi * radius * texelsPerUnit), minSide, maxSide) rows (two products, left
+// to right; not a number: minSide) and w = 2 h columns, and EVERY texel (i, j) of the block the point {k, a = (i + 0.5) / w,
+// b = (j + 0.5) / h, 0} — sphereSurfel's longitude and latitude fractions, one float sum and one float division each — rows bottom up,
+// after all triangle points. It also says where each block lies (ptss_surface_block; a primitive always gets one here, width >= 1).
+// Refused beyond atlas' list: null spheres with numSpheres > 0 and 2 * maxSide > atlasWidth when numSpheres > 0 (-1); firstSphere +
+// numSpheres at or above 2^30 (-3).
 #if !defined(__HIP_DEVICE_COMPILE__)
-inline int atlas(const ptss_triangle* triangles, size_t first, size_t count, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
-                 ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints) {
-    if (!numPoints || (count > 0 && !triangles)) return -1;
-    if (!(texelsPerUnit > 0.0f && texelsPerUnit < ptm::inf())) return -1;
-    if (minSide < 1 || maxSide < minSide || maxSide > 4096 || maxSide > atlasWidth) return -1;
-    if (first >= ((size_t)1 << 30) || count > ((size_t)1 << 30) - first) return -3;
+inline int sideOf(float want, int minSide, int maxSide) {
+    int s = minSide;
+    if (want >= (float)maxSide) s = maxSide;
+    else if (want > (float)minSide) s = (int)__builtin_ceilf(want);
+    return s;
+}
+
+struct Shelves {   // the shelf walk: where the next block goes
+    unsigned long long atlasWidth;
     unsigned long long x0 = 0, y0 = 0, shelf = 0;   // the next block's corner and the tallest block of the current shelf
-    size_t made = 0;
-    for (size_t k = 0; k < count; ++k) {
-        const ptss_triangle& t = triangles[first + k];
-        const float e01 = length(t.vertex1 - t.vertex0), e02 = length(t.vertex2 - t.vertex0), e12 = length(t.vertex2 - t.vertex1);
-        const float want = ptm::max(ptm::max(e01, e02), e12) * texelsPerUnit;
-        int s = minSide;
-        if (want >= (float)maxSide) s = maxSide;
-        else if (want > (float)minSide) s = (int)__builtin_ceilf(want);
-        if (x0 + (unsigned long long)s > (unsigned long long)atlasWidth) {   // a new shelf, one empty row above the old one
+    // the corner of a block of w x h texels, w <= atlasWidth; false: the atlas would reach 2^31 texels
+    bool place(int w, int h, unsigned long long* bx, unsigned long long* by) {
+        if (x0 + (unsigned long long)w > atlasWidth) {   // a new shelf, one empty row above the old one
             y0 += shelf + 1;
             x0 = 0;
             shelf = 0;
         }
-        if ((y0 + (unsigned long long)s) * (unsigned long long)atlasWidth >= (1ull << 31)) return -3;
+        if ((y0 + (unsigned long long)h) * atlasWidth >= (1ull << 31)) return false;
+        *bx = x0;
+        *by = y0;
+        if ((unsigned long long)h > shelf) shelf = (unsigned long long)h;
+        x0 += (unsigned long long)w + 1;
+        return true;
+    }
+};
+
+inline int atlasBlocks(const ptss_triangle* triangles, size_t first, size_t count, const ptss_sphere* spheres, size_t firstSphere, size_t numSpheres,
+                       float texelsPerUnit, int minSide, int maxSide, int atlasWidth, ptss_surface_block* blocksTri, ptss_surface_block* blocksSph,
+                       ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints) {
+    if (!numPoints || (count > 0 && !triangles) || (numSpheres > 0 && !spheres)) return -1;
+    if (!(texelsPerUnit > 0.0f && texelsPerUnit < ptm::inf())) return -1;
+    if (minSide < 1 || maxSide < minSide || maxSide > 4096 || maxSide > atlasWidth) return -1;
+    if (numSpheres > 0 && 2 * maxSide > atlasWidth) return -1;
+    if (first >= ((size_t)1 << 30) || count > ((size_t)1 << 30) - first) return -3;
+    if (firstSphere >= ((size_t)1 << 30) || numSpheres > ((size_t)1 << 30) - firstSphere) return -3;
+    Shelves shelves{(unsigned long long)atlasWidth};
+    unsigned long long x0, y0;
+    size_t made = 0;
+    for (size_t k = 0; k < count; ++k) {
+        const ptss_triangle& t = triangles[first + k];
+        const float e01 = length(t.vertex1 - t.vertex0), e02 = length(t.vertex2 - t.vertex0), e12 = length(t.vertex2 - t.vertex1);
+        const int s = sideOf(ptm::max(ptm::max(e01, e02), e12) * texelsPerUnit, minSide, maxSide);
+        if (!shelves.place(s, s, &x0, &y0)) return -3;
+        if (blocksTri) blocksTri[k] = ptss_surface_block{(int)x0, (int)y0, s, s};
         for (int j = 0; j < s; ++j)
             for (int i = 0; i + j <= s - 1; ++i, ++made) {
                 if (made >= capacity) continue;
@@ -205,12 +236,27 @@ inline int atlas(const ptss_triangle* triangles, size_t first, size_t count, flo
                                                       (float)(3 * j + 1) / (float)(3 * s), 0u};
                 if (texels) texels[made] = (uint32_t)((y0 + (unsigned long long)j) * (unsigned long long)atlasWidth + x0 + (unsigned long long)i);
             }
-        if ((unsigned long long)s > shelf) shelf = (unsigned long long)s;
-        x0 += (unsigned long long)s + 1;
     }
-    if (atlasHeight) *atlasHeight = (int)(y0 + shelf);
+    for (size_t k = 0; k < numSpheres; ++k) {
+        const int h = sideOf(ptm::kPi * spheres[firstSphere + k].radius * texelsPerUnit, minSide, maxSide), w = 2 * h;
+        if (!shelves.place(w, h, &x0, &y0)) return -3;
+        if (blocksSph) blocksSph[k] = ptss_surface_block{(int)x0, (int)y0, w, h};
+        for (int j = 0; j < h; ++j)
+            for (int i = 0; i < w; ++i, ++made) {
+                if (made >= capacity) continue;
+                if (points) points[made] = ptss_surface_point{(int)(firstSphere + k), ((float)i + 0.5f) / (float)w, ((float)j + 0.5f) / (float)h, 0u};
+                if (texels) texels[made] = (uint32_t)((y0 + (unsigned long long)j) * (unsigned long long)atlasWidth + x0 + (unsigned long long)i);
+            }
+    }
+    if (atlasHeight) *atlasHeight = (int)(shelves.y0 + shelves.shelf);
     *numPoints = made;
     return 0;
+}
+
+inline int atlas(const ptss_triangle* triangles, size_t first, size_t count, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
+                 ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints) {
+    return atlasBlocks(triangles, first, count, nullptr, 0, 0, texelsPerUnit, minSide, maxSide, atlasWidth, nullptr, nullptr, points, texels, capacity,
+                       atlasHeight, numPoints);
 }
 #endif
 

@@ -25,6 +25,7 @@
 #include "ptmotion.h"
 #include "ptspecular.h"
 #include "ptsurface.h"
+#include "ptlightmap.h"
 #include "ptquant.h"
 #include "ptlocate.h"
 #include "ptmesh.h"
@@ -1301,6 +1302,41 @@ int ptss_surface_atlas(const ptss_triangle* triangles, size_t first, size_t coun
                        ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints) {
     static_assert(PTSS_HOST_EINVAL == -1 && PTSS_HOST_ERANGE == -3, "ptsurf::atlas returns these");
     return ptsurf::atlas(triangles, first, count, texelsPerUnit, minSide, maxSide, atlasWidth, points, texels, capacity, atlasHeight, numPoints);
+}
+
+// ---- light maps read back: the blocks of the atlas, the lookup (csrc/ptsurface.h, csrc/ptlightmap.h) ----
+int ptss_surface_atlas_blocks(const ptss_triangle* triangles, size_t firstTriangle, size_t numTriangles, const ptss_sphere* spheres,
+                              size_t firstSphere, size_t numSpheres, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
+                              ptss_surface_block* blocksTri, ptss_surface_block* blocksSph, ptss_surface_point* points, uint32_t* texels,
+                              size_t capacity, int* atlasHeight, size_t* numPoints) {
+    return ptsurf::atlasBlocks(triangles, firstTriangle, numTriangles, spheres, firstSphere, numSpheres, texelsPerUnit, minSide, maxSide, atlasWidth,
+                               blocksTri, blocksSph, points, texels, capacity, atlasHeight, numPoints);
+}
+
+int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+                               const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
+                               const ptss_linear_entry* map, const ptss_ray_hit* hits, size_t n, ptss_linear_entry* out, uint32_t* info) {
+    if (ptlm::paramsError(params) || ptlin::paramsError(film)) return PTSS_HOST_EINVAL;
+    if (ptlm::rangeError(params) || n >= (size_t(1) << 31) || numMaterials >= (size_t(1) << 31)) return PTSS_HOST_ERANGE;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!map || !hits || !out || (params->numTriangleBlocks > 0 && !blocksTri) || (params->numSphereBlocks > 0 && !blocksSph) ||
+        (numMaterials > 0 && !materials))
+        return PTSS_HOST_EINVAL;
+    if (ptlrp::rangesOverlap(out, 32 * n, map, 32 * (size_t)params->atlasWidth * (size_t)params->atlasHeight)) return PTSS_HOST_EINVAL;
+    const ptlm::Rule R = ptlm::ruleOf(*params, *film, (int)numMaterials);
+    auto block = [](const ptss_surface_block* table, int row) { return ptlm::Block{table[row].x, table[row].y, table[row].width, table[row].height}; };
+    auto at = [&](uint32_t texel) { return ptlm::Texel{map[texel].r, map[texel].g, map[texel].b, map[texel].samples}; };
+    auto material = [&](int idx, int row) { return row == 0 ? materials[idx].diffuseColor : materials[idx].emmitance; };
+    for (size_t i = 0; i < n; ++i) {
+        const ptss_ray_hit& g = hits[i];
+        const ptlm::Hit h{g.normal, g.materialIdx, g.kind, g.primitive, g.w1, g.w2};
+        ptlm::u64 m[3];
+        const int verdict = ptlm::lookup(
+            h, R, [&](int row) { return block(blocksTri, row); }, [&](int row) { return block(blocksSph, row); }, at, material, m);
+        out[i] = ptss_linear_entry{m[0], m[1], m[2], verdict == ptlm::kFiltered ? 1u : 0u, 0u};
+        if (info) ++info[verdict];
+    }
+    return PTSS_HOST_OK;
 }
 
 }  // extern "C"

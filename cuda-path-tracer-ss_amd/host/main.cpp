@@ -78,6 +78,12 @@
 //                                   ptss_trace_paths -> ptss_accumulate_paths_linear indexed by texel, `passes` (default 1) of ptss_dilate_linear,
 //                                   ptss_resolve_linear; writes the linear means to --out (default lightmap.pfm) and prints the atlas size
 //                                   and the rejected count. Not with --film, --temporal, --denoise, --upscale, --pick, --gpus
+//             [--bake-view [nearest|bilinear]]   with --bake: the bake goes through ptss_surface_atlas_blocks, so the spheres
+//                                   get texels too (sides up to --size's width / 2 then); after the gutter fills the camera's centre rays
+//                                   (ptss_generate_rays, jitter 0; --keys move the camera first) -> ptss_intersect -> ptss_lookup_lightmap with
+//                                   modulate and emission (default bilinear) -> ptss_resolve_linear at --size; writes the view's linear means
+//                                   next to the map (<out without .pfm>_view.pfm) and prints the four counts. Without the flag --bake writes
+//                                   exactly what it wrote before
 //             [--upscale-linear F]  with --film and --linear, with or without --filter, --refill, --denoise-linear, --auto-exposure and --glare:
 //                                   the film is traced (and denoised) at the given size and upsampled in linear light to F (1..4) times the
 //                                   size — the features are ptss_ray_features of the centre rays of the same film camera at
@@ -137,6 +143,7 @@ int main(int argc, char* argv[]) {
     bool bake = false;                                // --bake: a light map of the scene's triangles instead of an image
     float bakeTexels = 4.f;                           // ... texels per unit of length, samples per texel, gutter-fill passes
     int bakeSamples = 16, bakePasses = 1;
+    int bakeView = -1;                                // --bake-view: the filter of the camera view looked up from the baked map, -1 none
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -261,6 +268,11 @@ int main(int argc, char* argv[]) {
                 }
             }
         }
+        else if (a == "--bake-view") {
+            bakeView = PTSS_LIGHTMAP_BILINEAR;
+            if (i + 1 < argc && (!strcmp(argv[i + 1], "nearest") || !strcmp(argv[i + 1], "bilinear")))
+                bakeView = !strcmp(next(), "nearest") ? PTSS_LIGHTMAP_NEAREST : PTSS_LIGHTMAP_BILINEAR;
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -329,6 +341,7 @@ int main(int argc, char* argv[]) {
                         "--pick\n");
         return 2;
     }
+    if (bakeView >= 0 && (!bake || height < 1)) { fprintf(stderr, "--bake-view needs --bake\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -397,18 +410,25 @@ int main(int argc, char* argv[]) {
 
     bitmap.set_max_ticks(ticks);
     if (bake) {   // the loop of INTEGRATION.md §2g "Baking": atlas, seed, then per sample generate, trace, accumulate by texel; gutter fills; resolve
-        const int maxSide = width < 64 ? width : 64;
-        size_t K = 0;
-        int atlasH = 0;
+        // with --bake-view the spheres take part (ptss_surface_atlas_blocks); without it the atlas is ptss_surface_atlas' as before
+        const bool view = bakeView >= 0;
         const ptss_triangle* tris = scene.trianglesVec.empty() ? nullptr : scene.trianglesVec.data();
         const size_t T = scene.trianglesVec.size();
-        if (T == 0 || ptsurf::atlas(tris, 0, T, bakeTexels, 1, maxSide, width, nullptr, nullptr, 0, &atlasH, &K) != 0 || K == 0) {
+        const ptss_sphere* sphs = view && !scene.spheresVec.empty() ? scene.spheresVec.data() : nullptr;
+        const size_t S = sphs ? scene.spheresVec.size() : 0;
+        const int maxSide = S > 0 ? (width / 2 < 64 ? width / 2 : 64) : (width < 64 ? width : 64);
+        size_t K = 0;
+        int atlasH = 0;
+        if (T + S == 0 || (!view && T == 0) || maxSide < 1 ||
+            ptsurf::atlasBlocks(tris, 0, T, sphs, 0, S, bakeTexels, 1, maxSide, width, nullptr, nullptr, nullptr, nullptr, 0, &atlasH, &K) != 0 || K == 0) {
             fprintf(stderr, "--bake: the scene has no triangles, or the atlas of %d columns does not fit 2^31 texels\n", width);
             return 2;
         }
         std::vector<ptss_surface_point> points(K);
         std::vector<uint32_t> texels(K);
-        ptsurf::atlas(tris, 0, T, bakeTexels, 1, maxSide, width, points.data(), texels.data(), K, &atlasH, &K);
+        std::vector<ptss_surface_block> blocksTri(T), blocksSph(S);
+        ptsurf::atlasBlocks(tris, 0, T, sphs, 0, S, bakeTexels, 1, maxSide, width, blocksTri.data(), blocksSph.data(), points.data(), texels.data(), K,
+                            &atlasH, &K);
         const size_t P = (size_t)width * (size_t)atlasH;
         void *dPoints = nullptr, *dTexels = nullptr, *dRng = nullptr, *dRays = nullptr, *dRes = nullptr, *dMap[2] = {nullptr, nullptr}, *dMeans = nullptr;
         if (hipMalloc(&dPoints, K * sizeof(ptss_surface_point)) != hipSuccess || hipMalloc(&dTexels, K * sizeof(uint32_t)) != hipSuccess ||
@@ -449,6 +469,60 @@ int main(int argc, char* argv[]) {
         if (!writePfm(name.c_str(), means.data(), width, atlasH)) { fprintf(stderr, "--bake: cannot write %s\n", name.c_str()); return 1; }
         printf("bake: atlas %d x %d, %zu texels of %zu triangles, %d samples, %d passes, rejected %llu\n", width, atlasH, K, T, bakeSamples, bakePasses,
                rejected);
+        if (view) {   // the loop of INTEGRATION.md §2g "Looking a light map up": centre rays, closest hits, the lookup, the resolve
+            for (char k : keys) moveCamera(data->camera, (unsigned char)k);
+            ptss_film_camera fc;
+            memset(&fc, 0, sizeof(fc));
+            fc.structSize = (unsigned int)sizeof(fc);
+            fc.kind = PTSS_FILM_PINHOLE;
+            fc.camera = data->camera;
+            fc.width = width;
+            fc.height = height;
+            fc.focusDistance = 1.f;
+            fc.jitter = 0;
+            ptss_lightmap_params lp;
+            PTSS_HANDLE(ptss_default_lightmap_params(&lp));
+            lp.atlasWidth = width;
+            lp.atlasHeight = atlasH;
+            lp.filter = bakeView;
+            lp.flags = PTSS_LIGHTMAP_MODULATE | PTSS_LIGHTMAP_EMISSION;
+            lp.numTriangleBlocks = (int)T;
+            lp.numSphereBlocks = (int)S;
+            const size_t n = (size_t)width * (size_t)height;
+            void *dBt = nullptr, *dBs = nullptr, *dVRng = nullptr, *dVRays = nullptr, *dHits = nullptr, *dView = nullptr, *dVMeans = nullptr, *dInfo = nullptr;
+            if (hipMalloc(&dBt, (T ? T : 1) * sizeof(ptss_surface_block)) != hipSuccess || hipMalloc(&dBs, (S ? S : 1) * sizeof(ptss_surface_block)) != hipSuccess ||
+                hipMalloc(&dVRng, n * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dVRays, n * sizeof(ptss_ray_query)) != hipSuccess ||
+                hipMalloc(&dHits, n * sizeof(ptss_ray_hit)) != hipSuccess || hipMalloc(&dView, n * sizeof(ptss_linear_entry)) != hipSuccess ||
+                hipMalloc(&dVMeans, n * sizeof(ptss_history_entry)) != hipSuccess || hipMalloc(&dInfo, 4 * sizeof(uint32_t)) != hipSuccess ||
+                hipMemcpy(dBt, blocksTri.data(), T * sizeof(ptss_surface_block), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(dBs, blocksSph.data(), S * sizeof(ptss_surface_block), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemset(dVRng, 0, n * sizeof(ptss_path_rng)) != hipSuccess || hipMemset(dInfo, 0, 4 * sizeof(uint32_t)) != hipSuccess) {
+                fprintf(stderr, "--bake-view: device buffers\n");
+                return 1;
+            }
+            PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dVRng, (ptss_ray_query*)dVRays, NULL));
+            PTSS_HANDLE(ptss_intersect(ctx, (const ptss_ray_query*)dVRays, (ptss_ray_hit*)dHits, n, NULL));
+            PTSS_HANDLE(ptss_lookup_lightmap(ctx, &lp, &linearParams, T ? (const ptss_surface_block*)dBt : NULL, S ? (const ptss_surface_block*)dBs : NULL,
+                                             (const ptss_linear_entry*)dMap[cur], (const ptss_ray_hit*)dHits, n, (ptss_linear_entry*)dView,
+                                             (uint32_t*)dInfo, NULL));
+            PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dView, 0, n, &linearParams, (ptss_history_entry*)dVMeans, NULL, NULL, NULL));
+            PTSS_HANDLE(ptss_synchronize(ctx));
+            std::vector<ptss_history_entry> viewMeans(n);
+            uint32_t info[4];
+            if (hipMemcpy(viewMeans.data(), dVMeans, n * sizeof(ptss_history_entry), hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(info, dInfo, sizeof(info), hipMemcpyDeviceToHost) != hipSuccess) {
+                fprintf(stderr, "--bake-view: read-back\n");
+                return 1;
+            }
+            std::string viewName = name;
+            const size_t dot = viewName.rfind(".pfm");
+            if (dot != std::string::npos && dot + 4 == viewName.size()) viewName.erase(dot);
+            viewName += "_view.pfm";
+            if (!writePfm(viewName.c_str(), viewMeans.data(), width, height)) { fprintf(stderr, "--bake-view: cannot write %s\n", viewName.c_str()); return 1; }
+            printf("bake view: %d x %d, %s, %zu sphere blocks, filtered %u, empty %u, no block %u, rejected %u\n", width, height,
+                   bakeView == PTSS_LIGHTMAP_NEAREST ? "nearest" : "bilinear", S, info[0], info[1], info[2], info[3]);
+            for (void* d : {dBt, dBs, dVRng, dVRays, dHits, dView, dVMeans, dInfo}) (void)hipFree(d);
+        }
         for (void* d : {dPoints, dTexels, dRng, dRays, dRes, dMap[0], dMap[1], dMeans}) (void)hipFree(d);
         PTSS_HANDLE(ptss_destroy(ctx));
         bitmap.free_resources();

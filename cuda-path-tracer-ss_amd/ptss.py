@@ -26,6 +26,8 @@ from ptss_types import DENOISE_LINEAR_EMPTY, DENOISE_LINEAR_WORKSPACE_BYTES, DEN
 from ptss_types import REPROJECT_LINEAR_INFO_DTYPE, REPROJECT_LINEAR_MAX_HISTORY, ReprojectLinearParams
 from ptss_types import UPSAMPLE_LINEAR_INFO_DTYPE, UPSAMPLE_LINEAR_WRAP_X, UpsampleLinearParams
 from ptss_types import SPHERE_DTYPE, SURFACE_BACK, SURFACE_COSINE, SURFACE_NORMAL, SURFACE_POINT_DTYPE, SURFACE_TRIANGLE, SurfaceParams
+from ptss_types import (LIGHTMAP_BILINEAR, LIGHTMAP_EMISSION, LIGHTMAP_MODULATE, LIGHTMAP_NEAREST, MATERIAL_DTYPE, SURFACE_BLOCK_DTYPE,
+                        LightmapParams)
 from ptss_types import TONE_CLAMP, TONE_FILMIC, TONE_LUMINANCE, TONE_REINHARD, TRANSFER_GAMMA22, TRANSFER_SRGB, ToneParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -242,6 +244,11 @@ def host_lib():
         L.ptss_probe_dilate_linear.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.ptss_surface_atlas.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+        L.ptss_surface_atlas_blocks.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_float, C.c_int, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_size_t)]
+        L.ptss_probe_lookup_lightmap.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(LightmapParams), C.POINTER(LinearParams), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         _host = L
     return _host
 
@@ -404,6 +411,10 @@ def device_lib():
         L.ptss_surface_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_surface_rejected.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_dilate_linear_form.argtypes = [vp, C.c_int]
+        L.ptss_default_lightmap_params.argtypes = [C.POINTER(LightmapParams)]
+        L.ptss_lookup_lightmap.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LinearParams), vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+        L.ptss_lightmap_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_debug_lightmap_form.argtypes = [vp, C.c_int]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -1548,6 +1559,115 @@ def probe_dilate_linear(film, width, height):
     if rc != 0:
         raise PtssError(f"ptss_probe_dilate_linear: {rc}")
     return out.view(LINEAR_DTYPE).reshape(-1)
+
+
+# ---- light maps read back: the blocks of the atlas, the lookup (ptss_surface_atlas_blocks / ptss_lookup_lightmap) ----
+_LIGHTMAP_FILTERS = {"nearest": LIGHTMAP_NEAREST, "bilinear": LIGHTMAP_BILINEAR}
+
+
+def surface_atlas_blocks(triangles, spheres, texels_per_unit, width, min_side=1, max_side=64, first_triangle=0, num_triangles=None,
+                         first_sphere=0, num_spheres=None, fill=True):
+    """ptss_surface_atlas_blocks (host only): the atlas of ptss_surface_atlas with its blocks named, continued over spheres -> ((T,)
+    SURFACE_BLOCK_DTYPE, (S,) SURFACE_BLOCK_DTYPE, (K,) SURFACE_POINT_DTYPE, (K,) uint32 texel numbers, the atlas height); with
+    fill=False only (K, height): the count-only call. triangles / spheres: records or None."""
+    tri = np.ascontiguousarray(triangles, dtype=TRIANGLE_DTYPE).reshape(-1) if triangles is not None else np.zeros(0, dtype=TRIANGLE_DTYPE)
+    sph = np.ascontiguousarray(spheres, dtype=SPHERE_DTYPE).reshape(-1) if spheres is not None else np.zeros(0, dtype=SPHERE_DTYPE)
+    T = len(tri) - int(first_triangle) if num_triangles is None else int(num_triangles)
+    S = len(sph) - int(first_sphere) if num_spheres is None else int(num_spheres)
+    if min(int(first_triangle), T, int(first_sphere), S) < 0 or int(first_triangle) + T > len(tri) or int(first_sphere) + S > len(sph):
+        raise ValueError("first + count leaves the triangles or the spheres")
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    height, made = C.c_int(0), C.c_size_t(0)
+    args = (ptr(tri), int(first_triangle), T, ptr(sph), int(first_sphere), S, float(texels_per_unit), int(min_side), int(max_side), int(width))
+    rc = host_lib().ptss_surface_atlas_blocks(*args, None, None, None, None, 0, C.byref(height), C.byref(made))
+    if rc != 0:
+        raise PtssError(f"ptss_surface_atlas_blocks: {rc}")
+    if not fill:
+        return int(made.value), int(height.value)
+    bt, bs = np.zeros(T, dtype=SURFACE_BLOCK_DTYPE), np.zeros(S, dtype=SURFACE_BLOCK_DTYPE)
+    points, texels = np.zeros(made.value, dtype=SURFACE_POINT_DTYPE), np.zeros(made.value, dtype=np.uint32)
+    rc = host_lib().ptss_surface_atlas_blocks(*args, ptr(bt), ptr(bs), ptr(points), ptr(texels), len(points), C.byref(height), C.byref(made))
+    if rc != 0 or made.value != len(points):
+        raise PtssError(f"ptss_surface_atlas_blocks: {rc}")
+    return bt, bs, points, texels, int(height.value)
+
+
+def lightmap_params(atlas_width, atlas_height, filter="bilinear", modulate=False, emission=False, first_triangle=0, num_triangle_blocks=0,
+                    first_sphere=0, num_sphere_blocks=0):
+    """A ptss_lightmap_params. filter: "nearest" / "bilinear" or a PTSS_LIGHTMAP_* value; the table counts are what lookup_lightmap is
+    given (it fills them in from its tables when they are left 0)."""
+    p = LightmapParams()
+    p.structSize = C.sizeof(LightmapParams)
+    p.atlasWidth, p.atlasHeight = int(atlas_width), int(atlas_height)
+    p.filter = _LIGHTMAP_FILTERS.get(filter, filter)
+    p.flags = (LIGHTMAP_MODULATE if modulate else 0) | (LIGHTMAP_EMISSION if emission else 0)
+    p.firstTriangle, p.numTriangleBlocks, p.firstSphere, p.numSphereBlocks = int(first_triangle), int(num_triangle_blocks), int(first_sphere), int(num_sphere_blocks)
+    p.reserved = 0
+    return p
+
+
+def scene_materials(scene):
+    """The materials of a ptss.Scene as an (M,) MATERIAL_DTYPE copy."""
+    d = scene.desc
+    mat = np.zeros(d.numMaterials, dtype=MATERIAL_DTYPE)
+    if d.numMaterials:
+        C.memmove(mat.ctypes.data, d.materials, mat.nbytes)
+    return mat
+
+
+def _lightmap_blocks(blocks):
+    if blocks is None:
+        return None
+    a = np.asarray(blocks)
+    if a.dtype == SURFACE_BLOCK_DTYPE:
+        a = np.ascontiguousarray(a).view(np.int32).reshape(-1, 4)
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("blocks: (N,) SURFACE_BLOCK_DTYPE or (N, 4) int32")
+    return a if len(a) else None
+
+
+def _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info):
+    """The buffers of a lookup_lightmap call as plain rows: [hits, map, triangle blocks or None, sphere blocks or None, out, info or None]."""
+    h = _rows(hits, HIT_DTYPE, 12, np.float32, "hits")
+    m = _rows(map, LINEAR_DTYPE, 4, np.uint64, "map")
+    if len(m) != int(params.atlasWidth) * int(params.atlasHeight):
+        raise ValueError("map: atlasWidth * atlasHeight entries")
+    bt, bs = _lightmap_blocks(blocks_tri), _lightmap_blocks(blocks_sph)
+    if (0 if bt is None else len(bt)) < params.numTriangleBlocks or (0 if bs is None else len(bs)) < params.numSphereBlocks:
+        raise ValueError("blocks: fewer rows than params counts")
+    inf = None if info is False else np.zeros(4, dtype=np.uint32)
+    if info is not None and info is not False:
+        inf[:] = info
+    return [h, m, bt, bs, np.zeros((len(h), 4), dtype=np.uint64), inf]
+
+
+def _lightmap_counts(params, blocks_tri, blocks_sph):
+    """params with table counts left at 0 filled in from the tables given (a copy)."""
+    p = LightmapParams()
+    C.memmove(C.byref(p), C.byref(params), C.sizeof(LightmapParams))
+    if p.numTriangleBlocks == 0 and blocks_tri is not None:
+        p.numTriangleBlocks = len(blocks_tri)
+    if p.numSphereBlocks == 0 and blocks_sph is not None:
+        p.numSphereBlocks = len(blocks_sph)
+    return p
+
+
+def probe_lookup_lightmap(materials, hits, map, params, blocks_tri=None, blocks_sph=None, film=None, info=None):
+    """ptss_lookup_lightmap on the host (csrc/ptlightmap.h; the specification of the device's rows). materials: (M,) MATERIAL_DTYPE, a
+    ptss.Scene or None; hits (N,) HIT_DTYPE; map (W H,) LINEAR_DTYPE -> ((N,) LINEAR_DTYPE, the four counts as (4,) uint32, or None with
+    info=False). info: the counts' content beforehand."""
+    film = film if film is not None else linear_params()
+    params = _lightmap_counts(params, blocks_tri, blocks_sph)
+    mat = scene_materials(materials) if isinstance(materials, Scene) else materials
+    mat = np.ascontiguousarray(mat, dtype=MATERIAL_DTYPE).reshape(-1) if mat is not None else np.zeros(0, dtype=MATERIAL_DTYPE)
+    h, m, bt, bs, out, inf = _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    rc = host_lib().ptss_probe_lookup_lightmap(ptr(mat), len(mat), C.byref(params), C.byref(film), ptr(bt), ptr(bs), ptr(m), ptr(h), len(h), ptr(out),
+                                               ptr(inf))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_lookup_lightmap: {rc}")
+    return out.view(LINEAR_DTYPE).reshape(-1), inf
 
 
 def default_denoise_params(**overrides):
@@ -2739,6 +2859,36 @@ class Renderer:
         """ptss_debug_dilate_linear_form (tests and measurements): 0 the shipped form, 1 the nine rows from global memory, 2 a tile with
         its ring staged in LDS. The bytes are the same."""
         _check(device_lib().ptss_debug_dilate_linear_form(self._ctx, int(form)))
+
+    # --- light maps read back (ptss_lookup_lightmap; DESIGN.md §3.39) ------------------
+    def lookup_lightmap(self, hits, map, params, blocks_tri=None, blocks_sph=None, film=None, info=None, out=None):
+        """ptss_lookup_lightmap: hits -> linear film rows through a baked map. params: a lightmap_params (table counts left at 0 are
+        the tables' lengths); film: the map's linear_params.
+        numpy: hits (N,) HIT_DTYPE, map (W H,) LINEAR_DTYPE, blocks (.,) SURFACE_BLOCK_DTYPE or None -> ((N,) LINEAR_DTYPE, the four
+        counts — filtered, empty, no block, rejected — as (4,) uint32, or None with info=False: dev_info NULL). info: the counts' content
+        beforehand.
+        torch: hits (N, 12) float32, map (W H, 4) int64, blocks (., 4) int32 or None, out an (N, 4) int64 device tensor to write (a new
+        one otherwise), info a (4,) int32 device tensor ADDED TO or None -> out, on the current stream."""
+        L = device_lib()
+        film = film if film is not None else linear_params()
+        params = _lightmap_counts(params, blocks_tri, blocks_sph)
+        P = int(params.atlasWidth) * int(params.atlasHeight)
+        return self._device_call(
+            [("hits", hits, "float32", 12, None, None), ("map", map, "int64", 4, P, None), ("blocks_tri", blocks_tri, "int32", 4, None, "null"),
+             ("blocks_sph", blocks_sph, "int32", 4, None, "null"), ("out", out, "int64", 4, "hits", "empty"),
+             ("info", info if info is not False else None, "int32", 0, 4, "null")],
+            lambda d, n, stream: L.ptss_lookup_lightmap(self._ctx, C.byref(params), C.byref(film), d[2], d[3], d[1], d[0], n["hits"], d[4], d[5], stream),
+            lambda: _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info), read=(4, 5),
+            result=lambda a: (_records(a[4], LINEAR_DTYPE), a[5]), returns="out")
+
+    def lightmap_launches(self):
+        """ptss_lightmap_launches: the lookup_lightmap calls that launched since the context was created."""
+        return self._counters("ptss_lightmap_launches", 1)
+
+    def debug_lightmap_form(self, form):
+        """ptss_debug_lightmap_form (tests and measurements): 0 the shipped form, 1 one lane per hit, 2 four lanes per hit. The bytes are
+        the same."""
+        _check(device_lib().ptss_debug_lightmap_form(self._ctx, int(form)))
 
     # --- the meter of the two linear films (ptss_meter_linear / ptss_meter_splat / ptss_meter_exposure) ------------------
     def _meter(self, call, film_dtype, film, first_pixel, count, histogram):

@@ -267,6 +267,22 @@ SURFACE_POINT_DTYPE = np.dtype([("surface", np.int32), ("a", np.float32), ("b", 
 SPHERE_DTYPE = np.dtype([("position", np.float32, 3), ("radius", np.float32), ("materialIdx", np.int32)])             # ptss_sphere
 
 
+# light maps read back (ptss_surface_atlas_blocks, ptss_lookup_lightmap)
+LIGHTMAP_NEAREST, LIGHTMAP_BILINEAR = 0, 1     # PTSS_LIGHTMAP_NEAREST, PTSS_LIGHTMAP_BILINEAR
+LIGHTMAP_MODULATE, LIGHTMAP_EMISSION = 1, 2    # PTSS_LIGHTMAP_MODULATE, PTSS_LIGHTMAP_EMISSION
+SURFACE_BLOCK_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("width", np.int32), ("height", np.int32)])          # ptss_surface_block
+MATERIAL_DTYPE = np.dtype({"names": ["diffuseColor", "specularColor", "absorption", "emmitance", "specularExponent", "indexOfRefraction",
+                                     "diffAvg", "specAvg", "refrAvg", "roughness", "flags"],
+                           "formats": [(np.float32, 3)] * 4 + [np.float32] * 6 + [np.int8],
+                           "offsets": [0, 12, 24, 36, 48, 52, 56, 60, 64, 68, 72], "itemsize": 76})                           # ptss_material
+
+
+class LightmapParams(C.Structure):   # ptss_lightmap_params
+    _fields_ = [("structSize", C.c_uint), ("atlasWidth", C.c_int), ("atlasHeight", C.c_int), ("filter", C.c_int), ("flags", C.c_uint),
+                ("firstTriangle", C.c_int), ("numTriangleBlocks", C.c_int), ("firstSphere", C.c_int), ("numSphereBlocks", C.c_int),
+                ("reserved", C.c_uint)]
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

@@ -796,6 +796,43 @@ int ptss_surface_launches(const ptss_context* ctx, unsigned long long* out2); /*
 int ptss_surface_rejected(ptss_context* ctx, unsigned long long* out);
 int ptss_debug_dilate_linear_form(ptss_context* ctx, int form);
 
+/* Reading a baked light map back: hits in, ordinary linear film rows out — one closest-hit query per pixel and a
+ * four-tap lookup instead of a path-traced round. dev_hits are whatever the caller has: ptss_intersect of ptss_generate_rays' centre
+ * rays for a camera view, the hits of reflection rays, ptss_generate_rays_surface's surfels. dev_blocksTri / dev_blocksSph are
+ * ptss_surface_atlas_blocks' tables (ptss_host.h) on the device: row k of the triangles belongs to the caller's triangle
+ * params->firstTriangle + k, k < numTriangleBlocks, the spheres alike; dev_map is the baked film of atlasWidth x atlasHeight entries,
+ * before or after ptss_dilate_linear. csrc/ptlightmap.h has the arithmetic and its head comment is the specification; its host build
+ * (ptss_probe_lookup_lightmap) and the device agree byte for byte.
+ *
+ * Per hit: the block of its primitive; the place in it (a triangle's w1, w2; a sphere's longitude and latitude from the hit's normal);
+ * four taps with integer weights in 1/65536 (PTSS_LIGHTMAP_NEAREST: one), columns clamped on a triangle block and wrapped on a sphere
+ * block, rows clamped — no tap leaves its block; the weighted mean m' of the integer means of the taps that hold samples, exact;
+ * PTSS_LIGHTMAP_MODULATE: times the hit's diffuseColor in 1/65536 (the radiance a Lambert surface sends out: the baker's cosine-
+ * weighted mean of the incoming radiance is E / pi); PTSS_LIGHTMAP_EMISSION: plus the hit's emmitance at the film's fixed point.
+ * dev_out[i] = {m'_r, m'_g, m'_b, samples = 1, clamped = 0}, which every consumer of a linear film takes (the meter, the glare build,
+ * ptss_denoise_linear, ptss_upsample_linear, every resolve); all zero for a hit with a block but no tap that holds samples (EMPTY),
+ * without a block (a miss, a primitive outside the tables, a row with width == 0: NO BLOCK), or REJECTED: a kind outside 0..2, a w1, w2
+ * or normal that is not finite, a block row that leaves the atlas (x, y, width or height negative, height 0, x + width > atlasWidth,
+ * y + height > atlasHeight, width > 8192, height > 4096), or, with either flag, a materialIdx the scene image does not hold. Block
+ * rows and hits are device memory and never trusted: no address is formed from a rejected one. All n rows are written.
+ * dev_info (may be NULL): four uint32 counts ADDED to — filtered, empty, no block, rejected; they add up to n.
+ *
+ * Asynchronous on hipStream (NULL: the context's); reads the scene image only for materials; leaves no frame state; owns no bit of
+ * ptss_launched_kernels; counted by ptss_lightmap_launches. n = 0 returns PTSS_OK. Refused before the device is touched, nothing
+ * counted: PTSS_EINVAL a null context, a null required pointer (a block table may be NULL with a count of 0), a wrong structSize of
+ * either params, an unknown filter or flag, a non-zero reserved, film parameters ptss_accumulate_paths_linear refuses, a pointer that
+ * is not aligned (16 bytes for blocks, map, hits and out, 4 for info), dev_out overlapping dev_map; PTSS_ERANGE n >= 2^31, an atlas
+ * side below 1 or atlasWidth * atlasHeight >= 2^31, a negative first or count.
+ * ptss_default_lightmap_params: a 1 x 1 atlas, bilinear, no flags, empty tables. ptss_debug_lightmap_form (tests and measurements):
+ * 0 the shipped form, 1 one lane per hit, 2 four lanes per hit. The bytes are the same. */
+int ptss_default_lightmap_params(ptss_lightmap_params* params);
+int ptss_lookup_lightmap(ptss_context* ctx, const ptss_lightmap_params* params, const ptss_linear_params* film,
+                         const ptss_surface_block* dev_blocksTri /* may be NULL with 0 */, const ptss_surface_block* dev_blocksSph /* may be NULL with 0 */,
+                         const ptss_linear_entry* dev_map, const ptss_ray_hit* dev_hits, size_t n, ptss_linear_entry* dev_out /* n rows, all written */,
+                         uint32_t* dev_info /* may be NULL: 4 counts, added to */, void* hipStream);
+int ptss_lightmap_launches(const ptss_context* ctx, unsigned long long* out);
+int ptss_debug_lightmap_form(ptss_context* ctx, int form);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

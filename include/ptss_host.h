@@ -352,6 +352,30 @@ int ptss_probe_dilate_linear(const ptss_linear_entry* film, int width, int heigh
 int ptss_surface_atlas(const ptss_triangle* triangles, size_t first, size_t count, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
                        ptss_surface_point* points, uint32_t* texels, size_t capacity, int* atlasHeight, size_t* numPoints);
 
+/* Light maps read back (csrc/ptlightmap.h, csrc/ptsurface.h).
+ *
+ * ptss_surface_atlas_blocks (host only; a convenience like ptss_surface_atlas): the same atlas, with the blocks named and continued
+ * over spheres[firstSphere .. firstSphere + numSpheres) (may be NULL with 0). The triangles come first and are packed by
+ * ptss_surface_atlas' rule — with numSpheres = 0 the points, texels, height and count are that function's —; the spheres continue on
+ * the same shelves with the same one-texel gaps: sphere k gets h = clamp(ceil(pi * radius * texelsPerUnit), minSide, maxSide) rows
+ * (not a number: minSide) and w = 2 h columns, and every texel (i, j) of its block the point {surface = k, a = (i + 0.5) / w,
+ * b = (j + 0.5) / h, flags = 0} — ptss_surface_point's longitude and latitude fractions — rows bottom up, after all triangle points.
+ * blocksTri[count], blocksSph[numSpheres] (each may be NULL): where each primitive's block lies; the texel of a block's (i, j) is
+ * (y + j) * atlasWidth + x + i. Refused as ptss_surface_atlas refuses, and PTSS_HOST_EINVAL null spheres with numSpheres > 0 or
+ * 2 * maxSide > atlasWidth when numSpheres > 0, PTSS_HOST_ERANGE firstSphere + numSpheres at or above 2^30.
+ *
+ * ptss_probe_lookup_lightmap: ptss_lookup_lightmap over the caller's own records — materials[numMaterials] stand for the scene image's
+ * (may be NULL with 0) — with the same remaining arguments and outputs; info (may be NULL): four counts ADDED to. The specification of
+ * the device's rows. PTSS_HOST_EINVAL / PTSS_HOST_ERANGE: whatever the device call refuses with PTSS_EINVAL / PTSS_ERANGE, alignment
+ * aside. */
+int ptss_surface_atlas_blocks(const ptss_triangle* triangles, size_t firstTriangle, size_t numTriangles, const ptss_sphere* spheres,
+                              size_t firstSphere, size_t numSpheres, float texelsPerUnit, int minSide, int maxSide, int atlasWidth,
+                              ptss_surface_block* blocksTri, ptss_surface_block* blocksSph, ptss_surface_point* points, uint32_t* texels,
+                              size_t capacity, int* atlasHeight, size_t* numPoints);
+int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+                               const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
+                               const ptss_linear_entry* map, const ptss_ray_hit* hits, size_t n, ptss_linear_entry* out, uint32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

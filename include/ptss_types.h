@@ -474,6 +474,30 @@ typedef struct ptss_surface_params {
     unsigned int reserved;   /* 0 */
 } ptss_surface_params;
 
+/* Where a primitive's texels lie in a light map's atlas (ptss_surface_atlas_blocks, ptss_lookup_lightmap): the block's
+ * lower-left texel and its extent. width == 0: the primitive has no block. 16 B, one row, 16-byte aligned access. */
+typedef struct ptss_surface_block {
+    int x, y, width, height;
+} ptss_surface_block;
+
+/* How ptss_lookup_lightmap reads a baked map (csrc/ptlightmap.h). atlasWidth x atlasHeight: the map's sides, both >= 1,
+ * their product below 2^31. filter: the nearest texel or four taps with integer weights. flags: PTSS_LIGHTMAP_MODULATE multiplies the
+ * looked-up mean by the hit's diffuseColor (the radiance a Lambert surface sends out), PTSS_LIGHTMAP_EMISSION adds the hit's emmitance.
+ * Block table row k of the triangles belongs to the caller's triangle firstTriangle + k, k < numTriangleBlocks; the spheres alike. */
+#define PTSS_LIGHTMAP_NEAREST 0
+#define PTSS_LIGHTMAP_BILINEAR 1
+#define PTSS_LIGHTMAP_MODULATE 1u
+#define PTSS_LIGHTMAP_EMISSION 2u
+typedef struct ptss_lightmap_params {
+    unsigned int structSize; /* sizeof(ptss_lightmap_params) as the caller compiled it */
+    int atlasWidth, atlasHeight;
+    int filter;              /* PTSS_LIGHTMAP_NEAREST or PTSS_LIGHTMAP_BILINEAR    default PTSS_LIGHTMAP_BILINEAR */
+    unsigned int flags;      /* PTSS_LIGHTMAP_MODULATE | PTSS_LIGHTMAP_EMISSION    default 0 */
+    int firstTriangle, numTriangleBlocks;
+    int firstSphere, numSphereBlocks;
+    unsigned int reserved;   /* 0 */
+} ptss_lightmap_params;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -589,6 +613,13 @@ static_assert(sizeof(ptss_surface_point) == 16 && offsetof(ptss_surface_point, a
 static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params, mode) == 4 && offsetof(ptss_surface_params, maxDistance) == 8 &&
                   offsetof(ptss_surface_params, reserved) == 12,
               "ptss_surface_params is four 32-bit words");
+static_assert(sizeof(ptss_surface_block) == 16 && offsetof(ptss_surface_block, y) == 4 && offsetof(ptss_surface_block, width) == 8 &&
+                  offsetof(ptss_surface_block, height) == 12,
+              "ptss_surface_block is one 16-byte row");
+static_assert(sizeof(ptss_lightmap_params) == 40 && offsetof(ptss_lightmap_params, atlasWidth) == 4 && offsetof(ptss_lightmap_params, filter) == 12 &&
+                  offsetof(ptss_lightmap_params, flags) == 16 && offsetof(ptss_lightmap_params, firstTriangle) == 20 &&
+                  offsetof(ptss_lightmap_params, firstSphere) == 28 && offsetof(ptss_lightmap_params, reserved) == 36,
+              "ptss_lightmap_params is ten 32-bit words");
 #elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
 _Static_assert(sizeof(ptss_ray_query) == 32 && offsetof(ptss_ray_query, tmax) == 12 && offsetof(ptss_ray_query, direction) == 16,
                "ptss_ray_query is two 16-byte rows");
@@ -672,6 +703,13 @@ _Static_assert(sizeof(ptss_surface_point) == 16 && offsetof(ptss_surface_point, 
 _Static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params, mode) == 4 && offsetof(ptss_surface_params, maxDistance) == 8 &&
                    offsetof(ptss_surface_params, reserved) == 12,
                "ptss_surface_params is four 32-bit words");
+_Static_assert(sizeof(ptss_surface_block) == 16 && offsetof(ptss_surface_block, y) == 4 && offsetof(ptss_surface_block, width) == 8 &&
+                   offsetof(ptss_surface_block, height) == 12,
+               "ptss_surface_block is one 16-byte row");
+_Static_assert(sizeof(ptss_lightmap_params) == 40 && offsetof(ptss_lightmap_params, atlasWidth) == 4 && offsetof(ptss_lightmap_params, filter) == 12 &&
+                   offsetof(ptss_lightmap_params, flags) == 16 && offsetof(ptss_lightmap_params, firstTriangle) == 20 &&
+                   offsetof(ptss_lightmap_params, firstSphere) == 28 && offsetof(ptss_lightmap_params, reserved) == 36,
+               "ptss_lightmap_params is ten 32-bit words");
 #endif
 
 #ifdef __cplusplus
