@@ -30,6 +30,13 @@
 //              or below 0: 0), m' = (m' q_c + 32768) >> 16 through a two-word product. PTSS_LIGHTMAP_EMISSION: m' += ptlin::toFixed(
 //              emmitance_c, clampMax, 2^scaleLog2), saturating at 2^64 - 1.
 //  6. ROW      FILTERED: {m'_r, m'_g, m'_b, samples = 1, clamped = 0}; every other verdict: all zero.
+//
+// ptss_lookup_lightmap_chain has a step 6 of its own after SHADE, in front of the row, for the light a chain of mirrors
+// and glass lets through (ptss_intersect_chain's throughput, one ptss_chain_result per hit, never trusted):
+//  6. TINT     per channel t_c = modulateWeight(throughput_c), step 5's conversion: clamp((int)(throughput_c * 65536 + 0.5f), 0, 65536),
+//              0 for a throughput that is not a number or below 0 — and 65,536 for every throughput ABOVE 1: the tint is clamped at 1 —;
+//              m' = (m' t_c + 32768) >> 16 through the same two-word product. A throughput of exactly 1 keeps m' (m' 2^16 + 2^15 >> 16).
+//              The verdicts and counts are those of the plain lookup.
 #pragma once
 #include "ptlinrp.h"
 
@@ -228,6 +235,12 @@ PTM_HD u64 shade(u64 m, uint32_t flags, float diffuse, float emission, const Rul
         m = m + e < m ? ~0ull : m + e;
     }
     return m;
+}
+
+// step 6 of one channel (ptss_lookup_lightmap_chain only)
+PTM_HD u64 tint(u64 m, float throughput) {
+    const U128 p = add128(ptls::mul64(m, (u64)modulateWeight(throughput)), U128{32768ull, 0ull});
+    return (p.lo >> 16) | (p.hi << 48);
 }
 
 // A whole hit, one tap after the other (the host probe; the kernel's one-lane form). blockTri(k) / blockSph(k) -> the Block of a table

@@ -94,4 +94,50 @@ PTM_HD Step step(const Material& m, vec3 d, vec3 point, vec3 normal) {
     return s;
 }
 
+// The factor by which the link step() follows multiplies the radiance that arrives along it (ptss_intersect_chain's throughput;
+// host_capi.cpp ptss_probe_specular_link): the probability with which scatter() picks the followed lobe times the
+// weight scatter() returns for it, so that a chain's product is the expectation of the reference's estimator restricted to the chain.
+// scatter()'s own expressions in scatter()'s order (ptshade.h; ptm::div where scatter() may take a proven fast path to the same
+// bits); cosI, n1 and n2 flipped as step() flips them:
+//   F = 1; the Snell / Fresnel terms only where scatter() reads them:
+//   (specAvg > 0 && !(flags & PURE_REFLECTION)) || refrAvg > 0:
+//     n = div(n1, n2), sinT2 = n * n * (1 - cosI * cosI)
+//     !(sinT2 > 1): cosT = sqrt(1 - sinT2), r_s = div(n1 cosI - n2 cosT, n1 cosI + n2 cosT), r_p = div(n2 cosI - n1 cosT,
+//                   n2 cosI + n1 cosT), F = (r_s r_s + r_p r_p) * 0.5
+//   a reflected link (MIRROR, or TRANSMIT in total internal reflection): p = (flags & PURE_REFLECTION) ? specAvg : specAvg * F,
+//                                                                      factor = specularColor * p
+//   a refracted link:                                                  p = refrAvg * (1 - F), factor = (p, p, p)
+// Meaningful only for a link that follows (step().follows); specularColor: the material's (scatter()'s xyz(mSpecular)), an argument
+// of its own so that Material stays what step() reads.
+PTM_HD vec3 linkFactor(const Material& m, vec3 specularColor, vec3 d, vec3 normal) {
+    const Class cls = classify(m);
+    float cosI = dot(-d, normal);
+    float n1, n2;
+    if (cosI > 0) {
+        n2 = m.indexOfRefraction;
+        n1 = 1.0f;
+    } else {
+        cosI = -cosI;
+        n1 = m.indexOfRefraction;
+        n2 = 1.0f;
+    }
+    float F = 1.0f, sinT2 = 0.0f;
+    if ((m.specAvg > 0.0f && !(m.flags & PTSS_MAT_FLAG_PURE_REFLECTION)) || m.refrAvg > 0.0f) {
+        const float n = ptm::div(n1, n2);
+        sinT2 = n * n * (1.0f - cosI * cosI);
+        if (!(sinT2 > 1.0f)) {
+            const float cosT = ptm::sqrt(1.0f - sinT2);
+            const float r_s = ptm::div(n1 * cosI - n2 * cosT, n1 * cosI + n2 * cosT);
+            const float r_p = ptm::div(n2 * cosI - n1 * cosT, n2 * cosI + n1 * cosT);
+            F = (r_s * r_s + r_p * r_p) * 0.5f;
+        }
+    }
+    if (cls == kMirror || (cls == kTransmit && sinT2 > 1.0f)) {
+        const float p = (m.flags & PTSS_MAT_FLAG_PURE_REFLECTION) ? m.specAvg : m.specAvg * F;
+        return specularColor * p;
+    }
+    const float p = m.refrAvg * (1.0f - F);
+    return v3(p, p, p);
+}
+
 }  // namespace ptsp

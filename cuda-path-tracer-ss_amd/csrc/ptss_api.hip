@@ -181,6 +181,9 @@ struct ptss_context {
     bool surfaceCounted = false;
     int dilateForm = 0;                                       // ptss_debug_dilate_linear_form: 0 the shipped form, 1 global memory, 2 staged
     unsigned long long lightmapLaunches = 0;                  // ptss_lookup_lightmap calls that launched
+    unsigned long long lightmapChainLaunches = 0;             // ptss_lookup_lightmap_chain calls that launched
+    unsigned long long chainLaunches[2] = {0, 0};             // ptss_intersect_chain launches: [0] one lane per ray, [1] refill
+    uint32_t* dChainHead = nullptr;                           // the refill schedule's queue head (ptss_device.h launchChainRefill), allocated by its first call
     int lightmapForm = 0;                                     // ptss_debug_lightmap_form: 0 the shipped form, 1 one lane per hit, 2 four lanes per hit
     int toneForm = 0;                                         // ptss_debug_tone_form: 0 the shipped lookup, 1 staged in LDS, 2 guess and settle
     int linDenoiseForm = 0;                                   // ptss_debug_denoise_linear_form: 0 the measured table, 1 unstaged, 2 staged, 4 + mask
@@ -801,6 +804,7 @@ int ptss_destroy(ptss_context* c) {
     ptss::releaseResortScratch(c->resortScratch);
     (void)hipFree(c->dPathJumpTable);
     (void)hipFree(c->dPathRefill);
+    (void)hipFree(c->dChainHead);
     delete c;
     return PTSS_OK;
 }
@@ -1202,6 +1206,56 @@ int ptss_specular_feature_launches(const ptss_context* c, unsigned long long* ou
     if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
     out2[0] = c->specularFeatureLaunches[0];
     out2[1] = c->specularFeatureLaunches[1];
+    return PTSS_OK;
+}
+
+// ptss_intersect_chain: ptss_intersect's image (images[0], exact for every ray), no frame state, the caller's stream; the chain of
+// csrc/ptspecular.h behind every hit (ptss_chain.hip)
+int ptss_default_chain_options(ptss_chain_options* o) {
+    if (!o) return fail(PTSS_EINVAL, "options is null");
+    o->structSize = (unsigned int)sizeof(ptss_chain_options);
+    o->schedule = PTSS_CHAIN_LANE_PER_RAY;
+    o->maxWorkgroups = 0;
+    o->reserved = 0;
+    return PTSS_OK;
+}
+
+int ptss_intersect_chain(ptss_context* c, const ptss_ray_query* dev_rays, size_t n, int maxSteps, const ptss_chain_options* options,
+                         ptss_ray_hit* dev_hits, ptss_chain_result* dev_chain, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (options) {
+        if (options->structSize != sizeof(ptss_chain_options)) return fail(PTSS_EINVAL, "options->structSize is not sizeof(ptss_chain_options)");
+        if (options->schedule != PTSS_CHAIN_LANE_PER_RAY && options->schedule != PTSS_CHAIN_REFILL) return fail(PTSS_EINVAL, "unknown schedule");
+        if (options->maxWorkgroups < 0) return fail(PTSS_EINVAL, "maxWorkgroups must not be negative");
+        if (options->reserved != 0) return fail(PTSS_EINVAL, "reserved must be 0");
+    }
+    if (maxSteps < 0 || maxSteps > ptsp::kMaxSteps) return fail(PTSS_ERANGE, "maxSteps must be in [0, 8]");
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_rays || !dev_hits) return fail(PTSS_EINVAL, "null buffer with n > 0");
+    if (((uintptr_t)dev_rays | (uintptr_t)dev_hits | (uintptr_t)dev_chain) & 15u) return fail(PTSS_EINVAL, "rays, hits and chain must be 16-byte aligned");
+    if (ptlrp::rangesOverlap(dev_hits, 48 * n, dev_rays, 32 * n)) return fail(PTSS_EINVAL, "dev_hits overlaps dev_rays");
+    if (dev_chain && (ptlrp::rangesOverlap(dev_chain, 32 * n, dev_rays, 32 * n) || ptlrp::rangesOverlap(dev_chain, 32 * n, dev_hits, 48 * n)))
+        return fail(PTSS_EINVAL, "dev_chain overlaps dev_rays or dev_hits");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    hipStream_t st = streamOf(c, hipStream);
+    if (!(options && options->schedule == PTSS_CHAIN_REFILL)) {
+        HIP_TRY(ptss::launchChain(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_hits, dev_chain, (uint32_t)n, maxSteps, c->gridCap * ptss::kShards,
+                                  &c->chainLaunches[0]));
+        return PTSS_OK;
+    }
+    if (!c->dChainHead) HIP_TRY(hipMalloc(&c->dChainHead, 2 * sizeof(uint32_t)));   // (set in front of every kernel: nothing to clear)
+    HIP_TRY(ptss::launchChainRefill(st, im.dBlob, im.layout, im.inLds, dev_rays, dev_hits, dev_chain, (uint32_t)n, maxSteps, options->maxWorkgroups,
+                                    c->numCUs, c->dChainHead, &c->chainLaunches[1]));
+    return PTSS_OK;
+}
+
+int ptss_chain_launches(const ptss_context* c, unsigned long long* out2) {
+    if (!c || !out2) return fail(PTSS_EINVAL, "null argument");
+    out2[0] = c->chainLaunches[0];
+    out2[1] = c->chainLaunches[1];
     return PTSS_OK;
 }
 
@@ -2027,6 +2081,41 @@ int ptss_lookup_lightmap(ptss_context* c, const ptss_lightmap_params* params, co
     HIP_TRY(hipSetDevice(c->cfg.device));
     HIP_TRY(ptss::launchLookupLightmap(streamOf(c, hipStream), im.dBlob, im.layout, *params, *film, dev_blocksTri, dev_blocksSph, dev_map, dev_hits,
                                        (uint32_t)n, c->lightmapForm, dev_out, dev_info, &c->lightmapLaunches));
+    return PTSS_OK;
+}
+
+// ptss_lookup_lightmap's checks and one more buffer: the chain rows whose throughput tints the FILTERED rows (ptlightmap.h step 6)
+int ptss_lookup_lightmap_chain(ptss_context* c, const ptss_lightmap_params* params, const ptss_linear_params* film,
+                               const ptss_surface_block* dev_blocksTri, const ptss_surface_block* dev_blocksSph, const ptss_linear_entry* dev_map,
+                               const ptss_ray_hit* dev_hits, const ptss_chain_result* dev_chain, size_t n, ptss_linear_entry* dev_out,
+                               uint32_t* dev_info, void* hipStream) {
+    if (!c) return fail(PTSS_EINVAL, "ctx is null");
+    if (const char* what = ptlm::paramsError(params)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlin::paramsError(film)) return fail(PTSS_EINVAL, what);
+    if (const char* what = ptlm::rangeError(params)) return fail(PTSS_ERANGE, what);
+    if (!fits31(n)) return fail(PTSS_ERANGE, "n must be below 2^31");
+    if (n == 0) return PTSS_OK;
+    if (!dev_map || !dev_hits || !dev_chain || !dev_out || (params->numTriangleBlocks > 0 && !dev_blocksTri) ||
+        (params->numSphereBlocks > 0 && !dev_blocksSph))
+        return fail(PTSS_EINVAL, kNullBuffer);
+    if ((((uintptr_t)dev_blocksTri | (uintptr_t)dev_blocksSph | (uintptr_t)dev_map | (uintptr_t)dev_hits | (uintptr_t)dev_chain | (uintptr_t)dev_out) & 15u) ||
+        ((uintptr_t)dev_info & 3u))
+        return fail(PTSS_EINVAL, "blocks, map, hits, chain and out must be 16-byte aligned, dev_info 4-byte aligned");
+    if (ptlrp::rangesOverlap(dev_out, 32 * n, dev_map, 32 * (size_t)params->atlasWidth * (size_t)params->atlasHeight))
+        return fail(PTSS_EINVAL, "dev_out overlaps dev_map");
+    if (ptlrp::rangesOverlap(dev_out, 32 * n, dev_chain, 32 * n) || ptlrp::rangesOverlap(dev_out, 32 * n, dev_hits, 48 * n))
+        return fail(PTSS_EINVAL, "dev_out overlaps dev_chain or dev_hits");
+    const SceneImage& im = c->images[0];
+    if (!im.dBlob) return fail(PTSS_EINVAL, "context has no scene image");
+    HIP_TRY(hipSetDevice(c->cfg.device));
+    HIP_TRY(ptss::launchLookupLightmapChain(streamOf(c, hipStream), im.dBlob, im.layout, *params, *film, dev_blocksTri, dev_blocksSph, dev_map, dev_hits,
+                                            dev_chain, (uint32_t)n, dev_out, dev_info, &c->lightmapChainLaunches));
+    return PTSS_OK;
+}
+
+int ptss_lightmap_chain_launches(const ptss_context* c, unsigned long long* out) {
+    if (!c || !out) return fail(PTSS_EINVAL, "null argument");
+    *out = c->lightmapChainLaunches;
     return PTSS_OK;
 }
 

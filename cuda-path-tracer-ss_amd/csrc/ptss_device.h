@@ -322,6 +322,18 @@ hipError_t launchDilateLinear(hipStream_t st, const void* film, int width, int h
 hipError_t launchLookupLightmap(hipStream_t st, const float4* sceneBlob, const SceneLayout& layout, const ptss_lightmap_params& params,
                                 const ptss_linear_params& film, const void* blocksTri, const void* blocksSph, const void* map, const void* hits,
                                 uint32_t n, int form, void* out, void* info, unsigned long long* launches);
+// ... tinted by a chain's throughput (ptss_lookup_lightmap_chain): chain = n rows of 32 B (ptss_chain_result), one lane per hit
+hipError_t launchLookupLightmapChain(hipStream_t st, const float4* sceneBlob, const SceneLayout& layout, const ptss_lightmap_params& params,
+                                     const ptss_linear_params& film, const void* blocksTri, const void* blocksSph, const void* map, const void* hits,
+                                     const void* chain, uint32_t n, void* out, void* info, unsigned long long* launches);
+// ray queries carried through mirrors and glass (ptss_chain.hip; ptss_intersect_chain): rays = n x 32 B, hits = n x 48 B,
+// chain = n x 32 B (ptss_chain_result) or nullptr, maxSteps 0 .. ptsp::kMaxSteps. No bit of ptss_launched_kernels: *launches is incremented.
+// launchChain: one lane per ray, launchQuery's grid. launchChainRefill: launchPathRefill's grid and claiming; head: a 32-bit device word of
+// the context for this kernel alone, set on `st` in front of the kernel
+hipError_t launchChain(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* hits, void* chain,
+                       uint32_t n, int maxSteps, int maxBlocks, unsigned long long* launches);
+hipError_t launchChainRefill(hipStream_t st, const float4* sceneBlob, SceneLayout layout, bool sceneInLds, const void* rays, void* hits, void* chain,
+                             uint32_t n, int maxSteps, int maxWorkgroups, int numCUs, uint32_t* head, unsigned long long* launches);
 // one pass of ptss_denoise (ptss_denoise.hip; PTSS_KERNEL_DENOISE of *launched). first: src is the accumulator (3 uint32 per pixel), else a colour
 // plane (float4 per pixel); last: dst is the display buffer (uchar4 per pixel), else a colour plane
 hipError_t launchDenoise(hipStream_t st, bool first, bool last, const void* src, void* dst, const void* features, int width, int height,

@@ -11,7 +11,8 @@
 //   <kQuad = true>    four adjacent lanes per hit, lane t of the quad reads tap t and divides its three means; W and the three
 //                     two-word sums travel across the quad through two DPP quad permutes each (no LDS); lane 0 of the quad divides
 //                     by W, shades and stores
-// Which one ships is kLightmapQuad below. Verdicts are counted with one atomic per wave and count; no bit of ptss_launched_kernels.
+// Which one ships is kLightmapQuad below. lightmapChainKernel (ptss_lookup_lightmap_chain) is the one-lane form with the
+// header's step 6, a tint by a chain's throughput, behind the lookup. Verdicts are counted with one atomic per wave and count; no bit of ptss_launched_kernels.
 #include <hip/hip_runtime.h>
 
 #include "ptss_device.h"
@@ -143,6 +144,47 @@ __global__ __launch_bounds__(kLightmapBlock) void lightmapKernel(const float4* _
         }
         countVerdicts(mine, verdict, info);
     }
+}
+
+// ptss_lookup_lightmap_chain: the one-lane form with ptlightmap.h's step 6 behind the lookup — the first row of the
+// hit's ptss_chain_result (16 B: the throughput, never trusted: ptlm::tint clamps it) tints a FILTERED row. A kernel of its own, so that
+// lightmapKernel's two instantiations stay what they were.
+__global__ __launch_bounds__(kLightmapBlock) void lightmapChainKernel(const float4* __restrict__ blob, LightmapArgs A, const int4* __restrict__ blocksTri,
+                                                                      const int4* __restrict__ blocksSph, const ulonglong2* __restrict__ map,
+                                                                      const float4* __restrict__ hits, const float4* __restrict__ chain, uint32_t n,
+                                                                      ulonglong2* __restrict__ out, uint32_t* __restrict__ info) {
+    const ptlm::Rule& R = A.rule;
+    auto material = [&](int idx, int row) { return xyz(blob[A.offMaterial + 5 * (size_t)idx + row]); };
+    unsigned long long m[3] = {0ull, 0ull, 0ull};
+    const uint32_t i = blockIdx.x * kLightmapBlock + threadIdx.x;
+    const bool inBatch = i < n;
+    int verdict = ptlm::kRejected;
+    if (inBatch) {
+        verdict = ptlm::lookup(
+            hitOf(hits, i), R, [&](int row) { return blockOf(blocksTri, row); }, [&](int row) { return blockOf(blocksSph, row); },
+            [&](uint32_t texel) { return texelAt(map, texel); }, material, m);
+        if (verdict == ptlm::kFiltered) {
+            const float4 t = chain[2 * (size_t)i];
+            m[0] = ptlm::tint(m[0], t.x);
+            m[1] = ptlm::tint(m[1], t.y);
+            m[2] = ptlm::tint(m[2], t.z);
+        }
+        storeRow(out, i, verdict, m);
+    }
+    countVerdicts(inBatch, verdict, info);
+}
+
+hipError_t launchLookupLightmapChain(hipStream_t st, const float4* sceneBlob, const SceneLayout& L, const ptss_lightmap_params& params,
+                                     const ptss_linear_params& film, const void* blocksTri, const void* blocksSph, const void* map, const void* hits,
+                                     const void* chain, uint32_t n, void* out, void* info, unsigned long long* launches) {
+    LightmapArgs A;
+    A.rule = ptlm::ruleOf(params, film, L.numMaterials);
+    A.offMaterial = L.offMaterial;
+    hipLaunchKernelGGL(lightmapChainKernel, dim3(filmBlocksFor(n, kLightmapBlock)), dim3(kLightmapBlock), 0, st, sceneBlob, A,
+                       static_cast<const int4*>(blocksTri), static_cast<const int4*>(blocksSph), static_cast<const ulonglong2*>(map),
+                       static_cast<const float4*>(hits), static_cast<const float4*>(chain), n, static_cast<ulonglong2*>(out),
+                       static_cast<uint32_t*>(info));
+    return counted(launches);
 }
 
 hipError_t launchLookupLightmap(hipStream_t st, const float4* sceneBlob, const SceneLayout& L, const ptss_lightmap_params& params,

@@ -558,6 +558,18 @@ int ptss_probe_specular_step(const ptss_ray_query* rays, const ptss_ray_hit* hit
     return PTSS_HOST_OK;
 }
 
+int ptss_probe_specular_link(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_material* materials, size_t numMaterials,
+                             ptss_ray_query* next, int* follows, ptss_vec3* factors) {
+    if (n > 0 && !factors) return PTSS_HOST_EINVAL;
+    if (const int rc = ptss_probe_specular_step(rays, hits, n, materials, numMaterials, next, follows)) return rc;
+    for (size_t i = 0; i < n; ++i) {
+        if (!follows[i]) continue;
+        const ptss_material& m = materials[hits[i].materialIdx];
+        factors[i] = ptsp::linkFactor(specularMaterial(m), m.specularColor, rays[i].direction, hits[i].normal);
+    }
+    return PTSS_HOST_OK;
+}
+
 int ptss_probe_specular_class(const ptss_material* material) {
     return material ? (int)ptsp::classify(specularMaterial(*material)) : -1;
 }
@@ -1313,9 +1325,11 @@ int ptss_surface_atlas_blocks(const ptss_triangle* triangles, size_t firstTriang
                                blocksTri, blocksSph, points, texels, capacity, atlasHeight, numPoints);
 }
 
-int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+// chain == nullptr: the plain lookup; else ptlightmap.h's step 6 with chain[i].throughput (the caller has refused a null chain with n > 0)
+static int lookupLightmapProbe(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
                                const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
-                               const ptss_linear_entry* map, const ptss_ray_hit* hits, size_t n, ptss_linear_entry* out, uint32_t* info) {
+                               const ptss_linear_entry* map, const ptss_ray_hit* hits, const ptss_chain_result* chain, size_t n,
+                               ptss_linear_entry* out, uint32_t* info) {
     if (ptlm::paramsError(params) || ptlin::paramsError(film)) return PTSS_HOST_EINVAL;
     if (ptlm::rangeError(params) || n >= (size_t(1) << 31) || numMaterials >= (size_t(1) << 31)) return PTSS_HOST_ERANGE;
     if (n == 0) return PTSS_HOST_OK;
@@ -1333,10 +1347,33 @@ int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMateria
         ptlm::u64 m[3];
         const int verdict = ptlm::lookup(
             h, R, [&](int row) { return block(blocksTri, row); }, [&](int row) { return block(blocksSph, row); }, at, material, m);
+        if (chain && verdict == ptlm::kFiltered) {
+            m[0] = ptlm::tint(m[0], chain[i].throughput.x);
+            m[1] = ptlm::tint(m[1], chain[i].throughput.y);
+            m[2] = ptlm::tint(m[2], chain[i].throughput.z);
+        }
         out[i] = ptss_linear_entry{m[0], m[1], m[2], verdict == ptlm::kFiltered ? 1u : 0u, 0u};
         if (info) ++info[verdict];
     }
     return PTSS_HOST_OK;
+}
+
+int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+                               const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
+                               const ptss_linear_entry* map, const ptss_ray_hit* hits, size_t n, ptss_linear_entry* out, uint32_t* info) {
+    return lookupLightmapProbe(materials, numMaterials, params, film, blocksTri, blocksSph, map, hits, nullptr, n, out, info);
+}
+
+int ptss_probe_lookup_lightmap_chain(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+                                     const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
+                                     const ptss_linear_entry* map, const ptss_ray_hit* hits, const ptss_chain_result* chain, size_t n,
+                                     ptss_linear_entry* out, uint32_t* info) {
+    if (ptlm::paramsError(params) || ptlin::paramsError(film)) return PTSS_HOST_EINVAL;
+    if (ptlm::rangeError(params) || n >= (size_t(1) << 31) || numMaterials >= (size_t(1) << 31)) return PTSS_HOST_ERANGE;
+    if (n == 0) return PTSS_HOST_OK;
+    if (!chain || !out || !hits) return PTSS_HOST_EINVAL;
+    if (ptlrp::rangesOverlap(out, 32 * n, chain, 32 * n) || ptlrp::rangesOverlap(out, 32 * n, hits, 48 * n)) return PTSS_HOST_EINVAL;
+    return lookupLightmapProbe(materials, numMaterials, params, film, blocksTri, blocksSph, map, hits, chain, n, out, info);
 }
 
 }  // extern "C"

@@ -84,6 +84,10 @@
 //                                   modulate and emission (default bilinear) -> ptss_resolve_linear at --size; writes the view's linear means
 //                                   next to the map (<out without .pfm>_view.pfm) and prints the four counts. Without the flag --bake writes
 //                                   exactly what it wrote before
+//             [--view-steps N]      with --bake-view: the view's rays are carried through mirrors and glass for at most N
+//                                   (0..8) links — ptss_intersect_chain in place of ptss_intersect — and the rows come from
+//                                   ptss_lookup_lightmap_chain, tinted by what the chain let through; also prints the links followed. N = 0 (the
+//                                   default) is the path above and writes its bytes
 //             [--upscale-linear F]  with --film and --linear, with or without --filter, --refill, --denoise-linear, --auto-exposure and --glare:
 //                                   the film is traced (and denoised) at the given size and upsampled in linear light to F (1..4) times the
 //                                   size — the features are ptss_ray_features of the centre rays of the same film camera at
@@ -144,6 +148,7 @@ int main(int argc, char* argv[]) {
     float bakeTexels = 4.f;                           // ... texels per unit of length, samples per texel, gutter-fill passes
     int bakeSamples = 16, bakePasses = 1;
     int bakeView = -1;                                // --bake-view: the filter of the camera view looked up from the baked map, -1 none
+    int viewSteps = -1;                               // --view-steps: the links the view's rays follow through mirrors and glass, -1 not given
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -273,6 +278,9 @@ int main(int argc, char* argv[]) {
             if (i + 1 < argc && (!strcmp(argv[i + 1], "nearest") || !strcmp(argv[i + 1], "bilinear")))
                 bakeView = !strcmp(next(), "nearest") ? PTSS_LIGHTMAP_NEAREST : PTSS_LIGHTMAP_BILINEAR;
         }
+        else if (a == "--view-steps") {
+            if (sscanf(next(), "%d", &viewSteps) != 1 || viewSteps < 0 || viewSteps > 8) { fprintf(stderr, "bad --view-steps (0..8)\n"); return 2; }
+        }
         else if (a == "--lens") { if (sscanf(next(), "%f,%f", &lensRadius, &focusDistance) != 2) { fprintf(stderr, "bad --lens (radius,focus)\n"); return 2; } }
         else if (a == "--pick") {
             int x, y;
@@ -342,6 +350,7 @@ int main(int argc, char* argv[]) {
         return 2;
     }
     if (bakeView >= 0 && (!bake || height < 1)) { fprintf(stderr, "--bake-view needs --bake\n"); return 2; }
+    if (viewSteps >= 0 && bakeView < 0) { fprintf(stderr, "--view-steps needs --bake-view\n"); return 2; }
     ptss_splat_filter splatFilter;
     PTSS_HANDLE(ptss_default_splat_filter(&splatFilter));
     if (!splat.empty()) {
@@ -490,6 +499,8 @@ int main(int argc, char* argv[]) {
             lp.numSphereBlocks = (int)S;
             const size_t n = (size_t)width * (size_t)height;
             void *dBt = nullptr, *dBs = nullptr, *dVRng = nullptr, *dVRays = nullptr, *dHits = nullptr, *dView = nullptr, *dVMeans = nullptr, *dInfo = nullptr;
+            void* dChain = nullptr;   // --view-steps above 0: what each ray's chain did on the way
+            if (viewSteps > 0 && hipMalloc(&dChain, n * sizeof(ptss_chain_result)) != hipSuccess) { fprintf(stderr, "--view-steps: device buffers\n"); return 1; }
             if (hipMalloc(&dBt, (T ? T : 1) * sizeof(ptss_surface_block)) != hipSuccess || hipMalloc(&dBs, (S ? S : 1) * sizeof(ptss_surface_block)) != hipSuccess ||
                 hipMalloc(&dVRng, n * sizeof(ptss_path_rng)) != hipSuccess || hipMalloc(&dVRays, n * sizeof(ptss_ray_query)) != hipSuccess ||
                 hipMalloc(&dHits, n * sizeof(ptss_ray_hit)) != hipSuccess || hipMalloc(&dView, n * sizeof(ptss_linear_entry)) != hipSuccess ||
@@ -501,10 +512,18 @@ int main(int argc, char* argv[]) {
                 return 1;
             }
             PTSS_HANDLE(ptss_generate_rays(ctx, &fc, 0, NULL, n, (ptss_path_rng*)dVRng, (ptss_ray_query*)dVRays, NULL));
-            PTSS_HANDLE(ptss_intersect(ctx, (const ptss_ray_query*)dVRays, (ptss_ray_hit*)dHits, n, NULL));
-            PTSS_HANDLE(ptss_lookup_lightmap(ctx, &lp, &linearParams, T ? (const ptss_surface_block*)dBt : NULL, S ? (const ptss_surface_block*)dBs : NULL,
-                                             (const ptss_linear_entry*)dMap[cur], (const ptss_ray_hit*)dHits, n, (ptss_linear_entry*)dView,
-                                             (uint32_t*)dInfo, NULL));
+            if (viewSteps > 0) {
+                PTSS_HANDLE(ptss_intersect_chain(ctx, (const ptss_ray_query*)dVRays, n, viewSteps, NULL, (ptss_ray_hit*)dHits, (ptss_chain_result*)dChain, NULL));
+                PTSS_HANDLE(ptss_lookup_lightmap_chain(ctx, &lp, &linearParams, T ? (const ptss_surface_block*)dBt : NULL,
+                                                       S ? (const ptss_surface_block*)dBs : NULL, (const ptss_linear_entry*)dMap[cur],
+                                                       (const ptss_ray_hit*)dHits, (const ptss_chain_result*)dChain, n, (ptss_linear_entry*)dView,
+                                                       (uint32_t*)dInfo, NULL));
+            } else {
+                PTSS_HANDLE(ptss_intersect(ctx, (const ptss_ray_query*)dVRays, (ptss_ray_hit*)dHits, n, NULL));
+                PTSS_HANDLE(ptss_lookup_lightmap(ctx, &lp, &linearParams, T ? (const ptss_surface_block*)dBt : NULL, S ? (const ptss_surface_block*)dBs : NULL,
+                                                 (const ptss_linear_entry*)dMap[cur], (const ptss_ray_hit*)dHits, n, (ptss_linear_entry*)dView,
+                                                 (uint32_t*)dInfo, NULL));
+            }
             PTSS_HANDLE(ptss_resolve_linear(ctx, (const ptss_linear_entry*)dView, 0, n, &linearParams, (ptss_history_entry*)dVMeans, NULL, NULL, NULL));
             PTSS_HANDLE(ptss_synchronize(ctx));
             std::vector<ptss_history_entry> viewMeans(n);
@@ -521,6 +540,14 @@ int main(int argc, char* argv[]) {
             if (!writePfm(viewName.c_str(), viewMeans.data(), width, height)) { fprintf(stderr, "--bake-view: cannot write %s\n", viewName.c_str()); return 1; }
             printf("bake view: %d x %d, %s, %zu sphere blocks, filtered %u, empty %u, no block %u, rejected %u\n", width, height,
                    bakeView == PTSS_LIGHTMAP_NEAREST ? "nearest" : "bilinear", S, info[0], info[1], info[2], info[3]);
+            if (viewSteps > 0) {
+                std::vector<ptss_chain_result> rows(n);
+                if (hipMemcpy(rows.data(), dChain, n * sizeof(ptss_chain_result), hipMemcpyDeviceToHost) != hipSuccess) { fprintf(stderr, "--view-steps: read-back\n"); return 1; }
+                unsigned long long links = 0, behind = 0;
+                for (const ptss_chain_result& c : rows) links += c.steps, behind += c.steps > 0u;
+                printf("view steps: at most %d, %llu links followed, %llu of %zu pixels seen through a mirror or glass\n", viewSteps, links, behind, n);
+                (void)hipFree(dChain);
+            }
             for (void* d : {dBt, dBs, dVRng, dVRays, dHits, dView, dVMeans, dInfo}) (void)hipFree(d);
         }
         for (void* d : {dPoints, dTexels, dRng, dRays, dRes, dMap[0], dMap[1], dMeans}) (void)hipFree(d);

@@ -28,6 +28,7 @@ from ptss_types import UPSAMPLE_LINEAR_INFO_DTYPE, UPSAMPLE_LINEAR_WRAP_X, Upsam
 from ptss_types import SPHERE_DTYPE, SURFACE_BACK, SURFACE_COSINE, SURFACE_NORMAL, SURFACE_POINT_DTYPE, SURFACE_TRIANGLE, SurfaceParams
 from ptss_types import (LIGHTMAP_BILINEAR, LIGHTMAP_EMISSION, LIGHTMAP_MODULATE, LIGHTMAP_NEAREST, MATERIAL_DTYPE, SURFACE_BLOCK_DTYPE,
                         LightmapParams)
+from ptss_types import CHAIN_DTYPE, CHAIN_LANE_PER_RAY, CHAIN_REFILL, ChainOptions
 from ptss_types import TONE_CLAMP, TONE_FILMIC, TONE_LUMINANCE, TONE_REINHARD, TRANSFER_GAMMA22, TRANSFER_SRGB, ToneParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -189,6 +190,9 @@ def host_lib():
         L.ptss_probe_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]
         L.ptss_probe_specular_step.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]
         L.ptss_probe_specular_class.argtypes = [C.c_void_p]
+        L.ptss_probe_specular_link.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        L.ptss_probe_lookup_lightmap_chain.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(LightmapParams), C.POINTER(LinearParams), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.ptss_probe_strip_masks.argtypes = [C.POINTER(SceneDesc), C.POINTER(Camera), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_void_p]
         L.ptss_probe_film_rays.argtypes = [C.POINTER(FilmCamera), C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
@@ -415,6 +419,11 @@ def device_lib():
         L.ptss_lookup_lightmap.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LinearParams), vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
         L.ptss_lightmap_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_debug_lightmap_form.argtypes = [vp, C.c_int]
+        L.ptss_default_chain_options.argtypes = [C.POINTER(ChainOptions)]
+        L.ptss_intersect_chain.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(ChainOptions), vp, vp, vp]
+        L.ptss_chain_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.ptss_lookup_lightmap_chain.argtypes = [vp, C.POINTER(LightmapParams), C.POINTER(LinearParams), vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]
+        L.ptss_lightmap_chain_launches.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.ptss_render_features_scaled.argtypes = [vp, C.c_int, vp, vp]
         L.ptss_default_upsample_params.argtypes = [C.POINTER(UpsampleParams)]
         L.ptss_upsample.argtypes = [vp, vp, vp, vp, C.POINTER(UpsampleParams), vp, vp, vp]
@@ -651,6 +660,18 @@ def path_options(schedule=PATHS_LANE_PER_RAY, max_workgroups=0):
     o = PathOptions()
     o.structSize = C.sizeof(PathOptions)
     o.schedule = {"lane_per_ray": PATHS_LANE_PER_RAY, "refill": PATHS_REFILL}.get(schedule, schedule)
+    o.maxWorkgroups = int(max_workgroups)
+    o.reserved = 0
+    return o
+
+
+# ---- the schedule of a chain query (ptss_intersect_chain) ----
+def chain_options(schedule=CHAIN_LANE_PER_RAY, max_workgroups=0):
+    """A ptss_chain_options. schedule: CHAIN_LANE_PER_RAY, CHAIN_REFILL or "lane" / "refill"; max_workgroups: the refill grid's cap,
+    0 = the library's choice."""
+    o = ChainOptions()
+    o.structSize = C.sizeof(ChainOptions)
+    o.schedule = {"lane": CHAIN_LANE_PER_RAY, "lane_per_ray": CHAIN_LANE_PER_RAY, "refill": CHAIN_REFILL}.get(schedule, schedule)
     o.maxWorkgroups = int(max_workgroups)
     o.reserved = 0
     return o
@@ -1627,8 +1648,9 @@ def _lightmap_blocks(blocks):
     return a if len(a) else None
 
 
-def _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info):
-    """The buffers of a lookup_lightmap call as plain rows: [hits, map, triangle blocks or None, sphere blocks or None, out, info or None]."""
+def _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info, chain=None):
+    """The buffers of a lookup_lightmap call as plain rows: [hits, map, triangle blocks or None, sphere blocks or None, out, info or None],
+    and with chain rows (lookup_lightmap(chain=...)) those, one per hit, as a seventh."""
     h = _rows(hits, HIT_DTYPE, 12, np.float32, "hits")
     m = _rows(map, LINEAR_DTYPE, 4, np.uint64, "map")
     if len(m) != int(params.atlasWidth) * int(params.atlasHeight):
@@ -1639,7 +1661,13 @@ def _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info):
     inf = None if info is False else np.zeros(4, dtype=np.uint32)
     if info is not None and info is not False:
         inf[:] = info
-    return [h, m, bt, bs, np.zeros((len(h), 4), dtype=np.uint64), inf]
+    bufs = [h, m, bt, bs, np.zeros((len(h), 4), dtype=np.uint64), inf]
+    if chain is not None:
+        c = _rows(chain, CHAIN_DTYPE, 8, np.float32, "chain")
+        if len(c) != len(h):
+            raise ValueError("chain: one row per hit")
+        bufs.append(c)
+    return bufs
 
 
 def _lightmap_counts(params, blocks_tri, blocks_sph):
@@ -1667,6 +1695,22 @@ def probe_lookup_lightmap(materials, hits, map, params, blocks_tri=None, blocks_
                                                ptr(inf))
     if rc != 0:
         raise PtssError(f"ptss_probe_lookup_lightmap: {rc}")
+    return out.view(LINEAR_DTYPE).reshape(-1), inf
+
+
+def probe_lookup_lightmap_chain(materials, hits, chain, map, params, blocks_tri=None, blocks_sph=None, film=None, info=None):
+    """ptss_lookup_lightmap_chain on the host (csrc/ptlightmap.h step 6; the specification of the device's rows): probe_lookup_lightmap
+    with chain, (N,) CHAIN_DTYPE or (N, 8) float32, whose throughput tints every filtered row (clamped into [0, 1])."""
+    film = film if film is not None else linear_params()
+    params = _lightmap_counts(params, blocks_tri, blocks_sph)
+    mat = scene_materials(materials) if isinstance(materials, Scene) else materials
+    mat = np.ascontiguousarray(mat, dtype=MATERIAL_DTYPE).reshape(-1) if mat is not None else np.zeros(0, dtype=MATERIAL_DTYPE)
+    h, m, bt, bs, out, inf, c = _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info, chain)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    rc = host_lib().ptss_probe_lookup_lightmap_chain(ptr(mat), len(mat), C.byref(params), C.byref(film), ptr(bt), ptr(bs), ptr(m), ptr(h), ptr(c),
+                                                     len(h), ptr(out), ptr(inf))
+    if rc != 0:
+        raise PtssError(f"ptss_probe_lookup_lightmap_chain: {rc}")
     return out.view(LINEAR_DTYPE).reshape(-1), inf
 
 
@@ -1878,6 +1922,29 @@ def probe_specular_step(rays, hits, materials):
     if rc != 0:
         raise PtssError(f"ptss_probe_specular_step: {rc}")
     return nxt, follows != 0
+
+
+def probe_specular_link(rays, hits, materials):
+    """One link of ptss_intersect_chain on the host (csrc/ptspecular.h): probe_specular_step's arguments and its very next and follows,
+    plus factors (N, 3) float32 — the factor by which each followed link multiplies the radiance; rows that do not follow hold zeros.
+    Returns (next, follows, factors)."""
+    r = np.ascontiguousarray(rays)
+    r = (r.view(np.float32) if r.dtype == RAY_DTYPE else r.astype(np.float32, copy=False)).reshape(-1, 8)
+    r = np.ascontiguousarray(r)
+    h = np.ascontiguousarray(hits, dtype=HIT_DTYPE).reshape(-1)
+    if len(r) != len(h):
+        raise ValueError("one hit per ray")
+    ptr, count, keep = _material_table(materials)
+    nxt = r.copy()
+    follows = np.zeros(len(h), dtype=np.int32)
+    factors = np.zeros((len(h), 3), dtype=np.float32)
+    rc = host_lib().ptss_probe_specular_link(r.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), len(h), ptr, count,
+                                             nxt.ctypes.data_as(C.c_void_p), follows.ctypes.data_as(C.POINTER(C.c_int)),
+                                             factors.ctypes.data_as(C.c_void_p))
+    del keep
+    if rc != 0:
+        raise PtssError(f"ptss_probe_specular_link: {rc}")
+    return nxt, follows != 0, factors
 
 
 def make_rays(origins, directions, tmax=float("inf")):
@@ -2231,6 +2298,38 @@ class Renderer:
         return self._device_call([("rays", rays, "float32", 8, None, None), ("out", None, *(("int32", 0) if any_hit else ("float32", 12)), "rays", "empty")],
                                  lambda d, n, stream: fn(self._ctx, d[0], d[1], n["rays"], stream) if d[0] is not None else 0,
                                  arrays, read=(1,), null=lambda n: n["rays"] == 0, result=lambda a: a[1], returns="out", texts=_QUERY_TEXTS)
+
+    def intersect_chain(self, rays, max_steps, schedule="lane", max_workgroups=0, chain=True):
+        """ptss_intersect_chain: intersect() carried through mirrors and glass for at most max_steps links (0 .. 8; csrc/ptspecular.h).
+        schedule: "lane" / "refill" or a CHAIN_* value, or None for the library's default (options NULL); max_workgroups: the refill
+        grid's cap. The refill calls of one context are ordered by the caller.
+        numpy: rays (N, 8) float32 or (N,) RAY_DTYPE -> ((N,) HIT_DTYPE: the hit of the last link's ray, (N,) CHAIN_DTYPE or None with
+        chain=False: dev_chain NULL). torch: a contiguous (N, 8) float32 device tensor -> (hits (N, 12) float32, chain (N, 8) float32 or
+        None), on the current stream; chain may also be an (N, 8) float32 tensor to write."""
+        L = device_lib()
+        options = chain_options(schedule, max_workgroups) if schedule is not None else None
+        wanted = chain is not False and chain is not None
+        rows = chain if wanted and chain is not True else None
+
+        def arrays():
+            a = _query_rays(rays)
+            return [a, np.empty(len(a), dtype=HIT_DTYPE), np.empty(len(a), dtype=CHAIN_DTYPE) if wanted else None]
+
+        bufs = [("rays", rays, "float32", 8, None, None), ("hits", None, "float32", 12, "rays", "empty"),
+                ("chain", rows, "float32", 8, "rays", "empty" if wanted else "null")]
+        call = lambda d, n, stream: L.ptss_intersect_chain(self._ctx, d[0], n["rays"], int(max_steps), C.byref(options) if options is not None else None,
+                                                           d[1], d[2], stream)
+        if _is_torch(rays):   # two tensors come back: the body returns one, the other is made here
+            torch = sys.modules["torch"]
+            if wanted and rows is None:
+                rows = torch.empty((rays.shape[0] if rays.dim() == 2 else 0, 8), dtype=torch.float32, device=rays.device)
+                bufs[2] = ("chain", rows, "float32", 8, "rays", None)
+            return self._device_call(bufs, call, arrays, returns="hits", texts=None), rows
+        return self._device_call(bufs, call, arrays, read=(1, 2), null=lambda n: n["rays"] == 0, result=lambda a: (a[1], a[2]))
+
+    def chain_launches(self):
+        """ptss_chain_launches: (ptss_intersect_chain launches with one lane per ray, with the refill schedule)."""
+        return self._counters("ptss_chain_launches", 2)
 
     # --- batched path queries (ptss_seed_path_rng / ptss_trace_paths) ------------------------------------
     def seed_path_rng(self, n, seed, first_sequence=0, skip=0, device=None):
@@ -2861,18 +2960,29 @@ class Renderer:
         _check(device_lib().ptss_debug_dilate_linear_form(self._ctx, int(form)))
 
     # --- light maps read back (ptss_lookup_lightmap) ------------------
-    def lookup_lightmap(self, hits, map, params, blocks_tri=None, blocks_sph=None, film=None, info=None, out=None):
+    def lookup_lightmap(self, hits, map, params, blocks_tri=None, blocks_sph=None, film=None, info=None, out=None, chain=None):
         """ptss_lookup_lightmap: hits -> linear film rows through a baked map. params: a lightmap_params (table counts left at 0 are
         the tables' lengths); film: the map's linear_params.
         numpy: hits (N,) HIT_DTYPE, map (W H,) LINEAR_DTYPE, blocks (.,) SURFACE_BLOCK_DTYPE or None -> ((N,) LINEAR_DTYPE, the four
         counts — filtered, empty, no block, rejected — as (4,) uint32, or None with info=False: dev_info NULL). info: the counts' content
         beforehand.
         torch: hits (N, 12) float32, map (W H, 4) int64, blocks (., 4) int32 or None, out an (N, 4) int64 device tensor to write (a new
-        one otherwise), info a (4,) int32 device tensor ADDED TO or None -> out, on the current stream."""
+        one otherwise), info a (4,) int32 device tensor ADDED TO or None -> out, on the current stream.
+        chain (ptss_lookup_lightmap_chain): intersect_chain's rows for the hits — (N,) CHAIN_DTYPE or (N, 8) float32,
+        torch (N, 8) float32 — whose throughput, clamped into [0, 1], tints every filtered row."""
         L = device_lib()
         film = film if film is not None else linear_params()
         params = _lightmap_counts(params, blocks_tri, blocks_sph)
         P = int(params.atlasWidth) * int(params.atlasHeight)
+        if chain is not None:
+            return self._device_call(
+                [("hits", hits, "float32", 12, None, None), ("map", map, "int64", 4, P, None), ("blocks_tri", blocks_tri, "int32", 4, None, "null"),
+                 ("blocks_sph", blocks_sph, "int32", 4, None, "null"), ("out", out, "int64", 4, "hits", "empty"),
+                 ("info", info if info is not False else None, "int32", 0, 4, "null"), ("chain", chain, "float32", 8, "hits", None)],
+                lambda d, n, stream: L.ptss_lookup_lightmap_chain(self._ctx, C.byref(params), C.byref(film), d[2], d[3], d[1], d[0], d[6], n["hits"], d[4],
+                                                                  d[5], stream),
+                lambda: _lightmap_buffers(hits, map, params, blocks_tri, blocks_sph, info, chain), read=(4, 5),
+                result=lambda a: (_records(a[4], LINEAR_DTYPE), a[5]), returns="out")
         return self._device_call(
             [("hits", hits, "float32", 12, None, None), ("map", map, "int64", 4, P, None), ("blocks_tri", blocks_tri, "int32", 4, None, "null"),
              ("blocks_sph", blocks_sph, "int32", 4, None, "null"), ("out", out, "int64", 4, "hits", "empty"),
@@ -2884,6 +2994,10 @@ class Renderer:
     def lightmap_launches(self):
         """ptss_lightmap_launches: the lookup_lightmap calls that launched since the context was created."""
         return self._counters("ptss_lightmap_launches", 1)
+
+    def lightmap_chain_launches(self):
+        """ptss_lightmap_chain_launches: the lookup_lightmap(chain=...) calls that launched since the context was created."""
+        return self._counters("ptss_lightmap_chain_launches", 1)
 
     def debug_lightmap_form(self, form):
         """ptss_debug_lightmap_form (tests and measurements): 0 the shipped form, 1 one lane per hit, 2 four lanes per hit. The bytes are

@@ -283,6 +283,18 @@ class LightmapParams(C.Structure):   # ptss_lightmap_params
                 ("reserved", C.c_uint)]
 
 
+# ray queries that follow mirrors and glass (ptss_intersect_chain, ptss_lookup_lightmap_chain)
+CHAIN_DTYPE = np.dtype([("throughput", np.float32, 3), ("steps", np.uint32), ("direction", np.float32, 3), ("pathLength", np.float32)])   # ptss_chain_result
+CHAIN_LANE_PER_RAY, CHAIN_REFILL = 0, 1   # PTSS_CHAIN_*
+
+
+class ChainOptions(C.Structure):   # ptss_chain_options: how ptss_intersect_chain schedules a batch
+    _fields_ = [("structSize", C.c_uint), ("schedule", C.c_int), ("maxWorkgroups", C.c_int), ("reserved", C.c_int)]
+
+
+assert CHAIN_DTYPE.itemsize == 32 and CHAIN_DTYPE.fields["steps"][1] == 12 and CHAIN_DTYPE.fields["pathLength"][1] == 28 and C.sizeof(ChainOptions) == 16
+
+
 # The bits of ptss_launched_kernels: PTSS_KERNEL_<name> and PTSS_KERNEL_WIDTH_<name> of include/ptss_types.h as name: (first bit,
 # bits owned). ptss.py names the instantiation behind every bit (KERNEL_OF_BIT).
 KERNEL_BITS = {

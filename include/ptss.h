@@ -833,6 +833,47 @@ int ptss_lookup_lightmap(ptss_context* ctx, const ptss_lightmap_params* params, 
 int ptss_lightmap_launches(const ptss_context* ctx, unsigned long long* out);
 int ptss_debug_lightmap_form(ptss_context* ctx, int form);
 
+/* Ray queries that follow mirrors and glass: the fourth member of the query family. ptss_intersect for n caller rays,
+ * each carried through the delta lobes of what it meets — perfect reflection, refraction; which one is decided from the material alone,
+ * csrc/ptspecular.h, the chain of ptss_render_features_specular — for at most maxSteps links (0 .. 8). The first link's query runs
+ * with the ray's own tmax, later links with +inf. The chain ends at a material the chain does not follow (diffuse, glossy,
+ * Cook-Torrance, total internal reflection without a specular lobe), a miss, a continued direction that is not finite, or maxSteps.
+ * dev_hits[i]: the ptss_ray_hit ptss_intersect writes for the LAST link's ray, the miss row included; maxSteps = 0 writes
+ * ptss_intersect's bytes. dev_chain[i] (may be NULL): what the chain did on the way (ptss_types.h) — the throughput, the product of
+ * the followed links' factors (ptsp::linkFactor: the followed lobe's probability in the reference's scatter times its weight), the
+ * steps, the last ray's direction and the path length. The host composition — ptss_intersect, ptss_probe_specular_link
+ * (ptss_host.h), ptss_intersect, .. — gives the same bytes.
+ * options (NULL: the defaults, ptss_default_chain_options: structSize, PTSS_CHAIN_LANE_PER_RAY, 0, 0) picks the schedule.
+ * PTSS_CHAIN_REFILL hands the next unclaimed ray of the batch to a lane whose chain has ended (ptss_trace_paths_opt's schedule, with a
+ * queue head of its own: chain calls and path queries do not disturb each other); maxWorkgroups caps its grid (0: the resident
+ * workgroups). Every output byte is the same for both schedules and every grid. ORDERING: ptss_trace_paths_opt's rule — the
+ * PTSS_CHAIN_REFILL calls of one context must be ordered among themselves by the caller (one stream, or an event between streams).
+ * Asynchronous on hipStream (NULL: the context's); reads the scene image only — the live one, after ptss_update_triangles and
+ * ptss_resort_triangles —; leaves no frame state; owns no bit of ptss_launched_kernels; ptss_chain_launches counts since ptss_create:
+ * out2[0] launches with one lane per ray, out2[1] with the refill schedule. n = 0 returns PTSS_OK. Refused before the device is touched,
+ * nothing counted: PTSS_EINVAL a null context, null rays or hits with n > 0, a wrong structSize, an unknown schedule, a non-zero
+ * reserved, a negative maxWorkgroups, a pointer that is not 16-byte aligned, outputs that overlap the rays or each other; PTSS_ERANGE
+ * maxSteps outside 0 .. 8, n >= 2^31. */
+int ptss_default_chain_options(ptss_chain_options* options);
+int ptss_intersect_chain(ptss_context* ctx, const ptss_ray_query* dev_rays, size_t n, int maxSteps /* 0..8 */,
+                         const ptss_chain_options* options /* NULL: defaults */, ptss_ray_hit* dev_hits,
+                         ptss_chain_result* dev_chain /* may be NULL */, void* hipStream);
+int ptss_chain_launches(const ptss_context* ctx, unsigned long long* out2); /* [0] lane per ray, [1] refill */
+
+/* ptss_lookup_lightmap for hits seen through a chain: the same arguments, checks, verdicts and counts, plus dev_chain,
+ * n rows of ptss_chain_result (16-byte aligned, required, device memory and never trusted). A FILTERED row is tinted after SHADE:
+ * per channel m' = (m' t + 32768) >> 16 with t = clamp((int)(throughput * 65536 + 0.5f), 0, 65536) — a throughput that is not a number
+ * or negative gives 0, a throughput ABOVE 1 IS CLAMPED TO 1. A throughput of exactly (1, 1, 1) gives ptss_lookup_lightmap's bytes.
+ * Also refused (PTSS_EINVAL): dev_out overlapping dev_chain or dev_hits. Counted by ptss_lightmap_chain_launches, not by
+ * ptss_lightmap_launches. The host build is ptss_probe_lookup_lightmap_chain. */
+int ptss_lookup_lightmap_chain(ptss_context* ctx, const ptss_lightmap_params* params, const ptss_linear_params* film,
+                               const ptss_surface_block* dev_blocksTri /* may be NULL with 0 */,
+                               const ptss_surface_block* dev_blocksSph /* may be NULL with 0 */, const ptss_linear_entry* dev_map,
+                               const ptss_ray_hit* dev_hits, const ptss_chain_result* dev_chain, size_t n,
+                               ptss_linear_entry* dev_out /* n rows, all written */, uint32_t* dev_info /* may be NULL: 4 counts, added to */,
+                               void* hipStream);
+int ptss_lightmap_chain_launches(const ptss_context* ctx, unsigned long long* out);
+
 /* First-hit features of the context's CURRENT camera for a frame of factor * width x factor * height, factor 1 .. 4 (DESIGN.md
  * §3.22): what ptss_upsample is guided by. The entry of hi-res pixel (X, Y) holds what ptss_intersect returns for
  * ptss_camera_ray(camera, factor * width, factor * height, X, Y, 0.5, 0.5) with tmax = +inf, albedo and the miss row as in

@@ -171,6 +171,14 @@ int ptss_probe_motion(const ptss_ray_query* rays, const ptss_ray_hit* hits, size
  * hit whose materialIdx is outside [0, numMaterials) (nothing has then been written). */
 int ptss_probe_specular_step(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_material* materials, size_t numMaterials,
                              ptss_ray_query* next, int* follows);
+/* One link of ptss_intersect_chain on the host (csrc/ptspecular.h ptsp::step and ptsp::linkFactor):
+ * ptss_probe_specular_step — the same arguments, refusals, and the very bytes of next and follows — plus factors[i], the factor by which
+ * the followed link multiplies the radiance (the followed lobe's probability in the reference's scatter times its weight there):
+ * specularColor * specAvg for a mirror with the pure-reflection flag, specularColor * (specAvg * F) for one without and for glass in
+ * total internal reflection, refrAvg * (1 - F) in every channel for a refracted link, F the Fresnel reflectance of the incidence.
+ * follows[i] = 0 leaves factors[i] untouched. A null factors with n > 0 is refused too. */
+int ptss_probe_specular_link(const ptss_ray_query* rays, const ptss_ray_hit* hits, size_t n, const ptss_material* materials, size_t numMaterials,
+                             ptss_ray_query* next, int* follows, ptss_vec3* factors);
 /* The class csrc/ptspecular.h gives a material: 0 terminal, 1 transmit, 2 mirror; -1 for a null pointer. */
 int ptss_probe_specular_class(const ptss_material* material);
 /* XORWOW state after curand_init(seed, subsequence, 0): out6 = v0..v4, d. */
@@ -375,6 +383,13 @@ int ptss_surface_atlas_blocks(const ptss_triangle* triangles, size_t firstTriang
 int ptss_probe_lookup_lightmap(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
                                const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
                                const ptss_linear_entry* map, const ptss_ray_hit* hits, size_t n, ptss_linear_entry* out, uint32_t* info);
+/* ptss_lookup_lightmap_chain over the caller's own records (csrc/ptlightmap.h step 6): ptss_probe_lookup_lightmap with
+ * chain[n], whose throughput tints every FILTERED row — clamped into [0, 1], not a number: 0. The specification of the device's rows.
+ * Also PTSS_HOST_EINVAL: a null chain with n > 0, out overlapping chain or hits. */
+int ptss_probe_lookup_lightmap_chain(const ptss_material* materials, size_t numMaterials, const ptss_lightmap_params* params,
+                                     const ptss_linear_params* film, const ptss_surface_block* blocksTri, const ptss_surface_block* blocksSph,
+                                     const ptss_linear_entry* map, const ptss_ray_hit* hits, const ptss_chain_result* chain, size_t n,
+                                     ptss_linear_entry* out, uint32_t* info);
 
 #ifdef __cplusplus
 }

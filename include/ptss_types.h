@@ -498,6 +498,28 @@ typedef struct ptss_lightmap_params {
     unsigned int reserved;   /* 0 */
 } ptss_lightmap_params;
 
+/* What ptss_intersect_chain returns for one ray beside the hit (csrc/ptspecular.h): two 16-byte rows. throughput:
+ * (1, 1, 1) times the factor of every followed link, in chain order, component by component in float32 (ptsp::linkFactor: the
+ * followed lobe's probability times its weight in the reference's scatter); steps: the links followed, 0 .. maxSteps; direction: of
+ * the last link's ray (the caller's own for steps == 0); pathLength: the float32 sum of the chain's hit distances in chain order,
+ * +inf when the chain ends in a miss. */
+typedef struct ptss_chain_result {
+    ptss_vec3 throughput;
+    unsigned int steps;
+    ptss_vec3 direction;
+    float pathLength;
+} ptss_chain_result;
+
+/* How ptss_intersect_chain schedules a batch (ptss_default_chain_options fills it in). */
+#define PTSS_CHAIN_LANE_PER_RAY 0 /* one lane per ray for the chain's whole life */
+#define PTSS_CHAIN_REFILL 1       /* a lane whose chain has ended takes the next unclaimed ray of the batch */
+typedef struct ptss_chain_options {
+    unsigned int structSize; /* sizeof(ptss_chain_options) as the caller compiled it */
+    int schedule;            /* PTSS_CHAIN_* */
+    int maxWorkgroups;       /* REFILL: cap on the grid, 0 = the library's choice (the resident workgroups); >= 0. LANE_PER_RAY: not read */
+    int reserved;            /* 0 */
+} ptss_chain_options;
+
 /* The bits of ptss_launched_kernels (ptss.h): every kernel owns the range [PTSS_KERNEL_x, PTSS_KERNEL_x + PTSS_KERNEL_WIDTH_x).
  * Inside a range: the bounce kernels variant*8 + last*4 + inLds*2 + first (variant 0 many-sphere chunks, 1 bounded sphere test with
  * paired shadow segments, 2 bounded sphere test, 3 the reference's sphere test; the mesh image's eight have a range of their own
@@ -616,6 +638,12 @@ static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params,
 static_assert(sizeof(ptss_surface_block) == 16 && offsetof(ptss_surface_block, y) == 4 && offsetof(ptss_surface_block, width) == 8 &&
                   offsetof(ptss_surface_block, height) == 12,
               "ptss_surface_block is one 16-byte row");
+static_assert(sizeof(ptss_chain_result) == 32 && offsetof(ptss_chain_result, steps) == 12 && offsetof(ptss_chain_result, direction) == 16 &&
+                  offsetof(ptss_chain_result, pathLength) == 28,
+              "ptss_chain_result is two 16-byte rows");
+static_assert(sizeof(ptss_chain_options) == 16 && offsetof(ptss_chain_options, schedule) == 4 && offsetof(ptss_chain_options, maxWorkgroups) == 8 &&
+                  offsetof(ptss_chain_options, reserved) == 12,
+              "ptss_chain_options is four 32-bit words");
 static_assert(sizeof(ptss_lightmap_params) == 40 && offsetof(ptss_lightmap_params, atlasWidth) == 4 && offsetof(ptss_lightmap_params, filter) == 12 &&
                   offsetof(ptss_lightmap_params, flags) == 16 && offsetof(ptss_lightmap_params, firstTriangle) == 20 &&
                   offsetof(ptss_lightmap_params, firstSphere) == 28 && offsetof(ptss_lightmap_params, reserved) == 36,
@@ -706,6 +734,12 @@ _Static_assert(sizeof(ptss_surface_params) == 16 && offsetof(ptss_surface_params
 _Static_assert(sizeof(ptss_surface_block) == 16 && offsetof(ptss_surface_block, y) == 4 && offsetof(ptss_surface_block, width) == 8 &&
                    offsetof(ptss_surface_block, height) == 12,
                "ptss_surface_block is one 16-byte row");
+_Static_assert(sizeof(ptss_chain_result) == 32 && offsetof(ptss_chain_result, steps) == 12 && offsetof(ptss_chain_result, direction) == 16 &&
+                   offsetof(ptss_chain_result, pathLength) == 28,
+               "ptss_chain_result is two 16-byte rows");
+_Static_assert(sizeof(ptss_chain_options) == 16 && offsetof(ptss_chain_options, schedule) == 4 && offsetof(ptss_chain_options, maxWorkgroups) == 8 &&
+                   offsetof(ptss_chain_options, reserved) == 12,
+               "ptss_chain_options is four 32-bit words");
 _Static_assert(sizeof(ptss_lightmap_params) == 40 && offsetof(ptss_lightmap_params, atlasWidth) == 4 && offsetof(ptss_lightmap_params, filter) == 12 &&
                    offsetof(ptss_lightmap_params, flags) == 16 && offsetof(ptss_lightmap_params, firstTriangle) == 20 &&
                    offsetof(ptss_lightmap_params, firstSphere) == 28 && offsetof(ptss_lightmap_params, reserved) == 36,
