@@ -7,7 +7,7 @@
 // of a pixel takes up to four uniforms of (0, 1] from the ray's own stream, in this order: jx, jy (where in the pixel), u1, u2 (where on
 // the lens). draws(kind, jitter) says how many a model takes; with jitter = 0 it takes none and jx = jy = 0.5, lens point = lens centre.
 // The constants s = -2 tan(fov / 2), aspect = H / W, invW = 1 / W, invH = 1 / H are evaluated once on the host (filmOf), with the
-// expressions of ptss_api.hip eyeParams and HostOps.cpp cameraRay, and travel by value.
+// expressions of ptss_context.h eyeParams and HostOps.cpp cameraRay, and travel by value.
 //
 //   PINHOLE     computeEyeRay (CudaTracer.cu:321-343) with bounce 0's operations, i.e. HostOps.cpp cameraRay:
 //                 X = x + jx;  Y = y + jy

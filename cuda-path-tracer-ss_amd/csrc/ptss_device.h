@@ -1,5 +1,5 @@
 // ptss_device.h — device-side data layout shared by the kernels (ptss_kernels.hip) and the
-// context code (ptss_api.hip). See DESIGN.md "Data layout in HBM". The scene image's own description (SceneLayout, the sizes that
+// context code (ptss_api*.hip, over ptss_context.h). See DESIGN.md "Data layout in HBM". The scene image's own description (SceneLayout, the sizes that
 // shape it, bounceLdsBytes) is host-clean and lives in ptscene.h.
 #pragma once
 #include <hip/hip_runtime.h>

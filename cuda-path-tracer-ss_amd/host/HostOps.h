@@ -10,7 +10,7 @@ bool writeTga(const char* filename, const ptss_uchar4* rgba, int width, int heig
 // the r, g, b of width * height entries (row 0 = bottom) as a little-endian PFM (ptss_main --linear)
 bool writePfm(const char* filename, const ptss_history_entry* rgbw, int width, int height);
 // computeEyeRay (CudaTracer.cu:321-343) through (x + jx, y + jy), with the operations of bounce 0 (ptss_kernels.hip bounceTile:
-// EyeParams as ptss_api.hip eyeParams builds them); tmax = +inf
+// EyeParams as csrc/ptss_context.h eyeParams builds them); tmax = +inf
 ptss_ray_query cameraRay(const ptss_camera& camera, int width, int height, int x, int y, float jx, float jy);
 // glm::quat(vec3 eulerAngles) — pitch (x), yaw (y), roll (z), radians.
 quat quatFromEuler(vec3 euler);

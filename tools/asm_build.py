@@ -2,7 +2,8 @@
 ptss_kernels.hip (the kernels, with the layer headers ptwave.h .. ptshade.h they are built from) passed through a text edit between the compiler and the assembler (measurement builds: what would a different
 instruction choice be worth?).  edit=cnd64: VOP2 `v_cndmask_b32_e32 d, a, b, vcc` -> VOP3 `v_cndmask_b32_e64 d, a, b, vcc`.
 Pipeline = hipcc's own (hipcc -###): device cc1 -> .s -> [edit] -> assembler -> lld -> clang-offload-bundler -> host cc1
-with -fcuda-include-gpubinary -> link with the ordinary object of ptss_api.hip."""
+with -fcuda-include-gpubinary -> link with the ordinary objects of every other csrc/*.hip (the C-ABI files ptss_api*.hip and
+the other kernel files)."""
 import importlib.util
 import os
 import re
@@ -51,7 +52,7 @@ def main():
     os.makedirs(tmp, exist_ok=True)
     inc = ["-I", b.INC, "-I", b.CSRC]
     kern = os.path.join(b.CSRC, "ptss_kernels.hip")
-    api = os.path.join(b.CSRC, "ptss_api.hip")
+    others = [f for f in sorted(os.listdir(b.CSRC)) if f.endswith(".hip") and f != "ptss_kernels.hip"]
     s = os.path.join(tmp, "k.s")
     run(["hipcc"] + b.HIP_FLAGS + defs + inc + ["--cuda-device-only", "-S", kern, "-o", s])
     text = open(s).read()
@@ -64,9 +65,12 @@ def main():
          "-input=/dev/null", "-input=" + os.path.join(tmp, "k.out"), "-output=" + os.path.join(tmp, "k.hipfb")])
     run(["hipcc"] + b.HIP_FLAGS + defs + inc + ["--cuda-host-only", "-c", kern, "-Xclang", "-fcuda-include-gpubinary", "-Xclang", os.path.join(tmp, "k.hipfb"),
                                                "-o", os.path.join(tmp, "k_host.o")])
-    run(["hipcc"] + b.HIP_FLAGS + defs + inc + ["-c", api, "-o", os.path.join(tmp, "api.o")])
+    objs = [os.path.join(tmp, "k_host.o")]
+    for f in others:
+        objs.append(os.path.join(tmp, f[:-4] + ".o"))
+        run(["hipcc"] + b.HIP_FLAGS + defs + inc + ["-c", os.path.join(b.CSRC, f), "-o", objs[-1]])
     out = os.path.join(b.LIBDIR, f"libptss_{tag}.so")
-    run(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", os.path.join(tmp, "k_host.o"), os.path.join(tmp, "api.o"), "-o", out])
+    run(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950"] + objs + ["-o", out])
     print(out)
 
 
